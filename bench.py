@@ -10,8 +10,11 @@ logits all-gather, and rank 0 checks the sharded logits against the unsharded ev
 (`config.sharded_vs_unsharded`).  `--scaling weak` gives every rank its own cfg-sized shard instead; in a
 strong N > 1 run the weak line is measured too and printed as the secondary field `weak_scaling`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-algorithmic bytes / HIP-event launch time) and `cpu_baseline` (the CPU restatement timed on this host).
+Prints ONE JSON line on rank 0: `metric`, `value` (cells/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed
+step), the workload.  A plain run only sets up, warms up, times `--steps` steps and prints the line.  `--full` adds everything
+else: `roofline` (dominant kernel, algorithmic bytes / HIP-event launch time), `cpu_baseline` (the CPU restatement timed on this
+host), the sustained / weak-scaling / training-step / one-shot secondaries, the generator statistics and the N > 1
+sharded == unsharded self-check.  `--dump-outputs DIR` writes what the last timed step returned (`DIR/logits.npy`, float32).
 """
 from __future__ import annotations
 
@@ -260,7 +263,9 @@ def self_launch(args):
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve()), *sys.argv[1:]]
-    os.execv(sys.executable, cmd)
+    # a child process, not exec: this process has already asked the runtime for its devices
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def build_workload(cfg, mode, rank, world, dev, S, shard_range):
@@ -329,6 +334,25 @@ def timed_steps(engine, feats_g, feats_c, steps, warmup, world, dev, profile=Tru
     return dt, dt_local, prof or [], out
 
 
+DUMP_BUDGET_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes every array as ``out_dir/<name>.npy`` in float32, so that two builds can be compared output for output.  An array
+    whose rows would pass the budget is written as a fixed, seeded sample of its rows (row indices in ``<name>_rows.npy``)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > DUMP_BUDGET_BYTES:
+            keep = DUMP_BUDGET_BYTES // 2 // max(1, a[0].nbytes)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            np.save(out_dir / f"{name}_rows.npy", rows.astype(np.float64))
+            a = a[rows]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -348,7 +372,14 @@ def main():
                          "default_rng), dense_head = rounds 1-5's generator (rank^-0.9 taken literally, denser head) for A/B")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the weak-scaling / sustained secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (per-launch HIP events in the timed steps), sharded == unsharded self-check, "
+                         "sustained / weak-scaling / training-step / one-shot secondaries, CPU baselines, generator statistics")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (all cells' logits) as DIR/logits.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     os.environ["WGNN_SYNTH_POPULARITY"] = args.popularity       # every synth_expression of this run (and of its child ranks)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -402,13 +433,14 @@ def main():
     torch.cuda.synchronize()
     t_generate = time.time() - t_setup
     C = feats_c.shape[0]                             # cells held by THIS rank
-    generator_desc = describe_workload(col, C, G, args.popularity, S)
+    generator_desc = describe_workload(col, C, G, args.popularity, S) if args.full else None
     torch.manual_seed(1234)
     model = sda.GNN(cfg.dense_dim, cfg.hidden, cfg.n_classes, cfg.n_layers, G, activation=F.relu)
     with torch.no_grad():
         model.alpha.uniform_(0.5, 1.5)               # reference init is ones; exercise the alpha path
     model = model.to(dev).eval()
     engine = ShardedWgnn.build(model, rp, col, val, G)          # world == 1 -> plain single-GPU graph
+    nnz_local = engine.nnz
     del rp, col, val
     torch.cuda.synchronize()
     t_setup = time.time() - t_setup
@@ -477,10 +509,13 @@ def main():
         engine.overlap_cu_budget = budgets[keep]
         comm_cus_calibration = {"ms_per_step": {k: round(v, 4) for k, v in cal.items()}, "kept": keep,
                                 "cus_planned_for_the_overlapped_pass": budgets[keep], "WGNN_COMM_CUS": sda.dist.COMM_CUS}
-    dt, dt_local, prof, out = timed_steps(engine, feats_g, feats_c, args.steps, args.warmup, world, dev, step=step_fn)
+    dt, dt_local, prof, out = timed_steps(engine, feats_g, feats_c, args.steps, args.warmup, world, dev, profile=args.full,
+                                          step=step_fn)
     assert torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
     eager_ms = None
-    if graphed:
+    if graphed and args.full:
         dt_e, _, prof, _ = timed_steps(engine, feats_g, feats_c, args.steps, 1, world, dev)
         eager_ms = round(dt_e / args.steps * 1e3, 4)
     ms_per_step = dt / args.steps * 1e3
@@ -489,7 +524,7 @@ def main():
     # ---- N > 1, strong: the sharded job's logits against the SAME graph evaluated unsharded on rank 0's GPU (outside the
     # timed region).  Skipped for jobs too large to repeat on one GPU within the run's time budget.
     self_check = None
-    if world > 1 and mode == "strong" and whole is not None and total_cells <= 200_000:
+    if args.full and world > 1 and mode == "strong" and whole is not None and total_cells <= 200_000:
         w_rp, w_col, w_val, w_fc = whole
         from scdeepsort_amd.graph import CellGeneGraph
         g1 = CellGeneGraph.from_device_csr(w_rp, w_col, w_val, G)
@@ -501,77 +536,79 @@ def main():
         del g1, ref
     whole = None
 
-    # ---- roofline of the dominant kernel (HIP events on the launch stream, averaged over the timed steps)
-    per = {}
-    for tag, e0, e1 in prof:
-        per.setdefault(tag, []).append(e0.elapsed_time(e1))
-    passes = []
-    for tag, ts in per.items():
-        d = dict(zip(tag[::2], tag[1::2]))
-        ms = sum(ts) / len(ts)
-        b = pass_bytes(d["nnz"], d["rows"], d["cols"], d["D"], G)
-        passes.append({"kernel": d["kernel"], "rows": d["rows"], "src_rows": d["cols"], "nnz": d["nnz"], "D": d["D"],
-                       "launches_per_step": len(ts) // args.steps, "avg_ms": round(ms, 4),
-                       "alg_bytes": b, "achieved_GBs": round(b / ms / 1e6, 1)})
-    passes.sort(key=lambda p: -p["avg_ms"] * p["launches_per_step"])
-    dom = passes[0]
-    # HBM bytes per launch of the dominant kernel from the PMC counters.  PMC collection needs rocprofv3 around the whole
-    # process (separate --pmc passes, scratch/profile_round.sh), so it cannot be taken inside this run: the number is
-    # read from the tracked capture of the SAME kernel on the SAME workload (profiles/hbm_traffic.json names the kernel
-    # and the round it was captured in) and is null when that capture does not match the kernel that ran here.
-    traffic, traffic_src = None, None
-    tf = ROOT / "profiles" / "hbm_traffic.json"
-    if tf.exists():
-        try:
-            rec = json.loads(tf.read_text())
-            ent = rec.get(f"{args.config}:{dom['rows']}x{dom['src_rows']}")
-            fresh = rec.get("_kernel_sources_sha") == kernel_sources_sha() and rec.get("_popularity") == args.popularity
-            if (isinstance(ent, dict) and ent.get("kernel") == dom["kernel"] and int(ent.get("D", 256)) == dom["D"]
-                    and ent.get("nnz", dom["nnz"]) == dom["nnz"]):
-                if fresh:
-                    traffic = ent["hbm_bytes_per_launch"]
-                    traffic_src = ("TRACKED capture, not a counter of this run (PMC needs rocprofv3 around the whole process): "
-                                   f"profiles/hbm_traffic.json ({rec.get('_captured', '?')}; commit {rec.get('_commit', '?')}, "
-                                   f"kernel sources {rec.get('_kernel_sources_sha', '?')[:12]} == this tree's)")
-                else:
-                    traffic_src = ("null: profiles/hbm_traffic.json was captured from other kernel sources or another workload "
-                                   f"(capture {str(rec.get('_kernel_sources_sha'))[:12]} / {rec.get('_popularity')}, this tree "
-                                   f"{kernel_sources_sha()[:12]} / {args.popularity}) - re-run scratch/profile_round.sh")
-        except Exception:
-            traffic = None
-    # measured device copy bandwidth (read + write of a 1 GiB fp32 buffer), outside the timed region: the achievable HBM rate
-    src_buf = torch.empty(256 * 1024 * 1024, dtype=torch.float32, device=dev); dst_buf = torch.empty_like(src_buf)
-    dst_buf.copy_(src_buf); torch.cuda.synchronize()
-    ce0, ce1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ce0.record()
-    for _ in range(5):
-        dst_buf.copy_(src_buf)
-    ce1.record(); torch.cuda.synchronize()
-    copy_gbs = 5 * 2 * src_buf.numel() * 4 / (ce0.elapsed_time(ce1) * 1e-3) / 1e9
-    del src_buf, dst_buf
-    fwd_bytes = engine.forward_alg_bytes(cfg.dense_dim, feats_g.element_size())
-    agg_ms = sum(p["avg_ms"] * p["launches_per_step"] for p in passes)
-    roofline = {"bound": "hbm", "kernel": f"{dom['kernel']} (rows={dom['rows']}, src={dom['src_rows']}, D={dom['D']})",
-                "achieved": dom["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(dom["achieved_GBs"] / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                "traffic_note": "FETCH_SIZE counts Infinity-Cache hits (MI355X_MICROARCH.md): the excess over the algorithmic "
-                                "bytes is the per-XCD re-fetch of the source table, part of which never reaches HBM",
-                "measured_copy_GBs": round(copy_gbs, 1), "frac_of_measured_copy": round(dom["achieved_GBs"] / copy_gbs, 4),
-                "alg_bytes_per_launch": dom["alg_bytes"], "avg_launch_ms": dom["avg_ms"], "passes": passes,
-                "agg_kernels_ms_per_step": round(agg_ms, 4), "outside_agg_kernels_ms_per_step": round(dt_local / args.steps * 1e3 - agg_ms, 4),
-                "forward_alg_bytes": fwd_bytes, "forward_achieved_GBs": round(fwd_bytes / (dt_local / args.steps * 1e3) / 1e6, 1),
-                # the resource that actually bounds the tile kernel: per launch every non-zero reads one D*4-byte source row
-                # from LDS and every tile streams its source range into LDS once
-                "on_chip": {"lds_read_bytes": dom["nnz"] * dom["D"] * 4,
-                            "lds_achieved_TBs": round(dom["nnz"] * dom["D"] * 4 / dom["avg_ms"] / 1e9, 1),
-                            "lds_peak_TBs": 157.0, "lds_frac": round(dom["nnz"] * dom["D"] * 4 / dom["avg_ms"] / 1e9 / 157.0, 3),
-                            "fp32_fma_TFLOPs": round(2 * dom["nnz"] * dom["D"] / dom["avg_ms"] / 1e9, 1), "fp32_vector_peak_TFLOPs": 157.3},
-                "note": "AI vs algorithmic bytes is 50-110 flop/B (> fp32 ridge ~20): the gather of nnz*D*4 B "
-                        "from L2/MALL and fp32 FMA issue bound this kernel before HBM does (DESIGN.md section 4)"}
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel (HIP events on the launch stream, averaged over the timed steps)
+        per = {}
+        for tag, e0, e1 in prof:
+            per.setdefault(tag, []).append(e0.elapsed_time(e1))
+        passes = []
+        for tag, ts in per.items():
+            d = dict(zip(tag[::2], tag[1::2]))
+            ms = sum(ts) / len(ts)
+            b = pass_bytes(d["nnz"], d["rows"], d["cols"], d["D"], G)
+            passes.append({"kernel": d["kernel"], "rows": d["rows"], "src_rows": d["cols"], "nnz": d["nnz"], "D": d["D"],
+                           "launches_per_step": len(ts) // args.steps, "avg_ms": round(ms, 4),
+                           "alg_bytes": b, "achieved_GBs": round(b / ms / 1e6, 1)})
+        passes.sort(key=lambda p: -p["avg_ms"] * p["launches_per_step"])
+        dom = passes[0]
+        # HBM bytes per launch of the dominant kernel from the PMC counters.  PMC collection needs rocprofv3 around the whole
+        # process (separate --pmc passes, scratch/profile_round.sh), so it cannot be taken inside this run: the number is
+        # read from the tracked capture of the SAME kernel on the SAME workload (profiles/hbm_traffic.json names the kernel
+        # and the round it was captured in) and is null when that capture does not match the kernel that ran here.
+        traffic, traffic_src = None, None
+        tf = ROOT / "profiles" / "hbm_traffic.json"
+        if tf.exists():
+            try:
+                rec = json.loads(tf.read_text())
+                ent = rec.get(f"{args.config}:{dom['rows']}x{dom['src_rows']}")
+                fresh = rec.get("_kernel_sources_sha") == kernel_sources_sha() and rec.get("_popularity") == args.popularity
+                if (isinstance(ent, dict) and ent.get("kernel") == dom["kernel"] and int(ent.get("D", 256)) == dom["D"]
+                        and ent.get("nnz", dom["nnz"]) == dom["nnz"]):
+                    if fresh:
+                        traffic = ent["hbm_bytes_per_launch"]
+                        traffic_src = ("TRACKED capture, not a counter of this run (PMC needs rocprofv3 around the whole process): "
+                                       f"profiles/hbm_traffic.json ({rec.get('_captured', '?')}; commit {rec.get('_commit', '?')}, "
+                                       f"kernel sources {rec.get('_kernel_sources_sha', '?')[:12]} == this tree's)")
+                    else:
+                        traffic_src = ("null: profiles/hbm_traffic.json was captured from other kernel sources or another workload "
+                                       f"(capture {str(rec.get('_kernel_sources_sha'))[:12]} / {rec.get('_popularity')}, this tree "
+                                       f"{kernel_sources_sha()[:12]} / {args.popularity}) - re-run scratch/profile_round.sh")
+            except Exception:
+                traffic = None
+        # measured device copy bandwidth (read + write of a 1 GiB fp32 buffer), outside the timed region: the achievable HBM rate
+        src_buf = torch.empty(256 * 1024 * 1024, dtype=torch.float32, device=dev); dst_buf = torch.empty_like(src_buf)
+        dst_buf.copy_(src_buf); torch.cuda.synchronize()
+        ce0, ce1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ce0.record()
+        for _ in range(5):
+            dst_buf.copy_(src_buf)
+        ce1.record(); torch.cuda.synchronize()
+        copy_gbs = 5 * 2 * src_buf.numel() * 4 / (ce0.elapsed_time(ce1) * 1e-3) / 1e9
+        del src_buf, dst_buf
+        fwd_bytes = engine.forward_alg_bytes(cfg.dense_dim, feats_g.element_size())
+        agg_ms = sum(p["avg_ms"] * p["launches_per_step"] for p in passes)
+        roofline = {"bound": "hbm", "kernel": f"{dom['kernel']} (rows={dom['rows']}, src={dom['src_rows']}, D={dom['D']})",
+                    "achieved": dom["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(dom["achieved_GBs"] / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                    "traffic_note": "FETCH_SIZE counts Infinity-Cache hits (MI355X_MICROARCH.md): the excess over the algorithmic "
+                                    "bytes is the per-XCD re-fetch of the source table, part of which never reaches HBM",
+                    "measured_copy_GBs": round(copy_gbs, 1), "frac_of_measured_copy": round(dom["achieved_GBs"] / copy_gbs, 4),
+                    "alg_bytes_per_launch": dom["alg_bytes"], "avg_launch_ms": dom["avg_ms"], "passes": passes,
+                    "agg_kernels_ms_per_step": round(agg_ms, 4), "outside_agg_kernels_ms_per_step": round(dt_local / args.steps * 1e3 - agg_ms, 4),
+                    "forward_alg_bytes": fwd_bytes, "forward_achieved_GBs": round(fwd_bytes / (dt_local / args.steps * 1e3) / 1e6, 1),
+                    # the resource that actually bounds the tile kernel: per launch every non-zero reads one D*4-byte source row
+                    # from LDS and every tile streams its source range into LDS once
+                    "on_chip": {"lds_read_bytes": dom["nnz"] * dom["D"] * 4,
+                                "lds_achieved_TBs": round(dom["nnz"] * dom["D"] * 4 / dom["avg_ms"] / 1e9, 1),
+                                "lds_peak_TBs": 157.0, "lds_frac": round(dom["nnz"] * dom["D"] * 4 / dom["avg_ms"] / 1e9 / 157.0, 3),
+                                "fp32_fma_TFLOPs": round(2 * dom["nnz"] * dom["D"] / dom["avg_ms"] / 1e9, 1), "fp32_vector_peak_TFLOPs": 157.3},
+                    "note": "AI vs algorithmic bytes is 50-110 flop/B (> fp32 ridge ~20): the gather of nnz*D*4 B "
+                            "from L2/MALL and fp32 FMA issue bound this kernel before HBM does (DESIGN.md section 4)"}
 
     # ---- N > 1: every rank's own dominant-kernel roofline (HIP events on that rank's stream) + the communicator's view
     per_gpu, comm = None, None
-    if world > 1:
+    if args.full and world > 1:
         mine = {"rank": rank, "device": f"cuda:{local_rank}", "gpu": torch.cuda.get_device_name(dev), "pci": ident.get("pci"),
                 "uuid": ident.get("uuid"), "cells": C,
                 "nnz": engine.nnz, "kernel": dom["kernel"], "avg_launch_ms": dom["avg_ms"],
@@ -596,7 +633,7 @@ def main():
     # ---- secondary measurements (never `value`): a sustained run of the same step (>= ~3 s of GPU time, so that an
     # outside sampler sees the device busy and the average is not 20 steps thin), and - N > 1 - the weak-scaling line
     sustained, weak = None, None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         n_sus = max(args.steps, min(20000, int(3.0 / max(dt / args.steps, 1e-5))))     # >= 3 s of the same step back to back
         dt_s, _, _, _ = timed_steps(engine, feats_g, feats_c, n_sus, 0, world, dev, profile=False, step=step_fn)
         sustained = {"steps": n_sus, "ms_per_step": round(dt_s / n_sus * 1e3, 4), "value": round(total_cells / (dt_s / n_sus), 1),
@@ -615,7 +652,7 @@ def main():
     # ---- secondary (never `value`): BASELINE cfg4's training step on the same resident graph at N = 1 - forward (dropout 0.1) +
     # CrossEntropyLoss(sum) + backward through K2t / the fused glue + Adam (reference train.py:80-87)
     train_step = None
-    if world == 1 and not args.no_secondary and not cfg.total_cells and os.environ.get("WGNN_BENCH_TRAIN_STEP", "1") == "1":
+    if args.full and world == 1 and not args.no_secondary and not cfg.total_cells and os.environ.get("WGNN_BENCH_TRAIN_STEP", "1") == "1":
         torch.manual_seed(4321)
         tm = sda.GNN(cfg.dense_dim, cfg.hidden, cfg.n_classes, cfg.n_layers, G, activation=F.relu, dropout=0.1).to(dev)
         topt = torch.optim.Adam(tm.parameters(), lr=1e-3, weight_decay=5e-4, fused=True)
@@ -671,23 +708,24 @@ def main():
 
     # ---- secondary (never `value`): the one-shot path - graph build, plan build, first forward, predictor-shaped end to end
     one_shot = None
-    if world == 1 and not args.no_secondary and os.environ.get("WGNN_BENCH_ONE_SHOT", "1") == "1":
+    if args.full and world == 1 and not args.no_secondary and os.environ.get("WGNN_BENCH_ONE_SHOT", "1") == "1":
         one_shot = one_shot_costs(cfg, model, dev, S, sda, ms_per_step)
         one_shot["bench_workload_generate_s"] = round(t_generate, 2)
 
     # ---- CPU baseline: the restatement (C/OpenMP aggregation + torch Linear) on this host, rank 0, N = 1 only
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(engine.graph, model, feats_g, feats_c, out, cfg)
 
-    try:
-        from scdeepsort_amd import ops as _ops
-        _kb = _ops.tiled_block_rows(-(-min(cfg.hidden, 256) // 4) * 4)
-        if _ops.tiled_kernel_serves(engine.graph.cg, cfg.hidden):
-            generator_desc["shared_pair_share"] = {"cells<-genes": shared_pair_share(engine.graph.cg.tile_plan(_kb)),
-                                                   "genes<-cells": shared_pair_share(engine.graph.gc.tile_plan(_kb))}
-    except Exception as e:                                       # descriptive only
-        generator_desc["shared_pair_share"] = f"unavailable: {e}"
+    if args.full:
+        try:
+            from scdeepsort_amd import ops as _ops
+            _kb = _ops.tiled_block_rows(-(-min(cfg.hidden, 256) // 4) * 4)
+            if _ops.tiled_kernel_serves(engine.graph.cg, cfg.hidden):
+                generator_desc["shared_pair_share"] = {"cells<-genes": shared_pair_share(engine.graph.cg.tile_plan(_kb)),
+                                                       "genes<-cells": shared_pair_share(engine.graph.gc.tile_plan(_kb))}
+        except Exception as e:                                   # descriptive only
+            generator_desc["shared_pair_share"] = f"unavailable: {e}"
     if rank == 0:
         line = {"metric": "cells embedded/sec (2-layer WGNN fwd)", "value": round(value, 1), "unit": "cells/s",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
@@ -695,7 +733,7 @@ def main():
                 "dtype": "f32" if cfg.feature_dtype == torch.float32 else "f32 (fp16-stored input features)", "data": "synthetic",
                 "config": {"workload": workload_string(cfg, total_cells, mode),
                            "generator": generator_desc, "cells_total": total_cells, "cells_this_rank": C,
-                           "nnz_per_gpu": per_gpu[0]["nnz"] if per_gpu else roofline["passes"][0]["nnz"],
+                           "nnz_per_gpu": per_gpu[0]["nnz"] if per_gpu else nnz_local,
                            "parallelism": f"cell-shard x{world}", "setup_s": round(t_setup, 1), "device": ident, "communicator": comm,
                            "gemm_selection": gemm_selection, "step_launch": launch_desc, "eager_ms_per_step": eager_ms, "launch_calibration_ms": launch_calibration,
                            "sharded_vs_unsharded": self_check},

@@ -129,7 +129,10 @@ class GraphedShardedForward:
         with torch.cuda.device(dev):
             if mode == "whole":
                 g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g), torch.no_grad():
+                # thread-local capture mode: ProcessGroupNCCL's watchdog thread keeps querying the events of the collectives
+                # issued before the capture (the warm-up above); under the default global mode that query fails while this
+                # thread captures, and the watchdog aborts the process.  This thread's own unsafe calls still fail the capture.
+                with torch.cuda.graph(g, capture_error_mode="thread_local"), torch.no_grad():
                     self.logits = engine.forward(self.feats_g, self.feats_c, gather_logits=gather_logits)
                 self._seq.append(g)
             else:

@@ -14,31 +14,31 @@ def run(cmd, env=None, timeout=900):
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=dict(os.environ, **(env or {})))
     return r.stdout, r.stderr, round(time.time() - t, 1)
 for cfg, extra in (("cfg2", []), ("cfg5", ["--no-cpu-baseline"])):
-    so, se, dt = run([sys.executable, "bench.py", "--config", cfg, "--steps", "20", "--warmup", "3"] + extra)
+    so, se, dt = run([sys.executable, "bench.py", "--full", "--config", cfg, "--steps", "20", "--warmup", "3"] + extra)
     line = [l for l in so.splitlines() if l.startswith("{")]
     d = json.loads(line[-1]) if line else {"error": se[-800:]}
     if "roofline" in d:
         d["roofline"].pop("note", None)
     if d.get("cpu_baseline"):
         d["cpu_baseline"].pop("all", None)
-    out[cfg + "_forward_1gpu"] = {"cmd": f"python bench.py --config {cfg} --steps 20 --warmup 3 " + " ".join(extra), "wall_s": dt, "line": d}
-so, se, dt = run([sys.executable, "bench.py", "--config", "cfg3", "--hidden", "200", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-secondary"])
+    out[cfg + "_forward_1gpu"] = {"cmd": f"python bench.py --full --config {cfg} --steps 20 --warmup 3 " + " ".join(extra), "wall_s": dt, "line": d}
+so, se, dt = run([sys.executable, "bench.py", "--full", "--config", "cfg3", "--hidden", "200", "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-secondary"])
 line = [l for l in so.splitlines() if l.startswith("{")]
 d = json.loads(line[-1]) if line else {"error": se[-800:]}
 if "roofline" in d:
     d["roofline"].pop("note", None)
-out["cfg3_hidden200_forward_1gpu"] = {"cmd": "python bench.py --config cfg3 --hidden 200 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary  (the reference's default hidden_dim, train.py:137)", "wall_s": dt, "line": d}
+out["cfg3_hidden200_forward_1gpu"] = {"cmd": "python bench.py --full --config cfg3 --hidden 200 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary  (the reference's default hidden_dim, train.py:137)", "wall_s": dt, "line": d}
 # the headline workload under BOTH popularity laws: SURVEY 8d's (the default) and rounds 1-5's dense head
 both = {}
 for pop in ("testis199", "dense_head"):
-    so, se, dt = run([sys.executable, "bench.py", "--popularity", pop, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-secondary"])
+    so, se, dt = run([sys.executable, "bench.py", "--full", "--popularity", pop, "--steps", "20", "--warmup", "3", "--no-cpu-baseline", "--no-secondary"])
     line = [l for l in so.splitlines() if l.startswith("{")]
     d = json.loads(line[-1]) if line else {"error": se[-800:]}
     both[pop] = {"ms_per_step": d.get("ms_per_step"), "cells_per_s": d.get("value"), "roofline_frac": (d.get("roofline") or {}).get("frac"),
                  "dominant_launch_ms": (d.get("roofline") or {}).get("avg_launch_ms"),
                  "passes": [(p["rows"], p["src_rows"], p["avg_ms"]) for p in (d.get("roofline") or {}).get("passes", [])],
                  "generator": (d.get("config") or {}).get("generator"), "workload": (d.get("config") or {}).get("workload")}
-out["cfg3_both_popularity_laws"] = {"cmd": "python bench.py --popularity {testis199|dense_head} --steps 20 --warmup 3 --no-cpu-baseline --no-secondary", **both}
+out["cfg3_both_popularity_laws"] = {"cmd": "python bench.py --full --popularity {testis199|dense_head} --steps 20 --warmup 3 --no-cpu-baseline --no-secondary", **both}
 so, se, dt = run([sys.executable, "examples/train_sharded.py", "--config", "cfg3", "--steps", "10"])
 out["cfg4_full_batch_training_step_1gpu"] = {"cmd": "python examples/train_sharded.py --config cfg3 --steps 10", "wall_s": dt,
                                              "stdout": so.strip().splitlines()[-1] if so.strip() else se[-800:]}

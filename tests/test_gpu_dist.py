@@ -231,7 +231,7 @@ def test_bench_two_ranks_on_one_gpu(tmp_path):
     debug mode.  The line must say n_gpus = 2 and carry one roofline record per rank."""
     env = dict(os.environ, WGNN_BENCH_SHARE_GPU="1", WGNN_BENCH_CONFIG="cfg2")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--graphed", "on"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--graphed", "on", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -257,7 +257,7 @@ def test_bench_strong_scaling_config_shards_the_job(tmp_path):
     env = dict(os.environ, WGNN_BENCH_SHARE_GPU="1", WGNN_BENCH_CONFIG="tiny_atlas")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -272,3 +272,23 @@ def test_bench_refuses_more_ranks_than_gpus():
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", str(n + 1), "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout)
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py --gpus 1` run prints the headline only (no roofline, no secondaries), times exactly `--steps` steps and,
+    with `--dump-outputs`, writes the logits of the last timed step; the same arguments give the same inputs, so two runs agree."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "WGNN_BENCH_SHARE_GPU")}
+    env["WGNN_BENCH_CONFIG"] = "tiny"
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+    assert all(line[k] is None for k in ("roofline", "cpu_baseline", "sustained", "weak_scaling", "train_step", "one_shot"))
+    a, b = np.load(tmp_path / "a" / "logits.npy"), np.load(tmp_path / "b" / "logits.npy")
+    assert a.dtype == np.float32 and a.shape == (512, 16) and np.isfinite(a).all() and np.abs(a).max() > 0
+    np.testing.assert_allclose(a, b, rtol=0, atol=1e-5)

@@ -466,6 +466,27 @@ def test_bench_workload_string_does_not_depend_on_the_rank_count():
     assert 'default=os.environ.get("WGNN_BENCH_CONFIG", "cfg3")' in src and 'default=os.environ.get("WGNN_BENCH_SCALING", "strong")' in src
 
 
+def test_bench_dump_outputs_writes_float32_within_the_budget(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: every array as DIR/<name>.npy in float32; one larger than the budget as a fixed, seeded
+    sample of its rows, the row indices beside it."""
+    import importlib.util
+    from pathlib import Path
+    spec = importlib.util.spec_from_file_location("bench_mod", Path(sda.__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    x = torch.arange(300 * 4, dtype=torch.float64).reshape(300, 4)
+    bench.dump_outputs(tmp_path / "whole", {"logits": x})
+    a = np.load(tmp_path / "whole" / "logits.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, x.numpy().astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1600)             # 300 rows x 16 B: a sample of 50 rows
+    for run in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / run, {"logits": x})
+    rows = np.load(tmp_path / "s1" / "logits_rows.npy")
+    s = np.load(tmp_path / "s1" / "logits.npy")
+    assert s.nbytes <= 1600 and s.shape == (50, 4) and rows.shape == (50,) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(s, x.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "logits_rows.npy"))
+
+
 def test_tracked_gemm_picks_file_is_wellformed():
     """scdeepsort_amd/tuned_gemms_gfx950.csv (PyTorch TunableOp result format): validator lines naming the library stack it was
     tuned against, then one `op,shape,solution,time` line per GEMM shape of the BASELINE workloads."""
