@@ -428,6 +428,41 @@ int wgnn_csr_transpose_fill(const int32_t* rowptr, const int32_t* col, const flo
                             int32_t n_cols, int64_t n_chunks, int32_t* counts, const int32_t* t_rowptr, int32_t* t_col, float* t_val,
                             void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Resident prediction (additive export, WGNN_VERSION stays 206: the binding looks the symbol up by name, and a caller that
+ * needs it checks for the symbol, not for a version).  One layer of a trained model over a batch of B TEST cells, against
+ * gene-side tables that are constants of the bundle: test cells get gene->cell edges only (reference preprocess.py:184-187)
+ * and PCA is fitted on the support cells, so a test cell's output depends on its own expression row alone.  No plan, no
+ * graph: one wavefront per cell (grid-stride), deterministic (fixed-order folds, no atomics).
+ *
+ *   rowptr [B+1] (int32, or int64 with WGNN_FLAG_ROWPTR_I64), col int32 gene ids in [0, n_genes), raw f32: the RAW
+ *   (unnormalised) expression values of the batch.  deg = row length, S = sum of the row's raw values:
+ *     self_rows == NULL (layer 1):  z = sum_j x_j (alpha[g_j] deg / S + alpha[G+1] / (S + 1e-6)) table[g_j] / (deg + 1) + bias
+ *                                   (table = gene_feat . W1^T; the second term is the self-loop on the cell feature
+ *                                   rownorm(X) . gene_feat, preprocess.py:201-204, folded through W1)
+ *     self_rows != NULL:            z = (sum_j alpha[g_j] deg x_j / S table[g_j] + alpha[G+1] self_rows[c]) / (deg + 1) + bias
+ *                                   (table = h_{l-1}[genes] . W_l^T, self_rows = h_{l-1}[cell] . W_l^T)
+ *   An empty row has z = bias (+ alpha[G+1] self_rows[c]).  h = ReLU(z).
+ *   table [n_genes, ld_table], H valid columns, H % 4 == 0, H <= 256 (else WGNN_ERR_ALIGNMENT / _UNSUPPORTED: the caller
+ *   zero-pads other widths); alpha [n_genes + 2]; bias [H].
+ *   Without a head (w_head == NULL): out [B, ld_out] = h.
+ *   With a head w_head [C, H] (contiguous), b_head [C]; C * H * 4 <= 64 KiB (staged in LDS once per workgroup; else
+ *   WGNN_ERR_UNSUPPORTED - run the head as a GEMM):
+ *     logits [B, ld_logits] = h . w_head^T + b_head     (may be NULL)
+ *     max_prob [B]          = 1 / sum_j exp(logits_j - max_j logits_j)         (softmax maximum, predict.py:78-80)
+ *     label [B]             = argmax (lowest index among equal maxima), or -1 when max_prob < unsure_threshold
+ *                             (the caller passes float32(unsure_rate / C), the comparison of predict.py:83)
+ *   flags: WGNN_FLAG_ROWPTR_I64 or 0.  B < 2^31.  wgnn_last_error_string(code), asked on the same thread right after a failing
+ *   call, names the check that failed.
+ * ------------------------------------------------------------------------- */
+int wgnn_predict_rows(const void* rowptr, const int32_t* col, const float* raw, int64_t n_rows,
+                      const float* table, int64_t ld_table, int32_t n_genes, int32_t H,
+                      const float* alpha, const float* bias, const float* self_rows, int64_t ld_self,
+                      float* out, int64_t ld_out,
+                      const float* w_head, const float* b_head, int32_t n_classes, float unsure_threshold,
+                      float* logits, int64_t ld_logits, int32_t* label, float* max_prob,
+                      uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,9 @@ SIGNATURES = {
     "wgnn_agg_linear_relu_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _int, _i32, _vp, _i64, _vp, _i64, _vp, _vp,
                                            _i64, _i32, _u32, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
                                            _vp, _i64, _vp, _i32, _u32, _vp, _i64, _vp]),
+    # additive export (the version stays 206): looked up by name like every other entry
+    "wgnn_predict_rows": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _i64,
+                                    _vp, _vp, _i32, C.c_float, _vp, _i64, _vp, _vp, _u32, _vp]),
 }
 
 

@@ -11,6 +11,8 @@ kernels; file ingest, vocabularies and PCA are ordinary host code kept deliberat
 """
 from __future__ import annotations
 
+import os
+import re
 from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
 
@@ -23,6 +25,7 @@ import torch.nn.functional as F
 from ._lib import WgnnError
 from .gnn import GNN
 from .graph import CellGeneGraph
+from . import ops as _ops
 from .ops import cross_entropy_sum
 
 
@@ -45,26 +48,35 @@ def _read_expression(path, file_type: str) -> pd.DataFrame:
     return df.transpose(copy=True)
 
 
-def _features(expr: sp.csr_matrix, n_support: int, dense_dim: int, seed, device) -> torch.Tensor:
-    """gene_feat = PCA(dense_dim) of the support cells' (genes x cells) matrix (host, sklearn, like the reference);
-    cell_feat = rownorm(X) . gene_feat on the device through K1 (preprocess_internal.py:183-202, preprocess.py:194-210)."""
+def _gene_features(expr: sp.csr_matrix, n_support: int, dense_dim: int, seed, device) -> torch.Tensor:
+    """gene_feat = PCA(dense_dim) of the support cells' (genes x cells) matrix (host, sklearn, like the reference,
+    preprocess.py:194-196); the support cells are the first ``n_support`` rows of ``expr``."""
     from sklearn.decomposition import PCA
     dense_sup = expr[:n_support].toarray().astype(np.float64)
     k = min(dense_dim, dense_sup.shape[1], n_support)
     gene_feat = PCA(k, random_state=seed).fit_transform(dense_sup.T)
     if k < dense_dim:
         gene_feat = np.pad(gene_feat, ((0, 0), (0, dense_dim - k)))
-    gf = torch.from_numpy(gene_feat.astype(np.float32)).to(device)
-    cf = CellGeneGraph.cell_features(torch.from_numpy(expr.indptr.astype(np.int64)).to(device),
-                                     torch.from_numpy(expr.indices.astype(np.int32)).to(device),
-                                     torch.from_numpy(expr.data.astype(np.float32)).to(device), gf)
-    return torch.cat([gf, cf])
+    return torch.from_numpy(gene_feat.astype(np.float32)).to(device)
 
 
-def read_xlsx_sheet(path, sheet_name: str) -> List[List[Optional[str]]]:
+def _cell_features(expr: sp.csr_matrix, gf: torch.Tensor, device) -> torch.Tensor:
+    """cell_feat = rownorm(X) . gene_feat on the device through K1 (preprocess_internal.py:197-202, preprocess.py:201-210)."""
+    return CellGeneGraph.cell_features(torch.from_numpy(expr.indptr.astype(np.int64)).to(device),
+                                       torch.from_numpy(expr.indices.astype(np.int32)).to(device),
+                                       torch.from_numpy(expr.data.astype(np.float32)).to(device), gf)
+
+
+def _features(expr: sp.csr_matrix, n_support: int, dense_dim: int, seed, device) -> torch.Tensor:
+    """[gene_feat; cell_feat] (preprocess_internal.py:183-202, preprocess.py:194-210)."""
+    gf = _gene_features(expr, n_support, dense_dim, seed, device)
+    return torch.cat([gf, _cell_features(expr, gf, device)])
+
+
+def read_xlsx_sheet(path, sheet_name: Optional[str]) -> List[List[Optional[str]]]:
     """Rows of one worksheet of an .xlsx workbook as lists of strings (None = empty cell).  A minimal reader (zip + XML,
     shared and inline strings, plain numbers) for ``map/celltype2subtype.xlsx`` (predict.py:125-128): neither xlrd nor
-    openpyxl is a dependency here."""
+    openpyxl is a dependency here.  ``sheet_name=None``: the first sheet (pandas.read_excel's default)."""
     import re
     import zipfile
     import xml.etree.ElementTree as ET
@@ -74,7 +86,7 @@ def read_xlsx_sheet(path, sheet_name: str) -> List[List[Optional[str]]]:
         wb = ET.fromstring(z.read("xl/workbook.xml"))
         rid = None
         for sh in wb.find("m:sheets", ns):
-            if sh.get("name") == sheet_name:
+            if sh.get("name") == sheet_name or (sheet_name is None and rid is None):
                 rid = sh.get(f"{{{ns['r']}}}id")
         if rid is None:
             raise KeyError(f"no sheet {sheet_name!r} in {path}")
@@ -342,10 +354,8 @@ def _predict(species, tissue, input_file, model_path: Path, save_path, unsure_ra
                            gpu_id, threshold, seed)
 
 
-def _predict_logits(species, tissue, input_file, model_path: Path, file_type, gpu_id, threshold, seed):
-    """The graph-side half of ``predict``: bundle -> predict graph (support cells + test cells) -> logits of the test cells.
-    Returns (logits [n_test, n_classes] on the device, test cell names, id2label, BundlePaths)."""
-    dev = _device(gpu_id)
+def _load_bundle(species, tissue, model_path: Path, dev) -> dict:
+    """The four files of a trained bundle (BundlePaths), parsed: vocabularies, support matrix, state dict and its sizes."""
     bundle = BundlePaths(model_path, species, tissue)
     missing = [str(f) for f in (bundle.model, bundle.support, bundle.genes, bundle.cell_types) if not f.exists()]
     if missing:
@@ -356,40 +366,306 @@ def _predict_logits(species, tissue, input_file, model_path: Path, file_type, gp
     state = torch.load(bundle.model, map_location=dev)['model']                          # predict.py:56-59
     n_layers = sum(1 for k in state if k.endswith("fc_neigh.weight"))
     hidden_dim, dense_dim = state["layers.0.fc_neigh.weight"].shape
-    G = len(id2gene)
-    gene2id = {g: i for i, g in enumerate(id2gene)}
+    return dict(bundle=bundle, id2gene=id2gene, id2label=id2label, support=support, state=state, n_layers=n_layers,
+                hidden_dim=hidden_dim, dense_dim=dense_dim, gene2id={g: i for i, g in enumerate(id2gene)})
+
+
+def _read_test_csr(input_file, file_type, gene2id: dict, threshold) -> Tuple[sp.csr_matrix, pd.Index]:
+    """A test file as a (cells x bundle genes) CSR of raw values > threshold; genes outside the bundle are dropped
+    (preprocess.py:160-161, 173-178)."""
     df = _read_expression(input_file, file_type)
     cols = [c for c in df.columns if str(c) in gene2id]                                  # preprocess.py:160-161
     arr = df[cols].to_numpy(dtype=np.float32)
     cid = np.array([gene2id[str(c)] for c in cols])
     r, c = np.nonzero(arr > threshold)
-    test = sp.csr_matrix((arr[r, c], (r, cid[c])), shape=(arr.shape[0], G))
-    expr = sp.vstack([support, test]).tocsr(); expr.sort_indices()
-    n_sup = support.shape[0]
-    mask = np.zeros(expr.shape[0], bool); mask[:n_sup] = True           # test cells: gene->cell edges only (preprocess.py:184-187)
-    feats = _features(expr, n_sup, dense_dim, seed, dev)
-    graph = CellGeneGraph.from_expression(expr, support_mask=mask, device=dev)
-    model = GNN(dense_dim, hidden_dim, len(id2label), n_layers, G, activation=F.relu, dropout=0.1).to(dev)
-    model.load_state_dict(state)
+    test = sp.csr_matrix((arr[r, c], (r, cid[c])), shape=(arr.shape[0], len(gene2id)))
+    return test, df.index
+
+
+def _load_model(b: dict, dev) -> GNN:
+    model = GNN(b["dense_dim"], b["hidden_dim"], len(b["id2label"]), b["n_layers"], len(b["id2gene"]), activation=F.relu,
+                dropout=0.1).to(dev)
+    model.load_state_dict(b["state"])
     model.eval()
+    return model
+
+
+def _graph_logits(model: GNN, support: sp.csr_matrix, test: sp.csr_matrix, gene_feat: torch.Tensor, dev,
+                  expr: Optional[sp.csr_matrix] = None) -> torch.Tensor:
+    """Logits of the test cells through the predict graph of support + test cells (test cells: gene->cell edges only,
+    preprocess.py:184-187) with the given gene features (predict.py:61-88).  ``expr``: the stacked, index-sorted matrix
+    when the caller has it already."""
+    G = support.shape[1]
+    if expr is None:
+        expr = sp.vstack([support, test]).tocsr(); expr.sort_indices()
+    n_sup = support.shape[0]
+    mask = np.zeros(expr.shape[0], bool); mask[:n_sup] = True
+    feats = torch.cat([gene_feat, _cell_features(expr, gene_feat, dev)])
+    graph = CellGeneGraph.from_expression(expr, support_mask=mask, device=dev)
     seeds = range(G + n_sup, G + expr.shape[0])           # the test cells: one contiguous block of node ids (predict.py:64-76)
     with torch.no_grad():
-        logits = model(graph, feats, seeds=seeds)
-    return logits, df.index, id2label, bundle
+        return model(graph, feats, seeds=seeds)
+
+
+def _predict_logits(species, tissue, input_file, model_path: Path, file_type, gpu_id, threshold, seed):
+    """The graph-side half of ``predict``: bundle -> predict graph (support cells + test cells) -> logits of the test cells.
+    Returns (logits [n_test, n_classes] on the device, test cell names, id2label, BundlePaths)."""
+    dev = _device(gpu_id)
+    b = _load_bundle(species, tissue, model_path, dev)
+    test, index = _read_test_csr(input_file, file_type, b["gene2id"], threshold)
+    support = b["support"]
+    expr = sp.vstack([support, test]).tocsr(); expr.sort_indices()
+    gf = _gene_features(expr, support.shape[0], b["dense_dim"], seed, dev)
+    logits = _graph_logits(_load_model(b, dev), support, test, gf, dev, expr)
+    return logits, index, b["id2label"], b["bundle"]
 
 
 def _predict_on(species, tissue, input_file, model_path: Path, save_path, unsure_rate, file_type, dense_dim, hidden_dim,
                 gpu_id, threshold, seed) -> pd.DataFrame:
     logits, index, id2label, bundle = _predict_logits(species, tissue, input_file, model_path, file_type, gpu_id, threshold, seed)
     pred, _ = _classify(logits, unsure_rate)
+    return _prediction_frame(species, tissue, input_file, index, pred, id2label, bundle, save_path)
+
+
+def _prediction_frame(species, tissue, input_file, index, pred, id2label, bundle: BundlePaths, save_path,
+                      original=None) -> pd.DataFrame:
+    """The output table of predict.py:124-146 (new type / subtype names when the bundle has a label map), optionally with
+    the evaluate mode's 'original label' column (:138-143); written to ``save_path`` when given."""
     names = [id2label[p] if p >= 0 else "unsure" for p in pred]
-    out = pd.DataFrame({"index": index, "cell_type": names})
+    cols = {"index": index}
+    if original is not None:
+        cols["original label"] = list(original)
     map_file = bundle.label_map()
     if map_file is not None:                                             # predict.py:124-146: new type / subtype names
         old2new, old2sub = load_label_map(map_file, species)
-        out = pd.DataFrame({"index": index, "cell_type": [old2new.get(p, p) for p in names],
-                            "cell_subtype": [old2sub.get(p, p) for p in names]})
+        cols["cell_type"] = [old2new.get(p, p) for p in names]
+        cols["cell_subtype"] = [old2sub.get(p, p) for p in names]
+    else:
+        cols["cell_type"] = names
+    out = pd.DataFrame(cols)
     if save_path is not None:
         Path(save_path).mkdir(parents=True, exist_ok=True)
         out.to_csv(Path(save_path) / f"{species}_{tissue}_{Path(input_file).stem}.csv", index=False)
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# resident prediction
+# ------------------------------------------------------------------------------------------------
+# nnz x H x n_layers of a batch above which ResidentPredictor takes the graph route.  A per-entry gather re-reads a whole
+# H-wide table row for every non-zero, which the LDS-streamed tile kernel of the graph route avoids; but the graph route
+# rebuilds the predict graph on every call.  Measured (profiles/resident_predict.json, DESIGN.md section 3): no crossover up
+# to the largest batch timed - 100 000 cells x 800 genes, 2 layers, H 200 = 3.2e10 - where the fused call takes 24.7 ms and
+# the graph call 748 ms.  The limit is that largest measured point: beyond it the graph route, whose scaling is known.
+RESIDENT_FUSED_MAX_WORK = int(os.environ.get("WGNN_RESIDENT_FUSED_MAX_WORK", 32_000_000_000))
+
+
+def load_map_dict(path, tissue: str) -> dict:
+    """``get_map_dict`` (reference preprocess.py:14-29): ``{num: {test cell type: {training cell types}}}`` from the rows of
+    ``map/{species}/map.xlsx`` (first sheet; columns Tissue, num, Test Datasets, Celltype, Training dataset cell type)
+    whose Tissue is ``tissue``."""
+    rows = read_xlsx_sheet(path, None)
+    if not rows:
+        return {}
+    header = [h.strip() if isinstance(h, str) else h for h in rows[0]]
+    try:
+        i_t, i_n, i_c = header.index("Tissue"), header.index("num"), header.index("Celltype")
+    except ValueError as e:
+        raise ValueError(f"{path}: map header {header} lacks {e}") from None
+    i_train = 4                                          # itertuples' `_5` = the fifth column (:22)
+    out: dict = {}
+    for row in rows[1:]:
+        row = row + [None] * (max(i_t, i_n, i_c, i_train) + 1 - len(row))
+        if row[i_t] != tissue:
+            continue
+        num = int(float(row[i_n]))
+        out.setdefault(num, {}).setdefault(row[i_c], set()).add(row[i_train])
+    return out
+
+
+def evaluate_predictions(pred, truth: Sequence[str], id2label: Sequence[str], mapping: dict):
+    """``evaluate_test``'s counting (predict.py:104-118): ``pred`` = label ids with -1 for unsure; a prediction is correct
+    iff its label is one of ``mapping[true label]``; unsure cells are counted and never correct.
+    Returns (correct, total, unsure, acc, predicted names)."""
+    correct = unsure = 0
+    names = []
+    for p, t in zip(pred, truth):
+        if p < 0:
+            unsure += 1
+            names.append("unsure")
+            continue
+        if t not in mapping:
+            raise ValueError(f"true cell type {t!r} is not in the evaluation map (its rows for this dataset: {sorted(mapping)})")
+        if id2label[p] in mapping[t]:
+            correct += 1
+        names.append(id2label[p])
+    total = len(names)
+    return correct, total, unsure, (correct / total if total else 0.0), names
+
+
+def dataset_number(data_file, tissue: str) -> int:
+    """The dataset number of a test file named as the reference's (``{species}_{tissue}{num}_data.csv``, preprocess.py:141):
+    the digits after the tissue name in the file's stem (``mouse_Testis199_data`` -> 199)."""
+    stem = Path(data_file).name.split(".")[0]
+    m = re.search(re.escape(tissue) + r"(\d+)", stem)
+    if m is None:
+        raise ValueError(f"no dataset number after {tissue!r} in {Path(data_file).name!r}: pass dataset_num")
+    return int(m.group(1))
+
+
+class ResidentPredictor:
+    """A trained bundle loaded ONCE, its gene side resident on the GPU, classifying any batch of test cells.
+
+    For a given bundle everything except the test rows is constant: gene features (PCA of the support cells), and - since
+    test cells feed no genes - every gene's embedding at every layer.  So a test cell's logits depend on its own expression
+    row alone, and a layer is one weighted gather over one [G, H] table per entry (``wgnn_predict_rows``; the head, softmax
+    and the unsure rule fused into the last layer's launch).  No graph build, no plans, no per-call PCA.
+
+    Resident: ``Q = gene_feat . W1^T``, ``T_l = h_{l-1}[genes] . W_l^T`` for l >= 2 (h of the genes from the existing
+    ``GNN._layer`` over a support-only graph), alpha, biases and the head.  A batch whose ``nnz * H * n_layers`` exceeds
+    ``RESIDENT_FUSED_MAX_WORK`` (or with a hidden width above 256) takes the graph route instead - the predict graph of
+    ``DeepSortPredictor`` with the cached gene features; ``last_route`` says which one ran ("fused" | "graph")."""
+
+    def __init__(self, species, tissue, model_path='pretrained', gpu_id=0, unsure_rate=2., file_type='csv', threshold=0,
+                 seed=10086):
+        self.species, self.tissue, self.unsure_rate, self.file_type, self.threshold = species, tissue, unsure_rate, file_type, threshold
+        self.model_path = Path(model_path)
+        self.device = _device(gpu_id)
+        self.last_route: Optional[str] = None
+        with torch.cuda.device(self.device), torch.no_grad():
+            self._setup(seed)
+
+    def _setup(self, seed):
+        dev = self.device
+        b = _load_bundle(self.species, self.tissue, self.model_path, dev)
+        self.bundle, self.id2label, self.id2gene, self._gene2id = b["bundle"], b["id2label"], b["id2gene"], b["gene2id"]
+        self.support: sp.csr_matrix = b["support"]
+        self.support.sort_indices()
+        self.model = _load_model(b, dev)
+        self.n_layers, self.n_genes, self.n_classes = b["n_layers"], len(self.id2gene), len(self.id2label)
+        self.gene_feat = _gene_features(self.support, self.support.shape[0], b["dense_dim"], seed, dev)
+        m = self.model
+        H = m.layers[0].fc_neigh.weight.shape[0]
+        self.hidden, self.hidden_padded = H, -(-H // 4) * 4
+        Hp = self.hidden_padded
+        self.unsure_threshold = float(np.float32(self.unsure_rate / self.n_classes))    # the comparison _classify makes
+        self.alpha = m.alpha.detach().reshape(-1).float().contiguous()
+
+        def rows_padded(w, n_cols):                      # [H, K] -> [Hp, n_cols] with zero rows / columns
+            w = w.detach().float()
+            return F.pad(w, (0, n_cols - w.shape[1], 0, Hp - w.shape[0])).contiguous()
+
+        gf = self.gene_feat
+        if gf.shape[1] % 4:                              # linear_fwd's K must be a multiple of 4
+            gf = F.pad(gf, (0, -gf.shape[1] % 4))
+        W1 = rows_padded(m.layers[0].fc_neigh.weight, gf.shape[1])
+        self.tables = [_ops.linear_fwd(gf.contiguous(), W1)]                 # Q = gene_feat . W1^T  [G, Hp]
+        self.biases = [F.pad(m.layers[0].fc_neigh.bias.detach().float(), (0, Hp - H)).contiguous()]
+        self.self_weights: List[Optional[torch.Tensor]] = [None]
+        if self.n_layers >= 2:
+            # h_{l-1}[genes] from the existing layer code over a SUPPORT-ONLY graph: test cells feed no genes, so its gene rows
+            # are those of every predict graph of this bundle
+            g = CellGeneGraph.from_expression(self.support, device=dev)
+            h_g, h_c = self.gene_feat, _cell_features(self.support, self.gene_feat, dev)
+            for l in range(1, self.n_layers):
+                h_g, h_c = m._layer(g, m.layers[l - 1], h_g, h_c, want_genes=True, cell_rows=None)
+                Wl = rows_padded(m.layers[l].fc_neigh.weight, Hp)
+                hg = h_g.float()
+                hg = F.pad(hg, (0, Hp - hg.shape[1])) if hg.shape[1] < Hp else hg[:, :Hp]
+                self.tables.append(_ops.linear_fwd(hg.contiguous(), Wl))     # T_l = h_{l-1}[genes] . W_l^T
+                self.biases.append(F.pad(m.layers[l].fc_neigh.bias.detach().float(), (0, Hp - H)).contiguous())
+                self.self_weights.append(Wl)
+            del g, h_g, h_c
+        self.w_head = F.pad(m.linear.weight.detach().float(), (0, Hp - H)).contiguous()
+        self.b_head = m.linear.bias.detach().float().contiguous()
+
+    # ---------------------------------------------------------------------------------------------
+    def _route(self, nnz: int) -> str:
+        if self.hidden_padded > 256 or nnz * self.hidden_padded * self.n_layers > RESIDENT_FUSED_MAX_WORK:
+            return "graph"
+        return "fused"
+
+    def classify(self, expr) -> Tuple[np.ndarray, np.ndarray, torch.Tensor]:
+        """Classify a batch: ``expr`` = a scipy CSR (cells x the bundle's genes, raw values) or a device
+        ``(rowptr, col, raw)`` triple over the bundle's gene ids.  Returns (label ids with -1 = unsure, max softmax
+        probability, logits on the device)."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._classify(expr)
+
+    def _classify(self, expr):
+        dev = self.device
+        if isinstance(expr, (tuple, list)):
+            rowptr, col, raw = expr
+            _ops._require_cuda(rowptr, col, raw)
+            rowptr = rowptr if rowptr.dtype in (torch.int32, torch.int64) else rowptr.long()
+            col, raw = col.to(torch.int32), raw.to(torch.float32)
+            checked, host = False, None
+        else:
+            host = sp.csr_matrix(expr)
+            if host.shape[1] != self.n_genes:
+                raise ValueError(f"expression matrix has {host.shape[1]} gene columns, the bundle {self.n_genes}")
+            rowptr = torch.from_numpy(host.indptr).to(dev)
+            col = torch.from_numpy(host.indices.astype(np.int32, copy=False)).to(dev)
+            raw = torch.from_numpy(host.data.astype(np.float32, copy=False)).to(dev)
+            checked = True
+        nnz = int(col.shape[0])
+        self.last_route = self._route(nnz)
+        if self.last_route == "graph":
+            if host is None:
+                if nnz and (int(col.min()) < 0 or int(col.max()) >= self.n_genes):
+                    raise WgnnError(f"gene id out of range [0, {self.n_genes}) in the batch's CSR")
+                n = rowptr.shape[0] - 1
+                host = sp.csr_matrix((raw.cpu().numpy(), col.cpu().numpy(), rowptr.cpu().numpy()), shape=(n, self.n_genes))
+            host = host.astype(np.float32)
+            logits = _graph_logits(self.model, self.support, host, self.gene_feat, dev)
+            pred, prob = _classify(logits, self.unsure_rate)
+            return pred, prob.max(axis=1) if prob.shape[0] else np.zeros(0, np.float32), logits
+        h = None
+        for l in range(self.n_layers):
+            self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
+            kw = dict(self_rows=self_rows, check_cols=not checked and l == 0)
+            if l < self.n_layers - 1:
+                h = _ops.predict_rows(rowptr, col, raw, self.tables[l], self.alpha, self.biases[l], **kw)
+            else:
+                logits, label, max_prob = _ops.predict_rows(rowptr, col, raw, self.tables[l], self.alpha, self.biases[l],
+                                                            head=(self.w_head, self.b_head),
+                                                            unsure_threshold=self.unsure_threshold, **kw)
+        return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits
+
+    # ---------------------------------------------------------------------------------------------
+    def predict(self, input_file, save_path=None) -> pd.DataFrame:
+        """``DeepSortPredictor.predict`` on the resident bundle: same columns, label-map handling and output file name."""
+        test, index = _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
+        pred, _, _ = self.classify(test)
+        return _prediction_frame(self.species, self.tissue, input_file, index, pred, self.id2label, self.bundle, save_path)
+
+    def predict_many(self, files, save_path=None) -> List[pd.DataFrame]:
+        """One table per test file (``predict.py --test_dataset 1 2 3``), the bundle loaded once."""
+        return [self.predict(f, save_path) for f in files]
+
+    def default_map_file(self) -> Optional[Path]:
+        root = self.bundle.root
+        return next((f for f in (root / "map.xlsx", root.parent / "map" / self.species / "map.xlsx") if f.exists()), None)
+
+    def evaluate(self, data_file, celltype_file, map_file=None, dataset_num=None):
+        """The reference's evaluate mode (predict.py:90-121, its default): predictions scored against the true labels of
+        ``celltype_file`` through ``map.xlsx`` (``get_map_dict``, preprocess.py:14-29).  Returns (correct, total, unsure,
+        acc, DataFrame with an 'original label' column, predict.py:138-143)."""
+        map_file = Path(map_file) if map_file is not None else self.default_map_file()
+        if map_file is None:
+            raise FileNotFoundError(f"no map.xlsx next to the bundle under {self.bundle.root} (pass map_file)")
+        num = int(dataset_num) if dataset_num is not None else dataset_number(data_file, self.tissue)
+        map_dict = load_map_dict(map_file, self.tissue)
+        if num not in map_dict:
+            raise ValueError(f"dataset {num} of tissue {self.tissue!r} is not in {map_file}")
+        ct = pd.read_csv(celltype_file, index_col=0)
+        ct.columns = ['cell', 'type']                                       # preprocess.py:147-150
+        truth = ct['type'].map(str.strip).tolist()
+        test, index = _read_test_csr(data_file, self.file_type, self._gene2id, self.threshold)
+        if len(truth) != test.shape[0]:
+            raise ValueError(f"{celltype_file} lists {len(truth)} cells, {data_file} holds {test.shape[0]}")
+        pred, _, _ = self.classify(test)
+        correct, total, unsure, acc, _ = evaluate_predictions(pred, truth, self.id2label, map_dict[num])
+        out = _prediction_frame(self.species, self.tissue, data_file, index, pred, self.id2label, self.bundle, None,
+                                original=truth)
+        return correct, total, unsure, acc, out

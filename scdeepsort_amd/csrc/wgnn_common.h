@@ -149,6 +149,10 @@ __device__ __forceinline__ void epilogue(const KArgs& a, float4 (&acc)[NV], int 
 }
 
 
+// wgnn_last_error_string's text for `code`, and the failing check of the last wgnn_predict_rows call on this thread (or NULL)
+const char* wgnn_generic_error_string(int code);
+const char* predict_error_detail(int code);
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 

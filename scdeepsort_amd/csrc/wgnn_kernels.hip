@@ -290,6 +290,13 @@ int wgnn_agg_workspace_bytes(int64_t n_partials, int64_t n_src, int32_t D, int a
 }
 
 const char* wgnn_last_error_string(int code) {
+    if (const char* d = wgnn::predict_error_detail(code)) return d;
+    return wgnn::wgnn_generic_error_string(code);
+}
+
+}  // extern "C"
+
+const char* wgnn::wgnn_generic_error_string(int code) {
     switch (code) {
         case WGNN_OK: return "ok";
         case WGNN_ERR_BAD_ARG: return "bad argument (null pointer, negative size or bad enum)";
@@ -301,6 +308,8 @@ const char* wgnn_last_error_string(int code) {
         default: return "unknown error";
     }
 }
+
+extern "C" {
 
 int wgnn_plan_build_host(const int32_t* rowptr, const int32_t* row_ids, int64_t n_rows, int32_t chunk,
                          int32_t* items, int32_t* long_rows, int64_t* n_items, int64_t* n_long, int64_t* n_partials) {

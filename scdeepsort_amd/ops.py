@@ -789,3 +789,89 @@ def linear_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
         return _LinearReluBigM.apply(x, weight, bias)
     out = linear(x, weight, bias)
     return torch.relu(out) if relu else out
+
+
+HEAD_LDS_BYTES = 64 * 1024          # wgnn_predict_rows stages a fused head [C, H] in LDS up to this size
+
+
+def _pad_cols(t: torch.Tensor, width: int) -> torch.Tensor:
+    t = t.float()
+    if t.shape[-1] != width:
+        t = torch.nn.functional.pad(t, (0, width - t.shape[-1]))
+    return t.contiguous()
+
+
+def predict_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
+                 bias: torch.Tensor, *, self_rows: Optional[torch.Tensor] = None,
+                 head: Optional[tuple] = None, unsure_threshold: float = 0.0, want_logits: bool = True,
+                 check_cols: bool = True):
+    """``wgnn_predict_rows``: one layer of a trained model over a batch of test cells given as a device CSR of RAW values
+    (``rowptr`` int32 / int64 [B+1], ``col`` int32 gene ids, ``raw`` f32), against the resident gene table ``table`` [G, H]
+    (H = ``bias.shape[0]`` valid columns).  ``self_rows`` [B, H] = None: the self-loop comes from the row (layer 1);
+    else it is the explicit ``h_{l-1}[c] . W_l^T``.
+
+    Without ``head`` returns ``ReLU(z)`` [B, H].  With ``head = (w_head [C, H], b_head [C])`` returns
+    ``(logits [B, C] | None, label int32 [B], max_prob f32 [B])``; ``label`` is -1 where ``max_prob < unsure_threshold``
+    (pass ``float32(unsure_rate / C)``).  A head wider than the kernel stages in LDS runs as ``linear_fwd`` plus the same
+    softmax rule instead.  Widths that are not a multiple of 4 are zero-padded here (table, bias, head and self columns).
+    ``check_cols``: verify ``0 <= col < G`` (one device reduction and a read-back) - CSRs built by the predictor from a
+    parsed file are in range by construction and skip it."""
+    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, self_rows, *(head or ()))
+    G = table.shape[0]
+    H = bias.shape[0]
+    Hp = -(-H // 4) * 4
+    B = rowptr.shape[0] - 1
+    if table.dim() != 2 or table.shape[1] < H:
+        raise WgnnError(f"table must be [G, >= {H}]")
+    if alpha.numel() != G + 2:
+        raise WgnnError(f"alpha has {alpha.numel()} entries, the table {G} rows (want G + 2)")
+    if col.shape[0] != raw.shape[0]:
+        raise WgnnError(f"col has {col.shape[0]} entries, raw {raw.shape[0]}")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or raw.dtype != torch.float32:
+        raise WgnnError("predict_rows takes rowptr int32 / int64, col int32, raw float32")
+    if check_cols and col.numel():
+        lo, hi = torch.aminmax(col)
+        if int(lo) < 0 or int(hi) >= G:
+            raise WgnnError(f"gene id out of range [0, {G}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+    if Hp != H or table.shape[1] % 4 or table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
+        table = _pad_cols(table[:, :H], Hp)
+    bias = _pad_cols(bias, Hp)
+    alpha = alpha.reshape(-1)
+    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+        alpha = alpha.float().contiguous()
+    if self_rows is not None:
+        if self_rows.shape[0] != B:
+            raise WgnnError(f"self_rows has {self_rows.shape[0]} rows, the batch {B}")
+        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    rowptr = rowptr.contiguous(); col = col.contiguous(); raw = raw.contiguous()
+    w_head = b_head = None
+    fused_head = False
+    if head is not None:
+        w_head, b_head = head
+        n_cls = w_head.shape[0]
+        fused_head = n_cls * Hp * 4 <= HEAD_LDS_BYTES
+    out = None if fused_head else torch.empty((B, Hp), dtype=torch.float32, device=dev)
+    logits = label = max_prob = None
+    if fused_head:
+        w_head = _pad_cols(w_head, Hp)
+        b_head = b_head.float().contiguous()
+        logits = torch.empty((B, n_cls), dtype=torch.float32, device=dev) if want_logits else None
+        label = torch.empty(B, dtype=torch.int32, device=dev)
+        max_prob = torch.empty(B, dtype=torch.float32, device=dev)
+    rc = _lib.call(dev, "wgnn_predict_rows", _ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp,
+                   _ptr(alpha), _ptr(bias), _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
+                   _ptr(out), Hp if out is not None else 0,
+                   _ptr(w_head if fused_head else None), _ptr(b_head if fused_head else None), n_cls if fused_head else 0,
+                   float(unsure_threshold), _ptr(logits), logits.shape[1] if logits is not None else 0, _ptr(label),
+                   _ptr(max_prob), flags, _stream(dev))
+    _lib.check(rc, "wgnn_predict_rows")
+    if head is None:
+        return out if Hp == H else out[:, :H]
+    if fused_head:
+        return logits, label, max_prob
+    # a head too wide for LDS: the GEMM, then the softmax rule of predict.py:78-88 on the [B, C] logits
+    logits = linear_fwd(out, _pad_cols(w_head, Hp), b_head)
+    mx, arg = torch.softmax(logits, dim=1).max(dim=1)
+    label = torch.where(mx < unsure_threshold, torch.full_like(arg, -1), arg).to(torch.int32)
+    return (logits if want_logits else None), label, mx
