@@ -13,7 +13,8 @@ container and EXECUTED over a ~70-line stand-in for the DGL objects it touches (
 ``fn.mean`` with their documented semantics); the resulting logits and normalised edge weights are committed as
 ``tests/golden/refcode_*.npz`` (script: ``tests/golden/make_refcode_golden.py``) and both formulations below reproduce
 them to 2e-6.  What stays restated-from-documentation is DGL's side: ``fn.mean`` = sum over in-edges / in-degree, a
-NodeFlow block = all parent in-edges when expand_factor >= degree, ``edata[...]`` writes through.  Further pins:
+NodeFlow block = all parent in-edges when expand_factor >= degree, ``edata[...]`` writes through.  Sampled NodeFlows
+(``picker``) are pinned the same way, given a recorded draw (``refcode_sampled.npz``).  Further pins:
 hand-derived known answers (tests/golden/kat_*.json), agreement of two independent formulations (edge-list vs CSR),
 algebraic properties, finite-difference gradients.
 
@@ -314,11 +315,12 @@ def csr_forward(sd: Dict[str, torch.Tensor], cg: CsrGraph, features: np.ndarray,
 # training step + post-processing   (train.py:34-36,80-87,106-113; predict.py:78-88)
 # ----------------------------------------------------------------------------
 def loss_and_grads(sd: Dict[str, torch.Tensor], g: RefGraph, features: torch.Tensor, seeds: Sequence[int],
-                   labels: torch.Tensor, n_layers: int, dtype=torch.float64):
+                   labels: torch.Tensor, n_layers: int, dtype=torch.float64, picker=None):
     """CrossEntropyLoss(reduction='sum') on one seed batch and autograd gradients of every
-    parameter (train.py:36,80-84), evaluated through the edge-list formulation."""
+    parameter (train.py:36,80-84), evaluated through the edge-list formulation.  ``picker``: replay a drawn NodeFlow
+    (see ``nodeflow_forward``); None = every in-edge."""
     p = {k: v.detach().clone().to(dtype).requires_grad_(True) for k, v in sd.items()}
-    logits = nodeflow_forward(p, g, features.to(dtype), seeds, n_layers)
+    logits = nodeflow_forward(p, g, features.to(dtype), seeds, n_layers, picker=picker)
     loss = torch.nn.functional.cross_entropy(logits, labels, reduction='sum')
     loss.backward()
     return loss.detach(), {k: v.grad for k, v in p.items()}, logits.detach()

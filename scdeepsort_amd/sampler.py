@@ -16,7 +16,7 @@ from typing import List, Optional, Tuple
 
 import torch
 
-from .graph import AggCsr, CellGeneGraph, device_plan
+from .graph import AggCsr, CellGeneGraph, Plan, device_plan
 
 
 @dataclass
@@ -32,7 +32,7 @@ def sample_block(csr: AggCsr, rows: torch.Tensor, k: int, gen: Optional[torch.Ge
     rows = rows.to(dev).long()
     n = rows.shape[0]
     rp = csr.rowptr.long()
-    beg, deg = rp[rows], rp[rows + 1] - rp[rows]
+    deg = rp[rows + 1] - rp[rows]
     cand = deg + 1                                              # + the self-loop
     off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     torch.cumsum(cand, 0, out=off[1:])
@@ -48,10 +48,21 @@ def sample_block(csr: AggCsr, rows: torch.Tensor, k: int, gen: Optional[torch.Ge
     self_drawn = torch.zeros(n, dtype=torch.float32, device=dev)
     self_drawn[owner[keep & is_self]] = 1.0
     real = keep & ~is_self
-    m_real = torch.bincount(owner[real], minlength=n)
+    return block_from_draw(csr, rows, owner[real], pos[real], self_drawn, k)
+
+
+def block_from_draw(csr: AggCsr, rows: torch.Tensor, owner: torch.Tensor, pos: torch.Tensor, self_drawn: torch.Tensor,
+                    k: int) -> SampledBlock:
+    """The CSR block of a given draw: row j = ``rows[j]`` of ``csr`` keeps the real in-edges at positions ``pos`` (0 .. deg-1
+    inside the parent row) where ``owner == j``; ``owner`` ascends and positions ascend within a row.  ``self_drawn[j]``
+    (float 0 / 1) flags the drawn self-loop, ``k`` bounds the drawn edges per row.  The mean divides by the drawn edges."""
+    dev = csr.device
+    rows = rows.to(dev).long()
+    n = rows.shape[0]
+    m_real = torch.bincount(owner, minlength=n)
     rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     torch.cumsum(m_real, 0, out=rowptr[1:])
-    eidx = (beg[owner] + pos)[real]                            # edge positions in the parent CSR (row-major, ascending)
+    eidx = csr.rowptr.long()[rows][owner] + pos                # edge positions in the parent CSR (row-major, ascending)
     inv = 1.0 / (m_real.float() + self_drawn).clamp(min=1.0)
     rowptr32 = rowptr.to(torch.int32)
     bound = max(1, min(int(k), csr.max_row_nnz))               # host-known bound on the drawn row length
@@ -79,7 +90,7 @@ def sample_block_static(csr: AggCsr, rows: Optional[torch.Tensor], k: int, sampl
     """K5 (``wgnn_sample_rows``): draw min(k, deg+1) of the deg+1 in-edges of every row in ``rows`` (None = all rows) with
     static output shapes and no host synchronisation.  The block is an ELL-padded ``AggCsr`` (``ell_k`` slots per row)."""
     from . import _lib
-    from .graph import _ptr, _stream, Plan
+    from .graph import _ptr, _stream
     dev = csr.device
     kk = max(1, min(int(k), csr.max_row_nnz + 1))               # host-known bound on the draws per row (same draw law)
     if kk > 256:
@@ -97,13 +108,23 @@ def sample_block_static(csr: AggCsr, rows: Optional[torch.Tensor], k: int, sampl
     _lib.check(_lib.call(dev, "wgnn_sample_rows", _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.val), _ptr(ids32), n, kk,
                          sampler.seed, _ptr(sampler.step), int(stream_id), _ptr(out_col), _ptr(out_val), _ptr(cnt),
                          _ptr(self_drawn), _ptr(inv), _stream(dev)), "wgnn_sample_rows")
+    return ell_block_from_draw(csr, rows_l, kk, out_col, out_val, cnt, self_drawn, inv)
+
+
+def ell_block_from_draw(csr: AggCsr, rows: torch.Tensor, kk: int, out_col: torch.Tensor, out_val: torch.Tensor,
+                        cnt: torch.Tensor, self_drawn: torch.Tensor, inv: torch.Tensor) -> SampledBlock:
+    """The ELL block of a given draw in K5's output layout: row j = ``rows[j]`` of ``csr`` owns ``out_col`` / ``out_val``
+    [j * kk, j * kk + cnt[j]) (int32 / float32, at least ``len(rows) * kk`` entries), ``self_drawn`` (float 0 / 1) and
+    ``inv`` = 1 / max(1, cnt + self_drawn) per row."""
+    dev = csr.device
+    n = rows.shape[0]
     slot = torch.arange(n, device=dev, dtype=torch.int32)
     items = torch.stack([slot, slot * kk, slot * kk + cnt, torch.full_like(slot, -1)], 1).contiguous()
     starts = torch.arange(n + 1, device=dev, dtype=torch.int32) * kk
     sub = AggCsr(starts, out_col[: n * kk], out_val[: n * kk], inv, n, csr.n_cols,
                  Plan(items, torch.empty((0, 4), dtype=torch.int32, device=dev), 0, kk), None, ell_k=kk, ell_cnt=cnt)
     sub._max_row_nnz = kk
-    return SampledBlock(rows_l, sub, self_drawn)
+    return SampledBlock(rows, sub, self_drawn)
 
 
 def sample_nodeflow_static(g: CellGeneGraph, seed_cells: torch.Tensor, n_layers: int, k: int,

@@ -225,6 +225,62 @@ def test_full_batch_gradient_oracle_matches_executed_reference_code(name):
         np.testing.assert_allclose(gval.numpy(), z["fullgrad." + k], atol=3e-6, rtol=1e-5, err_msg=k)
 
 
+# ---- neighbour-sampled NodeFlows (num_neighbors > 0, train.py:37-40): refcode_sampled.npz holds recorded draws and what the
+# reference's own GNN.forward computed over them
+SAMPLED_CASES = ["L1k3", "L2k1", "L2k3", "L2k7"]
+
+
+def _sampled_case(prefix):
+    z = np.load(GOLDEN / "refcode_sampled.npz")
+    sd = {k[len(prefix) + 7:]: torch.from_numpy(z[k]) for k in z.files if k.startswith(prefix + ".param.")}
+    draw = {}
+    for b, d, s in zip(z[prefix + ".draw_block"], z[prefix + ".draw_dst"], z[prefix + ".draw_src"]):
+        draw.setdefault((int(b), int(d)), []).append(int(s))
+    return z, sd, draw
+
+
+def test_sampled_fixture_holds_every_case():
+    z = np.load(GOLDEN / "refcode_sampled.npz")
+    assert list(z["cases"]) == SAMPLED_CASES
+    assert int(z["dim"]) % 4 and int(z["hidden"]) % 4              # both widths are padded by the HIP path
+
+
+@pytest.mark.parametrize("prefix", SAMPLED_CASES)
+def test_oracle_replays_the_executed_reference_draw(prefix, monkeypatch):
+    """The oracle's NodeFlow, replaying the recorded draw through ``picker``, uses exactly the recorded edges per block and
+    reproduces the logits the reference's own GNN.forward computed over that draw."""
+    z, sd, draw = _sampled_case(prefix)
+    L = int(z[prefix + ".n_layers"])
+    rg = O.build_reference_graph(sp.csr_matrix(z["expr"]), z["support_mask"])
+    used = []
+    real_of = O._InEdges.of
+
+    def recording(self, nodes, rng, num_neighbors, picker=None, block=0):
+        s, d, w = real_of(self, nodes, rng, num_neighbors, picker, block)
+        used.extend((block, int(nodes[j]), int(v)) for j, v in zip(d, s))
+        return s, d, w
+    monkeypatch.setattr(O._InEdges, "of", recording)
+    logits = O.nodeflow_forward(sd, rg, torch.from_numpy(z["feats"]), z[prefix + ".seeds"], L,
+                                picker=lambda block, v: np.array(draw[(block, v)])).numpy()
+    want = sorted(zip(z[prefix + ".draw_block"].tolist(), z[prefix + ".draw_dst"].tolist(), z[prefix + ".draw_src"].tolist()))
+    assert sorted(used) == want
+    np.testing.assert_allclose(logits, z[prefix + ".logits"], atol=2e-6)
+
+
+@pytest.mark.parametrize("prefix", SAMPLED_CASES)
+def test_gradient_oracle_matches_executed_reference_code_on_a_drawn_nodeflow(prefix):
+    z, sd, draw = _sampled_case(prefix)
+    rg = O.build_reference_graph(sp.csr_matrix(z["expr"]), z["support_mask"])
+    loss, grads, _ = O.loss_and_grads(sd, rg, torch.from_numpy(z["feats"]), z[prefix + ".seeds"],
+                                      torch.from_numpy(z[prefix + ".labels"]), int(z[prefix + ".n_layers"]),
+                                      picker=lambda block, v: np.array(draw[(block, v)]))
+    ref = float(z[prefix + ".loss"])
+    assert abs(float(loss) - ref) < 1e-5 * max(1.0, abs(ref))
+    assert grads.keys() == sd.keys()
+    for k, gval in grads.items():
+        np.testing.assert_allclose(gval.numpy(), z[f"{prefix}.grad.{k}"], atol=3e-6, rtol=1e-5, err_msg=k)
+
+
 def _kat_rational():
     import json
     kat = json.loads((GOLDEN / "kat_2layer_predict.json").read_text())
