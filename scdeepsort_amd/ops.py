@@ -187,11 +187,13 @@ def agg_fwd(csr: AggCsr, alpha: Optional[torch.Tensor], mode: int, self_idx: int
 def agg_bwd_src(csr: AggCsr, alpha: Optional[torch.Tensor], mode: int, g: torch.Tensor,
                 h_src: Optional[torch.Tensor], dalpha: Optional[torch.Tensor] = None,
                 dh_src: Optional[torch.Tensor] = None, accumulate: bool = False,
-                dst_scale: Optional[torch.Tensor] = None, prescaled: bool = False) -> torch.Tensor:
+                dst_scale: Optional[torch.Tensor] = None, prescaled: bool = False, tplan=None) -> torch.Tensor:
     """K2 ``wgnn_agg_bwd_src``: gradient w.r.t. the gathered rows (transposed SpMM);
     for SRC_IS_GENE also writes dalpha[0:n_src] = <h_src[s], T[s]>.  ``dst_scale`` replaces the per-destination
     factor 1/(deg+1) (``csr.inv_deg``), e.g. ones for the backward of a plain weighted sum.  ``prescaled``: ``g`` already
-    carries the per-destination factors (``agg_bwd_prepare``) - LDS-streamed route only."""
+    carries the per-destination factors (``agg_bwd_prepare``) - LDS-streamed route only.  ``tplan``: a tile plan of
+    ``csr.transposed()`` (``graph.build_tile_plan``) - the LDS-streamed K2t then runs over it, whatever the dispatch rule
+    says (default: the rule decides, and K2t takes the cached heuristic plan)."""
     dev = _require_cuda(g, h_src, alpha)
     inv_deg = csr.inv_deg if dst_scale is None else dst_scale.float().contiguous()
     t = csr.transposed()
@@ -206,9 +208,9 @@ def agg_bwd_src(csr: AggCsr, alpha: Optional[torch.Tensor], mode: int, g: torch.
         h_src = _rowmajor(h_src.float())
     if alpha is not None:
         alpha = alpha.reshape(-1).float().contiguous()
-    if tiled_kernel_serves(csr, D):
+    if tplan is not None or tiled_kernel_serves(csr, D):
         # K2t: LDS-streamed kernel over the transposed structure; per-destination factors folded into g once
-        tp = t.tile_plan(tiled_block_rows(D))
+        tp = tplan if tplan is not None else t.tile_plan(tiled_block_rows(D))
         g = g.contiguous()
         if prescaled:
             scale, scratch = None, None
@@ -269,8 +271,10 @@ def agg_bwd_src_block(csr: AggCsr, row_ids: torch.Tensor, alpha: Optional[torch.
 
 
 def agg_bwd_alpha(csr: AggCsr, g: torch.Tensor, h_src: torch.Tensor, h_self: Optional[torch.Tensor],
-                  row_ids: Optional[torch.Tensor] = None, self_compact: bool = False):
-    """K3 ``wgnn_agg_bwd_alpha``: per-row alpha gradients for DST_IS_GENE rows and the self-loop scalar."""
+                  row_ids: Optional[torch.Tensor] = None, self_compact: bool = False, tplan=None):
+    """K3 ``wgnn_agg_bwd_alpha``: per-row alpha gradients for DST_IS_GENE rows and the self-loop scalar.  ``tplan``: a tile
+    plan of ``csr`` (``graph.build_tile_plan``; all rows only) - the LDS-streamed K3t then runs over it, whatever the
+    dispatch rule says."""
     dev = _require_cuda(g, h_src, h_self)
     g = _rowmajor(g.float()); h_src = _rowmajor(h_src.float())
     D = g.shape[1]
@@ -283,8 +287,10 @@ def agg_bwd_alpha(csr: AggCsr, g: torch.Tensor, h_src: torch.Tensor, h_self: Opt
         h_self = _rowmajor(h_self.float())
     d_row = torch.empty(n_out, dtype=torch.float32, device=dev)
     d_self = torch.empty(n_out, dtype=torch.float32, device=dev) if h_self is not None else None
-    if row_ids is None and tiled_kernel_serves(csr, D):
-        tp = csr.tile_plan(tiled_block_rows(D))                                   # K3t
+    if tplan is not None and row_ids is not None:
+        raise WgnnError("a tile plan covers all rows: K3t takes no row_ids")
+    if row_ids is None and (tplan is not None or tiled_kernel_serves(csr, D)):
+        tp = tplan if tplan is not None else csr.tile_plan(tiled_block_rows(D))   # K3t
         h_src = h_src.contiguous()
         part = torch.empty(tp.n_partials * D, dtype=torch.float32, device=dev) if tp.n_partials else None
         n_long = tp.long_rows.shape[0]

@@ -535,7 +535,8 @@ def test_sharded_train_step_world1_matches_plain_autograd():
 
 
 def test_tiled_backward_kernels_match_rowwave():
-    """K2t / K3t (LDS-streamed) == K2 / K3 (row-wave) on the same inputs, both alpha modes, incl. dalpha."""
+    """K2t / K3t (LDS-streamed) == K2 / K3 (row-wave) on the same inputs, both alpha modes, incl. dalpha.
+    The row-wave kernels themselves are pinned to fp64 in tests/test_gpu_backward_ops.py."""
     from scdeepsort_amd import ops, synthetic as S
     G, C, D = 500, 3000, 256
     rp, col, val = S.synth_expression(C, G, 0.1, device=DEV)
@@ -1837,7 +1838,8 @@ def test_tall_tile_kernel_matches_the_oracle_and_the_flat_kernel(D):
     plan bit WGNN_PLAN_TALL; opt-in through `graph.TILE_TALL`, see there for why).  Forward in both directions with explicit and
     heuristic geometries, column splits, several LDS block heights incl. segments of more than four chunks (the on-demand chunk
     path), D = 200 (global rows shorter than their LDS slots: the one-piece DMA form) - against the oracle; and the backward
-    entries K2t / K3t with TILE_TALL = "on" against the row-wave kernels."""
+    entries K2t / K3t with TILE_TALL = "on" against the row-wave kernels.
+    The row-wave kernels themselves are pinned to fp64 in tests/test_gpu_backward_ops.py."""
     from scdeepsort_amd.graph import build_tile_plan
     from scdeepsort_amd import ops, graph as GR
     c = small_case(cells=1900, genes=420, dim=D, seed=D + 5, density=0.3, test_cells=40)
@@ -2089,7 +2091,8 @@ def test_tile_kernel_packed_lds_rows_at_full_block_height(D, direction):
     """Round 4: the flat tile kernel's LDS rows are 256 / 512 / 1024 bytes by width (512 B at D = 128 instead of a 1 KiB slot),
     and `ops.tiled_block_rows(D)` fills the 160 KiB of a CU with them: 255 / 156 / 78 source rows per block.  Every
     stride at its full block height (several blocks per tile, column splits, loader wave, shared pairs), forward and the
-    two backward entries, against the oracle / the row-wave kernels."""
+    two backward entries, against the oracle / the row-wave kernels.
+    The row-wave kernels themselves are pinned to fp64 in tests/test_gpu_backward_ops.py."""
     from scdeepsort_amd.graph import build_tile_plan
     from scdeepsort_amd import ops
     kb = ops.tiled_block_rows(D)
@@ -2528,7 +2531,8 @@ def test_joint_projection_of_one_feature_table_matches_separate_projections():
 def test_device_built_transpose_cuts_only_the_hub_source():
     """the source-major (transposed) copy of a device-built block - the backward structure of sampled training - cuts only
     sources longer than the chunk (here ONE hub gene drawn by all 3000 seed cells) into parts on static hub slots; every other source
-    keeps one item and no partial rows.  K2 over it against a dense evaluation of the same block."""
+    keeps one item and no partial rows.  K2 over it against a dense evaluation of the same block.
+    The row-wave backward kernels are pinned to fp64 at every width, mode and option in tests/test_gpu_backward_ops.py."""
     from scdeepsort_amd import ops
     from scdeepsort_amd.sampler import sample_block
     rng = np.random.default_rng(3)
