@@ -463,6 +463,45 @@ int wgnn_predict_rows(const void* rowptr, const int32_t* col, const float* raw, 
                       float* logits, int64_t ld_logits, int32_t* label, float* max_prob,
                       uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Per-cell gene attribution on the resident tables (additive exports, WGNN_VERSION stays 206).  For one test cell with the
+ * ReLU pattern m_l = (z_l > 0) fixed, the target logit is linear in the cell's per-gene message weights
+ *     u_j = x_j (alpha[g_j] deg / S + alpha[G+1] / (S + 1e-6)) / (deg + 1)      self-loop from the row (layer 1)
+ *     u_j = alpha[g_j] (deg x_j / S) / (deg + 1)                                explicit-self layers (l >= 2)
+ * and splits exactly: logit_t = sum_j phi_j + base, phi_j = sum_l u_{l,j} <T_l[g_j], v_l>, base = bh[t] + sum_l <v_l, b_l>, with
+ *     v_L = m_L * Wh[t] ,   v_{l-1} = m_{l-1} * (W_l^T v_l) * alpha[G+1] / (deg + 1)         (the caller's small [B, H] step).
+ *
+ * wgnn_attrib_rows, one wavefront per cell, deterministic (no atomics, fixed fold order).  rowptr / col / raw / table / alpha /
+ * n_genes / H / ld_table as wgnn_predict_rows (H % 4 == 0, H <= 256).  score f32 [nnz], in the CSR order of the batch.
+ *   Head mode (w_head != NULL, direction == NULL; the model's last layer): bias, self_rows, w_head [C, H], b_head, C as
+ *     wgnn_predict_rows with a head (C * H * 4 <= 64 KiB).  The gather is wgnn_predict_rows' own, operation for operation: the
+ *     logits and the arg max carry the bits of that call.  target int32 [B] or NULL (= the arg max, lowest index among equal
+ *     maxima, also for a cell wgnn_predict_rows would label -1); the caller checks 0 <= target < C (the kernel clamps).
+ *       target_out [B] = t,  logit_out [B] = logit_t,  base_out [B] = b_head[t] + <v, bias>,  score[j] = u_j <table[g_j], v>
+ *       dir_out [B, ld_dir_out] = v = (z > 0) * w_head[t]    (may be NULL)
+ *       label_out [B] = wgnn_predict_rows' label for unsure_threshold (arg max, or -1; whatever `target` says; may be NULL)
+ *     With self_rows the logit also holds alpha[G+1] <self_rows[c], v> / (deg + 1): the share the layers below split further.
+ *   Direction mode (w_head == NULL, direction [B, ld_dir] given; layers below the last): score[j] = u_j <table[g_j], direction[c]>,
+ *     added to score[j] with WGNN_ATTRIB_ACCUMULATE (a row is owned by one wave).  WGNN_ATTRIB_EXPLICIT_SELF selects the
+ *     second coefficient rule.  bias, self_rows, the head and the *_out arrays are ignored.
+ *   flags: WGNN_FLAG_ROWPTR_I64 | WGNN_ATTRIB_ACCUMULATE | WGNN_ATTRIB_EXPLICIT_SELF (the last two in direction mode only).
+ *
+ * wgnn_rows_topk: per row of a CSR with f32 scores the k (1..64) entries with the largest score, descending, equal scores by
+ * the lower CSR position: gene_out int32 [B, k] = their col (-1 where the row has fewer than k entries), score_out f32 [B, k]
+ * (0 there).  One wavefront per row, deterministic, `score` is only read.  flags: WGNN_FLAG_ROWPTR_I64 or 0.
+ * ------------------------------------------------------------------------- */
+#define WGNN_ATTRIB_ACCUMULATE 256
+#define WGNN_ATTRIB_EXPLICIT_SELF 512
+int wgnn_attrib_rows(const void* rowptr, const int32_t* col, const float* raw, int64_t n_rows,
+                     const float* table, int64_t ld_table, int32_t n_genes, int32_t H,
+                     const float* alpha, const float* bias, const float* self_rows, int64_t ld_self,
+                     const float* w_head, const float* b_head, int32_t n_classes, const int32_t* target,
+                     float unsure_threshold, int32_t* label_out, const float* direction, int64_t ld_dir,
+                     float* score, int32_t* target_out, float* logit_out, float* base_out,
+                     float* dir_out, int64_t ld_dir_out, uint32_t flags, void* stream);
+int wgnn_rows_topk(const void* rowptr, const int32_t* col, const float* score, int64_t n_rows, int32_t k,
+                   int32_t* gene_out, float* score_out, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import os
 import re
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
 
@@ -513,6 +514,26 @@ def dataset_number(data_file, tissue: str) -> int:
     return int(m.group(1))
 
 
+@dataclass
+class Attribution:
+    """What ``ResidentPredictor.explain`` returns for a batch of B cells.  ``label`` as ``classify`` gives it (-1 = unsure),
+    ``target`` the class explained, ``logit`` its logit, ``base`` the bias share (numpy, [B]); ``scores`` the per-entry
+    shares (device f32 [nnz], in the CSR order of the batch): ``sum(scores of a cell) + base == logit``.  ``top_genes``
+    [B, k] gene ids by descending score (-1 where a cell expresses fewer than k genes), ``top_scores`` [B, k] (0 there)."""
+    label: np.ndarray
+    target: np.ndarray
+    logit: np.ndarray
+    base: np.ndarray
+    scores: torch.Tensor
+    top_genes: np.ndarray
+    top_scores: np.ndarray
+    id2gene: Sequence[str] = field(default=(), repr=False)
+
+    def gene_names(self, i: int) -> List[str]:
+        """The names of cell ``i``'s top genes, best first (shorter than k when the cell expresses fewer genes)."""
+        return [self.id2gene[g] for g in self.top_genes[i] if g >= 0]
+
+
 class ResidentPredictor:
     """A trained bundle loaded ONCE, its gene side resident on the GPU, classifying any batch of test cells.
 
@@ -592,22 +613,27 @@ class ResidentPredictor:
         with torch.cuda.device(self.device), torch.no_grad():
             return self._classify(expr)
 
-    def _classify(self, expr):
+    def _device_csr(self, expr):
+        """A batch as the kernels take it: (rowptr, col int32, raw f32) on the device, whether its gene ids are in range by
+        construction, and the host CSR when the batch came as one."""
         dev = self.device
         if isinstance(expr, (tuple, list)):
             rowptr, col, raw = expr
             _ops._require_cuda(rowptr, col, raw)
             rowptr = rowptr if rowptr.dtype in (torch.int32, torch.int64) else rowptr.long()
             col, raw = col.to(torch.int32), raw.to(torch.float32)
-            checked, host = False, None
-        else:
-            host = sp.csr_matrix(expr)
-            if host.shape[1] != self.n_genes:
-                raise ValueError(f"expression matrix has {host.shape[1]} gene columns, the bundle {self.n_genes}")
-            rowptr = torch.from_numpy(host.indptr).to(dev)
-            col = torch.from_numpy(host.indices.astype(np.int32, copy=False)).to(dev)
-            raw = torch.from_numpy(host.data.astype(np.float32, copy=False)).to(dev)
-            checked = True
+            return rowptr, col, raw, False, None
+        host = sp.csr_matrix(expr)
+        if host.shape[1] != self.n_genes:
+            raise ValueError(f"expression matrix has {host.shape[1]} gene columns, the bundle {self.n_genes}")
+        rowptr = torch.from_numpy(host.indptr).to(dev)
+        col = torch.from_numpy(host.indices.astype(np.int32, copy=False)).to(dev)
+        raw = torch.from_numpy(host.data.astype(np.float32, copy=False)).to(dev)
+        return rowptr, col, raw, True, host
+
+    def _classify(self, expr):
+        dev = self.device
+        rowptr, col, raw, checked, host = self._device_csr(expr)
         nnz = int(col.shape[0])
         self.last_route = self._route(nnz)
         if self.last_route == "graph":
@@ -633,11 +659,98 @@ class ResidentPredictor:
         return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits
 
     # ---------------------------------------------------------------------------------------------
+    def explain(self, expr, top_k: int = 10, target="predicted") -> "Attribution":
+        """Which genes made the model say so: the target logit of every cell split, without approximation, into one share
+        per expressed gene plus a bias share (``sum(scores of the cell) + base == logit``; ``include/wgnn.h``,
+        ``wgnn_attrib_rows``).  ``expr`` as ``classify`` takes it.  ``target``: ``"predicted"`` (the arg max, also for a
+        cell that comes out unsure), a class id, a label string, or one class id per cell.  ``top_k`` in 0..64: the
+        highest-scoring genes per cell (0 = scores only).  Cells are independent, so there is no graph route."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._explain(expr, top_k, target)
+
+    def _target_ids(self, target, n_cells: int) -> Optional[torch.Tensor]:
+        """``explain``'s ``target`` as None (the predicted class) or an int32 device vector with one class per cell."""
+        if isinstance(target, str):
+            if target == "predicted":
+                return None
+            if target not in self.id2label:
+                raise ValueError(f"target {target!r} is not a cell type of this bundle ({len(self.id2label)} types)")
+            target = self.id2label.index(target)
+        if isinstance(target, (int, np.integer)):
+            ids = np.full(n_cells, int(target), np.int64)
+        else:
+            ids = (target.detach().cpu().numpy() if isinstance(target, torch.Tensor) else np.asarray(target)).astype(np.int64)
+            if ids.shape != (n_cells,):
+                raise ValueError(f"target lists {ids.shape} classes, the batch holds {n_cells} cells")
+        if ids.size and (ids.min() < 0 or ids.max() >= self.n_classes):
+            raise ValueError(f"target class out of range [0, {self.n_classes})")
+        return torch.from_numpy(ids.astype(np.int32)).to(self.device)
+
+    def _explain(self, expr, top_k, target):
+        if not 0 <= int(top_k) <= 64:
+            raise ValueError(f"top_k = {top_k} is outside [0, 64]")
+        Hp, L = self.hidden_padded, self.n_layers
+        if Hp > 256:
+            raise WgnnError(f"explain: hidden width {self.hidden} > 256 is not built (WGNN_ERR_UNSUPPORTED)")
+        if self.n_classes * Hp * 4 > _ops.HEAD_LDS_BYTES:
+            raise WgnnError(f"explain: a [{self.n_classes}, {Hp}] head does not fit the kernel's LDS (WGNN_ERR_UNSUPPORTED)")
+        rowptr, col, raw, checked, _ = self._device_csr(expr)
+        if int(col.shape[0]) >= 2 ** 31:
+            raise WgnnError("explain: nnz >= 2^31 (split the batch)")
+        B = rowptr.shape[0] - 1
+        tgt = self._target_ids(target, B)
+        # forward below the last layer (h_1 .. h_{L-1}), then the last layer's head-mode launch
+        hs = []
+        for l in range(L - 1):
+            self_rows = None if l == 0 else _ops.linear_fwd(hs[-1], self.self_weights[l])
+            hs.append(_ops.predict_rows(rowptr, col, raw, self.tables[l], self.alpha, self.biases[l], self_rows=self_rows,
+                                        check_cols=not checked and l == 0))
+        self_rows = None if L == 1 else _ops.linear_fwd(hs[-1], self.self_weights[L - 1])
+        scores, t_out, logit, base, label, v = _ops.attrib_rows(
+            rowptr, col, raw, self.tables[L - 1], self.alpha, self.biases[L - 1], head=(self.w_head, self.b_head), target=tgt,
+            self_rows=self_rows, unsure_threshold=self.unsure_threshold, want_direction=L > 1,
+            check_cols=not checked and L == 1)
+        if L > 1:
+            deg = (rowptr[1:] - rowptr[:-1]).to(torch.float32)
+            back = (self.alpha[self.n_genes + 1] / (deg + 1.0)).unsqueeze(1)
+            widen = lambda t: t if t.shape[1] == Hp else F.pad(t, (0, Hp - t.shape[1]))      # the tables' padded width
+            v = widen(v)
+            for l in range(L - 1, 0, -1):                    # v_l = (h_l > 0) * (v_{l+1} . W_{l+1}) * alpha[G+1] / (deg + 1)
+                v = widen(hs[l - 1] > 0) * _ops.linear_fwd(v.contiguous(), self.self_weights[l].t().contiguous()) * back
+                base = base + (v * self.biases[l - 1]).sum(dim=1)
+                _ops.attrib_rows(rowptr, col, raw, self.tables[l - 1], self.alpha, self.biases[l - 1], direction=v,
+                                 scores=scores, accumulate=True, explicit_self=l > 1, check_cols=False)
+        if int(top_k) > 0:
+            top_genes, top_scores = _ops.rows_topk(rowptr, col, scores, int(top_k))
+            top_genes, top_scores = top_genes.cpu().numpy().astype(np.int64), top_scores.cpu().numpy()
+        else:
+            top_genes, top_scores = np.zeros((B, 0), np.int64), np.zeros((B, 0), np.float32)
+        return Attribution(label=label.cpu().numpy().astype(np.int64), target=t_out.cpu().numpy().astype(np.int64),
+                           logit=logit.cpu().numpy(), base=base.cpu().numpy(), scores=scores, top_genes=top_genes,
+                           top_scores=top_scores, id2gene=self.id2gene)
+
     def predict(self, input_file, save_path=None) -> pd.DataFrame:
         """``DeepSortPredictor.predict`` on the resident bundle: same columns, label-map handling and output file name."""
         test, index = _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
         pred, _, _ = self.classify(test)
         return _prediction_frame(self.species, self.tissue, input_file, index, pred, self.id2label, self.bundle, save_path)
+
+    def explain_file(self, input_file, top_k: int = 10, save_path=None) -> pd.DataFrame:
+        """``explain`` on a test file, in long form: one row per (cell, rank) with the columns ``index``, ``cell_type`` (and
+        ``cell_subtype`` with a label map, as ``predict`` names them), ``rank`` (1 = highest score), ``gene``, ``score``.
+        Written as ``{species}_{tissue}_{stem}_genes.csv`` under ``save_path`` when given."""
+        test, index = _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
+        att = self.explain(test, top_k=top_k)
+        cells = _prediction_frame(self.species, self.tissue, input_file, index, att.label, self.id2label, self.bundle, None)
+        r, k = np.nonzero(att.top_genes >= 0)
+        out = cells.iloc[r].reset_index(drop=True)
+        out["rank"] = k + 1
+        out["gene"] = [self.id2gene[g] for g in att.top_genes[r, k]]
+        out["score"] = att.top_scores[r, k]
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_{Path(input_file).stem}_genes.csv", index=False)
+        return out
 
     def predict_many(self, files, save_path=None) -> List[pd.DataFrame]:
         """One table per test file (``predict.py --test_dataset 1 2 3``), the bundle loaded once."""

@@ -881,3 +881,129 @@ def predict_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tab
     mx, arg = torch.softmax(logits, dim=1).max(dim=1)
     label = torch.where(mx < unsure_threshold, torch.full_like(arg, -1), arg).to(torch.int32)
     return (logits if want_logits else None), label, mx
+
+
+def _attrib_common(name, rowptr, col, raw, table, alpha, H, check_cols):
+    """The batch / table handling ``predict_rows`` does, shared by ``attrib_rows``: returns (table, alpha, G, Hp, B, flags,
+    rowptr, col, raw) ready for the C call."""
+    G = table.shape[0]
+    Hp = -(-H // 4) * 4
+    B = rowptr.shape[0] - 1
+    if table.dim() != 2 or table.shape[1] < H:
+        raise WgnnError(f"table must be [G, >= {H}]")
+    if alpha.numel() != G + 2:
+        raise WgnnError(f"alpha has {alpha.numel()} entries, the table {G} rows (want G + 2)")
+    if col.shape[0] != raw.shape[0]:
+        raise WgnnError(f"col has {col.shape[0]} entries, raw {raw.shape[0]}")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or raw.dtype != torch.float32:
+        raise WgnnError(f"{name} takes rowptr int32 / int64, col int32, raw float32")
+    if col.shape[0] >= 2 ** 31:
+        raise WgnnError(f"{name}: nnz >= 2^31 (split the batch)")
+    if check_cols and col.numel():
+        lo, hi = torch.aminmax(col)
+        if int(lo) < 0 or int(hi) >= G:
+            raise WgnnError(f"gene id out of range [0, {G}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+    if Hp != H or table.shape[1] % 4 or table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
+        table = _pad_cols(table[:, :H], Hp)
+    alpha = alpha.reshape(-1)
+    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+        alpha = alpha.float().contiguous()
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    return table, alpha, G, Hp, B, flags, rowptr.contiguous(), col.contiguous(), raw.contiguous()
+
+
+def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
+                bias: torch.Tensor, *, head: Optional[tuple] = None, target: Optional[torch.Tensor] = None,
+                self_rows: Optional[torch.Tensor] = None, direction: Optional[torch.Tensor] = None,
+                scores: Optional[torch.Tensor] = None, accumulate: bool = False, want_direction: bool = False,
+                unsure_threshold: float = 0.0, explicit_self: Optional[bool] = None, check_cols: bool = True):
+    """``wgnn_attrib_rows``: per-entry attribution scores of one layer over a batch given as ``predict_rows`` takes it
+    (``include/wgnn.h``).  ``H = bias.shape[0]`` valid columns; other widths are zero-padded here.
+
+    Head mode, ``head = (w_head [C, H], b_head [C])`` (the model's last layer): the gather of ``predict_rows`` with the same
+    bits, then ``score[j] = u_j <table[g_j], v>`` with ``v = (z > 0) * w_head[t]``.  ``target`` int [B] in ``[0, C)`` (checked
+    here with one ``aminmax``) or None = the class ``predict_rows`` picks.  Returns ``(scores f32 [nnz], target int32 [B],
+    logit f32 [B], base f32 [B], label int32 [B], v [B, H] | None)``: ``label`` as ``predict_rows`` gives it for
+    ``unsure_threshold``, ``v`` only with ``want_direction``.  A head wider than the kernel stages
+    in LDS raises ``WgnnError``.
+
+    Direction mode, ``direction [B, H]`` (layers below the last): ``score[j] = u_j <table[g_j], direction[c]>``, written into
+    ``scores`` (allocated when None) or added to it with ``accumulate``.  ``explicit_self`` picks the coefficient rule of
+    layers with an explicit self term (default: ``self_rows is not None``).  Returns ``scores``."""
+    if (head is None) == (direction is None):
+        raise WgnnError("attrib_rows takes either head= (last layer) or direction= (layers below it)")
+    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, self_rows, target, direction, scores, *(head or ()))
+    H = bias.shape[0]
+    table, alpha, G, Hp, B, flags, rowptr, col, raw = _attrib_common("attrib_rows", rowptr, col, raw, table, alpha, H, check_cols)
+    nnz = col.shape[0]
+    if scores is None:
+        if accumulate:
+            raise WgnnError("accumulate needs the scores to add to")
+        scores = torch.empty(nnz, dtype=torch.float32, device=dev)
+    elif scores.dtype != torch.float32 or scores.shape != (nnz,) or not scores.is_contiguous():
+        raise WgnnError(f"scores must be a contiguous float32 [{nnz}]")
+    if head is None:
+        if direction.shape[0] != B or direction.shape[1] < H:
+            raise WgnnError(f"direction must be [{B}, >= {H}]")
+        direction = _rowmajor(direction.float()) if direction.shape[1] == Hp else _pad_cols(direction[:, :H], Hp)
+        if explicit_self is None:
+            explicit_self = self_rows is not None
+        flags |= (_lib.ATTRIB_ACCUMULATE if accumulate else 0) | (_lib.ATTRIB_EXPLICIT_SELF if explicit_self else 0)
+        rc = _lib.call(dev, "wgnn_attrib_rows", _ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp,
+                       _ptr(alpha), None, None, 0, None, None, 0, None, 0.0, None, _ptr(direction), direction.stride(0),
+                       _ptr(scores), None, None, None, None, 0, flags, _stream(dev))
+        _lib.check(rc, "wgnn_attrib_rows")
+        return scores
+    if accumulate:
+        raise WgnnError("head mode overwrites the scores")
+    w_head, b_head = head
+    n_cls = w_head.shape[0]
+    if n_cls * Hp * 4 > HEAD_LDS_BYTES:
+        raise WgnnError(f"attrib_rows: a [{n_cls}, {Hp}] head does not fit the {HEAD_LDS_BYTES >> 10} KiB the kernel stages in LDS")
+    bias = _pad_cols(bias, Hp)
+    w_head = _pad_cols(w_head, Hp)
+    b_head = b_head.float().contiguous()
+    if self_rows is not None:
+        if self_rows.shape[0] != B:
+            raise WgnnError(f"self_rows has {self_rows.shape[0]} rows, the batch {B}")
+        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
+    if target is not None:
+        if target.shape != (B,):
+            raise WgnnError(f"target must hold one class per cell ([{B}])")
+        if B:
+            lo, hi = torch.aminmax(target)
+            if int(lo) < 0 or int(hi) >= n_cls:
+                raise WgnnError(f"target class out of range [0, {n_cls}) (min {int(lo)}, max {int(hi)})")
+        target = target.to(torch.int32).contiguous()
+    target_out = torch.empty(B, dtype=torch.int32, device=dev)
+    logit = torch.empty(B, dtype=torch.float32, device=dev)
+    base = torch.empty(B, dtype=torch.float32, device=dev)
+    label = torch.empty(B, dtype=torch.int32, device=dev)
+    v = torch.empty((B, Hp), dtype=torch.float32, device=dev) if want_direction else None
+    rc = _lib.call(dev, "wgnn_attrib_rows", _ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp,
+                   _ptr(alpha), _ptr(bias), _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
+                   _ptr(w_head), _ptr(b_head), n_cls, _ptr(target), float(unsure_threshold), _ptr(label), None, 0,
+                   _ptr(scores), _ptr(target_out), _ptr(logit), _ptr(base), _ptr(v), Hp if v is not None else 0,
+                   flags, _stream(dev))
+    _lib.check(rc, "wgnn_attrib_rows")
+    return scores, target_out, logit, base, label, (v if v is None or Hp == H else v[:, :H])
+
+
+def rows_topk(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Tensor, k: int):
+    """``wgnn_rows_topk``: per CSR row the ``k`` (1..64) entries with the largest score, descending, equal scores by the lower
+    CSR position.  Returns ``(gene int32 [B, k], score f32 [B, k])``: -1 / 0 where a row has fewer than ``k`` entries."""
+    dev = _require_cuda(rowptr, col, scores)
+    if not 1 <= int(k) <= 64:
+        raise WgnnError(f"rows_topk: k = {k} is outside [1, 64]")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or scores.dtype != torch.float32:
+        raise WgnnError("rows_topk takes rowptr int32 / int64, col int32, scores float32")
+    if col.shape[0] != scores.shape[0]:
+        raise WgnnError(f"col has {col.shape[0]} entries, scores {scores.shape[0]}")
+    B = rowptr.shape[0] - 1
+    rowptr = rowptr.contiguous(); col = col.contiguous(); scores = scores.contiguous()
+    gene = torch.empty((B, int(k)), dtype=torch.int32, device=dev)
+    top = torch.empty((B, int(k)), dtype=torch.float32, device=dev)
+    rc = _lib.call(dev, "wgnn_rows_topk", _ptr(rowptr), _ptr(col), _ptr(scores), B, int(k), _ptr(gene), _ptr(top),
+                   _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0, _stream(dev))
+    _lib.check(rc, "wgnn_rows_topk")
+    return gene, top
