@@ -502,6 +502,34 @@ int wgnn_attrib_rows(const void* rowptr, const int32_t* col, const float* raw, i
 int wgnn_rows_topk(const void* rowptr, const int32_t* col, const float* score, int64_t n_rows, int32_t k,
                    int32_t* gene_out, float* score_out, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Per-group gene tables (additive exports, WGNN_VERSION stays 206): the reduction over cells behind
+ * api.ResidentPredictor.markers.  For a batch of B cells with one f32 score per stored (cell, gene) entry (wgnn_attrib_rows'
+ * `score`) and one group id per cell,
+ *     sum   f64   [n_groups, n_genes] : sum[k, g]   = sum over the cells i with group[i] == k that list g of score[i, g]
+ *     count int32 [n_groups, n_genes] : count[k, g] = number of those cells
+ * wgnn_group_gene_reduce takes the batch GENE-MAJOR: t_rowptr int32 [n_genes + 1], t_cell int32 (the cells that list gene g,
+ * ascending, in [0, n_rows)), t_score f32 in the same order - wgnn_csr_transpose_count / _fill with the scores as values (or a
+ * stable sort by gene above that kernel's 32 768 columns).  Precondition as there: a cell lists a gene at most once.
+ * group int32 [n_rows]: in [0, n_groups), or -1 = the cell takes no part (cells the transpose already dropped may be absent).
+ * An entry whose cell id or group id is out of range takes no part either (callers check their operands; never a fault).
+ *   One wavefront per gene, per-lane private fp64 / int32 bins in LDS (64 lanes x up to 85 groups per pass, more groups =
+ *   more passes over the gene's run), an xor butterfly over the lanes at the end of the run.  f32 terms, fp64 accumulation, no
+ *   atomics; the order of a bin's additions depends on the operand alone: two launches are bit-identical.  n_groups <= 2^20, no
+ *   limit on n_genes beyond int32.  B = 0 is a valid batch (t_cell / t_score / group may be NULL then).
+ *   flags: WGNN_MARKERS_ACCUMULATE - add to what sum / count hold (a cohort streamed in batches); without it EVERY element of
+ *   both outputs is written, zeros included (the caller does not pre-clear).
+ *   workspace: wgnn_group_gene_reduce_workspace bytes, caller-owned (0 for the present route, whose partial sums never leave
+ *   LDS; `workspace` may then be NULL).  Errors: WGNN_ERR_BAD_ARG (NULL sum / count / t_rowptr, n_groups <= 0, n_genes <= 0,
+ *   n_rows outside [0, 2^31), unknown flag), WGNN_ERR_UNSUPPORTED, WGNN_ERR_ALIGNMENT, WGNN_ERR_WORKSPACE;
+ *   wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+#define WGNN_MARKERS_ACCUMULATE 256
+int wgnn_group_gene_reduce_workspace(int64_t n_rows, int64_t nnz, int32_t n_groups, int32_t n_genes, int64_t* bytes);
+int wgnn_group_gene_reduce(const int32_t* t_rowptr, const int32_t* t_cell, const float* t_score, const int32_t* group,
+                           int64_t n_rows, int32_t n_groups, int32_t n_genes, double* sum, int32_t* count,
+                           void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

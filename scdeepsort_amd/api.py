@@ -534,6 +534,100 @@ class Attribution:
         return [self.id2gene[g] for g in self.top_genes[i] if g >= 0]
 
 
+@dataclass
+class MarkerTable:
+    """What ``ResidentPredictor.markers`` returns: the attribution scores of a cohort summed per (group, gene).  K groups
+    (``group_names``), G genes (``id2gene``).  ``n_cells`` int64 [K]: the cells of each group that took part; ``n_skipped``:
+    cells with group -1 (unsure, or excluded by the caller); ``score_sum`` f64 [K, G] and ``expr_count`` int32 [K, G] (on the
+    device): the summed scores of the group's cells that express the gene, and how many do; ``base_sum`` / ``logit_sum`` f64
+    [K]: ``Attribution.base`` / ``.logit`` summed over the group's cells, so that for every group
+    ``score_sum[k].sum() + base_sum[k] == logit_sum[k]`` up to rounding."""
+    group_names: Sequence[str]
+    id2gene: Sequence[str]
+    n_cells: np.ndarray
+    n_skipped: int
+    score_sum: torch.Tensor
+    expr_count: torch.Tensor
+    base_sum: np.ndarray
+    logit_sum: np.ndarray
+
+    def _cells(self) -> torch.Tensor:
+        return torch.from_numpy(np.asarray(self.n_cells, np.float64)).to(self.score_sum.device)[:, None]
+
+    def mean_score(self) -> torch.Tensor:
+        """f64 [K, G]: ``score_sum / n_cells`` - a cell that does not express the gene counts 0; 0 for an empty group."""
+        n = self._cells()
+        return torch.where(n > 0, self.score_sum / n.clamp(min=1.0), torch.zeros_like(self.score_sum))
+
+    def fraction(self) -> torch.Tensor:
+        """f64 [K, G]: the share of the group's cells that express the gene (0 for an empty group)."""
+        n = self._cells()
+        return torch.where(n > 0, self.expr_count.to(torch.float64) / n.clamp(min=1.0), torch.zeros_like(self.score_sum))
+
+    def top(self, k: int = 20, min_fraction: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
+        """Per group the ``k`` genes with the highest ``float32(mean_score)``, descending, equal scores by the lower gene
+        id, among the genes with ``expr_count > 0`` and ``fraction >= min_fraction``: (genes int64 [K, k], -1 where a group
+        has fewer; scores f32 [K, k], 0 there).  Device tables go through ``wgnn_rows_topk`` (``k <= 64``)."""
+        k = int(k)
+        K, G = self.score_sum.shape
+        if k < 1:
+            raise ValueError(f"top: k = {k} must be positive")
+        key = self.mean_score().to(torch.float32)
+        ok = (self.expr_count > 0) & (self.fraction() >= float(min_fraction))
+        key = torch.where(ok, key, torch.full_like(key, -float("inf")))
+        if key.is_cuda:
+            if k > 64:
+                raise ValueError(f"top: k = {k} > 64 is not built (wgnn_rows_topk)")
+            dev = key.device
+            rowptr = torch.arange(K + 1, dtype=torch.int64, device=dev) * G
+            col = torch.arange(G, dtype=torch.int32, device=dev).repeat(K)
+            genes, scores = _ops.rows_topk(rowptr, col, key.reshape(-1).contiguous(), k)
+        else:
+            order = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :k]
+            genes, scores = order, key.gather(1, order)
+            if k > G:
+                genes = F.pad(genes, (0, k - G), value=-1)
+                scores = F.pad(scores, (0, k - G), value=-float("inf"))
+        genes, scores = genes.cpu().numpy().astype(np.int64), scores.cpu().numpy().astype(np.float32)
+        out = np.isneginf(scores) | (genes < 0)
+        genes[out] = -1
+        scores[out] = 0.0
+        return genes, scores
+
+    def frame(self, k: int = 20, min_fraction: float = 0.0) -> pd.DataFrame:
+        """Long form, one row per (group, rank): ``group``, ``n_cells``, ``rank`` (1 = highest), ``gene``, ``mean_score``
+        (f64), ``fraction``."""
+        genes, _ = self.top(k, min_fraction)
+        r, c = np.nonzero(genes >= 0)
+        g = genes[r, c]
+        at = (torch.from_numpy(r).to(self.score_sum.device), torch.from_numpy(g).to(self.score_sum.device))
+        return pd.DataFrame({"group": [self.group_names[i] for i in r], "n_cells": np.asarray(self.n_cells)[r], "rank": c + 1,
+                             "gene": [self.id2gene[j] for j in g], "mean_score": self.mean_score()[at].cpu().numpy(),
+                             "fraction": self.fraction()[at].cpu().numpy()})
+
+    def _require_same(self, group_names: Sequence[str], n_genes: int, id2gene: Optional[Sequence[str]] = None) -> None:
+        """``into=``: the batch must be grouped and indexed as this table is."""
+        K, G = self.score_sum.shape
+        if len(group_names) != K:
+            raise ValueError(f"into: the table holds {K} groups, the batch is grouped into {len(group_names)}")
+        if int(n_genes) != G:
+            raise ValueError(f"into: the table holds {G} genes, the bundle {int(n_genes)}")
+        if list(group_names) != list(self.group_names):
+            raise ValueError("into: the table's group names differ from the batch's")
+        if id2gene is not None and list(id2gene) != list(self.id2gene):
+            raise ValueError("into: the table's gene names differ from the bundle's")
+
+    def _add_cells(self, group: np.ndarray, base: np.ndarray, logit: np.ndarray) -> None:
+        """The [B] vectors of one batch into the per-group host sums (fp64)."""
+        K = len(self.group_names)
+        group = np.asarray(group, np.int64)
+        on = group >= 0
+        self.n_cells = np.asarray(self.n_cells, np.int64) + np.bincount(group[on], minlength=K).astype(np.int64)
+        self.n_skipped = int(self.n_skipped) + int((~on).sum())
+        self.base_sum = self.base_sum + np.bincount(group[on], weights=np.asarray(base, np.float64)[on], minlength=K)
+        self.logit_sum = self.logit_sum + np.bincount(group[on], weights=np.asarray(logit, np.float64)[on], minlength=K)
+
+
 class ResidentPredictor:
     """A trained bundle loaded ONCE, its gene side resident on the GPU, classifying any batch of test cells.
 
@@ -728,6 +822,83 @@ class ResidentPredictor:
         return Attribution(label=label.cpu().numpy().astype(np.int64), target=t_out.cpu().numpy().astype(np.int64),
                            logit=logit.cpu().numpy(), base=base.cpu().numpy(), scores=scores, top_genes=top_genes,
                            top_scores=top_scores, id2gene=self.id2gene)
+
+    # ---------------------------------------------------------------------------------------------
+    def markers(self, expr, groups="predicted", target="predicted", into: Optional[MarkerTable] = None,
+                group_names: Optional[Sequence[str]] = None, n_groups: Optional[int] = None) -> MarkerTable:
+        """Which genes drive each group of cells across a cohort: ``explain``'s per-entry scores summed per (group, gene)
+        on the device (``wgnn_group_gene_reduce``: fp64, deterministic), nothing per-entry leaves the GPU.  ``expr`` as
+        ``classify`` takes it.  ``groups="predicted"``: a cell's group is its label from the same launch (unsure cells are
+        skipped), named by ``id2label``; else one integer id per cell (-1 = skip) with ``group_names`` or ``n_groups`` -
+        clusters, true labels, conditions.  ``target`` as for ``explain``.  ``into``: an earlier table of the same bundle
+        and grouping, which this batch is ADDED to (and which is returned): a cohort of any size streams through."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._markers(expr, groups, target, into, group_names, n_groups)
+
+    def _markers(self, expr, groups, target, into, group_names, n_groups):
+        predicted = isinstance(groups, str)
+        if predicted:
+            if groups != "predicted":
+                raise ValueError(f"groups = {groups!r}: pass \"predicted\" or one integer id per cell")
+            names = list(self.id2label)
+        else:
+            if group_names is not None:
+                names = list(group_names)
+                if n_groups is not None and int(n_groups) != len(names):
+                    raise ValueError(f"n_groups = {n_groups} but {len(names)} group names")
+            elif n_groups is not None:
+                names = [str(i) for i in range(int(n_groups))]
+            else:
+                raise ValueError("groups given per cell need group_names or n_groups")
+            if not names:
+                raise ValueError("no groups")
+        if into is not None:
+            into._require_same(names, self.n_genes, self.id2gene)
+        rowptr, col, raw, _, _ = csr = self._device_csr(expr)
+        B = rowptr.shape[0] - 1
+        if not predicted:
+            ids = groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)
+            if ids.shape != (B,):
+                raise ValueError(f"groups lists {ids.shape} ids, the batch holds {B} cells")
+            if not np.issubdtype(ids.dtype, np.integer):
+                raise ValueError(f"groups must be integer ids, got {ids.dtype}")
+            if ids.size and (ids.min() < -1 or ids.max() >= len(names)):
+                raise ValueError(f"group id out of range [-1, {len(names)})")
+        att = self._explain(csr[:3] if csr[4] is None else csr[4], 0, target)
+        group = att.label if predicted else ids.astype(np.int64)
+        dev_group = torch.from_numpy(group.astype(np.int32)).to(self.device)
+        out = None if into is None else (into.score_sum, into.expr_count)
+        total, count = _ops.group_gene_reduce(rowptr, col, att.scores, dev_group, len(names), self.n_genes, out=out,
+                                              accumulate=into is not None, check=False)
+        table = into if into is not None else MarkerTable(
+            group_names=names, id2gene=self.id2gene, n_cells=np.zeros(len(names), np.int64), n_skipped=0, score_sum=total,
+            expr_count=count, base_sum=np.zeros(len(names)), logit_sum=np.zeros(len(names)))
+        table._add_cells(group, att.base, att.logit)
+        return table
+
+    def markers_files(self, files, top_k: int = 20, min_fraction: float = 0.0, save_path=None) -> pd.DataFrame:
+        """``markers`` over test files streamed into one table (groups = the predicted types), as ``frame(top_k)`` with
+        ``cell_type`` (and ``cell_subtype`` with a label map, as ``predict`` names them) in place of ``group``.  Written as
+        ``{species}_{tissue}_markers.csv`` under ``save_path`` when given."""
+        table = None
+        for f in files:
+            test, _ = _read_test_csr(f, self.file_type, self._gene2id, self.threshold)
+            table = self.markers(test, into=table)
+        if table is None:
+            raise ValueError("markers_files: no files")
+        out = table.frame(top_k, min_fraction)
+        names = out.pop("group").tolist()
+        map_file = self.bundle.label_map()
+        if map_file is not None:                                             # as _prediction_frame names them
+            old2new, old2sub = load_label_map(map_file, self.species)
+            out.insert(0, "cell_subtype", [old2sub.get(p, p) for p in names])
+            out.insert(0, "cell_type", [old2new.get(p, p) for p in names])
+        else:
+            out.insert(0, "cell_type", names)
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_markers.csv", index=False)
+        return out
 
     def predict(self, input_file, save_path=None) -> pd.DataFrame:
         """``DeepSortPredictor.predict`` on the resident bundle: same columns, label-map handling and output file name."""

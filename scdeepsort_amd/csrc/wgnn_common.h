@@ -153,6 +153,7 @@ __device__ __forceinline__ void epilogue(const KArgs& a, float4 (&acc)[NV], int 
 const char* wgnn_generic_error_string(int code);
 const char* predict_error_detail(int code);
 const char* attrib_error_detail(int code);       // the same for wgnn_attrib_rows / wgnn_rows_topk
+const char* markers_error_detail(int code);      // and for wgnn_group_gene_reduce
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }

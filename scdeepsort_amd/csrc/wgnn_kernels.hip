@@ -292,6 +292,7 @@ int wgnn_agg_workspace_bytes(int64_t n_partials, int64_t n_src, int32_t D, int a
 const char* wgnn_last_error_string(int code) {
     if (const char* d = wgnn::predict_error_detail(code)) return d;
     if (const char* d = wgnn::attrib_error_detail(code)) return d;
+    if (const char* d = wgnn::markers_error_detail(code)) return d;
     return wgnn::wgnn_generic_error_string(code);
 }
 

@@ -1007,3 +1007,63 @@ def rows_topk(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Tensor, k: 
                    _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0, _stream(dev))
     _lib.check(rc, "wgnn_rows_topk")
     return gene, top
+
+
+def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Tensor, group: torch.Tensor, n_groups: int,
+                      n_genes: int, out: Optional[tuple] = None, accumulate: bool = False, check: bool = True):
+    """``wgnn_group_gene_reduce``: per (group, gene) the fp64 sum of the f32 ``scores`` of a batch given cell-major as
+    ``attrib_rows`` hands it over (``rowptr`` int32 / int64 [B+1], ``col`` int32 gene ids in ``[0, n_genes)``, one score per
+    stored entry; a cell lists a gene at most once) and the number of cells behind it.  ``group`` int [B]: a cell's group in
+    ``[0, n_groups)``, or -1 = the cell takes no part.
+
+    Returns ``(sum f64 [n_groups, n_genes], count int32 [n_groups, n_genes])`` - ``out`` when given (every element is
+    written, the caller does not pre-clear), added to with ``accumulate``.  The batch is re-ordered gene-major by the
+    library's stable transpose (``group >= 0`` as its row mask; a stable sort above that kernel's 32 768 columns), then one
+    wavefront per gene adds in a fixed order: no atomics, two calls are bit-identical.  ``check``: verify the ranges of
+    ``group`` and ``col`` (one ``aminmax`` each and a read-back)."""
+    import ctypes as C
+    from .graph import _transpose_by_sort, _transpose_on_device
+    dev = _require_cuda(rowptr, col, scores, group, *(out or ()))
+    K, G = int(n_groups), int(n_genes)
+    if K <= 0 or G <= 0:
+        raise WgnnError(f"group_gene_reduce: n_groups = {K} and n_genes = {G} must be positive")
+    B = rowptr.shape[0] - 1
+    nnz = col.shape[0]
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or scores.dtype != torch.float32:
+        raise WgnnError("group_gene_reduce takes rowptr int32 / int64, col int32, scores float32")
+    if scores.shape != (nnz,):
+        raise WgnnError(f"col has {nnz} entries, scores {tuple(scores.shape)}")
+    if nnz >= 2 ** 31:
+        raise WgnnError("group_gene_reduce: nnz >= 2^31 (split the batch and accumulate)")
+    if group.shape != (B,):
+        raise WgnnError(f"group must hold one id per cell ([{B}]), got {tuple(group.shape)}")
+    if group.dtype not in (torch.int32, torch.int64):
+        raise WgnnError("group must be int32 / int64")
+    if check and B:
+        lo, hi = torch.aminmax(group)
+        if int(lo) < -1 or int(hi) >= K:
+            raise WgnnError(f"group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
+    if check and nnz:
+        lo, hi = torch.aminmax(col)
+        if int(lo) < 0 or int(hi) >= G:
+            raise WgnnError(f"gene id out of range [0, {G}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+    if out is None:
+        if accumulate:
+            raise WgnnError("accumulate needs the tables to add to (out=)")
+        out = (torch.empty((K, G), dtype=torch.float64, device=dev), torch.empty((K, G), dtype=torch.int32, device=dev))
+    total, count = out
+    if total.dtype != torch.float64 or count.dtype != torch.int32 or total.shape != (K, G) or count.shape != (K, G) or \
+            not total.is_contiguous() or not count.is_contiguous():
+        raise WgnnError(f"out must be contiguous (float64 [{K}, {G}], int32 [{K}, {G}])")
+    group = group.to(torch.int32).contiguous()
+    rowptr32 = rowptr.to(torch.int32).contiguous()           # nnz < 2^31: a safe narrowing
+    col = col.contiguous(); scores = scores.contiguous()
+    transpose = _transpose_on_device if G <= 32768 else _transpose_by_sort
+    t_rowptr, t_cell, t_score = transpose(rowptr32, col, scores, B, G, group >= 0)
+    nb = C.c_int64()
+    _lib.check(_lib.lib().wgnn_group_gene_reduce_workspace(B, nnz, K, G, C.addressof(nb)), "wgnn_group_gene_reduce_workspace")
+    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev) if nb.value else None
+    rc = _lib.call(dev, "wgnn_group_gene_reduce", _ptr(t_rowptr), _ptr(t_cell), _ptr(t_score), _ptr(group), B, K, G,
+                   _ptr(total), _ptr(count), _ptr(ws), nb.value, _lib.MARKERS_ACCUMULATE if accumulate else 0, _stream(dev))
+    _lib.check(rc, "wgnn_group_gene_reduce")
+    return total, count
