@@ -530,6 +530,44 @@ int wgnn_group_gene_reduce(const int32_t* t_rowptr, const int32_t* t_cell, const
                            int64_t n_rows, int32_t n_groups, int32_t n_genes, double* sum, int32_t* count,
                            void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Batch alignment (additive exports, WGNN_VERSION stays 206): a batch over the CALLER's gene list made into the clean
+ * bundle-vocabulary CSR that wgnn_predict_rows / wgnn_attrib_rows / wgnn_group_gene_reduce take - the device counterpart of the
+ * column selection, `> threshold` and COO -> CSR of api._read_test_csr (reference preprocess.py:160-161, 173-178).  It runs
+ * BEFORE those kernels because their deg and S are the row length and row sum over the bundle's genes only.
+ *
+ * Two passes over the same row walk, one wavefront per row (grid-stride), wave ballots for the slots: no atomics on the data
+ * path, no LDS, two launches are bit-identical.
+ *   wgnn_align_count: row_count int32 [B] = kept entries per row.
+ *   wgnn_align_fill : out_rowptr int64 [B + 1] = the exclusive scan of row_count (the caller's; out_rowptr[B] = the total),
+ *                     out_col int32 [total] bundle gene ids, out_raw f32 [total].
+ * Input, one of two forms (the other's pointers NULL):
+ *   dense: x f32 [B, ld] row-major, n_cols valid columns, ld >= n_cols (elements; the last row needs n_cols of them).  Rows that
+ *          are 16-byte aligned (x and gene_map 16-byte aligned, ld % 4 == 0) are read 16 bytes per lane.
+ *   CSR  : rowptr [B + 1] (int32, or int64 with WGNN_FLAG_ROWPTR_I64), col int32 in [0, n_cols), val f32 - the caller's columns.
+ * gene_map int32 [n_cols]: the bundle id in [0, n_genes) of a column, or -1 = not in the bundle.  threshold f32.
+ * Semantics, exact: entry (r, j) with value v is kept iff gene_map[j] >= 0 && v > threshold (a NaN is dropped; an explicit CSR
+ * entry at or below the threshold too).  A row's kept entries leave in their INPUT order (stable) as (gene_map[j], v), v's bits
+ * untouched - wgnn_predict_rows sums a row in CSR order.  Nothing is sorted or merged: a gene listed twice stays listed twice.
+ * Malformed operands never fault: a CSR entry with col outside [0, n_cols) is not looked up, a gene_map value outside
+ * [-1, n_genes) is not stored, a slot past out_rowptr[r + 1] is not written; each such entry is skipped and ORs its bit into
+ * *status (int32, device memory, zeroed by the caller; required).  All address arithmetic is 64-bit (B * ld may exceed 2^31);
+ * B < 2^31, a row keeps < 2^31 entries.  B = 0 and n_cols = 0 are valid (x / gene_map may be NULL then).
+ * Errors: WGNN_ERR_BAD_ARG (status NULL, both or neither input form, ld < n_cols, n_genes <= 0, negative sizes, a missing
+ * output, unknown flag), WGNN_ERR_ALIGNMENT (out_rowptr not 8-byte, x / val / gene_map not 4-byte aligned);
+ * wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+#define WGNN_ALIGN_BAD_COL    1   /* status bit: a CSR entry's col was outside [0, n_cols)            */
+#define WGNN_ALIGN_BAD_MAP    2   /* status bit: a gene_map value was outside [-1, n_genes)           */
+#define WGNN_ALIGN_BAD_ROWPTR 4   /* status bit: out_rowptr left a row less room than it keeps (fill) */
+int wgnn_align_count(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                     int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                     int32_t* row_count, int32_t* status, uint32_t flags, void* stream);
+int wgnn_align_fill(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                    int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                    const int64_t* out_rowptr, int32_t* out_col, float* out_raw, int32_t* status,
+                    uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -383,6 +383,23 @@ def _read_test_csr(input_file, file_type, gene2id: dict, threshold) -> Tuple[sp.
     return test, df.index
 
 
+def _gene_map_ids(genes, gene2id: dict) -> np.ndarray:
+    """The caller's gene list as bundle ids: int32 [len(genes)], names compared as ``str`` (as ``_read_test_csr`` compares
+    column names), -1 for a name outside the bundle.  Two positions naming the same bundle gene, or no name inside the
+    bundle at all, raise ValueError."""
+    ids = np.fromiter((gene2id.get(str(g), -1) for g in genes), dtype=np.int64, count=len(genes)).astype(np.int32)
+    hit = ids[ids >= 0]
+    if hit.size == 0:
+        raise ValueError(f"none of the {len(ids)} gene names is a gene of the bundle ({len(gene2id)} genes)")
+    uniq, first, n = np.unique(hit, return_index=True, return_counts=True)
+    if (n > 1).any():
+        dup = int(uniq[n > 1][0])
+        where = np.flatnonzero(ids == dup)[:2].tolist()
+        raise ValueError(f"positions {where[0]} and {where[1]} of the gene list both name bundle gene {dup} "
+                         f"({str(genes[where[0]])!r}): a cell may list a gene once")
+    return ids
+
+
 def _load_model(b: dict, dev) -> GNN:
     model = GNN(b["dense_dim"], b["hidden_dim"], len(b["id2label"]), b["n_layers"], len(b["id2gene"]), activation=F.relu,
                 dropout=0.1).to(dev)
@@ -628,6 +645,12 @@ class MarkerTable:
         self.logit_sum = self.logit_sum + np.bincount(group[on], weights=np.asarray(logit, np.float64)[on], minlength=K)
 
 
+@dataclass
+class _Aligned:
+    """``ResidentPredictor.align``'s output on its way into the kernels: gene ids in range by construction."""
+    csr: Tuple[torch.Tensor, torch.Tensor, torch.Tensor]
+
+
 class ResidentPredictor:
     """A trained bundle loaded ONCE, its gene side resident on the GPU, classifying any batch of test cells.
 
@@ -700,17 +723,80 @@ class ResidentPredictor:
             return "graph"
         return "fused"
 
-    def classify(self, expr) -> Tuple[np.ndarray, np.ndarray, torch.Tensor]:
+    def classify(self, expr, genes=None) -> Tuple[np.ndarray, np.ndarray, torch.Tensor]:
         """Classify a batch: ``expr`` = a scipy CSR (cells x the bundle's genes, raw values) or a device
         ``(rowptr, col, raw)`` triple over the bundle's gene ids.  Returns (label ids with -1 = unsure, max softmax
-        probability, logits on the device)."""
+        probability, logits on the device).  With ``genes`` the batch is over the caller's own gene list, in any of the
+        forms ``align`` takes, and goes through ``align`` first."""
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._classify(expr)
+            return self._classify(expr if genes is None else _Aligned(self._align(expr, genes, None)))
+
+    # ---------------------------------------------------------------------------------------------
+    def gene_map(self, genes) -> torch.Tensor:
+        """The caller's gene list as ``align`` wants it: int32 ``[len(genes)]`` on the device, a name's bundle gene id or -1
+        for a name outside the bundle (names compared as ``str``).  Raises ValueError when two positions name the same
+        bundle gene (a cell may list a gene once) or when no name is in the bundle.  Build it once for a stream of batches
+        and pass it as ``genes=``."""
+        return torch.from_numpy(_gene_map_ids(genes, self._gene2id)).to(self.device)
+
+    def align(self, expr, genes, threshold=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """An in-memory batch over the caller's own gene list as the device ``(rowptr int64, col int32, raw f32)`` triple
+        over the bundle's gene ids that ``classify`` / ``explain`` / ``markers`` take (``wgnn_align_count`` / ``_fill``):
+        columns outside the bundle and values ``<= threshold`` (default: the predictor's) are dropped, a cell's kept
+        entries keep the caller's order and their bits.  ``expr``: a 2-D ``torch.Tensor`` on any device (other dtypes are
+        converted to float32), a 2-D numpy array, a scipy sparse matrix, or a device ``(rowptr, col, val)`` triple whose
+        column ids index ``genes``.  ``genes``: the column names, or the tensor ``gene_map`` made of them.  The file route
+        (``predict``) lists a cell's genes by ascending bundle id instead; the two orders coincide, and the results are
+        bit-identical, when the caller's bundle genes come in the bundle's order."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._align(expr, genes, threshold)
+
+    def _align(self, expr, genes, threshold):
+        dev = self.device
+        if isinstance(genes, torch.Tensor):
+            gmap = genes.to(device=dev, dtype=torch.int32).contiguous()
+            if gmap.dim() != 1:
+                raise ValueError("a gene map is a vector (ResidentPredictor.gene_map)")
+        else:
+            gmap = self.gene_map(genes)
+        n_cols = int(gmap.shape[0])
+        thr = self.threshold if threshold is None else threshold
+        if isinstance(expr, (tuple, list)):
+            rowptr, col, val = expr
+            _ops._require_cuda(rowptr, col, val)
+            rowptr = rowptr if rowptr.dtype in (torch.int32, torch.int64) else rowptr.long()
+            batch = (rowptr.contiguous(), col.to(torch.int32).contiguous(), val.to(torch.float32).contiguous())
+        elif sp.issparse(expr):
+            host = expr.tocsr()
+            if host.shape[1] != n_cols:
+                raise ValueError(f"expression matrix has {host.shape[1]} columns, the gene list {n_cols} names")
+            batch = (torch.from_numpy(host.indptr).to(dev), torch.from_numpy(host.indices.astype(np.int32, copy=False)).to(dev),
+                     torch.from_numpy(host.data.astype(np.float32, copy=False)).to(dev))
+        else:
+            x = expr if isinstance(expr, torch.Tensor) else torch.from_numpy(np.asarray(expr))
+            if x.dim() != 2:
+                raise ValueError(f"expression matrix must be 2-D (cells x genes), got {x.dim()} dimensions")
+            if x.shape[1] != n_cols:
+                raise ValueError(f"expression matrix has {x.shape[1]} columns, the gene list {n_cols} names")
+            x = x.to(device=dev, dtype=torch.float32)
+            batch = x if x.stride(1) == 1 and (x.shape[0] <= 1 or x.stride(0) >= n_cols) else x.contiguous()
+        return _ops.align_rows(batch, gmap, self.n_genes, float(thr))
+
+    def predict_matrix(self, expr, genes, index=None) -> pd.DataFrame:
+        """``predict`` for an in-memory batch over the caller's gene list (``expr``, ``genes`` as ``align`` takes them): the
+        same table, ``index`` (default ``range(B)``) in place of the file's cell names."""
+        pred, _, _ = self.classify(expr, genes=genes)
+        index = pd.RangeIndex(len(pred)) if index is None else index
+        if len(index) != len(pred):
+            raise ValueError(f"index names {len(index)} cells, the batch holds {len(pred)}")
+        return _prediction_frame(self.species, self.tissue, "matrix", index, pred, self.id2label, self.bundle, None)
 
     def _device_csr(self, expr):
         """A batch as the kernels take it: (rowptr, col int32, raw f32) on the device, whether its gene ids are in range by
         construction, and the host CSR when the batch came as one."""
         dev = self.device
+        if isinstance(expr, _Aligned):                   # align's output: ids in range by construction
+            return (*expr.csr, True, None)
         if isinstance(expr, (tuple, list)):
             rowptr, col, raw = expr
             _ops._require_cuda(rowptr, col, raw)
@@ -753,14 +839,15 @@ class ResidentPredictor:
         return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits
 
     # ---------------------------------------------------------------------------------------------
-    def explain(self, expr, top_k: int = 10, target="predicted") -> "Attribution":
+    def explain(self, expr, top_k: int = 10, target="predicted", genes=None) -> "Attribution":
         """Which genes made the model say so: the target logit of every cell split, without approximation, into one share
         per expressed gene plus a bias share (``sum(scores of the cell) + base == logit``; ``include/wgnn.h``,
         ``wgnn_attrib_rows``).  ``expr`` as ``classify`` takes it.  ``target``: ``"predicted"`` (the arg max, also for a
         cell that comes out unsure), a class id, a label string, or one class id per cell.  ``top_k`` in 0..64: the
-        highest-scoring genes per cell (0 = scores only).  Cells are independent, so there is no graph route."""
+        highest-scoring genes per cell (0 = scores only).  Cells are independent, so there is no graph route.  ``genes``: as
+        for ``classify``; the scores then follow ``align``'s entries (gene ids of the bundle, the caller's order)."""
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._explain(expr, top_k, target)
+            return self._explain(expr if genes is None else _Aligned(self._align(expr, genes, None)), top_k, target)
 
     def _target_ids(self, target, n_cells: int) -> Optional[torch.Tensor]:
         """``explain``'s ``target`` as None (the predicted class) or an int32 device vector with one class per cell."""
@@ -825,14 +912,17 @@ class ResidentPredictor:
 
     # ---------------------------------------------------------------------------------------------
     def markers(self, expr, groups="predicted", target="predicted", into: Optional[MarkerTable] = None,
-                group_names: Optional[Sequence[str]] = None, n_groups: Optional[int] = None) -> MarkerTable:
+                group_names: Optional[Sequence[str]] = None, n_groups: Optional[int] = None, genes=None) -> MarkerTable:
         """Which genes drive each group of cells across a cohort: ``explain``'s per-entry scores summed per (group, gene)
         on the device (``wgnn_group_gene_reduce``: fp64, deterministic), nothing per-entry leaves the GPU.  ``expr`` as
         ``classify`` takes it.  ``groups="predicted"``: a cell's group is its label from the same launch (unsure cells are
         skipped), named by ``id2label``; else one integer id per cell (-1 = skip) with ``group_names`` or ``n_groups`` -
         clusters, true labels, conditions.  ``target`` as for ``explain``.  ``into``: an earlier table of the same bundle
-        and grouping, which this batch is ADDED to (and which is returned): a cohort of any size streams through."""
+        and grouping, which this batch is ADDED to (and which is returned): a cohort of any size streams through.
+        ``genes``: as for ``classify``."""
         with torch.cuda.device(self.device), torch.no_grad():
+            if genes is not None:
+                expr = _Aligned(self._align(expr, genes, None))
             return self._markers(expr, groups, target, into, group_names, n_groups)
 
     def _markers(self, expr, groups, target, into, group_names, n_groups):
@@ -864,7 +954,7 @@ class ResidentPredictor:
                 raise ValueError(f"groups must be integer ids, got {ids.dtype}")
             if ids.size and (ids.min() < -1 or ids.max() >= len(names)):
                 raise ValueError(f"group id out of range [-1, {len(names)})")
-        att = self._explain(csr[:3] if csr[4] is None else csr[4], 0, target)
+        att = self._explain(expr if isinstance(expr, _Aligned) else csr[:3] if csr[4] is None else csr[4], 0, target)
         group = att.label if predicted else ids.astype(np.int64)
         dev_group = torch.from_numpy(group.astype(np.int32)).to(self.device)
         out = None if into is None else (into.score_sum, into.expr_count)

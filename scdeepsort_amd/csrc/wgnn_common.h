@@ -154,6 +154,7 @@ const char* wgnn_generic_error_string(int code);
 const char* predict_error_detail(int code);
 const char* attrib_error_detail(int code);       // the same for wgnn_attrib_rows / wgnn_rows_topk
 const char* markers_error_detail(int code);      // and for wgnn_group_gene_reduce
+const char* align_error_detail(int code);        // and for wgnn_align_count / wgnn_align_fill
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }

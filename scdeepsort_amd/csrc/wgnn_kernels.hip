@@ -293,6 +293,7 @@ const char* wgnn_last_error_string(int code) {
     if (const char* d = wgnn::predict_error_detail(code)) return d;
     if (const char* d = wgnn::attrib_error_detail(code)) return d;
     if (const char* d = wgnn::markers_error_detail(code)) return d;
+    if (const char* d = wgnn::align_error_detail(code)) return d;
     return wgnn::wgnn_generic_error_string(code);
 }
 

@@ -1067,3 +1067,66 @@ def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Ten
                    _ptr(total), _ptr(count), _ptr(ws), nb.value, _lib.MARKERS_ACCUMULATE if accumulate else 0, _stream(dev))
     _lib.check(rc, "wgnn_group_gene_reduce")
     return total, count
+
+
+_ALIGN_STATUS = ((_lib.ALIGN_BAD_COL, "a CSR entry's column is outside [0, n_cols)"),
+                 (_lib.ALIGN_BAD_MAP, "a gene_map value is outside [-1, n_genes)"),
+                 (_lib.ALIGN_BAD_ROWPTR, "a row kept more entries than were counted"))
+
+
+def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.0):
+    """``wgnn_align_count`` / ``wgnn_align_fill``: a batch over the caller's gene list as the bundle-vocabulary CSR that
+    ``predict_rows`` takes.  ``expr``: a dense float32 ``[B, n_cols]`` device matrix (unit column stride; the row stride is its
+    leading dimension) or a device ``(rowptr int32 / int64 [B+1], col int32, val float32)`` triple over the caller's columns.
+    ``gene_map`` int32 ``[n_cols]`` on the device: a column's bundle gene id in ``[0, n_genes)``, or -1.
+
+    An entry is kept iff its column maps to a gene and its value is ``> threshold`` (a NaN is dropped); a row's kept entries
+    keep their input order and their bits.  Returns ``(rowptr int64 [B+1], col int32, raw float32)`` on the device: the count
+    pass, a ``torch.cumsum``, one read-back of the total to size the outputs, the fill pass, and a read-back of the status word -
+    a column outside ``[0, n_cols)`` or a map value outside ``[-1, n_genes)`` raises ``WgnnError`` (the kernels skip it)."""
+    dense = isinstance(expr, torch.Tensor)
+    if not dense and not (isinstance(expr, (tuple, list)) and len(expr) == 3):
+        raise WgnnError("align_rows takes a dense [B, n_cols] tensor or a (rowptr, col, val) triple")
+    dev = _require_cuda(gene_map, *((expr,) if dense else expr))
+    if gene_map.dtype != torch.int32 or gene_map.dim() != 1 or not gene_map.is_contiguous():
+        raise WgnnError("gene_map must be a contiguous int32 vector")
+    n_cols, G = int(gene_map.shape[0]), int(n_genes)
+    if G <= 0:
+        raise WgnnError(f"align_rows: n_genes = {G} must be positive")
+    x = rowptr = col = val = None
+    ld = flags = 0
+    if dense:
+        x = expr
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise WgnnError(f"align_rows takes a 2-D float32 matrix, got {x.dtype} with {x.dim()} dimensions")
+        if x.shape[1] != n_cols:
+            raise WgnnError(f"the matrix has {x.shape[1]} columns, gene_map {n_cols} entries")
+        B = int(x.shape[0])
+        if (n_cols > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n_cols):
+            raise WgnnError("align_rows takes row-major rows (unit column stride, row stride >= n_cols)")
+        ld = int(x.stride(0)) if B > 1 else n_cols           # a single row's stride says nothing
+    else:
+        rowptr, col, val = expr
+        if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
+            raise WgnnError("align_rows takes rowptr int32 / int64, col int32, val float32")
+        if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
+            raise WgnnError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, val {tuple(val.shape)}")
+        if not (rowptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()):
+            raise WgnnError("align_rows takes contiguous rowptr, col and val")
+        B = int(rowptr.shape[0]) - 1
+        flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int32, device=dev)
+    head = (_ptr(x), ld, _ptr(rowptr), _ptr(col), _ptr(val), B, n_cols, _ptr(gene_map), G, float(threshold))
+    _lib.check(_lib.call(dev, "wgnn_align_count", *head, _ptr(counts), _ptr(status), flags, _stream(dev)), "wgnn_align_count")
+    out_rowptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(counts, 0, dtype=torch.int64, out=out_rowptr[1:])
+    total = int(out_rowptr[-1])                              # the one read-back that sizes the outputs
+    out_col = torch.empty(total, dtype=torch.int32, device=dev)
+    out_raw = torch.empty(total, dtype=torch.float32, device=dev)
+    _lib.check(_lib.call(dev, "wgnn_align_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status), flags,
+                         _stream(dev)), "wgnn_align_fill")
+    bits = int(status)
+    if bits:
+        raise WgnnError("align_rows: " + "; ".join(text for bit, text in _ALIGN_STATUS if bits & bit))
+    return out_rowptr, out_col, out_raw
