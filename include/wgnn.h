@@ -560,6 +560,7 @@ int wgnn_group_gene_reduce(const int32_t* t_rowptr, const int32_t* t_cell, const
 #define WGNN_ALIGN_BAD_COL    1   /* status bit: a CSR entry's col was outside [0, n_cols)            */
 #define WGNN_ALIGN_BAD_MAP    2   /* status bit: a gene_map value was outside [-1, n_genes)           */
 #define WGNN_ALIGN_BAD_ROWPTR 4   /* status bit: out_rowptr left a row less room than it keeps (fill) */
+#define WGNN_ALIGN_BAD_VALUE  8   /* status bit: a count was negative / NaN / infinite, or a library size unusable (_ln) */
 int wgnn_align_count(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
                      int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
                      int32_t* row_count, int32_t* status, uint32_t flags, void* stream);
@@ -567,6 +568,43 @@ int wgnn_align_fill(const float* x, int64_t ld, const void* rowptr, const int32_
                     int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
                     const int64_t* out_rowptr, int32_t* out_col, float* out_raw, int32_t* status,
                     uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Log-normalising alignment (additive exports, WGNN_VERSION stays 206): the same walk over RAW COUNTS, leaving what Seurat's
+ * NormalizeData defaults ("LogNormalize", reference pre-process.R:33) make of them - the values the model was trained on.
+ * For a batch of B cells over the caller's n_cols columns holding counts x[r, j]:
+ *
+ *   total[r] = sum over ALL j of double(x[r, j])          (columns outside the bundle included; fp64, fixed order)
+ *   v[r, j]  = float( log1p( double(x[r, j]) / total[r] * scale ) )          (fp64 throughout, Seurat's operation order)
+ *   entry (r, j) is kept  iff  gene_map[j] >= 0  &&  x[r, j] > 0  &&  v[r, j] > threshold
+ *
+ * The total is taken BEFORE the vocabulary filter, as the reference does (it normalises at pre-process.R:33 and drops unknown
+ * symbols at :61): aligning first and normalising second gives another library size and other values.  Kept entries leave as
+ * (gene_map[j], v[r, j]) in the row's input order, exactly as wgnn_align_fill orders them.  scale > 0 (Seurat: 10000);
+ * threshold >= 0 is required (an entry that is not stored counts as 0).  A row whose total is 0 keeps nothing and no division
+ * is made for it (its malformed columns and map values are still reported).  Counts need not be integers; a -0.0 is a zero.  No normalised matrix is stored: v is evaluated inside the
+ * COUNT and the FILL walk by the same instructions, in fp64, and only for candidates (mapped column, x > 0).
+ *   wgnn_align_count_ln: wgnn_align_count, and total double [B] (written).  The walk reads a row twice: first every column
+ *                        into the total (dense: the row's n_cols columns; CSR: the row's stored entries, col is not read) - a
+ *                        lane adds its entries in ascending position, the wave's 64 partial sums fold in a fixed butterfly: no
+ *                        atomics, two launches are bit-identical - then the keep test.  library_size (double [B], or NULL): the
+ *                        caller's own depths, which replace the sum on every row that holds a count > 0 (for a caller who has
+ *                        already subset the genes); a value that is <= 0 or not finite on such a row is reported and the row's
+ *                        total is 0.  The summing read also finds, on EVERY column, the counts that are negative, NaN or
+ *                        infinite: such a count poisons the total whether or not its column maps, so it is left out and
+ *                        WGNN_ALIGN_BAD_VALUE is raised in *status (as the other bits: never a fault, skip and report).
+ *   wgnn_align_fill_ln : wgnn_align_fill over the totals wgnn_align_count_ln stored.
+ * Every other argument, operand form, status bit and error as wgnn_align_count / _fill.  Further errors: WGNN_ERR_BAD_ARG
+ * (threshold < 0 or NaN, scale not positive and finite, total NULL), WGNN_ERR_ALIGNMENT (total / library_size not 8-byte aligned).
+ * ------------------------------------------------------------------------- */
+int wgnn_align_count_ln(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                        int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                        const double* library_size, double* total, double scale, int32_t* row_count, int32_t* status,
+                        uint32_t flags, void* stream);
+int wgnn_align_fill_ln(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                       int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                       const double* total, double scale, const int64_t* out_rowptr, int32_t* out_col, float* out_raw,
+                       int32_t* status, uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

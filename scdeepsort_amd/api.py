@@ -645,6 +645,25 @@ class MarkerTable:
         self.logit_sum = self.logit_sum + np.bincount(group[on], weights=np.asarray(logit, np.float64)[on], minlength=K)
 
 
+@dataclass(frozen=True)
+class LogNormalize:
+    """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
+    (``LogNormalize``, reference ``pre-process.R:33``) are applied on the device while the batch is aligned -
+    ``log1p(count / library size * scale_factor)`` in fp64, the library size taken over ALL of the caller's columns, those
+    outside the bundle included.  ``library_size``: one value per cell that replaces that total, for a caller who has
+    already subset the genes but kept the true depths.  ``normalize="lognorm"`` is ``LogNormalize()``."""
+    scale_factor: float = 1e4
+    library_size: Optional[object] = None
+
+
+def _normalize_spec(normalize) -> Optional[LogNormalize]:
+    if normalize is None or isinstance(normalize, LogNormalize):
+        return normalize
+    if isinstance(normalize, str) and normalize == "lognorm":
+        return LogNormalize()
+    raise ValueError(f"normalize = {normalize!r}: pass None, \"lognorm\" or a LogNormalize")
+
+
 @dataclass
 class _Aligned:
     """``ResidentPredictor.align``'s output on its way into the kernels: gene ids in range by construction."""
@@ -662,11 +681,18 @@ class ResidentPredictor:
     Resident: ``Q = gene_feat . W1^T``, ``T_l = h_{l-1}[genes] . W_l^T`` for l >= 2 (h of the genes from the existing
     ``GNN._layer`` over a support-only graph), alpha, biases and the head.  A batch whose ``nnz * H * n_layers`` exceeds
     ``RESIDENT_FUSED_MAX_WORK`` (or with a hidden width above 256) takes the graph route instead - the predict graph of
-    ``DeepSortPredictor`` with the cached gene features; ``last_route`` says which one ran ("fused" | "graph")."""
+    ``DeepSortPredictor`` with the cached gene features; ``last_route`` says which one ran ("fused" | "graph").
+
+    ``normalize`` (``None`` | ``"lognorm"`` | ``LogNormalize``): the default of the ``normalize=`` argument of every method
+    that takes ``genes=`` or a file - set it when the batches and files hold raw counts (``LogNormalize``).  A batch given
+    over the bundle's own gene ids (no ``genes=``) is never normalised."""
+
+    normalize: Optional[LogNormalize] = None
 
     def __init__(self, species, tissue, model_path='pretrained', gpu_id=0, unsure_rate=2., file_type='csv', threshold=0,
-                 seed=10086):
+                 seed=10086, normalize=None):
         self.species, self.tissue, self.unsure_rate, self.file_type, self.threshold = species, tissue, unsure_rate, file_type, threshold
+        self.normalize = _normalize_spec(normalize)
         self.model_path = Path(model_path)
         self.device = _device(gpu_id)
         self.last_route: Optional[str] = None
@@ -723,13 +749,22 @@ class ResidentPredictor:
             return "graph"
         return "fused"
 
-    def classify(self, expr, genes=None) -> Tuple[np.ndarray, np.ndarray, torch.Tensor]:
+    def classify(self, expr, genes=None, normalize=None) -> Tuple[np.ndarray, np.ndarray, torch.Tensor]:
         """Classify a batch: ``expr`` = a scipy CSR (cells x the bundle's genes, raw values) or a device
         ``(rowptr, col, raw)`` triple over the bundle's gene ids.  Returns (label ids with -1 = unsure, max softmax
         probability, logits on the device).  With ``genes`` the batch is over the caller's own gene list, in any of the
-        forms ``align`` takes, and goes through ``align`` first."""
+        forms ``align`` takes, and goes through ``align`` first - with ``normalize`` as ``align`` takes it (raw counts in)."""
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._classify(expr if genes is None else _Aligned(self._align(expr, genes, None)))
+            return self._classify(self._over_genes(expr, genes, normalize))
+
+    def _over_genes(self, expr, genes, normalize):
+        """``expr`` as the kernels' routes take it: untouched without ``genes``, else ``align``'s output."""
+        if genes is None:
+            if normalize is not None:
+                raise ValueError("normalize needs genes=: a batch over the bundle's gene ids has lost the columns the cell's total "
+                                 "is taken over (pass genes=predictor.id2gene if the batch really holds all of them)")
+            return expr
+        return _Aligned(self._align(expr, genes, None, normalize))
 
     # ---------------------------------------------------------------------------------------------
     def gene_map(self, genes) -> torch.Tensor:
@@ -739,7 +774,7 @@ class ResidentPredictor:
         and pass it as ``genes=``."""
         return torch.from_numpy(_gene_map_ids(genes, self._gene2id)).to(self.device)
 
-    def align(self, expr, genes, threshold=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    def align(self, expr, genes, threshold=None, normalize=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """An in-memory batch over the caller's own gene list as the device ``(rowptr int64, col int32, raw f32)`` triple
         over the bundle's gene ids that ``classify`` / ``explain`` / ``markers`` take (``wgnn_align_count`` / ``_fill``):
         columns outside the bundle and values ``<= threshold`` (default: the predictor's) are dropped, a cell's kept
@@ -747,12 +782,21 @@ class ResidentPredictor:
         converted to float32), a 2-D numpy array, a scipy sparse matrix, or a device ``(rowptr, col, val)`` triple whose
         column ids index ``genes``.  ``genes``: the column names, or the tensor ``gene_map`` made of them.  The file route
         (``predict``) lists a cell's genes by ascending bundle id instead; the two orders coincide, and the results are
-        bit-identical, when the caller's bundle genes come in the bundle's order."""
-        with torch.cuda.device(self.device), torch.no_grad():
-            return self._align(expr, genes, threshold)
+        bit-identical, when the caller's bundle genes come in the bundle's order.
 
-    def _align(self, expr, genes, threshold):
+        ``normalize`` (``None`` = the predictor's default | ``"lognorm"`` | ``LogNormalize``): ``expr`` holds raw counts
+        (they need not be integers) and the values that leave are Seurat's ``LogNormalize`` of them, computed in fp64 inside
+        the same walk (``wgnn_align_count_ln`` / ``_fill_ln``) - no normalised matrix is stored.  A cell's
+        total is taken over ALL of ``genes``' columns before the ones outside the bundle are dropped, as the reference's R
+        step does (``pre-process.R`` normalises at line 33 and filters symbols at line 61); an entry is kept iff its count
+        is ``> 0`` and its normalised value ``> threshold``, which must be ``>= 0`` (``ValueError``).  A negative, NaN or
+        infinite count anywhere in the batch raises ``WgnnError``."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._align(expr, genes, threshold, normalize)
+
+    def _align(self, expr, genes, threshold, normalize=None):
         dev = self.device
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
         if isinstance(genes, torch.Tensor):
             gmap = genes.to(device=dev, dtype=torch.int32).contiguous()
             if gmap.dim() != 1:
@@ -780,12 +824,15 @@ class ResidentPredictor:
                 raise ValueError(f"expression matrix has {x.shape[1]} columns, the gene list {n_cols} names")
             x = x.to(device=dev, dtype=torch.float32)
             batch = x if x.stride(1) == 1 and (x.shape[0] <= 1 or x.stride(0) >= n_cols) else x.contiguous()
-        return _ops.align_rows(batch, gmap, self.n_genes, float(thr))
+        if spec is None:
+            return _ops.align_rows(batch, gmap, self.n_genes, float(thr))
+        return _ops.align_rows(batch, gmap, self.n_genes, float(thr), normalize="lognorm", scale=float(spec.scale_factor),
+                               library_size=spec.library_size)
 
-    def predict_matrix(self, expr, genes, index=None) -> pd.DataFrame:
-        """``predict`` for an in-memory batch over the caller's gene list (``expr``, ``genes`` as ``align`` takes them): the
-        same table, ``index`` (default ``range(B)``) in place of the file's cell names."""
-        pred, _, _ = self.classify(expr, genes=genes)
+    def predict_matrix(self, expr, genes, index=None, normalize=None) -> pd.DataFrame:
+        """``predict`` for an in-memory batch over the caller's gene list (``expr``, ``genes``, ``normalize`` as ``align``
+        takes them): the same table, ``index`` (default ``range(B)``) in place of the file's cell names."""
+        pred, _, _ = self.classify(expr, genes=genes, normalize=normalize)
         index = pd.RangeIndex(len(pred)) if index is None else index
         if len(index) != len(pred):
             raise ValueError(f"index names {len(index)} cells, the batch holds {len(pred)}")
@@ -839,15 +886,16 @@ class ResidentPredictor:
         return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits
 
     # ---------------------------------------------------------------------------------------------
-    def explain(self, expr, top_k: int = 10, target="predicted", genes=None) -> "Attribution":
+    def explain(self, expr, top_k: int = 10, target="predicted", genes=None, normalize=None) -> "Attribution":
         """Which genes made the model say so: the target logit of every cell split, without approximation, into one share
         per expressed gene plus a bias share (``sum(scores of the cell) + base == logit``; ``include/wgnn.h``,
         ``wgnn_attrib_rows``).  ``expr`` as ``classify`` takes it.  ``target``: ``"predicted"`` (the arg max, also for a
         cell that comes out unsure), a class id, a label string, or one class id per cell.  ``top_k`` in 0..64: the
         highest-scoring genes per cell (0 = scores only).  Cells are independent, so there is no graph route.  ``genes``: as
-        for ``classify``; the scores then follow ``align``'s entries (gene ids of the bundle, the caller's order)."""
+        for ``classify``; the scores then follow ``align``'s entries (gene ids of the bundle, the caller's order).
+        ``normalize``: as for ``align`` (needs ``genes``)."""
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._explain(expr if genes is None else _Aligned(self._align(expr, genes, None)), top_k, target)
+            return self._explain(self._over_genes(expr, genes, normalize), top_k, target)
 
     def _target_ids(self, target, n_cells: int) -> Optional[torch.Tensor]:
         """``explain``'s ``target`` as None (the predicted class) or an int32 device vector with one class per cell."""
@@ -912,18 +960,17 @@ class ResidentPredictor:
 
     # ---------------------------------------------------------------------------------------------
     def markers(self, expr, groups="predicted", target="predicted", into: Optional[MarkerTable] = None,
-                group_names: Optional[Sequence[str]] = None, n_groups: Optional[int] = None, genes=None) -> MarkerTable:
+                group_names: Optional[Sequence[str]] = None, n_groups: Optional[int] = None, genes=None,
+                normalize=None) -> MarkerTable:
         """Which genes drive each group of cells across a cohort: ``explain``'s per-entry scores summed per (group, gene)
         on the device (``wgnn_group_gene_reduce``: fp64, deterministic), nothing per-entry leaves the GPU.  ``expr`` as
         ``classify`` takes it.  ``groups="predicted"``: a cell's group is its label from the same launch (unsure cells are
         skipped), named by ``id2label``; else one integer id per cell (-1 = skip) with ``group_names`` or ``n_groups`` -
         clusters, true labels, conditions.  ``target`` as for ``explain``.  ``into``: an earlier table of the same bundle
         and grouping, which this batch is ADDED to (and which is returned): a cohort of any size streams through.
-        ``genes``: as for ``classify``."""
+        ``genes``: as for ``classify``; ``normalize``: as for ``align`` (needs ``genes``)."""
         with torch.cuda.device(self.device), torch.no_grad():
-            if genes is not None:
-                expr = _Aligned(self._align(expr, genes, None))
-            return self._markers(expr, groups, target, into, group_names, n_groups)
+            return self._markers(self._over_genes(expr, genes, normalize), groups, target, into, group_names, n_groups)
 
     def _markers(self, expr, groups, target, into, group_names, n_groups):
         predicted = isinstance(groups, str)
@@ -966,13 +1013,27 @@ class ResidentPredictor:
         table._add_cells(group, att.base, att.logit)
         return table
 
-    def markers_files(self, files, top_k: int = 20, min_fraction: float = 0.0, save_path=None) -> pd.DataFrame:
+    def _read_test(self, input_file, normalize=None):
+        """A test file as a batch the kernels' routes take, and its cell names.  Without normalisation: ``_read_test_csr``'s
+        host CSR, a cell's genes by ascending bundle id.  With it (``normalize``, else the predictor's default) the file
+        holds raw counts: its full table and gene names go through ``align``, so the cell totals cover every gene of the
+        file, and a cell's genes then come in the FILE's order - the results agree with the ascending-id route in everything
+        but the last bits of a row sum (bit for bit when the file lists its bundle genes in the bundle's order)."""
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
+        if spec is None:
+            return _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
+        df = _read_expression(input_file, self.file_type)
+        with torch.cuda.device(self.device), torch.no_grad():
+            csr = self._align(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], None, spec)
+        return _Aligned(csr), df.index
+
+    def markers_files(self, files, top_k: int = 20, min_fraction: float = 0.0, save_path=None, normalize=None) -> pd.DataFrame:
         """``markers`` over test files streamed into one table (groups = the predicted types), as ``frame(top_k)`` with
         ``cell_type`` (and ``cell_subtype`` with a label map, as ``predict`` names them) in place of ``group``.  Written as
-        ``{species}_{tissue}_markers.csv`` under ``save_path`` when given."""
+        ``{species}_{tissue}_markers.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``."""
         table = None
         for f in files:
-            test, _ = _read_test_csr(f, self.file_type, self._gene2id, self.threshold)
+            test, _ = self._read_test(f, normalize)
             table = self.markers(test, into=table)
         if table is None:
             raise ValueError("markers_files: no files")
@@ -990,17 +1051,20 @@ class ResidentPredictor:
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_markers.csv", index=False)
         return out
 
-    def predict(self, input_file, save_path=None) -> pd.DataFrame:
-        """``DeepSortPredictor.predict`` on the resident bundle: same columns, label-map handling and output file name."""
-        test, index = _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
+    def predict(self, input_file, save_path=None, normalize=None) -> pd.DataFrame:
+        """``DeepSortPredictor.predict`` on the resident bundle: same columns, label-map handling and output file name.
+        ``normalize`` (``None`` = the predictor's default | ``"lognorm"`` | ``LogNormalize``): the file holds raw counts, which
+        are log-normalised on the device over ALL of the file's genes (``align``); a cell's genes then come in the file's order,
+        and the results agree with the ascending-id route in everything but the last bits of a row sum."""
+        test, index = self._read_test(input_file, normalize)
         pred, _, _ = self.classify(test)
         return _prediction_frame(self.species, self.tissue, input_file, index, pred, self.id2label, self.bundle, save_path)
 
-    def explain_file(self, input_file, top_k: int = 10, save_path=None) -> pd.DataFrame:
+    def explain_file(self, input_file, top_k: int = 10, save_path=None, normalize=None) -> pd.DataFrame:
         """``explain`` on a test file, in long form: one row per (cell, rank) with the columns ``index``, ``cell_type`` (and
         ``cell_subtype`` with a label map, as ``predict`` names them), ``rank`` (1 = highest score), ``gene``, ``score``.
-        Written as ``{species}_{tissue}_{stem}_genes.csv`` under ``save_path`` when given."""
-        test, index = _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
+        Written as ``{species}_{tissue}_{stem}_genes.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        test, index = self._read_test(input_file, normalize)
         att = self.explain(test, top_k=top_k)
         cells = _prediction_frame(self.species, self.tissue, input_file, index, att.label, self.id2label, self.bundle, None)
         r, k = np.nonzero(att.top_genes >= 0)
@@ -1013,18 +1077,19 @@ class ResidentPredictor:
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_{Path(input_file).stem}_genes.csv", index=False)
         return out
 
-    def predict_many(self, files, save_path=None) -> List[pd.DataFrame]:
-        """One table per test file (``predict.py --test_dataset 1 2 3``), the bundle loaded once."""
-        return [self.predict(f, save_path) for f in files]
+    def predict_many(self, files, save_path=None, normalize=None) -> List[pd.DataFrame]:
+        """One table per test file (``predict.py --test_dataset 1 2 3``), the bundle loaded once.  ``normalize``: as for
+        ``predict``."""
+        return [self.predict(f, save_path, normalize=normalize) for f in files]
 
     def default_map_file(self) -> Optional[Path]:
         root = self.bundle.root
         return next((f for f in (root / "map.xlsx", root.parent / "map" / self.species / "map.xlsx") if f.exists()), None)
 
-    def evaluate(self, data_file, celltype_file, map_file=None, dataset_num=None):
+    def evaluate(self, data_file, celltype_file, map_file=None, dataset_num=None, normalize=None):
         """The reference's evaluate mode (predict.py:90-121, its default): predictions scored against the true labels of
         ``celltype_file`` through ``map.xlsx`` (``get_map_dict``, preprocess.py:14-29).  Returns (correct, total, unsure,
-        acc, DataFrame with an 'original label' column, predict.py:138-143)."""
+        acc, DataFrame with an 'original label' column, predict.py:138-143).  ``normalize``: as for ``predict``."""
         map_file = Path(map_file) if map_file is not None else self.default_map_file()
         if map_file is None:
             raise FileNotFoundError(f"no map.xlsx next to the bundle under {self.bundle.root} (pass map_file)")
@@ -1035,9 +1100,9 @@ class ResidentPredictor:
         ct = pd.read_csv(celltype_file, index_col=0)
         ct.columns = ['cell', 'type']                                       # preprocess.py:147-150
         truth = ct['type'].map(str.strip).tolist()
-        test, index = _read_test_csr(data_file, self.file_type, self._gene2id, self.threshold)
-        if len(truth) != test.shape[0]:
-            raise ValueError(f"{celltype_file} lists {len(truth)} cells, {data_file} holds {test.shape[0]}")
+        test, index = self._read_test(data_file, normalize)
+        if len(truth) != len(index):
+            raise ValueError(f"{celltype_file} lists {len(truth)} cells, {data_file} holds {len(index)}")
         pred, _, _ = self.classify(test)
         correct, total, unsure, acc, _ = evaluate_predictions(pred, truth, self.id2label, map_dict[num])
         out = _prediction_frame(self.species, self.tissue, data_file, index, pred, self.id2label, self.bundle, None,

@@ -21,7 +21,21 @@
 // n_cols * 4 bytes).
 // Never a fault: a CSR entry whose col is outside [0, n_cols) is not looked up, a gene_map value outside [-1, n_genes) is not
 // stored; both are skipped and raise a bit in the caller's status word (an ordinary global atomic OR, off the data path).
+//
+// Log-normalising walk (wgnn_align_count_ln / wgnn_align_fill_ln, the LN instantiation of the same kernel): the operand holds
+// raw counts, total[r] is the fp64 sum of the caller's WHOLE row, and a candidate - a mapped column
+// with a finite count > 0 - becomes v = float(log1p(double(x) / total * scale)) before the keep test `v > threshold`; what is
+// no candidate becomes 0 and fails that test (threshold >= 0).  log1p in fp64 costs on the order of a hundred instructions a
+// wave, and a dense row is mostly zeros: the candidates of the 256 entries a wave holds in flight are packed into consecutive
+// slots of a 1 KB LDS slab (ballot + mbcnt, as the output slots), evaluated 64 at a time by consecutive lanes, and read back -
+// one round where a lane-per-column evaluation would take four.  COUNT and FILL run the same instructions on the same slab
+// order, so they agree on every keep decision.  The total: COUNT reads the row twice - first every column into the sum (a lane
+// adds its columns in ascending order, the 64 partial sums fold in a fixed butterfly; no atomics), storing it for FILL, then the
+// walk.  Measured once against a launch of its own for the totals (profiles/resident_lognorm.md): no difference in kernel time
+// that the run resolves (the normalising walk is bound by its fp64 arithmetic), so the launch was saved.  The summing read sees every column, so it is where a count that is negative, NaN or infinite is
+// skipped and reported (WGNN_ALIGN_BAD_VALUE).
 
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 #include "wgnn_common.h"
@@ -45,6 +59,8 @@ struct AArgs {
     int* row_count;                                            // COUNT
     const long long* out_rowptr; int* out_col; float* out_raw; // FILL
     int* status;
+    const double* total; double scale;                         // LN: the row totals (FILL reads them), Seurat's scale.factor
+    const double* lib; double* total_out;                      // LN COUNT: the caller's library sizes (or null), the totals it stores
 };
 
 // number of set bits of `mask` below this lane
@@ -65,7 +81,111 @@ __device__ __forceinline__ void put(const AArgs& a, long s, long room, int g, fl
     else bad |= WGNN_ALIGN_BAD_ROWPTR;
 }
 
-template <int FORM, bool FILL, typename TPtr>
+// LN: a count that can be kept - finite and > 0 (a -0.0, a NaN, a negative count and an infinity are none)
+__device__ __forceinline__ bool countable(float x) { return x > 0.f && x < __builtin_inff(); }
+
+// LN: the definition's value, fp64 throughout in Seurat's operation order (divide, scale, log1p), each step rounded on its own
+__device__ __forceinline__ float lognorm(float x, double total, double scale) {
+#pragma clang fp contract(off)
+    const double q = (double)x / total;
+    const double y = q * scale;
+    return (float)log1p(y);
+}
+
+// LN: the wave's candidates among the 4 entries per lane it holds (c[k]) become their log-normalised values, every other entry
+// 0.  Candidates are packed into the wave's slab (k-major, lane-minor), consecutive lanes evaluate consecutive slots, and each
+// candidate reads its slot back; the fences order the slab's writes and reads among the lanes of this one wave.
+__device__ __forceinline__ void lognorm_group(float* slab, int lane, float (&x)[4], const bool (&c)[4], double total, double scale) {
+    int pos[4], n = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long m = __ballot(c[k]);
+        pos[k] = n + below(m);
+        n += __popcll(m);
+    }
+    if (n == 0) {                                                // wave-uniform: no candidate, the slab is not touched
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] = 0.f;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (c[k]) slab[pos[k]] = x[k];                           // pos < n <= 256
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (int i = lane; i < n; i += 64) slab[i] = lognorm(slab[i], total, scale);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = c[k] ? slab[pos[k]] : 0.f;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// LN COUNT: one count into a lane's partial sum; what cannot be counted and is not a zero is reported and left out
+__device__ __forceinline__ void add_count(double& acc, float x, unsigned& bad) {
+    if (countable(x)) acc += (double)x;
+    else if (!(x == 0.f)) bad |= WGNN_ALIGN_BAD_VALUE;
+}
+
+// LN COUNT: the fp64 sum of row r over ALL its columns (CSR: all its stored entries), the same bits in every lane.  Fixed order: a
+// lane adds its entries in ascending position, then the 64 partial sums fold in a butterfly (both operands of every add are
+// the same pair in both lanes).  With library sizes, a row that holds a count takes the caller's value instead - a value that
+// is not finite and > 0 is reported and the row's total is 0 (the row keeps nothing).
+template <int FORM, typename TPtr>
+__device__ __forceinline__ double row_total(const AArgs& a, long r, int lane, unsigned& bad) {
+    double acc = 0.0;
+    if constexpr (FORM == FORM_DENSE_V4) {
+        const float* xr = a.x + (size_t)r * a.ld;
+        for (long j0 = 0; j0 < a.n_cols; j0 += 256 * kVecAhead) {
+            float4 v[kVecAhead];
+#pragma unroll
+            for (int u = 0; u < kVecAhead; ++u) {
+                const long j = j0 + u * 256 + lane * 4;
+                if (j + 3 < a.n_cols) v[u] = ld4(xr + j);
+                else {
+                    v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (j < a.n_cols) v[u].x = xr[j];
+                    if (j + 1 < a.n_cols) v[u].y = xr[j + 1];
+                    if (j + 2 < a.n_cols) v[u].z = xr[j + 2];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < kVecAhead; ++u) {
+                add_count(acc, v[u].x, bad); add_count(acc, v[u].y, bad);
+                add_count(acc, v[u].z, bad); add_count(acc, v[u].w, bad);
+            }
+        }
+    } else {
+        long b = 0, e = a.n_cols;
+        const float* vals = a.x + (FORM == FORM_DENSE ? (size_t)r * a.ld : 0);
+        if constexpr (FORM == FORM_CSR) {
+            const TPtr* rp = reinterpret_cast<const TPtr*>(a.rowptr);
+            b = rp[r]; e = rp[r + 1];
+            vals = a.val;
+        }
+        for (long j0 = b; j0 < e; j0 += 64 * kAhead) {
+            float v[kAhead];
+#pragma unroll
+            for (int u = 0; u < kAhead; ++u) {
+                const long j = j0 + u * 64 + lane;
+                v[u] = j < e ? vals[j] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < kAhead; ++u) add_count(acc, v[u], bad);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (a.lib && acc > 0.0) {                                  // wave-uniform
+        const double size = a.lib[r];
+        if (size > 0.0 && size < __builtin_inf()) acc = size;
+        else { bad |= WGNN_ALIGN_BAD_VALUE; acc = 0.0; }
+    }
+    return acc;
+}
+
+template <int FORM, bool FILL, bool LN, typename TPtr>
 __global__ void __launch_bounds__(kABlock) align_rows_kernel(const AArgs a) {
     const int lane = threadIdx.x & 63;
     const long stride = (long)gridDim.x * kAWaves;
@@ -74,6 +194,19 @@ __global__ void __launch_bounds__(kABlock) align_rows_kernel(const AArgs a) {
         long base = FILL ? (long)a.out_rowptr[r] : 0;
         const long first = base;
         const long room = FILL ? (long)a.out_rowptr[r + 1] : 0;      // a slot at or past it is not written (see `bad`)
+        double total = 0.0;
+        bool live = true;                                            // LN: the row has a total > 0 (wave-uniform); else it has
+        float* slab = nullptr;                                       // no candidate - nothing divided, nothing kept - and the walk
+                                                                     // below only reports malformed columns and map values
+        if constexpr (LN) {
+            __shared__ float s_slab[kAWaves][256];                   // the wave's candidates, packed (lognorm_group)
+            slab = s_slab[threadIdx.x >> 6];
+            if constexpr (!FILL) {                                   // the row's first read: every column into the total
+                total = row_total<FORM, TPtr>(a, r, lane, bad);
+                if (lane == 0) a.total_out[r] = total;
+            } else total = a.total[r];
+            live = total > 0.0;
+        }
         if constexpr (FORM == FORM_DENSE_V4) {
             const float* xr = a.x + (size_t)r * a.ld;
             for (long j0 = 0; j0 < a.n_cols; j0 += 256 * kVecAhead) {
@@ -91,6 +224,16 @@ __global__ void __launch_bounds__(kABlock) align_rows_kernel(const AArgs a) {
                         if (j < a.n_cols)     { v[u].x = xr[j];     g[u].x = a.gene_map[j]; }
                         if (j + 1 < a.n_cols) { v[u].y = xr[j + 1]; g[u].y = a.gene_map[j + 1]; }
                         if (j + 2 < a.n_cols) { v[u].z = xr[j + 2]; g[u].z = a.gene_map[j + 2]; }
+                    }
+                }
+                if constexpr (LN) {                                  // counts -> values; what is no candidate -> 0
+#pragma unroll
+                    for (int u = 0; u < kVecAhead; ++u) {
+                        float x[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+                        const bool c[4] = {live && g[u].x >= 0 && countable(x[0]), live && g[u].y >= 0 && countable(x[1]),
+                                           live && g[u].z >= 0 && countable(x[2]), live && g[u].w >= 0 && countable(x[3])};
+                        lognorm_group(slab, lane, x, c, total, a.scale);
+                        v[u] = make_float4(x[0], x[1], x[2], x[3]);
                     }
                 }
 #pragma unroll
@@ -137,6 +280,12 @@ __global__ void __launch_bounds__(kABlock) align_rows_kernel(const AArgs a) {
                         g[u] = on[u] ? a.gene_map[g[u]] : -1;
                     }
                 }
+                if constexpr (LN) {                                  // counts -> values; what is no candidate -> 0
+                    static_assert(kAhead == 4, "lognorm_group takes 4 entries per lane");
+                    const bool c[4] = {live && on[0] && g[0] >= 0 && countable(v[0]), live && on[1] && g[1] >= 0 && countable(v[1]),
+                                       live && on[2] && g[2] >= 0 && countable(v[2]), live && on[3] && g[3] >= 0 && countable(v[3])};
+                    lognorm_group(slab, lane, v, c, total, a.scale);
+                }
 #pragma unroll
                 for (int u = 0; u < kAhead; ++u) {
                     const bool k = keep_entry(a, on[u], g[u], v[u], bad);
@@ -155,12 +304,12 @@ __global__ void __launch_bounds__(kABlock) align_rows_kernel(const AArgs a) {
     if (bad) atomicOr(a.status, (int)bad);                     // malformed operands only
 }
 
-template <int FORM, bool FILL>
+template <int FORM, bool FILL, bool LN>
 int launch(const AArgs& a, bool i64, hipStream_t st) {
     const long want = (a.n_rows + kAWaves - 1) / kAWaves;
     const unsigned nb = (unsigned)(want < kAMaxBlocks ? want : kAMaxBlocks);
-    if (i64) hipLaunchKernelGGL((align_rows_kernel<FORM, FILL, long long>), dim3(nb), dim3(kABlock), 0, st, a);
-    else hipLaunchKernelGGL((align_rows_kernel<FORM, FILL, int>), dim3(nb), dim3(kABlock), 0, st, a);
+    if (i64) hipLaunchKernelGGL((align_rows_kernel<FORM, FILL, LN, long long>), dim3(nb), dim3(kABlock), 0, st, a);
+    else hipLaunchKernelGGL((align_rows_kernel<FORM, FILL, LN, int>), dim3(nb), dim3(kABlock), 0, st, a);
     return hipGetLastError() == hipSuccess ? WGNN_OK : WGNN_ERR_LAUNCH;
 }
 
@@ -189,12 +338,14 @@ const char* align_error_detail(int code) {
 }
 }  // namespace wgnn
 
-// the checks COUNT and FILL share, then the launch; fn names the entry point in the error detail
-template <bool FILL>
+// the checks COUNT and FILL share, then the launch; fn names the entry point in the error detail.  LN: the log-normalising walk
+// (COUNT stores the row totals in total_out, FILL reads them from total).
+template <bool FILL, bool LN>
 static int align_run(const char* fn, const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
                      int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
                      int32_t* row_count, const int64_t* out_rowptr, int32_t* out_col, float* out_raw, int32_t* status,
-                     uint32_t flags, void* stream) {
+                     uint32_t flags, void* stream, const double* total = nullptr, double scale = 0.0,
+                     double* total_out = nullptr, const double* library_size = nullptr) {
     auto fail = [fn](int code, const char* what) { return wgnn::align_fail(code, fn, what); };
     wgnn::align_err_code = 0;
     if (!status) return fail(WGNN_ERR_BAD_ARG, "status is required");
@@ -213,31 +364,54 @@ static int align_run(const char* fn, const float* x, int64_t ld, const void* row
     if (FILL && !wgnn::aligned8(out_rowptr)) return fail(WGNN_ERR_ALIGNMENT, "out_rowptr must be 8-byte aligned");
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(val) | reinterpret_cast<uintptr_t>(gene_map)) & 3u)
         return fail(WGNN_ERR_ALIGNMENT, "x, val and gene_map must be 4-byte aligned");
+    if (LN) {
+        if (!(threshold >= 0.f)) return fail(WGNN_ERR_BAD_ARG, "threshold must be >= 0 when normalising");
+        if (!(scale > 0.0 && scale < HUGE_VAL)) return fail(WGNN_ERR_BAD_ARG, "scale must be positive and finite");
+        if (n_rows > 0 && !(FILL ? total != nullptr : total_out != nullptr)) return fail(WGNN_ERR_BAD_ARG, "total is required");
+        if (!wgnn::aligned8(total) || !wgnn::aligned8(total_out) || !wgnn::aligned8(library_size))
+            return fail(WGNN_ERR_ALIGNMENT, "total and library_size must be 8-byte aligned");
+    }
     if (n_rows == 0) return WGNN_OK;
     AArgs a{};
     a.x = x; a.ld = ld; a.rowptr = rowptr; a.col = col; a.val = val; a.n_rows = n_rows; a.n_cols = n_cols;
     a.gene_map = gene_map; a.n_genes = n_genes; a.thr = threshold;
     a.row_count = row_count; a.out_rowptr = reinterpret_cast<const long long*>(out_rowptr); a.out_col = out_col; a.out_raw = out_raw;
-    a.status = status;
+    a.status = status; a.total = total; a.scale = scale; a.total_out = total_out; a.lib = library_size;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc;
-    if (!dense) rc = launch<FORM_CSR, FILL>(a, flags & WGNN_FLAG_ROWPTR_I64, st);
-    else if (wgnn::aligned16(x) && wgnn::aligned16(gene_map) && ld % 4 == 0) rc = launch<FORM_DENSE_V4, FILL>(a, false, st);
-    else rc = launch<FORM_DENSE, FILL>(a, false, st);
+    if (!dense) rc = launch<FORM_CSR, FILL, LN>(a, flags & WGNN_FLAG_ROWPTR_I64, st);
+    else if (wgnn::aligned16(x) && wgnn::aligned16(gene_map) && ld % 4 == 0) rc = launch<FORM_DENSE_V4, FILL, LN>(a, false, st);
+    else rc = launch<FORM_DENSE, FILL, LN>(a, false, st);
     return rc == WGNN_OK ? rc : fail(rc, "HIP launch failed");
 }
 
 extern "C" int wgnn_align_count(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
                                 int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
                                 int32_t* row_count, int32_t* status, uint32_t flags, void* stream) {
-    return align_run<false>("wgnn_align_count", x, ld, rowptr, col, val, n_rows, n_cols, gene_map, n_genes, threshold,
-                            row_count, nullptr, nullptr, nullptr, status, flags, stream);
+    return align_run<false, false>("wgnn_align_count", x, ld, rowptr, col, val, n_rows, n_cols, gene_map, n_genes, threshold,
+                                   row_count, nullptr, nullptr, nullptr, status, flags, stream);
 }
 
 extern "C" int wgnn_align_fill(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
                                int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
                                const int64_t* out_rowptr, int32_t* out_col, float* out_raw, int32_t* status,
                                uint32_t flags, void* stream) {
-    return align_run<true>("wgnn_align_fill", x, ld, rowptr, col, val, n_rows, n_cols, gene_map, n_genes, threshold,
-                           nullptr, out_rowptr, out_col, out_raw, status, flags, stream);
+    return align_run<true, false>("wgnn_align_fill", x, ld, rowptr, col, val, n_rows, n_cols, gene_map, n_genes, threshold,
+                                  nullptr, out_rowptr, out_col, out_raw, status, flags, stream);
+}
+
+extern "C" int wgnn_align_count_ln(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                                   int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                                   const double* library_size, double* total, double scale, int32_t* row_count, int32_t* status,
+                                   uint32_t flags, void* stream) {
+    return align_run<false, true>("wgnn_align_count_ln", x, ld, rowptr, col, val, n_rows, n_cols, gene_map, n_genes, threshold,
+                                  row_count, nullptr, nullptr, nullptr, status, flags, stream, nullptr, scale, total, library_size);
+}
+
+extern "C" int wgnn_align_fill_ln(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                                  int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                                  const double* total, double scale, const int64_t* out_rowptr, int32_t* out_col, float* out_raw,
+                                  int32_t* status, uint32_t flags, void* stream) {
+    return align_run<true, true>("wgnn_align_fill_ln", x, ld, rowptr, col, val, n_rows, n_cols, gene_map, n_genes, threshold,
+                                 nullptr, out_rowptr, out_col, out_raw, status, flags, stream, total, scale);
 }

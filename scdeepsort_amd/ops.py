@@ -1071,10 +1071,13 @@ def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Ten
 
 _ALIGN_STATUS = ((_lib.ALIGN_BAD_COL, "a CSR entry's column is outside [0, n_cols)"),
                  (_lib.ALIGN_BAD_MAP, "a gene_map value is outside [-1, n_genes)"),
-                 (_lib.ALIGN_BAD_ROWPTR, "a row kept more entries than were counted"))
+                 (_lib.ALIGN_BAD_ROWPTR, "a row kept more entries than were counted"),
+                 (_lib.ALIGN_BAD_VALUE, "a count is negative, NaN or infinite, or the library size of a row that holds counts "
+                                        "is not a finite number > 0"))
 
 
-def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.0):
+def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.0, normalize=None, scale: float = 1e4,
+               library_size=None):
     """``wgnn_align_count`` / ``wgnn_align_fill``: a batch over the caller's gene list as the bundle-vocabulary CSR that
     ``predict_rows`` takes.  ``expr``: a dense float32 ``[B, n_cols]`` device matrix (unit column stride; the row stride is its
     leading dimension) or a device ``(rowptr int32 / int64 [B+1], col int32, val float32)`` triple over the caller's columns.
@@ -1083,7 +1086,24 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
     An entry is kept iff its column maps to a gene and its value is ``> threshold`` (a NaN is dropped); a row's kept entries
     keep their input order and their bits.  Returns ``(rowptr int64 [B+1], col int32, raw float32)`` on the device: the count
     pass, a ``torch.cumsum``, one read-back of the total to size the outputs, the fill pass, and a read-back of the status word -
-    a column outside ``[0, n_cols)`` or a map value outside ``[-1, n_genes)`` raises ``WgnnError`` (the kernels skip it)."""
+    a column outside ``[0, n_cols)`` or a map value outside ``[-1, n_genes)`` raises ``WgnnError`` (the kernels skip it).
+
+    ``normalize="lognorm"``: ``expr`` holds raw counts and the values that leave are Seurat's ``LogNormalize``
+    (``wgnn_align_count_ln`` / ``wgnn_align_fill_ln``, the contract in ``include/wgnn.h``):
+    ``float32(log1p(float64(x) / total * scale))`` with ``total`` the fp64 sum of the cell's WHOLE row, columns outside the
+    bundle included; an entry is kept iff its column maps, its count is ``> 0`` and the value is ``> threshold``
+    (``threshold >= 0``, else ``ValueError``).  No normalised matrix is stored.  ``library_size``: a ``[B]`` vector (any real
+    dtype, made fp64 on the device) that replaces the totals.  A negative, NaN or infinite count on any column, or a library
+    size that is not finite and ``> 0`` on a cell that holds a count, raises ``WgnnError``.  Still two host synchronisations."""
+    if normalize not in (None, "lognorm"):
+        raise ValueError(f"normalize = {normalize!r}: pass None or \"lognorm\"")
+    lognorm = normalize is not None
+    if lognorm and not float(threshold) >= 0:
+        raise ValueError(f"threshold = {threshold} must be >= 0 when normalising (a dropped entry counts as 0)")
+    if lognorm and not (0 < float(scale) < float("inf")):
+        raise ValueError(f"scale = {scale} must be positive and finite")
+    if not lognorm and library_size is not None:
+        raise ValueError("library_size belongs to normalize=\"lognorm\"")
     dense = isinstance(expr, torch.Tensor)
     if not dense and not (isinstance(expr, (tuple, list)) and len(expr) == 3):
         raise WgnnError("align_rows takes a dense [B, n_cols] tensor or a (rowptr, col, val) triple")
@@ -1118,14 +1138,30 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     head = (_ptr(x), ld, _ptr(rowptr), _ptr(col), _ptr(val), B, n_cols, _ptr(gene_map), G, float(threshold))
-    _lib.check(_lib.call(dev, "wgnn_align_count", *head, _ptr(counts), _ptr(status), flags, _stream(dev)), "wgnn_align_count")
+    if lognorm:
+        lib = None
+        if library_size is not None:
+            lib = library_size if isinstance(library_size, torch.Tensor) else torch.as_tensor(library_size)
+            if lib.dim() != 1 or lib.shape[0] != B or lib.is_complex():
+                raise ValueError(f"library_size must be a real vector with one entry per cell ({B}), got {tuple(lib.shape)}")
+            lib = lib.to(dev).to(torch.float64).contiguous()       # widened on the device
+        row_total = torch.empty(B, dtype=torch.float64, device=dev)    # alive until the fill pass has been launched
+        ln = (_ptr(row_total), float(scale))                       # the count pass stores the totals, the fill pass reads them
+        _lib.check(_lib.call(dev, "wgnn_align_count_ln", *head, _ptr(lib), *ln, _ptr(counts), _ptr(status), flags, _stream(dev)),
+                   "wgnn_align_count_ln")
+    else:
+        _lib.check(_lib.call(dev, "wgnn_align_count", *head, _ptr(counts), _ptr(status), flags, _stream(dev)), "wgnn_align_count")
     out_rowptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
     torch.cumsum(counts, 0, dtype=torch.int64, out=out_rowptr[1:])
     total = int(out_rowptr[-1])                              # the one read-back that sizes the outputs
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_raw = torch.empty(total, dtype=torch.float32, device=dev)
-    _lib.check(_lib.call(dev, "wgnn_align_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status), flags,
-                         _stream(dev)), "wgnn_align_fill")
+    if lognorm:
+        _lib.check(_lib.call(dev, "wgnn_align_fill_ln", *head, *ln, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status),
+                             flags, _stream(dev)), "wgnn_align_fill_ln")
+    else:
+        _lib.check(_lib.call(dev, "wgnn_align_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status), flags,
+                             _stream(dev)), "wgnn_align_fill")
     bits = int(status)
     if bits:
         raise WgnnError("align_rows: " + "; ".join(text for bit, text in _ALIGN_STATUS if bits & bit))
