@@ -606,6 +606,39 @@ int wgnn_align_fill_ln(const float* x, int64_t ld, const void* rowptr, const int
                        const double* total, double scale, const int64_t* out_rowptr, int32_t* out_col, float* out_raw,
                        int32_t* status, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Vocabulary coverage (additive export, WGNN_VERSION stays 206): how much of a batch over the CALLER's gene list the bundle
+ * sees - what wgnn_align_count / _fill drop without a word.  The operand is wgnn_align_count's, in the same two forms (dense
+ * x / ld, or CSR rowptr / col / val with WGNN_FLAG_ROWPTR_I64), with gene_map [n_cols] and n_genes; it is only read.
+ * An entry COUNTS iff its value is finite and > 0 (the candidates of wgnn_align_count_ln: a 0, a -0.0, a NaN, a negative and
+ * an infinite value do not count).  A column is MAPPED iff gene_map[j] >= 0.
+ * Per row r (all [n_rows]):
+ *   n_expressed int32 : counting entries over ALL of the caller's columns (CSR: all the row's stored entries).
+ *   n_mapped    int32 : those on mapped columns.
+ *   total       double: the sum of the counting values over all columns - bit for bit the total wgnn_align_count_ln stores
+ *                       for the same operand without library_size (the same code: a lane adds its entries in ascending
+ *                       position, the wave's 64 partial sums fold in a fixed butterfly).
+ *   total_mapped double: the same sum over the mapped columns only, in the same fixed order.
+ *   n_bad       int32 : entries that are negative, NaN or infinite.  They are counted here and are in no other output; this
+ *                       is a diagnostic, no status bit is raised for them.
+ * Per caller column j:
+ *   col_cells int32 [n_cols]: rows in which column j counts (written in full: cleared on the stream, then raised).
+ * No floating-point atomics: the sums have a fixed order; the column counts are integer atomics (one per workgroup and column
+ * for the dense form, whose columns are walked a second time by column-owning threads; one per counting entry for the CSR
+ * form).  Two launches on the same operand give identical bits in every output.  Any n_cols.
+ * Malformed operands never fault and raise wgnn_align's bits in *status (int32, device memory, zeroed by the caller; required):
+ * a CSR entry with col outside [0, n_cols) is not looked up - it stays one of the row's stored entries (n_expressed, total, as
+ * in wgnn_align_count_ln's total) but is unmapped and in no column's count - WGNN_ALIGN_BAD_COL; a gene_map value outside
+ * [-1, n_genes) counts as unmapped, WGNN_ALIGN_BAD_MAP.  B = 0 and n_cols = 0 are valid.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (status NULL, both or neither input form, ld < n_cols, the i64 flag on the dense
+ * form, n_genes <= 0, negative sizes, a missing output, unknown flag), WGNN_ERR_ALIGNMENT (total / total_mapped not 8-byte,
+ * x / val / gene_map / an int32 output not 4-byte aligned); wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+int wgnn_coverage_rows(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                       int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes,
+                       int32_t* n_expressed, int32_t* n_mapped, int32_t* n_bad, double* total, double* total_mapped,
+                       int32_t* col_cells, int32_t* status, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,7 @@ SIGNATURES = {
                                       _u32, _vp]),
     "wgnn_align_fill_ln": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, C.c_double, _vp, _vp, _vp, _vp,
                                      _u32, _vp]),
+    "wgnn_coverage_rows": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
 }
 
 

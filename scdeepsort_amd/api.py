@@ -645,6 +645,110 @@ class MarkerTable:
         self.logit_sum = self.logit_sum + np.bincount(group[on], weights=np.asarray(logit, np.float64)[on], minlength=K)
 
 
+class CoverageSummary(dict):
+    """``Coverage.summary()``: a dict that prints as two or three lines."""
+
+    def __str__(self) -> str:
+        d = self
+        lines = [f"{d['n_matched']} of {d['n_columns']} columns are genes of the bundle; {d['n_bundle_absent']} of its "
+                 f"{d['n_bundle_genes']} genes are absent from the list",
+                 f"{d['n_cells']} cells: fraction of counts seen median {d['median_fraction_counts']:.3f}, min "
+                 f"{d['min_fraction_counts']:.3f}; fraction of expressed genes seen median {d['median_fraction_genes']:.3f}, "
+                 f"min {d['min_fraction_genes']:.3f}; {d['n_cells_below']} cells below {d['min_counts']:g} of their counts"]
+        if d["n_bad"]:
+            lines.append(f"{d['n_bad']} values are negative, NaN or infinite (left out of everything above)")
+        return "\n".join(lines)
+
+
+@dataclass
+class Coverage:
+    """``ResidentPredictor.coverage``'s report.  An entry COUNTS iff its value is finite and ``> 0``; a column is MATCHED iff
+    its name is a gene of the bundle.  Per cell (numpy ``[B]``): ``n_expressed`` / ``total`` = the counting entries over ALL
+    of the caller's columns and their fp64 sum (the library size ``align(..., normalize="lognorm")`` divides by),
+    ``n_mapped`` / ``total_mapped`` = the same over the matched columns - what the model sees - and ``n_bad`` = the values
+    that are negative, NaN or infinite (in none of the others).  ``col_cells`` (int32 ``[n_columns]``, on the device): the
+    cells in which each column counts.  ``columns``: the caller's names (``None`` when a gene map was passed)."""
+    n_columns: int
+    n_matched: int
+    n_bundle_genes: int
+    n_bundle_absent: int
+    n_expressed: np.ndarray
+    n_mapped: np.ndarray
+    n_bad: np.ndarray
+    total: np.ndarray
+    total_mapped: np.ndarray
+    col_cells: torch.Tensor
+    index: Sequence
+    columns: Optional[List[str]] = None
+    matched: Optional[np.ndarray] = None             # bool [n_columns]
+    absent_ids: Optional[np.ndarray] = None          # bundle gene ids no column names, ascending
+    absent_support_cells: Optional[np.ndarray] = None  # support cells that express each of them
+    absent_names: Optional[List[str]] = None
+    n_support_cells: int = 0
+
+    def fraction_counts(self) -> np.ndarray:
+        """``total_mapped / total`` per cell: the share of the cell's counts on genes the model knows; 0 where ``total == 0``."""
+        t = np.asarray(self.total, np.float64)
+        return np.divide(np.asarray(self.total_mapped, np.float64), t, out=np.zeros_like(t), where=t > 0)
+
+    def fraction_genes(self) -> np.ndarray:
+        """``n_mapped / n_expressed`` per cell; 0 where ``n_expressed == 0``."""
+        n = np.asarray(self.n_expressed, np.float64)
+        return np.divide(np.asarray(self.n_mapped, np.float64), n, out=np.zeros_like(n), where=n > 0)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: the per-cell columns and the two fractions."""
+        return pd.DataFrame({"n_expressed": self.n_expressed, "n_mapped": self.n_mapped, "n_bad": self.n_bad,
+                             "total": self.total, "total_mapped": self.total_mapped,
+                             "fraction_counts": self.fraction_counts(), "fraction_genes": self.fraction_genes()},
+                            index=self.index)
+
+    def unmatched(self, k: int = 20) -> pd.DataFrame:
+        """The caller's columns outside the bundle, by the cells in which they count (descending, ties by lower position):
+        ``position``, ``gene`` (when the names are known), ``cells``, ``fraction_of_cells``."""
+        cells = self.col_cells.cpu().numpy().astype(np.int64)
+        pos = np.flatnonzero(~np.asarray(self.matched, bool))
+        pos = pos[np.argsort(-cells[pos], kind="stable")][:k]
+        B = len(self.n_expressed)
+        out = {"position": pos}
+        if self.columns is not None:
+            out["gene"] = [self.columns[i] for i in pos]
+        out["cells"] = cells[pos]
+        out["fraction_of_cells"] = cells[pos] / B if B else np.zeros(len(pos))
+        return pd.DataFrame(out)
+
+    def absent(self, k: int = 20) -> pd.DataFrame:
+        """The bundle's genes the caller's list lacks, by the support cells that express them (descending, ties by lower gene
+        id) - which missing genes the model leaned on in training: ``gene_id``, ``gene``, ``support_cells``,
+        ``fraction_of_support``."""
+        ids = np.asarray(self.absent_ids, np.int64)
+        n = np.asarray(self.absent_support_cells, np.int64)
+        order = np.argsort(-n, kind="stable")[:k]
+        out = {"gene_id": ids[order]}
+        if self.absent_names is not None:
+            out["gene"] = [self.absent_names[i] for i in order]
+        out["support_cells"] = n[order]
+        out["fraction_of_support"] = n[order] / self.n_support_cells if self.n_support_cells else np.zeros(len(order))
+        return pd.DataFrame(out)
+
+    def below(self, min_counts: float = 0.5, min_genes: int = 0) -> np.ndarray:
+        """Boolean ``[B]``: cells whose ``fraction_counts`` is below ``min_counts`` or whose ``n_mapped`` is below ``min_genes``."""
+        return (self.fraction_counts() < min_counts) | (np.asarray(self.n_mapped) < min_genes)
+
+    def summary(self, min_counts: float = 0.5, min_genes: int = 0) -> CoverageSummary:
+        """Matched and absent counts, the median and minimum of both fractions, the cells ``below`` the given bounds and the
+        number of bad values; ``print`` it."""
+        fc, fg = self.fraction_counts(), self.fraction_genes()
+        stat = lambda a, f: float(f(a)) if a.size else 0.0
+        return CoverageSummary(
+            n_columns=self.n_columns, n_matched=self.n_matched, n_bundle_genes=self.n_bundle_genes,
+            n_bundle_absent=self.n_bundle_absent, n_cells=int(fc.size),
+            median_fraction_counts=stat(fc, np.median), min_fraction_counts=stat(fc, np.min),
+            median_fraction_genes=stat(fg, np.median), min_fraction_genes=stat(fg, np.min),
+            min_counts=float(min_counts), min_genes=int(min_genes),
+            n_cells_below=int(self.below(min_counts, min_genes).sum()), n_bad=int(np.asarray(self.n_bad, np.int64).sum()))
+
+
 @dataclass(frozen=True)
 class LogNormalize:
     """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
@@ -794,9 +898,10 @@ class ResidentPredictor:
         with torch.cuda.device(self.device), torch.no_grad():
             return self._align(expr, genes, threshold, normalize)
 
-    def _align(self, expr, genes, threshold, normalize=None):
+    def _caller_batch(self, expr, genes):
+        """``expr`` and ``genes`` of ``align`` / ``coverage`` as the ops take them: the batch on the device (a float32 matrix or
+        a CSR triple over the caller's columns) and the int32 gene map."""
         dev = self.device
-        spec = self.normalize if normalize is None else _normalize_spec(normalize)
         if isinstance(genes, torch.Tensor):
             gmap = genes.to(device=dev, dtype=torch.int32).contiguous()
             if gmap.dim() != 1:
@@ -804,7 +909,6 @@ class ResidentPredictor:
         else:
             gmap = self.gene_map(genes)
         n_cols = int(gmap.shape[0])
-        thr = self.threshold if threshold is None else threshold
         if isinstance(expr, (tuple, list)):
             rowptr, col, val = expr
             _ops._require_cuda(rowptr, col, val)
@@ -824,6 +928,12 @@ class ResidentPredictor:
                 raise ValueError(f"expression matrix has {x.shape[1]} columns, the gene list {n_cols} names")
             x = x.to(device=dev, dtype=torch.float32)
             batch = x if x.stride(1) == 1 and (x.shape[0] <= 1 or x.stride(0) >= n_cols) else x.contiguous()
+        return batch, gmap
+
+    def _align(self, expr, genes, threshold, normalize=None):
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
+        batch, gmap = self._caller_batch(expr, genes)
+        thr = self.threshold if threshold is None else threshold
         if spec is None:
             return _ops.align_rows(batch, gmap, self.n_genes, float(thr))
         return _ops.align_rows(batch, gmap, self.n_genes, float(thr), normalize="lognorm", scale=float(spec.scale_factor),
@@ -837,6 +947,41 @@ class ResidentPredictor:
         if len(index) != len(pred):
             raise ValueError(f"index names {len(index)} cells, the batch holds {len(pred)}")
         return _prediction_frame(self.species, self.tissue, "matrix", index, pred, self.id2label, self.bundle, None)
+
+    def coverage(self, expr, genes, index=None) -> "Coverage":
+        """How much of a batch over the caller's own gene list the bundle's vocabulary sees - what ``align`` drops without a
+        word (``wgnn_coverage_rows``, computed on the device where the batch is).  ``expr`` and ``genes`` exactly as ``align``
+        takes them; there is no ``normalize`` or ``threshold``: the report describes the operand as given, and an entry
+        counts iff its value is finite and ``> 0``.  ``index``: the cells' names (default ``range(B)``).  A matrix with
+        Ensembl ids, another species' casing or old synonyms classifies from a fraction of each cell's reads; read
+        ``Coverage.summary()`` before trusting ``classify`` on a new source.  Nothing else of the predictor calls this."""
+        with torch.cuda.device(self.device), torch.no_grad():
+            batch, gmap = self._caller_batch(expr, genes)
+            n_expressed, n_mapped, n_bad, total, total_mapped, col_cells = _ops.coverage_rows(batch, gmap, self.n_genes)
+        ids = gmap.cpu().numpy()
+        matched = ids >= 0
+        present = np.zeros(self.n_genes, bool)
+        present[ids[matched]] = True
+        absent = np.flatnonzero(~present)
+        if getattr(self, "_support_detected", None) is None:                      # support cells that express each gene: once
+            self._support_detected = np.bincount(self.support.indices, minlength=self.n_genes)
+        detected = self._support_detected
+        names = None if isinstance(genes, torch.Tensor) else [str(g) for g in genes]
+        B = int(n_expressed.shape[0])
+        index = pd.RangeIndex(B) if index is None else index
+        if len(index) != B:
+            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        return Coverage(n_columns=int(ids.shape[0]), n_matched=int(matched.sum()), n_bundle_genes=self.n_genes,
+                        n_bundle_absent=int(absent.shape[0]), n_expressed=n_expressed.cpu().numpy(),
+                        n_mapped=n_mapped.cpu().numpy(), n_bad=n_bad.cpu().numpy(), total=total.cpu().numpy(),
+                        total_mapped=total_mapped.cpu().numpy(), col_cells=col_cells, index=index, columns=names,
+                        matched=matched, absent_ids=absent, absent_support_cells=detected[absent],
+                        absent_names=[self.id2gene[i] for i in absent], n_support_cells=int(self.support.shape[0]))
+
+    def coverage_file(self, input_file) -> "Coverage":
+        """``coverage`` of a test file: its full table and gene names, the cells named by the file's index."""
+        df = _read_expression(input_file, self.file_type)
+        return self.coverage(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], index=df.index)
 
     def _device_csr(self, expr):
         """A batch as the kernels take it: (rowptr, col int32, raw f32) on the device, whether its gene ids are in range by

@@ -39,6 +39,7 @@
 #include <stdio.h>
 #include <string.h>
 #include "wgnn_common.h"
+#include "wgnn_align_rows.h"
 
 namespace {
 using namespace wgnn;
@@ -46,10 +47,7 @@ using namespace wgnn;
 constexpr int kAWaves = 8;                    // waves per workgroup, as the predict kernel
 constexpr int kABlock = 64 * kAWaves;
 constexpr int kAMaxBlocks = 1024;             // 256 CUs x 4 workgroups: grid-stride beyond that
-constexpr int kAhead = 4;                     // 64-entry steps in flight per wave (scalar forms)
-constexpr int kVecAhead = 2;                  // 256-entry steps in flight per wave (16-byte dense form)
-
-enum { FORM_DENSE = 0, FORM_DENSE_V4 = 1, FORM_CSR = 2 };
+// kAhead / kVecAhead (steps in flight per wave) and the FORM_* operand forms: wgnn_align_rows.h
 
 struct AArgs {
     const float* x; long ld;                                   // dense
@@ -80,9 +78,6 @@ __device__ __forceinline__ void put(const AArgs& a, long s, long room, int g, fl
     if (s < room) { a.out_col[s] = g; a.out_raw[s] = v; }
     else bad |= WGNN_ALIGN_BAD_ROWPTR;
 }
-
-// LN: a count that can be kept - finite and > 0 (a -0.0, a NaN, a negative count and an infinity are none)
-__device__ __forceinline__ bool countable(float x) { return x > 0.f && x < __builtin_inff(); }
 
 // LN: the definition's value, fp64 throughout in Seurat's operation order (divide, scale, log1p), each step rounded on its own
 __device__ __forceinline__ float lognorm(float x, double total, double scale) {
@@ -122,61 +117,16 @@ __device__ __forceinline__ void lognorm_group(float* slab, int lane, float (&x)[
     __builtin_amdgcn_wave_barrier();
 }
 
-// LN COUNT: one count into a lane's partial sum; what cannot be counted and is not a zero is reported and left out
-__device__ __forceinline__ void add_count(double& acc, float x, unsigned& bad) {
-    if (countable(x)) acc += (double)x;
-    else if (!(x == 0.f)) bad |= WGNN_ALIGN_BAD_VALUE;
-}
-
 // LN COUNT: the fp64 sum of row r over ALL its columns (CSR: all its stored entries), the same bits in every lane.  Fixed order: a
 // lane adds its entries in ascending position, then the 64 partial sums fold in a butterfly (both operands of every add are
-// the same pair in both lanes).  With library sizes, a row that holds a count takes the caller's value instead - a value that
-// is not finite and > 0 is reported and the row's total is 0 (the row keeps nothing).
+// the same pair in both lanes) - row_visit / wave_fold of wgnn_align_rows.h, which wgnn_coverage_rows shares.  With library
+// sizes, a row that holds a count takes the caller's value instead - a value that is not finite and > 0 is reported and the
+// row's total is 0 (the row keeps nothing).
 template <int FORM, typename TPtr>
 __device__ __forceinline__ double row_total(const AArgs& a, long r, int lane, unsigned& bad) {
     double acc = 0.0;
-    if constexpr (FORM == FORM_DENSE_V4) {
-        const float* xr = a.x + (size_t)r * a.ld;
-        for (long j0 = 0; j0 < a.n_cols; j0 += 256 * kVecAhead) {
-            float4 v[kVecAhead];
-#pragma unroll
-            for (int u = 0; u < kVecAhead; ++u) {
-                const long j = j0 + u * 256 + lane * 4;
-                if (j + 3 < a.n_cols) v[u] = ld4(xr + j);
-                else {
-                    v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (j < a.n_cols) v[u].x = xr[j];
-                    if (j + 1 < a.n_cols) v[u].y = xr[j + 1];
-                    if (j + 2 < a.n_cols) v[u].z = xr[j + 2];
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < kVecAhead; ++u) {
-                add_count(acc, v[u].x, bad); add_count(acc, v[u].y, bad);
-                add_count(acc, v[u].z, bad); add_count(acc, v[u].w, bad);
-            }
-        }
-    } else {
-        long b = 0, e = a.n_cols;
-        const float* vals = a.x + (FORM == FORM_DENSE ? (size_t)r * a.ld : 0);
-        if constexpr (FORM == FORM_CSR) {
-            const TPtr* rp = reinterpret_cast<const TPtr*>(a.rowptr);
-            b = rp[r]; e = rp[r + 1];
-            vals = a.val;
-        }
-        for (long j0 = b; j0 < e; j0 += 64 * kAhead) {
-            float v[kAhead];
-#pragma unroll
-            for (int u = 0; u < kAhead; ++u) {
-                const long j = j0 + u * 64 + lane;
-                v[u] = j < e ? vals[j] : 0.f;
-            }
-#pragma unroll
-            for (int u = 0; u < kAhead; ++u) add_count(acc, v[u], bad);
-        }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    row_visit<FORM, TPtr>(a, r, lane, [&](long, bool, float v) { add_count(acc, v, bad); });
+    acc = wave_fold(acc);
     if (a.lib && acc > 0.0) {                                  // wave-uniform
         const double size = a.lib[r];
         if (size > 0.0 && size < __builtin_inf()) acc = size;
@@ -321,7 +271,7 @@ thread_local int align_err_code = 0;
 thread_local char align_err_msg[256];
 thread_local char align_err_out[256];
 
-static int align_fail(int code, const char* fn, const char* what) {
+int align_fail(int code, const char* fn, const char* what) {
     (void)predict_error_detail(code);             // a detail another entry left unasked for this code would be handed out first:
     (void)attrib_error_detail(code);              // the last failing call is the one wgnn_last_error_string speaks of
     (void)markers_error_detail(code);
@@ -329,6 +279,8 @@ static int align_fail(int code, const char* fn, const char* what) {
     snprintf(align_err_msg, sizeof align_err_msg, "%s - %s: %s", wgnn_generic_error_string(code), fn, what);
     return code;
 }
+
+void align_error_clear() { align_err_code = 0; }
 
 const char* align_error_detail(int code) {
     if (code == 0 || code != align_err_code) return nullptr;

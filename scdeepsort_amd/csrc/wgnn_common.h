@@ -154,7 +154,9 @@ const char* wgnn_generic_error_string(int code);
 const char* predict_error_detail(int code);
 const char* attrib_error_detail(int code);       // the same for wgnn_attrib_rows / wgnn_rows_topk
 const char* markers_error_detail(int code);      // and for wgnn_group_gene_reduce
-const char* align_error_detail(int code);        // and for wgnn_align_count / wgnn_align_fill
+const char* align_error_detail(int code);        // and for wgnn_align_count / wgnn_align_fill / wgnn_coverage_rows
+int align_fail(int code, const char* fn, const char* what);      // records that detail for entry point `fn`, returns code
+void align_error_clear();                                        // a new call of those entries forgets the last detail
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }

@@ -1076,6 +1076,43 @@ _ALIGN_STATUS = ((_lib.ALIGN_BAD_COL, "a CSR entry's column is outside [0, n_col
                                         "is not a finite number > 0"))
 
 
+def _align_operand(name: str, expr, gene_map: torch.Tensor, n_genes: int):
+    """The checks ``align_rows`` and ``coverage_rows`` make of their batch: ``(dev, x, ld, rowptr, col, val, B, n_cols, G,
+    flags)`` as the C entry points take them (the other form's tensors ``None``)."""
+    dense = isinstance(expr, torch.Tensor)
+    if not dense and not (isinstance(expr, (tuple, list)) and len(expr) == 3):
+        raise WgnnError(f"{name} takes a dense [B, n_cols] tensor or a (rowptr, col, val) triple")
+    dev = _require_cuda(gene_map, *((expr,) if dense else expr))
+    if gene_map.dtype != torch.int32 or gene_map.dim() != 1 or not gene_map.is_contiguous():
+        raise WgnnError("gene_map must be a contiguous int32 vector")
+    n_cols, G = int(gene_map.shape[0]), int(n_genes)
+    if G <= 0:
+        raise WgnnError(f"{name}: n_genes = {G} must be positive")
+    x = rowptr = col = val = None
+    ld = flags = 0
+    if dense:
+        x = expr
+        if x.dtype != torch.float32 or x.dim() != 2:
+            raise WgnnError(f"{name} takes a 2-D float32 matrix, got {x.dtype} with {x.dim()} dimensions")
+        if x.shape[1] != n_cols:
+            raise WgnnError(f"the matrix has {x.shape[1]} columns, gene_map {n_cols} entries")
+        B = int(x.shape[0])
+        if (n_cols > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n_cols):
+            raise WgnnError(f"{name} takes row-major rows (unit column stride, row stride >= n_cols)")
+        ld = int(x.stride(0)) if B > 1 else n_cols           # a single row's stride says nothing
+    else:
+        rowptr, col, val = expr
+        if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
+            raise WgnnError(f"{name} takes rowptr int32 / int64, col int32, val float32")
+        if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
+            raise WgnnError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, val {tuple(val.shape)}")
+        if not (rowptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()):
+            raise WgnnError(f"{name} takes contiguous rowptr, col and val")
+        B = int(rowptr.shape[0]) - 1
+        flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    return dev, x, ld, rowptr, col, val, B, n_cols, G, flags
+
+
 def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.0, normalize=None, scale: float = 1e4,
                library_size=None):
     """``wgnn_align_count`` / ``wgnn_align_fill``: a batch over the caller's gene list as the bundle-vocabulary CSR that
@@ -1104,37 +1141,7 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
         raise ValueError(f"scale = {scale} must be positive and finite")
     if not lognorm and library_size is not None:
         raise ValueError("library_size belongs to normalize=\"lognorm\"")
-    dense = isinstance(expr, torch.Tensor)
-    if not dense and not (isinstance(expr, (tuple, list)) and len(expr) == 3):
-        raise WgnnError("align_rows takes a dense [B, n_cols] tensor or a (rowptr, col, val) triple")
-    dev = _require_cuda(gene_map, *((expr,) if dense else expr))
-    if gene_map.dtype != torch.int32 or gene_map.dim() != 1 or not gene_map.is_contiguous():
-        raise WgnnError("gene_map must be a contiguous int32 vector")
-    n_cols, G = int(gene_map.shape[0]), int(n_genes)
-    if G <= 0:
-        raise WgnnError(f"align_rows: n_genes = {G} must be positive")
-    x = rowptr = col = val = None
-    ld = flags = 0
-    if dense:
-        x = expr
-        if x.dtype != torch.float32 or x.dim() != 2:
-            raise WgnnError(f"align_rows takes a 2-D float32 matrix, got {x.dtype} with {x.dim()} dimensions")
-        if x.shape[1] != n_cols:
-            raise WgnnError(f"the matrix has {x.shape[1]} columns, gene_map {n_cols} entries")
-        B = int(x.shape[0])
-        if (n_cols > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n_cols):
-            raise WgnnError("align_rows takes row-major rows (unit column stride, row stride >= n_cols)")
-        ld = int(x.stride(0)) if B > 1 else n_cols           # a single row's stride says nothing
-    else:
-        rowptr, col, val = expr
-        if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
-            raise WgnnError("align_rows takes rowptr int32 / int64, col int32, val float32")
-        if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
-            raise WgnnError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, val {tuple(val.shape)}")
-        if not (rowptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()):
-            raise WgnnError("align_rows takes contiguous rowptr, col and val")
-        B = int(rowptr.shape[0]) - 1
-        flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    dev, x, ld, rowptr, col, val, B, n_cols, G, flags = _align_operand("align_rows", expr, gene_map, n_genes)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
     head = (_ptr(x), ld, _ptr(rowptr), _ptr(col), _ptr(val), B, n_cols, _ptr(gene_map), G, float(threshold))
@@ -1166,3 +1173,28 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
     if bits:
         raise WgnnError("align_rows: " + "; ".join(text for bit, text in _ALIGN_STATUS if bits & bit))
     return out_rowptr, out_col, out_raw
+
+
+def coverage_rows(expr, gene_map: torch.Tensor, n_genes: int):
+    """``wgnn_coverage_rows``: what of a batch over the caller's gene list the bundle's vocabulary sees.  ``expr`` and
+    ``gene_map`` as ``align_rows`` takes them (a dense float32 ``[B, n_cols]`` device matrix or a device CSR triple over the
+    caller's columns); the batch is only read.  An entry counts iff its value is finite and ``> 0``.
+
+    Returns six device tensors ``(n_expressed int32 [B], n_mapped int32 [B], n_bad int32 [B], total float64 [B],
+    total_mapped float64 [B], col_cells int32 [n_cols])``: per cell the counting entries over all columns and over the mapped
+    ones, the entries that are negative, NaN or infinite (in no other output), the fp64 sum of the counting values over all
+    columns - the very bits ``align_rows(..., normalize="lognorm")`` divides by - and over the mapped ones; per column the
+    cells in which it counts.  Two calls give identical bits.  One read-back, of the status word: a column outside
+    ``[0, n_cols)`` or a map value outside ``[-1, n_genes)`` raises ``WgnnError`` with ``align_rows``' message."""
+    dev, x, ld, rowptr, col, val, B, n_cols, G, flags = _align_operand("coverage_rows", expr, gene_map, n_genes)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_expressed, n_mapped, n_bad = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    total, total_mapped = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
+    col_cells = torch.empty(n_cols, dtype=torch.int32, device=dev)       # cleared by the entry point, on the stream
+    _lib.check(_lib.call(dev, "wgnn_coverage_rows", _ptr(x), ld, _ptr(rowptr), _ptr(col), _ptr(val), B, n_cols, _ptr(gene_map), G,
+                         _ptr(n_expressed), _ptr(n_mapped), _ptr(n_bad), _ptr(total), _ptr(total_mapped), _ptr(col_cells),
+                         _ptr(status), flags, _stream(dev)), "wgnn_coverage_rows")
+    bits = int(status)
+    if bits:
+        raise WgnnError("coverage_rows: " + "; ".join(text for bit, text in _ALIGN_STATUS if bits & bit))
+    return n_expressed, n_mapped, n_bad, total, total_mapped, col_cells
