@@ -607,6 +607,46 @@ int wgnn_align_fill_ln(const float* x, int64_t ld, const void* rowptr, const int
                        int32_t* status, uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Merging log-normalising alignment (additive exports, WGNN_VERSION stays 206): wgnn_align_count_ln / _fill_ln for a gene list
+ * in which several columns name ONE bundle gene (several Ensembl ids of a symbol, a symbol and its synonym).  The counts of
+ * such columns are added per cell BEFORE the logarithm - counts add, log-values do not.
+ * A GROUP is the set of columns that name one bundle gene, when there are two or more of them (its MEMBERS; all carry the same
+ * gene_map value).  The caller describes the groups by three int32 device tables:
+ *   col_group  [n_cols]       : the group of column j in [0, n_groups), or -1 for a column that is alone in its gene;
+ *   group_ptr  [n_groups + 1] : group s has the members group_cols[group_ptr[s] .. group_ptr[s + 1]);
+ *   group_cols [n_members]    : member columns, ascending within a group.
+ * For cell r and a group with gene g:
+ *   total[r]  is unchanged - the fp64 sum over ALL of the caller's columns, members like any other; library_size replaces it.
+ *   c = the fp64 sum of double(x[r, j]) over the members that COUNT (finite and > 0), added in the row's input order:
+ *       ascending column for a dense row, ascending position for a CSR row (whatever the column ids say);
+ *   v = float( log1p( c / total[r] * scale ) ), the operation order of wgnn_align_count_ln;
+ *   ONE entry (g, v) is kept iff c > 0 && v > threshold - a group may pass a positive threshold jointly - and it sits where the
+ *   FIRST counting member sits in the row's input order; every later member leaves nothing.
+ * A column that is alone behaves exactly as in wgnn_align_count_ln / _fill_ln, and a row in which no group has two counting
+ * members leaves bit for bit what those leave.  COUNT and FILL take the same decisions by the same instructions; no atomics on
+ * the data path, two launches are bit-identical.  A CSR row may hold any number of member entries (beyond 256 counting ones the
+ * walk searches the row's own entries instead of a list in LDS: slower, the same result).
+ * Both operand forms, every argument, status bit and error as wgnn_align_count_ln / _fill_ln; a negative, NaN or infinite
+ * count on a member raises WGNN_ALIGN_BAD_VALUE like on any column.  Malformed tables never fault: a col_group value outside
+ * [-1, n_groups) (the column is then alone), a group_ptr range outside [0, n_members] (clamped) and a member outside
+ * [0, n_cols) (skipped) raise WGNN_ALIGN_BAD_MAP (the CSR form finds a row's members by col_group alone and does not read
+ * group_ptr / group_cols).  Rows are read 16 bytes per lane when col_group is 16-byte aligned too.
+ * n_groups == 0 runs wgnn_align_count_ln / _fill_ln themselves (the tables may be NULL then).  Further errors: WGNN_ERR_BAD_ARG
+ * (n_groups or n_members negative, a table NULL), WGNN_ERR_ALIGNMENT (a table not 4-byte aligned).
+ * ------------------------------------------------------------------------- */
+int wgnn_align_count_ln_merge(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                              int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                              const int32_t* col_group, const int32_t* group_ptr, const int32_t* group_cols,
+                              int32_t n_groups, int32_t n_members, const double* library_size, double* total, double scale,
+                              int32_t* row_count, int32_t* status, uint32_t flags, void* stream);
+int wgnn_align_fill_ln_merge(const float* x, int64_t ld, const void* rowptr, const int32_t* col, const float* val,
+                             int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes, float threshold,
+                             const int32_t* col_group, const int32_t* group_ptr, const int32_t* group_cols,
+                             int32_t n_groups, int32_t n_members, const double* total, double scale,
+                             const int64_t* out_rowptr, int32_t* out_col, float* out_raw, int32_t* status,
+                             uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Vocabulary coverage (additive export, WGNN_VERSION stays 206): how much of a batch over the CALLER's gene list the bundle
  * sees - what wgnn_align_count / _fill drop without a word.  The operand is wgnn_align_count's, in the same two forms (dense
  * x / ld, or CSR rowptr / col / val with WGNN_FLAG_ROWPTR_I64), with gene_map [n_cols] and n_genes; it is only read.

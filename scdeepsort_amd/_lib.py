@@ -79,6 +79,10 @@ SIGNATURES = {
                                       _u32, _vp]),
     "wgnn_align_fill_ln": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, C.c_double, _vp, _vp, _vp, _vp,
                                      _u32, _vp]),
+    "wgnn_align_count_ln_merge": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, _vp, _i32, _i32,
+                                            _vp, _vp, C.c_double, _vp, _vp, _u32, _vp]),
+    "wgnn_align_fill_ln_merge": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, _vp, _i32, _i32,
+                                           _vp, C.c_double, _vp, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_coverage_rows": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
 }
 

@@ -383,21 +383,59 @@ def _read_test_csr(input_file, file_type, gene2id: dict, threshold) -> Tuple[sp.
     return test, df.index
 
 
-def _gene_map_ids(genes, gene2id: dict) -> np.ndarray:
-    """The caller's gene list as bundle ids: int32 [len(genes)], names compared as ``str`` (as ``_read_test_csr`` compares
-    column names), -1 for a name outside the bundle.  Two positions naming the same bundle gene, or no name inside the
-    bundle at all, raise ValueError."""
-    ids = np.fromiter((gene2id.get(str(g), -1) for g in genes), dtype=np.int64, count=len(genes)).astype(np.int32)
+DUPLICATES = ("error", "drop", "first", "sum")
+
+
+def _resolve_genes(genes, gene2id: dict, aliases=None, duplicates: str = "error"):
+    """The caller's gene list as bundle ids, and the columns that share a gene: ``(ids int32 [len(genes)], groups)``.
+    Names are compared as ``str`` (as ``_read_test_csr`` compares column names); a name outside the bundle is looked up in
+    ``aliases`` (caller name -> bundle gene name) - a name that IS a bundle gene is never aliased (exact symbols first, as
+    reference ``pre-process.R:14-16``), an alias whose target is no bundle gene leaves -1.  No name inside the bundle at all
+    raises ValueError.  Positions that name the same bundle gene form a group, and ``duplicates`` says what becomes of it:
+    ``"error"`` raises ValueError, ``"drop"`` sets every member to -1 (the reference keeps the names that occur once,
+    ``pre-process.R``: ``genedata1$Freq == 1``), ``"first"`` keeps the lowest position, ``"sum"`` keeps all of them and returns
+    ``groups = (col_group int32 [len(genes)], group_ptr int32 [n_groups + 1], group_cols int32 [n_members])`` - a position's
+    group or -1, and each group's positions, ascending (groups by ascending gene id).  ``groups`` is ``None`` otherwise, and
+    whenever nothing collides."""
+    if duplicates not in DUPLICATES:
+        raise ValueError(f"duplicates = {duplicates!r}: pass one of {', '.join(map(repr, DUPLICATES))}")
+    alias = {str(k): str(v) for k, v in aliases.items()} if aliases else {}
+
+    def lookup(g):
+        name = str(g)
+        i = gene2id.get(name, -1)
+        return gene2id.get(alias[name], -1) if i < 0 and name in alias else i
+
+    ids = np.fromiter((lookup(g) for g in genes), dtype=np.int64, count=len(genes)).astype(np.int32)
     hit = ids[ids >= 0]
     if hit.size == 0:
         raise ValueError(f"none of the {len(ids)} gene names is a gene of the bundle ({len(gene2id)} genes)")
     uniq, first, n = np.unique(hit, return_index=True, return_counts=True)
-    if (n > 1).any():
+    if not (n > 1).any():
+        return ids, None
+    if duplicates == "error":
         dup = int(uniq[n > 1][0])
         where = np.flatnonzero(ids == dup)[:2].tolist()
         raise ValueError(f"positions {where[0]} and {where[1]} of the gene list both name bundle gene {dup} "
                          f"({str(genes[where[0]])!r}): a cell may list a gene once")
-    return ids
+    member = np.isin(ids, uniq[n > 1])
+    if duplicates == "drop":
+        ids[member] = -1
+        return ids, None
+    pos = np.flatnonzero(member)
+    pos = pos[np.argsort(ids[pos], kind="stable")]                       # by gene, ascending position within a gene
+    starts = np.flatnonzero(np.r_[True, np.diff(ids[pos]) != 0])
+    if duplicates == "first":
+        ids[np.delete(pos, starts)] = -1
+        return ids, None
+    col_group = np.full(len(ids), -1, np.int32)
+    col_group[pos] = np.repeat(np.arange(len(starts), dtype=np.int32), np.diff(np.r_[starts, len(pos)]))
+    return ids, (col_group, np.r_[starts, len(pos)].astype(np.int32), pos.astype(np.int32))
+
+
+def _gene_map_ids(genes, gene2id: dict, aliases=None, duplicates: str = "error") -> np.ndarray:
+    """``_resolve_genes``' ids alone (``duplicates="sum"`` needs the groups as well: use ``_resolve_genes``)."""
+    return _resolve_genes(genes, gene2id, aliases, duplicates)[0]
 
 
 def _load_model(b: dict, dev) -> GNN:
@@ -685,6 +723,7 @@ class Coverage:
     absent_support_cells: Optional[np.ndarray] = None  # support cells that express each of them
     absent_names: Optional[List[str]] = None
     n_support_cells: int = 0
+    n_merged_columns: int = 0                        # matched columns that share their gene with another (a GeneMap's groups)
 
     def fraction_counts(self) -> np.ndarray:
         """``total_mapped / total`` per cell: the share of the cell's counts on genes the model knows; 0 where ``total == 0``."""
@@ -769,6 +808,26 @@ def _normalize_spec(normalize) -> Optional[LogNormalize]:
 
 
 @dataclass
+class GeneMap:
+    """``ResidentPredictor.gene_map(..., duplicates="sum")`` of a gene list in which several columns name one bundle gene:
+    ``ids`` (int32 ``[n_cols]``, on the device) as the plain map, and the colliding columns as the tables the merging walk
+    takes (``wgnn_align_count_ln_merge``): ``col_group`` int32 ``[n_cols]`` = a column's group or -1 when it is alone in its
+    gene, ``group_ptr`` int32 ``[n_groups + 1]`` / ``group_cols`` int32 = each group's columns, ascending.
+    ``n_merged_columns`` = the columns that are in a group.  Pass it as ``genes=`` wherever a gene map is taken; the batch
+    must then hold raw counts (``normalize=``): the members' counts are added per cell before the logarithm."""
+    ids: torch.Tensor
+    col_group: torch.Tensor
+    group_ptr: torch.Tensor
+    group_cols: torch.Tensor
+    n_groups: int
+    n_merged_columns: int
+
+    @property
+    def groups(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.col_group, self.group_ptr, self.group_cols
+
+
+@dataclass
 class _Aligned:
     """``ResidentPredictor.align``'s output on its way into the kernels: gene ids in range by construction."""
     csr: Tuple[torch.Tensor, torch.Tensor, torch.Tensor]
@@ -789,14 +848,24 @@ class ResidentPredictor:
 
     ``normalize`` (``None`` | ``"lognorm"`` | ``LogNormalize``): the default of the ``normalize=`` argument of every method
     that takes ``genes=`` or a file - set it when the batches and files hold raw counts (``LogNormalize``).  A batch given
-    over the bundle's own gene ids (no ``genes=``) is never normalised."""
+    over the bundle's own gene ids (no ``genes=``) is never normalised.
+
+    ``aliases`` / ``duplicates``: how a list of NAMES passed as ``genes=``, and a file's column names, are resolved
+    (``gene_map``): a mapping from other names (Ensembl ids, synonyms) to bundle gene names, and what becomes of columns
+    that then name the same gene - ``"error"`` | ``"drop"`` | ``"first"`` | ``"sum"`` (add their raw counts on the device;
+    needs ``normalize``).  With either set, files are read through ``align``; with both at their defaults nothing changes."""
 
     normalize: Optional[LogNormalize] = None
+    aliases: Optional[dict] = None
+    duplicates: str = "error"
 
     def __init__(self, species, tissue, model_path='pretrained', gpu_id=0, unsure_rate=2., file_type='csv', threshold=0,
-                 seed=10086, normalize=None):
+                 seed=10086, normalize=None, aliases=None, duplicates="error"):
         self.species, self.tissue, self.unsure_rate, self.file_type, self.threshold = species, tissue, unsure_rate, file_type, threshold
         self.normalize = _normalize_spec(normalize)
+        if duplicates not in DUPLICATES:
+            raise ValueError(f"duplicates = {duplicates!r}: pass one of {', '.join(map(repr, DUPLICATES))}")
+        self.aliases, self.duplicates = (dict(aliases) if aliases else None), duplicates
         self.model_path = Path(model_path)
         self.device = _device(gpu_id)
         self.last_route: Optional[str] = None
@@ -871,12 +940,26 @@ class ResidentPredictor:
         return _Aligned(self._align(expr, genes, None, normalize))
 
     # ---------------------------------------------------------------------------------------------
-    def gene_map(self, genes) -> torch.Tensor:
+    def gene_map(self, genes, aliases=None, duplicates="error"):
         """The caller's gene list as ``align`` wants it: int32 ``[len(genes)]`` on the device, a name's bundle gene id or -1
         for a name outside the bundle (names compared as ``str``).  Raises ValueError when two positions name the same
         bundle gene (a cell may list a gene once) or when no name is in the bundle.  Build it once for a stream of batches
-        and pass it as ``genes=``."""
-        return torch.from_numpy(_gene_map_ids(genes, self._gene2id)).to(self.device)
+        and pass it as ``genes=``.
+
+        ``aliases``: a mapping from a caller's name to a bundle gene name (an Ensembl id or a synonym to its symbol),
+        consulted only for names that are no bundle gene themselves; a target outside the bundle leaves the column
+        unmatched.  ``duplicates``: what becomes of columns that name the same bundle gene - ``"error"`` (the ValueError
+        above), ``"drop"`` (all of them unmatched: the reference's R step keeps the names that occur once), ``"first"`` (the
+        lowest position stays) or ``"sum"``: all stay and their raw counts are added per cell inside ``align`` - the return
+        value is then a ``GeneMap``, which every ``genes=`` takes, and the batch must be normalised there.  Without a
+        collision the result is the plain tensor whatever ``duplicates`` is."""
+        ids, groups = _resolve_genes(genes, self._gene2id, aliases, duplicates)
+        dev = self.device
+        if groups is None:
+            return torch.from_numpy(ids).to(dev)
+        col_group, group_ptr, group_cols = (torch.from_numpy(a).to(dev) for a in groups)
+        return GeneMap(ids=torch.from_numpy(ids).to(dev), col_group=col_group, group_ptr=group_ptr, group_cols=group_cols,
+                       n_groups=int(group_ptr.shape[0]) - 1, n_merged_columns=int(group_cols.shape[0]))
 
     def align(self, expr, genes, threshold=None, normalize=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """An in-memory batch over the caller's own gene list as the device ``(rowptr int64, col int32, raw f32)`` triple
@@ -884,7 +967,10 @@ class ResidentPredictor:
         columns outside the bundle and values ``<= threshold`` (default: the predictor's) are dropped, a cell's kept
         entries keep the caller's order and their bits.  ``expr``: a 2-D ``torch.Tensor`` on any device (other dtypes are
         converted to float32), a 2-D numpy array, a scipy sparse matrix, or a device ``(rowptr, col, val)`` triple whose
-        column ids index ``genes``.  ``genes``: the column names, or the tensor ``gene_map`` made of them.  The file route
+        column ids index ``genes``.  ``genes``: the column names (resolved with the predictor's ``aliases`` / ``duplicates``),
+        or what ``gene_map`` made of them - a tensor, or a ``GeneMap`` whose colliding columns are added per cell before the
+        logarithm (``wgnn_align_count_ln_merge`` / ``_fill_ln_merge``; raw counts and ``normalize`` required, else
+        ``ValueError``; the merged entry sits where the cell's first counting member sits).  The file route
         (``predict``) lists a cell's genes by ascending bundle id instead; the two orders coincide, and the results are
         bit-identical, when the caller's bundle genes come in the bundle's order.
 
@@ -900,14 +986,17 @@ class ResidentPredictor:
 
     def _caller_batch(self, expr, genes):
         """``expr`` and ``genes`` of ``align`` / ``coverage`` as the ops take them: the batch on the device (a float32 matrix or
-        a CSR triple over the caller's columns) and the int32 gene map."""
+        a CSR triple over the caller's columns), the int32 gene map, and the ``GeneMap`` it came from (or ``None``).  A list
+        of names is resolved with the predictor's ``aliases`` / ``duplicates``."""
         dev = self.device
-        if isinstance(genes, torch.Tensor):
-            gmap = genes.to(device=dev, dtype=torch.int32).contiguous()
-            if gmap.dim() != 1:
-                raise ValueError("a gene map is a vector (ResidentPredictor.gene_map)")
-        else:
-            gmap = self.gene_map(genes)
+        merged = None
+        if not isinstance(genes, (torch.Tensor, GeneMap)):
+            genes = self.gene_map(genes, self.aliases, self.duplicates)
+        if isinstance(genes, GeneMap):
+            merged, genes = genes, genes.ids
+        gmap = genes.to(device=dev, dtype=torch.int32).contiguous()
+        if gmap.dim() != 1:
+            raise ValueError("a gene map is a vector (ResidentPredictor.gene_map)")
         n_cols = int(gmap.shape[0])
         if isinstance(expr, (tuple, list)):
             rowptr, col, val = expr
@@ -928,16 +1017,20 @@ class ResidentPredictor:
                 raise ValueError(f"expression matrix has {x.shape[1]} columns, the gene list {n_cols} names")
             x = x.to(device=dev, dtype=torch.float32)
             batch = x if x.stride(1) == 1 and (x.shape[0] <= 1 or x.stride(0) >= n_cols) else x.contiguous()
-        return batch, gmap
+        return batch, gmap, merged
 
     def _align(self, expr, genes, threshold, normalize=None):
         spec = self.normalize if normalize is None else _normalize_spec(normalize)
-        batch, gmap = self._caller_batch(expr, genes)
+        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
+        if spec is None and (isinstance(genes, GeneMap) or (by_name and self.duplicates == "sum")):
+            raise ValueError("duplicates=\"sum\" needs normalize=: the batch then holds log-values, and their sum is not the log "
+                             "of the summed counts (pass raw counts and normalize=\"lognorm\", or duplicates=\"drop\" / \"first\")")
+        batch, gmap, merged = self._caller_batch(expr, genes)
         thr = self.threshold if threshold is None else threshold
         if spec is None:
             return _ops.align_rows(batch, gmap, self.n_genes, float(thr))
         return _ops.align_rows(batch, gmap, self.n_genes, float(thr), normalize="lognorm", scale=float(spec.scale_factor),
-                               library_size=spec.library_size)
+                               library_size=spec.library_size, groups=None if merged is None else merged.groups)
 
     def predict_matrix(self, expr, genes, index=None, normalize=None) -> pd.DataFrame:
         """``predict`` for an in-memory batch over the caller's gene list (``expr``, ``genes``, ``normalize`` as ``align``
@@ -952,11 +1045,13 @@ class ResidentPredictor:
         """How much of a batch over the caller's own gene list the bundle's vocabulary sees - what ``align`` drops without a
         word (``wgnn_coverage_rows``, computed on the device where the batch is).  ``expr`` and ``genes`` exactly as ``align``
         takes them; there is no ``normalize`` or ``threshold``: the report describes the operand as given, and an entry
-        counts iff its value is finite and ``> 0``.  ``index``: the cells' names (default ``range(B)``).  A matrix with
+        counts iff its value is finite and ``> 0``.  A ``GeneMap`` (or names that collide under ``duplicates="sum"``) counts
+        every member column as matched and reports them in ``n_merged_columns``.  ``index``: the cells' names (default
+        ``range(B)``).  A matrix with
         Ensembl ids, another species' casing or old synonyms classifies from a fraction of each cell's reads; read
         ``Coverage.summary()`` before trusting ``classify`` on a new source.  Nothing else of the predictor calls this."""
         with torch.cuda.device(self.device), torch.no_grad():
-            batch, gmap = self._caller_batch(expr, genes)
+            batch, gmap, merged = self._caller_batch(expr, genes)
             n_expressed, n_mapped, n_bad, total, total_mapped, col_cells = _ops.coverage_rows(batch, gmap, self.n_genes)
         ids = gmap.cpu().numpy()
         matched = ids >= 0
@@ -966,7 +1061,7 @@ class ResidentPredictor:
         if getattr(self, "_support_detected", None) is None:                      # support cells that express each gene: once
             self._support_detected = np.bincount(self.support.indices, minlength=self.n_genes)
         detected = self._support_detected
-        names = None if isinstance(genes, torch.Tensor) else [str(g) for g in genes]
+        names = None if isinstance(genes, (torch.Tensor, GeneMap)) else [str(g) for g in genes]
         B = int(n_expressed.shape[0])
         index = pd.RangeIndex(B) if index is None else index
         if len(index) != B:
@@ -976,7 +1071,8 @@ class ResidentPredictor:
                         n_mapped=n_mapped.cpu().numpy(), n_bad=n_bad.cpu().numpy(), total=total.cpu().numpy(),
                         total_mapped=total_mapped.cpu().numpy(), col_cells=col_cells, index=index, columns=names,
                         matched=matched, absent_ids=absent, absent_support_cells=detected[absent],
-                        absent_names=[self.id2gene[i] for i in absent], n_support_cells=int(self.support.shape[0]))
+                        absent_names=[self.id2gene[i] for i in absent], n_support_cells=int(self.support.shape[0]),
+                        n_merged_columns=0 if merged is None else merged.n_merged_columns)
 
     def coverage_file(self, input_file) -> "Coverage":
         """``coverage`` of a test file: its full table and gene names, the cells named by the file's index."""
@@ -1165,9 +1261,9 @@ class ResidentPredictor:
         file, and a cell's genes then come in the FILE's order - the results agree with the ascending-id route in everything
         but the last bits of a row sum (bit for bit when the file lists its bundle genes in the bundle's order)."""
         spec = self.normalize if normalize is None else _normalize_spec(normalize)
-        if spec is None:
+        if spec is None and self.aliases is None and self.duplicates == "error":
             return _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
-        df = _read_expression(input_file, self.file_type)
+        df = _read_expression(input_file, self.file_type)       # aliases / duplicates are align's: the file goes through it
         with torch.cuda.device(self.device), torch.no_grad():
             csr = self._align(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], None, spec)
         return _Aligned(csr), df.index

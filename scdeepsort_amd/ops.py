@@ -1114,7 +1114,7 @@ def _align_operand(name: str, expr, gene_map: torch.Tensor, n_genes: int):
 
 
 def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.0, normalize=None, scale: float = 1e4,
-               library_size=None):
+               library_size=None, groups=None):
     """``wgnn_align_count`` / ``wgnn_align_fill``: a batch over the caller's gene list as the bundle-vocabulary CSR that
     ``predict_rows`` takes.  ``expr``: a dense float32 ``[B, n_cols]`` device matrix (unit column stride; the row stride is its
     leading dimension) or a device ``(rowptr int32 / int64 [B+1], col int32, val float32)`` triple over the caller's columns.
@@ -1131,7 +1131,13 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
     bundle included; an entry is kept iff its column maps, its count is ``> 0`` and the value is ``> threshold``
     (``threshold >= 0``, else ``ValueError``).  No normalised matrix is stored.  ``library_size``: a ``[B]`` vector (any real
     dtype, made fp64 on the device) that replaces the totals.  A negative, NaN or infinite count on any column, or a library
-    size that is not finite and ``> 0`` on a cell that holds a count, raises ``WgnnError``.  Still two host synchronisations."""
+    size that is not finite and ``> 0`` on a cell that holds a count, raises ``WgnnError``.  Still two host synchronisations.
+
+    ``groups`` (``normalize="lognorm"`` only, else ``ValueError``): ``(col_group int32 [n_cols], group_ptr int32 [n_groups + 1],
+    group_cols int32 [n_members])`` on the device - the columns that name one bundle gene, whose counts are added per cell
+    before the logarithm (``wgnn_align_count_ln_merge`` / ``wgnn_align_fill_ln_merge``; the contract in ``include/wgnn.h``):
+    one entry per cell and gene, at the place of the first member that counts.  ``None``, or tables without a group, run the
+    kernels above - a caller without duplicates never runs the merging walk."""
     if normalize not in (None, "lognorm"):
         raise ValueError(f"normalize = {normalize!r}: pass None or \"lognorm\"")
     lognorm = normalize is not None
@@ -1141,6 +1147,21 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
         raise ValueError(f"scale = {scale} must be positive and finite")
     if not lognorm and library_size is not None:
         raise ValueError("library_size belongs to normalize=\"lognorm\"")
+    merge = ()
+    if groups is not None:
+        col_group, group_ptr, group_cols = groups
+        if not lognorm:
+            raise ValueError("groups belongs to normalize=\"lognorm\": counts add, log-values do not")
+        _require_cuda(gene_map, col_group, group_ptr, group_cols)
+        for name, tab in (("col_group", col_group), ("group_ptr", group_ptr), ("group_cols", group_cols)):
+            if tab.dtype != torch.int32 or tab.dim() != 1 or not tab.is_contiguous():
+                raise WgnnError(f"{name} must be a contiguous int32 vector")
+        if col_group.shape[0] != gene_map.shape[0] or group_ptr.shape[0] < 1:
+            raise WgnnError(f"col_group has {col_group.shape[0]} entries for {gene_map.shape[0]} columns, group_ptr "
+                            f"{group_ptr.shape[0]}")
+        if group_ptr.shape[0] > 1:                                 # no group: the walk without merging
+            merge = (_ptr(col_group), _ptr(group_ptr), _ptr(group_cols), int(group_ptr.shape[0]) - 1, int(group_cols.shape[0]))
+    sfx = "_merge" if merge else ""
     dev, x, ld, rowptr, col, val, B, n_cols, G, flags = _align_operand("align_rows", expr, gene_map, n_genes)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     counts = torch.empty(B, dtype=torch.int32, device=dev)
@@ -1154,8 +1175,8 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
             lib = lib.to(dev).to(torch.float64).contiguous()       # widened on the device
         row_total = torch.empty(B, dtype=torch.float64, device=dev)    # alive until the fill pass has been launched
         ln = (_ptr(row_total), float(scale))                       # the count pass stores the totals, the fill pass reads them
-        _lib.check(_lib.call(dev, "wgnn_align_count_ln", *head, _ptr(lib), *ln, _ptr(counts), _ptr(status), flags, _stream(dev)),
-                   "wgnn_align_count_ln")
+        _lib.check(_lib.call(dev, "wgnn_align_count_ln" + sfx, *head, *merge, _ptr(lib), *ln, _ptr(counts), _ptr(status), flags,
+                             _stream(dev)), "wgnn_align_count_ln" + sfx)
     else:
         _lib.check(_lib.call(dev, "wgnn_align_count", *head, _ptr(counts), _ptr(status), flags, _stream(dev)), "wgnn_align_count")
     out_rowptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
@@ -1164,14 +1185,17 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_raw = torch.empty(total, dtype=torch.float32, device=dev)
     if lognorm:
-        _lib.check(_lib.call(dev, "wgnn_align_fill_ln", *head, *ln, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status),
-                             flags, _stream(dev)), "wgnn_align_fill_ln")
+        _lib.check(_lib.call(dev, "wgnn_align_fill_ln" + sfx, *head, *merge, *ln, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw),
+                             _ptr(status), flags, _stream(dev)), "wgnn_align_fill_ln" + sfx)
     else:
         _lib.check(_lib.call(dev, "wgnn_align_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status), flags,
                              _stream(dev)), "wgnn_align_fill")
     bits = int(status)
     if bits:
-        raise WgnnError("align_rows: " + "; ".join(text for bit, text in _ALIGN_STATUS if bits & bit))
+        texts = [text for bit, text in _ALIGN_STATUS if bits & bit]
+        if merge and bits & _lib.ALIGN_BAD_MAP:
+            texts.append("or a group table (col_group, group_ptr, group_cols) points outside its range")
+        raise WgnnError("align_rows: " + "; ".join(texts))
     return out_rowptr, out_col, out_raw
 
 
