@@ -531,6 +531,45 @@ int wgnn_group_gene_reduce(const int32_t* t_rowptr, const int32_t* t_cell, const
                            void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Per-group class tables (additive exports, WGNN_VERSION stays 206): the reduction over cells behind
+ * api.ResidentPredictor.annotate - one cell type per CLUSTER from what wgnn_predict_rows leaves on the device.  For a batch of
+ * B cells with logits f32 [n_rows, ld_logits] (ld_logits >= n_classes = C; columns beyond C are never read), label int32
+ * [n_rows] (wgnn_predict_rows' label: a class id, or -1 = unsure) and K groups, per cell in fp64 from the f32 logits
+ *     m = max_j l_j,  e_j = exp((double)l_j - (double)m),  Z = sum_j e_j,  p_j = e_j / Z,  conf = max_j p_j = 1 / Z
+ * and a cell is BAD if its logits hold a NaN or a +inf or are all -inf (a -inf next to finite logits is fine: p_j = 0).  Over
+ * the cells of group k that are not bad:
+ *     prob_sum f64   [K, C] : sum of p_ij                  conf_sum f64 [K] : sum of conf_i
+ *     votes    int32 [K, C] : cells with label == j        tally int32 [K, 3] : {cells that take part, cells with label -1,
+ *                                                                              bad cells}; a bad cell counts in tally[k][2] only
+ * so tally[k][0] == sum_j votes[k][j] + tally[k][1].
+ * The batch comes GROUP-MAJOR: seg_ptr int64 [K + 1] (non-decreasing, 0 <= seg_ptr[0], seg_ptr[K] <= n_rows), order int32
+ * [seg_ptr[K]] with the ids of the cells of group k, ascending, in order[seg_ptr[k] .. seg_ptr[k + 1]); cells that take no part
+ * are absent.  An order entry outside [0, n_rows) or whose label is outside [-1, C) takes no part; a seg_ptr value outside
+ * [0, min(seg_ptr[K], n_rows)] is clamped into it: malformed operands never fault.  n_rows == 0 or seg_ptr[K] == 0 is valid
+ * (logits / label / order may be NULL then, the outputs are still written; with one of them NULL no cell takes part).
+ *   A group's run is cut into chunks of 256 cells (a constant of the kernel, not of the device), one wavefront per chunk, lanes
+ *   laid out (cell slot, class); per-cell max and Z by an xor butterfly, per-lane private fp64 sums, an xor butterfly over the
+ *   cell slots, one partial per chunk in the workspace; a second kernel adds a group's partials in ascending chunk order.  No
+ *   atomics of any kind; the order of a bin's additions depends on the operand alone: two launches are bit-identical whatever
+ *   the grid.  No limit on C beyond int32 (C > 64 walks the classes 64 at a time).
+ *   flags: WGNN_CLUSTERS_ACCUMULATE - add the batch to what the four outputs hold; without it EVERY element of all four is
+ *   written, zeros included (the caller does not pre-clear).
+ *   workspace: wgnn_group_class_reduce_workspace bytes, caller-owned, 8-byte aligned.
+ *   Errors, before any launch: WGNN_ERR_BAD_ARG (a NULL output or seg_ptr, K <= 0, C <= 0, ld_logits < C, n_rows outside
+ *   [0, 2^31), unknown flag), WGNN_ERR_ALIGNMENT (prob_sum / conf_sum / seg_ptr / workspace not 8-byte, the others not 4-byte
+ *   aligned), WGNN_ERR_WORKSPACE, WGNN_ERR_UNSUPPORTED (sizes whose workspace is beyond 2^63 bytes); wgnn_last_error_string
+ *   names the check.  Whether logits / label / order are missing while
+ *   seg_ptr[K] > 0 is not visible to the host without a read-back: wrappers check it.
+ * ------------------------------------------------------------------------- */
+#define WGNN_CLUSTERS_ACCUMULATE 256
+int wgnn_group_class_reduce_workspace(int64_t n_rows, int32_t n_groups, int32_t n_classes, int64_t* bytes);
+int wgnn_group_class_reduce(const float* logits, int64_t ld_logits, const int32_t* label,
+                            const int32_t* order, const void* seg_ptr /* int64_t[n_groups+1] */,
+                            int64_t n_rows, int32_t n_groups, int32_t n_classes,
+                            double* prob_sum, double* conf_sum, int32_t* votes, int32_t* tally,
+                            void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Batch alignment (additive exports, WGNN_VERSION stays 206): a batch over the CALLER's gene list made into the clean
  * bundle-vocabulary CSR that wgnn_predict_rows / wgnn_attrib_rows / wgnn_group_gene_reduce take - the device counterpart of the
  * column selection, `> threshold` and COO -> CSR of api._read_test_csr (reference preprocess.py:160-161, 173-178).  It runs

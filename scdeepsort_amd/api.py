@@ -683,6 +683,171 @@ class MarkerTable:
         self.logit_sum = self.logit_sum + np.bincount(group[on], weights=np.asarray(logit, np.float64)[on], minlength=K)
 
 
+def _cluster_ids(clusters, cluster_names=None, n_clusters=None, into: Optional["ClusterCalls"] = None,
+                 n_cells: Optional[int] = None) -> Tuple[np.ndarray, List[str]]:
+    """``annotate``'s ``clusters`` as ``(ids int64 [B], names)``.  A sequence of ``str`` is matched against ``into``'s names,
+    else against ``cluster_names``, else factorised in sorted order; an unknown name raises ValueError.  Integer ids (-1 =
+    the cell takes no part) need ``cluster_names``, ``n_clusters`` or ``into`` and are checked against ``[-1, K)``."""
+    if cluster_names is not None:
+        names = [str(n) for n in cluster_names]
+        if n_clusters is not None and int(n_clusters) != len(names):
+            raise ValueError(f"n_clusters = {n_clusters} but {len(names)} cluster names")
+    elif n_clusters is not None:
+        names = [str(i) for i in range(int(n_clusters))]
+    else:
+        names = None
+    if into is not None:
+        if names is not None and names != list(into.cluster_names):
+            raise ValueError("into: the table's cluster names differ from the batch's")
+        names = list(into.cluster_names)
+    arr = clusters.detach().cpu().numpy() if isinstance(clusters, torch.Tensor) else np.asarray(clusters)
+    if arr.ndim != 1:
+        raise ValueError(f"clusters must hold one id or name per cell, got shape {arr.shape}")
+    if n_cells is not None and arr.shape[0] != n_cells:
+        raise ValueError(f"clusters lists {arr.shape[0]} cells, the batch holds {n_cells}")
+    if arr.dtype.kind in "USO" and all(isinstance(c, str) for c in arr.tolist()):
+        if names is None:
+            names = sorted(set(arr.tolist()))
+        lookup = {n: i for i, n in enumerate(names)}
+        unknown = sorted(set(arr.tolist()) - set(lookup))
+        if unknown:
+            raise ValueError(f"cluster name {unknown[0]!r} is not one of the table's {len(names)} clusters")
+        ids = np.fromiter((lookup[c] for c in arr.tolist()), dtype=np.int64, count=arr.shape[0])
+    elif np.issubdtype(arr.dtype, np.integer):
+        if names is None:
+            raise ValueError("clusters given as integer ids need cluster_names or n_clusters")
+        ids = arr.astype(np.int64)
+        if ids.size and (ids.min() < -1 or ids.max() >= len(names)):
+            raise ValueError(f"cluster id out of range [-1, {len(names)})")
+    else:
+        raise ValueError(f"clusters must be integer ids or str names, got {arr.dtype}")
+    if not names:
+        raise ValueError("no clusters")
+    return ids, names
+
+
+def _call_names(ids, id2label: Sequence[str], label_map=None) -> Tuple[list, list]:
+    """(cell_type, cell_subtype) of cluster calls as ``_prediction_frame`` names per-cell ones: the label map's new type and
+    subtype names when there is one, ``unsure`` for -1, ``empty`` for -2, ``None`` for anything below (no call)."""
+    old2new, old2sub = label_map if label_map is not None else ({}, {})
+    names = [id2label[p] if p >= 0 else {-1: "unsure", -2: "empty"}.get(int(p)) for p in ids]
+    return [old2new.get(p, p) for p in names], [old2sub.get(p, p) for p in names]
+
+
+@dataclass
+class ClusterCalls:
+    """What ``ResidentPredictor.annotate`` returns: one row per cluster of a cohort.  K clusters (``cluster_names``), C cell
+    types (``id2label``).  The four tables of ``wgnn_group_class_reduce``, on the device they were made on (tables built
+    from CPU tensors serve the host logic just as well): ``prob_sum`` f64 [K, C] the cells' softmax probabilities summed
+    (fp64 from the f32 logits), ``conf_sum`` f64 [K] their largest probability summed, ``votes`` int32 [K, C] the cells per
+    predicted type, ``tally`` int32 [K, 3] = (cells that took part, of them unsure, bad cells: logits with a NaN or +inf or
+    all -inf, counted nowhere else).  ``unsure_rate``: the predictor's, for the ``"mean_prob"`` rule.  ``label_map``:
+    ``load_label_map``'s two dicts when the bundle has one."""
+    cluster_names: Sequence[str]
+    id2label: Sequence[str]
+    prob_sum: torch.Tensor
+    conf_sum: torch.Tensor
+    votes: torch.Tensor
+    tally: torch.Tensor
+    unsure_rate: float = 2.0
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    RULES = ("vote", "mean_prob")
+
+    @property
+    def n_cells(self) -> np.ndarray:
+        """int64 [K]: the cells of each cluster that took part (bad cells are not among them)."""
+        return self.tally[:, 0].cpu().numpy().astype(np.int64)
+
+    @property
+    def n_unsure(self) -> np.ndarray:
+        return self.tally[:, 1].cpu().numpy().astype(np.int64)
+
+    @property
+    def n_bad(self) -> np.ndarray:
+        return self.tally[:, 2].cpu().numpy().astype(np.int64)
+
+    def _cells(self) -> torch.Tensor:
+        return self.tally[:, :1].to(torch.float64)
+
+    def fraction(self) -> torch.Tensor:
+        """f64 [K, C]: ``votes / n_cells``, the share of a cluster's cells called each type (NaN for an empty cluster)."""
+        return self.votes.to(torch.float64) / self._cells()
+
+    def mean_prob(self) -> torch.Tensor:
+        """f64 [K, C]: ``prob_sum / n_cells``, the cluster's mean softmax distribution (NaN for an empty cluster)."""
+        return self.prob_sum / self._cells()
+
+    def _ranked(self, rule: str) -> Tuple[np.ndarray, np.ndarray]:
+        """The rule's score table as f64 [K, C] on the host (vote share | mean probability) and the classes of every cluster by
+        descending score, equal scores by the lower id (int64 [K, C])."""
+        if rule not in self.RULES:
+            raise ValueError(f"rule = {rule!r}: pass one of {', '.join(map(repr, self.RULES))}")
+        score = (self.fraction() if rule == "vote" else self.mean_prob()).cpu().numpy()
+        key = (self.votes if rule == "vote" else self.prob_sum).cpu().numpy()
+        return score, np.argsort(-key.astype(np.float64), axis=1, kind="stable")
+
+    def consensus(self, rule: str = "vote", min_fraction: float = 0.0) -> Tuple[np.ndarray, np.ndarray]:
+        """One call per cluster: ``(ids int64 [K], confidence f64 [K])``.  ``"vote"``: the type most of the cluster's cells were
+        called (equal counts: the lower id), confidence = its share of ``n_cells``; -1 (unsure) when strictly more cells are
+        unsure than voted for it, or when the share is ``< min_fraction``.  ``"mean_prob"``: the arg max of the cluster's mean
+        distribution, confidence = that mean probability; -1 when it is ``< float32(unsure_rate / C)`` - the per-cell rule
+        (reference ``predict.py:83``) applied to the mean.  A cluster without cells: -2 and NaN."""
+        score, ranked = self._ranked(rule)
+        K, C = score.shape
+        n, win = self.n_cells, ranked[:, 0]
+        conf = score[np.arange(K), win]
+        ids = win.astype(np.int64)
+        if rule == "vote":
+            top = self.votes.cpu().numpy().astype(np.int64)[np.arange(K), win]
+            ids[(self.n_unsure > top) | (conf < float(min_fraction))] = -1
+        else:
+            ids[conf < float(np.float32(self.unsure_rate / C))] = -1
+        ids[n == 0] = -2
+        return ids, np.where(n == 0, np.nan, conf)
+
+    def frame(self, rule: str = "vote", min_fraction: float = 0.0) -> pd.DataFrame:
+        """One row per cluster: ``cluster``, ``n_cells``, ``n_unsure``, ``n_bad``, the call as ``cell_type`` /
+        ``cell_subtype`` (named as ``predict`` names cells; ``unsure`` / ``empty`` spelled out; without a label map both hold
+        the bundle's name), then of the LEADING type - the rule's winner, also where the call came out unsure - ``fraction``
+        (its vote share), ``mean_prob`` and the cluster's ``mean_confidence`` (``conf_sum / n_cells``), and the runner-up
+        under the rule as ``second_type`` with its score (vote share | mean probability) as ``second_fraction`` (``None`` /
+        NaN when no other type scored)."""
+        ids, _ = self.consensus(rule, min_fraction)
+        score, ranked = self._ranked(rule)
+        K, C = score.shape
+        n, rows, win = self.n_cells, np.arange(K), ranked[:, 0]
+        types, subtypes = _call_names(ids, self.id2label, self.label_map)
+        second = ranked[:, 1] if C > 1 else np.zeros(K, np.int64)
+        second_score = score[rows, second] if C > 1 else np.full(K, np.nan)
+        has = (n > 0) & (second_score > 0) if C > 1 else np.zeros(K, bool)
+        second_names, _ = _call_names(np.where(has, second, -3), self.id2label, self.label_map)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean_conf = self.conf_sum.cpu().numpy() / n
+        return pd.DataFrame({"cluster": list(self.cluster_names), "n_cells": n, "n_unsure": self.n_unsure, "n_bad": self.n_bad,
+                             "cell_type": types, "cell_subtype": subtypes,
+                             "fraction": self.fraction().cpu().numpy()[rows, win], "mean_prob": self.mean_prob().cpu().numpy()[rows, win],
+                             "mean_confidence": mean_conf, "second_type": second_names,
+                             "second_fraction": np.where(has, second_score, np.nan)})
+
+    def cell_labels(self, clusters, rule: str = "vote", min_fraction: float = 0.0) -> np.ndarray:
+        """The clusters' calls broadcast back to the cells: int64 [B] for ``clusters`` as ``annotate`` takes them (ids, or
+        names of this table); a cell of cluster -1 gets -1."""
+        ids, _ = _cluster_ids(clusters, into=self)
+        calls, _ = self.consensus(rule, min_fraction)
+        return np.where(ids >= 0, calls[np.maximum(ids, 0)], -1).astype(np.int64)
+
+    def _require_same(self, cluster_names: Sequence[str], id2label: Sequence[str]) -> None:
+        """``into=``: the batch must be clustered and classified as this table is."""
+        K, C = self.prob_sum.shape
+        if len(cluster_names) != K:
+            raise ValueError(f"into: the table holds {K} clusters, the batch is clustered into {len(cluster_names)}")
+        if list(cluster_names) != list(self.cluster_names):
+            raise ValueError("into: the table's cluster names differ from the batch's")
+        if len(id2label) != C or list(id2label) != list(self.id2label):
+            raise ValueError("into: the table's cell types differ from the bundle's")
+
+
 class CoverageSummary(dict):
     """``Coverage.summary()``: a dict that prints as two or three lines."""
 
@@ -1032,14 +1197,33 @@ class ResidentPredictor:
         return _ops.align_rows(batch, gmap, self.n_genes, float(thr), normalize="lognorm", scale=float(spec.scale_factor),
                                library_size=spec.library_size, groups=None if merged is None else merged.groups)
 
-    def predict_matrix(self, expr, genes, index=None, normalize=None) -> pd.DataFrame:
+    def predict_matrix(self, expr, genes, index=None, normalize=None, clusters=None, rule: str = "vote",
+                       min_fraction: float = 0.0) -> pd.DataFrame:
         """``predict`` for an in-memory batch over the caller's gene list (``expr``, ``genes``, ``normalize`` as ``align``
-        takes them): the same table, ``index`` (default ``range(B)``) in place of the file's cell names."""
-        pred, _, _ = self.classify(expr, genes=genes, normalize=normalize)
+        takes them): the same table, ``index`` (default ``range(B)``) in place of the file's cell names.  ``clusters`` (one
+        ``str`` name or integer id per cell, -1 = none; ids are taken as ``0 .. max``): the table gains ``cluster_type`` and
+        ``cluster_subtype``, the call of the cell's cluster (``annotate``, ``ClusterCalls.consensus(rule, min_fraction)``) named
+        as ``cell_type`` is - both hold the bundle's name without a label map, ``None`` for a cell of no cluster."""
+        if clusters is None:
+            pred, _, _ = self.classify(expr, genes=genes, normalize=normalize)
+        else:
+            if rule not in ClusterCalls.RULES:
+                raise ValueError(f"rule = {rule!r}: pass one of {', '.join(map(repr, ClusterCalls.RULES))}")
+            arr = clusters.detach().cpu().numpy() if isinstance(clusters, torch.Tensor) else np.asarray(clusters)
+            by_id = np.issubdtype(arr.dtype, np.integer)
+            ids, names = _cluster_ids(arr, n_clusters=max(int(arr.max(initial=0)) + 1, 1) if by_id else None,
+                                      n_cells=self._n_cells(expr))
+            with torch.cuda.device(self.device), torch.no_grad():
+                calls, pred = self._annotate(self._over_genes(expr, genes, normalize), ids, names, None)
         index = pd.RangeIndex(len(pred)) if index is None else index
         if len(index) != len(pred):
             raise ValueError(f"index names {len(index)} cells, the batch holds {len(pred)}")
-        return _prediction_frame(self.species, self.tissue, "matrix", index, pred, self.id2label, self.bundle, None)
+        out = _prediction_frame(self.species, self.tissue, "matrix", index, pred, self.id2label, self.bundle, None)
+        if clusters is not None:
+            per_cluster, _ = calls.consensus(rule, min_fraction)
+            per_cell = np.where(ids >= 0, per_cluster[np.maximum(ids, 0)], -3)
+            out["cluster_type"], out["cluster_subtype"] = _call_names(per_cell, self.id2label, calls.label_map)
+        return out
 
     def coverage(self, expr, genes, index=None) -> "Coverage":
         """How much of a batch over the caller's own gene list the bundle's vocabulary sees - what ``align`` drops without a
@@ -1100,6 +1284,11 @@ class ResidentPredictor:
         return rowptr, col, raw, True, host
 
     def _classify(self, expr):
+        return self._classify_on_device(expr)[:3]
+
+    def _classify_on_device(self, expr):
+        """``_classify``'s three results, and the labels as the fused route leaves them on the device (int32 [B]; ``None`` on
+        the graph route, whose labels are made on the host)."""
         dev = self.device
         rowptr, col, raw, checked, host = self._device_csr(expr)
         nnz = int(col.shape[0])
@@ -1113,7 +1302,7 @@ class ResidentPredictor:
             host = host.astype(np.float32)
             logits = _graph_logits(self.model, self.support, host, self.gene_feat, dev)
             pred, prob = _classify(logits, self.unsure_rate)
-            return pred, prob.max(axis=1) if prob.shape[0] else np.zeros(0, np.float32), logits
+            return pred, prob.max(axis=1) if prob.shape[0] else np.zeros(0, np.float32), logits, None
         h = None
         for l in range(self.n_layers):
             self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
@@ -1124,7 +1313,68 @@ class ResidentPredictor:
                 logits, label, max_prob = _ops.predict_rows(rowptr, col, raw, self.tables[l], self.alpha, self.biases[l],
                                                             head=(self.w_head, self.b_head),
                                                             unsure_threshold=self.unsure_threshold, **kw)
-        return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits
+        return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits, label
+
+    # ---------------------------------------------------------------------------------------------
+    def annotate(self, expr, clusters, cluster_names: Optional[Sequence[str]] = None, n_clusters: Optional[int] = None,
+                 into: Optional[ClusterCalls] = None, genes=None, normalize=None) -> ClusterCalls:
+        """One cell type per CLUSTER: the batch is classified as ``classify`` does (either route), and its logits and labels
+        are reduced per (cluster, type) where they lie (``wgnn_group_class_reduce``: softmax and sums in fp64, deterministic,
+        no atomics) into a ``ClusterCalls`` - votes, summed probabilities, unsure and bad cells per cluster, with
+        ``consensus`` / ``frame`` / ``cell_labels`` on top.  ``expr``, ``genes`` and ``normalize`` as for ``classify``.
+        ``clusters``: one integer id per cell (-1 = skip) with ``cluster_names`` or ``n_clusters``, or one ``str`` name per
+        cell - factorised in sorted order, or matched against ``into``'s names.  ``into``: an earlier table of the same
+        bundle and clusters, which this batch is ADDED to (and which is returned): a cohort of any size streams through.
+        Shape, range and name errors are ``ValueError`` before anything is launched."""
+        ids, names = _cluster_ids(clusters, cluster_names, n_clusters, into, n_cells=self._n_cells(expr))
+        if into is not None:
+            into._require_same(names, self.id2label)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._annotate(self._over_genes(expr, genes, normalize), ids, names, into)[0]
+
+    @staticmethod
+    def _n_cells(expr) -> int:
+        if isinstance(expr, _Aligned):
+            expr = expr.csr
+        return int(expr[0].shape[0]) - 1 if isinstance(expr, (tuple, list)) else int(expr.shape[0])
+
+    def _label_names(self) -> Optional[Tuple[dict, dict]]:
+        map_file = self.bundle.label_map()
+        return None if map_file is None else load_label_map(map_file, self.species)
+
+    def _annotate(self, expr, ids: np.ndarray, names: Sequence[str], into: Optional[ClusterCalls]):
+        """(the table, the per-cell labels) of one classified batch; ``ids`` / ``names`` as ``_cluster_ids`` made them."""
+        pred, _, logits, label = self._classify_on_device(expr)
+        if label is None:                                 # the graph route classifies on the host
+            label = torch.from_numpy(pred.astype(np.int32)).to(self.device)
+        group = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+        out = None if into is None else (into.prob_sum, into.conf_sum, into.votes, into.tally)
+        tables = _ops.group_class_reduce(logits.float(), label, group, len(names), out=out, accumulate=into is not None,
+                                         check=False)
+        calls = into if into is not None else ClusterCalls(list(names), list(self.id2label), *tables,
+                                                           unsure_rate=self.unsure_rate, label_map=self._label_names())
+        return calls, pred
+
+    def annotate_file(self, input_file, clusters_file, save_path=None, normalize=None, rule: str = "vote",
+                      min_fraction: float = 0.0) -> pd.DataFrame:
+        """``annotate`` on a test file and a clusters file laid out as the reference's cell-type files (an index column, the
+        cell's name, its cluster's name; the cells in the data file's order, else ``ValueError``): ``ClusterCalls.frame(rule,
+        min_fraction)``, written as ``{species}_{tissue}_clusters.csv`` under ``save_path`` when given.  ``normalize``: as for
+        ``predict``.  Cluster names are compared as stripped ``str`` and come in sorted order."""
+        if rule not in ClusterCalls.RULES:
+            raise ValueError(f"rule = {rule!r}: pass one of {', '.join(map(repr, ClusterCalls.RULES))}")
+        test, index = self._read_test(input_file, normalize)
+        ct = pd.read_csv(clusters_file, index_col=0)
+        if ct.shape[1] != 2:
+            raise ValueError(f"{clusters_file}: expected an index column, the cell names and the cluster names")
+        ct.columns = ['cell', 'cluster']
+        if [str(c) for c in ct['cell']] != [str(c) for c in index]:
+            raise ValueError(f"cell order of {input_file} and {clusters_file} differs")
+        out = self.annotate(test, [str(c).strip() for c in ct['cluster']]).frame(rule, min_fraction)
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_clusters.csv", index=False)
+        return out
 
     # ---------------------------------------------------------------------------------------------
     def explain(self, expr, top_k: int = 10, target="predicted", genes=None, normalize=None) -> "Attribution":

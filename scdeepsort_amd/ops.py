@@ -1069,6 +1069,70 @@ def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Ten
     return total, count
 
 
+def group_class_reduce(logits: torch.Tensor, label: torch.Tensor, group: torch.Tensor, n_groups: int,
+                       out: Optional[tuple] = None, accumulate: bool = False, check: bool = True):
+    """``wgnn_group_class_reduce``: per (group, class) the fp64 sum of the cells' softmax probabilities, taken in fp64 from the
+    f32 ``logits`` [B, C] that ``predict_rows`` leaves (any row stride ``>= C``), with the votes of its ``label`` int32 /
+    int64 [B] (a class id, or -1 = unsure).  ``group`` int32 / int64 [B]: a cell's group in ``[0, n_groups)``, or -1 = the cell
+    takes no part.  A cell whose logits hold a NaN or a +inf, or are all -inf, is bad: counted in ``tally[:, 2]`` and in
+    nothing else.
+
+    Returns ``(prob_sum f64 [K, C], conf_sum f64 [K], votes int32 [K, C], tally int32 [K, 3])`` with ``tally[k] = (cells that
+    took part, cells with label -1, bad cells)`` - ``out`` when given (every element is written, the caller does not
+    pre-clear), added to with ``accumulate``.  The batch is re-ordered group-major on the device (a stable sort of the group
+    ids, the groups' bounds by a search in the sorted ids: no read-back), then one wavefront per 256-cell chunk of a group
+    adds in a fixed order: no atomics, two calls are bit-identical.  ``check``: verify the range of ``group`` (one ``aminmax``
+    and a read-back); without it an id outside ``[0, n_groups)`` takes no part."""
+    import ctypes as C
+    dev = _require_cuda(logits, label, group, *(out or ()))
+    K = int(n_groups)
+    if K <= 0:
+        raise WgnnError(f"group_class_reduce: n_groups = {K} must be positive")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[1] < 1:
+        raise WgnnError("group_class_reduce takes logits float32 [B, C] with C >= 1")
+    B, n_cls = logits.shape
+    if B >= 2 ** 31:
+        raise WgnnError("group_class_reduce: B >= 2^31 (split the batch and accumulate)")
+    if label.shape != (B,) or label.dtype not in (torch.int32, torch.int64):
+        raise WgnnError(f"label must hold one int32 / int64 class id per cell ([{B}]), got {label.dtype} {tuple(label.shape)}")
+    if group.shape != (B,):
+        raise WgnnError(f"group must hold one id per cell ([{B}]), got {tuple(group.shape)}")
+    if group.dtype not in (torch.int32, torch.int64):
+        raise WgnnError("group must be int32 / int64")
+    if check and B:
+        lo, hi = torch.aminmax(group)
+        if int(lo) < -1 or int(hi) >= K:
+            raise WgnnError(f"group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
+    if out is None:
+        if accumulate:
+            raise WgnnError("accumulate needs the tables to add to (out=)")
+        out = (torch.empty((K, n_cls), dtype=torch.float64, device=dev), torch.empty(K, dtype=torch.float64, device=dev),
+               torch.empty((K, n_cls), dtype=torch.int32, device=dev), torch.empty((K, 3), dtype=torch.int32, device=dev))
+    if len(out) != 4:
+        raise WgnnError("out must be (prob_sum, conf_sum, votes, tally)")
+    want = ((K, n_cls), torch.float64), ((K,), torch.float64), ((K, n_cls), torch.int32), ((K, 3), torch.int32)
+    if any(tuple(o.shape) != s or o.dtype != d or not o.is_contiguous() for o, (s, d) in zip(out, want)):
+        raise WgnnError(f"out must be contiguous (float64 [{K}, {n_cls}], float64 [{K}], int32 [{K}, {n_cls}], int32 [{K}, 3])")
+    prob_sum, conf_sum, votes, tally = out
+    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < n_cls):
+        logits = logits.contiguous()
+    ld = logits.stride(0) if B > 1 else max(int(logits.stride(0)), n_cls)
+    label = label.to(torch.int32).contiguous()
+    ids = group.to(torch.int64)
+    ids = torch.where((ids < 0) | (ids >= K), torch.full_like(ids, K), ids)       # the cells that take no part sort last
+    ids, order = torch.sort(ids, stable=True)                                     # cells of a group ascending
+    seg_ptr = torch.searchsorted(ids, torch.arange(K + 1, dtype=torch.int64, device=dev)).contiguous()
+    order = order.to(torch.int32)
+    nb = C.c_int64()
+    _lib.check(_lib.lib().wgnn_group_class_reduce_workspace(B, K, n_cls, C.addressof(nb)), "wgnn_group_class_reduce_workspace")
+    ws = torch.empty(nb.value // 8 + 1, dtype=torch.float64, device=dev)
+    rc = _lib.call(dev, "wgnn_group_class_reduce", _ptr(logits), ld, _ptr(label), _ptr(order), _ptr(seg_ptr), B, K, n_cls,
+                   _ptr(prob_sum), _ptr(conf_sum), _ptr(votes), _ptr(tally), _ptr(ws), ws.numel() * 8,
+                   _lib.CLUSTERS_ACCUMULATE if accumulate else 0, _stream(dev))
+    _lib.check(rc, "wgnn_group_class_reduce")
+    return prob_sum, conf_sum, votes, tally
+
+
 _ALIGN_STATUS = ((_lib.ALIGN_BAD_COL, "a CSR entry's column is outside [0, n_cols)"),
                  (_lib.ALIGN_BAD_MAP, "a gene_map value is outside [-1, n_genes)"),
                  (_lib.ALIGN_BAD_ROWPTR, "a row kept more entries than were counted"),
