@@ -570,6 +570,62 @@ int wgnn_group_class_reduce(const float* logits, int64_t ld_logits, const int32_
                             void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Calls re-drawn under gene dropout (additive export, WGNN_VERSION stays 206): the kernel behind
+ * api.ResidentPredictor.stability.  One layer of wgnn_predict_rows for every (cell, draw) pair of a batch, a draw being the
+ * cell with a random subset of its stored entries kept.  rowptr / col / raw / table / ld_table / n_genes / H / alpha / bias /
+ * w_head / b_head / n_classes / unsure_threshold exactly as wgnn_predict_rows takes them (H % 4 == 0, H <= 256, C * H * 4 <=
+ * 64 KiB, WGNN_FLAG_ROWPTR_I64); an out-of-range gene id is the caller's to check, as there.
+ *
+ * Which entries are kept.  The mask is a pure function of (seed, cell, draw, gene id) - no generator state.  All arithmetic
+ * in uint64 with wrap-around; mix32 is the upper half of the splitmix64 finaliser:
+ *     mix32(x):  x += 0x9E3779B97F4A7C15;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;  x = (x ^ (x >> 27)) * 0x94D049BB133111EB;
+ *                x ^= x >> 31;  return (uint32)(x >> 32)
+ *     cell = row0 + r,  draw = draw0 + d,  g = col[j]                      (r in [0, n_rows), d in [0, n_draws))
+ *     key  = seed ^ (cell * 0x9FB21C651E98DF25) ^ (draw * 0xD6E8FEB86659FD93)
+ *     u    = mix32(key + g * 0xC2B2AE3D27D4EB4F)
+ *     kept iff (uint64)u < T,   T = (uint64)floor(keep * 4294967296.0)      (computed on the host, here)
+ *   keep == 1 keeps every entry, keep == 0 none.  The mask follows the GENE, not the entry's position: a cell's mask is the
+ *   same in whatever order its genes are stored.  row0 / draw0 (>= 0) let a caller split a batch by cells or by draws and get
+ *   the same masks.  keep outside [0, 1], NaN included: WGNN_ERR_BAD_ARG.
+ *
+ * What a draw computes: wgnn_predict_rows' formula over the kept entries only - deg' = their number, S' = their f32 sum, z by
+ * the layer-1 rule (self_rows == NULL) or the explicit-self rule, with the gather and the fold order of wgnn_predict_rows; a
+ * masked entry has weight 0 (selected, not multiplied).  A draw that keeps nothing - or whose kept values sum to exactly 0,
+ * where wgnn_predict_rows would divide 0 by 0 - is an empty row, z = bias (+ alpha[G+1] self_rows): never a NaN.  With
+ * keep == 1 a draw's output, label and max_prob carry THE BITS of wgnn_predict_rows on the same batch.
+ *
+ * Without a head (w_head == NULL; the layers below the last): out [n_rows * n_draws, ld_out], row r * n_draws + d = ReLU(z) of
+ * that draw; self_rows, when given, is indexed the same way, [n_rows * n_draws, ld_self] - a deeper model runs
+ * wgnn_linear_fwd between the launches and every draw carries its own mask through every layer.
+ * With a head, reduced over the draws of a cell on the device:
+ *     votes    int32 [n_rows, ld_votes], ld_votes >= C : draws whose label (wgnn_predict_rows' rule for unsure_threshold) is j
+ *     unsure   int32 [n_rows] : draws labelled -1
+ *     empty    int32 [n_rows] : draws that kept no entry (still counted in votes / unsure by the label they get)
+ *     conf_sum f64   [n_rows] : the draws' f32 max_prob added in fp64 in ascending draw order
+ *     draw_label int32 [n_rows, n_draws], draw_prob f32 [n_rows, n_draws] : per draw; either may be NULL
+ *   so sum_j votes[r][j] + unsure[r] == n_draws per call.  WGNN_STABILITY_ACCUMULATE (head only): add this call's draws to
+ *   what the four tables hold (conf_sum continues the running sum: 32 draws, then 32 more with draw0 = 32, leave the bits of
+ *   64 at once); without it EVERY element of the four is written, zeros included.  Columns of votes beyond C are not touched.
+ *
+ * One workgroup per cell, its 8 waves take draws d, d + 8, ...; the kept entries of a 64-entry chunk are compacted to the low
+ * lanes (the identity permutation when nothing is masked) so masked entries load no table row; the draws' results are
+ * tallied in LDS.  No atomics of any kind, one addition order whatever the grid: two launches are bit-identical.
+ * n_rows * n_draws < 2^31.  Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand, n_draws < 1, n_rows * n_draws >=
+ * 2^31, negative row0 / draw0, keep outside [0, 1], a head without votes / unsure / empty / conf_sum, ld_votes < C, an unknown
+ * flag), WGNN_ERR_ALIGNMENT (H % 4, leading dimensions, pointers), WGNN_ERR_UNSUPPORTED (H > 256, a head beyond 64 KiB);
+ * wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+#define WGNN_STABILITY_ACCUMULATE 256
+int wgnn_predict_rows_dropout(const void* rowptr, const int32_t* col, const float* raw, int64_t n_rows,
+                              const float* table, int64_t ld_table, int32_t n_genes, int32_t H,
+                              const float* alpha, const float* bias, const float* self_rows, int64_t ld_self,
+                              int32_t n_draws, int64_t row0, int32_t draw0, uint64_t seed, double keep,
+                              float* out, int64_t ld_out,
+                              const float* w_head, const float* b_head, int32_t n_classes, float unsure_threshold,
+                              int32_t* votes, int64_t ld_votes, int32_t* unsure, int32_t* empty, double* conf_sum,
+                              int32_t* draw_label, float* draw_prob, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Batch alignment (additive exports, WGNN_VERSION stays 206): a batch over the CALLER's gene list made into the clean
  * bundle-vocabulary CSR that wgnn_predict_rows / wgnn_attrib_rows / wgnn_group_gene_reduce take - the device counterpart of the
  * column selection, `> threshold` and COO -> CSR of api._read_test_csr (reference preprocess.py:160-161, 173-178).  It runs

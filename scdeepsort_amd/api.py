@@ -514,6 +514,9 @@ def _prediction_frame(species, tissue, input_file, index, pred, id2label, bundle
 # to the largest batch timed - 100 000 cells x 800 genes, 2 layers, H 200 = 3.2e10 - where the fused call takes 24.7 ms and
 # the graph call 748 ms.  The limit is that largest measured point: beyond it the graph route, whose scaling is known.
 RESIDENT_FUSED_MAX_WORK = int(os.environ.get("WGNN_RESIDENT_FUSED_MAX_WORK", 32_000_000_000))
+# ResidentPredictor.stability: bytes of [cells x draws, H] f32 intermediates one launch of a deeper model may hold; the cells
+# of a batch are chunked under it (the masks follow the cell's number in the batch, so chunking changes no bit)
+STABILITY_CHUNK_BYTES = 256 * 1024 * 1024
 
 
 def load_map_dict(path, tissue: str) -> dict:
@@ -953,6 +956,148 @@ class Coverage:
             n_cells_below=int(self.below(min_counts, min_genes).sum()), n_bad=int(np.asarray(self.n_bad, np.int64).sum()))
 
 
+def _keep_levels(keep) -> Tuple[float, ...]:
+    """``stability``'s ``keep`` as a tuple of floats in [0, 1] (a single number is one level); ValueError otherwise."""
+    levels = (keep,) if isinstance(keep, (int, float, np.integer, np.floating)) else tuple(keep)
+    if not levels:
+        raise ValueError("keep: no levels")
+    out = []
+    for k in levels:
+        k = float(k)
+        if not 0.0 <= k <= 1.0:                               # NaN fails both comparisons
+            raise ValueError(f"keep = {k!r}: every level must be in [0, 1]")
+        out.append(k)
+    return tuple(out)
+
+
+class StabilitySummary(dict):
+    """``Stability.summary()``: a dict that prints as one line per level and one about the fragile cells."""
+
+    def __str__(self) -> str:
+        d = self
+        lines = [f"{d['n_cells']} cells, {d['n_draws']} draws per level"]
+        for k, med, p5 in zip(d["keep"], d["median_agreement"], d["p5_agreement"]):
+            lines.append(f"keep {k:g}: agreement median {med:.3f}, 5th percentile {p5:.3f}")
+        lines.append(f"{d['n_fragile']} cells below {d['min_agreement']:g} agreement at keep {d['at']:g}: median n_genes "
+                     f"{d['median_n_genes_fragile']:g} against {d['median_n_genes_rest']:g} for the rest")
+        return "\n".join(lines)
+
+
+@dataclass
+class Stability:
+    """What ``ResidentPredictor.stability`` returns: per cell, how its call fares when only a share ``keep`` of its detected
+    genes is left.  B cells (``index``), C cell types (``id2label``), L levels (``keep``), ``n_draws`` draws per level.
+    ``label`` int64 [B] / ``max_prob`` f32 [B]: the call on the cell as given (``classify``'s, -1 = unsure); ``n_entries``
+    int64 [B]: its stored genes.  The tallies of ``wgnn_predict_rows_dropout``, on the device they were made on (tables built
+    from CPU tensors serve the host logic just as well): ``votes`` int32 [L, B, C] the draws per label, ``unsure`` int32
+    [L, B] the draws labelled -1, ``empty`` int32 [L, B] the draws that kept no gene at all (also counted under the label
+    they got), ``conf_sum`` f64 [L, B] the draws' largest softmax probability summed.  ``seed``: the masks' seed."""
+    keep: Tuple[float, ...]
+    n_draws: int
+    label: np.ndarray
+    max_prob: np.ndarray
+    votes: torch.Tensor
+    unsure: torch.Tensor
+    empty: torch.Tensor
+    conf_sum: torch.Tensor
+    n_entries: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    seed: int = 0
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def _host(self) -> Tuple[np.ndarray, np.ndarray]:
+        return self.votes.cpu().numpy().astype(np.int64), self.unsure.cpu().numpy().astype(np.int64)
+
+    def agreement(self) -> np.ndarray:
+        """f64 [L, B]: the share of a cell's draws whose label equals the full call - for a cell that is unsure as given, the
+        share of draws that are unsure too."""
+        votes, unsure = self._host()
+        lab = np.asarray(self.label, np.int64)
+        L, B, _ = votes.shape
+        same = np.where(lab[None, :] >= 0, votes[:, np.arange(B), np.maximum(lab, 0)], unsure) if B else np.zeros((L, 0))
+        return same.astype(np.float64) / self.n_draws
+
+    def mean_prob(self) -> np.ndarray:
+        """f64 [L, B]: the draws' mean largest softmax probability (whatever label it belongs to)."""
+        return self.conf_sum.cpu().numpy().astype(np.float64) / self.n_draws
+
+    def flips_to(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(ids int64 [L, B], share f64 [L, B])``: per level the cell type OTHER than the full call that most draws were
+        labelled (equal counts: the lower id) and its share of the draws; -1 and 0 when no draw went to another type (draws
+        that came out unsure are in ``unsure``, not here)."""
+        votes, _ = self._host()
+        L, B, C = votes.shape
+        lab = np.asarray(self.label, np.int64)
+        other = votes.copy()
+        if B:
+            other[:, np.arange(B), np.maximum(lab, 0)] = np.where(lab >= 0, -1, other[:, np.arange(B), np.maximum(lab, 0)])
+        ids = other.argmax(axis=2) if C else np.zeros((L, B), np.int64)
+        top = np.take_along_axis(other, ids[:, :, None], axis=2)[:, :, 0] if C else np.zeros((L, B), np.int64)
+        none = top <= 0
+        return np.where(none, -1, ids).astype(np.int64), np.where(none, 0.0, top / self.n_draws)
+
+    def _level(self, at: float) -> int:
+        return int(np.argmin(np.abs(np.asarray(self.keep, np.float64) - float(at))))
+
+    def fragile(self, at: float = 0.5, min_agreement: float = 0.9) -> np.ndarray:
+        """Boolean [B]: cells whose agreement at the level nearest ``at`` (the first of equally near ones) is below
+        ``min_agreement``."""
+        return self.agreement()[self._level(at)] < float(min_agreement)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` (named as ``predict`` names it), ``prob`` (the full call's), ``n_genes``,
+        then per level ``agree_{keep}``, ``flip_{keep}`` (``flips_to``'s type by name, ``None`` without one) and
+        ``flip_share_{keep}``."""
+        types, _ = _call_names(np.asarray(self.label, np.int64), self.id2label, self.label_map)
+        out = {"index": list(self.index), "cell_type": types, "prob": np.asarray(self.max_prob), "n_genes": np.asarray(self.n_entries)}
+        agree = self.agreement()
+        ids, share = self.flips_to()
+        for l, k in enumerate(self.keep):
+            out[f"agree_{k:g}"] = agree[l]
+            out[f"flip_{k:g}"] = _call_names(np.where(ids[l] >= 0, ids[l], -3), self.id2label, self.label_map)[0]
+            out[f"flip_share_{k:g}"] = share[l]
+        return pd.DataFrame(out)
+
+    def summary(self, at: float = 0.5, min_agreement: float = 0.9) -> StabilitySummary:
+        """Per level the median and the 5th percentile of the agreement, the number of ``fragile(at, min_agreement)`` cells
+        and the median ``n_genes`` of the fragile cells against the rest (NaN for an empty side); ``print`` it."""
+        agree = self.agreement()
+        frag = self.fragile(at, min_agreement)
+        n = np.asarray(self.n_entries, np.float64)
+        med = lambda a: float(np.median(a)) if a.size else float("nan")
+        return StabilitySummary(
+            n_cells=int(agree.shape[1]), n_draws=int(self.n_draws), keep=tuple(self.keep),
+            median_agreement=[med(a) for a in agree], p5_agreement=[float(np.percentile(a, 5)) if a.size else float("nan") for a in agree],
+            at=float(self.keep[self._level(at)]), min_agreement=float(min_agreement), n_fragile=int(frag.sum()),
+            median_n_genes_fragile=med(n[frag]), median_n_genes_rest=med(n[~frag]))
+
+    def by_cluster(self, clusters) -> pd.DataFrame:
+        """Mean agreement per cluster and level: ``clusters`` holds one name or id per cell; one row per distinct value (sorted)
+        with ``cluster``, ``n_cells`` and ``agree_{keep}`` per level.  Host code over the per-cell table."""
+        arr = clusters.detach().cpu().numpy() if isinstance(clusters, torch.Tensor) else np.asarray(clusters)
+        agree = self.agreement()
+        if arr.ndim != 1 or arr.shape[0] != agree.shape[1]:
+            raise ValueError(f"clusters must hold one id or name per cell ({agree.shape[1]}), got shape {arr.shape}")
+        names, inv = np.unique(arr, return_inverse=True)
+        n = np.bincount(inv, minlength=len(names))
+        out = {"cluster": names.tolist(), "n_cells": n}
+        for l, k in enumerate(self.keep):
+            out[f"agree_{k:g}"] = np.bincount(inv, weights=agree[l], minlength=len(names)) / np.maximum(n, 1)
+        return pd.DataFrame(out)
+
+    def _require_same(self, keep: Sequence[float], n_cells: int, id2label: Sequence[str], seed: int) -> None:
+        """``into=``: the further draws must be of the same batch shape, levels, cell types and seed."""
+        if tuple(keep) != tuple(self.keep):
+            raise ValueError(f"into: the table holds the levels {tuple(self.keep)}, this call asks for {tuple(keep)}")
+        if n_cells != len(self.label):
+            raise ValueError(f"into: the table holds {len(self.label)} cells, the batch {n_cells}")
+        if list(id2label) != list(self.id2label):
+            raise ValueError("into: the table's cell types differ from the bundle's")
+        if int(seed) != int(self.seed):
+            raise ValueError(f"into: the table was drawn with seed {self.seed}, this call passes {seed}")
+
+
 @dataclass(frozen=True)
 class LogNormalize:
     """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
@@ -1374,6 +1519,97 @@ class ResidentPredictor:
         if save_path is not None:
             Path(save_path).mkdir(parents=True, exist_ok=True)
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_clusters.csv", index=False)
+        return out
+
+    # ---------------------------------------------------------------------------------------------
+    def stability(self, expr, keep=(0.75, 0.5, 0.25), n_draws: int = 32, seed: int = 0, genes=None, normalize=None,
+                  index=None, into: Optional[Stability] = None) -> Stability:
+        """Would the call survive a shallower sequencing run?  The batch is classified once as given (``classify``'s call,
+        bit for bit), then every cell is re-classified ``n_draws`` times per level of ``keep`` with only that share of its
+        detected genes left - ``wgnn_predict_rows_dropout`` draws the subsets itself, runs every layer per (cell, draw) and
+        tallies a cell's draws on the device - into a ``Stability``: ``agreement`` / ``flips_to`` / ``fragile`` / ``frame`` /
+        ``summary`` / ``by_cluster`` on top.  ``expr``, ``genes`` and ``normalize`` as for ``classify``; ``index``: the cells'
+        names (default ``range(B)``).
+
+        The masks are UNIFORM PER-GENE DROPOUT: every stored gene of a cell is kept with probability ``keep``, whatever
+        its value, the mask a pure function of ``(seed, cell, draw, gene)`` - the same whatever the order of a cell's genes,
+        nested across levels (what survives at 0.25 survives at 0.5), the same however the cells are chunked.  Count-aware
+        thinning (binomial on the raw counts before the logarithm) is deliberately out of scope.
+
+        ``into``: an earlier ``Stability`` of the same batch, levels and seed, to which ``n_draws`` FURTHER draws are added
+        (and which is returned): 32 draws and 32 more equal 64 at once.  Cells are chunked so that the ``[cells x draws, H]``
+        intermediates of a deeper model stay under ``STABILITY_CHUNK_BYTES``.  The draws run on the fused kernels only: a
+        bundle they cannot serve (hidden width above 256) raises ValueError, there is no graph route.  Argument errors are
+        ValueError before anything is launched."""
+        levels = _keep_levels(keep)
+        n_draws = int(n_draws)
+        if n_draws < 1:
+            raise ValueError(f"n_draws = {n_draws} must be >= 1")
+        B = self._n_cells(expr)
+        if into is not None:
+            into._require_same(levels, B, self.id2label, seed)
+        if index is not None and len(index) != B:
+            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        if self.hidden_padded > 256 or self.n_classes * self.hidden_padded * 4 > _ops.HEAD_LDS_BYTES:
+            raise ValueError(f"stability runs on the fused kernels only (hidden width <= 256, head <= {_ops.HEAD_LDS_BYTES} bytes); "
+                             f"this bundle has hidden width {self.hidden_padded} and {self.n_classes} cell types")
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._stability(self._over_genes(expr, genes, normalize), levels, n_draws, int(seed), index, into)
+
+    def _stability(self, expr, levels, n_draws, seed, index, into):
+        dev = self.device
+        rowptr, col, raw, checked, _ = self._device_csr(expr)
+        if not checked and col.numel():                    # once for the whole call: every launch below skips the check
+            lo, hi = torch.aminmax(col)
+            if int(lo) < 0 or int(hi) >= self.n_genes:
+                raise WgnnError(f"gene id out of range [0, {self.n_genes}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+        pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
+        B, L, C, Hp = int(rowptr.shape[0]) - 1, len(levels), self.n_classes, self.hidden_padded
+        if into is None:
+            st = Stability(keep=levels, n_draws=0, label=pred, max_prob=np.asarray(max_prob, np.float32),
+                           votes=torch.zeros((L, B, C), dtype=torch.int32, device=dev),
+                           unsure=torch.zeros((L, B), dtype=torch.int32, device=dev),
+                           empty=torch.zeros((L, B), dtype=torch.int32, device=dev),
+                           conf_sum=torch.zeros((L, B), dtype=torch.float64, device=dev),
+                           n_entries=np.diff(rowptr.cpu().numpy()).astype(np.int64),
+                           index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label), seed=seed,
+                           label_map=self._label_names())
+        else:
+            st = into
+        draw0 = st.n_draws
+        # cells per launch: the [cells x draws, Hp] f32 intermediates of a deeper model (h, its self rows, the next h) under the
+        # budget, and cells x draws below the kernel's 2^31
+        per_cell = n_draws * Hp * 4 * (3 if self.n_layers > 1 else 0)
+        step = (2 ** 31 - 1) // n_draws if per_cell == 0 else max(1, min(STABILITY_CHUNK_BYTES // per_cell, (2 ** 31 - 1) // n_draws))
+        for li, k in enumerate(levels):
+            for r0 in range(0, B, step):
+                r1 = min(B, r0 + step)
+                rp = rowptr[r0:r1 + 1]
+                kw = dict(check_cols=False, n_draws=n_draws, keep=k, seed=seed, row0=r0, draw0=draw0)
+                h = None
+                for l in range(self.n_layers):
+                    self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
+                    if l < self.n_layers - 1:
+                        h = _ops.predict_rows_dropout(rp, col, raw, self.tables[l], self.alpha, self.biases[l],
+                                                      self_rows=self_rows, **kw)
+                    else:
+                        _ops.predict_rows_dropout(rp, col, raw, self.tables[l], self.alpha, self.biases[l], self_rows=self_rows,
+                                                  head=(self.w_head, self.b_head), unsure_threshold=self.unsure_threshold,
+                                                  out=(st.votes[li, r0:r1], st.unsure[li, r0:r1], st.empty[li, r0:r1],
+                                                       st.conf_sum[li, r0:r1]), accumulate=draw0 > 0, **kw)
+        st.n_draws = draw0 + n_draws
+        return st
+
+    def stability_file(self, input_file, keep=(0.75, 0.5, 0.25), n_draws: int = 32, seed: int = 0, save_path=None,
+                       normalize=None) -> pd.DataFrame:
+        """``stability`` on a test file: ``Stability.frame()`` with the file's cell names, written as
+        ``{species}_{tissue}_stability.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        levels = _keep_levels(keep)
+        test, index = self._read_test(input_file, normalize)
+        out = self.stability(test, keep=levels, n_draws=n_draws, seed=seed, index=index).frame()
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_stability.csv", index=False)
         return out
 
     # ---------------------------------------------------------------------------------------------

@@ -883,6 +883,96 @@ def predict_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tab
     return (logits if want_logits else None), label, mx
 
 
+def predict_rows_dropout(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
+                         bias: torch.Tensor, *, self_rows: Optional[torch.Tensor] = None,
+                         head: Optional[tuple] = None, unsure_threshold: float = 0.0, check_cols: bool = True,
+                         n_draws: int, keep: float, seed: int, row0: int = 0, draw0: int = 0, out=None,
+                         accumulate: bool = False, want_draws: bool = False):
+    """``wgnn_predict_rows_dropout``: one layer of ``predict_rows`` for every (cell, draw) pair of a batch, a draw keeping
+    each stored entry with probability ``keep`` - the mask a pure function of ``(seed, row0 + cell, draw0 + draw, gene id)``
+    (``include/wgnn.h``), so a batch split by cells (``row0``) or by draws (``draw0``) gets the same masks.  The batch, the
+    table, ``alpha``, ``bias``, ``head``, ``unsure_threshold`` and ``check_cols`` as ``predict_rows`` takes them, widths
+    that are not a multiple of 4 zero-padded in the same way.  ``self_rows`` [B * n_draws, H]: row ``r * n_draws + d``
+    belongs to draw ``d`` of cell ``r``.  With ``keep == 1`` every draw carries the bits of ``predict_rows``.
+
+    Without ``head`` returns ``ReLU(z)`` [B * n_draws, H], rows laid out like ``self_rows`` (``out``: a float32
+    [B * n_draws, Hp] buffer to write into).  With ``head = (w_head [C, H], b_head [C])`` returns ``(votes int32 [B, C],
+    unsure int32 [B], empty int32 [B], conf_sum f64 [B], draw_label int32 [B, n_draws] | None, draw_prob f32 [B, n_draws] |
+    None)``: the draws per label, the draws labelled -1, the draws that kept no entry, and the draws' ``max_prob`` added in
+    fp64 in draw order; the last two with ``want_draws``.  ``out``: the first four (``votes`` may be a view with a row stride
+    ``>= C``), or all six, to write into - every element is written, or added to with ``accumulate`` (further draws of the
+    same cells: pass ``draw0``).  There is no GEMM route for a head beyond what the kernel stages in LDS."""
+    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, self_rows, *(head or ()))
+    n_draws = int(n_draws)
+    keep = float(keep)
+    if n_draws < 1:
+        raise WgnnError(f"predict_rows_dropout: n_draws = {n_draws} must be >= 1")
+    if not 0.0 <= keep <= 1.0:
+        raise WgnnError(f"predict_rows_dropout: keep = {keep} must be in [0, 1]")
+    if int(row0) < 0 or int(draw0) < 0:
+        raise WgnnError("predict_rows_dropout: row0 and draw0 must not be negative")
+    H = bias.shape[0]
+    table, alpha, G, Hp, B, flags, rowptr, col, raw = _attrib_common("predict_rows_dropout", rowptr, col, raw, table, alpha, H,
+                                                                     check_cols)
+    if B * n_draws >= 2 ** 31:
+        raise WgnnError("predict_rows_dropout: B * n_draws >= 2^31 (split the batch or the draws)")
+    bias = _pad_cols(bias, Hp)
+    if self_rows is not None:
+        if self_rows.shape[0] != B * n_draws:
+            raise WgnnError(f"self_rows has {self_rows.shape[0]} rows, the batch {B} cells x {n_draws} draws")
+        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
+    common = (_ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp, _ptr(alpha), _ptr(bias),
+              _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
+              n_draws, int(row0), int(draw0), int(seed) & (2 ** 64 - 1), keep)
+    if head is None:
+        if accumulate or want_draws:
+            raise WgnnError("predict_rows_dropout: accumulate and want_draws need a head")
+        if out is None:
+            out = torch.empty((B * n_draws, Hp), dtype=torch.float32, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B * n_draws, Hp)
+              or out.stride(1) != 1 or out.stride(0) % 4 or out.stride(0) < Hp or out.data_ptr() % 16):
+            raise WgnnError(f"out must be float32 [{B * n_draws}, {Hp}], unit column stride, 16-byte aligned rows")
+        rc = _lib.call(dev, "wgnn_predict_rows_dropout", *common, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
+                       None, None, 0, 0.0, None, 0, None, None, None, None, None, flags, _stream(dev))
+        _lib.check(rc, "wgnn_predict_rows_dropout")
+        return out if Hp == H else out[:, :H]
+    w_head, b_head = head
+    n_cls = w_head.shape[0]
+    if n_cls * Hp * 4 > HEAD_LDS_BYTES:
+        raise WgnnError(f"predict_rows_dropout: a [{n_cls}, {Hp}] head is beyond the {HEAD_LDS_BYTES} bytes the kernel stages")
+    w_head = _pad_cols(w_head, Hp)
+    b_head = b_head.float().contiguous()
+    if out is None:
+        if accumulate:
+            raise WgnnError("accumulate needs the tables to add to (out=)")
+        out = (torch.empty((B, n_cls), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float64, device=dev))
+    if len(out) not in (4, 6):
+        raise WgnnError("out must be (votes, unsure, empty, conf_sum[, draw_label, draw_prob])")
+    votes, unsure, empty, conf_sum = out[:4]
+    draw_label, draw_prob = out[4:] if len(out) == 6 else (None, None)
+    if draw_label is None and want_draws:
+        draw_label = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
+        draw_prob = torch.empty((B, n_draws), dtype=torch.float32, device=dev)
+    _require_cuda(votes, unsure, empty, conf_sum, draw_label, draw_prob)
+    if (votes.dtype != torch.int32 or tuple(votes.shape) != (B, n_cls) or (n_cls > 1 and votes.stride(1) != 1)
+            or (B > 1 and votes.stride(0) < n_cls)):
+        raise WgnnError(f"votes must be int32 [{B}, {n_cls}] with unit column stride and a row stride >= {n_cls}")
+    want = ((unsure, torch.int32, (B,)), (empty, torch.int32, (B,)), (conf_sum, torch.float64, (B,)))
+    if any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want):
+        raise WgnnError(f"unsure and empty must be contiguous int32 [{B}], conf_sum float64 [{B}]")
+    if draw_label is not None:
+        per = ((draw_label, torch.int32), (draw_prob, torch.float32))
+        if any(t is None or t.dtype != d or tuple(t.shape) != (B, n_draws) or not t.is_contiguous() for t, d in per):
+            raise WgnnError(f"draw_label / draw_prob must be contiguous int32 / float32 [{B}, {n_draws}]")
+    rc = _lib.call(dev, "wgnn_predict_rows_dropout", *common, None, 0, _ptr(w_head), _ptr(b_head), n_cls,
+                   float(unsure_threshold), _ptr(votes), votes.stride(0) if B > 1 else max(int(votes.stride(0)), n_cls),
+                   _ptr(unsure), _ptr(empty), _ptr(conf_sum), _ptr(draw_label), _ptr(draw_prob),
+                   flags | (_lib.STABILITY_ACCUMULATE if accumulate else 0), _stream(dev))
+    _lib.check(rc, "wgnn_predict_rows_dropout")
+    return votes, unsure, empty, conf_sum, draw_label, draw_prob
+
+
 def _attrib_common(name, rowptr, col, raw, table, alpha, H, check_cols):
     """The batch / table handling ``predict_rows`` does, shared by ``attrib_rows``: returns (table, alpha, G, Hp, B, flags,
     rowptr, col, raw) ready for the C call."""
