@@ -626,6 +626,61 @@ int wgnn_predict_rows_dropout(const void* rowptr, const int32_t* col, const floa
                               int32_t* draw_label, float* draw_prob, uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Calls re-drawn under READ-LEVEL THINNING (additive export, WGNN_VERSION stays 206): the kernel behind
+ * api.ResidentPredictor.stability(thin="reads").  wgnn_predict_rows_dropout drops whole genes of the normalised values; this
+ * entry re-sequences the cell at a share `keep` of its depth: `raw` holds COUNTS (f32 integers in [1, 2^24]; anything else
+ * counts as no read), every read survives with probability keep, low-count genes drop out first, and the library size the
+ * logarithm divides by shrinks with the reads.  No thinned matrix is stored.  Every operand of wgnn_predict_rows_dropout is
+ * taken as there; further: rest int64 [n_rows] = the cell's reads in columns OUTSIDE the bundle (negative counts as 0), scale
+ * (Seurat's scale.factor, > 0) and threshold (>= 0) of wgnn_align_count_ln.
+ *
+ * Which reads are kept.  mix32, key(seed, cell, draw) and T = (uint64)floor(keep * 4294967296.0) are the dropout block's;
+ * mix64(x) is the same splitmix64 finaliser returning all 64 bits, so mix32(x) == (uint32)(mix64(x) >> 32).  All in uint64
+ * with wrap-around:
+ *     ek = mix64(key + g * 0xC2B2AE3D27D4EB4F)                                   (K_GENE, g = col[j])
+ *     read i in [0, c) of the entry (cell, g, count c) is kept iff (uint64)mix32(ek + i * 0xA0761D6478BD642F) < T     (K_READ)
+ *     c' = the number of kept reads of the entry;   rest' = the same over rest[r] reads with g = n_genes
+ *   Pure consequences of the hash: c' is Binomial(c, T / 2^32); the result does not depend on the order of a cell's genes;
+ *   levels are nested (a read kept at 0.25 is kept at 0.5); row0 / draw0 split a batch by cells or draws without changing a bit.
+ *   keep == 1 keeps every read, keep == 0 none.
+ *
+ * The draw's values.  total' = sum over the cell's entries of c' + rest' (an integer), and
+ *     v' = float( log1p( double(c') / double(total') * scale ) )
+ *   in fp64 with contraction off: the function wgnn_align_count_ln evaluates (one definition in the source, csrc/
+ *   wgnn_align_rows.h).  An entry TAKES PART iff c' > 0 && v' > threshold.
+ * The draw's layer.  The participating entries, in row order, form a row of wgnn_predict_rows: deg' = their number, S' = their
+ *   f32 sum, the same weights (selected to 0 for a draw whose S' is 0), the same gather and fold, then - with a head - the
+ *   head, label rule and tallies of wgnn_predict_rows_dropout.  The arithmetic order is wgnn_predict_rows' on that compacted
+ *   row, so a draw carries the bits wgnn_predict_rows leaves on the materialised draw run through wgnn_align_count_ln / _fill_ln
+ *   (one more column holding rest'), and with keep == 1 THE BITS of wgnn_predict_rows on the lognorm-aligned batch, whatever
+ *   the threshold.  A draw with nothing left - total' == 0 included - is the empty row (z = bias (+ alpha[G+1] self_rows)) and
+ *   counts in `empty`.
+ *
+ * Outputs as wgnn_predict_rows_dropout (out without a head; votes / unsure / empty / conf_sum / draw_label / draw_prob with
+ * one, WGNN_THIN_ACCUMULATE as WGNN_STABILITY_ACCUMULATE), and per pair, in either mode, either may be NULL:
+ *     draw_reads   int32 [n_rows, n_draws] : total' (the caller keeps a cell's reads below 2^31; a larger value saturates)
+ *     draw_entries int32 [n_rows, n_draws] : deg'
+ *
+ * One workgroup per cell, its 8 waves take the draws.  The hash costs O(reads): c' is computed once per (cell, draw) and the
+ * surviving entries are kept in a per-wave stash in LDS (1024 entries) for the later sweeps; of a draw that outgrows it the
+ * tail is recomputed.  Entries with c >= 16, and rest, are thinned by the whole wave, 64 reads per step.  No atomics of any
+ * kind, vector stores only, one addition order whatever the grid: two launches are bit-identical.
+ * Errors, before any launch: those of wgnn_predict_rows_dropout, and WGNN_ERR_BAD_ARG for rest NULL, scale not positive and
+ * finite, threshold < 0 or NaN; WGNN_ERR_ALIGNMENT for rest not 8-byte, draw_reads / draw_entries not 4-byte aligned.
+ * ------------------------------------------------------------------------- */
+#define WGNN_THIN_ACCUMULATE 256
+int wgnn_predict_rows_thin(const void* rowptr, const int32_t* col, const float* raw, int64_t n_rows,
+                           const float* table, int64_t ld_table, int32_t n_genes, int32_t H,
+                           const float* alpha, const float* bias, const float* self_rows, int64_t ld_self,
+                           const int64_t* rest, double scale, float threshold,
+                           int32_t n_draws, int64_t row0, int32_t draw0, uint64_t seed, double keep,
+                           float* out, int64_t ld_out,
+                           const float* w_head, const float* b_head, int32_t n_classes, float unsure_threshold,
+                           int32_t* votes, int64_t ld_votes, int32_t* unsure, int32_t* empty, double* conf_sum,
+                           int32_t* draw_label, float* draw_prob, int32_t* draw_reads, int32_t* draw_entries,
+                           uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Batch alignment (additive exports, WGNN_VERSION stays 206): a batch over the CALLER's gene list made into the clean
  * bundle-vocabulary CSR that wgnn_predict_rows / wgnn_attrib_rows / wgnn_group_gene_reduce take - the device counterpart of the
  * column selection, `> threshold` and COO -> CSR of api._read_test_csr (reference preprocess.py:160-161, 173-178).  It runs

@@ -20,6 +20,7 @@ ATTRIB_ACCUMULATE, ATTRIB_EXPLICIT_SELF = 256, 512     # wgnn_attrib_rows' own f
 MARKERS_ACCUMULATE = 256           # wgnn_group_gene_reduce's flag bit (include/wgnn.h)
 CLUSTERS_ACCUMULATE = 256          # wgnn_group_class_reduce's flag bit (include/wgnn.h)
 STABILITY_ACCUMULATE = 256         # wgnn_predict_rows_dropout's flag bit (include/wgnn.h)
+THIN_ACCUMULATE = 256              # wgnn_predict_rows_thin's flag bit (include/wgnn.h)
 ALIGN_BAD_COL, ALIGN_BAD_MAP, ALIGN_BAD_ROWPTR, ALIGN_BAD_VALUE = 1, 2, 4, 8     # wgnn_align_*'s status bits (include/wgnn.h)
 ABI_MAJOR = 2                    # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
@@ -80,6 +81,10 @@ SIGNATURES = {
     "wgnn_predict_rows_dropout": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64,
                                             _i32, _i64, _i32, C.c_uint64, C.c_double, _vp, _i64,
                                             _vp, _vp, _i32, C.c_float, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_predict_rows_thin": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64,
+                                         _vp, C.c_double, C.c_float,
+                                         _i32, _i64, _i32, C.c_uint64, C.c_double, _vp, _i64,
+                                         _vp, _vp, _i32, C.c_float, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_align_count": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, _u32, _vp]),
     "wgnn_align_fill": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_align_count_ln": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, C.c_double, _vp, _vp,

@@ -11,6 +11,7 @@ kernels; file ingest, vocabularies and PCA are ordinary host code kept deliberat
 """
 from __future__ import annotations
 
+import functools
 import os
 import re
 from dataclasses import dataclass, field
@@ -975,7 +976,7 @@ class StabilitySummary(dict):
 
     def __str__(self) -> str:
         d = self
-        lines = [f"{d['n_cells']} cells, {d['n_draws']} draws per level"]
+        lines = [f"{d['n_cells']} cells, {d['n_draws']} draws per level" + (f", thinned by {d['thin']}" if "thin" in d else "")]
         for k, med, p5 in zip(d["keep"], d["median_agreement"], d["p5_agreement"]):
             lines.append(f"keep {k:g}: agreement median {med:.3f}, 5th percentile {p5:.3f}")
         lines.append(f"{d['n_fragile']} cells below {d['min_agreement']:g} agreement at keep {d['at']:g}: median n_genes "
@@ -991,7 +992,10 @@ class Stability:
     int64 [B]: its stored genes.  The tallies of ``wgnn_predict_rows_dropout``, on the device they were made on (tables built
     from CPU tensors serve the host logic just as well): ``votes`` int32 [L, B, C] the draws per label, ``unsure`` int32
     [L, B] the draws labelled -1, ``empty`` int32 [L, B] the draws that kept no gene at all (also counted under the label
-    they got), ``conf_sum`` f64 [L, B] the draws' largest softmax probability summed.  ``seed``: the masks' seed."""
+    they got), ``conf_sum`` f64 [L, B] the draws' largest softmax probability summed.  ``seed``: the masks' seed.
+    ``thin``: what a draw drops - ``"genes"`` (whole genes of the values as given, ``wgnn_predict_rows_dropout``) or ``"reads"``
+    (single reads of the raw counts, ``wgnn_predict_rows_thin``; ``keep`` is then a share of the DEPTH, ``empty`` counts the
+    draws in which no gene took part, and ``n_reads`` int64 [B] holds a cell's library size, else ``None``)."""
     keep: Tuple[float, ...]
     n_draws: int
     label: np.ndarray
@@ -1005,6 +1009,8 @@ class Stability:
     id2label: Sequence[str]
     seed: int = 0
     label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+    thin: str = "genes"
+    n_reads: Optional[np.ndarray] = None
 
     def _host(self) -> Tuple[np.ndarray, np.ndarray]:
         return self.votes.cpu().numpy().astype(np.int64), self.unsure.cpu().numpy().astype(np.int64)
@@ -1046,11 +1052,13 @@ class Stability:
         return self.agreement()[self._level(at)] < float(min_agreement)
 
     def frame(self) -> pd.DataFrame:
-        """One row per cell: ``index``, ``cell_type`` (named as ``predict`` names it), ``prob`` (the full call's), ``n_genes``,
-        then per level ``agree_{keep}``, ``flip_{keep}`` (``flips_to``'s type by name, ``None`` without one) and
+        """One row per cell: ``index``, ``cell_type`` (named as ``predict`` names it), ``prob`` (the full call's), ``n_genes``
+        (and ``n_reads`` under ``thin="reads"``), then per level ``agree_{keep}``, ``flip_{keep}`` (``flips_to``'s type by name, ``None`` without one) and
         ``flip_share_{keep}``."""
         types, _ = _call_names(np.asarray(self.label, np.int64), self.id2label, self.label_map)
         out = {"index": list(self.index), "cell_type": types, "prob": np.asarray(self.max_prob), "n_genes": np.asarray(self.n_entries)}
+        if self.n_reads is not None:
+            out["n_reads"] = np.asarray(self.n_reads)
         agree = self.agreement()
         ids, share = self.flips_to()
         for l, k in enumerate(self.keep):
@@ -1067,7 +1075,7 @@ class Stability:
         n = np.asarray(self.n_entries, np.float64)
         med = lambda a: float(np.median(a)) if a.size else float("nan")
         return StabilitySummary(
-            n_cells=int(agree.shape[1]), n_draws=int(self.n_draws), keep=tuple(self.keep),
+            n_cells=int(agree.shape[1]), n_draws=int(self.n_draws), keep=tuple(self.keep), thin=self.thin,
             median_agreement=[med(a) for a in agree], p5_agreement=[float(np.percentile(a, 5)) if a.size else float("nan") for a in agree],
             at=float(self.keep[self._level(at)]), min_agreement=float(min_agreement), n_fragile=int(frag.sum()),
             median_n_genes_fragile=med(n[frag]), median_n_genes_rest=med(n[~frag]))
@@ -1086,8 +1094,10 @@ class Stability:
             out[f"agree_{k:g}"] = np.bincount(inv, weights=agree[l], minlength=len(names)) / np.maximum(n, 1)
         return pd.DataFrame(out)
 
-    def _require_same(self, keep: Sequence[float], n_cells: int, id2label: Sequence[str], seed: int) -> None:
-        """``into=``: the further draws must be of the same batch shape, levels, cell types and seed."""
+    def _require_same(self, keep: Sequence[float], n_cells: int, id2label: Sequence[str], seed: int, thin: str = "genes") -> None:
+        """``into=``: the further draws must be of the same batch shape, levels, cell types, seed and kind of thinning."""
+        if thin != self.thin:
+            raise ValueError(f"into: the table was drawn with thin={self.thin!r}, this call passes thin={thin!r}")
         if tuple(keep) != tuple(self.keep):
             raise ValueError(f"into: the table holds the levels {tuple(self.keep)}, this call asks for {tuple(keep)}")
         if n_cells != len(self.label):
@@ -1523,47 +1533,94 @@ class ResidentPredictor:
 
     # ---------------------------------------------------------------------------------------------
     def stability(self, expr, keep=(0.75, 0.5, 0.25), n_draws: int = 32, seed: int = 0, genes=None, normalize=None,
-                  index=None, into: Optional[Stability] = None) -> Stability:
+                  index=None, into: Optional[Stability] = None, thin: str = "genes") -> Stability:
         """Would the call survive a shallower sequencing run?  The batch is classified once as given (``classify``'s call,
-        bit for bit), then every cell is re-classified ``n_draws`` times per level of ``keep`` with only that share of its
-        detected genes left - ``wgnn_predict_rows_dropout`` draws the subsets itself, runs every layer per (cell, draw) and
-        tallies a cell's draws on the device - into a ``Stability``: ``agreement`` / ``flips_to`` / ``fragile`` / ``frame`` /
-        ``summary`` / ``by_cluster`` on top.  ``expr``, ``genes`` and ``normalize`` as for ``classify``; ``index``: the cells'
-        names (default ``range(B)``).
+        bit for bit), then every cell is re-classified ``n_draws`` times per level of ``keep`` on a thinned copy of itself -
+        the kernels draw the copies themselves, run every layer per (cell, draw) and tally a cell's draws on the device - into
+        a ``Stability``: ``agreement`` / ``flips_to`` / ``fragile`` / ``frame`` / ``summary`` / ``by_cluster`` on top.  ``expr``,
+        ``genes`` and ``normalize`` as for ``classify``; ``index``: the cells' names (default ``range(B)``).
 
-        The masks are UNIFORM PER-GENE DROPOUT: every stored gene of a cell is kept with probability ``keep``, whatever
-        its value, the mask a pure function of ``(seed, cell, draw, gene)`` - the same whatever the order of a cell's genes,
-        nested across levels (what survives at 0.25 survives at 0.5), the same however the cells are chunked.  Count-aware
-        thinning (binomial on the raw counts before the logarithm) is deliberately out of scope.
+        ``thin="genes"`` (the default) is UNIFORM PER-GENE DROPOUT on the values as given (``wgnn_predict_rows_dropout``): every
+        stored gene of a cell is kept with probability ``keep``, whatever its value, and the survivors keep their values.
 
-        ``into``: an earlier ``Stability`` of the same batch, levels and seed, to which ``n_draws`` FURTHER draws are added
-        (and which is returned): 32 draws and 32 more equal 64 at once.  Cells are chunked so that the ``[cells x draws, H]``
-        intermediates of a deeper model stay under ``STABILITY_CHUNK_BYTES``.  The draws run on the fused kernels only: a
+        ``thin="reads"`` is what a shallower run does (``wgnn_predict_rows_thin``): the batch holds raw integer COUNTS
+        (``genes=`` and a ``normalize`` spec are required, else ``ValueError``), every READ is kept with probability ``keep`` -
+        binomial thinning of each count, so a one-read gene drops out long before a 400-read gene - the reads in columns
+        outside the bundle are thinned with the rest, and the surviving counts are log-normalised against the draw's OWN
+        library size before the layers run; no thinned matrix is stored.  With ``LogNormalize(library_size=)`` the reads
+        outside the batch's columns are ``library_size`` minus the cell's matched reads.  A count that is no integer in
+        [1, 2^24], a library size below the matched reads, or a cell of 2^31 reads or more raises ``WgnnError`` naming the
+        cell (one device check); a ``GeneMap`` with merged columns raises ``ValueError``.  A deeper model redoes the thinning
+        in every layer's launch.
+
+        Either way a draw is a pure function of ``(seed, cell, draw, gene[, read])``: the same whatever the order of a cell's
+        genes, nested across levels (what survives at 0.25 survives at 0.5), the same however the cells are chunked.
+
+        ``into``: an earlier ``Stability`` of the same batch, levels, seed and ``thin``, to which ``n_draws`` FURTHER draws are
+        added (and which is returned): 32 draws and 32 more equal 64 at once.  Cells are chunked so that the ``[cells x draws,
+        H]`` intermediates of a deeper model stay under ``STABILITY_CHUNK_BYTES``.  The draws run on the fused kernels only: a
         bundle they cannot serve (hidden width above 256) raises ValueError, there is no graph route.  Argument errors are
         ValueError before anything is launched."""
+        if thin not in ("genes", "reads"):
+            raise ValueError(f"thin = {thin!r}: pass \"genes\" or \"reads\"")
         levels = _keep_levels(keep)
         n_draws = int(n_draws)
         if n_draws < 1:
             raise ValueError(f"n_draws = {n_draws} must be >= 1")
         B = self._n_cells(expr)
         if into is not None:
-            into._require_same(levels, B, self.id2label, seed)
+            into._require_same(levels, B, self.id2label, seed, thin)
         if index is not None and len(index) != B:
             raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
         if self.hidden_padded > 256 or self.n_classes * self.hidden_padded * 4 > _ops.HEAD_LDS_BYTES:
             raise ValueError(f"stability runs on the fused kernels only (hidden width <= 256, head <= {_ops.HEAD_LDS_BYTES} bytes); "
                              f"this bundle has hidden width {self.hidden_padded} and {self.n_classes} cell types")
+        if thin == "reads":
+            spec = self.normalize if normalize is None else _normalize_spec(normalize)
+            if genes is None or spec is None:
+                raise ValueError("thin=\"reads\" thins raw counts: pass the batch over its own gene list (genes=) and a normalize "
+                                 "spec (the values a draw leaves are log-normalised against the draw's own library size)")
+            by_name = not isinstance(genes, (torch.Tensor, GeneMap))
+            if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
+                raise ValueError("thin=\"reads\" does not take merged columns (duplicates=\"sum\"): merging under thinning is not built")
+            with torch.cuda.device(self.device), torch.no_grad():
+                return self._stability(None, levels, n_draws, int(seed), index, into, counts=(expr, genes, spec))
         with torch.cuda.device(self.device), torch.no_grad():
             return self._stability(self._over_genes(expr, genes, normalize), levels, n_draws, int(seed), index, into)
 
-    def _stability(self, expr, levels, n_draws, seed, index, into):
+    def _thin_operands(self, expr, genes, spec):
+        """``thin="reads"``: the batch's raw counts aligned to the bundle (threshold 0, no normalisation), a cell's reads
+        outside the bundle (int64) and its library size (int64), from one ``coverage_rows`` launch and one fused check."""
+        batch, gmap, _ = self._caller_batch(expr, genes)
+        _, _, n_bad, total, total_mapped, _ = _ops.coverage_rows(batch, gmap, self.n_genes)
+        if int(n_bad.sum()):
+            raise WgnnError("stability: a count is negative, NaN or infinite")
+        if spec.library_size is not None:
+            lib = spec.library_size if isinstance(spec.library_size, torch.Tensor) else torch.as_tensor(spec.library_size)
+            if lib.dim() != 1 or lib.shape[0] != total.shape[0] or lib.is_complex():
+                raise ValueError(f"library_size must be a real vector with one entry per cell ({total.shape[0]}), got {tuple(lib.shape)}")
+            total = torch.where(total > 0, lib.to(self.device).to(torch.float64), total)     # as align: only on a cell with a count
+        rest = total - total_mapped
+        csr = _ops.align_rows(batch, gmap, self.n_genes, 0.0)
+        _ops.thin_operand_check(csr[0], csr[2], rest, total)
+        return csr, rest.to(torch.int64), total.to(torch.int64)
+
+    def _stability(self, expr, levels, n_draws, seed, index, into, counts=None):
         dev = self.device
-        rowptr, col, raw, checked, _ = self._device_csr(expr)
-        if not checked and col.numel():                    # once for the whole call: every launch below skips the check
-            lo, hi = torch.aminmax(col)
-            if int(lo) < 0 or int(hi) >= self.n_genes:
-                raise WgnnError(f"gene id out of range [0, {self.n_genes}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
-        pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
+        thin, rest, n_reads = "genes", None, None
+        if counts is not None:                             # thin="reads": the draws run on the counts, the full call on the values
+            thin = "reads"
+            c_expr, c_genes, spec = counts
+            (rowptr, col, raw), rest, n_reads = self._thin_operands(c_expr, c_genes, spec)
+            pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(c_expr, c_genes, None, spec)))
+            thin_kw = dict(scale=float(spec.scale_factor), threshold=float(self.threshold))
+        else:
+            rowptr, col, raw, checked, _ = self._device_csr(expr)
+            if not checked and col.numel():                # once for the whole call: every launch below skips the check
+                lo, hi = torch.aminmax(col)
+                if int(lo) < 0 or int(hi) >= self.n_genes:
+                    raise WgnnError(f"gene id out of range [0, {self.n_genes}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+            pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
         B, L, C, Hp = int(rowptr.shape[0]) - 1, len(levels), self.n_classes, self.hidden_padded
         if into is None:
             st = Stability(keep=levels, n_draws=0, label=pred, max_prob=np.asarray(max_prob, np.float32),
@@ -1573,7 +1630,8 @@ class ResidentPredictor:
                            conf_sum=torch.zeros((L, B), dtype=torch.float64, device=dev),
                            n_entries=np.diff(rowptr.cpu().numpy()).astype(np.int64),
                            index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label), seed=seed,
-                           label_map=self._label_names())
+                           label_map=self._label_names(), thin=thin,
+                           n_reads=None if n_reads is None else n_reads.cpu().numpy())
         else:
             st = into
         draw0 = st.n_draws
@@ -1586,27 +1644,38 @@ class ResidentPredictor:
                 r1 = min(B, r0 + step)
                 rp = rowptr[r0:r1 + 1]
                 kw = dict(check_cols=False, n_draws=n_draws, keep=k, seed=seed, row0=r0, draw0=draw0)
+                if thin == "reads":
+                    draw = functools.partial(_ops.predict_rows_thin, rest=rest[r0:r1], **thin_kw)
+                else:
+                    draw = _ops.predict_rows_dropout
                 h = None
                 for l in range(self.n_layers):
                     self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
                     if l < self.n_layers - 1:
-                        h = _ops.predict_rows_dropout(rp, col, raw, self.tables[l], self.alpha, self.biases[l],
-                                                      self_rows=self_rows, **kw)
+                        h = draw(rp, col, raw, self.tables[l], self.alpha, self.biases[l], self_rows=self_rows, **kw)
                     else:
-                        _ops.predict_rows_dropout(rp, col, raw, self.tables[l], self.alpha, self.biases[l], self_rows=self_rows,
-                                                  head=(self.w_head, self.b_head), unsure_threshold=self.unsure_threshold,
-                                                  out=(st.votes[li, r0:r1], st.unsure[li, r0:r1], st.empty[li, r0:r1],
-                                                       st.conf_sum[li, r0:r1]), accumulate=draw0 > 0, **kw)
+                        draw(rp, col, raw, self.tables[l], self.alpha, self.biases[l], self_rows=self_rows,
+                             head=(self.w_head, self.b_head), unsure_threshold=self.unsure_threshold,
+                             out=(st.votes[li, r0:r1], st.unsure[li, r0:r1], st.empty[li, r0:r1],
+                                  st.conf_sum[li, r0:r1]), accumulate=draw0 > 0, **kw)
         st.n_draws = draw0 + n_draws
         return st
 
     def stability_file(self, input_file, keep=(0.75, 0.5, 0.25), n_draws: int = 32, seed: int = 0, save_path=None,
-                       normalize=None) -> pd.DataFrame:
+                       normalize=None, thin: str = "genes") -> pd.DataFrame:
         """``stability`` on a test file: ``Stability.frame()`` with the file's cell names, written as
-        ``{species}_{tissue}_stability.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        ``{species}_{tissue}_stability.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``.
+        ``thin="reads"``: the file holds raw counts (``normalize`` required); its full table and gene names are thinned."""
         levels = _keep_levels(keep)
-        test, index = self._read_test(input_file, normalize)
-        out = self.stability(test, keep=levels, n_draws=n_draws, seed=seed, index=index).frame()
+        if thin == "reads":
+            if (self.normalize if normalize is None else _normalize_spec(normalize)) is None:
+                raise ValueError("thin=\"reads\" thins raw counts: the file needs a normalize spec")
+            df = _read_expression(input_file, self.file_type)
+            out = self.stability(df.to_numpy(dtype=np.float32), keep=levels, n_draws=n_draws, seed=seed, index=df.index,
+                                 genes=[str(c) for c in df.columns], normalize=normalize, thin=thin).frame()
+        else:
+            test, index = self._read_test(input_file, normalize)
+            out = self.stability(test, keep=levels, n_draws=n_draws, seed=seed, index=index, thin=thin).frame()
         if save_path is not None:
             Path(save_path).mkdir(parents=True, exist_ok=True)
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_stability.csv", index=False)

@@ -79,13 +79,7 @@ __device__ __forceinline__ void put(const AArgs& a, long s, long room, int g, fl
     else bad |= WGNN_ALIGN_BAD_ROWPTR;
 }
 
-// LN: the definition's value, fp64 throughout in Seurat's operation order (divide, scale, log1p), each step rounded on its own
-__device__ __forceinline__ float lognorm(float x, double total, double scale) {
-#pragma clang fp contract(off)
-    const double q = (double)x / total;
-    const double y = q * scale;
-    return (float)log1p(y);
-}
+// LN: the definition's value is lognorm() of wgnn_align_rows.h (wgnn_predict_rows_thin evaluates the same function)
 
 // LN: the wave's candidates among the 4 entries per lane it holds (c[k]) become their log-normalised values, every other entry
 // 0.  Candidates are packed into the wave's slab (k-major, lane-minor), consecutive lanes evaluate consecutive slots, and each

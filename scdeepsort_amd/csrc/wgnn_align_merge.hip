@@ -75,7 +75,7 @@ __device__ __forceinline__ void put(const MArgs& a, long s, long room, int g, fl
     else bad |= WGNN_ALIGN_BAD_ROWPTR;
 }
 
-// the definition's value of a (merged) count: wgnn_align.hip's lognorm with the count already in fp64
+// the definition's value of a (merged) count: wgnn_align_rows.h's lognorm with the count already in fp64
 __device__ __forceinline__ float lognorm(double c, double total, double scale) {
 #pragma clang fp contract(off)
     const double q = c / total;

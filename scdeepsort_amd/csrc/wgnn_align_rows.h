@@ -2,6 +2,7 @@
 // total) and wgnn_coverage.hip (wgnn_coverage_rows' total / total_mapped): both sums come out of THIS code, so they agree bit
 // for bit.  One wavefront per row; a lane visits its entries in ascending position, the 64 partial sums fold in a butterfly.
 #pragma once
+#include <math.h>
 #include "wgnn_common.h"
 
 namespace wgnn {
@@ -18,6 +19,16 @@ __device__ __forceinline__ bool countable(float x) { return x > 0.f && x < __bui
 __device__ __forceinline__ void add_count(double& acc, float x, unsigned& bad) {
     if (countable(x)) acc += (double)x;
     else if (!(x == 0.f)) bad |= WGNN_ALIGN_BAD_VALUE;
+}
+
+// The log-normalised value of a count: fp64 throughout in Seurat's operation order (divide, scale, log1p), each step rounded on
+// its own.  ONE definition for wgnn_align_count_ln / _fill_ln (and their merging forms) and for wgnn_predict_rows_thin, whose
+// draws at keep == 1 must carry the bits of the aligned batch.
+__device__ __forceinline__ float lognorm(float x, double total, double scale) {
+#pragma clang fp contract(off)
+    const double q = (double)x / total;
+    const double y = q * scale;
+    return (float)log1p(y);
 }
 
 // Every entry of row r - ALL its columns (CSR: all its stored entries) - handed to visit(j, on, v) in the lane's order of

@@ -973,6 +973,127 @@ def predict_rows_dropout(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Ten
     return votes, unsure, empty, conf_sum, draw_label, draw_prob
 
 
+def predict_rows_thin(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
+                      bias: torch.Tensor, *, rest: torch.Tensor, scale: float = 1e4, threshold: float = 0.0,
+                      self_rows: Optional[torch.Tensor] = None, head: Optional[tuple] = None, unsure_threshold: float = 0.0,
+                      check_cols: bool = True, n_draws: int, keep: float, seed: int, row0: int = 0, draw0: int = 0, out=None,
+                      accumulate: bool = False, want_draws: bool = False, want_reads: bool = False):
+    """``wgnn_predict_rows_thin``: ``predict_rows_dropout`` with READ-LEVEL thinning.  ``raw`` holds the cells' COUNTS over the
+    bundle's genes (float32 integers in [1, 2^24]), ``rest`` int64 [B] a cell's reads outside the bundle; in a draw every read
+    survives with probability ``keep`` - a pure hash of ``(seed, row0 + cell, draw0 + draw, gene id, read number)``
+    (``include/wgnn.h``) - and the surviving counts are log-normalised against the draw's own library size (``scale``, and
+    ``threshold`` on the normalised value, as ``align_rows(normalize="lognorm")`` takes them) before the layer runs.  With
+    ``keep == 1`` every draw carries the bits of ``predict_rows`` on the lognorm-aligned batch.
+
+    Every other argument, the layouts and the return values as ``predict_rows_dropout``.  ``want_reads``: two more per-pair
+    tables ``draw_reads`` / ``draw_entries`` int32 [B, n_draws] - a draw's library size and its participating entries -
+    appended to the return value (without a head: ``(out, draw_reads, draw_entries)``).  CPU tensors are refused; argument
+    errors are ``ValueError``."""
+    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, rest, self_rows, *(head or ()))
+    n_draws = int(n_draws)
+    keep = float(keep)
+    if n_draws < 1:
+        raise ValueError(f"predict_rows_thin: n_draws = {n_draws} must be >= 1")
+    if not 0.0 <= keep <= 1.0:
+        raise ValueError(f"predict_rows_thin: keep = {keep} must be in [0, 1]")
+    if int(row0) < 0 or int(draw0) < 0:
+        raise ValueError("predict_rows_thin: row0 and draw0 must not be negative")
+    if not 0 < float(scale) < float("inf"):
+        raise ValueError(f"predict_rows_thin: scale = {scale} must be positive and finite")
+    if not float(threshold) >= 0:
+        raise ValueError(f"predict_rows_thin: threshold = {threshold} must be >= 0")
+    H = bias.shape[0]
+    table, alpha, G, Hp, B, flags, rowptr, col, raw = _attrib_common("predict_rows_thin", rowptr, col, raw, table, alpha, H,
+                                                                     check_cols)
+    if rest.dtype != torch.int64 or tuple(rest.shape) != (B,):
+        raise ValueError(f"predict_rows_thin: rest must be int64 [{B}]")
+    rest = rest.contiguous()
+    if B * n_draws >= 2 ** 31:
+        raise ValueError("predict_rows_thin: B * n_draws >= 2^31 (split the batch or the draws)")
+    bias = _pad_cols(bias, Hp)
+    if self_rows is not None:
+        if self_rows.shape[0] != B * n_draws:
+            raise ValueError(f"self_rows has {self_rows.shape[0]} rows, the batch {B} cells x {n_draws} draws")
+        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
+    common = (_ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp, _ptr(alpha), _ptr(bias),
+              _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0, _ptr(rest), float(scale), float(threshold),
+              n_draws, int(row0), int(draw0), int(seed) & (2 ** 64 - 1), keep)
+    draw_reads = draw_entries = None
+    if want_reads:
+        draw_reads = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
+        draw_entries = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
+    reads = (draw_reads, draw_entries) if want_reads else ()
+    if head is None:
+        if accumulate or want_draws:
+            raise ValueError("predict_rows_thin: accumulate and want_draws need a head")
+        if out is None:
+            out = torch.empty((B * n_draws, Hp), dtype=torch.float32, device=dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B * n_draws, Hp)
+              or out.stride(1) != 1 or out.stride(0) % 4 or out.stride(0) < Hp or out.data_ptr() % 16):
+            raise ValueError(f"out must be float32 [{B * n_draws}, {Hp}], unit column stride, 16-byte aligned rows")
+        rc = _lib.call(dev, "wgnn_predict_rows_thin", *common, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
+                       None, None, 0, 0.0, None, 0, None, None, None, None, None, _ptr(draw_reads), _ptr(draw_entries), flags,
+                       _stream(dev))
+        _lib.check(rc, "wgnn_predict_rows_thin")
+        h = out if Hp == H else out[:, :H]
+        return (h, *reads) if want_reads else h
+    w_head, b_head = head
+    n_cls = w_head.shape[0]
+    if n_cls * Hp * 4 > HEAD_LDS_BYTES:
+        raise ValueError(f"predict_rows_thin: a [{n_cls}, {Hp}] head is beyond the {HEAD_LDS_BYTES} bytes the kernel stages")
+    w_head = _pad_cols(w_head, Hp)
+    b_head = b_head.float().contiguous()
+    if out is None:
+        if accumulate:
+            raise ValueError("accumulate needs the tables to add to (out=)")
+        out = (torch.empty((B, n_cls), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float64, device=dev))
+    if len(out) not in (4, 6):
+        raise ValueError("out must be (votes, unsure, empty, conf_sum[, draw_label, draw_prob])")
+    votes, unsure, empty, conf_sum = out[:4]
+    draw_label, draw_prob = out[4:] if len(out) == 6 else (None, None)
+    if draw_label is None and want_draws:
+        draw_label = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
+        draw_prob = torch.empty((B, n_draws), dtype=torch.float32, device=dev)
+    _require_cuda(votes, unsure, empty, conf_sum, draw_label, draw_prob)
+    if (votes.dtype != torch.int32 or tuple(votes.shape) != (B, n_cls) or (n_cls > 1 and votes.stride(1) != 1)
+            or (B > 1 and votes.stride(0) < n_cls)):
+        raise ValueError(f"votes must be int32 [{B}, {n_cls}] with unit column stride and a row stride >= {n_cls}")
+    want = ((unsure, torch.int32, (B,)), (empty, torch.int32, (B,)), (conf_sum, torch.float64, (B,)))
+    if any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want):
+        raise ValueError(f"unsure and empty must be contiguous int32 [{B}], conf_sum float64 [{B}]")
+    if draw_label is not None:
+        per = ((draw_label, torch.int32), (draw_prob, torch.float32))
+        if any(t is None or t.dtype != d or tuple(t.shape) != (B, n_draws) or not t.is_contiguous() for t, d in per):
+            raise ValueError(f"draw_label / draw_prob must be contiguous int32 / float32 [{B}, {n_draws}]")
+    rc = _lib.call(dev, "wgnn_predict_rows_thin", *common, None, 0, _ptr(w_head), _ptr(b_head), n_cls,
+                   float(unsure_threshold), _ptr(votes), votes.stride(0) if B > 1 else max(int(votes.stride(0)), n_cls),
+                   _ptr(unsure), _ptr(empty), _ptr(conf_sum), _ptr(draw_label), _ptr(draw_prob), _ptr(draw_reads),
+                   _ptr(draw_entries), flags | (_lib.THIN_ACCUMULATE if accumulate else 0), _stream(dev))
+    _lib.check(rc, "wgnn_predict_rows_thin")
+    return (votes, unsure, empty, conf_sum, draw_label, draw_prob, *reads)
+
+
+def thin_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, rest: torch.Tensor, total: torch.Tensor) -> None:
+    """The one fused device check ``stability(thin="reads")`` makes of its operand: every count of ``raw`` an integer in
+    [1, 2^24], every ``rest`` (float64 [B], exact) a non-negative integer, every cell's ``total`` below 2^31.  One reduction to
+    the first offending cell and one read-back; ``WgnnError`` naming that cell."""
+    B = int(rowptr.shape[0]) - 1
+    if B == 0:
+        return
+    bad_entry = (raw != torch.floor(raw)) | (raw < 1) | (raw > 16777216.0) if raw.numel() else raw.new_zeros(0, dtype=torch.bool)
+    rows = torch.repeat_interleave(torch.arange(B, device=raw.device), (rowptr[1:] - rowptr[:-1]).long(), output_size=raw.shape[0])
+    bad_cell = (rest != torch.floor(rest)) | (rest < 0) | ~(total < 2.0 ** 31)
+    first = torch.where(bad_cell, torch.arange(B, device=raw.device), B).min()
+    if raw.numel():
+        first = torch.minimum(first, torch.where(bad_entry, rows, B).min())
+    first = int(first)
+    if first < B:
+        raise WgnnError(f"thin=\"reads\" takes integer counts: cell {first} holds a count that is no integer in [1, 2^24], reads "
+                        f"outside the bundle that are no non-negative integer (a library size below the cell's matched reads?), "
+                        f"or 2^31 reads or more")
+
+
 def _attrib_common(name, rowptr, col, raw, table, alpha, H, check_cols):
     """The batch / table handling ``predict_rows`` does, shared by ``attrib_rows``: returns (table, alpha, G, Hp, B, flags,
     rowptr, col, raw) ready for the C call."""
