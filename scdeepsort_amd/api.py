@@ -1616,10 +1616,8 @@ class ResidentPredictor:
             thin_kw = dict(scale=float(spec.scale_factor), threshold=float(self.threshold))
         else:
             rowptr, col, raw, checked, _ = self._device_csr(expr)
-            if not checked and col.numel():                # once for the whole call: every launch below skips the check
-                lo, hi = torch.aminmax(col)
-                if int(lo) < 0 or int(hi) >= self.n_genes:
-                    raise WgnnError(f"gene id out of range [0, {self.n_genes}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+            if not checked:                                # once for the whole call: every launch below skips the check
+                _ops.check_gene_ids(col, self.n_genes)
             pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
         B, L, C, Hp = int(rowptr.shape[0]) - 1, len(levels), self.n_classes, self.hidden_padded
         if into is None:

@@ -36,8 +36,6 @@
 // skipped and reported (WGNN_ALIGN_BAD_VALUE).
 
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
 #include "wgnn_common.h"
 #include "wgnn_align_rows.h"
 
@@ -259,31 +257,6 @@ int launch(const AArgs& a, bool i64, hipStream_t st) {
 
 }  // namespace
 
-namespace wgnn {
-// the failing check of the last wgnn_align_count / wgnn_align_fill call on this thread, handed out once (as predict_error_detail)
-thread_local int align_err_code = 0;
-thread_local char align_err_msg[256];
-thread_local char align_err_out[256];
-
-int align_fail(int code, const char* fn, const char* what) {
-    (void)predict_error_detail(code);             // a detail another entry left unasked for this code would be handed out first:
-    (void)attrib_error_detail(code);              // the last failing call is the one wgnn_last_error_string speaks of
-    (void)markers_error_detail(code);
-    align_err_code = code;
-    snprintf(align_err_msg, sizeof align_err_msg, "%s - %s: %s", wgnn_generic_error_string(code), fn, what);
-    return code;
-}
-
-void align_error_clear() { align_err_code = 0; }
-
-const char* align_error_detail(int code) {
-    if (code == 0 || code != align_err_code) return nullptr;
-    align_err_code = 0;
-    memcpy(align_err_out, align_err_msg, sizeof align_err_out);
-    return align_err_out;
-}
-}  // namespace wgnn
-
 // the checks COUNT and FILL share, then the launch; fn names the entry point in the error detail.  LN: the log-normalising walk
 // (COUNT stores the row totals in total_out, FILL reads them from total).
 template <bool FILL, bool LN>
@@ -292,8 +265,8 @@ static int align_run(const char* fn, const float* x, int64_t ld, const void* row
                      int32_t* row_count, const int64_t* out_rowptr, int32_t* out_col, float* out_raw, int32_t* status,
                      uint32_t flags, void* stream, const double* total = nullptr, double scale = 0.0,
                      double* total_out = nullptr, const double* library_size = nullptr) {
-    auto fail = [fn](int code, const char* what) { return wgnn::align_fail(code, fn, what); };
-    wgnn::align_err_code = 0;
+    auto fail = [fn](int code, const char* what) { return wgnn::fail(code, fn, what); };
+    wgnn::error_clear();
     if (!status) return fail(WGNN_ERR_BAD_ARG, "status is required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
     if (n_cols < 0) return fail(WGNN_ERR_BAD_ARG, "n_cols must not be negative");

@@ -387,8 +387,8 @@ int merge_run(const char* fn, const float* x, int64_t ld, const void* rowptr, co
               const int32_t* group_ptr, const int32_t* group_cols, int32_t n_groups, int32_t n_members, int32_t* row_count,
               const int64_t* out_rowptr, int32_t* out_col, float* out_raw, int32_t* status, uint32_t flags, void* stream,
               const double* total, double scale, double* total_out, const double* library_size) {
-    auto fail = [fn](int code, const char* what) { return wgnn::align_fail(code, fn, what); };
-    wgnn::align_error_clear();
+    auto fail = [fn](int code, const char* what) { return wgnn::fail(code, fn, what); };
+    wgnn::error_clear();
     if (!status) return fail(WGNN_ERR_BAD_ARG, "status is required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
     if (n_cols < 0) return fail(WGNN_ERR_BAD_ARG, "n_cols must not be negative");

@@ -17,9 +17,7 @@
 // store.  A row is owned by one wave (the accumulate is race-free); no atomics, fixed fold order: two launches are bit-identical.
 
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
-#include "wgnn_common.h"
+#include "wgnn_resident_rows.h"
 
 namespace {
 using namespace wgnn;
@@ -27,7 +25,6 @@ using namespace wgnn;
 constexpr int kAWaves = 8;                    // waves per workgroup (one head image in LDS serves all of them)
 constexpr int kABlock = 64 * kAWaves;
 constexpr int kAMaxBlocks = 1024;             // 256 CUs x 4 workgroups: grid-stride beyond that
-constexpr int kAHeadLdsBytes = 64 * 1024;
 constexpr int kTWaves = 4;                    // wgnn_rows_topk
 constexpr int kTBlock = 64 * kTWaves;
 constexpr int kTMaxBlocks = 2048;
@@ -42,17 +39,6 @@ struct AArgs {
     float* score; int accumulate;
     int* target_out; float* logit_out; float* base_out; float* dir_out; long ld_dir_out;
 };
-
-// (value, index) maximum over the lane groups: larger value wins, the lower index among equal values
-template <int LPR>
-__device__ __forceinline__ void group_argmax_fold(float& m, int& am) {
-#pragma unroll
-    for (int off = LPR; off < 64; off <<= 1) {
-        const float mo = __shfl_xor(m, off, 64);
-        const int ao = __shfl_xor(am, off, 64);
-        if (mo > m || (mo == m && ao < am)) { m = mo; am = ao; }
-    }
-}
 
 // HEAD: gather + head + scores of the last layer; else scores against a given direction.  SELF_ROWS: the layer's self-loop is
 // explicit (no self term in the per-entry coefficient; in head mode a.self_rows enters z).
@@ -225,16 +211,6 @@ int launch_lpr(const AArgs& a, bool rowptr_i64, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? WGNN_OK : WGNN_ERR_LAUNCH;
 }
 
-template <bool HEAD, bool SELF_ROWS>
-int dispatch_lpr(const AArgs& a, bool i64, hipStream_t st) {
-    const int q = a.H / 4;
-    if (q <= 4)  return launch_lpr<4, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 8)  return launch_lpr<8, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 16) return launch_lpr<16, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 32) return launch_lpr<32, HEAD, SELF_ROWS>(a, i64, st);
-    return launch_lpr<64, HEAD, SELF_ROWS>(a, i64, st);
-}
-
 // wgnn_rows_topk: k rounds of "the best entry after the one taken last" in the order (score descending, position ascending).
 // Lane i scans positions i, i + 64, ... (ascending, so a strict > keeps its lowest position), a butterfly picks the wave's
 // best.  Round i's result is kept by lane i and the k results leave with one store.  `score` is only read.
@@ -274,26 +250,6 @@ __global__ void __launch_bounds__(kTBlock) rows_topk_kernel(const TPtr* rp, cons
 
 }  // namespace
 
-namespace wgnn {
-// the failing check of the last wgnn_attrib_rows / wgnn_rows_topk call on this thread, handed out once (as predict_error_detail)
-thread_local int attrib_err_code = 0;
-thread_local char attrib_err_msg[256];
-thread_local char attrib_err_out[256];
-
-static int attrib_fail(int code, const char* fn, const char* what) {
-    attrib_err_code = code;
-    snprintf(attrib_err_msg, sizeof attrib_err_msg, "%s - %s: %s", wgnn_generic_error_string(code), fn, what);
-    return code;
-}
-
-const char* attrib_error_detail(int code) {
-    if (code == 0 || code != attrib_err_code) return nullptr;
-    attrib_err_code = 0;
-    memcpy(attrib_err_out, attrib_err_msg, sizeof attrib_err_out);
-    return attrib_err_out;
-}
-}  // namespace wgnn
-
 extern "C" int wgnn_attrib_rows(const void* rowptr, const int32_t* col, const float* raw, int64_t n_rows,
                                 const float* table, int64_t ld_table, int32_t n_genes, int32_t H,
                                 const float* alpha, const float* bias, const float* self_rows, int64_t ld_self,
@@ -301,8 +257,8 @@ extern "C" int wgnn_attrib_rows(const void* rowptr, const int32_t* col, const fl
                                 float unsure_threshold, int32_t* label_out, const float* direction, int64_t ld_dir,
                                 float* score, int32_t* target_out, float* logit_out, float* base_out,
                                 float* dir_out, int64_t ld_dir_out, uint32_t flags, void* stream) {
-    auto fail = [](int code, const char* what) { return wgnn::attrib_fail(code, "wgnn_attrib_rows", what); };
-    wgnn::attrib_err_code = 0;
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_attrib_rows", what); };
+    wgnn::error_clear();
     if (!rowptr || !col || !raw || !table || !alpha || !score)
         return fail(WGNN_ERR_BAD_ARG, "rowptr, col, raw, table, alpha and score are required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
@@ -326,7 +282,7 @@ extern "C" int wgnn_attrib_rows(const void* rowptr, const int32_t* col, const fl
         if (self_rows && (ld_self < H || ld_self % 4 || !aligned16(self_rows)))
             return fail(WGNN_ERR_ALIGNMENT, "self_rows: ld_self >= H, a multiple of 4, 16-byte aligned");
         if (n_classes <= 0) return fail(WGNN_ERR_BAD_ARG, "n_classes must be positive");
-        if ((int64_t)n_classes * H * 4 > kAHeadLdsBytes)
+        if ((int64_t)n_classes * H * 4 > kHeadLdsBytes)
             return fail(WGNN_ERR_UNSUPPORTED, "the head needs C*H*4 <= 64 KiB");
         if (!aligned16(w_head)) return fail(WGNN_ERR_ALIGNMENT, "w_head must be 16-byte aligned");
         if (dir_out && (ld_dir_out < H || ld_dir_out % 4 || !aligned16(dir_out)))
@@ -348,16 +304,16 @@ extern "C" int wgnn_attrib_rows(const void* rowptr, const int32_t* col, const fl
     a.target_out = target_out; a.logit_out = logit_out; a.base_out = base_out; a.dir_out = dir_out; a.ld_dir_out = ld_dir_out;
     const bool i64 = flags & WGNN_FLAG_ROWPTR_I64;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    if (head) rc = explicit_self ? dispatch_lpr<true, true>(a, i64, st) : dispatch_lpr<true, false>(a, i64, st);
-    else rc = explicit_self ? dispatch_lpr<false, true>(a, i64, st) : dispatch_lpr<false, false>(a, i64, st);
+    const int rc = wgnn::dispatch_rows(H, head, explicit_self, [&](auto lpr, auto hd, auto sf) {
+        return launch_lpr<decltype(lpr)::value, decltype(hd)::value, decltype(sf)::value>(a, i64, st);
+    });
     return rc == WGNN_OK ? rc : fail(rc, "HIP launch failed");
 }
 
 extern "C" int wgnn_rows_topk(const void* rowptr, const int32_t* col, const float* score, int64_t n_rows, int32_t k,
                               int32_t* gene_out, float* score_out, uint32_t flags, void* stream) {
-    auto fail = [](int code, const char* what) { return wgnn::attrib_fail(code, "wgnn_rows_topk", what); };
-    wgnn::attrib_err_code = 0;
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_rows_topk", what); };
+    wgnn::error_clear();
     if (!rowptr || !col || !score || !gene_out || !score_out)
         return fail(WGNN_ERR_BAD_ARG, "rowptr, col, score, gene_out and score_out are required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");

@@ -190,8 +190,8 @@ void launch_chunks(unsigned nb, hipStream_t st, const CArgs& a) {
 }  // namespace
 
 extern "C" int wgnn_group_class_reduce_workspace(int64_t n_rows, int32_t n_groups, int32_t n_classes, int64_t* bytes) {
-    auto fail = [](int code, const char* what) { return wgnn::align_fail(code, "wgnn_group_class_reduce_workspace", what); };
-    wgnn::align_error_clear();
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_group_class_reduce_workspace", what); };
+    wgnn::error_clear();
     if (!bytes) return fail(WGNN_ERR_BAD_ARG, "bytes is required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
     if (n_groups <= 0) return fail(WGNN_ERR_BAD_ARG, "n_groups must be positive");
@@ -206,9 +206,9 @@ extern "C" int wgnn_group_class_reduce(const float* logits, int64_t ld_logits, c
                                        const void* seg_ptr, int64_t n_rows, int32_t n_groups, int32_t n_classes,
                                        double* prob_sum, double* conf_sum, int32_t* votes, int32_t* tally,
                                        void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream) {
-    auto fail = [](int code, const char* what) { return wgnn::align_fail(code, "wgnn_group_class_reduce", what); };
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_group_class_reduce", what); };
     auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
-    wgnn::align_error_clear();
+    wgnn::error_clear();
     if (!prob_sum || !conf_sum || !votes || !tally) return fail(WGNN_ERR_BAD_ARG, "prob_sum, conf_sum, votes and tally are required");
     if (!seg_ptr) return fail(WGNN_ERR_BAD_ARG, "seg_ptr is required");
     if (n_groups <= 0) return fail(WGNN_ERR_BAD_ARG, "n_groups must be positive");

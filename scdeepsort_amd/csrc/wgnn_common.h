@@ -149,14 +149,12 @@ __device__ __forceinline__ void epilogue(const KArgs& a, float4 (&acc)[NV], int 
 }
 
 
-// wgnn_last_error_string's text for `code`, and the failing check of the last wgnn_predict_rows call on this thread (or NULL)
+// wgnn_last_error_string's text for `code`, and the one per-thread slot behind it that the resident entries (wgnn_predict_rows*,
+// wgnn_attrib_rows, wgnn_rows_topk, wgnn_group_*_reduce, wgnn_align_*, wgnn_coverage_rows) report through (wgnn_kernels.hip)
 const char* wgnn_generic_error_string(int code);
-const char* predict_error_detail(int code);
-const char* attrib_error_detail(int code);       // the same for wgnn_attrib_rows / wgnn_rows_topk
-const char* markers_error_detail(int code);      // and for wgnn_group_gene_reduce
-const char* align_error_detail(int code);        // and for wgnn_align_count / wgnn_align_fill / wgnn_coverage_rows
-int align_fail(int code, const char* fn, const char* what);      // records that detail for entry point `fn`, returns code
-void align_error_clear();                                        // a new call of those entries forgets the last detail
+int fail(int code, const char* fn, const char* what);    // records the failing check of entry point `fn`, returns code
+void error_clear();                                      // a new call of those entries forgets the last detail
+const char* error_detail(int code);                      // the detail recorded for `code`, handed out once (else NULL)
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }

@@ -153,8 +153,8 @@ extern "C" int wgnn_coverage_rows(const float* x, int64_t ld, const void* rowptr
                                   int64_t n_rows, int32_t n_cols, const int32_t* gene_map, int32_t n_genes,
                                   int32_t* n_expressed, int32_t* n_mapped, int32_t* n_bad, double* total, double* total_mapped,
                                   int32_t* col_cells, int32_t* status, uint32_t flags, void* stream) {
-    auto fail = [](int code, const char* what) { return wgnn::align_fail(code, "wgnn_coverage_rows", what); };
-    wgnn::align_error_clear();
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_coverage_rows", what); };
+    wgnn::error_clear();
     if (!status) return fail(WGNN_ERR_BAD_ARG, "status is required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
     if (n_cols < 0) return fail(WGNN_ERR_BAD_ARG, "n_cols must not be negative");

@@ -20,6 +20,8 @@
 // no atomics).
 
 #include <limits.h>
+#include <stdio.h>
+#include <string.h>
 #include "wgnn_common.h"
 
 namespace {
@@ -290,14 +292,36 @@ int wgnn_agg_workspace_bytes(int64_t n_partials, int64_t n_src, int32_t D, int a
 }
 
 const char* wgnn_last_error_string(int code) {
-    if (const char* d = wgnn::predict_error_detail(code)) return d;
-    if (const char* d = wgnn::attrib_error_detail(code)) return d;
-    if (const char* d = wgnn::markers_error_detail(code)) return d;
-    if (const char* d = wgnn::align_error_detail(code)) return d;
+    if (const char* d = wgnn::error_detail(code)) return d;
     return wgnn::wgnn_generic_error_string(code);
 }
 
 }  // extern "C"
+
+// What the last failing call of a resident entry on this thread found wrong: handed out ONCE, by the next
+// wgnn_last_error_string(code) on the same thread with the same code (python's _lib.check asks right after the call); every
+// later request, and every other code, gets the generic text.  One slot for all those entries: each clears it on entry, so the
+// detail is that of the last call whichever entry it went to.
+namespace wgnn {
+static thread_local int err_code = 0;
+static thread_local char err_msg[256];
+static thread_local char err_out[256];
+
+int fail(int code, const char* fn, const char* what) {
+    err_code = code;
+    snprintf(err_msg, sizeof err_msg, "%s - %s: %s", wgnn_generic_error_string(code), fn, what);
+    return code;
+}
+
+void error_clear() { err_code = 0; }
+
+const char* error_detail(int code) {
+    if (code == 0 || code != err_code) return nullptr;
+    err_code = 0;
+    memcpy(err_out, err_msg, sizeof err_out);
+    return err_out;
+}
+}  // namespace wgnn
 
 const char* wgnn::wgnn_generic_error_string(int code) {
     switch (code) {

@@ -14,8 +14,6 @@
 // bit-identical.  More groups than fit (64 KiB of LDS per workgroup, 12 bytes per lane and group: 85 per wave) are cut into
 // passes over the run, which L2 holds by then.  Up to 4 waves per workgroup while their bins fit.
 
-#include <stdio.h>
-#include <string.h>
 #include "wgnn_common.h"
 
 namespace {
@@ -104,31 +102,9 @@ void geometry(int n_groups, int* per_pass, int* waves) {
 
 }  // namespace
 
-namespace wgnn {
-// the failing check of the last wgnn_group_gene_reduce call on this thread, handed out once (as predict_error_detail)
-thread_local int markers_err_code = 0;
-thread_local char markers_err_msg[256];
-thread_local char markers_err_out[256];
-
-static int markers_fail(int code, const char* fn, const char* what) {
-    (void)predict_error_detail(code);             // a detail another entry left unasked for this code would be handed out first:
-    (void)attrib_error_detail(code);              // the last failing call is the one wgnn_last_error_string speaks of
-    markers_err_code = code;
-    snprintf(markers_err_msg, sizeof markers_err_msg, "%s - %s: %s", wgnn_generic_error_string(code), fn, what);
-    return code;
-}
-
-const char* markers_error_detail(int code) {
-    if (code == 0 || code != markers_err_code) return nullptr;
-    markers_err_code = 0;
-    memcpy(markers_err_out, markers_err_msg, sizeof markers_err_out);
-    return markers_err_out;
-}
-}  // namespace wgnn
-
 extern "C" int wgnn_group_gene_reduce_workspace(int64_t n_rows, int64_t nnz, int32_t n_groups, int32_t n_genes, int64_t* bytes) {
-    auto fail = [](int code, const char* what) { return wgnn::markers_fail(code, "wgnn_group_gene_reduce_workspace", what); };
-    wgnn::markers_err_code = 0;
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_group_gene_reduce_workspace", what); };
+    wgnn::error_clear();
     if (!bytes) return fail(WGNN_ERR_BAD_ARG, "bytes is required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
     if (nnz < 0 || nnz > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "nnz must be in [0, 2^31)");
@@ -142,8 +118,8 @@ extern "C" int wgnn_group_gene_reduce_workspace(int64_t n_rows, int64_t nnz, int
 extern "C" int wgnn_group_gene_reduce(const int32_t* t_rowptr, const int32_t* t_cell, const float* t_score, const int32_t* group,
                                       int64_t n_rows, int32_t n_groups, int32_t n_genes, double* sum, int32_t* count,
                                       void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream) {
-    auto fail = [](int code, const char* what) { return wgnn::markers_fail(code, "wgnn_group_gene_reduce", what); };
-    wgnn::markers_err_code = 0;
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_group_gene_reduce", what); };
+    wgnn::error_clear();
     (void)workspace;
     if (!sum || !count) return fail(WGNN_ERR_BAD_ARG, "sum and count are required");
     if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");

@@ -19,9 +19,7 @@
 // before the first FMA.  No plan, no atomics: every sum is folded in a fixed order, two launches are bit-identical.
 
 #include <math.h>
-#include <stdio.h>
-#include <string.h>
-#include "wgnn_common.h"
+#include "wgnn_resident_rows.h"
 
 namespace {
 using namespace wgnn;
@@ -29,7 +27,6 @@ using namespace wgnn;
 constexpr int kPWaves = 8;                    // waves per workgroup (one head image in LDS serves all of them)
 constexpr int kPBlock = 64 * kPWaves;
 constexpr int kPMaxBlocks = 1024;             // 256 CUs x 4 workgroups: grid-stride beyond that
-constexpr int kHeadLdsBytes = 64 * 1024;
 
 struct PArgs {
     const void* rowptr; const int* col; const float* raw; long n_rows;
@@ -40,17 +37,6 @@ struct PArgs {
     const float* w_head; const float* b_head; int C; float thr;
     float* logits; long ld_logits; int* label; float* max_prob;
 };
-
-// (value, index) maximum over the lane groups: larger value wins, the lower index among equal values
-template <int LPR>
-__device__ __forceinline__ void group_argmax_fold(float& m, int& am) {
-#pragma unroll
-    for (int off = LPR; off < 64; off <<= 1) {
-        const float mo = __shfl_xor(m, off, 64);
-        const int ao = __shfl_xor(am, off, 64);
-        if (mo > m || (mo == m && ao < am)) { m = mo; am = ao; }
-    }
-}
 
 template <int LPR, bool HEAD, bool SELF_ROWS, typename TPtr>
 __global__ void __launch_bounds__(kPBlock) predict_rows_kernel(const PArgs a) {
@@ -171,39 +157,7 @@ int launch_lpr(const PArgs& a, bool rowptr_i64, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? WGNN_OK : WGNN_ERR_LAUNCH;
 }
 
-template <bool HEAD, bool SELF_ROWS>
-int dispatch_lpr(const PArgs& a, bool i64, hipStream_t st) {
-    const int q = a.H / 4;
-    if (q <= 4)  return launch_lpr<4, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 8)  return launch_lpr<8, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 16) return launch_lpr<16, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 32) return launch_lpr<32, HEAD, SELF_ROWS>(a, i64, st);
-    return launch_lpr<64, HEAD, SELF_ROWS>(a, i64, st);
-}
-
 }  // namespace
-
-namespace wgnn {
-// What the last failing wgnn_predict_rows call on this thread found wrong: handed out ONCE, by the next
-// wgnn_last_error_string(code) on the same thread with the same code (python's _lib.check asks right after the call), so a
-// later failure of another entry point with that code still gets the generic text.
-thread_local int predict_err_code = 0;
-thread_local char predict_err_msg[256];
-thread_local char predict_err_out[256];
-
-static int predict_fail(int code, const char* what) {
-    predict_err_code = code;
-    snprintf(predict_err_msg, sizeof predict_err_msg, "%s - wgnn_predict_rows: %s", wgnn_generic_error_string(code), what);
-    return code;
-}
-
-const char* predict_error_detail(int code) {
-    if (code == 0 || code != predict_err_code) return nullptr;
-    predict_err_code = 0;
-    memcpy(predict_err_out, predict_err_msg, sizeof predict_err_out);
-    return predict_err_out;
-}
-}  // namespace wgnn
 
 extern "C" int wgnn_predict_rows(const void* rowptr, const int32_t* col, const float* raw, int64_t n_rows,
                                  const float* table, int64_t ld_table, int32_t n_genes, int32_t H,
@@ -212,32 +166,32 @@ extern "C" int wgnn_predict_rows(const void* rowptr, const int32_t* col, const f
                                  const float* w_head, const float* b_head, int32_t n_classes, float unsure_threshold,
                                  float* logits, int64_t ld_logits, int32_t* label, float* max_prob,
                                  uint32_t flags, void* stream) {
-    using wgnn::predict_fail;
-    wgnn::predict_err_code = 0;
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_predict_rows", what); };
+    wgnn::error_clear();
     if (!rowptr || !col || !raw || !table || !alpha || !bias)
-        return predict_fail(WGNN_ERR_BAD_ARG, "rowptr, col, raw, table, alpha and bias are required");
-    if (n_rows < 0 || n_rows > INT32_MAX) return predict_fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
-    if (n_genes <= 0) return predict_fail(WGNN_ERR_BAD_ARG, "n_genes must be positive");
-    if (flags & ~WGNN_FLAG_ROWPTR_I64) return predict_fail(WGNN_ERR_BAD_ARG, "only WGNN_FLAG_ROWPTR_I64 is a valid flag");
-    if (H <= 0) return predict_fail(WGNN_ERR_BAD_ARG, "H must be positive");
-    if (H % 4) return predict_fail(WGNN_ERR_ALIGNMENT, "H must be a multiple of 4 (zero-pad the table, bias and head)");
-    if (H > 256) return predict_fail(WGNN_ERR_UNSUPPORTED, "H > 256 is not built (use the graph route)");
-    if (ld_table < H || ld_table % 4) return predict_fail(WGNN_ERR_ALIGNMENT, "ld_table must be >= H and a multiple of 4");
-    if (!aligned16(table) || !aligned16(bias)) return predict_fail(WGNN_ERR_ALIGNMENT, "table and bias must be 16-byte aligned");
+        return fail(WGNN_ERR_BAD_ARG, "rowptr, col, raw, table, alpha and bias are required");
+    if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
+    if (n_genes <= 0) return fail(WGNN_ERR_BAD_ARG, "n_genes must be positive");
+    if (flags & ~WGNN_FLAG_ROWPTR_I64) return fail(WGNN_ERR_BAD_ARG, "only WGNN_FLAG_ROWPTR_I64 is a valid flag");
+    if (H <= 0) return fail(WGNN_ERR_BAD_ARG, "H must be positive");
+    if (H % 4) return fail(WGNN_ERR_ALIGNMENT, "H must be a multiple of 4 (zero-pad the table, bias and head)");
+    if (H > 256) return fail(WGNN_ERR_UNSUPPORTED, "H > 256 is not built (use the graph route)");
+    if (ld_table < H || ld_table % 4) return fail(WGNN_ERR_ALIGNMENT, "ld_table must be >= H and a multiple of 4");
+    if (!aligned16(table) || !aligned16(bias)) return fail(WGNN_ERR_ALIGNMENT, "table and bias must be 16-byte aligned");
     if (self_rows && (ld_self < H || ld_self % 4 || !aligned16(self_rows)))
-        return predict_fail(WGNN_ERR_ALIGNMENT, "self_rows: ld_self >= H, a multiple of 4, 16-byte aligned");
+        return fail(WGNN_ERR_ALIGNMENT, "self_rows: ld_self >= H, a multiple of 4, 16-byte aligned");
     const bool head = w_head != nullptr;
     if (head) {
-        if (!b_head || !label || !max_prob) return predict_fail(WGNN_ERR_BAD_ARG, "a head needs b_head, label and max_prob");
-        if (n_classes <= 0) return predict_fail(WGNN_ERR_BAD_ARG, "n_classes must be positive");
+        if (!b_head || !label || !max_prob) return fail(WGNN_ERR_BAD_ARG, "a head needs b_head, label and max_prob");
+        if (n_classes <= 0) return fail(WGNN_ERR_BAD_ARG, "n_classes must be positive");
         if ((int64_t)n_classes * H * 4 > kHeadLdsBytes)
-            return predict_fail(WGNN_ERR_UNSUPPORTED, "the head needs C*H*4 <= 64 KiB (run it as a GEMM)");
-        if (!aligned16(w_head)) return predict_fail(WGNN_ERR_ALIGNMENT, "w_head must be 16-byte aligned");
-        if (logits && ld_logits < n_classes) return predict_fail(WGNN_ERR_BAD_ARG, "ld_logits must be >= n_classes");
+            return fail(WGNN_ERR_UNSUPPORTED, "the head needs C*H*4 <= 64 KiB (run it as a GEMM)");
+        if (!aligned16(w_head)) return fail(WGNN_ERR_ALIGNMENT, "w_head must be 16-byte aligned");
+        if (logits && ld_logits < n_classes) return fail(WGNN_ERR_BAD_ARG, "ld_logits must be >= n_classes");
     } else {
-        if (!out) return predict_fail(WGNN_ERR_BAD_ARG, "without a head `out` is required");
+        if (!out) return fail(WGNN_ERR_BAD_ARG, "without a head `out` is required");
         if (ld_out < H || ld_out % 4 || !aligned16(out))
-            return predict_fail(WGNN_ERR_ALIGNMENT, "out: ld_out >= H, a multiple of 4, 16-byte aligned");
+            return fail(WGNN_ERR_ALIGNMENT, "out: ld_out >= H, a multiple of 4, 16-byte aligned");
     }
     if (n_rows == 0) return WGNN_OK;
     PArgs a{};
@@ -249,8 +203,8 @@ extern "C" int wgnn_predict_rows(const void* rowptr, const int32_t* col, const f
     a.logits = logits; a.ld_logits = ld_logits; a.label = label; a.max_prob = max_prob;
     const bool i64 = flags & WGNN_FLAG_ROWPTR_I64;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    if (head) rc = self_rows ? dispatch_lpr<true, true>(a, i64, st) : dispatch_lpr<true, false>(a, i64, st);
-    else rc = self_rows ? dispatch_lpr<false, true>(a, i64, st) : dispatch_lpr<false, false>(a, i64, st);
-    return rc == WGNN_OK ? rc : predict_fail(rc, "HIP launch failed");
+    const int rc = wgnn::dispatch_rows(H, head, self_rows != nullptr, [&](auto lpr, auto hd, auto sf) {
+        return launch_lpr<decltype(lpr)::value, decltype(hd)::value, decltype(sf)::value>(a, i64, st);
+    });
+    return rc == WGNN_OK ? rc : fail(rc, "HIP launch failed");
 }

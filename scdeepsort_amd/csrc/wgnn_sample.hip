@@ -12,7 +12,7 @@
 // counter-based hash of (seed, step, stream, row, draw) - no generator state is read back, so the call is free of host
 // synchronisation and a captured hipGraph draws a fresh sample on every replay (`step` is a device counter the caller
 // increments on the stream).  Output is ELL: row i owns out_col/out_val[i*k .. i*k + out_cnt[i]), real edges first.
-#include "wgnn_common.h"
+#include "wgnn_resident_rows.h"          // mix32, the splitmix64 finaliser's upper half
 
 namespace {
 using namespace wgnn;
@@ -22,14 +22,6 @@ struct SArgs {
     unsigned long long seed; const long long* step; int stream_id;
     int* out_col; float* out_val; int* out_cnt; float* out_self; float* out_inv;
 };
-
-__device__ __forceinline__ unsigned mix32(unsigned long long x) {          // splitmix64 finaliser, upper half
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return (unsigned)(x >> 32);
-}
 
 constexpr int kMaxQ = 4;                                                   // k <= 64 * kMaxQ
 

@@ -21,8 +21,7 @@
 // weights are SELECTED to 0, never multiplied, so no NaN comes out of 0 / 0.
 
 #include <math.h>
-#include <string.h>
-#include "wgnn_common.h"
+#include "wgnn_resident_rows.h"
 
 namespace {
 using namespace wgnn;
@@ -31,7 +30,6 @@ constexpr int kSWaves = 8;                    // waves per workgroup = draws of 
 constexpr int kSBlock = 64 * kSWaves;
 constexpr int kSMaxBlocks = 1024;             // 256 CUs x 4 workgroups: grid-stride beyond that
 constexpr int kSSlots = 256;                  // draws tallied per LDS round
-constexpr int kSHeadLdsBytes = 64 * 1024;
 constexpr int kSSlotBytes = kSSlots * 12;     // max_prob f32, label int32, empty int32
 
 struct SArgs {
@@ -46,29 +44,8 @@ struct SArgs {
     int* draw_label; float* draw_prob; int accumulate;
 };
 
-__device__ __forceinline__ unsigned mix32(unsigned long long x) {          // splitmix64 finaliser, upper half (as wgnn_sample.hip)
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return (unsigned)(x >> 32);
-}
-
 __device__ __forceinline__ bool kept_entry(unsigned long long key, int gene, unsigned long long T) {
     return (unsigned long long)mix32(key + (unsigned long long)(long long)gene * 0xC2B2AE3D27D4EB4Full) < T;
-}
-
-// lane `dst` receives this lane's value (dst is a permutation of 0..63 over the wave)
-__device__ __forceinline__ int push_to_lane(int dst, int v) { return __builtin_amdgcn_ds_permute(dst << 2, v); }
-
-template <int LPR>
-__device__ __forceinline__ void group_argmax_fold(float& m, int& am) {     // as predict_rows_kernel
-#pragma unroll
-    for (int off = LPR; off < 64; off <<= 1) {
-        const float mo = __shfl_xor(m, off, 64);
-        const int ao = __shfl_xor(am, off, 64);
-        if (mo > m || (mo == m && ao < am)) { m = mo; am = ao; }
-    }
 }
 
 template <int LPR, bool HEAD, bool SELF_ROWS, typename TPtr>
@@ -227,7 +204,7 @@ int launch_one(const SArgs& a, hipStream_t st) {
     const unsigned nb = (unsigned)(a.n_rows < kSMaxBlocks ? a.n_rows : kSMaxBlocks);
     const size_t lds = HEAD ? (size_t)a.C * a.H * sizeof(float) + kSSlotBytes : 0;
     auto fn = predict_rows_dropout_kernel<LPR, HEAD, SELF_ROWS, TPtr>;
-    if (lds > (size_t)kSHeadLdsBytes &&                  // a head of (nearly) 64 KiB plus the slots: ask for the larger window
+    if (lds > (size_t)kHeadLdsBytes &&                   // a head of (nearly) 64 KiB plus the slots: ask for the larger window
         hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return WGNN_ERR_LAUNCH;
     hipLaunchKernelGGL(fn, dim3(nb), dim3(kSBlock), lds, st, a);
@@ -237,16 +214,6 @@ int launch_one(const SArgs& a, hipStream_t st) {
 template <int LPR, bool HEAD, bool SELF_ROWS>
 int launch_lpr(const SArgs& a, bool i64, hipStream_t st) {
     return i64 ? launch_one<LPR, HEAD, SELF_ROWS, long long>(a, st) : launch_one<LPR, HEAD, SELF_ROWS, int>(a, st);
-}
-
-template <bool HEAD, bool SELF_ROWS>
-int dispatch_lpr(const SArgs& a, bool i64, hipStream_t st) {
-    const int q = a.H / 4;
-    if (q <= 4)  return launch_lpr<4, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 8)  return launch_lpr<8, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 16) return launch_lpr<16, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 32) return launch_lpr<32, HEAD, SELF_ROWS>(a, i64, st);
-    return launch_lpr<64, HEAD, SELF_ROWS>(a, i64, st);
 }
 
 }  // namespace
@@ -259,60 +226,21 @@ extern "C" int wgnn_predict_rows_dropout(const void* rowptr, const int32_t* col,
                                          const float* w_head, const float* b_head, int32_t n_classes, float unsure_threshold,
                                          int32_t* votes, int64_t ld_votes, int32_t* unsure, int32_t* empty, double* conf_sum,
                                          int32_t* draw_label, float* draw_prob, uint32_t flags, void* stream) {
-    using wgnn::aligned16;
-    auto fail = [](int code, const char* what) { return wgnn::align_fail(code, "wgnn_predict_rows_dropout", what); };
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
-    wgnn::align_error_clear();
-    if (!rowptr || !col || !raw || !table || !alpha || !bias)
-        return fail(WGNN_ERR_BAD_ARG, "rowptr, col, raw, table, alpha and bias are required");
-    if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
-    if (n_draws < 1) return fail(WGNN_ERR_BAD_ARG, "n_draws must be >= 1");
-    if (n_rows * (int64_t)n_draws > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows * n_draws must be < 2^31 (split the batch or the draws)");
-    if (row0 < 0 || draw0 < 0) return fail(WGNN_ERR_BAD_ARG, "row0 and draw0 must not be negative");
-    if (!(keep >= 0.0 && keep <= 1.0)) return fail(WGNN_ERR_BAD_ARG, "keep must be in [0, 1]");
-    if (n_genes <= 0) return fail(WGNN_ERR_BAD_ARG, "n_genes must be positive");
-    if (flags & ~(uint32_t)(WGNN_FLAG_ROWPTR_I64 | WGNN_STABILITY_ACCUMULATE))
-        return fail(WGNN_ERR_BAD_ARG, "only WGNN_FLAG_ROWPTR_I64 and WGNN_STABILITY_ACCUMULATE are valid flags");
-    if (H <= 0) return fail(WGNN_ERR_BAD_ARG, "H must be positive");
-    if (H % 4) return fail(WGNN_ERR_ALIGNMENT, "H must be a multiple of 4 (zero-pad the table, bias and head)");
-    if (H > 256) return fail(WGNN_ERR_UNSUPPORTED, "H > 256 is not built");
-    if (ld_table < H || ld_table % 4) return fail(WGNN_ERR_ALIGNMENT, "ld_table must be >= H and a multiple of 4");
-    if (!aligned16(table) || !aligned16(bias)) return fail(WGNN_ERR_ALIGNMENT, "table and bias must be 16-byte aligned");
-    if (self_rows && (ld_self < H || ld_self % 4 || !aligned16(self_rows)))
-        return fail(WGNN_ERR_ALIGNMENT, "self_rows: ld_self >= H, a multiple of 4, 16-byte aligned");
-    const bool head = w_head != nullptr;
-    if (head) {
-        if (!b_head || !votes || !unsure || !empty || !conf_sum)
-            return fail(WGNN_ERR_BAD_ARG, "a head needs b_head, votes, unsure, empty and conf_sum");
-        if (n_classes <= 0) return fail(WGNN_ERR_BAD_ARG, "n_classes must be positive");
-        if ((int64_t)n_classes * H * 4 > kSHeadLdsBytes)
-            return fail(WGNN_ERR_UNSUPPORTED, "the head needs C*H*4 <= 64 KiB");
-        if (!aligned16(w_head)) return fail(WGNN_ERR_ALIGNMENT, "w_head must be 16-byte aligned");
-        if (ld_votes < n_classes) return fail(WGNN_ERR_BAD_ARG, "ld_votes must be >= n_classes");
-        if (!wgnn::aligned8(conf_sum)) return fail(WGNN_ERR_ALIGNMENT, "conf_sum must be 8-byte aligned");
-        if (!aligned4(votes) || !aligned4(unsure) || !aligned4(empty) || !aligned4(draw_label) || !aligned4(draw_prob))
-            return fail(WGNN_ERR_ALIGNMENT, "votes, unsure, empty, draw_label and draw_prob must be 4-byte aligned");
-    } else {
-        if (flags & WGNN_STABILITY_ACCUMULATE) return fail(WGNN_ERR_BAD_ARG, "WGNN_STABILITY_ACCUMULATE needs a head");
-        if (!out) return fail(WGNN_ERR_BAD_ARG, "without a head `out` is required");
-        if (ld_out < H || ld_out % 4 || !aligned16(out))
-            return fail(WGNN_ERR_ALIGNMENT, "out: ld_out >= H, a multiple of 4, 16-byte aligned");
-    }
+    static const wgnn::DrawEntry entry{"wgnn_predict_rows_dropout", WGNN_STABILITY_ACCUMULATE,
+                                       "only WGNN_FLAG_ROWPTR_I64 and WGNN_STABILITY_ACCUMULATE are valid flags",
+                                       "WGNN_STABILITY_ACCUMULATE needs a head"};
+    const wgnn::DrawCall c{rowptr, col, raw, n_rows, table, ld_table, n_genes, H, alpha, bias, self_rows, ld_self,
+                           n_draws, row0, draw0, seed, keep, out, ld_out, w_head, b_head, n_classes, unsure_threshold,
+                           votes, ld_votes, unsure, empty, conf_sum, draw_label, draw_prob, flags};
+    wgnn::error_clear();
+    if (const int bad = wgnn::check_draw_call(entry, c, nullptr)) return bad;
     if (n_rows == 0) return WGNN_OK;
     SArgs a{};
-    a.rowptr = rowptr; a.col = col; a.raw = raw; a.n_rows = n_rows;
-    a.table = table; a.ld_table = ld_table; a.n_genes = n_genes; a.H = H;
-    a.alpha = alpha; a.bias = bias; a.self_rows = self_rows; a.ld_self = ld_self;
-    a.n_draws = n_draws; a.row0 = row0; a.draw0 = draw0; a.seed = seed;
-    a.T = (unsigned long long)floor(keep * 4294967296.0);          // keep == 1: 2^32, above every 32-bit hash
-    a.out = out; a.ld_out = ld_out;
-    a.w_head = w_head; a.b_head = b_head; a.C = n_classes; a.thr = unsure_threshold;
-    a.votes = votes; a.ld_votes = ld_votes; a.unsure = unsure; a.empty = empty; a.conf_sum = conf_sum;
-    a.draw_label = draw_label; a.draw_prob = draw_prob; a.accumulate = (flags & WGNN_STABILITY_ACCUMULATE) ? 1 : 0;
+    wgnn::fill_draw_args(a, c, entry.accumulate);
     const bool i64 = flags & WGNN_FLAG_ROWPTR_I64;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    if (head) rc = self_rows ? dispatch_lpr<true, true>(a, i64, st) : dispatch_lpr<true, false>(a, i64, st);
-    else rc = self_rows ? dispatch_lpr<false, true>(a, i64, st) : dispatch_lpr<false, false>(a, i64, st);
-    return rc == WGNN_OK ? rc : fail(rc, "HIP launch failed");
+    const int rc = wgnn::dispatch_rows(H, w_head != nullptr, self_rows != nullptr, [&](auto lpr, auto hd, auto sf) {
+        return launch_lpr<decltype(lpr)::value, decltype(hd)::value, decltype(sf)::value>(a, i64, st);
+    });
+    return rc == WGNN_OK ? rc : wgnn::fail(rc, entry.fn, "HIP launch failed");
 }

@@ -43,8 +43,7 @@
 // / tally code below restates wgnn_stability.hip's on purpose: that file's kernel stays as it is.
 
 #include <math.h>
-#include <string.h>
-#include "wgnn_common.h"
+#include "wgnn_resident_rows.h"
 #include "wgnn_align_rows.h"
 
 namespace {
@@ -54,7 +53,6 @@ constexpr int kTWaves = 8;                    // waves per workgroup = draws of 
 constexpr int kTBlock = 64 * kTWaves;
 constexpr int kTMaxBlocks = 1024;             // grid-stride beyond that
 constexpr int kTSlots = 256;                  // draws tallied per LDS round
-constexpr int kTHeadLdsBytes = 64 * 1024;
 constexpr int kTSlotBytes = kTSlots * 12;     // max_prob f32, label int32, empty int32
 constexpr int kTStash = 1024;                 // (gene, value) pairs a wave keeps of one draw
 constexpr int kTStashBytes = kTStash * 8;
@@ -74,18 +72,9 @@ struct TArgs {
     int* draw_label; float* draw_prob; int* draw_reads; int* draw_entries; int accumulate;
 };
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {        // splitmix64 finaliser
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ unsigned mix32(unsigned long long x) { return (unsigned)(mix64(x) >> 32); }
-
 __device__ __forceinline__ int below(unsigned long long mask) {                    // set bits of `mask` below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
-__device__ __forceinline__ int push_to_lane(int dst, int v) { return __builtin_amdgcn_ds_permute(dst << 2, v); }
 
 // orders this wave's LDS writes before its later reads (and reads before later writes): the stash is private to the wave
 __device__ __forceinline__ void wave_sync() {
@@ -127,16 +116,6 @@ __device__ __forceinline__ unsigned thin_entry(unsigned long long key, int g, un
         if (lane == src) kept = n;
     }
     return kept;
-}
-
-template <int LPR>
-__device__ __forceinline__ void group_argmax_fold(float& m, int& am) {             // as predict_rows_kernel
-#pragma unroll
-    for (int off = LPR; off < 64; off <<= 1) {
-        const float mo = __shfl_xor(m, off, 64);
-        const int ao = __shfl_xor(am, off, 64);
-        if (mo > m || (mo == m && ao < am)) { m = mo; am = ao; }
-    }
 }
 
 // One draw's participating entries, handed to f(gene, value, on, p0) 64 lanes at a time in row order: `on` lanes hold an
@@ -375,7 +354,7 @@ int launch_one(const TArgs& a, hipStream_t st) {
     const unsigned nb = (unsigned)(a.n_rows < kTMaxBlocks ? a.n_rows : kTMaxBlocks);
     const size_t lds = (HEAD ? (size_t)a.C * a.H * sizeof(float) + kTSlotBytes : 0) + (size_t)kTWaves * kTStashBytes;
     auto fn = predict_rows_thin_kernel<LPR, HEAD, SELF_ROWS, TPtr>;
-    if (lds > (size_t)kTHeadLdsBytes &&                  // beyond the default window: ask for the larger one
+    if (lds > (size_t)kHeadLdsBytes &&                   // beyond the default window: ask for the larger one
         hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return WGNN_ERR_LAUNCH;
     hipLaunchKernelGGL(fn, dim3(nb), dim3(kTBlock), lds, st, a);
@@ -385,16 +364,6 @@ int launch_one(const TArgs& a, hipStream_t st) {
 template <int LPR, bool HEAD, bool SELF_ROWS>
 int launch_lpr(const TArgs& a, bool i64, hipStream_t st) {
     return i64 ? launch_one<LPR, HEAD, SELF_ROWS, long long>(a, st) : launch_one<LPR, HEAD, SELF_ROWS, int>(a, st);
-}
-
-template <bool HEAD, bool SELF_ROWS>
-int dispatch_lpr(const TArgs& a, bool i64, hipStream_t st) {
-    const int q = a.H / 4;
-    if (q <= 4)  return launch_lpr<4, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 8)  return launch_lpr<8, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 16) return launch_lpr<16, HEAD, SELF_ROWS>(a, i64, st);
-    if (q <= 32) return launch_lpr<32, HEAD, SELF_ROWS>(a, i64, st);
-    return launch_lpr<64, HEAD, SELF_ROWS>(a, i64, st);
 }
 
 }  // namespace
@@ -409,68 +378,24 @@ extern "C" int wgnn_predict_rows_thin(const void* rowptr, const int32_t* col, co
                                       int32_t* votes, int64_t ld_votes, int32_t* unsure, int32_t* empty, double* conf_sum,
                                       int32_t* draw_label, float* draw_prob, int32_t* draw_reads, int32_t* draw_entries,
                                       uint32_t flags, void* stream) {
-    using wgnn::aligned16;
-    auto fail = [](int code, const char* what) { return wgnn::align_fail(code, "wgnn_predict_rows_thin", what); };
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
-    wgnn::align_error_clear();
-    if (!rowptr || !col || !raw || !table || !alpha || !bias)
-        return fail(WGNN_ERR_BAD_ARG, "rowptr, col, raw, table, alpha and bias are required");
-    if (!rest) return fail(WGNN_ERR_BAD_ARG, "rest is required (the cell's reads outside the bundle; zeros when there are none)");
-    if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
-    if (n_draws < 1) return fail(WGNN_ERR_BAD_ARG, "n_draws must be >= 1");
-    if (n_rows * (int64_t)n_draws > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows * n_draws must be < 2^31 (split the batch or the draws)");
-    if (row0 < 0 || draw0 < 0) return fail(WGNN_ERR_BAD_ARG, "row0 and draw0 must not be negative");
-    if (!(keep >= 0.0 && keep <= 1.0)) return fail(WGNN_ERR_BAD_ARG, "keep must be in [0, 1]");
-    if (!(scale > 0.0 && scale < HUGE_VAL)) return fail(WGNN_ERR_BAD_ARG, "scale must be positive and finite");
-    if (!(threshold >= 0.f)) return fail(WGNN_ERR_BAD_ARG, "threshold must be >= 0");
-    if (n_genes <= 0) return fail(WGNN_ERR_BAD_ARG, "n_genes must be positive");
-    if (flags & ~(uint32_t)(WGNN_FLAG_ROWPTR_I64 | WGNN_THIN_ACCUMULATE))
-        return fail(WGNN_ERR_BAD_ARG, "only WGNN_FLAG_ROWPTR_I64 and WGNN_THIN_ACCUMULATE are valid flags");
-    if (H <= 0) return fail(WGNN_ERR_BAD_ARG, "H must be positive");
-    if (H % 4) return fail(WGNN_ERR_ALIGNMENT, "H must be a multiple of 4 (zero-pad the table, bias and head)");
-    if (H > 256) return fail(WGNN_ERR_UNSUPPORTED, "H > 256 is not built");
-    if (ld_table < H || ld_table % 4) return fail(WGNN_ERR_ALIGNMENT, "ld_table must be >= H and a multiple of 4");
-    if (!aligned16(table) || !aligned16(bias)) return fail(WGNN_ERR_ALIGNMENT, "table and bias must be 16-byte aligned");
-    if (self_rows && (ld_self < H || ld_self % 4 || !aligned16(self_rows)))
-        return fail(WGNN_ERR_ALIGNMENT, "self_rows: ld_self >= H, a multiple of 4, 16-byte aligned");
-    if (!wgnn::aligned8(rest)) return fail(WGNN_ERR_ALIGNMENT, "rest must be 8-byte aligned");
-    if (!aligned4(draw_reads) || !aligned4(draw_entries))
-        return fail(WGNN_ERR_ALIGNMENT, "draw_reads and draw_entries must be 4-byte aligned");
-    const bool head = w_head != nullptr;
-    if (head) {
-        if (!b_head || !votes || !unsure || !empty || !conf_sum)
-            return fail(WGNN_ERR_BAD_ARG, "a head needs b_head, votes, unsure, empty and conf_sum");
-        if (n_classes <= 0) return fail(WGNN_ERR_BAD_ARG, "n_classes must be positive");
-        if ((int64_t)n_classes * H * 4 > kTHeadLdsBytes)
-            return fail(WGNN_ERR_UNSUPPORTED, "the head needs C*H*4 <= 64 KiB");
-        if (!aligned16(w_head)) return fail(WGNN_ERR_ALIGNMENT, "w_head must be 16-byte aligned");
-        if (ld_votes < n_classes) return fail(WGNN_ERR_BAD_ARG, "ld_votes must be >= n_classes");
-        if (!wgnn::aligned8(conf_sum)) return fail(WGNN_ERR_ALIGNMENT, "conf_sum must be 8-byte aligned");
-        if (!aligned4(votes) || !aligned4(unsure) || !aligned4(empty) || !aligned4(draw_label) || !aligned4(draw_prob))
-            return fail(WGNN_ERR_ALIGNMENT, "votes, unsure, empty, draw_label and draw_prob must be 4-byte aligned");
-    } else {
-        if (flags & WGNN_THIN_ACCUMULATE) return fail(WGNN_ERR_BAD_ARG, "WGNN_THIN_ACCUMULATE needs a head");
-        if (!out) return fail(WGNN_ERR_BAD_ARG, "without a head `out` is required");
-        if (ld_out < H || ld_out % 4 || !aligned16(out))
-            return fail(WGNN_ERR_ALIGNMENT, "out: ld_out >= H, a multiple of 4, 16-byte aligned");
-    }
+    static const wgnn::DrawEntry entry{"wgnn_predict_rows_thin", WGNN_THIN_ACCUMULATE,
+                                       "only WGNN_FLAG_ROWPTR_I64 and WGNN_THIN_ACCUMULATE are valid flags",
+                                       "WGNN_THIN_ACCUMULATE needs a head"};
+    const wgnn::DrawCall c{rowptr, col, raw, n_rows, table, ld_table, n_genes, H, alpha, bias, self_rows, ld_self,
+                           n_draws, row0, draw0, seed, keep, out, ld_out, w_head, b_head, n_classes, unsure_threshold,
+                           votes, ld_votes, unsure, empty, conf_sum, draw_label, draw_prob, flags};
+    const wgnn::ThinCall thin{rest, scale, threshold, draw_reads, draw_entries};
+    wgnn::error_clear();
+    if (const int bad = wgnn::check_draw_call(entry, c, &thin)) return bad;
     if (n_rows == 0) return WGNN_OK;
     TArgs a{};
-    a.rowptr = rowptr; a.col = col; a.raw = raw; a.n_rows = n_rows;
-    a.table = table; a.ld_table = ld_table; a.n_genes = n_genes; a.H = H;
-    a.alpha = alpha; a.bias = bias; a.self_rows = self_rows; a.ld_self = ld_self;
+    wgnn::fill_draw_args(a, c, entry.accumulate);
     a.rest = reinterpret_cast<const long long*>(rest); a.scale = scale; a.vthr = threshold;
-    a.n_draws = n_draws; a.row0 = row0; a.draw0 = draw0; a.seed = seed;
-    a.T = (unsigned long long)floor(keep * 4294967296.0);          // keep == 1: 2^32, above every 32-bit hash
-    a.out = out; a.ld_out = ld_out;
-    a.w_head = w_head; a.b_head = b_head; a.C = n_classes; a.thr = unsure_threshold;
-    a.votes = votes; a.ld_votes = ld_votes; a.unsure = unsure; a.empty = empty; a.conf_sum = conf_sum;
-    a.draw_label = draw_label; a.draw_prob = draw_prob; a.draw_reads = draw_reads; a.draw_entries = draw_entries;
-    a.accumulate = (flags & WGNN_THIN_ACCUMULATE) ? 1 : 0;
+    a.draw_reads = draw_reads; a.draw_entries = draw_entries;
     const bool i64 = flags & WGNN_FLAG_ROWPTR_I64;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc;
-    if (head) rc = self_rows ? dispatch_lpr<true, true>(a, i64, st) : dispatch_lpr<true, false>(a, i64, st);
-    else rc = self_rows ? dispatch_lpr<false, true>(a, i64, st) : dispatch_lpr<false, false>(a, i64, st);
-    return rc == WGNN_OK ? rc : fail(rc, "HIP launch failed");
+    const int rc = wgnn::dispatch_rows(H, w_head != nullptr, self_rows != nullptr, [&](auto lpr, auto hd, auto sf) {
+        return launch_lpr<decltype(lpr)::value, decltype(hd)::value, decltype(sf)::value>(a, i64, st);
+    });
+    return rc == WGNN_OK ? rc : wgnn::fail(rc, entry.fn, "HIP launch failed");
 }

@@ -9,7 +9,7 @@ non-CUDA tensor or a missing ``libwgnn_hip.so`` raises ``WgnnError``.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -797,7 +797,7 @@ def linear_act(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     return torch.relu(out) if relu else out
 
 
-HEAD_LDS_BYTES = 64 * 1024          # wgnn_predict_rows stages a fused head [C, H] in LDS up to this size
+HEAD_LDS_BYTES = 64 * 1024          # the resident row kernels stage a fused head [C, H] in LDS up to this size
 
 
 def _pad_cols(t: torch.Tensor, width: int) -> torch.Tensor:
@@ -805,6 +805,122 @@ def _pad_cols(t: torch.Tensor, width: int) -> torch.Tensor:
     if t.shape[-1] != width:
         t = torch.nn.functional.pad(t, (0, width - t.shape[-1]))
     return t.contiguous()
+
+
+def check_gene_ids(col: torch.Tensor, n_genes: int) -> None:
+    """``0 <= col < n_genes`` over a batch's CSR: one device reduction and a read-back."""
+    if col.numel():
+        lo, hi = torch.aminmax(col)
+        if int(lo) < 0 or int(hi) >= n_genes:
+            raise WgnnError(f"gene id out of range [0, {n_genes}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+
+
+class _RowOperands(NamedTuple):
+    """The batch, the table and ``alpha`` of a resident row op, ready for the C call."""
+    rowptr: torch.Tensor
+    col: torch.Tensor
+    raw: torch.Tensor
+    table: torch.Tensor
+    alpha: torch.Tensor
+    B: int
+    G: int
+    Hp: int
+    flags: int
+
+    @property
+    def c_args(self) -> tuple:
+        """the arguments every ``wgnn_*_rows`` entry starts with"""
+        return (_ptr(self.rowptr), _ptr(self.col), _ptr(self.raw), self.B, _ptr(self.table), self.table.stride(0), self.G, self.Hp,
+                _ptr(self.alpha))
+
+
+def _row_operands(name, rowptr, col, raw, table, alpha, H, check_cols, nnz_below_2_31=True) -> _RowOperands:
+    """The batch / table / alpha handling ``predict_rows``, ``predict_rows_dropout``, ``predict_rows_thin`` and ``attrib_rows``
+    share: shapes and dtypes, the column range (``check_cols``), the table zero-padded to ``Hp = ceil(H / 4) * 4`` columns.
+    ``nnz_below_2_31``: refuse a batch of 2^31 entries or more (``predict_rows``' kernel indexes entries with 64 bits and takes
+    one)."""
+    G = table.shape[0]
+    Hp = -(-H // 4) * 4
+    if table.dim() != 2 or table.shape[1] < H:
+        raise WgnnError(f"table must be [G, >= {H}]")
+    if alpha.numel() != G + 2:
+        raise WgnnError(f"alpha has {alpha.numel()} entries, the table {G} rows (want G + 2)")
+    if col.shape[0] != raw.shape[0]:
+        raise WgnnError(f"col has {col.shape[0]} entries, raw {raw.shape[0]}")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or raw.dtype != torch.float32:
+        raise WgnnError(f"{name} takes rowptr int32 / int64, col int32, raw float32")
+    if nnz_below_2_31 and col.shape[0] >= 2 ** 31:
+        raise WgnnError(f"{name}: nnz >= 2^31 (split the batch)")
+    if check_cols:
+        check_gene_ids(col, G)
+    if Hp != H or table.shape[1] % 4 or table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
+        table = _pad_cols(table[:, :H], Hp)
+    alpha = alpha.reshape(-1)
+    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
+        alpha = alpha.float().contiguous()
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    return _RowOperands(rowptr.contiguous(), col.contiguous(), raw.contiguous(), table, alpha, rowptr.shape[0] - 1, G, Hp, flags)
+
+
+def _self_rows(self_rows, n_rows, batch, H, Hp, exc):
+    """``self_rows`` [n_rows, H] as the kernels read it (float32, ``Hp`` columns, aligned rows); ``batch`` says in ``exc``'s
+    message what ``n_rows`` is."""
+    if self_rows is None:
+        return None
+    if self_rows.shape[0] != n_rows:
+        raise exc(f"self_rows has {self_rows.shape[0]} rows, the batch {batch}")
+    return _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
+
+
+def _fused_head(head, Hp, refuse=None):
+    """``(w_head [C, Hp], b_head [C], C)`` as the kernels stage a head in LDS.  A head beyond ``HEAD_LDS_BYTES``: the exception
+    ``refuse(C)`` is raised, or None is returned where the caller has another route for it (``refuse`` None)."""
+    w_head, b_head = head
+    n_cls = w_head.shape[0]
+    if n_cls * Hp * 4 > HEAD_LDS_BYTES:
+        if refuse is None:
+            return None
+        raise refuse(n_cls)
+    return _pad_cols(w_head, Hp), b_head.float().contiguous(), n_cls
+
+
+def _headless_out(out, n_rows, Hp, dev, exc):
+    """The ``ReLU(z)`` buffer [n_rows, Hp] of a call without a head: ``out`` checked, or a new one."""
+    if out is None:
+        return torch.empty((n_rows, Hp), dtype=torch.float32, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n_rows, Hp)
+            or out.stride(1) != 1 or out.stride(0) % 4 or out.stride(0) < Hp or out.data_ptr() % 16):
+        raise exc(f"out must be float32 [{n_rows}, {Hp}], unit column stride, 16-byte aligned rows")
+    return out
+
+
+def _draw_outputs(out, B, n_cls, n_draws, accumulate, want_draws, dev, exc):
+    """``(votes, unsure, empty, conf_sum, draw_label | None, draw_prob | None)`` of a call with a head: ``out`` (the first four
+    or all six) checked, what it does not hold allocated."""
+    if out is None:
+        if accumulate:
+            raise exc("accumulate needs the tables to add to (out=)")
+        out = (torch.empty((B, n_cls), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float64, device=dev))
+    if len(out) not in (4, 6):
+        raise exc("out must be (votes, unsure, empty, conf_sum[, draw_label, draw_prob])")
+    votes, unsure, empty, conf_sum = out[:4]
+    draw_label, draw_prob = out[4:] if len(out) == 6 else (None, None)
+    if draw_label is None and want_draws:
+        draw_label = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
+        draw_prob = torch.empty((B, n_draws), dtype=torch.float32, device=dev)
+    _require_cuda(votes, unsure, empty, conf_sum, draw_label, draw_prob)
+    if (votes.dtype != torch.int32 or tuple(votes.shape) != (B, n_cls) or (n_cls > 1 and votes.stride(1) != 1)
+            or (B > 1 and votes.stride(0) < n_cls)):
+        raise exc(f"votes must be int32 [{B}, {n_cls}] with unit column stride and a row stride >= {n_cls}")
+    want = ((unsure, torch.int32, (B,)), (empty, torch.int32, (B,)), (conf_sum, torch.float64, (B,)))
+    if any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want):
+        raise exc(f"unsure and empty must be contiguous int32 [{B}], conf_sum float64 [{B}]")
+    if draw_label is not None:
+        per = ((draw_label, torch.int32), (draw_prob, torch.float32))
+        if any(t is None or t.dtype != d or tuple(t.shape) != (B, n_draws) or not t.is_contiguous() for t, d in per):
+            raise exc(f"draw_label / draw_prob must be contiguous int32 / float32 [{B}, {n_draws}]")
+    return votes, unsure, empty, conf_sum, draw_label, draw_prob
 
 
 def predict_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
@@ -823,64 +939,91 @@ def predict_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tab
     ``check_cols``: verify ``0 <= col < G`` (one device reduction and a read-back) - CSRs built by the predictor from a
     parsed file are in range by construction and skip it."""
     dev = _require_cuda(rowptr, col, raw, table, alpha, bias, self_rows, *(head or ()))
-    G = table.shape[0]
     H = bias.shape[0]
-    Hp = -(-H // 4) * 4
-    B = rowptr.shape[0] - 1
-    if table.dim() != 2 or table.shape[1] < H:
-        raise WgnnError(f"table must be [G, >= {H}]")
-    if alpha.numel() != G + 2:
-        raise WgnnError(f"alpha has {alpha.numel()} entries, the table {G} rows (want G + 2)")
-    if col.shape[0] != raw.shape[0]:
-        raise WgnnError(f"col has {col.shape[0]} entries, raw {raw.shape[0]}")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or raw.dtype != torch.float32:
-        raise WgnnError("predict_rows takes rowptr int32 / int64, col int32, raw float32")
-    if check_cols and col.numel():
-        lo, hi = torch.aminmax(col)
-        if int(lo) < 0 or int(hi) >= G:
-            raise WgnnError(f"gene id out of range [0, {G}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
-    if Hp != H or table.shape[1] % 4 or table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
-        table = _pad_cols(table[:, :H], Hp)
+    o = _row_operands("predict_rows", rowptr, col, raw, table, alpha, H, check_cols, nnz_below_2_31=False)
+    B, Hp = o.B, o.Hp
     bias = _pad_cols(bias, Hp)
-    alpha = alpha.reshape(-1)
-    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
-        alpha = alpha.float().contiguous()
-    if self_rows is not None:
-        if self_rows.shape[0] != B:
-            raise WgnnError(f"self_rows has {self_rows.shape[0]} rows, the batch {B}")
-        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
-    rowptr = rowptr.contiguous(); col = col.contiguous(); raw = raw.contiguous()
-    w_head = b_head = None
-    fused_head = False
-    if head is not None:
-        w_head, b_head = head
-        n_cls = w_head.shape[0]
-        fused_head = n_cls * Hp * 4 <= HEAD_LDS_BYTES
-    out = None if fused_head else torch.empty((B, Hp), dtype=torch.float32, device=dev)
+    self_rows = _self_rows(self_rows, B, B, H, Hp, WgnnError)
+    fused = _fused_head(head, Hp) if head is not None else None
+    w_head, b_head, n_cls = fused or (None, None, 0)
+    out = None if fused else torch.empty((B, Hp), dtype=torch.float32, device=dev)
     logits = label = max_prob = None
-    if fused_head:
-        w_head = _pad_cols(w_head, Hp)
-        b_head = b_head.float().contiguous()
+    if fused:
         logits = torch.empty((B, n_cls), dtype=torch.float32, device=dev) if want_logits else None
         label = torch.empty(B, dtype=torch.int32, device=dev)
         max_prob = torch.empty(B, dtype=torch.float32, device=dev)
-    rc = _lib.call(dev, "wgnn_predict_rows", _ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp,
-                   _ptr(alpha), _ptr(bias), _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
-                   _ptr(out), Hp if out is not None else 0,
-                   _ptr(w_head if fused_head else None), _ptr(b_head if fused_head else None), n_cls if fused_head else 0,
-                   float(unsure_threshold), _ptr(logits), logits.shape[1] if logits is not None else 0, _ptr(label),
-                   _ptr(max_prob), flags, _stream(dev))
+    rc = _lib.call(dev, "wgnn_predict_rows", *o.c_args, _ptr(bias), _ptr(self_rows),
+                   self_rows.stride(0) if self_rows is not None else 0, _ptr(out), Hp if out is not None else 0,
+                   _ptr(w_head), _ptr(b_head), n_cls, float(unsure_threshold), _ptr(logits),
+                   logits.shape[1] if logits is not None else 0, _ptr(label), _ptr(max_prob), o.flags, _stream(dev))
     _lib.check(rc, "wgnn_predict_rows")
     if head is None:
         return out if Hp == H else out[:, :H]
-    if fused_head:
+    if fused:
         return logits, label, max_prob
     # a head too wide for LDS: the GEMM, then the softmax rule of predict.py:78-88 on the [B, C] logits
+    w_head, b_head = head
     logits = linear_fwd(out, _pad_cols(w_head, Hp), b_head)
     mx, arg = torch.softmax(logits, dim=1).max(dim=1)
     label = torch.where(mx < unsure_threshold, torch.full_like(arg, -1), arg).to(torch.int32)
     return (logits if want_logits else None), label, mx
+
+
+def _predict_rows_draws(name, exc, accumulate_flag, thin, rowptr, col, raw, table, alpha, bias, self_rows, head, unsure_threshold,
+                        check_cols, n_draws, keep, seed, row0, draw0, out, accumulate, want_draws):
+    """``predict_rows_dropout`` and ``predict_rows_thin`` behind their signatures: the entry point ``name``, the class ``exc`` of
+    its argument errors, its accumulate bit, and ``thin`` = None or ``(rest, scale, threshold, want_reads)`` - the operands
+    ``wgnn_predict_rows_thin`` takes after ``ld_self`` and the two per-pair tables it writes after ``draw_prob``."""
+    rest, scale, threshold, want_reads = thin or (None, None, None, False)
+    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, rest, self_rows, *(head or ()))
+    n_draws = int(n_draws)
+    keep = float(keep)
+    if n_draws < 1:
+        raise exc(f"{name}: n_draws = {n_draws} must be >= 1")
+    if not 0.0 <= keep <= 1.0:
+        raise exc(f"{name}: keep = {keep} must be in [0, 1]")
+    if int(row0) < 0 or int(draw0) < 0:
+        raise exc(f"{name}: row0 and draw0 must not be negative")
+    if thin and not 0 < float(scale) < float("inf"):
+        raise exc(f"{name}: scale = {scale} must be positive and finite")
+    if thin and not float(threshold) >= 0:
+        raise exc(f"{name}: threshold = {threshold} must be >= 0")
+    H = bias.shape[0]
+    o = _row_operands(name, rowptr, col, raw, table, alpha, H, check_cols)
+    B, Hp = o.B, o.Hp
+    if thin:
+        if rest.dtype != torch.int64 or tuple(rest.shape) != (B,):
+            raise exc(f"{name}: rest must be int64 [{B}]")
+        rest = rest.contiguous()
+    if B * n_draws >= 2 ** 31:
+        raise exc(f"{name}: B * n_draws >= 2^31 (split the batch or the draws)")
+    bias = _pad_cols(bias, Hp)
+    self_rows = _self_rows(self_rows, B * n_draws, f"{B} cells x {n_draws} draws", H, Hp, exc)
+    lead = (*o.c_args, _ptr(bias), _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
+            *((_ptr(rest), float(scale), float(threshold)) if thin else ()),
+            n_draws, int(row0), int(draw0), int(seed) & (2 ** 64 - 1), keep)
+    reads = ()
+    if want_reads:
+        reads = (torch.empty((B, n_draws), dtype=torch.int32, device=dev), torch.empty((B, n_draws), dtype=torch.int32, device=dev))
+    read_ptrs = tuple(_ptr(t) for t in reads or (None, None)) if thin else ()
+    if head is None:
+        if accumulate or want_draws:
+            raise exc(f"{name}: accumulate and want_draws need a head")
+        out = _headless_out(out, B * n_draws, Hp, dev, exc)
+        rc = _lib.call(dev, "wgnn_" + name, *lead, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
+                       None, None, 0, 0.0, None, 0, None, None, None, None, None, *read_ptrs, o.flags, _stream(dev))
+        _lib.check(rc, "wgnn_" + name)
+        h = out if Hp == H else out[:, :H]
+        return (h, *reads) if want_reads else h
+    w_head, b_head, n_cls = _fused_head(
+        head, Hp, lambda c: exc(f"{name}: a [{c}, {Hp}] head is beyond the {HEAD_LDS_BYTES} bytes the kernel stages"))
+    votes, unsure, empty, conf_sum, draw_label, draw_prob = _draw_outputs(out, B, n_cls, n_draws, accumulate, want_draws, dev, exc)
+    rc = _lib.call(dev, "wgnn_" + name, *lead, None, 0, _ptr(w_head), _ptr(b_head), n_cls,
+                   float(unsure_threshold), _ptr(votes), votes.stride(0) if B > 1 else max(int(votes.stride(0)), n_cls),
+                   _ptr(unsure), _ptr(empty), _ptr(conf_sum), _ptr(draw_label), _ptr(draw_prob), *read_ptrs,
+                   o.flags | (accumulate_flag if accumulate else 0), _stream(dev))
+    _lib.check(rc, "wgnn_" + name)
+    return (votes, unsure, empty, conf_sum, draw_label, draw_prob, *reads)
 
 
 def predict_rows_dropout(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
@@ -902,75 +1045,9 @@ def predict_rows_dropout(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Ten
     fp64 in draw order; the last two with ``want_draws``.  ``out``: the first four (``votes`` may be a view with a row stride
     ``>= C``), or all six, to write into - every element is written, or added to with ``accumulate`` (further draws of the
     same cells: pass ``draw0``).  There is no GEMM route for a head beyond what the kernel stages in LDS."""
-    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, self_rows, *(head or ()))
-    n_draws = int(n_draws)
-    keep = float(keep)
-    if n_draws < 1:
-        raise WgnnError(f"predict_rows_dropout: n_draws = {n_draws} must be >= 1")
-    if not 0.0 <= keep <= 1.0:
-        raise WgnnError(f"predict_rows_dropout: keep = {keep} must be in [0, 1]")
-    if int(row0) < 0 or int(draw0) < 0:
-        raise WgnnError("predict_rows_dropout: row0 and draw0 must not be negative")
-    H = bias.shape[0]
-    table, alpha, G, Hp, B, flags, rowptr, col, raw = _attrib_common("predict_rows_dropout", rowptr, col, raw, table, alpha, H,
-                                                                     check_cols)
-    if B * n_draws >= 2 ** 31:
-        raise WgnnError("predict_rows_dropout: B * n_draws >= 2^31 (split the batch or the draws)")
-    bias = _pad_cols(bias, Hp)
-    if self_rows is not None:
-        if self_rows.shape[0] != B * n_draws:
-            raise WgnnError(f"self_rows has {self_rows.shape[0]} rows, the batch {B} cells x {n_draws} draws")
-        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
-    common = (_ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp, _ptr(alpha), _ptr(bias),
-              _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
-              n_draws, int(row0), int(draw0), int(seed) & (2 ** 64 - 1), keep)
-    if head is None:
-        if accumulate or want_draws:
-            raise WgnnError("predict_rows_dropout: accumulate and want_draws need a head")
-        if out is None:
-            out = torch.empty((B * n_draws, Hp), dtype=torch.float32, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B * n_draws, Hp)
-              or out.stride(1) != 1 or out.stride(0) % 4 or out.stride(0) < Hp or out.data_ptr() % 16):
-            raise WgnnError(f"out must be float32 [{B * n_draws}, {Hp}], unit column stride, 16-byte aligned rows")
-        rc = _lib.call(dev, "wgnn_predict_rows_dropout", *common, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
-                       None, None, 0, 0.0, None, 0, None, None, None, None, None, flags, _stream(dev))
-        _lib.check(rc, "wgnn_predict_rows_dropout")
-        return out if Hp == H else out[:, :H]
-    w_head, b_head = head
-    n_cls = w_head.shape[0]
-    if n_cls * Hp * 4 > HEAD_LDS_BYTES:
-        raise WgnnError(f"predict_rows_dropout: a [{n_cls}, {Hp}] head is beyond the {HEAD_LDS_BYTES} bytes the kernel stages")
-    w_head = _pad_cols(w_head, Hp)
-    b_head = b_head.float().contiguous()
-    if out is None:
-        if accumulate:
-            raise WgnnError("accumulate needs the tables to add to (out=)")
-        out = (torch.empty((B, n_cls), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float64, device=dev))
-    if len(out) not in (4, 6):
-        raise WgnnError("out must be (votes, unsure, empty, conf_sum[, draw_label, draw_prob])")
-    votes, unsure, empty, conf_sum = out[:4]
-    draw_label, draw_prob = out[4:] if len(out) == 6 else (None, None)
-    if draw_label is None and want_draws:
-        draw_label = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
-        draw_prob = torch.empty((B, n_draws), dtype=torch.float32, device=dev)
-    _require_cuda(votes, unsure, empty, conf_sum, draw_label, draw_prob)
-    if (votes.dtype != torch.int32 or tuple(votes.shape) != (B, n_cls) or (n_cls > 1 and votes.stride(1) != 1)
-            or (B > 1 and votes.stride(0) < n_cls)):
-        raise WgnnError(f"votes must be int32 [{B}, {n_cls}] with unit column stride and a row stride >= {n_cls}")
-    want = ((unsure, torch.int32, (B,)), (empty, torch.int32, (B,)), (conf_sum, torch.float64, (B,)))
-    if any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want):
-        raise WgnnError(f"unsure and empty must be contiguous int32 [{B}], conf_sum float64 [{B}]")
-    if draw_label is not None:
-        per = ((draw_label, torch.int32), (draw_prob, torch.float32))
-        if any(t is None or t.dtype != d or tuple(t.shape) != (B, n_draws) or not t.is_contiguous() for t, d in per):
-            raise WgnnError(f"draw_label / draw_prob must be contiguous int32 / float32 [{B}, {n_draws}]")
-    rc = _lib.call(dev, "wgnn_predict_rows_dropout", *common, None, 0, _ptr(w_head), _ptr(b_head), n_cls,
-                   float(unsure_threshold), _ptr(votes), votes.stride(0) if B > 1 else max(int(votes.stride(0)), n_cls),
-                   _ptr(unsure), _ptr(empty), _ptr(conf_sum), _ptr(draw_label), _ptr(draw_prob),
-                   flags | (_lib.STABILITY_ACCUMULATE if accumulate else 0), _stream(dev))
-    _lib.check(rc, "wgnn_predict_rows_dropout")
-    return votes, unsure, empty, conf_sum, draw_label, draw_prob
+    return _predict_rows_draws("predict_rows_dropout", WgnnError, _lib.STABILITY_ACCUMULATE, None, rowptr, col, raw, table, alpha,
+                               bias, self_rows, head, unsure_threshold, check_cols, n_draws, keep, seed, row0, draw0, out,
+                               accumulate, want_draws)
 
 
 def predict_rows_thin(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
@@ -989,89 +1066,9 @@ def predict_rows_thin(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor
     tables ``draw_reads`` / ``draw_entries`` int32 [B, n_draws] - a draw's library size and its participating entries -
     appended to the return value (without a head: ``(out, draw_reads, draw_entries)``).  CPU tensors are refused; argument
     errors are ``ValueError``."""
-    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, rest, self_rows, *(head or ()))
-    n_draws = int(n_draws)
-    keep = float(keep)
-    if n_draws < 1:
-        raise ValueError(f"predict_rows_thin: n_draws = {n_draws} must be >= 1")
-    if not 0.0 <= keep <= 1.0:
-        raise ValueError(f"predict_rows_thin: keep = {keep} must be in [0, 1]")
-    if int(row0) < 0 or int(draw0) < 0:
-        raise ValueError("predict_rows_thin: row0 and draw0 must not be negative")
-    if not 0 < float(scale) < float("inf"):
-        raise ValueError(f"predict_rows_thin: scale = {scale} must be positive and finite")
-    if not float(threshold) >= 0:
-        raise ValueError(f"predict_rows_thin: threshold = {threshold} must be >= 0")
-    H = bias.shape[0]
-    table, alpha, G, Hp, B, flags, rowptr, col, raw = _attrib_common("predict_rows_thin", rowptr, col, raw, table, alpha, H,
-                                                                     check_cols)
-    if rest.dtype != torch.int64 or tuple(rest.shape) != (B,):
-        raise ValueError(f"predict_rows_thin: rest must be int64 [{B}]")
-    rest = rest.contiguous()
-    if B * n_draws >= 2 ** 31:
-        raise ValueError("predict_rows_thin: B * n_draws >= 2^31 (split the batch or the draws)")
-    bias = _pad_cols(bias, Hp)
-    if self_rows is not None:
-        if self_rows.shape[0] != B * n_draws:
-            raise ValueError(f"self_rows has {self_rows.shape[0]} rows, the batch {B} cells x {n_draws} draws")
-        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
-    common = (_ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp, _ptr(alpha), _ptr(bias),
-              _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0, _ptr(rest), float(scale), float(threshold),
-              n_draws, int(row0), int(draw0), int(seed) & (2 ** 64 - 1), keep)
-    draw_reads = draw_entries = None
-    if want_reads:
-        draw_reads = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
-        draw_entries = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
-    reads = (draw_reads, draw_entries) if want_reads else ()
-    if head is None:
-        if accumulate or want_draws:
-            raise ValueError("predict_rows_thin: accumulate and want_draws need a head")
-        if out is None:
-            out = torch.empty((B * n_draws, Hp), dtype=torch.float32, device=dev)
-        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (B * n_draws, Hp)
-              or out.stride(1) != 1 or out.stride(0) % 4 or out.stride(0) < Hp or out.data_ptr() % 16):
-            raise ValueError(f"out must be float32 [{B * n_draws}, {Hp}], unit column stride, 16-byte aligned rows")
-        rc = _lib.call(dev, "wgnn_predict_rows_thin", *common, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
-                       None, None, 0, 0.0, None, 0, None, None, None, None, None, _ptr(draw_reads), _ptr(draw_entries), flags,
-                       _stream(dev))
-        _lib.check(rc, "wgnn_predict_rows_thin")
-        h = out if Hp == H else out[:, :H]
-        return (h, *reads) if want_reads else h
-    w_head, b_head = head
-    n_cls = w_head.shape[0]
-    if n_cls * Hp * 4 > HEAD_LDS_BYTES:
-        raise ValueError(f"predict_rows_thin: a [{n_cls}, {Hp}] head is beyond the {HEAD_LDS_BYTES} bytes the kernel stages")
-    w_head = _pad_cols(w_head, Hp)
-    b_head = b_head.float().contiguous()
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate needs the tables to add to (out=)")
-        out = (torch.empty((B, n_cls), dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
-               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float64, device=dev))
-    if len(out) not in (4, 6):
-        raise ValueError("out must be (votes, unsure, empty, conf_sum[, draw_label, draw_prob])")
-    votes, unsure, empty, conf_sum = out[:4]
-    draw_label, draw_prob = out[4:] if len(out) == 6 else (None, None)
-    if draw_label is None and want_draws:
-        draw_label = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
-        draw_prob = torch.empty((B, n_draws), dtype=torch.float32, device=dev)
-    _require_cuda(votes, unsure, empty, conf_sum, draw_label, draw_prob)
-    if (votes.dtype != torch.int32 or tuple(votes.shape) != (B, n_cls) or (n_cls > 1 and votes.stride(1) != 1)
-            or (B > 1 and votes.stride(0) < n_cls)):
-        raise ValueError(f"votes must be int32 [{B}, {n_cls}] with unit column stride and a row stride >= {n_cls}")
-    want = ((unsure, torch.int32, (B,)), (empty, torch.int32, (B,)), (conf_sum, torch.float64, (B,)))
-    if any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want):
-        raise ValueError(f"unsure and empty must be contiguous int32 [{B}], conf_sum float64 [{B}]")
-    if draw_label is not None:
-        per = ((draw_label, torch.int32), (draw_prob, torch.float32))
-        if any(t is None or t.dtype != d or tuple(t.shape) != (B, n_draws) or not t.is_contiguous() for t, d in per):
-            raise ValueError(f"draw_label / draw_prob must be contiguous int32 / float32 [{B}, {n_draws}]")
-    rc = _lib.call(dev, "wgnn_predict_rows_thin", *common, None, 0, _ptr(w_head), _ptr(b_head), n_cls,
-                   float(unsure_threshold), _ptr(votes), votes.stride(0) if B > 1 else max(int(votes.stride(0)), n_cls),
-                   _ptr(unsure), _ptr(empty), _ptr(conf_sum), _ptr(draw_label), _ptr(draw_prob), _ptr(draw_reads),
-                   _ptr(draw_entries), flags | (_lib.THIN_ACCUMULATE if accumulate else 0), _stream(dev))
-    _lib.check(rc, "wgnn_predict_rows_thin")
-    return (votes, unsure, empty, conf_sum, draw_label, draw_prob, *reads)
+    return _predict_rows_draws("predict_rows_thin", ValueError, _lib.THIN_ACCUMULATE, (rest, scale, threshold, want_reads), rowptr,
+                               col, raw, table, alpha, bias, self_rows, head, unsure_threshold, check_cols, n_draws, keep, seed,
+                               row0, draw0, out, accumulate, want_draws)
 
 
 def thin_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, rest: torch.Tensor, total: torch.Tensor) -> None:
@@ -1092,35 +1089,6 @@ def thin_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, rest: torch.Tens
         raise WgnnError(f"thin=\"reads\" takes integer counts: cell {first} holds a count that is no integer in [1, 2^24], reads "
                         f"outside the bundle that are no non-negative integer (a library size below the cell's matched reads?), "
                         f"or 2^31 reads or more")
-
-
-def _attrib_common(name, rowptr, col, raw, table, alpha, H, check_cols):
-    """The batch / table handling ``predict_rows`` does, shared by ``attrib_rows``: returns (table, alpha, G, Hp, B, flags,
-    rowptr, col, raw) ready for the C call."""
-    G = table.shape[0]
-    Hp = -(-H // 4) * 4
-    B = rowptr.shape[0] - 1
-    if table.dim() != 2 or table.shape[1] < H:
-        raise WgnnError(f"table must be [G, >= {H}]")
-    if alpha.numel() != G + 2:
-        raise WgnnError(f"alpha has {alpha.numel()} entries, the table {G} rows (want G + 2)")
-    if col.shape[0] != raw.shape[0]:
-        raise WgnnError(f"col has {col.shape[0]} entries, raw {raw.shape[0]}")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or raw.dtype != torch.float32:
-        raise WgnnError(f"{name} takes rowptr int32 / int64, col int32, raw float32")
-    if col.shape[0] >= 2 ** 31:
-        raise WgnnError(f"{name}: nnz >= 2^31 (split the batch)")
-    if check_cols and col.numel():
-        lo, hi = torch.aminmax(col)
-        if int(lo) < 0 or int(hi) >= G:
-            raise WgnnError(f"gene id out of range [0, {G}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
-    if Hp != H or table.shape[1] % 4 or table.stride(1) != 1 or table.stride(0) % 4 or table.data_ptr() % 16:
-        table = _pad_cols(table[:, :H], Hp)
-    alpha = alpha.reshape(-1)
-    if alpha.dtype != torch.float32 or not alpha.is_contiguous():
-        alpha = alpha.float().contiguous()
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
-    return table, alpha, G, Hp, B, flags, rowptr.contiguous(), col.contiguous(), raw.contiguous()
 
 
 def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
@@ -1145,8 +1113,9 @@ def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tabl
         raise WgnnError("attrib_rows takes either head= (last layer) or direction= (layers below it)")
     dev = _require_cuda(rowptr, col, raw, table, alpha, bias, self_rows, target, direction, scores, *(head or ()))
     H = bias.shape[0]
-    table, alpha, G, Hp, B, flags, rowptr, col, raw = _attrib_common("attrib_rows", rowptr, col, raw, table, alpha, H, check_cols)
-    nnz = col.shape[0]
+    o = _row_operands("attrib_rows", rowptr, col, raw, table, alpha, H, check_cols)
+    B, Hp, flags = o.B, o.Hp, o.flags
+    nnz = o.col.shape[0]
     if scores is None:
         if accumulate:
             raise WgnnError("accumulate needs the scores to add to")
@@ -1160,24 +1129,16 @@ def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tabl
         if explicit_self is None:
             explicit_self = self_rows is not None
         flags |= (_lib.ATTRIB_ACCUMULATE if accumulate else 0) | (_lib.ATTRIB_EXPLICIT_SELF if explicit_self else 0)
-        rc = _lib.call(dev, "wgnn_attrib_rows", _ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp,
-                       _ptr(alpha), None, None, 0, None, None, 0, None, 0.0, None, _ptr(direction), direction.stride(0),
-                       _ptr(scores), None, None, None, None, 0, flags, _stream(dev))
+        rc = _lib.call(dev, "wgnn_attrib_rows", *o.c_args, None, None, 0, None, None, 0, None, 0.0, None, _ptr(direction),
+                       direction.stride(0), _ptr(scores), None, None, None, None, 0, flags, _stream(dev))
         _lib.check(rc, "wgnn_attrib_rows")
         return scores
     if accumulate:
         raise WgnnError("head mode overwrites the scores")
-    w_head, b_head = head
-    n_cls = w_head.shape[0]
-    if n_cls * Hp * 4 > HEAD_LDS_BYTES:
-        raise WgnnError(f"attrib_rows: a [{n_cls}, {Hp}] head does not fit the {HEAD_LDS_BYTES >> 10} KiB the kernel stages in LDS")
+    w_head, b_head, n_cls = _fused_head(head, Hp, lambda c: WgnnError(
+        f"attrib_rows: a [{c}, {Hp}] head does not fit the {HEAD_LDS_BYTES >> 10} KiB the kernel stages in LDS"))
     bias = _pad_cols(bias, Hp)
-    w_head = _pad_cols(w_head, Hp)
-    b_head = b_head.float().contiguous()
-    if self_rows is not None:
-        if self_rows.shape[0] != B:
-            raise WgnnError(f"self_rows has {self_rows.shape[0]} rows, the batch {B}")
-        self_rows = _rowmajor(self_rows.float()) if self_rows.shape[1] == Hp else _pad_cols(self_rows[:, :H], Hp)
+    self_rows = _self_rows(self_rows, B, B, H, Hp, WgnnError)
     if target is not None:
         if target.shape != (B,):
             raise WgnnError(f"target must hold one class per cell ([{B}])")
@@ -1191,11 +1152,10 @@ def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tabl
     base = torch.empty(B, dtype=torch.float32, device=dev)
     label = torch.empty(B, dtype=torch.int32, device=dev)
     v = torch.empty((B, Hp), dtype=torch.float32, device=dev) if want_direction else None
-    rc = _lib.call(dev, "wgnn_attrib_rows", _ptr(rowptr), _ptr(col), _ptr(raw), B, _ptr(table), table.stride(0), G, Hp,
-                   _ptr(alpha), _ptr(bias), _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
-                   _ptr(w_head), _ptr(b_head), n_cls, _ptr(target), float(unsure_threshold), _ptr(label), None, 0,
-                   _ptr(scores), _ptr(target_out), _ptr(logit), _ptr(base), _ptr(v), Hp if v is not None else 0,
-                   flags, _stream(dev))
+    rc = _lib.call(dev, "wgnn_attrib_rows", *o.c_args, _ptr(bias), _ptr(self_rows),
+                   self_rows.stride(0) if self_rows is not None else 0, _ptr(w_head), _ptr(b_head), n_cls, _ptr(target),
+                   float(unsure_threshold), _ptr(label), None, 0, _ptr(scores), _ptr(target_out), _ptr(logit), _ptr(base), _ptr(v),
+                   Hp if v is not None else 0, flags, _stream(dev))
     _lib.check(rc, "wgnn_attrib_rows")
     return scores, target_out, logit, base, label, (v if v is None or Hp == H else v[:, :H])
 
@@ -1254,10 +1214,8 @@ def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Ten
         lo, hi = torch.aminmax(group)
         if int(lo) < -1 or int(hi) >= K:
             raise WgnnError(f"group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
-    if check and nnz:
-        lo, hi = torch.aminmax(col)
-        if int(lo) < 0 or int(hi) >= G:
-            raise WgnnError(f"gene id out of range [0, {G}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
+    if check:
+        check_gene_ids(col, G)
     if out is None:
         if accumulate:
             raise WgnnError("accumulate needs the tables to add to (out=)")

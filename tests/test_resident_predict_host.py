@@ -50,6 +50,182 @@ def test_predict_rows_validation_returns_error_codes_without_gpu():
     assert lib.wgnn_last_error_string(-3) == b"unsupported dtype, feature width (D <= 1024 required) or nnz >= 2^31 (shard the cell axis)"
 
 
+@pytest.fixture(scope="module")
+def generic():
+    """The generic text of each code: what wgnn_last_error_string says when no call has failed with it."""
+    lib = _lib.lib()
+    texts = {}
+    for code in (-1, -2, -3):
+        for _ in range(8):                                                # drop the details earlier tests left unasked
+            texts[code] = lib.wgnn_last_error_string(code)
+        assert b" - wgnn_" not in texts[code]
+    return texts
+
+
+# ------------------------------------------------------------------------------------------------
+# the refusals of wgnn_predict_rows_dropout / wgnn_predict_rows_thin / wgnn_attrib_rows: the code and the check that
+# wgnn_last_error_string names, one perturbed argument per row (the cases test_{stability,thin,attrib}_reference.py assert
+# already are not repeated).  Fake pointers: 16 is aligned; 24 is 8- but not 16-byte aligned, 20 is 4- but not 8-byte
+# aligned, 18 is not 4-byte aligned.  None of them is dereferenced: validation returns first.
+# ------------------------------------------------------------------------------------------------
+_ROW = ("rowptr", "col", "raw", "n_rows", "table", "ld_table", "n_genes", "H", "alpha", "bias", "self_rows", "ld_self")
+_DRAW = ("n_draws", "row0", "draw0", "seed", "keep", "out", "ld_out", "w_head", "b_head", "n_classes", "unsure_threshold",
+         "votes", "ld_votes", "unsure", "empty", "conf_sum", "draw_label", "draw_prob")
+_ORDER = {      # the arguments in the order include/wgnn.h declares them
+    "wgnn_predict_rows_dropout": _ROW + _DRAW + ("flags", "stream"),
+    "wgnn_predict_rows_thin": _ROW + ("rest", "scale", "threshold") + _DRAW + ("draw_reads", "draw_entries", "flags", "stream"),
+    "wgnn_attrib_rows": _ROW + ("w_head", "b_head", "n_classes", "target", "unsure_threshold", "label_out", "direction", "ld_dir",
+                                "score", "target_out", "logit_out", "base_out", "dir_out", "ld_dir_out", "flags", "stream"),
+}
+_P = 16
+_ROW_OK = dict(rowptr=_P, col=_P, raw=_P, n_rows=4, table=_P, ld_table=8, n_genes=10, H=8, alpha=_P, bias=_P, self_rows=None,
+               ld_self=0, flags=0, stream=None)
+_DRAW_OK = dict(_ROW_OK, n_draws=2, row0=0, draw0=0, seed=7, keep=0.5, out=_P, ld_out=8, w_head=None, b_head=None, n_classes=0,
+                unsure_threshold=0.5, votes=None, ld_votes=0, unsure=None, empty=None, conf_sum=None, draw_label=None,
+                draw_prob=None)
+_DRAW_HEAD = dict(out=None, ld_out=0, w_head=_P, b_head=_P, n_classes=3, votes=_P, ld_votes=3, unsure=_P, empty=_P, conf_sum=_P)
+_BASE = {       # a call every check lets through: (without a head | in direction mode, the changes that give it a head)
+    "wgnn_predict_rows_dropout": (_DRAW_OK, _DRAW_HEAD),
+    "wgnn_predict_rows_thin": (dict(_DRAW_OK, rest=_P, scale=1e4, threshold=0.0, draw_reads=None, draw_entries=None), _DRAW_HEAD),
+    "wgnn_attrib_rows": (dict(_ROW_OK, bias=None, w_head=None, b_head=None, n_classes=0, target=None, unsure_threshold=0.5,
+                              label_out=None, direction=_P, ld_dir=8, score=_P, target_out=None, logit_out=None, base_out=None,
+                              dir_out=None, ld_dir_out=0),
+                         dict(bias=_P, w_head=_P, b_head=_P, n_classes=3, direction=None, ld_dir=0, target_out=_P, logit_out=_P,
+                              base_out=_P)),
+}
+_DROPOUT, _THIN, _ATTRIB = _ORDER
+_DRAWS = (_DROPOUT, _THIN)
+_ALL = (_DROPOUT, _THIN, _ATTRIB)
+_ACC = 256          # WGNN_STABILITY_ACCUMULATE == WGNN_THIN_ACCUMULATE == WGNN_ATTRIB_ACCUMULATE
+
+
+def _refusals():
+    """(entry, head, perturbed arguments, return code, fragment of the detail)"""
+    rows = []
+
+    def add(entries, head, change, code, word):
+        rows.extend((e, head, change, code, word) for e in entries)
+
+    for head in (False, True):
+        for p in ("rowptr", "col", "raw", "table", "alpha"):
+            add(_ALL, head, {p: None}, -1, b"are required")
+        add(_ALL, head, dict(n_rows=-1), -1, b"n_rows must be in [0, 2^31)")
+        add(_ALL, head, dict(n_genes=0), -1, b"n_genes must be positive")
+        add(_ALL, head, dict(H=0), -1, b"H must be positive")
+        add(_ALL, head, dict(ld_table=4), -2, b"ld_table must be >= H and a multiple of 4")
+        add(_ALL, head, dict(ld_table=10), -2, b"ld_table must be >= H and a multiple of 4")
+        add(_DRAWS, head, dict(table=24), -2, b"table and bias must be 16-byte aligned")
+        add(_DRAWS, head, dict(bias=24), -2, b"table and bias must be 16-byte aligned")
+        add(_DRAWS, head, dict(bias=None), -1, b"are required")
+        add(_DRAWS, head, dict(self_rows=_P, ld_self=4), -2, b"self_rows: ld_self >= H")
+        add(_DRAWS, head, dict(self_rows=_P, ld_self=10), -2, b"self_rows: ld_self >= H")
+        add(_DRAWS, head, dict(self_rows=24, ld_self=8), -2, b"self_rows: ld_self >= H")
+        add(_DRAWS, head, dict(n_rows=2 ** 31 - 1, n_draws=2), -1, b"n_rows * n_draws must be < 2^31")
+        add((_THIN,), head, dict(n_draws=-3), -1, b"n_draws must be >= 1")
+        add((_THIN,), head, dict(draw_reads=20, draw_entries=18), -2, b"draw_reads and draw_entries must be 4-byte aligned")
+        add((_THIN,), head, dict(rest=24), 0, None)                       # 8-byte alignment is all `rest` needs
+    # without a head
+    add(_DRAWS, False, dict(ld_out=4), -2, b"out: ld_out >= H")
+    add(_DRAWS, False, dict(ld_out=10), -2, b"out: ld_out >= H")
+    add(_DRAWS, False, dict(out=24), -2, b"out: ld_out >= H")
+    add(_DRAWS, False, dict(H=256, ld_table=256, ld_out=256, n_classes=65), 0, None)     # n_classes is not read
+    # with a head
+    add(_DRAWS, True, dict(b_head=None), -1, b"a head needs b_head, votes, unsure, empty and conf_sum")
+    add((_THIN,), True, dict(unsure=None), -1, b"a head needs b_head, votes, unsure, empty and conf_sum")
+    add((_THIN,), True, dict(empty=None), -1, b"a head needs b_head, votes, unsure, empty and conf_sum")
+    add(_ALL, True, dict(n_classes=0), -1, b"n_classes must be positive")
+    add(_DRAWS, True, dict(H=256, ld_table=256, n_classes=65, ld_votes=65), -3, b"the head needs C*H*4 <= 64 KiB")
+    add(_DRAWS, True, dict(H=256, ld_table=256, n_classes=64, ld_votes=64), 0, None)
+    add((_ATTRIB,), True, dict(H=256, ld_table=256, n_classes=64), 0, None)
+    add(_ALL, True, dict(w_head=24), -2, b"w_head must be 16-byte aligned")
+    add(_DRAWS, True, dict(conf_sum=24), 0, None)
+    add(_DRAWS, True, dict(conf_sum=20), -2, b"conf_sum must be 8-byte aligned")
+    for p in ("votes", "unsure", "empty", "draw_label", "draw_prob"):
+        add(_DRAWS, True, {p: 18}, -2, b"votes, unsure, empty, draw_label and draw_prob must be 4-byte aligned")
+        add(_DRAWS, True, {p: 20}, 0, None)
+    add(_DRAWS, True, dict(ld_votes=2), -1, b"ld_votes must be >= n_classes")
+    add(_DRAWS, True, dict(flags=_ACC), 0, None)
+    add(_DRAWS, True, dict(flags=_ACC | _lib.FLAG_ROWPTR_I64), 0, None)
+    add((_THIN,), True, dict(flags=512), -1, b"only WGNN_FLAG_ROWPTR_I64 and WGNN_THIN_ACCUMULATE are valid flags")
+    # wgnn_attrib_rows' own rules
+    add((_ATTRIB,), False, dict(score=None), -1, b"rowptr, col, raw, table, alpha and score are required")
+    add((_ATTRIB,), True, dict(score=None), -1, b"rowptr, col, raw, table, alpha and score are required")
+    add((_ATTRIB,), False, dict(flags=_lib.FLAG_RELU), -1, b"valid flags: WGNN_FLAG_ROWPTR_I64, WGNN_ATTRIB_ACCUMULATE")
+    add((_ATTRIB,), False, dict(H=6), -2, b"H must be a multiple of 4 (zero-pad the table, bias, head and direction)")
+    add((_ATTRIB,), False, dict(H=260, ld_table=260, ld_dir=260), -3, b"H > 256 is not built")
+    add((_ATTRIB,), False, dict(table=24), -2, b"table must be 16-byte aligned")
+    add((_ATTRIB,), True, dict(table=24), -2, b"table must be 16-byte aligned")
+    add((_ATTRIB,), False, dict(direction=None), -1, b"give either a head (w_head) or a direction")
+    add((_ATTRIB,), True, dict(direction=_P, ld_dir=8), -1, b"give either a head (w_head) or a direction")
+    for p in ("bias", "b_head", "target_out", "logit_out", "base_out"):
+        add((_ATTRIB,), True, {p: None}, -1, b"a head needs bias, b_head, target_out, logit_out and base_out")
+    for f in (_lib.ATTRIB_ACCUMULATE, _lib.ATTRIB_EXPLICIT_SELF):
+        add((_ATTRIB,), True, dict(flags=f), -1, b"head mode overwrites score and takes its self rule from self_rows")
+        add((_ATTRIB,), False, dict(flags=f), 0, None)
+    add((_ATTRIB,), True, dict(bias=24), -2, b"bias must be 16-byte aligned")
+    add((_ATTRIB,), False, dict(bias=24), 0, None)                        # direction mode does not read the bias
+    add((_ATTRIB,), True, dict(self_rows=_P, ld_self=4), -2, b"self_rows: ld_self >= H")
+    add((_ATTRIB,), True, dict(self_rows=_P, ld_self=10), -2, b"self_rows: ld_self >= H")
+    add((_ATTRIB,), True, dict(self_rows=24, ld_self=8), -2, b"self_rows: ld_self >= H")
+    add((_ATTRIB,), False, dict(self_rows=24, ld_self=4), 0, None)        # nor the self rows
+    add((_ATTRIB,), True, dict(H=256, ld_table=256, n_classes=65), -3, b"the head needs C*H*4 <= 64 KiB")
+    add((_ATTRIB,), True, dict(dir_out=_P, ld_dir_out=4), -2, b"dir_out: ld_dir_out >= H")
+    add((_ATTRIB,), True, dict(dir_out=_P, ld_dir_out=10), -2, b"dir_out: ld_dir_out >= H")
+    add((_ATTRIB,), True, dict(dir_out=24, ld_dir_out=8), -2, b"dir_out: ld_dir_out >= H")
+    add((_ATTRIB,), False, dict(ld_dir=4), -2, b"direction: ld_dir >= H")
+    add((_ATTRIB,), False, dict(ld_dir=10), -2, b"direction: ld_dir >= H")
+    add((_ATTRIB,), False, dict(direction=24), -2, b"direction: ld_dir >= H")
+    return rows
+
+
+def _refusal_id(row):
+    entry, head, change, code, _ = row
+    return f"{entry[5:]}-{'head' if head else 'nohead'}-{','.join(f'{k}={v}' for k, v in change.items())}->{code}"
+
+
+@pytest.mark.parametrize("row", _refusals(), ids=_refusal_id)
+def test_resident_row_entries_refuse_with_code_and_detail_without_gpu(row, generic):
+    entry, head, change, code, word = row
+    lib = _lib.lib()
+    base, with_head = _BASE[entry]
+    kw = {**base, **(with_head if head else {}), **change}
+    # an accepted call must not reach a launch: it runs on an empty batch (n_rows == 0 returns after every check)
+    if code == 0:
+        kw["n_rows"] = 0
+    assert set(kw) == set(_ORDER[entry])
+    assert getattr(lib, entry)(*(kw[k] for k in _ORDER[entry])) == code
+    if code:
+        msg = lib.wgnn_last_error_string(code)
+        assert entry.encode() + b": " in msg and word in msg, msg
+        assert lib.wgnn_last_error_string(code) == generic[code]         # handed out once
+
+
+@pytest.mark.parametrize("entry", _ALL)
+@pytest.mark.parametrize("head", (False, True))
+def test_resident_row_entries_accept_an_empty_batch_without_gpu(entry, head):
+    base, with_head = _BASE[entry]
+    kw = {**base, **(with_head if head else {}), "n_rows": 0}
+    assert getattr(_lib.lib(), entry)(*(kw[k] for k in _ORDER[entry])) == 0
+
+
+def test_last_error_detail_is_that_of_the_last_failing_call_whatever_the_entry(generic):
+    """``wgnn_predict_rows`` refused with -3 and nobody asks; then ``wgnn_attrib_rows`` refused with -3: the string is the second
+    call's, once, then the generic text.  A call that passes forgets an unasked detail too."""
+    lib = _lib.lib()
+    p = C.c_void_p(_P)
+    predict = lambda H: lib.wgnn_predict_rows(p, p, p, 4, p, H, 10, H, p, p, None, 0, p, H, None, None, 0, 0.5, None, 0, None, None, 0, None)
+    base, with_head = _BASE[_ATTRIB]
+    attrib = lambda **kw: lib.wgnn_attrib_rows(*({**base, **with_head, **kw}[k] for k in _ORDER[_ATTRIB]))
+    assert predict(260) == -3
+    assert attrib(H=260, ld_table=260) == -3
+    msg = lib.wgnn_last_error_string(-3)
+    assert b" - wgnn_attrib_rows: H > 256 is not built" in msg and b"wgnn_predict_rows" not in msg
+    assert lib.wgnn_last_error_string(-3) == generic[-3]
+    assert predict(260) == -3
+    assert attrib(n_rows=0) == 0
+    assert lib.wgnn_last_error_string(-3) == generic[-3]
+
+
 def test_ops_predict_rows_refuses_cpu_tensors():
     rp = torch.tensor([0, 1], dtype=torch.int32)
     with pytest.raises(sda.WgnnError):
