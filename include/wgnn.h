@@ -829,6 +829,53 @@ int wgnn_coverage_rows(const float* x, int64_t ld, const void* rowptr, const int
                        int32_t* n_expressed, int32_t* n_mapped, int32_t* n_bad, double* total, double* total_mapped,
                        int32_t* col_cells, int32_t* status, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Pair rows (additive exports, WGNN_VERSION stays 206): two cells' COUNT rows merged into the log-normalised row of their sum -
+ * a synthetic doublet, the operand of api.ResidentPredictor.doublets.  The merged rows are written out as a CSR that
+ * wgnn_predict_rows takes unchanged; the scheme is wgnn_align_count_ln / _fill_ln's: count, the caller's exclusive scan, fill.
+ * Operand: a bundle-vocabulary CSR of raw counts - rowptr [n_rows + 1] (int32, or int64 with WGNN_FLAG_ROWPTR_I64), col int32,
+ * cnt f32, nnz = the length of col / cnt - whose EVERY ROW IS STRICTLY ASCENDING in col (so a gene occurs once per row), every
+ * count an integer in [1, 2^23] (the caller's check; the f32 sum of two counts is then exact).  lib int64 [n_rows]: a cell's
+ * library size, ALL its reads, those in columns outside the bundle included.  a, b int32 [n_pairs]: the pairs' rows.
+ * scale > 0 (Seurat's scale.factor), threshold >= 0.  For pair q, with A = a[q] and B = b[q]:
+ *
+ *   total = double(lib[A] + lib[B])
+ *   for every gene g in the union of the two rows:  c = cnt_A(g) + cnt_B(g)        (a missing entry counts 0)
+ *   v = float( log1p( double(c) / total * scale ) )      - lognorm() of csrc/wgnn_align_rows.h, the ONE definition that
+ *                                                          wgnn_align_count_ln and wgnn_predict_rows_thin evaluate
+ *   the entry (g, v) leaves  iff  c > 0 && v > threshold;  entries leave in ascending g.
+ *
+ * So a merged row carries THE BITS wgnn_align_count_ln / _fill_ln leave on the two cells' summed count row (one more column
+ * holding their reads outside the bundle), and a self pair (A == B, allowed) the bits of the cell's own lognorm-aligned row:
+ * 2c / 2T == c / T exactly.  total == 0 gives the empty row.
+ *   wgnn_pair_rows_count: n_out int32 [n_pairs] = the entries pair q leaves.
+ *   wgnn_pair_rows_fill : out_rowptr int64 [n_pairs + 1] = the exclusive scan of n_out (the caller's), out_col int32 and
+ *                         out_val f32 [out_rowptr[n_pairs]].
+ * One wavefront per pair (grid-stride); COUNT and FILL are the same walk - a merge path over the two sorted rows, 64 merged
+ * positions per step, each lane finding its element by a binary search on its diagonal (ties: A's element first; B's equal
+ * element is the duplicate, added to A's and dropped) - so they agree on every decision.  Wave ballots give the slots: no
+ * atomics on the data path, no LDS, vector stores only; a slot depends on the pair alone, so two launches are bit-identical
+ * and splitting the pair list changes no bit.
+ * Malformed operands never fault; each is skipped and ORs its bit into *status (int32, device memory, zeroed by the caller;
+ * required): a pair with A or B outside [0, n_rows) leaves the empty row, WGNN_PAIR_BAD_INDEX; a row that is found not strictly
+ * ascending, WGNN_PAIR_UNSORTED (what leaves for its pairs is unspecified, every read stays inside the two rows); a row range
+ * outside [0, nnz] (the empty row) or a slot at or past out_rowptr[q + 1] (not written), WGNN_PAIR_BAD_ROWPTR.
+ * n_rows < 2^31, n_pairs < 2^31, a merged row keeps < 2^31 entries.  n_pairs = 0 is valid.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (status NULL, a missing operand or output, a negative size, n_pairs >= 2^31, scale
+ * not positive and finite, threshold < 0 or NaN, an unknown flag), WGNN_ERR_ALIGNMENT (lib / out_rowptr / an int64 rowptr not
+ * 8-byte, any other operand not 4-byte aligned); wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+#define WGNN_PAIR_BAD_INDEX  1   /* status bit: a[q] or b[q] was outside [0, n_rows)                              */
+#define WGNN_PAIR_UNSORTED   2   /* status bit: a row was not strictly ascending in col                           */
+#define WGNN_PAIR_BAD_ROWPTR 4   /* status bit: a row range outside [0, nnz], or out_rowptr left a pair less room */
+int wgnn_pair_rows_count(const void* rowptr, const int32_t* col, const float* cnt, int64_t n_rows, int64_t nnz,
+                         const int64_t* lib, const int32_t* a, const int32_t* b, int64_t n_pairs, double scale,
+                         float threshold, int32_t* n_out, int32_t* status, uint32_t flags, void* stream);
+int wgnn_pair_rows_fill(const void* rowptr, const int32_t* col, const float* cnt, int64_t n_rows, int64_t nnz,
+                        const int64_t* lib, const int32_t* a, const int32_t* b, int64_t n_pairs, double scale,
+                        float threshold, const int64_t* out_rowptr, int32_t* out_col, float* out_val, int32_t* status,
+                        uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

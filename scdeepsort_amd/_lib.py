@@ -22,6 +22,7 @@ CLUSTERS_ACCUMULATE = 256          # wgnn_group_class_reduce's flag bit (include
 STABILITY_ACCUMULATE = 256         # wgnn_predict_rows_dropout's flag bit (include/wgnn.h)
 THIN_ACCUMULATE = 256              # wgnn_predict_rows_thin's flag bit (include/wgnn.h)
 ALIGN_BAD_COL, ALIGN_BAD_MAP, ALIGN_BAD_ROWPTR, ALIGN_BAD_VALUE = 1, 2, 4, 8     # wgnn_align_*'s status bits (include/wgnn.h)
+PAIR_BAD_INDEX, PAIR_UNSORTED, PAIR_BAD_ROWPTR = 1, 2, 4     # wgnn_pair_rows_*'s status bits (include/wgnn.h)
 ABI_MAJOR = 2                    # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
@@ -96,6 +97,9 @@ SIGNATURES = {
     "wgnn_align_fill_ln_merge": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, _vp, _i32, _i32,
                                            _vp, C.c_double, _vp, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_coverage_rows": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_pair_rows_count": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, C.c_double, C.c_float, _vp, _vp, _u32, _vp]),
+    "wgnn_pair_rows_fill": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, C.c_double, C.c_float, _vp, _vp, _vp, _vp,
+                                      _u32, _vp]),
 }
 
 

@@ -518,6 +518,9 @@ RESIDENT_FUSED_MAX_WORK = int(os.environ.get("WGNN_RESIDENT_FUSED_MAX_WORK", 32_
 # ResidentPredictor.stability: bytes of [cells x draws, H] f32 intermediates one launch of a deeper model may hold; the cells
 # of a batch are chunked under it (the masks follow the cell's number in the batch, so chunking changes no bit)
 STABILITY_CHUNK_BYTES = 256 * 1024 * 1024
+# ResidentPredictor.doublets: bytes of merged CSR (col + val, 8 per entry) one chunk of pairs may hold; a pair's merged row is
+# at most as long as its two rows together, so the chunks are cut before any launch (chunking changes no bit)
+DOUBLETS_CHUNK_BYTES = 256 * 1024 * 1024
 
 
 def load_map_dict(path, tissue: str) -> dict:
@@ -1108,6 +1111,213 @@ class Stability:
             raise ValueError(f"into: the table was drawn with seed {self.seed}, this call passes {seed}")
 
 
+_PAIR_K_CELL, _PAIR_K_DRAW, _PAIR_GOLDEN = 0x9FB21C651E98DF25, 0xD6E8FEB86659FD93, 0x9E3779B97F4A7C15
+
+
+def _i64(x: int) -> int:
+    """A 64-bit pattern as the int64 that holds it (two's complement)."""
+    x &= 2 ** 64 - 1
+    return x - 2 ** 64 if x >= 2 ** 63 else x
+
+
+def _lsr(x: torch.Tensor, s: int) -> torch.Tensor:
+    """Logical right shift of int64 bit patterns."""
+    return (x >> s) & ((1 << (64 - s)) - 1)
+
+
+def _mix64(x: torch.Tensor) -> torch.Tensor:
+    """The splitmix64 finaliser of include/wgnn.h (``mix64``) on int64 tensors holding uint64 bit patterns: sums and products
+    wrap around, shifts are logical."""
+    x = x + _i64(_PAIR_GOLDEN)
+    x = (x ^ _lsr(x, 30)) * _i64(0xBF58476D1CE4E5B9)
+    x = (x ^ _lsr(x, 27)) * _i64(0x94D049BB133111EB)
+    return x ^ _lsr(x, 31)
+
+
+def _draw_partners(label: torch.Tensor, n_partners: int, seed: int, across: str, draw0: int = 0) -> torch.Tensor:
+    """``doublets``' partner rule (its docstring states it) on the device: ``label`` int [B] = the cells' full calls (-1 =
+    unsure), returns int32 [B, n_partners]."""
+    B, dev = int(label.shape[0]), label.device
+    cell = torch.arange(B, dtype=torch.int64, device=dev)[:, None]
+    draw = torch.arange(draw0, draw0 + n_partners, dtype=torch.int64, device=dev)[None, :]
+    key = (cell * _i64(_PAIR_K_CELL)) ^ (draw * _i64(_PAIR_K_DRAW)) ^ _i64(int(seed))
+    u = _mix64(key + _i64(_PAIR_GOLDEN))
+    if across == "any":
+        if B < 2:
+            raise ValueError("doublets: a batch of one cell has no partner")
+        M = torch.full((B, 1), B - 1, dtype=torch.int64, device=dev)
+    else:
+        sorted_label, order = torch.sort(label.to(torch.int64), stable=True)      # by (full call, index); -1 = its own group
+        start = torch.searchsorted(sorted_label, label.to(torch.int64), right=False)[:, None]
+        size = torch.searchsorted(sorted_label, label.to(torch.int64), right=True)[:, None] - start
+        if int(size.max()) >= B:
+            raise ValueError("doublets: every cell of the batch has the same call, so across=\"types\" has no partner to draw - "
+                             "pass across=\"any\"")
+        M = B - size
+    # u mod M for the unsigned u = hi * 2^32 + lo: every intermediate is below 2^63 (M < 2^31)
+    hi, lo = _lsr(u, 32), u & 0xFFFFFFFF
+    k = ((hi % M) * ((1 << 32) % M) + lo) % M
+    if across == "any":
+        return (k + (k >= cell).to(torch.int64)).to(torch.int32)
+    return order[k + torch.where(k >= start, size, torch.zeros_like(size))].to(torch.int32)
+
+
+class DoubletsSummary(dict):
+    """``Doublets.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_cells']} cells x {d['n_partners']} partners drawn across {d['across']}: {d['n_heterotypic']} heterotypic pairs",
+            f"called as a parent {d['parent_share']:.3f}, as a third type {d['third_share']:.3f}, unsure (caught) {d['caught']:.3f}",
+            f"largest sink: {d['top_sink']} takes {d['top_sink_pairs']} pairs neither of whose parents it is"])
+
+
+@dataclass
+class Doublets:
+    """What ``ResidentPredictor.doublets`` returns: what the model calls synthetic doublets of a batch.  B cells (``index``), C
+    cell types (``id2label``), D = ``n_partners`` draws per cell.  ``label`` int64 [B] / ``max_prob`` f32 [B]: the call on the
+    real cell (``classify``'s, -1 = unsure).  Per (cell, draw), numpy arrays [B, D]: ``partner`` int32 = the second cell of the
+    pair, ``draw_label`` int32 / ``draw_prob`` f32 = the call on the summed counts of the two.  ``seed`` / ``across``: how the
+    partners were drawn.
+
+    In the methods a pair's PARENTS are the real calls of its two cells.  A pair is HETEROTYPIC when both parents are called
+    (not unsure) and differ; the other pairs are in ``pair_table`` and in nothing else.  This table characterises the MODEL on
+    doublets; it does not say which real cells are doublets."""
+    label: np.ndarray
+    max_prob: np.ndarray
+    partner: np.ndarray
+    draw_label: np.ndarray
+    draw_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    seed: int = 0
+    across: str = "types"
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    @property
+    def n_partners(self) -> int:
+        return int(self.partner.shape[1])
+
+    def _parents(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(type of the cell, type of the partner, heterotypic) as [B, D] arrays."""
+        lab = np.asarray(self.label, np.int64)
+        own = np.broadcast_to(lab[:, None], self.partner.shape)
+        other = lab[self.partner.astype(np.int64)] if self.partner.size else own
+        return own, other, (own >= 0) & (other >= 0) & (own != other)
+
+    def pair_table(self) -> np.ndarray:
+        """int64 [C + 1, C + 1, C + 1]: the pairs by (type of the cell, type of the partner, call of the pair), unsure as the
+        last slot of every axis."""
+        C = len(self.id2label)
+        own, other, _ = self._parents()
+        slot = lambda x: np.where(x >= 0, x, C).astype(np.int64).ravel()
+        flat = (slot(own) * (C + 1) + slot(other)) * (C + 1) + slot(np.asarray(self.draw_label, np.int64))
+        return np.bincount(flat, minlength=(C + 1) ** 3).reshape(C + 1, C + 1, C + 1)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per unordered heterotypic type pair that was drawn: ``type_a`` / ``type_b`` (the lower id first, named as
+        ``predict`` names a call), ``n`` pairs, ``parent_share`` (called as either parent), ``third_share`` (called a third
+        type), ``unsure_share``, ``top_third`` (the most frequent third type, the lower id among equals, ``None`` without one)
+        and ``mean_prob`` (the pairs' mean largest softmax probability)."""
+        C = len(self.id2label)
+        t = self.pair_table()[:C, :C]
+        t = t + t.transpose(1, 0, 2)                                  # unordered: (S, T) and (T, S) together
+        own, other, het = self._parents()
+        lo, hi = np.minimum(own, other)[het], np.maximum(own, other)[het]
+        prob = np.bincount(lo * C + hi, weights=np.asarray(self.draw_prob, np.float64)[het], minlength=C * C).reshape(C, C)
+        rows = []
+        for s in range(C):
+            for u in range(s + 1, C):
+                n = int(t[s, u].sum())
+                if n == 0:
+                    continue
+                third = t[s, u, :C].copy()
+                third[[s, u]] = 0
+                top = int(third.argmax())
+                rows.append((s, u, n, (t[s, u, s] + t[s, u, u]) / n, third.sum() / n, t[s, u, C] / n,
+                             top if third[top] > 0 else -3, prob[s, u] / n))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(8)]
+        name = lambda ids: _call_names(np.asarray(ids, np.int64), self.id2label, self.label_map)[0]
+        return pd.DataFrame({"type_a": name(cols[0]), "type_b": name(cols[1]), "n": np.asarray(cols[2], np.int64),
+                             "parent_share": np.asarray(cols[3], np.float64), "third_share": np.asarray(cols[4], np.float64),
+                             "unsure_share": np.asarray(cols[5], np.float64), "top_third": name(cols[6]),
+                             "mean_prob": np.asarray(cols[7], np.float64)})
+
+    def _het_calls(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The heterotypic pairs' (type of the cell, type of the partner, call) as flat arrays."""
+        own, other, het = self._parents()
+        return own[het], other[het], np.asarray(self.draw_label, np.int64)[het]
+
+    def caught(self) -> float:
+        """The share of the heterotypic pairs that the unsure rule flags (NaN without such a pair)."""
+        _, _, call = self._het_calls()
+        return float((call < 0).mean()) if call.size else float("nan")
+
+    def sinks(self) -> np.ndarray:
+        """f64 [C]: per type T, of the heterotypic pairs CALLED T, the share neither of whose parents is T (NaN for a type no
+        such pair was called).  A type with a high share and many pairs takes in doublets of other types."""
+        C = len(self.id2label)
+        own, other, call = self._het_calls()
+        called = np.bincount(call[call >= 0], minlength=C).astype(np.float64)
+        foreign = np.bincount(call[(call >= 0) & (call != own) & (call != other)], minlength=C)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(called > 0, foreign / called, np.nan)
+
+    def artifact_risk(self, rate: float = 0.05) -> np.ndarray:
+        """f64 [C]: per type T, the share of the cells called T that would be doublets of two OTHER types if a fraction ``rate``
+        of the barcodes were heterotypic doublets: ``rate * q / (rate * q + (1 - rate) * r)`` with ``q`` = the share of the
+        heterotypic pairs that are called T while T is neither parent and ``r`` = the share of the real cells called T (NaN where
+        both are 0).  An approximation: the doublets' composition is the partner rule's (``across``), not the sample's;
+        homotypic doublets and doublets called as a parent count as harmless; and ``r`` is taken from this batch, which holds
+        its own doublets."""
+        rate = float(rate)
+        if not 0.0 <= rate <= 1.0:
+            raise ValueError(f"rate = {rate!r} must be in [0, 1]")
+        C = len(self.id2label)
+        own, other, call = self._het_calls()
+        q = np.bincount(call[(call >= 0) & (call != own) & (call != other)], minlength=C) / max(call.size, 1)
+        lab = np.asarray(self.label, np.int64)
+        r = np.bincount(lab[lab >= 0], minlength=C) / max(lab.size, 1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(rate * q + (1 - rate) * r > 0, rate * q / (rate * q + (1 - rate) * r), np.nan)
+
+    def dominance(self) -> np.ndarray:
+        """f64 [B]: per cell, the share of its heterotypic draws that keep the cell's own call (NaN for a cell without one -
+        an unsure cell has none)."""
+        own, _, het = self._parents()
+        same = (het & (np.asarray(self.draw_label, np.int64) == own)).sum(axis=1)
+        n = het.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, same / n, np.nan)
+
+    def summary(self) -> DoubletsSummary:
+        """The heterotypic pairs at a glance - their number, the shares called as a parent, as a third type and unsure
+        (``caught``) - and the type that takes in most pairs it is no parent of; ``print`` it."""
+        C = len(self.id2label)
+        own, other, call = self._het_calls()
+        n = int(call.size)
+        parent = (call == own) | (call == other)
+        foreign = np.bincount(call[(call >= 0) & ~parent], minlength=C)
+        top = int(foreign.argmax()) if C and foreign.max(initial=0) > 0 else -3
+        share = lambda m: float(m.mean()) if n else float("nan")
+        return DoubletsSummary(n_cells=len(self.label), n_partners=self.n_partners, across=self.across, seed=int(self.seed),
+                               n_heterotypic=n, parent_share=share(parent), third_share=share((call >= 0) & ~parent),
+                               caught=self.caught(), top_sink=_call_names([top], self.id2label, self.label_map)[0][0],
+                               top_sink_pairs=int(foreign[top]) if top >= 0 else 0)
+
+    def _require_same(self, n_cells: int, id2label: Sequence[str], seed: int, across: str) -> None:
+        """``into=``: the further partners must be of the same batch shape, cell types, seed and partner rule."""
+        if across != self.across:
+            raise ValueError(f"into: the table was drawn across={self.across!r}, this call passes across={across!r}")
+        if n_cells != len(self.label):
+            raise ValueError(f"into: the table holds {len(self.label)} cells, the batch {n_cells}")
+        if list(id2label) != list(self.id2label):
+            raise ValueError("into: the table's cell types differ from the bundle's")
+        if int(seed) != int(self.seed):
+            raise ValueError(f"into: the table was drawn with seed {self.seed}, this call passes {seed}")
+
+
 @dataclass(frozen=True)
 class LogNormalize:
     """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
@@ -1677,6 +1887,105 @@ class ResidentPredictor:
         if save_path is not None:
             Path(save_path).mkdir(parents=True, exist_ok=True)
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_stability.csv", index=False)
+        return out
+
+    # ---------------------------------------------------------------------------------------------
+    def doublets(self, expr, genes, normalize=None, n_partners: int = 16, across: str = "types", seed: int = 0, index=None,
+                 into: Optional[Doublets] = None) -> Doublets:
+        """What does this model call a DOUBLET - two cells in one droplet, whose reads are the sum of both cells'?  Every cell
+        of the batch is paired with ``n_partners`` other cells of the batch, the two cells' raw counts are added on the device
+        and log-normalised against the sum of their library sizes (``wgnn_pair_rows_count`` / ``_fill``; the merged rows are
+        stored, one chunk of pairs at a time under ``DOUBLETS_CHUNK_BYTES``), and the merged rows go through the predictor's own
+        ``classify`` path - every layer, either route - so a pair's call is bit for bit ``classify`` of the host-summed count
+        matrix.  Returns a ``Doublets``: ``pair_table`` / ``frame`` / ``caught`` / ``sinks`` / ``artifact_risk`` / ``dominance`` /
+        ``summary`` on top.
+
+        The batch holds raw integer COUNTS: ``genes=`` and a ``normalize`` spec are required exactly as
+        ``stability(thin="reads")`` requires them (else ``ValueError``), a ``GeneMap`` with merged columns raises ``ValueError``,
+        a count that is no integer in [1, 2^23] raises ``WgnnError`` naming the cell.  The genes may come in any order (the
+        rows are sorted by bundle id when they are not; a pair's call follows the sorted row).  The real cells' call is
+        ``classify``'s on the lognorm-aligned batch.  ``index``: the cells' names (default ``range(B)``).
+
+        The partners, drawn on the device over the whole batch, are a pure function of ``(seed, cell, draw)``.  With ``key`` and
+        ``mix64`` of ``include/wgnn.h`` (the dropout block), in uint64 with wrap-around:
+        ``u = mix64((seed ^ cell * 0x9FB21C651E98DF25 ^ draw * 0xD6E8FEB86659FD93) + 0x9E3779B97F4A7C15)`` and ``k = u mod M``
+        (the modulo bias is below 2^-32).  ``across="any"``: ``M = B - 1`` and the partner is ``k + (k >= cell)`` - any other
+        cell.  ``across="types"`` (the default): the cells are ordered stably by (full call, index), -1 (unsure) being a group
+        of its own; ``M = B`` minus the size of the cell's own group, and the partner is the ``k``-th cell of that order outside
+        the group - so two cells of one call are never paired.  A batch with a single group raises ``ValueError`` (pass
+        ``across="any"``).
+
+        ``into``: an earlier ``Doublets`` of the same batch, seed and ``across``, to which ``n_partners`` FURTHER draws are
+        appended (and which is returned): 8 and 8 more equal 16 at once.
+
+        Out of scope: this characterises the model on doublets, it does not call real cells doublets - there is no kNN or
+        embedding score here."""
+        if across not in ("types", "any"):
+            raise ValueError(f"across = {across!r}: pass \"types\" or \"any\"")
+        n_partners = int(n_partners)
+        if n_partners < 1:
+            raise ValueError(f"n_partners = {n_partners} must be >= 1")
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
+        if genes is None or spec is None:
+            raise ValueError("doublets adds raw counts: pass the batch over its own gene list (genes=) and a normalize spec (the "
+                             "summed counts are log-normalised against the sum of the two library sizes)")
+        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
+        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
+            raise ValueError("doublets does not take merged columns (duplicates=\"sum\"): merging under pairing is not built")
+        B = self._n_cells(expr)
+        if into is not None:
+            into._require_same(B, self.id2label, seed, across)
+        if index is not None and len(index) != B:
+            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._doublets(expr, genes, spec, n_partners, across, int(seed), index, into)
+
+    def _doublets(self, expr, genes, spec, n_partners, across, seed, index, into):
+        dev = self.device
+        (rowptr, col, cnt), _, lib = self._thin_operands(expr, genes, spec)
+        _ops.pair_operand_check(rowptr, cnt)
+        rowptr, col, cnt = _ops.csr_rows_ascending(rowptr, col, cnt)
+        pred, max_prob, _, label = self._classify_on_device(_Aligned(self._align(expr, genes, None, spec)))
+        if label is None:                                 # the graph route classifies on the host
+            label = torch.from_numpy(pred.astype(np.int32)).to(dev)
+        B, D = int(rowptr.shape[0]) - 1, n_partners
+        draw0 = 0 if into is None else into.n_partners
+        partner = _draw_partners(label, D, seed, across, draw0)
+        a = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(D)
+        b = partner.reshape(-1).contiguous()
+        # chunks of consecutive pairs whose merged rows (at most the two rows' lengths, 8 bytes per entry) fit the budget
+        lens = (rowptr[1:] - rowptr[:-1]).long()
+        bound = torch.cumsum((lens[a.long()] + lens[b.long()]) * 8, 0).cpu().numpy()
+        draw_label = np.empty(B * D, np.int32)
+        draw_prob = np.empty(B * D, np.float32)
+        q0 = 0
+        while q0 < B * D:
+            done = int(bound[q0 - 1]) if q0 else 0
+            q1 = max(q0 + 1, int(np.searchsorted(bound, done + DOUBLETS_CHUNK_BYTES, side="right")))
+            merged = _ops.pair_rows(rowptr, col, cnt, lib, a[q0:q1], b[q0:q1], scale=float(spec.scale_factor),
+                                    threshold=float(self.threshold))
+            draw_label[q0:q1], draw_prob[q0:q1] = self._classify_on_device(_Aligned(merged))[:2]
+            q0 = q1
+        partner, draw_label, draw_prob = partner.cpu().numpy(), draw_label.reshape(B, D), draw_prob.reshape(B, D)
+        if into is None:
+            return Doublets(label=pred, max_prob=np.asarray(max_prob, np.float32), partner=partner, draw_label=draw_label,
+                            draw_prob=draw_prob, index=pd.RangeIndex(B) if index is None else index,
+                            id2label=list(self.id2label), seed=seed, across=across, label_map=self._label_names())
+        into.partner = np.concatenate([into.partner, partner], axis=1)
+        into.draw_label = np.concatenate([into.draw_label, draw_label], axis=1)
+        into.draw_prob = np.concatenate([into.draw_prob, draw_prob], axis=1)
+        return into
+
+    def doublets_file(self, input_file, normalize="lognorm", n_partners: int = 16, across: str = "types", seed: int = 0,
+                      save_path=None) -> pd.DataFrame:
+        """``doublets`` on a test file of raw counts (its full table and gene names): ``Doublets.frame()``, written as
+        ``{species}_{tissue}_doublets.csv`` under ``save_path`` when given."""
+        df = _read_expression(input_file, self.file_type)
+        out = self.doublets(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], normalize=normalize,
+                            n_partners=n_partners, across=across, seed=seed, index=df.index).frame()
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_doublets.csv", index=False)
         return out
 
     # ---------------------------------------------------------------------------------------------

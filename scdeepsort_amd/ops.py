@@ -1091,6 +1091,99 @@ def thin_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, rest: torch.Tens
                         f"or 2^31 reads or more")
 
 
+PAIR_MAX_COUNT = float(2 ** 23)     # pair_rows adds two counts in float32: exact up to here
+
+
+def pair_operand_check(rowptr: torch.Tensor, raw: torch.Tensor) -> None:
+    """What ``doublets`` asks of its counts beyond ``thin_operand_check``: none above 2^23, so that the float32 sum of two
+    cells' counts is exact.  One reduction to the first offending cell and one read-back; ``WgnnError`` naming that cell."""
+    B = int(rowptr.shape[0]) - 1
+    if B == 0 or not raw.numel():
+        return
+    rows = torch.repeat_interleave(torch.arange(B, device=raw.device), (rowptr[1:] - rowptr[:-1]).long(), output_size=raw.shape[0])
+    first = int(torch.where(raw > PAIR_MAX_COUNT, rows, B).min())
+    if first < B:
+        raise WgnnError(f"doublets adds two cells' counts in float32: cell {first} holds a count above 2^23")
+
+
+def csr_rows_ascending(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor):
+    """``(rowptr, col, val)`` with every row strictly ascending in ``col``, as ``pair_rows`` takes it: the operand itself when it
+    already is (one device reduction and a read-back), else the entries stably sorted by ``(row, col)``.  A column listed twice
+    within a row raises ``WgnnError``.  Torch ops only; off the hot path."""
+    n = int(col.shape[0])
+    if n < 2:
+        return rowptr, col, val
+    B = int(rowptr.shape[0]) - 1
+    rows = torch.repeat_interleave(torch.arange(B, device=col.device), (rowptr[1:] - rowptr[:-1]).long(), output_size=n)
+    lo, hi = torch.aminmax(col)
+    key = rows * (int(hi) - int(lo) + 1) + (col.long() - int(lo))         # ascending in (row, col)
+    if bool((key[1:] > key[:-1]).all()):
+        return rowptr, col, val
+    key, order = torch.sort(key, stable=True)
+    twice = key[1:] == key[:-1]
+    if bool(twice.any()):
+        at = int(torch.nonzero(twice)[0])
+        raise WgnnError(f"row {int(rows[order[at]])} lists column {int(col[order[at]])} twice")
+    return rowptr, col[order].contiguous(), val[order].contiguous()
+
+
+_PAIR_STATUS = ((_lib.PAIR_BAD_INDEX, "a pair names a row outside [0, n_rows)"),
+                (_lib.PAIR_UNSORTED, "a row is not strictly ascending in col (csr_rows_ascending sorts a batch)"),
+                (_lib.PAIR_BAD_ROWPTR, "rowptr points outside col / cnt, or a pair kept more entries than were counted"))
+
+
+def pair_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
+              scale: float = 1e4, threshold: float = 0.0):
+    """``wgnn_pair_rows_count`` / ``wgnn_pair_rows_fill``: pairs of cells merged into the log-normalised rows of their summed
+    counts - synthetic doublets.  ``(rowptr int32 / int64 [B+1], col int32, cnt float32)``: a device CSR of raw counts over the
+    bundle's gene ids, every row strictly ascending in ``col``, every count an integer in [1, 2^23] (``pair_operand_check``);
+    ``lib`` int64 [B]: each cell's library size, columns outside the bundle included; ``a``, ``b`` int32 [n_pairs]: the rows of
+    a pair (``a[q] == b[q]`` is allowed).
+
+    Pair ``q`` leaves, in ascending gene id, ``float32(log1p(float64(c) / (lib[a] + lib[b]) * scale))`` for every gene of
+    either row with ``c = cnt_a + cnt_b > 0`` and a value ``> threshold`` (``>= 0``) - the bits
+    ``align_rows(..., normalize="lognorm")`` leaves on the summed count matrix (the contract in ``include/wgnn.h``).  Returns
+    ``(rowptr int64 [n_pairs + 1], col int32, val float32)`` on the device, which ``predict_rows`` takes: the count pass, a
+    ``torch.cumsum``, one read-back of the total to size the outputs, the fill pass, and a read-back of the status word - a pair
+    index out of range, a row that is not ascending or a ``rowptr`` outside ``col`` raises ``WgnnError`` (the kernels skip it).
+    Argument errors are ``ValueError``."""
+    dev = _require_cuda(rowptr, col, cnt, lib, a, b)
+    if not 0 < float(scale) < float("inf"):
+        raise ValueError(f"pair_rows: scale = {scale} must be positive and finite")
+    if not float(threshold) >= 0:
+        raise ValueError(f"pair_rows: threshold = {threshold} must be >= 0")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
+        raise ValueError("pair_rows takes rowptr int32 / int64, col int32, cnt float32")
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
+        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
+    B = int(rowptr.shape[0]) - 1
+    if lib.dtype != torch.int64 or tuple(lib.shape) != (B,):
+        raise ValueError(f"pair_rows: lib must be int64 [{B}]")
+    if a.dtype != torch.int32 or b.dtype != torch.int32 or a.dim() != 1 or a.shape != b.shape:
+        raise ValueError("pair_rows: a and b must be int32 vectors of one length")
+    n_pairs = int(a.shape[0])
+    if n_pairs >= 2 ** 31:
+        raise ValueError("pair_rows: n_pairs >= 2^31 (split the pair list)")
+    rowptr, col, cnt, lib, a, b = (t.contiguous() for t in (rowptr, col, cnt, lib, a, b))
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_out = torch.empty(n_pairs, dtype=torch.int32, device=dev)
+    head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, int(col.shape[0]), _ptr(lib), _ptr(a), _ptr(b), n_pairs, float(scale),
+            float(threshold))
+    _lib.check(_lib.call(dev, "wgnn_pair_rows_count", *head, _ptr(n_out), _ptr(status), flags, _stream(dev)), "wgnn_pair_rows_count")
+    out_rowptr = torch.zeros(n_pairs + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(n_out, 0, dtype=torch.int64, out=out_rowptr[1:])
+    total = int(out_rowptr[-1])                              # the one read-back that sizes the outputs
+    out_col = torch.empty(total, dtype=torch.int32, device=dev)
+    out_val = torch.empty(total, dtype=torch.float32, device=dev)
+    _lib.check(_lib.call(dev, "wgnn_pair_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(status), flags,
+                         _stream(dev)), "wgnn_pair_rows_fill")
+    bits = int(status)
+    if bits:
+        raise WgnnError("pair_rows: " + "; ".join(text for bit, text in _PAIR_STATUS if bits & bit))
+    return out_rowptr, out_col, out_val
+
+
 def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
                 bias: torch.Tensor, *, head: Optional[tuple] = None, target: Optional[torch.Tensor] = None,
                 self_rows: Optional[torch.Tensor] = None, direction: Optional[torch.Tensor] = None,
