@@ -876,6 +876,77 @@ int wgnn_pair_rows_fill(const void* rowptr, const int32_t* col, const float* cnt
                         float threshold, const int64_t* out_rowptr, int32_t* out_col, float* out_val, int32_t* status,
                         uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Pool rows (additive exports, WGNN_VERSION stays 206): the COUNT rows of all cells of a group - a cluster, a sample, a metacell -
+ * added into one pooled count row per group, and that row log-normalised against the group's pooled library size: the operand
+ * of api.ResidentPredictor.pseudobulk.  Two steps: ACCUMULATE adds cells into a dense integer table, FINISH turns the table
+ * into a CSR that wgnn_predict_rows takes unchanged (count, the caller's exclusive scan, fill, as wgnn_pair_rows_*).
+ *
+ * wgnn_pool_rows_accumulate
+ * Operand: a bundle-vocabulary CSR of raw counts - rowptr [n_rows + 1] (int32, or int64 with WGNN_FLAG_ROWPTR_I64), col int32,
+ * cnt f32, nnz = the length of col / cnt.  Every count is an integer in [1, 2^23] (the caller's check; any other value is
+ * left out without a word).  Rows need NOT be sorted, and a gene listed twice in a row adds twice.
+ * group_ptr int64 [n_groups + 1], ascending, and members int32 [n_rows]: the cells of group k are
+ * members[group_ptr[k] : group_ptr[k + 1]] (one stable sort of the cells' group ids gives both; the member buffer always holds
+ * n_rows entries, of which [group_ptr[0], group_ptr[n_groups]) are read, so a slice group_ptr + k0 of a longer list is a valid
+ * operand next to the same members).  acc uint64 [n_groups, ld_acc], ld_acc >= n_genes: zeroed or pre-seeded by the caller;
+ *
+ *   acc[k][g] += sum over the members r of group k, over the entries j of row r with col[j] == g, of uint64(cnt[j])
+ *
+ * columns [n_genes, ld_acc) are never touched.  All sums are integers: the result is exact and the same bits in every order - two
+ * launches, any split of the group list, any permutation of the cells.
+ * Work unit: (group k, a run of at most cells_per_unit consecutive members, a slab of at most slab_genes genes); the runs are
+ * cut at multiples of cells_per_unit of the POSITION in the member list counted from group_ptr[0] (so the number of units is
+ * known without reading group_ptr back) and at the groups' ends; a big group is thus spread over n / cells_per_unit workgroups,
+ * a workgroup whose window of positions holds several small groups takes them one after the other.  One workgroup per (window,
+ * slab), grid-stride: it zeroes a uint32 LDS slab, its waves walk the unit's rows (one wave per row, entries outside the slab
+ * skipped by comparison, so a row is read once per slab), LDS integer atomics take the counts - cells_per_unit <= 256 and
+ * 256 x 2^23 < 2^31, no overflow - and only the NON-ZERO slab entries go to acc, one 64-bit global atomic add each.
+ * cells_per_unit: 0 = the default (64), at most 256.  slab_genes: 0 = the default (16384: 64 KiB of the CU's 160 KiB LDS, two
+ * workgroups per CU), at most 16384; a slab is never wider than n_genes.
+ *
+ * wgnn_pool_rows_count / wgnn_pool_rows_fill
+ * total int64 [n_groups]: the groups' summed library sizes, ALL reads, those outside the bundle included, each < 2^53.
+ * scale > 0, threshold >= 0.  For group k, g ascending:
+ *
+ *   c = acc[k][g];   v = float( log1p( double(c) / double(total[k]) * scale ) )   - lognorm() of csrc/wgnn_align_rows.h in its
+ *                                                        form that takes the count as a double (a pooled count may exceed 2^24)
+ *   the entry leaves  iff  c > 0 && v > threshold;   total[k] <= 0 gives the empty row.
+ *
+ *   count: n_out int32 [n_groups] = the entries group k leaves.
+ *   fill : out_rowptr int64 [n_groups + 1] = the exclusive scan of n_out (the caller's), out_col int32, out_val f32 and - may be
+ *          NULL - out_cnt int64 [out_rowptr[n_groups]]: gene, value and c of every kept entry.
+ * So wherever every c <= 2^24 a pooled row carries THE BITS wgnn_align_count_ln / _fill_ln leave on the group's summed count row
+ * (one more column holding the reads outside the bundle), a group of two the bits of wgnn_pair_rows_*, a group of one the bits
+ * of the cell's own lognorm-aligned row.  One wavefront per group row (grid-stride), 64 genes per step, wave ballots give the
+ * slots; COUNT and FILL are the same walk.  No atomics, vector stores only.
+ *
+ * Malformed operands never fault; each is skipped and ORs its bit into *status (int32, device memory, zeroed by the caller;
+ * required): a member outside [0, n_rows), WGNN_POOL_BAD_INDEX; a row range outside [0, nnz], a group_ptr that is not ascending
+ * or leaves [0, n_rows] (what is added for the groups around it is unspecified, every read stays inside the operands), a slot at
+ * or past out_rowptr[k + 1] (not written), WGNN_POOL_BAD_ROWPTR; a gene id outside [0, n_genes), WGNN_POOL_BAD_COL.
+ * n_rows, n_groups, n_genes < 2^31.  n_groups = 0 and n_rows = 0 are valid.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (status NULL, a missing operand or output, a negative size, a size >= 2^31,
+ * ld_acc < n_genes, cells_per_unit outside [0, 256], slab_genes outside [0, 16384] - a wider slab does not fit the LDS budget -,
+ * scale not positive and finite, threshold < 0 or NaN, an unknown flag), WGNN_ERR_ALIGNMENT (group_ptr / acc / total /
+ * out_rowptr / out_cnt / an int64 rowptr not 8-byte, any other operand not 4-byte aligned); wgnn_last_error_string names the
+ * check.
+ * ------------------------------------------------------------------------- */
+#define WGNN_POOL_BAD_INDEX  1   /* status bit: a member was outside [0, n_rows)                                      */
+#define WGNN_POOL_BAD_ROWPTR 2   /* status bit: a row range outside [0, nnz], a malformed group_ptr, or too little room */
+#define WGNN_POOL_BAD_COL    4   /* status bit: a gene id was outside [0, n_genes)                                    */
+#define WGNN_POOL_MAX_CELLS_PER_UNIT 256
+#define WGNN_POOL_MAX_SLAB_GENES     16384
+int wgnn_pool_rows_accumulate(const void* rowptr, const int32_t* col, const float* cnt, int64_t n_rows, int64_t nnz,
+                              const int64_t* group_ptr, const int32_t* members, int64_t n_groups, int32_t n_genes,
+                              uint64_t* acc, int64_t ld_acc, int32_t cells_per_unit, int32_t slab_genes, int32_t* status,
+                              uint32_t flags, void* stream);
+int wgnn_pool_rows_count(const uint64_t* acc, int64_t ld_acc, const int64_t* total, int64_t n_groups, int32_t n_genes,
+                         double scale, float threshold, int32_t* n_out, int32_t* status, void* stream);
+int wgnn_pool_rows_fill(const uint64_t* acc, int64_t ld_acc, const int64_t* total, int64_t n_groups, int32_t n_genes,
+                        double scale, float threshold, const int64_t* out_rowptr, int32_t* out_col, float* out_val,
+                        int64_t* out_cnt, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

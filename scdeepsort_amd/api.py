@@ -1318,6 +1318,93 @@ class Doublets:
             raise ValueError(f"into: the table was drawn with seed {self.seed}, this call passes {seed}")
 
 
+class PseudobulkSummary(dict):
+    """``Pseudobulk.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_clusters']} clusters pooled from {d['n_cells']} cells: {d['n_called']} called, {d['n_unsure']} unsure, "
+            f"{d['n_empty']} empty",
+            f"reads per cluster: median {d['median_reads']:.0f}, smallest {d['min_reads']}; genes per cluster: median "
+            f"{d['median_genes']:.0f}"])
+
+
+@dataclass
+class Pseudobulk:
+    """What ``ResidentPredictor.pseudobulk`` returns: one pooled profile per cluster.  K clusters (``names``), G bundle genes
+    (``id2gene``).  Per cluster, numpy arrays [K]: ``n_cells`` int64 the cells pooled, ``n_reads`` int64 their summed library
+    sizes (ALL reads, those of genes outside the bundle included), ``n_genes`` int64 the pooled row's entries, ``label`` int64 /
+    ``max_prob`` f32 the call on the pooled profile as ``classify`` makes it (-1 = unsure; what an EMPTY cluster's row of zeros
+    is called is in here too - ``calls()`` puts -2 there).  On the device: ``logits`` [K, C], the pooled rows as the CSR
+    ``(rowptr int64 [K + 1], col int32, val f32)`` the classify path took - ``val`` the log-normalised value of the summed
+    count against ``n_reads`` - and ``cnt`` int64, the summed count of every entry."""
+    names: Sequence[str]
+    n_cells: np.ndarray
+    n_reads: np.ndarray
+    n_genes: np.ndarray
+    label: np.ndarray
+    max_prob: np.ndarray
+    logits: torch.Tensor
+    rowptr: torch.Tensor
+    col: torch.Tensor
+    val: torch.Tensor
+    cnt: torch.Tensor
+    id2label: Sequence[str]
+    id2gene: Sequence[str] = field(repr=False, default=())
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    @property
+    def cluster_names(self) -> Sequence[str]:
+        return self.names
+
+    def counts(self) -> sp.csr_matrix:
+        """The pooled count matrix, a scipy int64 CSR ``[K, G]`` over the bundle's genes (columns in ``id2gene``'s order) - what
+        pseudobulk differential expression starts from.  Reads of genes OUTSIDE the bundle are not in it: they are only in
+        ``n_reads``.  With a predictor ``threshold > 0`` the entries whose normalised value is at or below it are absent too."""
+        K = len(self.names)
+        return sp.csr_matrix((self.cnt.cpu().numpy(), self.col.cpu().numpy(), self.rowptr.cpu().numpy()),
+                             shape=(K, len(self.id2gene)), dtype=np.int64)
+
+    def calls(self) -> np.ndarray:
+        """int64 [K]: ``label``, with -2 for a cluster without cells (as ``ClusterCalls.consensus`` gives)."""
+        return np.where(np.asarray(self.n_cells) == 0, -2, np.asarray(self.label, np.int64)).astype(np.int64)
+
+    def frame(self, calls: Optional["ClusterCalls"] = None, rule: str = "vote", min_fraction: float = 0.0) -> pd.DataFrame:
+        """One row per cluster: ``cluster``, ``n_cells``, ``n_reads``, ``n_genes``, the call on the pooled profile as ``cell_type``
+        / ``cell_subtype`` (named as ``predict`` names cells; ``unsure`` / ``empty`` spelled out) and its ``probability`` (NaN
+        for an empty cluster).  ``calls``: ``annotate``'s table of the same clusters - the frame gains ``vote_type``, the
+        per-cell consensus under ``rule`` / ``min_fraction``, and ``agrees``, whether the two calls are the same id."""
+        ids = self.calls()
+        types, subtypes = _call_names(ids, self.id2label, self.label_map)
+        out = pd.DataFrame({"cluster": list(self.names), "n_cells": self.n_cells, "n_reads": self.n_reads, "n_genes": self.n_genes,
+                            "cell_type": types, "cell_subtype": subtypes,
+                            "probability": np.where(ids == -2, np.nan, np.asarray(self.max_prob, np.float64))})
+        if calls is not None:
+            if list(calls.cluster_names) != list(self.names):
+                raise ValueError("calls: the table's cluster names differ from the pooled profiles'")
+            vote, _ = calls.consensus(rule, min_fraction)
+            out["vote_type"] = _call_names(vote, self.id2label, self.label_map)[0]
+            out["agrees"] = vote == ids
+        return out
+
+    def summary(self) -> PseudobulkSummary:
+        """The pooled profiles at a glance - clusters called, unsure and empty, reads and genes per cluster; ``print`` it."""
+        ids = self.calls()
+        on = ids != -2
+        med = lambda x: float(np.median(x[on])) if on.any() else float("nan")
+        return PseudobulkSummary(n_clusters=len(self.names), n_cells=int(np.sum(self.n_cells)), n_called=int((ids >= 0).sum()),
+                                 n_unsure=int((ids == -1).sum()), n_empty=int((~on).sum()), median_reads=med(self.n_reads),
+                                 min_reads=int(self.n_reads[on].min()) if on.any() else 0, median_genes=med(self.n_genes))
+
+    def _require_same(self, names: Sequence[str], id2label: Sequence[str], id2gene: Sequence[str]) -> None:
+        """``into=``: the batch must be clustered as these profiles are, over the same bundle."""
+        if list(names) != list(self.names):
+            raise ValueError("into: the profiles' cluster names differ from the batch's")
+        if list(id2label) != list(self.id2label) or len(id2gene) != len(self.id2gene):
+            raise ValueError("into: the profiles were pooled over another bundle")
+
+
 @dataclass(frozen=True)
 class LogNormalize:
     """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
@@ -1986,6 +2073,84 @@ class ResidentPredictor:
         if save_path is not None:
             Path(save_path).mkdir(parents=True, exist_ok=True)
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_doublets.csv", index=False)
+        return out
+
+    # ---------------------------------------------------------------------------------------------
+    def pseudobulk(self, expr, genes, clusters, normalize=None, cluster_names: Optional[Sequence[str]] = None,
+                   n_clusters: Optional[int] = None, into: Optional[Pseudobulk] = None) -> Pseudobulk:
+        """One PROFILE per cluster, and the call on it: the raw counts of all cells of a cluster (a sample, a metacell) are
+        added on the device (``wgnn_pool_rows_accumulate``: integer sums, exact in any order), the pooled row is log-normalised
+        against the cluster's summed library size (``wgnn_pool_rows_count`` / ``_fill``) and goes through the predictor's own
+        ``classify`` path - every layer, either route.  A cluster's call is therefore ``classify(..., normalize="lognorm")`` of
+        the host-summed count row with one more column holding the reads outside the bundle; shallow cells whose own calls fall
+        apart (``stability(thin="reads")``) are called together.  Returns a ``Pseudobulk``: the calls, the pooled value CSR and
+        the pooled integer counts (``counts()``: what pseudobulk differential expression takes), ``frame`` / ``summary`` on top.
+
+        The batch holds raw integer COUNTS: ``genes=`` and a ``normalize`` spec are required exactly as ``doublets`` requires
+        them (else ``ValueError``), a ``GeneMap`` with merged columns raises ``ValueError``, a count that is no integer in
+        [1, 2^23] raises ``WgnnError`` naming the cell.  The genes may come in any order.  ``clusters``, ``cluster_names`` and
+        ``n_clusters`` as ``annotate`` takes them: one integer id per cell (-1 = skip), or one ``str`` name per cell - factorised
+        in sorted order, or matched against ``into``'s names.  Choosing the clusters or metacells is the caller's.
+
+        ``into``: an earlier ``Pseudobulk`` of the same bundle and cluster names; this batch is pooled ON TOP of it, the
+        clusters are classified again, and ``into`` is returned: two halves of a cohort equal the whole, bit for bit.  It needs
+        the predictor's ``threshold`` to be 0 (a pooled row that dropped entries cannot be added to)."""
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
+        if genes is None or spec is None:
+            raise ValueError("pseudobulk adds raw counts: pass the batch over its own gene list (genes=) and a normalize spec (the "
+                             "summed counts are log-normalised against the summed library sizes)")
+        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
+        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
+            raise ValueError("pseudobulk does not take merged columns (duplicates=\"sum\"): merging under pooling is not built")
+        if into is not None and not isinstance(into, Pseudobulk):
+            raise ValueError("into: pass an earlier Pseudobulk")
+        ids, names = _cluster_ids(clusters, cluster_names, n_clusters, into=into,
+                                  n_cells=self._n_cells(expr))
+        if into is not None:
+            into._require_same(names, self.id2label, self.id2gene)
+            if float(self.threshold) > 0:
+                raise ValueError("into: needs a predictor threshold of 0 (entries at or below it were dropped from the profiles)")
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._pseudobulk(expr, genes, spec, ids, names, into)
+
+    def _pseudobulk(self, expr, genes, spec, ids, names, into):
+        dev = self.device
+        (rowptr, col, cnt), _, lib = self._thin_operands(expr, genes, spec)
+        _ops.pair_operand_check(rowptr, cnt, "pseudobulk adds up to 256 cells' counts in a 32-bit partial sum")
+        group = torch.from_numpy(ids.astype(np.int32)).to(dev)
+        seed = None if into is None else (into.rowptr, into.col, into.cnt, torch.from_numpy(np.asarray(into.n_reads, np.int64)).to(dev),
+                                          torch.from_numpy(np.asarray(into.n_cells, np.int64)).to(dev))
+        p_rowptr, p_col, p_val, p_cnt, total, n_cells = _ops.pool_rows(
+            rowptr, col, cnt, lib, group, len(names), scale=float(spec.scale_factor), threshold=float(self.threshold), seed=seed,
+            n_genes=self.n_genes)
+        pred, max_prob, logits, _ = self._classify_on_device(_Aligned((p_rowptr, p_col, p_val)))
+        fields = dict(n_cells=n_cells.cpu().numpy(), n_reads=total.cpu().numpy(), n_genes=np.diff(p_rowptr.cpu().numpy()),
+                      label=pred, max_prob=np.asarray(max_prob, np.float32), logits=logits, rowptr=p_rowptr, col=p_col, val=p_val,
+                      cnt=p_cnt)
+        if into is None:
+            return Pseudobulk(names=list(names), id2label=list(self.id2label), id2gene=list(self.id2gene),
+                              label_map=self._label_names(), **fields)
+        for name, value in fields.items():
+            setattr(into, name, value)
+        return into
+
+    def pseudobulk_file(self, input_file, clusters_file, normalize="lognorm", save_path=None) -> pd.DataFrame:
+        """``pseudobulk`` on a test file of raw counts (its full table and gene names) and a clusters file laid out as
+        ``annotate_file`` takes it (an index column, the cell's name, its cluster's name; the cells in the data file's order,
+        else ``ValueError``): ``Pseudobulk.frame()``, written as ``{species}_{tissue}_pseudobulk.csv`` under ``save_path`` when
+        given.  Cluster names are compared as stripped ``str`` and come in sorted order."""
+        df = _read_expression(input_file, self.file_type)
+        ct = pd.read_csv(clusters_file, index_col=0)
+        if ct.shape[1] != 2:
+            raise ValueError(f"{clusters_file}: expected an index column, the cell names and the cluster names")
+        ct.columns = ['cell', 'cluster']
+        if [str(c) for c in ct['cell']] != [str(c) for c in df.index]:
+            raise ValueError(f"cell order of {input_file} and {clusters_file} differs")
+        out = self.pseudobulk(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns],
+                              [str(c).strip() for c in ct['cluster']], normalize=normalize).frame()
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_pseudobulk.csv", index=False)
         return out
 
     # ---------------------------------------------------------------------------------------------

@@ -75,14 +75,6 @@ __device__ __forceinline__ void put(const MArgs& a, long s, long room, int g, fl
     else bad |= WGNN_ALIGN_BAD_ROWPTR;
 }
 
-// the definition's value of a (merged) count: wgnn_align_rows.h's lognorm with the count already in fp64
-__device__ __forceinline__ float lognorm(double c, double total, double scale) {
-#pragma clang fp contract(off)
-    const double q = c / total;
-    const double y = q * scale;
-    return (float)log1p(y);
-}
-
 // the wave's candidates among the 4 entries per lane it holds (counts c[k]) become their values v[k], every other entry 0:
 // lognorm_group of wgnn_align.hip over a slab of doubles (the value comes back as a double that holds a float exactly)
 __device__ __forceinline__ void lognorm_group(double* slab, int lane, const double (&c)[4], const bool (&cand)[4], float (&v)[4],

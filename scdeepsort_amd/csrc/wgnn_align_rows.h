@@ -23,13 +23,16 @@ __device__ __forceinline__ void add_count(double& acc, float x, unsigned& bad) {
 
 // The log-normalised value of a count: fp64 throughout in Seurat's operation order (divide, scale, log1p), each step rounded on
 // its own.  ONE definition for wgnn_align_count_ln / _fill_ln (and their merging forms) and for wgnn_predict_rows_thin, whose
-// draws at keep == 1 must carry the bits of the aligned batch.
-__device__ __forceinline__ float lognorm(float x, double total, double scale) {
+// draws at keep == 1 must carry the bits of the aligned batch.  The count comes in fp64: wgnn_align_*_ln_merge's merged counts and
+// wgnn_pool_rows_*'s pooled ones (integers up to 2^53, beyond what a float holds) enter here as they are; a float count is widened
+// first, so (double)x is the first step of both forms.
+__device__ __forceinline__ float lognorm(double x, double total, double scale) {
 #pragma clang fp contract(off)
-    const double q = (double)x / total;
+    const double q = x / total;
     const double y = q * scale;
     return (float)log1p(y);
 }
+__device__ __forceinline__ float lognorm(float x, double total, double scale) { return lognorm((double)x, total, scale); }
 
 // Every entry of row r - ALL its columns (CSR: all its stored entries) - handed to visit(j, on, v) in the lane's order of
 // addition: j = the column (dense) or the entry's position in col / val (CSR), on = the lane holds an entry there (else v = 0).

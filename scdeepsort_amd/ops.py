@@ -1094,16 +1094,17 @@ def thin_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, rest: torch.Tens
 PAIR_MAX_COUNT = float(2 ** 23)     # pair_rows adds two counts in float32: exact up to here
 
 
-def pair_operand_check(rowptr: torch.Tensor, raw: torch.Tensor) -> None:
+def pair_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, what: str = "doublets adds two cells' counts in float32") -> None:
     """What ``doublets`` asks of its counts beyond ``thin_operand_check``: none above 2^23, so that the float32 sum of two
-    cells' counts is exact.  One reduction to the first offending cell and one read-back; ``WgnnError`` naming that cell."""
+    cells' counts is exact (``pseudobulk`` asks the same for the 32-bit partial sums of ``pool_rows`` and says so in ``what``).
+    One reduction to the first offending cell and one read-back; ``WgnnError`` naming that cell."""
     B = int(rowptr.shape[0]) - 1
     if B == 0 or not raw.numel():
         return
     rows = torch.repeat_interleave(torch.arange(B, device=raw.device), (rowptr[1:] - rowptr[:-1]).long(), output_size=raw.shape[0])
     first = int(torch.where(raw > PAIR_MAX_COUNT, rows, B).min())
     if first < B:
-        raise WgnnError(f"doublets adds two cells' counts in float32: cell {first} holds a count above 2^23")
+        raise WgnnError(f"{what}: cell {first} holds a count above 2^23")
 
 
 def csr_rows_ascending(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor):
@@ -1182,6 +1183,157 @@ def pair_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     if bits:
         raise WgnnError("pair_rows: " + "; ".join(text for bit, text in _PAIR_STATUS if bits & bit))
     return out_rowptr, out_col, out_val
+
+
+POOL_CHUNK_BYTES = 256 << 20        # pool_rows: the [groups of a chunk, n_genes] uint64 accumulator stays under this
+
+_POOL_STATUS = ((_lib.POOL_BAD_INDEX, "a member names a row outside [0, n_rows)"),
+                (_lib.POOL_BAD_ROWPTR, "rowptr points outside col / cnt, group_ptr is not ascending within [0, n_rows], or a "
+                                       "group kept more entries than were counted"),
+                (_lib.POOL_BAD_COL, "a gene id is outside [0, n_genes)"))
+
+
+def pool_rows_grouped(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, group_ptr: torch.Tensor, members: torch.Tensor,
+                      total: torch.Tensor, n_genes: int, scale: float = 1e4, threshold: float = 0.0, seed=None,
+                      cells_per_unit: int = 0, slab_genes: int = 0, max_bytes: int = POOL_CHUNK_BYTES):
+    """``wgnn_pool_rows_accumulate`` / ``_count`` / ``_fill`` on group lists that are already made - the core of ``pool_rows``,
+    which documents the operands and the result.  ``group_ptr`` int64 [K + 1] (ascending) and ``members`` int32 [B]: the cells of
+    group ``k`` are ``members[group_ptr[k]:group_ptr[k + 1]]`` (``members`` always holds one entry per row, the groups use
+    ``[group_ptr[0], group_ptr[K])`` of them); ``total`` int64 [K]: the pooled library sizes.  ``seed``: ``(rowptr, col, cnt)``
+    of an earlier result over the same K groups, written into the accumulator before the kernel adds to it (``total`` already
+    holds the seed's share).  Returns ``(rowptr int64 [K + 1], col int32, val float32, cnt int64)``."""
+    dev = _require_cuda(rowptr, col, cnt, group_ptr, members, total)
+    if not 0 < float(scale) < float("inf"):
+        raise ValueError(f"pool_rows: scale = {scale} must be positive and finite")
+    if not float(threshold) >= 0:
+        raise ValueError(f"pool_rows: threshold = {threshold} must be >= 0")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
+        raise ValueError("pool_rows takes rowptr int32 / int64, col int32, cnt float32")
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
+        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
+    B, G = int(rowptr.shape[0]) - 1, int(n_genes)
+    if group_ptr.dtype != torch.int64 or group_ptr.dim() != 1 or group_ptr.shape[0] < 1:
+        raise ValueError("pool_rows: group_ptr must be an int64 vector [n_groups + 1]")
+    K = int(group_ptr.shape[0]) - 1
+    if members.dtype != torch.int32 or tuple(members.shape) != (B,):
+        raise ValueError(f"pool_rows: members must be int32 [{B}], one entry per row")
+    if total.dtype != torch.int64 or tuple(total.shape) != (K,):
+        raise ValueError(f"pool_rows: total must be int64 [{K}]")
+    if not 0 <= G < 2 ** 31 or B >= 2 ** 31 or K >= 2 ** 31:
+        raise ValueError("pool_rows: n_genes, the rows and the groups must each be below 2^31")
+    if not 0 <= int(cells_per_unit) <= _lib.POOL_MAX_CELLS_PER_UNIT:
+        raise ValueError(f"pool_rows: cells_per_unit = {cells_per_unit} must be in [0, {_lib.POOL_MAX_CELLS_PER_UNIT}]")
+    if not 0 <= int(slab_genes) <= _lib.POOL_MAX_SLAB_GENES:
+        raise ValueError(f"pool_rows: slab_genes = {slab_genes} must be in [0, {_lib.POOL_MAX_SLAB_GENES}]")
+    if int(max_bytes) < 1:
+        raise ValueError(f"pool_rows: max_bytes = {max_bytes} must be positive")
+    if seed is not None:
+        s_rowptr, s_col, s_cnt = seed
+        _require_cuda(s_rowptr, s_col, s_cnt)
+        if tuple(s_rowptr.shape) != (K + 1,) or s_col.shape != s_cnt.shape or s_col.dim() != 1 or s_cnt.dtype != torch.int64:
+            raise ValueError(f"pool_rows: seed must be an earlier result over the same {K} groups")
+        if s_col.numel() and (int(s_col.min()) < 0 or int(s_col.max()) >= G):
+            raise ValueError(f"pool_rows: seed holds a gene id outside [0, {G})")
+    rowptr, col, cnt, group_ptr, members, total = (t.contiguous() for t in (rowptr, col, cnt, group_ptr, members, total))
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    step = max(1, int(max_bytes) // max(8 * G, 1))
+    parts = []
+    for k0 in range(0, K, step):
+        k1 = min(K, k0 + step)
+        n = k1 - k0
+        acc = torch.zeros((n, G), dtype=torch.int64, device=dev)          # the kernels' uint64: the same bits below 2^63
+        if seed is not None:
+            e0, e1 = int(s_rowptr[k0]), int(s_rowptr[k1])
+            rows = torch.repeat_interleave(torch.arange(n, device=dev), s_rowptr[k0 + 1:k1 + 1] - s_rowptr[k0:k1], output_size=e1 - e0)
+            acc[rows, s_col[e0:e1].long()] = s_cnt[e0:e1]                 # a seeded group's genes are unique: plain stores
+        gp, tot = group_ptr[k0:k1 + 1], total[k0:k1]
+        _lib.check(_lib.call(dev, "wgnn_pool_rows_accumulate", _ptr(rowptr), _ptr(col), _ptr(cnt), B, int(col.shape[0]), _ptr(gp),
+                             _ptr(members), n, G, _ptr(acc), G, int(cells_per_unit), int(slab_genes), _ptr(status), flags,
+                             _stream(dev)), "wgnn_pool_rows_accumulate")
+        head = (_ptr(acc), G, _ptr(tot), n, G, float(scale), float(threshold))
+        n_out = torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.check(_lib.call(dev, "wgnn_pool_rows_count", *head, _ptr(n_out), _ptr(status), _stream(dev)), "wgnn_pool_rows_count")
+        ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(n_out, 0, dtype=torch.int64, out=ptr[1:])
+        kept = int(ptr[-1])                                              # the one read-back that sizes the chunk's outputs
+        out_col = torch.empty(kept, dtype=torch.int32, device=dev)
+        out_val = torch.empty(kept, dtype=torch.float32, device=dev)
+        out_cnt = torch.empty(kept, dtype=torch.int64, device=dev)
+        _lib.check(_lib.call(dev, "wgnn_pool_rows_fill", *head, _ptr(ptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt), _ptr(status),
+                             _stream(dev)), "wgnn_pool_rows_fill")
+        parts.append((n_out, out_col, out_val, out_cnt))
+    bits = int(status)
+    if bits:
+        raise WgnnError("pool_rows: " + "; ".join(text for bit, text in _POOL_STATUS if bits & bit))
+    out_rowptr = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    if parts:
+        torch.cumsum(torch.cat([p[0] for p in parts]), 0, dtype=torch.int64, out=out_rowptr[1:])
+        return (out_rowptr,) + tuple(torch.cat([p[i] for p in parts]) for i in (1, 2, 3))
+    return (out_rowptr, torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+            torch.empty(0, dtype=torch.int64, device=dev))
+
+
+def pool_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: torch.Tensor, group: torch.Tensor, n_groups: int,
+              scale: float = 1e4, threshold: float = 0.0, seed=None, cells_per_unit: int = 0, slab_genes: int = 0,
+              max_bytes: int = POOL_CHUNK_BYTES, n_genes: Optional[int] = None):
+    """``wgnn_pool_rows_accumulate`` / ``_count`` / ``_fill``: the cells of every group pooled into one log-normalised row of
+    their summed counts - pseudobulk profiles.  ``(rowptr int32 / int64 [B+1], col int32, cnt float32)``: a device CSR of raw
+    counts over the bundle's gene ids, every count an integer in [1, 2^23] (``pair_operand_check``); the rows need not be
+    sorted.  ``lib`` int64 [B]: each cell's library size, columns outside the bundle included.  ``group`` int32 [B]: the cell's
+    group in ``[0, n_groups)``, -1 = the cell takes no part.  ``n_genes``: the width of the vocabulary (default: the largest
+    gene id of ``col`` and of ``seed``, plus one - a read-back).
+
+    Group ``k`` leaves, in ascending gene id, ``float32(log1p(float64(c) / total[k] * scale))`` for every gene with
+    ``c`` = the group's summed count ``> 0`` and a value ``> threshold`` (``>= 0``), ``total[k]`` = the group's summed ``lib``
+    (the contract in ``include/wgnn.h``): integer sums, exact, the same bits for any order of the cells, any
+    ``cells_per_unit`` / ``slab_genes`` (the kernel's unit geometry, 0 = its defaults) and any ``max_bytes`` - the groups are
+    processed in chunks whose uint64 ``[groups, n_genes]`` accumulator stays under it.  Returns ``(rowptr int64 [K + 1], col
+    int32, val float32, cnt int64, total int64 [K], n_cells int64 [K])`` on the device; the first three are what
+    ``predict_rows`` takes, ``cnt`` holds the summed count of every kept entry.
+
+    ``seed``: an earlier result's ``(rowptr, col, cnt, total, n_cells)`` over the same groups, made at a threshold that dropped
+    nothing (0): this batch is pooled ON TOP of it - its counts are written into the accumulator before the kernel adds, its
+    totals and cell counts are added - so two halves of a cohort equal the whole, bit for bit.
+
+    A group whose summed library size reaches 2^53 raises ``ValueError`` naming it; a malformed operand the kernels skipped (a
+    ``rowptr`` outside ``col``, a gene id outside ``[0, n_genes)``) raises ``WgnnError``; argument errors are ``ValueError``."""
+    dev = _require_cuda(rowptr, col, cnt, lib, group)
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1:
+        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}")
+    B, K = int(rowptr.shape[0]) - 1, int(n_groups)
+    if K < 0:
+        raise ValueError(f"pool_rows: n_groups = {n_groups} must not be negative")
+    if lib.dtype != torch.int64 or tuple(lib.shape) != (B,):
+        raise ValueError(f"pool_rows: lib must be int64 [{B}]")
+    if group.dtype != torch.int32 or tuple(group.shape) != (B,):
+        raise ValueError(f"pool_rows: group must be int32 [{B}]")
+    if B and (int(group.min()) < -1 or int(group.max()) >= K):
+        raise ValueError(f"pool_rows: group id out of range [-1, {K})")
+    s_total = s_cells = None
+    if seed is not None:
+        if len(seed) != 5:
+            raise ValueError("pool_rows: seed is an earlier result's (rowptr, col, cnt, total, n_cells)")
+        *seed, s_total, s_cells = seed
+        if tuple(s_total.shape) != (K,) or tuple(s_cells.shape) != (K,):
+            raise ValueError(f"pool_rows: seed must be an earlier result over the same {K} groups")
+    if n_genes is None:
+        n_genes = max(int(col.max()) + 1 if col.numel() else 0, int(seed[1].max()) + 1 if seed is not None and seed[1].numel() else 0)
+    # one stable sort: the cells by group, the skipped ones last
+    key = torch.where(group < 0, K, group.long())
+    members = torch.sort(key, stable=True)[1].to(torch.int32)
+    n_cells = torch.bincount(key, minlength=K + 1)[:K]
+    group_ptr = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(n_cells, 0, out=group_ptr[1:])
+    total = torch.zeros(K + 1, dtype=torch.int64, device=dev).index_add_(0, key, lib)[:K].contiguous()      # integer adds: exact
+    if s_total is not None:
+        total, n_cells = total + s_total.to(dev), n_cells + s_cells.to(dev)
+    over = torch.nonzero((total >= 2 ** 53) | (total < 0))
+    if over.numel():
+        raise ValueError(f"pool_rows: group {int(over[0])} pools a library size of 2^53 or more (fp64 no longer holds it exactly)")
+    out = pool_rows_grouped(rowptr, col, cnt, group_ptr, members, total, n_genes, scale, threshold, seed, cells_per_unit,
+                            slab_genes, max_bytes)
+    return out + (total, n_cells)
 
 
 def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
