@@ -947,6 +947,56 @@ int wgnn_pool_rows_fill(const uint64_t* acc, int64_t ld_acc, const int64_t* tota
                         double scale, float threshold, const int64_t* out_rowptr, int32_t* out_col, float* out_val,
                         int64_t* out_cnt, int32_t* status, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Calls on GIVEN gene subsets (additive export, WGNN_VERSION stays 206): the kernel behind api.ResidentPredictor.panels, the
+ * third member of the family of wgnn_predict_rows_dropout (a mask drawn per gene) and wgnn_predict_rows_thin (reads drawn).
+ * One layer of wgnn_predict_rows for every (cell, panel) pair of a batch; no sub-matrix is stored.  Every operand of
+ * wgnn_predict_rows is taken as there (H % 4 == 0, H <= 256, a head of C * H * 4 <= 64 KiB, WGNN_FLAG_ROWPTR_I64); further:
+ *     member   uint64 [n_genes] : bit p of member[g] = gene g belongs to panel p (one 8-byte load beside col[j] answers for
+ *                                 all panels of the launch); bits at or above n_panels are ignored
+ *     n_panels in [1, 64]
+ *     lib      int64 [n_rows, ld_lib] or NULL, ld_lib >= n_panels; with it scale (> 0, finite) and threshold (>= 0)
+ * A pair is (r, p); its row in out, self_rows, logits, label, max_prob and entries is r * n_panels + p.  A deeper model runs
+ * wgnn_linear_fwd between the launches; the mask is applied again in every layer.
+ *
+ * Values mode (lib == NULL).  The kept entries of pair (r, p) are the row's entries whose gene is in panel p, in row order,
+ *   their values as given.
+ * Counts mode (lib != NULL).  raw holds COUNTS; lib[r, p] = the cell's reads inside panel p over ALL the caller's columns
+ *   (the host computes it; panel columns outside the bundle count).  An entry takes part iff its gene is in the panel, its
+ *   count is countable (finite and > 0) and
+ *     v' = float( log1p( double(count) / double(lib[r, p]) * scale ) )  >  threshold
+ *   - the function wgnn_align_count_ln evaluates (one definition in the source, csrc/wgnn_align_rows.h).  lib[r, p] <= 0 gives
+ *   the empty row.
+ * The pair's layer.  The kept / participating entries form a row of wgnn_predict_rows: deg' = their number, S' = their f32
+ *   sum, the same weights, gather, fold order, head, softmax maximum and label rule.  A pair that keeps nothing is the empty
+ *   row, z = bias (+ alpha[G+1] self_rows); where the kept values sum to exactly 0 the weights are selected to 0 and never
+ *   divided.  The arithmetic order is wgnn_predict_rows' on the COMPACTED row (a kept entry's position in the compacted row
+ *   decides its lane in the S' sum and its lane group and step in the gather), so in values mode every pair carries THE BITS
+ *   wgnn_predict_rows leaves on the materialised sub-row (out, logits, label, max_prob), and in counts mode those it leaves
+ *   on wgnn_align_count_ln / _fill_ln of the count matrix with the non-panel columns zeroed.
+ *
+ * Outputs.  Without a head: out [n_rows * n_panels, ld_out] = ReLU(z).  With one: label int32 and max_prob f32
+ * [n_rows, n_panels] (required), logits [n_rows * n_panels, ld_logits] (may be NULL).  In either mode entries int32
+ * [n_rows, n_panels] = deg' (may be NULL).  There are no tallies across panels.
+ *
+ * One workgroup per cell, its 8 waves take the panels; a pair's kept entries sit in a per-wave stash in LDS (1024 entries), of
+ * a pair that outgrows it the tail is tested again.  No atomics of any kind, vector stores only, one addition order whatever
+ * the grid: two launches are bit-identical.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand, member included; n_panels outside [1, 64]; n_rows * n_panels
+ * >= 2^31; with lib: ld_lib < n_panels, scale not positive and finite, threshold < 0 or NaN; a head without label or max_prob;
+ * no head and no out; an unknown flag), WGNN_ERR_ALIGNMENT (H % 4, leading dimensions, pointers - member and lib 8-byte),
+ * WGNN_ERR_UNSUPPORTED (H > 256, a head beyond 64 KiB); wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+int wgnn_predict_rows_panels(const void* rowptr, const int32_t* col, const float* raw, int64_t n_rows,
+                             const float* table, int64_t ld_table, int32_t n_genes, int32_t H,
+                             const float* alpha, const float* bias, const float* self_rows, int64_t ld_self,
+                             const uint64_t* member, int32_t n_panels,
+                             const int64_t* lib, int64_t ld_lib, double scale, float threshold,
+                             float* out, int64_t ld_out,
+                             const float* w_head, const float* b_head, int32_t n_classes, float unsure_threshold,
+                             float* logits, int64_t ld_logits, int32_t* label, float* max_prob, int32_t* entries,
+                             uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

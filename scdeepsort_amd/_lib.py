@@ -88,6 +88,9 @@ SIGNATURES = {
                                          _vp, C.c_double, C.c_float,
                                          _i32, _i64, _i32, C.c_uint64, C.c_double, _vp, _i64,
                                          _vp, _vp, _i32, C.c_float, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_predict_rows_panels": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64,
+                                           _vp, _i32, _vp, _i64, C.c_double, C.c_float, _vp, _i64,
+                                           _vp, _vp, _i32, C.c_float, _vp, _i64, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_align_count": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, _u32, _vp]),
     "wgnn_align_fill": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_align_count_ln": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _i32, C.c_float, _vp, _vp, C.c_double, _vp, _vp,

@@ -1405,6 +1405,188 @@ class Pseudobulk:
             raise ValueError("into: the profiles were pooled over another bundle")
 
 
+def _resolve_panels(panels, without, gene2id: dict, aliases=None, columns=None, column_ids=None):
+    """``ResidentPredictor.panels``' specifications as membership tables: ``(names, complement bool [P], member_genes bool
+    [P, G], member_cols bool [P, n_cols] | None, missing)``.  ``panels`` maps a name to the gene names to keep, ``without`` a name
+    to those to remove (its panel is the complement); the order is ``panels`` first, then ``without``.  Gene names are compared
+    as ``str``; a name that is no bundle gene is looked up in ``aliases`` (caller name -> bundle gene name), as
+    ``_resolve_genes`` does.  ``column_ids`` (int [n_cols], a column's bundle gene or -1): the batch is over the caller's own
+    columns, ``columns`` their names when the caller gave names - a gene name then hits the columns of that very name and the
+    columns of the bundle gene it resolves to; the complement is taken over the caller's columns, and a bundle gene belongs to a
+    panel iff one of the panel's columns maps to it.  Without ``column_ids`` names resolve against the bundle vocabulary.  A
+    name that resolves nowhere is collected in ``missing[panel]``, in the order given.  ValueError: no panel at all, a panel
+    name used twice."""
+    specs = [(str(k), v, False) for k, v in (panels or {}).items()] + [(str(k), v, True) for k, v in (without or {}).items()]
+    if not specs:
+        raise ValueError("panels: pass at least one panel (panels={name: genes to keep}) or one set to remove (without=)")
+    names = [s[0] for s in specs]
+    twice = sorted({n for n in names if names.count(n) > 1})
+    if twice:
+        raise ValueError(f"panels: the name {twice[0]!r} is used twice (names are unique across panels= and without=)")
+    alias = {str(k): str(v) for k, v in aliases.items()} if aliases else {}
+    G, P = len(gene2id), len(specs)
+
+    def bundle_id(name):
+        i = gene2id.get(name, -1)
+        return gene2id.get(alias[name], -1) if i < 0 and name in alias else i
+
+    member_cols = cols_of_name = cols_of_gene = None
+    if column_ids is not None:
+        column_ids = np.asarray(column_ids, np.int64)
+        member_cols = np.zeros((P, column_ids.shape[0]), bool)
+        cols_of_name, cols_of_gene = {}, {}
+        for j, g in enumerate(column_ids.tolist()):
+            if g >= 0:
+                cols_of_gene.setdefault(g, []).append(j)
+        for j, c in enumerate(columns if columns is not None else ()):
+            cols_of_name.setdefault(str(c), []).append(j)
+    member_genes = np.zeros((P, G), bool)
+    missing = {}
+    for p, (name, gene_names, complement) in enumerate(specs):
+        if isinstance(gene_names, (str, bytes)):
+            raise ValueError(f"panels: {name!r} must list gene names, got one string")
+        lost = []
+        for g in gene_names:
+            g = str(g)
+            gid = bundle_id(g)
+            if column_ids is None:
+                if gid >= 0:
+                    member_genes[p, gid] = True
+                else:
+                    lost.append(g)
+                continue
+            hit = cols_of_name.get(g, []) + (cols_of_gene.get(gid, []) if gid >= 0 else [])
+            if hit:
+                member_cols[p, hit] = True
+            else:
+                lost.append(g)
+        missing[name] = lost
+        if complement:
+            if column_ids is None:
+                member_genes[p] = ~member_genes[p]
+            else:
+                member_cols[p] = ~member_cols[p]
+        if column_ids is not None:
+            on = column_ids[member_cols[p]]
+            member_genes[p, on[on >= 0]] = True
+    return names, np.array([s[2] for s in specs], bool), member_genes, member_cols, missing
+
+
+def _member_words(member_genes: np.ndarray) -> np.ndarray:
+    """bool [P <= 64, G] -> the membership words of ``wgnn_predict_rows_panels`` as int64 [G]: bit ``p`` of word ``g`` = gene
+    ``g`` belongs to panel ``p``."""
+    P = member_genes.shape[0]
+    shifted = member_genes.astype(np.uint64) << np.arange(P, dtype=np.uint64)[:, None]
+    return np.bitwise_or.reduce(shifted, axis=0).view(np.int64)
+
+
+class PanelSummary(dict):
+    """``PanelCalls.summary()``: a dict that prints as one line per panel."""
+
+    def __str__(self) -> str:
+        d = self
+        lines = [f"{d['n_cells']} cells ({d['n_called']} with a call), {len(d['names'])} panels"
+                 + (", re-normalised per panel" if d["renormalize"] else "")]
+        for name, n, a, lost, miss in zip(d["names"], d["n_genes"], d["agreement"], d["n_lost_types"], d["n_missing"]):
+            lines.append(f"{name}: {n} bundle genes, agreement {a:.3f}, {lost} types below {d['min_agreement']:g} retained"
+                         + (f", {miss} names not found" if miss else ""))
+        return "\n".join(lines)
+
+
+@dataclass
+class PanelCalls:
+    """What ``ResidentPredictor.panels`` returns: per cell, its call when only a NAMED set of genes is measured.  B cells
+    (``index``), C cell types (``id2label``), P panels (``names``, ``panels=`` first, then ``without=``), all small host tables.
+    ``missing[name]``: the gene names of that panel that resolved nowhere; ``n_genes`` int64 [P]: a panel's bundle genes;
+    ``n_columns`` int64 [P]: its caller columns (``None`` without ``genes=``).  ``label`` int64 [B] / ``max_prob`` f32 [B]: the
+    call on the cell as given (``classify``'s, -1 = unsure).  ``panel_label`` int64 [B, P] / ``panel_prob`` f32 [B, P]: the call
+    on the panel's genes alone; ``n_entries`` int64 [B, P]: the cell's entries that took part; ``n_reads`` int64 [B, P]: the
+    cell's reads inside the panel, its library size there (``renormalize=True`` only, else ``None``)."""
+    names: List[str]
+    missing: dict
+    n_genes: np.ndarray
+    n_columns: Optional[np.ndarray]
+    label: np.ndarray
+    max_prob: np.ndarray
+    panel_label: np.ndarray
+    panel_prob: np.ndarray
+    n_entries: np.ndarray
+    n_reads: Optional[np.ndarray]
+    index: Sequence
+    id2label: Sequence[str]
+    renormalize: bool = False
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def _panel(self, name) -> int:
+        if name not in self.names:
+            raise ValueError(f"no panel {name!r}: the panels are {', '.join(map(repr, self.names))}")
+        return list(self.names).index(name)
+
+    def agreement(self) -> np.ndarray:
+        """f64 [P]: the share of the cells with a full call (``label != -1``) whose panel call equals it (NaN without one)."""
+        lab = np.asarray(self.label, np.int64)
+        called = lab >= 0
+        same = np.asarray(self.panel_label, np.int64)[called] == lab[called, None]
+        return same.mean(axis=0) if called.any() else np.full(len(self.names), np.nan)
+
+    def confusion(self, name) -> np.ndarray:
+        """int64 [C + 1, C + 1]: cells by full call (rows) and the call on panel ``name`` (columns), the last index = unsure."""
+        C = len(self.id2label)
+        full = np.asarray(self.label, np.int64)
+        sub = np.asarray(self.panel_label, np.int64)[:, self._panel(name)]
+        full, sub = np.where(full >= 0, full, C), np.where(sub >= 0, sub, C)
+        return np.bincount(full * (C + 1) + sub, minlength=(C + 1) ** 2).reshape(C + 1, C + 1).astype(np.int64)
+
+    def by_type(self) -> pd.DataFrame:
+        """One row per (panel, cell type that holds a cell's full call): ``panel``, ``cell_type`` (named as ``predict`` names
+        it), ``n_cells``, ``retained`` (the share whose panel call is the same type), ``unsure`` (the share the panel leaves
+        unsure), ``other`` (the other type most of them become, the lower id among equals, ``None`` without one) and
+        ``other_share``."""
+        C = len(self.id2label)
+        rows = {k: [] for k in ("panel", "cell_type", "n_cells", "retained", "unsure", "other", "other_share")}
+        for name in self.names:
+            conf = self.confusion(name)
+            for t in np.flatnonzero(conf[:C].sum(axis=1)):
+                n = int(conf[t].sum())
+                others = conf[t, :C].copy()
+                others[t] = 0
+                o = int(others.argmax()) if C else 0
+                rows["panel"].append(name); rows["cell_type"].append(int(t)); rows["n_cells"].append(n)
+                rows["retained"].append(conf[t, t] / n); rows["unsure"].append(conf[t, C] / n)
+                rows["other"].append(o if C and others[o] > 0 else -3); rows["other_share"].append(others[o] / n if C else 0.0)
+        rows["cell_type"] = _call_names(rows["cell_type"], self.id2label, self.label_map)[0]
+        rows["other"] = _call_names(rows["other"], self.id2label, self.label_map)[0]
+        return pd.DataFrame(rows)
+
+    def lost(self, min_agreement: float = 0.9) -> pd.DataFrame:
+        """The rows of ``by_type()`` whose ``retained`` is below ``min_agreement``: the cell types a panel does not carry."""
+        t = self.by_type()
+        return t[t["retained"] < float(min_agreement)].reset_index(drop=True)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` (named as ``predict`` names it), ``prob`` (the full call's), then per panel
+        ``call_{name}``, ``prob_{name}``, ``entries_{name}`` (and ``reads_{name}`` under ``renormalize``)."""
+        out = {"index": list(self.index), "cell_type": _call_names(np.asarray(self.label, np.int64), self.id2label, self.label_map)[0],
+               "prob": np.asarray(self.max_prob)}
+        for p, name in enumerate(self.names):
+            out[f"call_{name}"] = _call_names(np.asarray(self.panel_label, np.int64)[:, p], self.id2label, self.label_map)[0]
+            out[f"prob_{name}"] = np.asarray(self.panel_prob)[:, p]
+            out[f"entries_{name}"] = np.asarray(self.n_entries)[:, p]
+            if self.n_reads is not None:
+                out[f"reads_{name}"] = np.asarray(self.n_reads)[:, p]
+        return pd.DataFrame(out)
+
+    def summary(self, min_agreement: float = 0.9) -> PanelSummary:
+        """Per panel its bundle genes, ``agreement()``, the number of ``lost(min_agreement)`` cell types and of names that were
+        not found; ``print`` it."""
+        lost = self.lost(min_agreement)
+        return PanelSummary(n_cells=int(len(self.label)), n_called=int((np.asarray(self.label) >= 0).sum()), names=list(self.names),
+                            renormalize=bool(self.renormalize), n_genes=[int(n) for n in self.n_genes],
+                            agreement=[float(a) for a in self.agreement()], min_agreement=float(min_agreement),
+                            n_lost_types=[int((lost["panel"] == n).sum()) for n in self.names],
+                            n_missing=[len(self.missing.get(n, ())) for n in self.names])
+
+
 @dataclass(frozen=True)
 class LogNormalize:
     """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
@@ -1974,6 +2156,158 @@ class ResidentPredictor:
         if save_path is not None:
             Path(save_path).mkdir(parents=True, exist_ok=True)
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_stability.csv", index=False)
+        return out
+
+    # ---------------------------------------------------------------------------------------------
+    def panels(self, expr, panels=None, without=None, genes=None, normalize=None, renormalize: bool = False,
+               index=None) -> PanelCalls:
+        """Would the call survive when only a KNOWN, NAMED set of genes is measured?  The batch is classified once as given
+        (``classify``'s call, bit for bit), then every cell is re-classified once per panel on the panel's genes alone - every
+        layer in one launch per 64 panels (``wgnn_predict_rows_panels``), no masked matrix is built - into a ``PanelCalls``:
+        ``agreement`` / ``by_type`` / ``confusion`` / ``lost`` / ``frame`` / ``summary`` on top.  ``expr``, ``genes`` and
+        ``normalize`` as for ``classify``; ``index``: the cells' names (default ``range(B)``).
+
+        ``panels`` maps a panel's name to the gene names to KEEP (a targeted assay: a probe panel, a qPCR set); ``without`` maps
+        a name to the gene names to REMOVE (a confounder set: mitochondrial, ribosomal, cell-cycle genes - the panel is the
+        complement).  At least one is needed, names are unique across both, the order is ``panels`` first.  With ``genes=`` given
+        as names the gene names resolve against the caller's columns, else against the bundle's vocabulary; they are compared as
+        ``str`` and go through the predictor's ``aliases``.  A name that resolves nowhere is no error: ``PanelCalls.missing``
+        collects it.
+
+        ``renormalize=False`` (the default) is the confounder question: the values as the model was given them, some genes taken
+        away; a panel's call carries the bits of ``classify`` on the batch with the other columns removed.
+        ``renormalize=True`` is the targeted-assay question: the batch holds raw integer COUNTS (``genes=`` and a ``normalize``
+        spec are required, else ``ValueError``), a panel's library size is the cell's counts over the panel's columns of the
+        CALLER's list, in the bundle or not, and the counts are log-normalised against it inside the kernel - the bits of
+        ``classify(counts with the other columns zeroed, genes, normalize)``.  ``LogNormalize(library_size=)`` and merged
+        columns (``duplicates="sum"``) raise ``ValueError``; a count that is no integer in [1, 2^24] raises ``WgnnError``.
+
+        Cells are chunked so that the ``[cells x panels, H]`` intermediates of a deeper model stay under
+        ``STABILITY_CHUNK_BYTES``.  The panels run on the fused kernels only: a bundle they cannot serve (hidden width above 256)
+        raises ValueError, there is no graph route.  Argument errors are ValueError before anything is launched."""
+        by_name = genes is not None and not isinstance(genes, (torch.Tensor, GeneMap))
+        spec = None
+        if renormalize:
+            spec = self.normalize if normalize is None else _normalize_spec(normalize)
+            if genes is None or spec is None:
+                raise ValueError("renormalize=True re-normalises raw counts per panel: pass the batch over its own gene list (genes=) "
+                                 "and a normalize spec")
+            if spec.library_size is not None:
+                raise ValueError("renormalize=True takes a panel's own reads as its library size: LogNormalize(library_size=) does "
+                                 "not apply")
+            if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
+                raise ValueError("renormalize=True does not take merged columns (duplicates=\"sum\"): merging under panels is not built")
+        B = self._n_cells(expr)
+        if index is not None and len(index) != B:
+            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        if self.hidden_padded > 256 or self.n_classes * self.hidden_padded * 4 > _ops.HEAD_LDS_BYTES:
+            raise ValueError(f"panels runs on the fused kernels only (hidden width <= 256, head <= {_ops.HEAD_LDS_BYTES} bytes); "
+                             f"this bundle has hidden width {self.hidden_padded} and {self.n_classes} cell types")
+        column_ids = columns = None
+        if genes is not None:
+            if by_name:                                    # resolved once: the map goes on to align in place of the names
+                columns = [str(g) for g in genes]
+                ids, groups = _resolve_genes(columns, self._gene2id, self.aliases, self.duplicates)
+                column_ids = ids
+            else:
+                ids = genes.ids if isinstance(genes, GeneMap) else genes
+                column_ids = ids.detach().cpu().numpy()
+        names, _, member_genes, member_cols, missing = _resolve_panels(panels, without, self._gene2id, self.aliases, columns, column_ids)
+        if by_name:
+            if self.duplicates == "sum" and (self.normalize if normalize is None else _normalize_spec(normalize)) is None:
+                raise ValueError("duplicates=\"sum\" needs normalize=: the batch then holds log-values (see align)")
+            genes = torch.from_numpy(ids).to(self.device) if groups is None else self.gene_map(columns, self.aliases, self.duplicates)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._panels(expr, genes, normalize, spec, names, member_genes, member_cols, missing, index)
+
+    def _panel_reads(self, batch, member_cols: np.ndarray) -> torch.Tensor:
+        """int64 [B, P]: a cell's counts summed over each panel's columns of the caller's list.  Integer sums in fp64 are exact
+        whatever their order; the rows (dense) or the entries (CSR) are taken in slices that keep the fp64 operand small."""
+        dev = self.device
+        M = torch.from_numpy(np.ascontiguousarray(member_cols.T)).to(dev).to(torch.float64)          # [n_cols, P]
+        n_cols, P = M.shape
+        budget = 64 * 1024 * 1024 // 8
+        if isinstance(batch, torch.Tensor):
+            B = int(batch.shape[0])
+            lib = torch.empty((B, P), dtype=torch.float64, device=dev)
+            step = max(1, budget // max(n_cols, 1))
+            for r0 in range(0, B, step):
+                lib[r0:r0 + step] = batch[r0:r0 + step].to(torch.float64) @ M
+            return lib.to(torch.int64)
+        rowptr, col, val = batch
+        B = int(rowptr.shape[0]) - 1
+        lib = torch.zeros((B, P), dtype=torch.float64, device=dev)
+        rows = torch.repeat_interleave(torch.arange(B, device=dev), (rowptr[1:] - rowptr[:-1]).long(), output_size=int(col.shape[0]))
+        step = max(1, budget // P)
+        for e0 in range(0, int(col.shape[0]), step):
+            sl = slice(e0, e0 + step)
+            lib.index_add_(0, rows[sl], M[col[sl].long()] * val[sl].to(torch.float64)[:, None])
+        return lib.to(torch.int64)
+
+    def _panels(self, expr, genes, normalize, spec, names, member_genes, member_cols, missing, index):
+        dev = self.device
+        lib = None
+        if spec is not None:                               # renormalize: the panels run on the counts, the full call on the values
+            batch, gmap, _ = self._caller_batch(expr, genes)           # on the device once, for the three walks below
+            (rowptr, col, raw), _, _ = self._thin_operands(batch, gmap, spec)
+            lib = self._panel_reads(batch, member_cols)
+            pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(batch, gmap, None, spec)))
+            mode_kw = dict(scale=float(spec.scale_factor), threshold=float(self.threshold))
+        else:
+            rowptr, col, raw, checked, _ = self._device_csr(self._over_genes(expr, genes, normalize))
+            if not checked:                                # once for the whole call: every launch below skips the check
+                _ops.check_gene_ids(col, self.n_genes)
+            pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
+            mode_kw = {}
+        B, P, Hp = int(rowptr.shape[0]) - 1, len(names), self.hidden_padded
+        label = torch.empty((B, P), dtype=torch.int32, device=dev)
+        prob = torch.empty((B, P), dtype=torch.float32, device=dev)
+        entries = torch.empty((B, P), dtype=torch.int32, device=dev)
+        for p0 in range(0, P, _ops.PANELS_PER_LAUNCH):
+            p1 = min(P, p0 + _ops.PANELS_PER_LAUNCH)
+            n_p = p1 - p0
+            member = torch.from_numpy(_member_words(member_genes[p0:p1])).to(dev)
+            # cells per launch: the [cells x panels, Hp] f32 intermediates of a deeper model (h, its self rows, the next h) under
+            # the budget, as _stability chunks its draws
+            per_cell = n_p * Hp * 4 * (3 if self.n_layers > 1 else 0)
+            step = (2 ** 31 - 1) // n_p if per_cell == 0 else max(1, min(STABILITY_CHUNK_BYTES // per_cell, (2 ** 31 - 1) // n_p))
+            for r0 in range(0, B, step):
+                r1 = min(B, r0 + step)
+                rp = rowptr[r0:r1 + 1]
+                kw = dict(check_cols=False, lib=None if lib is None else lib[r0:r1, p0:p1], **mode_kw)
+                h = None
+                for l in range(self.n_layers):
+                    self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
+                    if l < self.n_layers - 1:
+                        h = _ops.predict_rows_panels(rp, col, raw, self.tables[l], self.alpha, self.biases[l], member, n_p,
+                                                     self_rows=self_rows, **kw)
+                    else:
+                        _, lab, mp, ent = _ops.predict_rows_panels(
+                            rp, col, raw, self.tables[l], self.alpha, self.biases[l], member, n_p, self_rows=self_rows,
+                            head=(self.w_head, self.b_head), unsure_threshold=self.unsure_threshold, want_entries=True, **kw)
+                        label[r0:r1, p0:p1], prob[r0:r1, p0:p1], entries[r0:r1, p0:p1] = lab, mp, ent
+        return PanelCalls(names=names, missing=missing, n_genes=member_genes.sum(axis=1).astype(np.int64),
+                          n_columns=None if member_cols is None else member_cols.sum(axis=1).astype(np.int64),
+                          label=pred, max_prob=np.asarray(max_prob, np.float32),
+                          panel_label=label.cpu().numpy().astype(np.int64), panel_prob=prob.cpu().numpy(),
+                          n_entries=entries.cpu().numpy().astype(np.int64),
+                          n_reads=None if lib is None else lib.cpu().numpy(),
+                          index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label),
+                          renormalize=spec is not None, label_map=self._label_names())
+
+    def panels_file(self, input_file, panels=None, without=None, normalize=None, renormalize: bool = False,
+                    save_path=None) -> pd.DataFrame:
+        """``panels`` on a test file - its full table, its gene names as ``genes=`` and its cell names: ``PanelCalls.by_type()``,
+        written as ``{species}_{tissue}_panels.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``;
+        ``renormalize=True``: the file holds raw counts (a ``normalize`` spec is required)."""
+        if renormalize and (self.normalize if normalize is None else _normalize_spec(normalize)) is None:
+            raise ValueError("renormalize=True re-normalises raw counts per panel: the file needs a normalize spec")
+        df = _read_expression(input_file, self.file_type)
+        out = self.panels(df.to_numpy(dtype=np.float32), panels=panels, without=without, genes=[str(c) for c in df.columns],
+                          normalize=normalize, renormalize=renormalize, index=df.index).by_type()
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_panels.csv", index=False)
         return out
 
     # ---------------------------------------------------------------------------------------------

@@ -1071,6 +1071,77 @@ def predict_rows_thin(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor
                                row0, draw0, out, accumulate, want_draws)
 
 
+PANELS_PER_LAUNCH = 64              # bits of a ``member`` word (include/wgnn.h)
+
+
+def predict_rows_panels(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
+                        bias: torch.Tensor, member: torch.Tensor, n_panels: int, *, lib: Optional[torch.Tensor] = None,
+                        scale: float = 1e4, threshold: float = 0.0, self_rows: Optional[torch.Tensor] = None,
+                        head: Optional[tuple] = None, unsure_threshold: float = 0.0, want_logits: bool = False,
+                        want_entries: bool = False, check_cols: bool = True, out=None):
+    """``wgnn_predict_rows_panels``: one layer of ``predict_rows`` for every (cell, panel) pair of a batch, a panel being a GIVEN
+    subset of the genes.  ``member`` int64 [G] holds the uint64 membership words: bit ``p`` of ``member[g]`` says that gene ``g``
+    belongs to panel ``p`` (``n_panels`` in [1, 64]; higher bits are ignored).  The batch, the table, ``alpha``, ``bias``,
+    ``head``, ``unsure_threshold`` and ``check_cols`` as ``predict_rows`` takes them.  ``self_rows`` [B * n_panels, H]: row
+    ``r * n_panels + p`` belongs to panel ``p`` of cell ``r``.
+
+    ``lib`` None (values mode): a pair keeps the row's entries whose gene is in the panel, values as given, and carries the
+    bits of ``predict_rows`` on that sub-row.  ``lib`` int64 [B, n_panels] (counts mode; may be a view with a wider row
+    stride): ``raw`` holds counts, ``lib[r, p]`` the cell's reads inside the panel over all of the caller's columns; the kept
+    counts are log-normalised against it (``scale``, and ``threshold`` on the normalised value, as
+    ``align_rows(normalize="lognorm")`` takes them) - the bits of ``predict_rows`` on the lognorm-aligned count matrix with
+    the other columns zeroed.  ``lib[r, p] <= 0`` is the empty row.
+
+    Without ``head`` returns ``ReLU(z)`` [B * n_panels, H] (``out``: a float32 [B * n_panels, Hp] buffer to write into).  With
+    ``head = (w_head [C, H], b_head [C])`` returns ``(logits [B * n_panels, C] | None, label int32 [B, n_panels], max_prob f32
+    [B, n_panels])``.  ``want_entries``: the pairs' kept entries, int32 [B, n_panels], appended to the return value (without a
+    head: ``(out, entries)``).  There is no GEMM route for a head beyond what the kernel stages in LDS.  CPU tensors are
+    refused; argument errors are ``ValueError``."""
+    name, exc = "predict_rows_panels", ValueError
+    dev = _require_cuda(rowptr, col, raw, table, alpha, bias, member, lib, self_rows, *(head or ()))
+    P = int(n_panels)
+    if not 1 <= P <= PANELS_PER_LAUNCH:
+        raise exc(f"{name}: n_panels = {P} must be in [1, {PANELS_PER_LAUNCH}] (split the panels)")
+    if lib is not None and not 0 < float(scale) < float("inf"):
+        raise exc(f"{name}: scale = {scale} must be positive and finite")
+    if lib is not None and not float(threshold) >= 0:
+        raise exc(f"{name}: threshold = {threshold} must be >= 0")
+    H = bias.shape[0]
+    o = _row_operands(name, rowptr, col, raw, table, alpha, H, check_cols)
+    B, Hp = o.B, o.Hp
+    if member.dtype != torch.int64 or tuple(member.shape) != (o.G,):
+        raise exc(f"{name}: member must be int64 [{o.G}] (the uint64 membership words)")
+    member = member.contiguous()
+    if lib is not None:
+        if lib.dtype != torch.int64 or tuple(lib.shape) != (B, P) or (P > 1 and lib.stride(1) != 1) or (B > 1 and lib.stride(0) < P):
+            raise exc(f"{name}: lib must be int64 [{B}, {P}] with unit column stride and a row stride >= {P}")
+    if B * P >= 2 ** 31:
+        raise exc(f"{name}: B * n_panels >= 2^31 (split the batch or the panels)")
+    bias = _pad_cols(bias, Hp)
+    self_rows = _self_rows(self_rows, B * P, f"{B} cells x {P} panels", H, Hp, exc)
+    ld_lib = (int(lib.stride(0)) if B > 1 else max(int(lib.stride(0)), P)) if lib is not None else 0
+    lead = (*o.c_args, _ptr(bias), _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
+            _ptr(member), P, _ptr(lib), ld_lib, float(scale), float(threshold))
+    entries = torch.empty((B, P), dtype=torch.int32, device=dev) if want_entries else None
+    if head is None:
+        out = _headless_out(out, B * P, Hp, dev, exc)
+        rc = _lib.call(dev, "wgnn_" + name, *lead, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
+                       None, None, 0, 0.0, None, 0, None, None, _ptr(entries), o.flags, _stream(dev))
+        _lib.check(rc, "wgnn_" + name)
+        h = out if Hp == H else out[:, :H]
+        return (h, entries) if want_entries else h
+    w_head, b_head, n_cls = _fused_head(
+        head, Hp, lambda c: exc(f"{name}: a [{c}, {Hp}] head is beyond the {HEAD_LDS_BYTES} bytes the kernel stages"))
+    logits = torch.empty((B * P, n_cls), dtype=torch.float32, device=dev) if want_logits else None
+    label = torch.empty((B, P), dtype=torch.int32, device=dev)
+    max_prob = torch.empty((B, P), dtype=torch.float32, device=dev)
+    rc = _lib.call(dev, "wgnn_" + name, *lead, None, 0, _ptr(w_head), _ptr(b_head), n_cls, float(unsure_threshold),
+                   _ptr(logits), n_cls if logits is not None else 0, _ptr(label), _ptr(max_prob), _ptr(entries), o.flags,
+                   _stream(dev))
+    _lib.check(rc, "wgnn_" + name)
+    return (logits, label, max_prob, entries) if want_entries else (logits, label, max_prob)
+
+
 def thin_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, rest: torch.Tensor, total: torch.Tensor) -> None:
     """The one fused device check ``stability(thin="reads")`` makes of its operand: every count of ``raw`` an integer in
     [1, 2^24], every ``rest`` (float64 [B], exact) a non-negative integer, every cell's ``total`` below 2^31.  One reduction to
