@@ -948,6 +948,76 @@ int wgnn_pool_rows_fill(const uint64_t* acc, int64_t ld_acc, const int64_t* tota
                         int64_t* out_cnt, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Soup rows (additive exports, WGNN_VERSION stays 206): a cell's COUNT row with reads of AMBIENT RNA - the "soup", free-floating
+ * transcripts every droplet captures besides its cell - drawn from a batch-wide profile and added to it, and the contaminated row
+ * log-normalised against the contaminated library size: the operand of api.ResidentPredictor.ambient.  The scheme is
+ * wgnn_pair_rows_*'s: count, the caller's exclusive scan, fill; the output is a CSR that wgnn_predict_rows takes unchanged.
+ * Operand: a bundle-vocabulary CSR of raw counts - rowptr [n_rows + 1] (int32, or int64 with WGNN_FLAG_ROWPTR_I64), col int32,
+ * cnt f32, nnz = the length of col / cnt.  Every count is an integer in [1, 2^23] (the caller's check; any other value is left
+ * out without a word, as in pool rows).  Rows need NOT be sorted, and a gene listed twice in a row adds twice (a gene's summed
+ * count stays below 2^32).  lib int64 [n_rows]: a cell's library size, ALL its reads, those in columns outside the bundle
+ * included.  n_add int64 [n_rows]: the soup reads added to the cell, each in [0, 2^23] (the caller makes it of its contamination
+ * level).  cdf uint64 [n_genes + 2], ascending, cdf[0] = 0: the soup profile as cumulative weights - bin g < n_genes is bundle
+ * gene g, bin n_genes is "a column outside the bundle", W = cdf[n_genes + 1] with 0 < W < 2^63.  n_draws >= 1; row0, draw0 >= 0;
+ * seed; scale > 0 (Seurat's scale.factor), threshold >= 0.
+ *
+ * Unit q = r * n_draws + d is cell r, draw d.  With key and mix64 of the dropout block and K_READ of the thinning block, in
+ * uint64 with wrap-around:
+ *
+ *   sk   = mix64(key(seed, row0 + r, draw0 + d) + K_SOUP)       K_SOUP = 0x94D049BB133111EB (a stream of its own)
+ *   u_t  = mix64(sk + t * K_READ)                                t in [0, n_add[r])
+ *   x_t  = the high 64 bits of the 128-bit product u_t * W       (exact, in [0, W))
+ *   bin_t = the k with cdf[k] <= x_t < cdf[k + 1]                (a bin of width zero is never drawn)
+ *   s(g) = #{t : bin_t == g},  s_rest = #{t : bin_t == n_genes}
+ *   c(g) = cnt_r(g) + s(g);    total = double(lib[r] + n_add[r])
+ *   v    = float( log1p( double(c) / total * scale ) )           - lognorm() of csrc/wgnn_align_rows.h in its form that takes the
+ *                                                                  count as a double, the ONE definition, as pool rows
+ *   the entry (g, v) leaves  iff  c > 0 && v > threshold;  entries leave in ascending g;  total <= 0 gives the empty row.
+ *
+ * Pure consequences of the hash: s is Multinomial(n_add, widths / W) up to the 2^-64 grain of x_t; the result does not depend
+ * on the order of a cell's genes; levels are NESTED - read t is the same read at every n_add that reaches it, so the reads added
+ * at a contamination of 5 % are a subset of those added at 10 %; row0 / draw0 split a batch by cells (rowptr + r0, lib + r0,
+ * n_add + r0, row0 = r0) or by draws without changing a bit; n_add == 0 gives the bits wgnn_align_count_ln / _fill_ln leave on
+ * the cell's own row.  So a unit carries THE BITS of the aligned, log-normalised, host-materialised contaminated count row (one
+ * more column holding lib - sum(cnt) + s_rest).
+ *   wgnn_soup_rows_count: n_out int32 [n_rows * n_draws] = the entries unit q leaves; soup_mapped int32 [n_rows * n_draws] (may be
+ *                         NULL) = n_add - s_rest, the soup reads that fell on bundle genes.
+ *   wgnn_soup_rows_fill : out_rowptr int64 [n_rows * n_draws + 1] = the exclusive scan of n_out (the caller's), out_col int32,
+ *                         out_val f32 and - may be NULL - out_cnt int64 [out_rowptr[n_rows * n_draws]]: gene, value and c of
+ *                         every kept entry.
+ * One workgroup per unit (grid-stride).  The genes are cut into slabs of slab_genes (0 = the default, 16384: 64 KiB of uint32, two
+ * workgroups per CU; at most 16384; never wider than n_genes); per slab the workgroup zeroes a uint32 LDS slab, adds the cell's own
+ * entries and the unit's reads with LDS integer atomics (what lies outside the slab is skipped by comparison, so every further
+ * slab hashes the reads again) and sweeps the slab 64 genes per wave step; wave ballots give the slots.  A read's bin is searched
+ * in two levels: a table of every 2^sh-th boundary of cdf in LDS (sh >= 6, at most 512 entries), then sh probes of cdf itself.
+ * COUNT and FILL are the same walk, so they agree on every decision.  All sums are integers: exact whatever the order, two
+ * launches are bit-identical.  No floating-point atomics, no global atomics on the data path, vector stores only.
+ * Malformed operands never fault; each ORs its bit into *status (int32, device memory, zeroed by the caller; required): a row
+ * range outside [0, nnz] (the unit leaves the empty row) or a slot at or past out_rowptr[q + 1] (not written; with out_col or
+ * out_val NULL every slot is such a slot), WGNN_SOUP_BAD_ROWPTR; a gene id outside [0, n_genes) (the entry is skipped),
+ * WGNN_SOUP_BAD_COL; an n_add outside [0, 2^23] (the unit is treated as 0 reads), WGNN_SOUP_BAD_ADD.  A cdf that is not
+ * ascending gives unspecified draws, but every read stays inside the operands.
+ * n_rows, n_rows * n_draws < 2^31, n_genes < 2^31 - 1.  n_rows = 0 is a valid no-op.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (status NULL, a missing operand or output, a negative size, a size >= 2^31,
+ * n_rows * n_draws >= 2^31, n_draws < 1, row0 or draw0 negative, scale not positive and finite, threshold < 0 or NaN, slab_genes
+ * outside [0, 16384], an unknown flag), WGNN_ERR_ALIGNMENT (lib / n_add / cdf / out_rowptr / out_cnt / an int64 rowptr not
+ * 8-byte, any other operand not 4-byte aligned); wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+#define WGNN_SOUP_BAD_ROWPTR 1   /* status bit: a row range outside [0, nnz], or out_rowptr left a unit less room */
+#define WGNN_SOUP_BAD_COL    2   /* status bit: a gene id was outside [0, n_genes)                                */
+#define WGNN_SOUP_BAD_ADD    4   /* status bit: an n_add was outside [0, 2^23]                                    */
+#define WGNN_SOUP_MAX_SLAB_GENES 16384
+int wgnn_soup_rows_count(const void* rowptr, const int32_t* col, const float* cnt, int64_t n_rows, int64_t nnz,
+                         const int64_t* lib, const int64_t* n_add, const uint64_t* cdf, int32_t n_genes, int32_t n_draws,
+                         int64_t row0, int32_t draw0, uint64_t seed, double scale, float threshold, int32_t slab_genes,
+                         int32_t* n_out, int32_t* soup_mapped, int32_t* status, uint32_t flags, void* stream);
+int wgnn_soup_rows_fill(const void* rowptr, const int32_t* col, const float* cnt, int64_t n_rows, int64_t nnz,
+                        const int64_t* lib, const int64_t* n_add, const uint64_t* cdf, int32_t n_genes, int32_t n_draws,
+                        int64_t row0, int32_t draw0, uint64_t seed, double scale, float threshold, int32_t slab_genes,
+                        const int64_t* out_rowptr, int32_t* out_col, float* out_val, int64_t* out_cnt, int32_t* status,
+                        uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Calls on GIVEN gene subsets (additive export, WGNN_VERSION stays 206): the kernel behind api.ResidentPredictor.panels, the
  * third member of the family of wgnn_predict_rows_dropout (a mask drawn per gene) and wgnn_predict_rows_thin (reads drawn).
  * One layer of wgnn_predict_rows for every (cell, panel) pair of a batch; no sub-matrix is stored.  Every operand of

@@ -25,6 +25,8 @@ ALIGN_BAD_COL, ALIGN_BAD_MAP, ALIGN_BAD_ROWPTR, ALIGN_BAD_VALUE = 1, 2, 4, 8    
 PAIR_BAD_INDEX, PAIR_UNSORTED, PAIR_BAD_ROWPTR = 1, 2, 4     # wgnn_pair_rows_*'s status bits (include/wgnn.h)
 POOL_BAD_INDEX, POOL_BAD_ROWPTR, POOL_BAD_COL = 1, 2, 4     # wgnn_pool_rows_*'s status bits (include/wgnn.h)
 POOL_MAX_CELLS_PER_UNIT, POOL_MAX_SLAB_GENES = 256, 16384    # wgnn_pool_rows_accumulate's unit geometry limits (include/wgnn.h)
+SOUP_BAD_ROWPTR, SOUP_BAD_COL, SOUP_BAD_ADD = 1, 2, 4     # wgnn_soup_rows_*'s status bits (include/wgnn.h)
+SOUP_MAX_SLAB_GENES = 16384        # wgnn_soup_rows_*'s widest LDS slab (include/wgnn.h)
 ABI_MAJOR = 2                    # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
@@ -108,6 +110,10 @@ SIGNATURES = {
     "wgnn_pool_rows_accumulate": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _u32, _vp]),
     "wgnn_pool_rows_count": (C.c_int, [_vp, _i64, _vp, _i64, _i32, C.c_double, C.c_float, _vp, _vp, _vp]),
     "wgnn_pool_rows_fill": (C.c_int, [_vp, _i64, _vp, _i64, _i32, C.c_double, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wgnn_soup_rows_count": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i64, _i32, C.c_uint64, C.c_double,
+                                       C.c_float, _i32, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_soup_rows_fill": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i64, _i32, C.c_uint64, C.c_double,
+                                      C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
 }
 
 

@@ -521,6 +521,9 @@ STABILITY_CHUNK_BYTES = 256 * 1024 * 1024
 # ResidentPredictor.doublets: bytes of merged CSR (col + val, 8 per entry) one chunk of pairs may hold; a pair's merged row is
 # at most as long as its two rows together, so the chunks are cut before any launch (chunking changes no bit)
 DOUBLETS_CHUNK_BYTES = 256 * 1024 * 1024
+# ResidentPredictor.ambient: bytes of contaminated CSR (col + val, 8 per entry) one chunk of cells x draws may hold; a unit's row
+# keeps at most its own entries plus min(n_add, G) soup genes, so the chunks are cut before any launch (chunking changes no bit)
+AMBIENT_CHUNK_BYTES = 256 * 1024 * 1024
 
 
 def load_map_dict(path, tissue: str) -> dict:
@@ -1310,6 +1313,186 @@ class Doublets:
         """``into=``: the further partners must be of the same batch shape, cell types, seed and partner rule."""
         if across != self.across:
             raise ValueError(f"into: the table was drawn across={self.across!r}, this call passes across={across!r}")
+        if n_cells != len(self.label):
+            raise ValueError(f"into: the table holds {len(self.label)} cells, the batch {n_cells}")
+        if list(id2label) != list(self.id2label):
+            raise ValueError("into: the table's cell types differ from the bundle's")
+        if int(seed) != int(self.seed):
+            raise ValueError(f"into: the table was drawn with seed {self.seed}, this call passes {seed}")
+
+
+def _rho_levels(rho) -> Tuple[float, ...]:
+    """``ambient``'s ``rho`` as an ascending tuple of distinct floats in [0, 1) (a single number is one level); ValueError
+    otherwise."""
+    levels = (rho,) if isinstance(rho, (int, float, np.integer, np.floating)) else tuple(rho)
+    if not levels:
+        raise ValueError("rho: no levels")
+    out = []
+    for k in levels:
+        k = float(k)
+        if not 0.0 <= k < 1.0:                                # NaN fails both comparisons
+            raise ValueError(f"rho = {k!r}: every level must be in [0, 1)")
+        out.append(k)
+    return tuple(sorted(set(out)))
+
+
+class AmbientSummary(dict):
+    """``Ambient.summary()``: a dict that prints as one line about the soup and one per level."""
+
+    def __str__(self) -> str:
+        d = self
+        lines = [f"{d['n_cells']} cells, {d['n_draws']} draws per level; the soup itself is called {d['soup_type']} "
+                 f"(probability {d['soup_prob']:.3f})"]
+        for k, med, p5 in zip(d["rho"], d["median_agreement"], d["p5_agreement"]):
+            lines.append(f"rho {k:g}: agreement median {med:.3f}, 5th percentile {p5:.3f}")
+        return "\n".join(lines)
+
+
+@dataclass
+class Ambient:
+    """What ``ResidentPredictor.ambient`` returns: how a batch's calls fare under ambient-RNA contamination.  B cells (``index``),
+    C cell types (``id2label``), L levels (``rho``, ascending: the share of the CONTAMINATED cell's reads that are soup), D draws
+    per level.  ``label`` int64 [B] / ``max_prob`` f32 [B]: the call on the cell as given (``classify``'s, -1 = unsure).  Numpy
+    arrays per (cell, level, draw) [B, L, D]: ``draw_label`` int32 / ``draw_prob`` f32 = the call on the contaminated counts,
+    ``n_mapped`` int32 = the soup reads that fell on bundle genes; ``n_added`` int64 [B, L] = the soup reads a cell takes at a
+    level.  ``soup_label`` / ``soup_prob``: what the model calls the soup profile itself - an empty droplet.  ``profile``: the
+    soup's weights as ``(int64 [G] over the bundle's genes, the weight outside the bundle)``.  ``seed``: the draws' seed.
+
+    This table characterises the MODEL under contamination; it neither estimates a sample's contamination nor decontaminates
+    counts."""
+    rho: Tuple[float, ...]
+    label: np.ndarray
+    max_prob: np.ndarray
+    draw_label: np.ndarray
+    draw_prob: np.ndarray
+    n_added: np.ndarray
+    n_mapped: np.ndarray
+    soup_label: int
+    soup_prob: float
+    profile: Tuple[np.ndarray, int]
+    index: Sequence
+    id2label: Sequence[str]
+    seed: int = 0
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    @property
+    def n_draws(self) -> int:
+        return int(self.draw_label.shape[2])
+
+    def _name(self, ids) -> list:
+        return _call_names(np.asarray(ids, np.int64), self.id2label, self.label_map)[0]
+
+    def agreement(self) -> np.ndarray:
+        """f64 [B, L]: the share of a cell's draws that keep the call as given; NaN for a cell that is unsure as given."""
+        lab = np.asarray(self.label, np.int64)
+        same = (np.asarray(self.draw_label, np.int64) == lab[:, None, None]).mean(axis=2) if self.n_draws else \
+            np.full(self.draw_label.shape[:2], np.nan)
+        return np.where(lab[:, None] >= 0, same, np.nan)
+
+    def mean_prob(self) -> np.ndarray:
+        """f64 [B, L]: the draws' mean largest softmax probability (whatever label it belongs to)."""
+        return np.asarray(self.draw_prob, np.float64).mean(axis=2)
+
+    def _votes(self) -> np.ndarray:
+        """int64 [B, L, C]: the draws per label (unsure draws are in none)."""
+        B, L, D = self.draw_label.shape
+        C = len(self.id2label)
+        lab = np.asarray(self.draw_label, np.int64)
+        cell_level = np.broadcast_to(np.arange(B * L).reshape(B, L, 1), lab.shape)
+        ok = lab >= 0
+        return np.bincount(cell_level[ok] * C + lab[ok], minlength=B * L * C).reshape(B, L, C)
+
+    def flips_to(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(ids int64 [B, L], share f64 [B, L])``: per level the cell type OTHER than the call as given that most draws were
+        labelled (equal counts: the lower id) and its share of the draws; -1 and 0 when no draw went to another type."""
+        other = self._votes()
+        B, L, C = other.shape
+        lab = np.asarray(self.label, np.int64)
+        if B:
+            other[np.arange(B), :, np.maximum(lab, 0)] = np.where(lab[:, None] >= 0, -1, other[np.arange(B), :, np.maximum(lab, 0)])
+        ids = other.argmax(axis=2) if C else np.zeros((B, L), np.int64)
+        top = np.take_along_axis(other, ids[:, :, None], axis=2)[:, :, 0] if C else np.zeros((B, L), np.int64)
+        none = top <= 0
+        return np.where(none, -1, ids).astype(np.int64), np.where(none, 0.0, top / max(self.n_draws, 1))
+
+    def _level(self, at: float) -> int:
+        return int(np.argmin(np.abs(np.asarray(self.rho, np.float64) - float(at))))
+
+    def fragile(self, at: float = 0.1, min_agreement: float = 0.9) -> np.ndarray:
+        """Boolean [B]: cells whose agreement at the level nearest ``at`` (the first of equally near ones) is below
+        ``min_agreement`` (never a cell that is unsure as given)."""
+        with np.errstate(invalid="ignore"):
+            return self.agreement()[:, self._level(at)] < float(min_agreement)
+
+    def sinks(self) -> np.ndarray:
+        """f64 [L, C]: per level and type T, of the draws CALLED T, the share whose cell is called another type as given (cells
+        unsure as given take no part; NaN for a type no draw was called).  A type with a high share takes in contaminated
+        cells of other types - for a soup that looks like T, that is the drift this method is about."""
+        B, L, D = self.draw_label.shape
+        C = len(self.id2label)
+        own = np.broadcast_to(np.asarray(self.label, np.int64)[:, None, None], (B, L, D))
+        call = np.asarray(self.draw_label, np.int64)
+        level = np.broadcast_to(np.arange(L)[None, :, None], (B, L, D))
+        ok = (own >= 0) & (call >= 0)
+        called = np.bincount(level[ok] * C + call[ok], minlength=L * C).reshape(L, C).astype(np.float64)
+        foreign = np.bincount(level[ok & (call != own)] * C + call[ok & (call != own)], minlength=L * C).reshape(L, C)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(called > 0, foreign / called, np.nan)
+
+    def by_type(self) -> pd.DataFrame:
+        """One row per level and type that a cell is called as given: ``rho``, ``cell_type``, ``n_cells``, ``retained`` (the share
+        of those cells' draws that keep the type), ``unsure`` (the share that come out unsure) and ``becomes`` (the type most of
+        the remaining draws are called, the lower id among equals, ``None`` without one)."""
+        votes = self._votes()
+        lab = np.asarray(self.label, np.int64)
+        draws_unsure = (np.asarray(self.draw_label, np.int64) < 0).sum(axis=2)
+        rows = []
+        for l, k in enumerate(self.rho):
+            for t in np.unique(lab[lab >= 0]):
+                cells = lab == t
+                n = int(cells.sum()) * self.n_draws
+                v = votes[cells, l].sum(axis=0)
+                rest = v.copy()
+                rest[t] = 0
+                top = int(rest.argmax())
+                rows.append((k, int(t), int(cells.sum()), v[t] / max(n, 1), draws_unsure[cells, l].sum() / max(n, 1),
+                             top if rest[top] > 0 else -3))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(6)]
+        return pd.DataFrame({"rho": np.asarray(cols[0], np.float64), "cell_type": self._name(cols[1]),
+                             "n_cells": np.asarray(cols[2], np.int64), "retained": np.asarray(cols[3], np.float64),
+                             "unsure": np.asarray(cols[4], np.float64), "becomes": self._name(cols[5])})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` (named as ``predict`` names it), ``prob`` (the call's as given), then per
+        level ``added_{rho}`` (the soup reads), ``agree_{rho}``, ``prob_{rho}`` (``mean_prob``), ``flip_{rho}`` (``flips_to``'s
+        type by name, ``None`` without one) and ``flip_share_{rho}``."""
+        out = {"index": list(self.index), "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob)}
+        agree, prob = self.agreement(), self.mean_prob()
+        ids, share = self.flips_to()
+        for l, k in enumerate(self.rho):
+            out[f"added_{k:g}"] = np.asarray(self.n_added)[:, l]
+            out[f"agree_{k:g}"] = agree[:, l]
+            out[f"prob_{k:g}"] = prob[:, l]
+            out[f"flip_{k:g}"] = self._name(np.where(ids[:, l] >= 0, ids[:, l], -3))
+            out[f"flip_share_{k:g}"] = share[:, l]
+        return pd.DataFrame(out)
+
+    def summary(self) -> AmbientSummary:
+        """The soup's own call and, per level, the median and the 5th percentile of the agreement over the cells that are
+        called as given (NaN without one); ``print`` it."""
+        agree = self.agreement()
+        called = np.asarray(self.label, np.int64) >= 0
+        stat = lambda f: [float(f(agree[called, l])) if called.any() else float("nan") for l in range(len(self.rho))]
+        return AmbientSummary(n_cells=len(self.label), n_draws=self.n_draws, rho=tuple(self.rho), seed=int(self.seed),
+                              soup_type=self._name([self.soup_label])[0], soup_label=int(self.soup_label),
+                              soup_prob=float(self.soup_prob), median_agreement=stat(np.median),
+                              p5_agreement=stat(lambda a: np.percentile(a, 5)))
+
+    def _require_same(self, rho: Sequence[float], n_cells: int, id2label: Sequence[str], seed: int) -> None:
+        """``into=``: the further draws must be of the same batch shape, levels, cell types and seed (the profile is compared
+        once it is made)."""
+        if tuple(rho) != tuple(self.rho):
+            raise ValueError(f"into: the table holds the levels {tuple(self.rho)}, this call asks for {tuple(rho)}")
         if n_cells != len(self.label):
             raise ValueError(f"into: the table holds {len(self.label)} cells, the batch {n_cells}")
         if list(id2label) != list(self.id2label):
@@ -2407,6 +2590,165 @@ class ResidentPredictor:
         if save_path is not None:
             Path(save_path).mkdir(parents=True, exist_ok=True)
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_doublets.csv", index=False)
+        return out
+
+    # ---------------------------------------------------------------------------------------------
+    def ambient(self, counts, genes, normalize=None, rho=(0.05, 0.1, 0.2), n_draws: int = 8, profile="batch", seed: int = 0,
+                index=None, into: Optional[Ambient] = None) -> Ambient:
+        """At which level of AMBIENT-RNA contamination does a call drift?  Every droplet also captures free-floating transcripts
+        of lysed cells - the "soup", which looks like the sample's most abundant cell types - so a rare or shallow cell is
+        pulled towards the dominant type.  Per level of ``rho`` and per draw, soup reads are drawn from ``profile`` and added
+        to every cell's raw counts on the device, the contaminated row is log-normalised against the contaminated library size
+        (``wgnn_soup_rows_count`` / ``_fill``; the rows are stored, one chunk of consecutive cells at a time under
+        ``AMBIENT_CHUNK_BYTES``) and goes through the predictor's own ``classify`` path - every layer, either route - so a
+        draw's call is bit for bit ``classify`` of the host-materialised contaminated count matrix.  Returns an ``Ambient``:
+        ``agreement`` / ``mean_prob`` / ``flips_to`` / ``fragile`` / ``sinks`` / ``by_type`` / ``frame`` / ``summary`` on top.
+
+        The batch holds raw integer COUNTS: ``genes=`` and a ``normalize`` spec are required exactly as ``doublets`` requires
+        them (else ``ValueError``), a ``GeneMap`` with merged columns raises ``ValueError``, a count that is no integer in
+        [1, 2^23] raises ``WgnnError`` naming the cell.  The genes may come in any order.  The call as given is ``classify``'s on
+        the lognorm-aligned batch.  ``index``: the cells' names (default ``range(B)``).
+
+        ``rho``: levels in [0, 1), sorted and de-duplicated: the share of the CONTAMINATED cell's reads that are soup, so a
+        cell of ``lib`` reads takes ``n_add = floor(lib * rho / (1 - rho) + 0.5)`` soup reads (fp64); more than 2^23 of them
+        raise ``WgnnError`` naming the cell.  The reads are a pure function of ``(seed, cell, draw, read)`` and NESTED: the
+        reads added at 5 % are the first of those added at 10 %.
+
+        ``profile``: ``"batch"`` - the batch's own column sums over ALL of the caller's columns, what SoupX falls back to
+        without empty droplets - or one non-negative integer (at most 2^40) per entry of ``genes``, e.g. the summed counts of
+        the run's empty droplets; columns outside the bundle fold into one bin whose reads only deepen the library.  A
+        negative, fractional or non-finite weight, and a profile without any weight, raise ``ValueError``.  The profile itself
+        is classified once (``soup_label`` / ``soup_prob``): what the model calls an empty droplet.
+
+        ``into``: an earlier ``Ambient`` of the same batch, seed, levels and profile, to which ``n_draws`` FURTHER draws are
+        appended (and which is returned): 4 and 4 more equal 8 at once.
+
+        Out of scope: this characterises the model under contamination.  It does not estimate a sample's ``rho`` and does not
+        decontaminate counts (SoupX, DecontX and CellBender do)."""
+        levels = _rho_levels(rho)
+        n_draws = int(n_draws)
+        if n_draws < 1:
+            raise ValueError(f"n_draws = {n_draws} must be >= 1")
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
+        if genes is None or spec is None:
+            raise ValueError("ambient adds soup reads to raw counts: pass the batch over its own gene list (genes=) and a normalize "
+                             "spec (the contaminated counts are log-normalised against the contaminated library size)")
+        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
+        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
+            raise ValueError("ambient does not take merged columns (duplicates=\"sum\"): merging under contamination is not built")
+        if into is not None and not isinstance(into, Ambient):
+            raise ValueError("into: pass an earlier Ambient")
+        B = self._n_cells(counts)
+        if into is not None:
+            into._require_same(levels, B, self.id2label, seed)
+        if index is not None and len(index) != B:
+            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        if not (isinstance(profile, str) and profile == "batch"):
+            if isinstance(profile, str):
+                raise ValueError(f"profile = {profile!r}: pass \"batch\" or one weight per entry of genes")
+            profile = profile.detach().cpu().numpy() if isinstance(profile, torch.Tensor) else np.asarray(profile)
+            if profile.ndim != 1 or not (np.issubdtype(profile.dtype, np.number) or profile.dtype == bool):
+                raise ValueError("profile: pass \"batch\" or a vector with one weight per entry of genes")
+            w = profile.astype(np.float64)
+            if not np.isfinite(w).all() or (w < 0).any() or (w != np.floor(w)).any() or (w > 2.0 ** 40).any():
+                raise ValueError("profile: every weight must be a non-negative integer of at most 2^40")
+            if not (w > 0).any():
+                raise ValueError("profile: no weight at all (an all-zero soup cannot be drawn from)")
+            profile = profile.astype(np.int64)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._ambient(counts, genes, spec, levels, n_draws, profile, int(seed), index, into)
+
+    def _soup_profile(self, profile, gmap, rowptr, col, cnt, lib):
+        """The soup as ``(weights int64 [G] over the bundle's genes, the weight of everything outside it)`` on the device."""
+        dev, G = self.device, self.n_genes
+        if isinstance(profile, str):                       # "batch": one pooled group of every cell, the rest from the library sizes
+            B = int(rowptr.shape[0]) - 1
+            _, p_col, _, p_cnt, total, _ = _ops.pool_rows(rowptr, col, cnt, lib, torch.zeros(B, dtype=torch.int32, device=dev), 1,
+                                                          threshold=0.0, n_genes=G)
+            bundle = torch.zeros(G, dtype=torch.int64, device=dev)
+            bundle[p_col.long()] = p_cnt
+            return bundle, int(total[0]) - int(p_cnt.sum())
+        if profile.shape[0] != gmap.shape[0]:
+            raise ValueError(f"profile holds {profile.shape[0]} weights, the gene list {gmap.shape[0]} names")
+        w = torch.from_numpy(profile).to(dev)
+        inside = gmap >= 0
+        bundle = torch.zeros(G, dtype=torch.int64, device=dev).index_add_(0, gmap[inside].long(), w[inside])
+        return bundle, int(w[~inside].sum())
+
+    def _ambient(self, counts, genes, spec, levels, n_draws, profile, seed, index, into):
+        dev, G, D, L = self.device, self.n_genes, n_draws, len(levels)
+        batch, gmap, _ = self._caller_batch(counts, genes)         # resolved once: every step below takes the device forms
+        (rowptr, col, cnt), _, lib = self._thin_operands(batch, gmap, spec)
+        _ops.pair_operand_check(rowptr, cnt, "ambient adds soup reads to counts held in 32-bit slots")
+        B = int(rowptr.shape[0]) - 1
+        bundle, rest = self._soup_profile(profile, gmap, rowptr, col, cnt, lib)
+        W = int(bundle.sum()) + rest
+        if W <= 0:
+            raise ValueError("profile: no weight at all (an all-zero soup cannot be drawn from)")
+        if W >= 2 ** 53:
+            raise ValueError("profile: the weights add up to 2^53 or more (fp64 no longer holds the total exactly)")
+        host_profile = (bundle.cpu().numpy(), int(rest))
+        if into is not None and not (np.array_equal(into.profile[0], host_profile[0]) and int(into.profile[1]) == host_profile[1]):
+            raise ValueError("into: the table was drawn from another soup profile")
+        cdf = torch.zeros(G + 2, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.cat([bundle, torch.tensor([rest], dtype=torch.int64, device=dev)]), 0, out=cdf[1:])
+        pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(batch, gmap, None, spec)))
+        scale, thr = float(spec.scale_factor), float(self.threshold)
+        # the soup itself: the profile as one pooled row against its own total
+        nz = torch.nonzero(bundle).reshape(-1)
+        s_ptr = torch.tensor([0, int(nz.shape[0])], dtype=torch.int64, device=dev)
+        none_i32 = torch.zeros(0, dtype=torch.int32, device=dev)
+        soup = _ops.pool_rows_grouped(torch.zeros(1, dtype=torch.int64, device=dev), none_i32, torch.zeros(0, dtype=torch.float32, device=dev),
+                                      torch.zeros(2, dtype=torch.int64, device=dev), none_i32,
+                                      torch.tensor([W], dtype=torch.int64, device=dev), G, scale, thr,
+                                      seed=(s_ptr, nz.to(torch.int32), bundle[nz]))
+        s_pred, s_prob, _, _ = self._classify_on_device(_Aligned(soup[:3]))
+        draw0 = 0 if into is None else into.n_draws
+        lens = (rowptr[1:] - rowptr[:-1]).long()
+        draw_label = np.empty((B, L, D), np.int32)
+        draw_prob = np.empty((B, L, D), np.float32)
+        n_mapped = np.empty((B, L, D), np.int32)
+        n_added = np.empty((B, L), np.int64)
+        for li, k in enumerate(levels):
+            n_add = torch.floor(lib.to(torch.float64) * (k / (1.0 - k)) + 0.5).to(torch.int64)
+            over = torch.nonzero(n_add > _ops.SOUP_MAX_ADD)
+            if over.numel():
+                raise WgnnError(f"ambient: cell {int(over[0])} would take more than 2^23 soup reads at rho = {k:g}")
+            n_added[:, li] = n_add.cpu().numpy()
+            # chunks of consecutive cells whose contaminated rows (own entries + min(n_add, G) soup genes, 8 bytes each, per
+            # draw) fit the budget
+            bound = torch.cumsum((lens + torch.clamp(n_add, max=G)) * (8 * D), 0).cpu().numpy()
+            r0 = 0
+            while r0 < B:
+                done = int(bound[r0 - 1]) if r0 else 0
+                r1 = max(r0 + 1, int(np.searchsorted(bound, done + AMBIENT_CHUNK_BYTES, side="right")))
+                r1 = min(r1, r0 + (2 ** 31 - 1) // D)
+                o_rowptr, o_col, o_val, mapped = _ops.soup_rows(rowptr[r0:r1 + 1], col, cnt, lib[r0:r1], n_add[r0:r1], cdf, D, row0=r0,
+                                                                draw0=draw0, seed=seed, scale=scale, threshold=thr)
+                lab, prob = self._classify_on_device(_Aligned((o_rowptr, o_col, o_val)))[:2]
+                draw_label[r0:r1, li], draw_prob[r0:r1, li] = lab.reshape(r1 - r0, D), np.asarray(prob).reshape(r1 - r0, D)
+                n_mapped[r0:r1, li] = mapped.cpu().numpy().reshape(r1 - r0, D)
+                r0 = r1
+        if into is None:
+            return Ambient(rho=levels, label=pred, max_prob=np.asarray(max_prob, np.float32), draw_label=draw_label, draw_prob=draw_prob,
+                           n_added=n_added, n_mapped=n_mapped, soup_label=int(s_pred[0]), soup_prob=float(np.asarray(s_prob)[0]),
+                           profile=host_profile, index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label),
+                           seed=seed, label_map=self._label_names())
+        into.draw_label = np.concatenate([into.draw_label, draw_label], axis=2)
+        into.draw_prob = np.concatenate([into.draw_prob, draw_prob], axis=2)
+        into.n_mapped = np.concatenate([into.n_mapped, n_mapped], axis=2)
+        return into
+
+    def ambient_file(self, data, normalize="lognorm", rho=(0.05, 0.1, 0.2), n_draws: int = 8, profile="batch", seed: int = 0,
+                     save_path=None) -> pd.DataFrame:
+        """``ambient`` on a test file of raw counts (its full table and gene names): ``Ambient.frame()``, written as
+        ``{species}_{tissue}_ambient.csv`` under ``save_path`` when given."""
+        df = _read_expression(data, self.file_type)
+        out = self.ambient(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], normalize=normalize, rho=rho,
+                           n_draws=n_draws, profile=profile, seed=seed, index=df.index).frame()
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_ambient.csv", index=False)
         return out
 
     # ---------------------------------------------------------------------------------------------

@@ -1407,6 +1407,86 @@ def pool_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     return out + (total, n_cells)
 
 
+SOUP_MAX_ADD = 2 ** 23              # soup_rows: the most soup reads a cell takes (with a count of 2^23 the sum stays exact in float32)
+
+_SOUP_STATUS = ((_lib.SOUP_BAD_ROWPTR, "rowptr points outside col / cnt, or a unit kept more entries than were counted"),
+                (_lib.SOUP_BAD_COL, "a gene id is outside [0, n_genes)"),
+                (_lib.SOUP_BAD_ADD, "an n_add is outside [0, 2^23]"))
+
+
+def soup_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: torch.Tensor, n_add: torch.Tensor, cdf: torch.Tensor,
+              n_draws: int, *, row0: int = 0, draw0: int = 0, seed: int = 0, scale: float, threshold: float, slab_genes: int = 0,
+              want_cnt: bool = False):
+    """``wgnn_soup_rows_count`` / ``wgnn_soup_rows_fill``: every cell's count row with ``n_add`` reads of ambient RNA added to
+    it, ``n_draws`` times - contaminated copies of a batch.  ``(rowptr int32 / int64 [B+1], col int32, cnt float32)``: a device
+    CSR of raw counts over the bundle's gene ids, every count an integer in [1, 2^23] (``pair_operand_check``); the rows need
+    not be sorted.  ``lib`` int64 [B]: each cell's library size, columns outside the bundle included.  ``n_add`` int64 [B]: the
+    soup reads a cell takes, each in [0, 2^23].  ``cdf`` int64 [G + 2] (the kernel's uint64: the same bits below 2^63),
+    ascending from 0: the soup profile as cumulative weights, bin ``g < G`` = bundle gene ``g``, bin ``G`` = a column outside
+    the bundle, ``0 < cdf[-1]`` (checked here with one read-back).
+
+    Unit ``q = r * n_draws + d`` leaves, in ascending gene id, ``float32(log1p(float64(c) / (lib[r] + n_add[r]) * scale))`` for
+    every gene with ``c = cnt_r(g) + s(g) > 0`` and a value ``> threshold`` (``>= 0``), ``s`` = the unit's soup reads per gene -
+    a pure function of ``(seed, row0 + r, draw0 + d, t)``, read ``t`` the same at every ``n_add`` that reaches it (the contract
+    in ``include/wgnn.h``): the bits ``align_rows(..., normalize="lognorm")`` leaves on the contaminated count matrix.
+    ``slab_genes``: the kernel's LDS slab width (0 = its default), which changes no bit.  Returns ``(rowptr int64 [B * n_draws
+    + 1], col int32, val float32, soup_mapped int32 [B * n_draws])`` on the device - the first three are what ``predict_rows``
+    takes, ``soup_mapped`` counts a unit's soup reads that fell on bundle genes - and with ``want_cnt`` a fifth, ``cnt`` int64:
+    ``c`` of every kept entry.  The count pass, a ``torch.cumsum``, one read-back of the total to size the outputs, the fill
+    pass, and a read-back of the status word - a ``rowptr`` outside ``col``, a gene id outside ``[0, G)`` or an ``n_add`` out of
+    range raises ``WgnnError`` (the kernels skip it).  Argument errors are ``ValueError``."""
+    dev = _require_cuda(rowptr, col, cnt, lib, n_add, cdf)
+    if not 0 < float(scale) < float("inf"):
+        raise ValueError(f"soup_rows: scale = {scale} must be positive and finite")
+    if not float(threshold) >= 0:
+        raise ValueError(f"soup_rows: threshold = {threshold} must be >= 0")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
+        raise ValueError("soup_rows takes rowptr int32 / int64, col int32, cnt float32")
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
+        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
+    B, D = int(rowptr.shape[0]) - 1, int(n_draws)
+    if lib.dtype != torch.int64 or tuple(lib.shape) != (B,):
+        raise ValueError(f"soup_rows: lib must be int64 [{B}]")
+    if n_add.dtype != torch.int64 or tuple(n_add.shape) != (B,):
+        raise ValueError(f"soup_rows: n_add must be int64 [{B}]")
+    if cdf.dtype != torch.int64 or cdf.dim() != 1 or cdf.shape[0] < 2 or cdf.shape[0] - 2 >= 2 ** 31 - 1:
+        raise ValueError("soup_rows: cdf must be an int64 vector [n_genes + 2]")
+    if D < 1:
+        raise ValueError(f"soup_rows: n_draws = {n_draws} must be >= 1")
+    if B * D >= 2 ** 31:
+        raise ValueError("soup_rows: B * n_draws >= 2^31 (split the batch or the draws)")
+    if int(row0) < 0 or int(draw0) < 0:
+        raise ValueError("soup_rows: row0 and draw0 must not be negative")
+    if not 0 <= int(slab_genes) <= _lib.SOUP_MAX_SLAB_GENES:
+        raise ValueError(f"soup_rows: slab_genes = {slab_genes} must be in [0, {_lib.SOUP_MAX_SLAB_GENES}]")
+    G = int(cdf.shape[0]) - 2
+    if B and not int(cdf[-1]) > 0:
+        raise ValueError("soup_rows: the profile's total weight cdf[-1] must be in (0, 2^63)")
+    rowptr, col, cnt, lib, n_add, cdf = (t.contiguous() for t in (rowptr, col, cnt, lib, n_add, cdf))
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_out = torch.empty(B * D, dtype=torch.int32, device=dev)
+    soup_mapped = torch.empty(B * D, dtype=torch.int32, device=dev)
+    head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, int(col.shape[0]), _ptr(lib), _ptr(n_add), _ptr(cdf), G, D, int(row0), int(draw0),
+            int(seed) & (2 ** 64 - 1), float(scale), float(threshold), int(slab_genes))
+    _lib.check(_lib.call(dev, "wgnn_soup_rows_count", *head, _ptr(n_out), _ptr(soup_mapped), _ptr(status), flags, _stream(dev)),
+               "wgnn_soup_rows_count")
+    out_rowptr = torch.zeros(B * D + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(n_out, 0, dtype=torch.int64, out=out_rowptr[1:])
+    total = int(out_rowptr[-1])                              # the one read-back that sizes the outputs
+    out_col = torch.empty(total, dtype=torch.int32, device=dev)
+    out_val = torch.empty(total, dtype=torch.float32, device=dev)
+    out_cnt = torch.empty(total, dtype=torch.int64, device=dev) if want_cnt else None
+    if total:
+        _lib.check(_lib.call(dev, "wgnn_soup_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt),
+                             _ptr(status), flags, _stream(dev)), "wgnn_soup_rows_fill")
+    bits = int(status)
+    if bits:
+        raise WgnnError("soup_rows: " + "; ".join(text for bit, text in _SOUP_STATUS if bits & bit))
+    out = (out_rowptr, out_col, out_val, soup_mapped)
+    return out + (out_cnt,) if want_cnt else out
+
+
 def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
                 bias: torch.Tensor, *, head: Optional[tuple] = None, target: Optional[torch.Tensor] = None,
                 self_rows: Optional[torch.Tensor] = None, direction: Optional[torch.Tensor] = None,
