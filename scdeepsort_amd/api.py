@@ -526,6 +526,17 @@ DOUBLETS_CHUNK_BYTES = 256 * 1024 * 1024
 AMBIENT_CHUNK_BYTES = 256 * 1024 * 1024
 
 
+def _byte_chunks(bound, budget: int, max_units: Optional[int] = None):
+    """``(start, stop)`` of chunks of consecutive units whose output bytes fit ``budget``; ``bound``: the cumulative bytes per
+    unit, on the host.  Every chunk takes at least one unit, and at most ``max_units``."""
+    start, cap = 0, len(bound) if max_units is None else max_units
+    while start < len(bound):
+        done = int(bound[start - 1]) if start else 0
+        stop = min(start + cap, max(start + 1, int(np.searchsorted(bound, done + budget, side="right"))))
+        yield start, stop
+        start = stop
+
+
 def load_map_dict(path, tissue: str) -> dict:
     """``get_map_dict`` (reference preprocess.py:14-29): ``{num: {test cell type: {training cell types}}}`` from the rows of
     ``map/{species}/map.xlsx`` (first sheet; columns Tissue, num, Test Datasets, Celltype, Training dataset cell type)
@@ -2562,14 +2573,10 @@ class ResidentPredictor:
         bound = torch.cumsum((lens[a.long()] + lens[b.long()]) * 8, 0).cpu().numpy()
         draw_label = np.empty(B * D, np.int32)
         draw_prob = np.empty(B * D, np.float32)
-        q0 = 0
-        while q0 < B * D:
-            done = int(bound[q0 - 1]) if q0 else 0
-            q1 = max(q0 + 1, int(np.searchsorted(bound, done + DOUBLETS_CHUNK_BYTES, side="right")))
+        for q0, q1 in _byte_chunks(bound, DOUBLETS_CHUNK_BYTES):
             merged = _ops.pair_rows(rowptr, col, cnt, lib, a[q0:q1], b[q0:q1], scale=float(spec.scale_factor),
                                     threshold=float(self.threshold))
             draw_label[q0:q1], draw_prob[q0:q1] = self._classify_on_device(_Aligned(merged))[:2]
-            q0 = q1
         partner, draw_label, draw_prob = partner.cpu().numpy(), draw_label.reshape(B, D), draw_prob.reshape(B, D)
         if into is None:
             return Doublets(label=pred, max_prob=np.asarray(max_prob, np.float32), partner=partner, draw_label=draw_label,
@@ -2718,17 +2725,12 @@ class ResidentPredictor:
             # chunks of consecutive cells whose contaminated rows (own entries + min(n_add, G) soup genes, 8 bytes each, per
             # draw) fit the budget
             bound = torch.cumsum((lens + torch.clamp(n_add, max=G)) * (8 * D), 0).cpu().numpy()
-            r0 = 0
-            while r0 < B:
-                done = int(bound[r0 - 1]) if r0 else 0
-                r1 = max(r0 + 1, int(np.searchsorted(bound, done + AMBIENT_CHUNK_BYTES, side="right")))
-                r1 = min(r1, r0 + (2 ** 31 - 1) // D)
+            for r0, r1 in _byte_chunks(bound, AMBIENT_CHUNK_BYTES, (2 ** 31 - 1) // D):
                 o_rowptr, o_col, o_val, mapped = _ops.soup_rows(rowptr[r0:r1 + 1], col, cnt, lib[r0:r1], n_add[r0:r1], cdf, D, row0=r0,
                                                                 draw0=draw0, seed=seed, scale=scale, threshold=thr)
                 lab, prob = self._classify_on_device(_Aligned((o_rowptr, o_col, o_val)))[:2]
                 draw_label[r0:r1, li], draw_prob[r0:r1, li] = lab.reshape(r1 - r0, D), np.asarray(prob).reshape(r1 - r0, D)
                 n_mapped[r0:r1, li] = mapped.cpu().numpy().reshape(r1 - r0, D)
-                r0 = r1
         if into is None:
             return Ambient(rho=levels, label=pred, max_prob=np.asarray(max_prob, np.float32), draw_label=draw_label, draw_prob=draw_prob,
                            n_added=n_added, n_mapped=n_mapped, soup_label=int(s_pred[0]), soup_prob=float(np.asarray(s_prob)[0]),

@@ -59,11 +59,6 @@ struct AArgs {
     const double* lib; double* total_out;                      // LN COUNT: the caller's library sizes (or null), the totals it stores
 };
 
-// number of set bits of `mask` below this lane
-__device__ __forceinline__ int below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // keep test of one entry; `on` = the lane holds an entry of the row.  A map value outside [-1, n_genes) is reported, not kept.
 __device__ __forceinline__ bool keep_entry(const AArgs& a, bool on, int g, float v, unsigned& bad) {
     if (on && (g < -1 || g >= a.n_genes)) { bad |= WGNN_ALIGN_BAD_MAP; return false; }

@@ -56,10 +56,6 @@ struct MArgs {
 
 struct MList { int group[kList]; float val[kList]; double sum[kList]; };   // one wave's counting member entries, position order
 
-__device__ __forceinline__ int below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 __device__ __forceinline__ void wave_sync() {                  // orders LDS writes and reads among the lanes of this one wave
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -1,6 +1,7 @@
 // wgnn_align_rows.h - the row walk that fixes the order of a row's fp64 total, shared by wgnn_align.hip (wgnn_align_count_ln's
 // total) and wgnn_coverage.hip (wgnn_coverage_rows' total / total_mapped): both sums come out of THIS code, so they agree bit
 // for bit.  One wavefront per row; a lane visits its entries in ascending position, the 64 partial sums fold in a butterfly.
+// Also here, for every kernel that compacts with a ballot or log-normalises a count: below() and lognorm().
 #pragma once
 #include <math.h>
 #include "wgnn_common.h"
@@ -83,6 +84,11 @@ __device__ __forceinline__ void row_visit(const A& a, long r, int lane, Visit&& 
             }
         }
     }
+}
+
+// number of set bits of `mask` below this lane: the lane's rank in a ballot
+__device__ __forceinline__ int below(unsigned long long mask) {
+    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
 }
 
 // the 64 partial sums of a wave folded in a fixed butterfly (both operands of every add are the same pair in both lanes): the

@@ -207,7 +207,6 @@ extern "C" int wgnn_group_class_reduce(const float* logits, int64_t ld_logits, c
                                        double* prob_sum, double* conf_sum, int32_t* votes, int32_t* tally,
                                        void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream) {
     auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_group_class_reduce", what); };
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
     wgnn::error_clear();
     if (!prob_sum || !conf_sum || !votes || !tally) return fail(WGNN_ERR_BAD_ARG, "prob_sum, conf_sum, votes and tally are required");
     if (!seg_ptr) return fail(WGNN_ERR_BAD_ARG, "seg_ptr is required");

@@ -25,8 +25,8 @@
 // reported too (every probe stays inside the two rows whatever their order).
 
 #include <math.h>
-#include "wgnn_common.h"
-#include "wgnn_align_rows.h"
+#include "wgnn_align_rows.h"             // lognorm, countable, below
+#include "wgnn_build_rows.h"
 
 namespace {
 using namespace wgnn;
@@ -44,11 +44,6 @@ struct PArgs {
     const long long* out_rowptr; int* out_col; float* out_val; // FILL
     int* status;
 };
-
-// number of set bits of `mask` below this lane
-__device__ __forceinline__ int below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 template <bool FILL, typename TPtr>
 __global__ void __launch_bounds__(kPBlock) pair_rows_kernel(const PArgs p) {
@@ -154,23 +149,18 @@ static int pair_run(const char* fn, const void* rowptr, const int32_t* col, cons
                     int32_t* n_out, const int64_t* out_rowptr, int32_t* out_col, float* out_val, int32_t* status,
                     uint32_t flags, void* stream) {
     auto fail = [fn](int code, const char* what) { return wgnn::fail(code, fn, what); };
-    auto aligned4 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) == 0; };
     wgnn::error_clear();
-    if (!status) return fail(WGNN_ERR_BAD_ARG, "status is required");
-    if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
-    if (nnz < 0) return fail(WGNN_ERR_BAD_ARG, "nnz must not be negative");
+    if (int rc = wgnn::check_count_csr(fn, status, n_rows, nnz)) return rc;
     if (n_pairs < 0 || n_pairs > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_pairs must be in [0, 2^31)");
-    if (flags & ~WGNN_FLAG_ROWPTR_I64) return fail(WGNN_ERR_BAD_ARG, "only WGNN_FLAG_ROWPTR_I64 is a valid flag");
-    if (!(scale > 0.0 && scale < HUGE_VAL)) return fail(WGNN_ERR_BAD_ARG, "scale must be positive and finite");
-    if (!(threshold >= 0.f)) return fail(WGNN_ERR_BAD_ARG, "threshold must be >= 0");
+    if (int rc = wgnn::check_rowptr_flag(fn, flags)) return rc;
+    if (int rc = wgnn::check_lognorm(fn, scale, threshold)) return rc;
     if (n_pairs > 0 && (!rowptr || !lib || !a || !b)) return fail(WGNN_ERR_BAD_ARG, "rowptr, lib, a and b are required");
-    if (n_pairs > 0 && nnz > 0 && (!col || !cnt)) return fail(WGNN_ERR_BAD_ARG, "col and cnt are required");
+    if (int rc = wgnn::check_count_entries(fn, n_pairs > 0, nnz, col, cnt)) return rc;
     if (!FILL && n_pairs > 0 && !n_out) return fail(WGNN_ERR_BAD_ARG, "n_out is required");
     if (FILL && n_pairs > 0 && !out_rowptr) return fail(WGNN_ERR_BAD_ARG, "out_rowptr is required");
     if (!wgnn::aligned8(lib)) return fail(WGNN_ERR_ALIGNMENT, "lib must be 8-byte aligned");
     if (FILL && !wgnn::aligned8(out_rowptr)) return fail(WGNN_ERR_ALIGNMENT, "out_rowptr must be 8-byte aligned");
-    if ((flags & WGNN_FLAG_ROWPTR_I64) ? !wgnn::aligned8(rowptr) : !aligned4(rowptr))
-        return fail(WGNN_ERR_ALIGNMENT, "rowptr must be aligned to its entries (8 bytes with WGNN_FLAG_ROWPTR_I64, else 4)");
+    if (int rc = wgnn::check_rowptr_alignment(fn, rowptr, flags)) return rc;
     if (!aligned4(col) || !aligned4(cnt) || !aligned4(a) || !aligned4(b) || !aligned4(n_out) || !aligned4(out_col) ||
         !aligned4(out_val) || !aligned4(status))
         return fail(WGNN_ERR_ALIGNMENT, "col, cnt, a, b, n_out, out_col, out_val and status must be 4-byte aligned");

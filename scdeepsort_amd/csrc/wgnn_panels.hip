@@ -65,10 +65,6 @@ struct NArgs {
     float* logits; long ld_logits; int* label; float* max_prob; int* entries;
 };
 
-__device__ __forceinline__ int below(unsigned long long mask) {                    // set bits of `mask` below this lane
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // orders this wave's LDS writes before its later reads (and reads before later writes): the stash is private to the wave
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -291,7 +287,6 @@ extern "C" int wgnn_predict_rows_panels(const void* rowptr, const int32_t* col, 
                                         float* logits, int64_t ld_logits, int32_t* label, float* max_prob, int32_t* entries,
                                         uint32_t flags, void* stream) {
     auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_predict_rows_panels", what); };
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
     wgnn::error_clear();
     if (!rowptr || !col || !raw || !table || !alpha || !bias)
         return fail(WGNN_ERR_BAD_ARG, "rowptr, col, raw, table, alpha and bias are required");

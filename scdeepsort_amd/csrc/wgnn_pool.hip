@@ -22,9 +22,8 @@
 // [0, n_rows), every accumulator row in [0, n_groups), whatever group_ptr holds in between.
 
 #include <math.h>
-#include <atomic>
-#include "wgnn_common.h"
-#include "wgnn_align_rows.h"
+#include "wgnn_align_rows.h"             // lognorm, below
+#include "wgnn_build_rows.h"
 
 namespace {
 using namespace wgnn;
@@ -34,7 +33,6 @@ constexpr int kLBlock = 64 * kLWaves;
 constexpr int kLMaxBlocks = 1024;             // 256 CUs x 4 workgroups (narrow slabs): grid-stride beyond that
 constexpr int kLDefCells = 64;                // cells_per_unit = 0
 constexpr int kLDefSlab = WGNN_POOL_MAX_SLAB_GENES;      // slab_genes = 0: 64 KiB of uint32
-constexpr float kLMaxCount = 8388608.f;       // 2^23
 
 constexpr int kFWaves = 4;                    // FINISH
 constexpr int kFBlock = 64 * kFWaves;
@@ -56,11 +54,6 @@ struct FArgs {
     const long long* out_rowptr; int* out_col; float* out_val; long long* out_cnt; // FILL
     int* status;
 };
-
-// number of set bits of `mask` below this lane
-__device__ __forceinline__ int below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 template <typename TPtr>
 __global__ void __launch_bounds__(kLBlock) pool_accumulate_kernel(const LArgs p) {
@@ -109,7 +102,7 @@ __global__ void __launch_bounds__(kLBlock) pool_accumulate_kernel(const LArgs p)
                         const int g = p.col[j];
                         const float x = p.cnt[j];
                         if ((unsigned)g >= (unsigned)p.n_genes) { bad |= WGNN_POOL_BAD_COL; continue; }
-                        if (g >= g0 && g < g1 && x >= 1.f && x <= kLMaxCount) atomicAdd(&s_slab[g - g0], (unsigned)x);
+                        if (g >= g0 && g < g1 && x >= 1.f && x <= kMaxCount) atomicAdd(&s_slab[g - g0], (unsigned)x);
                     }
                 }
                 __syncthreads();
@@ -174,21 +167,7 @@ __global__ void __launch_bounds__(kFBlock) pool_finish_kernel(const FArgs p) {
     if (bad) atomicOr(p.status, (int)bad);
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device (cf. wgnn_transpose.hip): remember per device what was raised
-constexpr int kMaxDevices = 64;
-std::atomic<int> g_lds_i32[kMaxDevices], g_lds_i64[kMaxDevices];
-
-int raise_lds(std::atomic<int>* marks, const void* fn, int lds) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return WGNN_ERR_LAUNCH;
-    if (marks[dev].load(std::memory_order_acquire) >= lds) return WGNN_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return WGNN_ERR_LAUNCH;
-    int seen = marks[dev].load(std::memory_order_relaxed);
-    while (seen < lds && !marks[dev].compare_exchange_weak(seen, lds, std::memory_order_release)) {}
-    return WGNN_OK;
-}
-
-inline bool aligned4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) == 0; }
+LdsMarks g_lds_i32, g_lds_i64;                // the accumulate kernel's raised LDS limit, per rowptr width
 
 }  // namespace
 
@@ -196,11 +175,10 @@ extern "C" int wgnn_pool_rows_accumulate(const void* rowptr, const int32_t* col,
                                          const int64_t* group_ptr, const int32_t* members, int64_t n_groups, int32_t n_genes,
                                          uint64_t* acc, int64_t ld_acc, int32_t cells_per_unit, int32_t slab_genes,
                                          int32_t* status, uint32_t flags, void* stream) {
-    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_pool_rows_accumulate", what); };
+    const char* fn = "wgnn_pool_rows_accumulate";
+    auto fail = [fn](int code, const char* what) { return wgnn::fail(code, fn, what); };
     wgnn::error_clear();
-    if (!status) return fail(WGNN_ERR_BAD_ARG, "status is required");
-    if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
-    if (nnz < 0) return fail(WGNN_ERR_BAD_ARG, "nnz must not be negative");
+    if (int rc = wgnn::check_count_csr(fn, status, n_rows, nnz)) return rc;
     if (n_groups < 0 || n_groups > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_groups must be in [0, 2^31)");
     if (n_genes < 0) return fail(WGNN_ERR_BAD_ARG, "n_genes must not be negative");
     if (ld_acc < n_genes) return fail(WGNN_ERR_BAD_ARG, "ld_acc must be >= n_genes");
@@ -208,14 +186,13 @@ extern "C" int wgnn_pool_rows_accumulate(const void* rowptr, const int32_t* col,
         return fail(WGNN_ERR_BAD_ARG, "cells_per_unit must be in [0, 256] (256 cells x 2^23 is what a uint32 slab entry holds)");
     if (slab_genes < 0 || slab_genes > WGNN_POOL_MAX_SLAB_GENES)
         return fail(WGNN_ERR_BAD_ARG, "slab_genes must be in [0, 16384] (a wider slab does not fit the LDS budget)");
-    if (flags & ~WGNN_FLAG_ROWPTR_I64) return fail(WGNN_ERR_BAD_ARG, "only WGNN_FLAG_ROWPTR_I64 is a valid flag");
+    if (int rc = wgnn::check_rowptr_flag(fn, flags)) return rc;
     const bool work = n_groups > 0 && n_rows > 0;
     if (work && (!rowptr || !group_ptr || !members)) return fail(WGNN_ERR_BAD_ARG, "rowptr, group_ptr and members are required");
-    if (work && nnz > 0 && (!col || !cnt)) return fail(WGNN_ERR_BAD_ARG, "col and cnt are required");
+    if (int rc = wgnn::check_count_entries(fn, work, nnz, col, cnt)) return rc;
     if (work && n_genes > 0 && !acc) return fail(WGNN_ERR_BAD_ARG, "acc is required");
     if (!wgnn::aligned8(group_ptr) || !wgnn::aligned8(acc)) return fail(WGNN_ERR_ALIGNMENT, "group_ptr and acc must be 8-byte aligned");
-    if ((flags & WGNN_FLAG_ROWPTR_I64) ? !wgnn::aligned8(rowptr) : !aligned4(rowptr))
-        return fail(WGNN_ERR_ALIGNMENT, "rowptr must be aligned to its entries (8 bytes with WGNN_FLAG_ROWPTR_I64, else 4)");
+    if (int rc = wgnn::check_rowptr_alignment(fn, rowptr, flags)) return rc;
     if (!aligned4(col) || !aligned4(cnt) || !aligned4(members) || !aligned4(status))
         return fail(WGNN_ERR_ALIGNMENT, "col, cnt, members and status must be 4-byte aligned");
     if (!work || n_genes == 0) return WGNN_OK;
@@ -230,9 +207,9 @@ extern "C" int wgnn_pool_rows_accumulate(const void* rowptr, const int32_t* col,
     p.status = status;
     const bool i64 = flags & WGNN_FLAG_ROWPTR_I64;
     const int lds = p.slab * (int)sizeof(unsigned);
-    const void* fn = i64 ? reinterpret_cast<const void*>(pool_accumulate_kernel<long long>)
-                         : reinterpret_cast<const void*>(pool_accumulate_kernel<int>);
-    if (raise_lds(i64 ? g_lds_i64 : g_lds_i32, fn, lds) != WGNN_OK) return fail(WGNN_ERR_LAUNCH, "could not reserve the LDS slab");
+    const void* kernel = i64 ? reinterpret_cast<const void*>(pool_accumulate_kernel<long long>)
+                             : reinterpret_cast<const void*>(pool_accumulate_kernel<int>);
+    if (raise_lds(i64 ? g_lds_i64 : g_lds_i32, kernel, lds) != WGNN_OK) return fail(WGNN_ERR_LAUNCH, "could not reserve the LDS slab");
     const long want = (n_rows + p.cells - 1) / p.cells * p.n_slabs;       // the items when every row is a member
     const unsigned nb = (unsigned)(want < kLMaxBlocks ? want : kLMaxBlocks);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -252,8 +229,7 @@ static int pool_finish(const char* fn, const uint64_t* acc, int64_t ld_acc, cons
     if (n_groups < 0 || n_groups > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_groups must be in [0, 2^31)");
     if (n_genes < 0) return fail(WGNN_ERR_BAD_ARG, "n_genes must not be negative");
     if (ld_acc < n_genes) return fail(WGNN_ERR_BAD_ARG, "ld_acc must be >= n_genes");
-    if (!(scale > 0.0 && scale < HUGE_VAL)) return fail(WGNN_ERR_BAD_ARG, "scale must be positive and finite");
-    if (!(threshold >= 0.f)) return fail(WGNN_ERR_BAD_ARG, "threshold must be >= 0");
+    if (int rc = wgnn::check_lognorm(fn, scale, threshold)) return rc;
     if (n_groups > 0 && !total) return fail(WGNN_ERR_BAD_ARG, "total is required");
     if (n_groups > 0 && n_genes > 0 && !acc) return fail(WGNN_ERR_BAD_ARG, "acc is required");
     if (!FILL && n_groups > 0 && !n_out) return fail(WGNN_ERR_BAD_ARG, "n_out is required");

@@ -69,7 +69,6 @@ struct DrawEntry { const char* fn; uint32_t accumulate; const char* valid_flags;
 // (the first failing check is the one reported); `thin`: wgnn_predict_rows_thin's operands, checked in their places.
 inline int check_draw_call(const DrawEntry& entry, const DrawCall& c, const ThinCall* thin) {
     auto refuse = [&](int code, const char* what) { return fail(code, entry.fn, what); };
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
     if (!c.rowptr || !c.col || !c.raw || !c.table || !c.alpha || !c.bias)
         return refuse(WGNN_ERR_BAD_ARG, "rowptr, col, raw, table, alpha and bias are required");
     if (thin && !thin->rest)

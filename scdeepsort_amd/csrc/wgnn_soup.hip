@@ -24,9 +24,8 @@
 // inside it whatever cdf holds, so a cdf that is not ascending gives unspecified bins in [0, n_genes], nothing else.
 
 #include <math.h>
-#include <atomic>
-#include "wgnn_common.h"
-#include "wgnn_align_rows.h"
+#include "wgnn_align_rows.h"             // lognorm, below
+#include "wgnn_build_rows.h"
 #include "wgnn_resident_rows.h"          // mix64
 
 namespace {
@@ -38,7 +37,6 @@ constexpr int kSMaxBlocks = 1024;             // 256 CUs x 2 resident workgroups
 constexpr int kSDefSlab = WGNN_SOUP_MAX_SLAB_GENES;      // slab_genes = 0: 64 KiB of uint32
 constexpr int kSCoarse = 512;                 // coarse boundaries kept in LDS, at most
 constexpr int kSFolds = 64;                   // bytes of LDS for the per-wave counts (2 x kSWaves int)
-constexpr float kSMaxCount = 8388608.f;       // 2^23
 constexpr long long kSMaxAdd = 1ll << 23;
 constexpr unsigned long long kCell = 0x9FB21C651E98DF25ull, kDraw = 0xD6E8FEB86659FD93ull;     // key() of the dropout block
 constexpr unsigned long long kSoup = 0x94D049BB133111EBull, kRead = 0xA0761D6478BD642Full;
@@ -53,11 +51,6 @@ struct SArgs {
     const long long* out_rowptr; int* out_col; float* out_val; long long* out_cnt; int writable; // FILL
     int* status;
 };
-
-// number of set bits of `mask` below this lane
-__device__ __forceinline__ int below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // The bin of x: the k in [0, n_genes] with cdf[k] <= x < cdf[k + 1], i.e. the smallest boundary j in [1, n_genes + 1] with
 // cdf[j] > x, less one (cdf[n_genes + 1] = W > x is never probed).  coarse[c] = cdf[min(c << sh, n_genes + 1)], c in [0, nc].
@@ -125,7 +118,7 @@ __global__ void __launch_bounds__(kSBlock) soup_rows_kernel(const SArgs p) {
                 const int g = p.col[j];
                 const float x = p.cnt[j];
                 if ((unsigned)g >= (unsigned)G) { bad |= WGNN_SOUP_BAD_COL; continue; }
-                if (g >= g0 && g < g1 && x >= 1.f && x <= kSMaxCount) atomicAdd(&s_slab[g - g0], (unsigned)x);
+                if (g >= g0 && g < g1 && x >= 1.f && x <= kMaxCount) atomicAdd(&s_slab[g - g0], (unsigned)x);
             }
             int rest = 0;                                                  // wave-uniform
             for (long t0 = (long)wave * 64; t0 < na; t0 += kSBlock) {      // wave-uniform
@@ -201,19 +194,7 @@ __global__ void __launch_bounds__(kSBlock) soup_rows_kernel(const SArgs p) {
     if (bad) atomicOr(p.status, (int)bad);                     // malformed operands only
 }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is per device (cf. wgnn_pool.hip): remember per device what was raised
-constexpr int kMaxDevices = 64;
-std::atomic<int> g_lds[4][kMaxDevices];
-
-int raise_lds(std::atomic<int>* marks, const void* fn, int lds) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return WGNN_ERR_LAUNCH;
-    if (marks[dev].load(std::memory_order_acquire) >= lds) return WGNN_OK;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return WGNN_ERR_LAUNCH;
-    int seen = marks[dev].load(std::memory_order_relaxed);
-    while (seen < lds && !marks[dev].compare_exchange_weak(seen, lds, std::memory_order_release)) {}
-    return WGNN_OK;
-}
+LdsMarks g_lds[4];                            // the raised LDS limit of COUNT / FILL x rowptr width
 
 template <bool FILL, typename TPtr>
 int launch(const SArgs& p, int which, int lds, unsigned nb, hipStream_t st) {
@@ -222,8 +203,6 @@ int launch(const SArgs& p, int which, int lds, unsigned nb, hipStream_t st) {
     hipLaunchKernelGGL((soup_rows_kernel<FILL, TPtr>), dim3(nb), dim3(kSBlock), lds, st, p);
     return hipGetLastError() == hipSuccess ? WGNN_OK : WGNN_ERR_LAUNCH;
 }
-
-inline bool aligned4(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 3u) == 0; }
 
 }  // namespace
 
@@ -236,27 +215,23 @@ static int soup_run(const char* fn, const void* rowptr, const int32_t* col, cons
                     int32_t* status, uint32_t flags, void* stream) {
     auto fail = [fn](int code, const char* what) { return wgnn::fail(code, fn, what); };
     wgnn::error_clear();
-    if (!status) return fail(WGNN_ERR_BAD_ARG, "status is required");
-    if (n_rows < 0 || n_rows > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_rows must be in [0, 2^31)");
-    if (nnz < 0) return fail(WGNN_ERR_BAD_ARG, "nnz must not be negative");
+    if (int rc = wgnn::check_count_csr(fn, status, n_rows, nnz)) return rc;
     if (n_genes < 0 || n_genes == INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n_genes must be in [0, 2^31 - 1)");
     if (n_draws < 1) return fail(WGNN_ERR_BAD_ARG, "n_draws must be >= 1");
     if (n_rows * (int64_t)n_draws > INT32_MAX)
         return fail(WGNN_ERR_BAD_ARG, "n_rows * n_draws must be < 2^31 (split the batch or the draws)");
     if (row0 < 0 || draw0 < 0) return fail(WGNN_ERR_BAD_ARG, "row0 and draw0 must not be negative");
-    if (!(scale > 0.0 && scale < HUGE_VAL)) return fail(WGNN_ERR_BAD_ARG, "scale must be positive and finite");
-    if (!(threshold >= 0.f)) return fail(WGNN_ERR_BAD_ARG, "threshold must be >= 0");
+    if (int rc = wgnn::check_lognorm(fn, scale, threshold)) return rc;
     if (slab_genes < 0 || slab_genes > WGNN_SOUP_MAX_SLAB_GENES)
         return fail(WGNN_ERR_BAD_ARG, "slab_genes must be in [0, 16384] (a wider slab does not fit the LDS budget)");
-    if (flags & ~WGNN_FLAG_ROWPTR_I64) return fail(WGNN_ERR_BAD_ARG, "only WGNN_FLAG_ROWPTR_I64 is a valid flag");
+    if (int rc = wgnn::check_rowptr_flag(fn, flags)) return rc;
     if (n_rows > 0 && (!rowptr || !lib || !n_add || !cdf)) return fail(WGNN_ERR_BAD_ARG, "rowptr, lib, n_add and cdf are required");
-    if (n_rows > 0 && nnz > 0 && (!col || !cnt)) return fail(WGNN_ERR_BAD_ARG, "col and cnt are required");
+    if (int rc = wgnn::check_count_entries(fn, n_rows > 0, nnz, col, cnt)) return rc;
     if (!FILL && n_rows > 0 && !n_out) return fail(WGNN_ERR_BAD_ARG, "n_out is required");
     if (FILL && n_rows > 0 && !out_rowptr) return fail(WGNN_ERR_BAD_ARG, "out_rowptr is required");
     if (!wgnn::aligned8(lib) || !wgnn::aligned8(n_add) || !wgnn::aligned8(cdf) || !wgnn::aligned8(out_rowptr) || !wgnn::aligned8(out_cnt))
         return fail(WGNN_ERR_ALIGNMENT, "lib, n_add, cdf, out_rowptr and out_cnt must be 8-byte aligned");
-    if ((flags & WGNN_FLAG_ROWPTR_I64) ? !wgnn::aligned8(rowptr) : !aligned4(rowptr))
-        return fail(WGNN_ERR_ALIGNMENT, "rowptr must be aligned to its entries (8 bytes with WGNN_FLAG_ROWPTR_I64, else 4)");
+    if (int rc = wgnn::check_rowptr_alignment(fn, rowptr, flags)) return rc;
     if (!aligned4(col) || !aligned4(cnt) || !aligned4(n_out) || !aligned4(soup_mapped) || !aligned4(out_col) || !aligned4(out_val) ||
         !aligned4(status))
         return fail(WGNN_ERR_ALIGNMENT, "col, cnt, n_out, soup_mapped, out_col, out_val and status must be 4-byte aligned");

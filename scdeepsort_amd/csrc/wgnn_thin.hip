@@ -72,10 +72,6 @@ struct TArgs {
     int* draw_label; float* draw_prob; int* draw_reads; int* draw_entries; int accumulate;
 };
 
-__device__ __forceinline__ int below(unsigned long long mask) {                    // set bits of `mask` below this lane
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // orders this wave's LDS writes before its later reads (and reads before later writes): the stash is private to the wave
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");

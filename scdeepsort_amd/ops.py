@@ -1199,6 +1199,44 @@ def csr_rows_ascending(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tenso
     return rowptr, col[order].contiguous(), val[order].contiguous()
 
 
+def _check_lognorm(name, scale, threshold) -> None:
+    """The ``scale`` / ``threshold`` check ``pair_rows``, ``pool_rows_grouped`` and ``soup_rows`` open with."""
+    if not 0 < float(scale) < float("inf"):
+        raise ValueError(f"{name}: scale = {scale} must be positive and finite")
+    if not float(threshold) >= 0:
+        raise ValueError(f"{name}: threshold = {threshold} must be >= 0")
+
+
+def _count_csr(name, rowptr, col, cnt, lib=None):
+    """The operand of those three ops - a device CSR of raw counts over the bundle's gene ids, and ``lib`` int64 [B] where the op
+    takes library sizes - checked (``ValueError`` under the op's ``name``): ``(rowptr, col, cnt, lib, B, nnz, flags)``, the
+    tensors contiguous, as the C entries take them."""
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
+        raise ValueError(f"{name} takes rowptr int32 / int64, col int32, cnt float32")
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
+        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
+    B = int(rowptr.shape[0]) - 1
+    if lib is not None and (lib.dtype != torch.int64 or tuple(lib.shape) != (B,)):
+        raise ValueError(f"{name}: lib must be int64 [{B}]")
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    return (rowptr.contiguous(), col.contiguous(), cnt.contiguous(), None if lib is None else lib.contiguous(), B,
+            int(col.shape[0]), flags)
+
+
+def _scan(n_out: torch.Tensor):
+    """A count pass's ``n_out`` int32 [n] -> ``(out_rowptr int64 [n + 1], total)``: the scan, and the one read-back that sizes
+    the outputs of the fill pass."""
+    out_rowptr = torch.zeros(n_out.shape[0] + 1, dtype=torch.int64, device=n_out.device)
+    torch.cumsum(n_out, 0, dtype=torch.int64, out=out_rowptr[1:])
+    return out_rowptr, int(out_rowptr[-1])
+
+
+def _check_status(name, bits: int, table, extra=()) -> None:
+    """The status word after the passes: ``WgnnError`` with the text of every bit of ``table`` that is set (then ``extra``)."""
+    if bits:
+        raise WgnnError(name + ": " + "; ".join([text for bit, text in table if bits & bit] + list(extra)))
+
+
 _PAIR_STATUS = ((_lib.PAIR_BAD_INDEX, "a pair names a row outside [0, n_rows)"),
                 (_lib.PAIR_UNSORTED, "a row is not strictly ascending in col (csr_rows_ascending sorts a batch)"),
                 (_lib.PAIR_BAD_ROWPTR, "rowptr points outside col / cnt, or a pair kept more entries than were counted"))
@@ -1220,39 +1258,24 @@ def pair_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     index out of range, a row that is not ascending or a ``rowptr`` outside ``col`` raises ``WgnnError`` (the kernels skip it).
     Argument errors are ``ValueError``."""
     dev = _require_cuda(rowptr, col, cnt, lib, a, b)
-    if not 0 < float(scale) < float("inf"):
-        raise ValueError(f"pair_rows: scale = {scale} must be positive and finite")
-    if not float(threshold) >= 0:
-        raise ValueError(f"pair_rows: threshold = {threshold} must be >= 0")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
-        raise ValueError("pair_rows takes rowptr int32 / int64, col int32, cnt float32")
-    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
-        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
-    B = int(rowptr.shape[0]) - 1
-    if lib.dtype != torch.int64 or tuple(lib.shape) != (B,):
-        raise ValueError(f"pair_rows: lib must be int64 [{B}]")
+    _check_lognorm("pair_rows", scale, threshold)
+    rowptr, col, cnt, lib, B, nnz, flags = _count_csr("pair_rows", rowptr, col, cnt, lib)
     if a.dtype != torch.int32 or b.dtype != torch.int32 or a.dim() != 1 or a.shape != b.shape:
         raise ValueError("pair_rows: a and b must be int32 vectors of one length")
     n_pairs = int(a.shape[0])
     if n_pairs >= 2 ** 31:
         raise ValueError("pair_rows: n_pairs >= 2^31 (split the pair list)")
-    rowptr, col, cnt, lib, a, b = (t.contiguous() for t in (rowptr, col, cnt, lib, a, b))
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    a, b = a.contiguous(), b.contiguous()
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     n_out = torch.empty(n_pairs, dtype=torch.int32, device=dev)
-    head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, int(col.shape[0]), _ptr(lib), _ptr(a), _ptr(b), n_pairs, float(scale),
-            float(threshold))
+    head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(lib), _ptr(a), _ptr(b), n_pairs, float(scale), float(threshold))
     _lib.check(_lib.call(dev, "wgnn_pair_rows_count", *head, _ptr(n_out), _ptr(status), flags, _stream(dev)), "wgnn_pair_rows_count")
-    out_rowptr = torch.zeros(n_pairs + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(n_out, 0, dtype=torch.int64, out=out_rowptr[1:])
-    total = int(out_rowptr[-1])                              # the one read-back that sizes the outputs
+    out_rowptr, total = _scan(n_out)
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_val = torch.empty(total, dtype=torch.float32, device=dev)
     _lib.check(_lib.call(dev, "wgnn_pair_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(status), flags,
                          _stream(dev)), "wgnn_pair_rows_fill")
-    bits = int(status)
-    if bits:
-        raise WgnnError("pair_rows: " + "; ".join(text for bit, text in _PAIR_STATUS if bits & bit))
+    _check_status("pair_rows", int(status), _PAIR_STATUS)
     return out_rowptr, out_col, out_val
 
 
@@ -1274,15 +1297,9 @@ def pool_rows_grouped(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor
     of an earlier result over the same K groups, written into the accumulator before the kernel adds to it (``total`` already
     holds the seed's share).  Returns ``(rowptr int64 [K + 1], col int32, val float32, cnt int64)``."""
     dev = _require_cuda(rowptr, col, cnt, group_ptr, members, total)
-    if not 0 < float(scale) < float("inf"):
-        raise ValueError(f"pool_rows: scale = {scale} must be positive and finite")
-    if not float(threshold) >= 0:
-        raise ValueError(f"pool_rows: threshold = {threshold} must be >= 0")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
-        raise ValueError("pool_rows takes rowptr int32 / int64, col int32, cnt float32")
-    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
-        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
-    B, G = int(rowptr.shape[0]) - 1, int(n_genes)
+    _check_lognorm("pool_rows", scale, threshold)
+    rowptr, col, cnt, _, B, nnz, flags = _count_csr("pool_rows", rowptr, col, cnt)
+    G = int(n_genes)
     if group_ptr.dtype != torch.int64 or group_ptr.dim() != 1 or group_ptr.shape[0] < 1:
         raise ValueError("pool_rows: group_ptr must be an int64 vector [n_groups + 1]")
     K = int(group_ptr.shape[0]) - 1
@@ -1305,8 +1322,7 @@ def pool_rows_grouped(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor
             raise ValueError(f"pool_rows: seed must be an earlier result over the same {K} groups")
         if s_col.numel() and (int(s_col.min()) < 0 or int(s_col.max()) >= G):
             raise ValueError(f"pool_rows: seed holds a gene id outside [0, {G})")
-    rowptr, col, cnt, group_ptr, members, total = (t.contiguous() for t in (rowptr, col, cnt, group_ptr, members, total))
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    group_ptr, members, total = group_ptr.contiguous(), members.contiguous(), total.contiguous()
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     step = max(1, int(max_bytes) // max(8 * G, 1))
     parts = []
@@ -1319,24 +1335,20 @@ def pool_rows_grouped(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor
             rows = torch.repeat_interleave(torch.arange(n, device=dev), s_rowptr[k0 + 1:k1 + 1] - s_rowptr[k0:k1], output_size=e1 - e0)
             acc[rows, s_col[e0:e1].long()] = s_cnt[e0:e1]                 # a seeded group's genes are unique: plain stores
         gp, tot = group_ptr[k0:k1 + 1], total[k0:k1]
-        _lib.check(_lib.call(dev, "wgnn_pool_rows_accumulate", _ptr(rowptr), _ptr(col), _ptr(cnt), B, int(col.shape[0]), _ptr(gp),
-                             _ptr(members), n, G, _ptr(acc), G, int(cells_per_unit), int(slab_genes), _ptr(status), flags,
-                             _stream(dev)), "wgnn_pool_rows_accumulate")
+        _lib.check(_lib.call(dev, "wgnn_pool_rows_accumulate", _ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(gp), _ptr(members),
+                             n, G, _ptr(acc), G, int(cells_per_unit), int(slab_genes), _ptr(status), flags, _stream(dev)),
+                   "wgnn_pool_rows_accumulate")
         head = (_ptr(acc), G, _ptr(tot), n, G, float(scale), float(threshold))
         n_out = torch.empty(n, dtype=torch.int32, device=dev)
         _lib.check(_lib.call(dev, "wgnn_pool_rows_count", *head, _ptr(n_out), _ptr(status), _stream(dev)), "wgnn_pool_rows_count")
-        ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(n_out, 0, dtype=torch.int64, out=ptr[1:])
-        kept = int(ptr[-1])                                              # the one read-back that sizes the chunk's outputs
+        ptr, kept = _scan(n_out)
         out_col = torch.empty(kept, dtype=torch.int32, device=dev)
         out_val = torch.empty(kept, dtype=torch.float32, device=dev)
         out_cnt = torch.empty(kept, dtype=torch.int64, device=dev)
         _lib.check(_lib.call(dev, "wgnn_pool_rows_fill", *head, _ptr(ptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt), _ptr(status),
                              _stream(dev)), "wgnn_pool_rows_fill")
         parts.append((n_out, out_col, out_val, out_cnt))
-    bits = int(status)
-    if bits:
-        raise WgnnError("pool_rows: " + "; ".join(text for bit, text in _POOL_STATUS if bits & bit))
+    _check_status("pool_rows", int(status), _POOL_STATUS)
     out_rowptr = torch.zeros(K + 1, dtype=torch.int64, device=dev)
     if parts:
         torch.cumsum(torch.cat([p[0] for p in parts]), 0, dtype=torch.int64, out=out_rowptr[1:])
@@ -1436,17 +1448,9 @@ def soup_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     pass, and a read-back of the status word - a ``rowptr`` outside ``col``, a gene id outside ``[0, G)`` or an ``n_add`` out of
     range raises ``WgnnError`` (the kernels skip it).  Argument errors are ``ValueError``."""
     dev = _require_cuda(rowptr, col, cnt, lib, n_add, cdf)
-    if not 0 < float(scale) < float("inf"):
-        raise ValueError(f"soup_rows: scale = {scale} must be positive and finite")
-    if not float(threshold) >= 0:
-        raise ValueError(f"soup_rows: threshold = {threshold} must be >= 0")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
-        raise ValueError("soup_rows takes rowptr int32 / int64, col int32, cnt float32")
-    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
-        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
-    B, D = int(rowptr.shape[0]) - 1, int(n_draws)
-    if lib.dtype != torch.int64 or tuple(lib.shape) != (B,):
-        raise ValueError(f"soup_rows: lib must be int64 [{B}]")
+    _check_lognorm("soup_rows", scale, threshold)
+    rowptr, col, cnt, lib, B, nnz, flags = _count_csr("soup_rows", rowptr, col, cnt, lib)
+    D = int(n_draws)
     if n_add.dtype != torch.int64 or tuple(n_add.shape) != (B,):
         raise ValueError(f"soup_rows: n_add must be int64 [{B}]")
     if cdf.dtype != torch.int64 or cdf.dim() != 1 or cdf.shape[0] < 2 or cdf.shape[0] - 2 >= 2 ** 31 - 1:
@@ -1462,27 +1466,22 @@ def soup_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     G = int(cdf.shape[0]) - 2
     if B and not int(cdf[-1]) > 0:
         raise ValueError("soup_rows: the profile's total weight cdf[-1] must be in (0, 2^63)")
-    rowptr, col, cnt, lib, n_add, cdf = (t.contiguous() for t in (rowptr, col, cnt, lib, n_add, cdf))
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    n_add, cdf = n_add.contiguous(), cdf.contiguous()
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     n_out = torch.empty(B * D, dtype=torch.int32, device=dev)
     soup_mapped = torch.empty(B * D, dtype=torch.int32, device=dev)
-    head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, int(col.shape[0]), _ptr(lib), _ptr(n_add), _ptr(cdf), G, D, int(row0), int(draw0),
+    head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(lib), _ptr(n_add), _ptr(cdf), G, D, int(row0), int(draw0),
             int(seed) & (2 ** 64 - 1), float(scale), float(threshold), int(slab_genes))
     _lib.check(_lib.call(dev, "wgnn_soup_rows_count", *head, _ptr(n_out), _ptr(soup_mapped), _ptr(status), flags, _stream(dev)),
                "wgnn_soup_rows_count")
-    out_rowptr = torch.zeros(B * D + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(n_out, 0, dtype=torch.int64, out=out_rowptr[1:])
-    total = int(out_rowptr[-1])                              # the one read-back that sizes the outputs
+    out_rowptr, total = _scan(n_out)
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_val = torch.empty(total, dtype=torch.float32, device=dev)
     out_cnt = torch.empty(total, dtype=torch.int64, device=dev) if want_cnt else None
     if total:
         _lib.check(_lib.call(dev, "wgnn_soup_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt),
                              _ptr(status), flags, _stream(dev)), "wgnn_soup_rows_fill")
-    bits = int(status)
-    if bits:
-        raise WgnnError("soup_rows: " + "; ".join(text for bit, text in _SOUP_STATUS if bits & bit))
+    _check_status("soup_rows", int(status), _SOUP_STATUS)
     out = (out_rowptr, out_col, out_val, soup_mapped)
     return out + (out_cnt,) if want_cnt else out
 
@@ -1808,9 +1807,7 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
                              _stream(dev)), "wgnn_align_count_ln" + sfx)
     else:
         _lib.check(_lib.call(dev, "wgnn_align_count", *head, _ptr(counts), _ptr(status), flags, _stream(dev)), "wgnn_align_count")
-    out_rowptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, dtype=torch.int64, out=out_rowptr[1:])
-    total = int(out_rowptr[-1])                              # the one read-back that sizes the outputs
+    out_rowptr, total = _scan(counts)
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_raw = torch.empty(total, dtype=torch.float32, device=dev)
     if lognorm:
@@ -1820,11 +1817,8 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
         _lib.check(_lib.call(dev, "wgnn_align_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status), flags,
                              _stream(dev)), "wgnn_align_fill")
     bits = int(status)
-    if bits:
-        texts = [text for bit, text in _ALIGN_STATUS if bits & bit]
-        if merge and bits & _lib.ALIGN_BAD_MAP:
-            texts.append("or a group table (col_group, group_ptr, group_cols) points outside its range")
-        raise WgnnError("align_rows: " + "; ".join(texts))
+    merge_text = ("or a group table (col_group, group_ptr, group_cols) points outside its range",)
+    _check_status("align_rows", bits, _ALIGN_STATUS, merge_text if merge and bits & _lib.ALIGN_BAD_MAP else ())
     return out_rowptr, out_col, out_raw
 
 
@@ -1847,7 +1841,5 @@ def coverage_rows(expr, gene_map: torch.Tensor, n_genes: int):
     _lib.check(_lib.call(dev, "wgnn_coverage_rows", _ptr(x), ld, _ptr(rowptr), _ptr(col), _ptr(val), B, n_cols, _ptr(gene_map), G,
                          _ptr(n_expressed), _ptr(n_mapped), _ptr(n_bad), _ptr(total), _ptr(total_mapped), _ptr(col_cells),
                          _ptr(status), flags, _stream(dev)), "wgnn_coverage_rows")
-    bits = int(status)
-    if bits:
-        raise WgnnError("coverage_rows: " + "; ".join(text for bit, text in _ALIGN_STATUS if bits & bit))
+    _check_status("coverage_rows", int(status), _ALIGN_STATUS)
     return n_expressed, n_mapped, n_bad, total, total_mapped, col_cells
