@@ -1018,6 +1018,74 @@ int wgnn_soup_rows_fill(const void* rowptr, const int32_t* col, const float* cnt
                         uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Hood rows (additive exports, WGNN_VERSION stays 206): every unit's COUNT rows POOLED - a cell's row added to the rows of its
+ * neighbours, the caller's kNN lists - and the pooled row log-normalised against the pooled library size: one step of kNN
+ * smoothing, the operand of api.ResidentPredictor.smooth.  The scheme is wgnn_pair_rows_*'s: count, the caller's exclusive scan,
+ * fill; the output is a CSR that wgnn_predict_rows takes unchanged.  Where wgnn_pool_rows_accumulate pools DISJOINT groups into a
+ * dense uint64 [n_groups, n_genes] table - n_rows x n_genes x 8 bytes with one group per cell -, the units here may overlap and
+ * their sums never leave the LDS.
+ * Operand: the count CSR of the pool-rows and soup-rows blocks - rowptr [n_rows + 1] (int32, or int64 with
+ * WGNN_FLAG_ROWPTR_I64), col int32, cnt f32, nnz = the length of col / cnt.  Every count is an integer in [1, 2^23] (the caller's
+ * check; any other value is left out without a word).  Rows need NOT be sorted, and a gene listed twice in a row adds twice.
+ * lib int64 [n_rows]: a cell's library size, ALL its reads, those in columns outside the bundle included, each >= 0.
+ * hood_ptr int64 [n_units + 1], ascending, and members int32 [n_members]: unit q pools the rows
+ * members[hood_ptr[q] : hood_ptr[q + 1]].  The indices refer to the whole member list, so hood_ptr + q0 (with n_units - q0) is a
+ * valid operand for a slice of the units next to the same members.  A member listed twice adds twice, counts and library size.
+ * scale > 0 (Seurat's scale.factor), threshold >= 0.  For unit q, g ascending:
+ *
+ *   c(g)  = sum over the unit's members r, over the entries j of row r with col[j] == g, of uint64(cnt[j])
+ *   total = double( sum over the members of lib[r] )               (an int64 sum; the caller keeps it below 2^53: a double holds it)
+ *   v     = float( log1p( double(c) / total * scale ) )            - lognorm() of csrc/wgnn_align_rows.h in its form that takes the
+ *                                                                    count as a double, the ONE definition, as pool rows
+ *   the entry (g, v) leaves  iff  c > 0 && v > threshold;  total <= 0, or a unit without a member, gives the empty row.
+ *
+ * A unit holds at most WGNN_HOOD_MAX_MEMBERS = 256 members: 256 x 2^23 = 2^31 fits the uint32 counter of a gene; where rows list
+ * a gene twice, keeping a gene's summed count in a unit below 2^32 is the caller's condition, as in the soup block.  All sums are
+ * integers, so the result does not depend on the order of the members, of a row's entries or of the slabs; two launches are
+ * bit-identical.  A unit of one carries THE BITS wgnn_align_count_ln / _fill_ln leave on the cell's own row (one more column
+ * holding the reads outside the bundle), a unit of two the bits of wgnn_pair_rows_*, a list of units that partitions the cells
+ * the bits of wgnn_pool_rows_*.
+ *   wgnn_hood_rows_count: n_out int32 [n_units] = the entries unit q leaves.
+ *   wgnn_hood_rows_fill : out_rowptr int64 [n_units + 1] = the exclusive scan of n_out (the caller's), out_col int32, out_val f32
+ *                         and - may be NULL - out_cnt int64 [out_rowptr[n_units]]: gene, value and c of every kept entry.
+ * One workgroup of 8 waves per unit (grid-stride).  The members are checked once and their row ranges staged in LDS.  The genes
+ * are cut into slabs of slab_genes (0 = the default, 16384: 64 KiB of uint32, two workgroups per CU; at most 16384; never wider
+ * than n_genes); per slab the workgroup zeroes a uint32 LDS slab, its waves take the member rows (one wave per row, lanes over its
+ * entries; what lies outside the slab is skipped by comparison, so with n_genes > slab_genes a row is read once per slab), LDS
+ * integer atomics take the counts, and the slab is swept 64 genes per wave step; wave ballots and the folded per-wave counts give
+ * the slots.  COUNT and FILL are the same walk, so they agree on every decision; at threshold == 0 && scale >= 1 every c > 0 is
+ * kept and the counting walk skips the logarithm.  No floating-point atomics, no global atomics on the data path, vector stores
+ * only.
+ * Malformed operands never fault; each is skipped and ORs its bit into *status (int32, device memory, zeroed by the caller;
+ * required): a member outside [0, n_rows) (that member is skipped, counts and library size), WGNN_HOOD_BAD_INDEX; a member's row
+ * range outside [0, nnz] (that member is skipped), a hood_ptr range that descends or leaves [0, n_members] (the unit leaves the
+ * empty row), a slot at or past out_rowptr[q + 1] (not written; with out_col or out_val NULL every slot is such a slot),
+ * WGNN_HOOD_BAD_ROWPTR; a gene id outside [0, n_genes) (the entry is skipped), WGNN_HOOD_BAD_COL; more than 256 members (the unit
+ * leaves the empty row), WGNN_HOOD_BAD_SIZE.
+ * n_rows, n_units, n_genes < 2^31.  n_units = 0 is a valid no-op; n_rows = 0 is valid too (rowptr, lib, col and cnt may then be
+ * NULL): every unit leaves the empty row, and a member it lists is WGNN_HOOD_BAD_INDEX.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (status NULL, a missing operand or output, a negative size, a size >= 2^31, scale
+ * not positive and finite, threshold < 0 or NaN, slab_genes outside [0, 16384], an unknown flag), WGNN_ERR_ALIGNMENT (lib /
+ * hood_ptr / out_rowptr / out_cnt / an int64 rowptr not 8-byte, any other operand not 4-byte aligned); wgnn_last_error_string
+ * names the entry and the check.
+ * ------------------------------------------------------------------------- */
+#define WGNN_HOOD_BAD_INDEX  1   /* status bit: a member was outside [0, n_rows)                                          */
+#define WGNN_HOOD_BAD_ROWPTR 2   /* status bit: a row range outside [0, nnz], a malformed hood_ptr range, or too little room */
+#define WGNN_HOOD_BAD_COL    4   /* status bit: a gene id was outside [0, n_genes)                                        */
+#define WGNN_HOOD_BAD_SIZE   8   /* status bit: a unit held more than WGNN_HOOD_MAX_MEMBERS members                       */
+#define WGNN_HOOD_MAX_MEMBERS    256
+#define WGNN_HOOD_MAX_SLAB_GENES 16384
+int wgnn_hood_rows_count(const void* rowptr, const int32_t* col, const float* cnt, int64_t n_rows, int64_t nnz,
+                         const int64_t* lib, const int64_t* hood_ptr, const int32_t* members, int64_t n_units,
+                         int64_t n_members, int32_t n_genes, double scale, float threshold, int32_t slab_genes,
+                         int32_t* n_out, int32_t* status, uint32_t flags, void* stream);
+int wgnn_hood_rows_fill(const void* rowptr, const int32_t* col, const float* cnt, int64_t n_rows, int64_t nnz,
+                        const int64_t* lib, const int64_t* hood_ptr, const int32_t* members, int64_t n_units,
+                        int64_t n_members, int32_t n_genes, double scale, float threshold, int32_t slab_genes,
+                        const int64_t* out_rowptr, int32_t* out_col, float* out_val, int64_t* out_cnt, int32_t* status,
+                        uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Calls on GIVEN gene subsets (additive export, WGNN_VERSION stays 206): the kernel behind api.ResidentPredictor.panels, the
  * third member of the family of wgnn_predict_rows_dropout (a mask drawn per gene) and wgnn_predict_rows_thin (reads drawn).
  * One layer of wgnn_predict_rows for every (cell, panel) pair of a batch; no sub-matrix is stored.  Every operand of

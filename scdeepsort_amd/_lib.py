@@ -27,6 +27,8 @@ POOL_BAD_INDEX, POOL_BAD_ROWPTR, POOL_BAD_COL = 1, 2, 4     # wgnn_pool_rows_*'s
 POOL_MAX_CELLS_PER_UNIT, POOL_MAX_SLAB_GENES = 256, 16384    # wgnn_pool_rows_accumulate's unit geometry limits (include/wgnn.h)
 SOUP_BAD_ROWPTR, SOUP_BAD_COL, SOUP_BAD_ADD = 1, 2, 4     # wgnn_soup_rows_*'s status bits (include/wgnn.h)
 SOUP_MAX_SLAB_GENES = 16384        # wgnn_soup_rows_*'s widest LDS slab (include/wgnn.h)
+HOOD_BAD_INDEX, HOOD_BAD_ROWPTR, HOOD_BAD_COL, HOOD_BAD_SIZE = 1, 2, 4, 8     # wgnn_hood_rows_*'s status bits (include/wgnn.h)
+HOOD_MAX_MEMBERS, HOOD_MAX_SLAB_GENES = 256, 16384     # wgnn_hood_rows_*'s largest unit and widest LDS slab (include/wgnn.h)
 ABI_MAJOR = 2                    # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
@@ -114,6 +116,10 @@ SIGNATURES = {
                                        C.c_float, _i32, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_soup_rows_fill": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i64, _i32, C.c_uint64, C.c_double,
                                       C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_hood_rows_count": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, C.c_double, C.c_float, _i32,
+                                       _vp, _vp, _u32, _vp]),
+    "wgnn_hood_rows_fill": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, C.c_double, C.c_float, _i32,
+                                      _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
 }
 
 

@@ -24,7 +24,7 @@ import scipy.sparse as sp
 import torch
 import torch.nn.functional as F
 
-from ._lib import WgnnError
+from ._lib import HOOD_MAX_MEMBERS, WgnnError
 from .gnn import GNN
 from .graph import CellGeneGraph
 from . import ops as _ops
@@ -524,6 +524,9 @@ DOUBLETS_CHUNK_BYTES = 256 * 1024 * 1024
 # ResidentPredictor.ambient: bytes of contaminated CSR (col + val, 8 per entry) one chunk of cells x draws may hold; a unit's row
 # keeps at most its own entries plus min(n_add, G) soup genes, so the chunks are cut before any launch (chunking changes no bit)
 AMBIENT_CHUNK_BYTES = 256 * 1024 * 1024
+# ResidentPredictor.smooth: bytes of pooled CSR (col + val, 8 per entry) one chunk of cells may hold; a pooled row keeps at most
+# min(G, its members' row lengths together) entries, so the chunks are cut before any launch (chunking changes no bit)
+SMOOTH_CHUNK_BYTES = 256 * 1024 * 1024
 
 
 def _byte_chunks(bound, budget: int, max_units: Optional[int] = None):
@@ -1510,6 +1513,190 @@ class Ambient:
             raise ValueError("into: the table's cell types differ from the bundle's")
         if int(seed) != int(self.seed):
             raise ValueError(f"into: the table was drawn with seed {self.seed}, this call passes {seed}")
+
+
+SMOOTH_MAX_NEIGHBORS = HOOD_MAX_MEMBERS - 1         # a cell and its neighbours are one unit of wgnn_hood_rows_*
+
+
+def _neighbor_lists(neighbors, B: int, include_self: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """``smooth``'s ``neighbors`` as ``(hood_ptr int64 [B + 1], members int32)``: cell ``i`` pools the rows
+    ``members[hood_ptr[i]:hood_ptr[i + 1]]`` - with ``include_self`` the cell itself first, then its neighbours in the caller's
+    order.  ``neighbors``: an integer ``[B, k]`` array or tensor (-1 = no neighbour) or a scipy sparse ``[B, B]`` matrix whose
+    stored non-zero entries of row ``i`` are cell ``i``'s neighbours.  A cell that is its own neighbour (a diagonal entry) is
+    dropped; an index outside ``[0, B)``, a neighbour listed twice for one cell and more than 255 neighbours raise
+    ``ValueError`` naming the cell.  Host only."""
+    B = int(B)
+    if sp.issparse(neighbors):
+        if tuple(neighbors.shape) != (B, B):
+            raise ValueError(f"neighbors: a sparse matrix of shape {tuple(neighbors.shape)}, the batch holds {B} cells ([{B}, {B}])")
+        m = sp.csr_matrix(neighbors, copy=True)
+        m.sum_duplicates()
+        m.eliminate_zeros()
+        rows = np.repeat(np.arange(B, dtype=np.int64), np.diff(m.indptr))
+        cols = m.indices.astype(np.int64)
+    else:
+        a = neighbors.detach().cpu().numpy() if isinstance(neighbors, torch.Tensor) else np.asarray(neighbors)
+        if a.ndim != 2 or a.shape[0] != B or not (np.issubdtype(a.dtype, np.integer) or a.size == 0):
+            raise ValueError(f"neighbors: pass an integer [{B}, k] array of cell indices (-1 = no neighbour) or a sparse "
+                             f"[{B}, {B}] matrix, got {a.dtype} {tuple(a.shape)}")
+        rows = np.repeat(np.arange(B, dtype=np.int64), a.shape[1])
+        cols = a.reshape(-1).astype(np.int64)
+        listed = cols != -1
+        rows, cols = rows[listed], cols[listed]
+    outside = np.flatnonzero((cols < 0) | (cols >= B))
+    if outside.size:
+        raise ValueError(f"neighbors: cell {int(rows[outside[0]])} lists the index {int(cols[outside[0]])}, outside [0, {B})")
+    other = cols != rows
+    rows, cols = rows[other], cols[other]
+    order = np.argsort(rows * max(B, 1) + cols, kind="stable")
+    twice = np.flatnonzero((rows[order][1:] == rows[order][:-1]) & (cols[order][1:] == cols[order][:-1]))
+    if twice.size:
+        at = order[twice[0]]
+        raise ValueError(f"neighbors: cell {int(rows[at])} lists the neighbour {int(cols[at])} twice")
+    n = np.bincount(rows, minlength=B).astype(np.int64)
+    over = np.flatnonzero(n > SMOOTH_MAX_NEIGHBORS)
+    if over.size:
+        raise ValueError(f"neighbors: cell {int(over[0])} lists {int(n[over[0]])} neighbours, more than {SMOOTH_MAX_NEIGHBORS}")
+    own = 1 if include_self else 0
+    hood_ptr = np.zeros(B + 1, np.int64)
+    np.cumsum(n + own, out=hood_ptr[1:])
+    members = np.empty(int(hood_ptr[-1]), np.int32)
+    if include_self:
+        members[hood_ptr[:-1]] = np.arange(B, dtype=np.int32)
+    start = np.concatenate([[0], np.cumsum(n)[:-1]]) if B else np.zeros(0, np.int64)      # rows is ascending: a cell's run
+    members[hood_ptr[rows] + own + (np.arange(rows.shape[0]) - start[rows])] = cols
+    return hood_ptr, members
+
+
+class SmoothedSummary(dict):
+    """``Smoothed.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_cells']} cells pooled with their neighbours (median {d['median_neighbors']:g}, "
+            f"{'with' if d['include_self'] else 'without'} the cell itself)",
+            f"unsure as given {d['n_unsure']}, unsure when pooled {d['n_smooth_unsure']}: {d['n_rescued']} rescued, {d['n_lost']} lost, "
+            f"{d['n_changed']} called another type",
+            f"median neighbour agreement {d['median_agreement']:.3f}"])
+
+
+@dataclass
+class Smoothed:
+    """What ``ResidentPredictor.smooth`` returns: a batch's calls on kNN-POOLED counts next to the calls as given.  B cells
+    (``index``), C cell types (``id2label``).  ``label`` int64 [B] / ``max_prob`` f32 [B]: the call on the cell as given
+    (``classify``'s, -1 = unsure).  ``smooth_label`` int64 [B] / ``smooth_prob`` f32 [B] / ``logits`` [B, C] (on the device, as
+    ``classify`` returns them): the call on the summed counts of the cell's pool.  ``n_neighbors`` int64 [B]: the neighbours the
+    cell was pooled with (itself not counted); ``n_reads`` int64 [B]: the pool's library size, reads outside the bundle
+    included; ``n_genes`` / ``smooth_n_genes`` int64 [B]: the bundle genes the cell's own row holds, and the entries its pooled row
+    kept.  ``hood_ptr`` / ``members``: the pools as ``_neighbor_lists`` made them; ``include_self``: whether a pool opens with
+    the cell itself.
+
+    Pooling across a type boundary blurs a rare cell into its neighbours' type: ``neighbor_agreement`` is the warning."""
+    label: np.ndarray
+    max_prob: np.ndarray
+    smooth_label: np.ndarray
+    smooth_prob: np.ndarray
+    logits: torch.Tensor
+    n_neighbors: np.ndarray
+    n_reads: np.ndarray
+    n_genes: np.ndarray
+    smooth_n_genes: np.ndarray
+    hood_ptr: np.ndarray
+    members: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    include_self: bool = True
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def _name(self, ids) -> list:
+        return _call_names(np.asarray(ids, np.int64), self.id2label, self.label_map)[0]
+
+    def _calls(self) -> Tuple[np.ndarray, np.ndarray]:
+        return np.asarray(self.label, np.int64), np.asarray(self.smooth_label, np.int64)
+
+    def rescued(self) -> np.ndarray:
+        """Boolean [B]: unsure as given, called when pooled."""
+        own, pooled = self._calls()
+        return (own < 0) & (pooled >= 0)
+
+    def lost(self) -> np.ndarray:
+        """Boolean [B]: called as given, unsure when pooled."""
+        own, pooled = self._calls()
+        return (own >= 0) & (pooled < 0)
+
+    def changed(self) -> np.ndarray:
+        """Boolean [B]: called both ways, and another type when pooled."""
+        own, pooled = self._calls()
+        return (own >= 0) & (pooled >= 0) & (own != pooled)
+
+    def transitions(self) -> np.ndarray:
+        """int64 [C + 1, C + 1]: the cells by (call as given, call when pooled), unsure as the last slot of both axes."""
+        C = len(self.id2label)
+        own, pooled = self._calls()
+        slot = lambda x: np.where(x >= 0, x, C)
+        return np.bincount(slot(own) * (C + 1) + slot(pooled), minlength=(C + 1) ** 2).reshape(C + 1, C + 1)
+
+    def neighbor_agreement(self) -> np.ndarray:
+        """f64 [B]: per cell, the share of its neighbours (itself not counted) whose OWN call is the cell's pooled call; NaN for
+        a cell without a neighbour or whose pooled call is unsure.  A low share under a confident pooled call says that the
+        neighbourhood straddles two types - or that the pool called what none of its shallow members could."""
+        own, pooled = self._calls()
+        B = own.shape[0]
+        ptr = np.asarray(self.hood_ptr, np.int64)
+        cell = np.repeat(np.arange(B), np.diff(ptr))
+        member = np.asarray(self.members, np.int64)
+        if self.include_self and member.size:                             # a pool opens with the cell itself
+            keep = np.ones(member.shape[0], bool)
+            keep[ptr[:-1]] = False
+            cell, member = cell[keep], member[keep]
+        same = np.bincount(cell, weights=(own[member] == pooled[cell]).astype(np.float64), minlength=B)
+        n = np.bincount(cell, minlength=B)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where((n > 0) & (pooled >= 0), same / n, np.nan)
+
+    def by_type(self) -> pd.DataFrame:
+        """One row per call as given (unsure included, last): ``cell_type``, ``n_cells``, ``kept`` (the share whose pooled call
+        is the same), ``unsure`` (the share that come out unsure when pooled) and ``becomes`` (the type most of the remaining
+        cells are called when pooled, the lower id among equals, ``None`` without one)."""
+        C = len(self.id2label)
+        t = self.transitions()
+        rows = []
+        for s in list(range(C)) + [C]:
+            n = int(t[s].sum())
+            if n == 0:
+                continue
+            rest = t[s, :C].copy()
+            if s < C:
+                rest[s] = 0
+            top = int(rest.argmax()) if C else 0
+            rows.append((s if s < C else -1, n, t[s, s] / n, t[s, C] / n, top if C and rest[top] > 0 else -3))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(5)]
+        return pd.DataFrame({"cell_type": self._name(cols[0]), "n_cells": np.asarray(cols[1], np.int64),
+                             "kept": np.asarray(cols[2], np.float64), "unsure": np.asarray(cols[3], np.float64),
+                             "becomes": self._name(cols[4])})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` / ``prob`` (the call as given, named as ``predict`` names it),
+        ``smooth_type`` / ``smooth_prob`` (the call when pooled), ``n_neighbors``, ``n_reads``, ``n_genes``, ``smooth_n_genes`` and
+        ``neighbor_agreement``."""
+        return pd.DataFrame({"index": list(self.index), "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob),
+                             "smooth_type": self._name(self.smooth_label), "smooth_prob": np.asarray(self.smooth_prob),
+                             "n_neighbors": np.asarray(self.n_neighbors), "n_reads": np.asarray(self.n_reads),
+                             "n_genes": np.asarray(self.n_genes), "smooth_n_genes": np.asarray(self.smooth_n_genes),
+                             "neighbor_agreement": self.neighbor_agreement()})
+
+    def summary(self) -> SmoothedSummary:
+        """The cells that pooling rescued, lost and moved to another type, and the median neighbour agreement (NaN without a
+        cell that has one); ``print`` it."""
+        own, pooled = self._calls()
+        agree = self.neighbor_agreement()
+        known = ~np.isnan(agree)
+        return SmoothedSummary(n_cells=len(own), include_self=bool(self.include_self),
+                               median_neighbors=float(np.median(self.n_neighbors)) if len(own) else float("nan"),
+                               n_unsure=int((own < 0).sum()), n_smooth_unsure=int((pooled < 0).sum()),
+                               n_rescued=int(self.rescued().sum()), n_lost=int(self.lost().sum()), n_changed=int(self.changed().sum()),
+                               median_agreement=float(np.median(agree[known])) if known.any() else float("nan"))
 
 
 class PseudobulkSummary(dict):
@@ -2751,6 +2938,107 @@ class ResidentPredictor:
         if save_path is not None:
             Path(save_path).mkdir(parents=True, exist_ok=True)
             out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_ambient.csv", index=False)
+        return out
+
+    # ---------------------------------------------------------------------------------------------
+    def smooth(self, counts, genes, neighbors, normalize=None, include_self: bool = True, index=None) -> Smoothed:
+        """Calls on kNN-POOLED counts: every cell's raw counts are added to those of its nearest neighbours on the device, the
+        pooled row is log-normalised against the pooled library size (``wgnn_hood_rows_count`` / ``_fill``: integer sums in
+        LDS, exact in any order; the rows are stored, one chunk of consecutive cells at a time under ``SMOOTH_CHUNK_BYTES``) and
+        goes through the predictor's own ``classify`` path - every layer, either route.  A pooled cell's call is therefore bit
+        for bit ``classify(..., normalize="lognorm")`` of the host-summed count matrix ``(A + I) @ counts`` (``A @ counts`` with
+        ``include_self=False``), ``A`` = the neighbour indicator.  This is one step of kNN smoothing (Wagner, Yan and Yanai),
+        the idea behind metacells: a 600-read cell that half its marker genes dropped out of borrows depth from the cells
+        around it, before any clustering.  Returns a ``Smoothed``: the call as given next to the pooled call, ``rescued`` /
+        ``lost`` / ``changed`` / ``transitions`` / ``neighbor_agreement`` / ``by_type`` / ``frame`` / ``summary`` on top.
+
+        The batch holds raw integer COUNTS: ``genes=`` and a ``normalize`` spec are required exactly as ``ambient`` requires
+        them (else ``ValueError``), a ``GeneMap`` with merged columns raises ``ValueError``, a count that is no integer in
+        [1, 2^23] raises ``WgnnError`` naming the cell.  The genes may come in any order.  The call as given is ``classify``'s on
+        the lognorm-aligned batch.  ``index``: the cells' names (default ``range(B)``).
+
+        ``neighbors``: the CALLER's graph - an integer ``[B, k]`` array or tensor of cell indices (-1 = no neighbour, so lists
+        may be ragged), or a scipy sparse ``[B, B]`` matrix whose stored non-zero entries of row ``i`` are cell ``i``'s
+        neighbours (``adata.obsp["connectivities"]``; the values are otherwise ignored).  A cell that is its own neighbour is
+        dropped (``include_self`` says whether it takes part); an index outside ``[0, B)``, a neighbour listed twice for one
+        cell and more than 255 neighbours raise ``ValueError``.  A cell without a neighbour keeps its own row (or, with
+        ``include_self=False``, the empty row).
+
+        Out of scope: this does not BUILD the graph - it runs no kNN and no embedding search - and it does not iterate: there
+        is one pooling step over the counts as given.  Pooling across a type boundary blurs a rare cell into its neighbours'
+        type; ``Smoothed.neighbor_agreement`` shows where a neighbourhood straddles two."""
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
+        if genes is None or spec is None:
+            raise ValueError("smooth adds raw counts: pass the batch over its own gene list (genes=) and a normalize spec (the "
+                             "pooled counts are log-normalised against the pooled library size)")
+        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
+        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
+            raise ValueError("smooth does not take merged columns (duplicates=\"sum\"): merging under pooling is not built")
+        B = self._n_cells(counts)
+        if index is not None and len(index) != B:
+            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        hood_ptr, members = _neighbor_lists(neighbors, B, include_self)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._smooth(counts, genes, spec, hood_ptr, members, bool(include_self), index)
+
+    def _smooth(self, counts, genes, spec, hood_ptr, members, include_self, index):
+        dev, G, C = self.device, self.n_genes, self.n_classes
+        batch, gmap, _ = self._caller_batch(counts, genes)         # resolved once: every step below takes the device forms
+        (rowptr, col, cnt), _, lib = self._thin_operands(batch, gmap, spec)
+        _ops.pair_operand_check(rowptr, cnt, "smooth adds up to 256 cells' counts in a 32-bit sum")
+        B = int(rowptr.shape[0]) - 1
+        pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(batch, gmap, None, spec)))
+        lens = (rowptr[1:] - rowptr[:-1]).long().cpu().numpy()
+        per_unit = lambda x: np.diff(np.concatenate([[0], np.cumsum(x[members])])[hood_ptr])      # a unit's sum over its members
+        # chunks of consecutive cells whose pooled rows (at most min(G, the members' row lengths together) entries, 8 bytes each)
+        # fit the budget
+        bound = np.cumsum(np.minimum(per_unit(lens), G) * 8)
+        d_ptr, d_members = torch.from_numpy(hood_ptr).to(dev), torch.from_numpy(members).to(dev)
+        smooth_label, smooth_prob = np.empty(B, np.int64), np.empty(B, np.float32)
+        kept, logits = np.empty(B, np.int64), []
+        for r0, r1 in _byte_chunks(bound, SMOOTH_CHUNK_BYTES):
+            pooled = _ops.hood_rows(rowptr, col, cnt, lib, d_ptr[r0:r1 + 1], d_members, G, scale=float(spec.scale_factor),
+                                    threshold=float(self.threshold))
+            smooth_label[r0:r1], smooth_prob[r0:r1], part, _ = self._classify_on_device(_Aligned(pooled[:3]))
+            logits.append(torch.as_tensor(part))
+            kept[r0:r1] = np.diff(pooled[0].cpu().numpy())
+        return Smoothed(label=pred, max_prob=np.asarray(max_prob, np.float32), smooth_label=smooth_label, smooth_prob=smooth_prob,
+                        logits=torch.cat(logits) if logits else torch.zeros((0, C), dtype=torch.float32, device=dev),
+                        n_neighbors=np.diff(hood_ptr) - (1 if include_self else 0), n_reads=per_unit(lib.cpu().numpy()),
+                        n_genes=lens.astype(np.int64), smooth_n_genes=kept, hood_ptr=hood_ptr, members=members,
+                        index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label),
+                        include_self=include_self, label_map=self._label_names())
+
+    def smooth_file(self, data, neighbors_file, normalize="lognorm", include_self: bool = True, save_path=None) -> pd.DataFrame:
+        """``smooth`` on a test file of raw counts (its full table and gene names) and a neighbours file laid out like the
+        cell-type files - a CSV with a header line; the first column holds a cell's name, the further columns the names of its
+        neighbours, empty fields allowed (ragged lists).  The cells may come in any order; a cell without a line has no
+        neighbour.  A name that is not in the data file, and a cell with two lines, raise ``ValueError``.  Returns
+        ``Smoothed.frame()``, written as ``{species}_{tissue}_smoothed.csv`` under ``save_path`` when given."""
+        df = _read_expression(data, self.file_type)
+        cells = [str(c) for c in df.index]
+        at = {name: i for i, name in enumerate(cells)}
+        if len(at) != len(cells):
+            raise ValueError(f"{data}: a cell name occurs twice")
+        table = pd.read_csv(neighbors_file, dtype=str, keep_default_na=False)
+        lists = np.full((len(cells), max(table.shape[1] - 1, 0)), -1, np.int64)
+        seen = set()
+        for line in table.itertuples(index=False):
+            names = [str(x).strip() for x in line]
+            for name in names:
+                if name and name not in at:
+                    raise ValueError(f"{neighbors_file}: {name!r} is not a cell of {data}")
+            if not names or not names[0]:
+                raise ValueError(f"{neighbors_file}: a line without a cell name")
+            if names[0] in seen:
+                raise ValueError(f"{neighbors_file}: the cell {names[0]!r} has two lines")
+            seen.add(names[0])
+            lists[at[names[0]]] = [at[name] if name else -1 for name in names[1:]]
+        out = self.smooth(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], lists, normalize=normalize,
+                          include_self=include_self, index=df.index).frame()
+        if save_path is not None:
+            Path(save_path).mkdir(parents=True, exist_ok=True)
+            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_smoothed.csv", index=False)
         return out
 
     # ---------------------------------------------------------------------------------------------

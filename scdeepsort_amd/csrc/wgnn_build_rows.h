@@ -1,5 +1,5 @@
 // wgnn_build_rows.h - what the units that BUILD a bundle-vocabulary CSR from raw counts (wgnn_pairs.hip, wgnn_pool.hip,
-// wgnn_soup.hip) share around their walks: the count cap, the per-device marks of a raised dynamic-LDS limit, and the entry
+// wgnn_soup.hip, wgnn_hood.hip) share around their walks: the count cap, the per-device marks of a raised dynamic-LDS limit, and the entry
 // checks of the count-CSR operand and of the log-normalisation.  below(), the lane's rank in a ballot, is one step further up,
 // in wgnn_align_rows.h: the aligning and the thinning kernels use it too.
 //

@@ -1200,7 +1200,7 @@ def csr_rows_ascending(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tenso
 
 
 def _check_lognorm(name, scale, threshold) -> None:
-    """The ``scale`` / ``threshold`` check ``pair_rows``, ``pool_rows_grouped`` and ``soup_rows`` open with."""
+    """The ``scale`` / ``threshold`` check ``pair_rows``, ``pool_rows_grouped``, ``soup_rows`` and ``hood_rows`` open with."""
     if not 0 < float(scale) < float("inf"):
         raise ValueError(f"{name}: scale = {scale} must be positive and finite")
     if not float(threshold) >= 0:
@@ -1208,7 +1208,7 @@ def _check_lognorm(name, scale, threshold) -> None:
 
 
 def _count_csr(name, rowptr, col, cnt, lib=None):
-    """The operand of those three ops - a device CSR of raw counts over the bundle's gene ids, and ``lib`` int64 [B] where the op
+    """The operand of those four ops - a device CSR of raw counts over the bundle's gene ids, and ``lib`` int64 [B] where the op
     takes library sizes - checked (``ValueError`` under the op's ``name``): ``(rowptr, col, cnt, lib, B, nnz, flags)``, the
     tensors contiguous, as the C entries take them."""
     if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
@@ -1484,6 +1484,63 @@ def soup_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     _check_status("soup_rows", int(status), _SOUP_STATUS)
     out = (out_rowptr, out_col, out_val, soup_mapped)
     return out + (out_cnt,) if want_cnt else out
+
+
+_HOOD_STATUS = ((_lib.HOOD_BAD_INDEX, "a member names a row outside [0, n_rows)"),
+                (_lib.HOOD_BAD_ROWPTR, "rowptr points outside col / cnt, hood_ptr is not ascending within [0, n_members], or a unit "
+                                       "kept more entries than were counted"),
+                (_lib.HOOD_BAD_COL, "a gene id is outside [0, n_genes)"),
+                (_lib.HOOD_BAD_SIZE, f"a unit holds more than {_lib.HOOD_MAX_MEMBERS} members"))
+
+
+def hood_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: torch.Tensor, hood_ptr: torch.Tensor,
+              members: torch.Tensor, n_genes: int, scale: float = 1e4, threshold: float = 0.0, slab_genes: int = 0):
+    """``wgnn_hood_rows_count`` / ``wgnn_hood_rows_fill``: the count rows of every unit's members pooled into one log-normalised
+    row - a cell with its nearest neighbours, one step of kNN smoothing.  ``(rowptr int32 / int64 [B+1], col int32, cnt
+    float32)``: a device CSR of raw counts over the bundle's gene ids, every count an integer in [1, 2^23]
+    (``pair_operand_check``); the rows need not be sorted.  ``lib`` int64 [B]: each cell's library size, columns outside the
+    bundle included.  ``hood_ptr`` int64 [U + 1] (ascending) and ``members`` int32 [M]: unit ``q`` pools the rows
+    ``members[hood_ptr[q]:hood_ptr[q + 1]]``, at most 256 of them; the units may overlap, a member listed twice adds twice, and
+    a slice ``hood_ptr[q0:q1 + 1]`` next to the same ``members`` is a valid operand.  Making the lists - a kNN search - is the
+    caller's.
+
+    Unit ``q`` leaves, in ascending gene id, ``float32(log1p(float64(c) / total * scale))`` for every gene with ``c`` = the
+    members' summed count ``> 0`` and a value ``> threshold`` (``>= 0``), ``total`` = the members' summed ``lib`` (the contract
+    in ``include/wgnn.h``): integer sums in LDS, exact, the same bits for any order of the members and any ``slab_genes`` (the
+    kernel's LDS slab width, 0 = its default).  A unit without a member leaves the empty row.  Returns ``(rowptr int64 [U + 1],
+    col int32, val float32, cnt int64)`` on the device; the first three are what ``predict_rows`` takes, ``cnt`` holds the summed
+    count of every kept entry.  The count pass, a ``torch.cumsum``, one read-back of the total to size the outputs, the fill
+    pass, and a read-back of the status word - a member out of range, a ``rowptr`` outside ``col``, a gene id outside
+    ``[0, n_genes)``, a malformed ``hood_ptr`` or a unit of more than 256 members raises ``WgnnError`` (the kernels skip it).
+    Argument errors are ``ValueError``."""
+    dev = _require_cuda(rowptr, col, cnt, lib, hood_ptr, members)
+    _check_lognorm("hood_rows", scale, threshold)
+    rowptr, col, cnt, lib, B, nnz, flags = _count_csr("hood_rows", rowptr, col, cnt, lib)
+    G = int(n_genes)
+    if hood_ptr.dtype != torch.int64 or hood_ptr.dim() != 1 or hood_ptr.shape[0] < 1:
+        raise ValueError("hood_rows: hood_ptr must be an int64 vector [n_units + 1]")
+    if members.dtype != torch.int32 or members.dim() != 1:
+        raise ValueError("hood_rows: members must be an int32 vector")
+    U, M = int(hood_ptr.shape[0]) - 1, int(members.shape[0])
+    if not 0 <= G < 2 ** 31 or B >= 2 ** 31 or U >= 2 ** 31:
+        raise ValueError("hood_rows: n_genes, the rows and the units must each be below 2^31")
+    if not 0 <= int(slab_genes) <= _lib.HOOD_MAX_SLAB_GENES:
+        raise ValueError(f"hood_rows: slab_genes = {slab_genes} must be in [0, {_lib.HOOD_MAX_SLAB_GENES}]")
+    hood_ptr, members = hood_ptr.contiguous(), members.contiguous()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    n_out = torch.empty(U, dtype=torch.int32, device=dev)
+    head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(lib), _ptr(hood_ptr), _ptr(members), U, M, G, float(scale),
+            float(threshold), int(slab_genes))
+    _lib.check(_lib.call(dev, "wgnn_hood_rows_count", *head, _ptr(n_out), _ptr(status), flags, _stream(dev)), "wgnn_hood_rows_count")
+    out_rowptr, total = _scan(n_out)
+    out_col = torch.empty(total, dtype=torch.int32, device=dev)
+    out_val = torch.empty(total, dtype=torch.float32, device=dev)
+    out_cnt = torch.empty(total, dtype=torch.int64, device=dev)
+    if total:
+        _lib.check(_lib.call(dev, "wgnn_hood_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt),
+                             _ptr(status), flags, _stream(dev)), "wgnn_hood_rows_fill")
+    _check_status("hood_rows", int(status), _HOOD_STATUS)
+    return out_rowptr, out_col, out_val, out_cnt
 
 
 def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, table: torch.Tensor, alpha: torch.Tensor,
