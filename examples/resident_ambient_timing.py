@@ -60,7 +60,7 @@ def main():
             am = rp.ambient(batch, genes, **kw)
             # the operands and chunks ambient works on, for the shares timed alone
             with torch.no_grad():
-                (rowptr, col, cnt), _, lib = rp._thin_operands(batch, genes, api.LogNormalize())
+                (rowptr, col, cnt), _, lib, *_ = rp._count_batch(batch, genes, api.LogNormalize(), "ambient", full_call=False)
             bundle = torch.from_numpy(am.profile[0]).cuda()
             cdf = torch.zeros(G + 2, dtype=torch.int64, device="cuda")
             torch.cumsum(torch.cat([bundle, torch.tensor([am.profile[1]], device="cuda")]), 0, out=cdf[1:])

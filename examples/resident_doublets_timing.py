@@ -66,7 +66,7 @@ def main():
             db = rp.doublets(batch, genes, normalize="lognorm", n_partners=N_PARTNERS, seed=1)
             # the operands and chunks doublets works on, for the shares timed alone
             with torch.no_grad():
-                (rowptr, col, cnt), _, lib = rp._thin_operands(batch, genes, api.LogNormalize())
+                (rowptr, col, cnt), _, lib, *_ = rp._count_batch(batch, genes, api.LogNormalize(), "doublets", full_call=False)
             a = torch.arange(B, dtype=torch.int32, device="cuda").repeat_interleave(N_PARTNERS)
             b = torch.from_numpy(db.partner.ravel()).cuda()
             lens = (rowptr[1:] - rowptr[:-1])

@@ -65,7 +65,7 @@ def main():
             rows = torch.repeat_interleave(torch.arange(B, device="cuda"), batch[0][1:] - batch[0][:-1])
             cell_total = torch.zeros(B, dtype=torch.float64, device="cuda").index_add_(0, rows, batch[2].double())
             with torch.no_grad():
-                (rowptr, col, cnt), _, lib = rp._thin_operands(batch, genes, api.LogNormalize())
+                (rowptr, col, cnt), _, lib, *_ = rp._count_batch(batch, genes, api.LogNormalize(), "pseudobulk", full_call=False)
             rng = np.random.default_rng(7)
             for grouping, ids in (("clusters", rng.integers(0, N_CLUSTERS, B)), ("metacells", rng.permutation(B) // METACELL)):
                 K = int(ids.max()) + 1

@@ -71,7 +71,7 @@ def main():
             host = count_batch(B)
             batch = tuple(torch.from_numpy(a).cuda() for a in (host.indptr.astype(np.int64), host.indices, host.data))
             with torch.no_grad():
-                (rowptr, col, cnt), _, lib = rp._thin_operands(batch, genes, api.LogNormalize())
+                (rowptr, col, cnt), _, lib, *_ = rp._count_batch(batch, genes, api.LogNormalize(), "smooth", full_call=False)
             lens = (rowptr[1:] - rowptr[:-1]).cpu().numpy()
             x_dev = torch.sparse_csr_tensor(batch[0], batch[1].long(), batch[2], size=(B, n_cols))
             for k in args.k:

@@ -16,7 +16,7 @@ import os
 import re
 from dataclasses import dataclass, field
 from pathlib import Path
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import pandas as pd
@@ -499,10 +499,14 @@ def _prediction_frame(species, tissue, input_file, index, pred, id2label, bundle
         cols["cell_subtype"] = [old2sub.get(p, p) for p in names]
     else:
         cols["cell_type"] = names
-    out = pd.DataFrame(cols)
+    return _write_table(pd.DataFrame(cols), save_path, species, tissue, Path(input_file).stem)
+
+
+def _write_table(out: pd.DataFrame, save_path, species, tissue, suffix: str) -> pd.DataFrame:
+    """``out``, written as ``{species}_{tissue}_{suffix}.csv`` under ``save_path`` when one is given."""
     if save_path is not None:
-        Path(save_path).mkdir(parents=True, exist_ok=True)
-        out.to_csv(Path(save_path) / f"{species}_{tissue}_{Path(input_file).stem}.csv", index=False)
+        os.makedirs(save_path, exist_ok=True)
+        out.to_csv(Path(save_path) / f"{species}_{tissue}_{suffix}.csv", index=False)
     return out
 
 
@@ -756,6 +760,19 @@ def _call_names(ids, id2label: Sequence[str], label_map=None) -> Tuple[list, lis
     old2new, old2sub = label_map if label_map is not None else ({}, {})
     names = [id2label[p] if p >= 0 else {-1: "unsure", -2: "empty"}.get(int(p)) for p in ids]
     return [old2new.get(p, p) for p in names], [old2sub.get(p, p) for p in names]
+
+
+class _NamesCalls:
+    """For a result table with ``id2label`` and ``label_map``: label ids as the type names ``predict`` gives them."""
+
+    def _name(self, ids) -> list:
+        return _call_names(np.asarray(ids, np.int64), self.id2label, self.label_map)[0]
+
+
+def _check_index(index, B: int) -> None:
+    """``index=`` of a call on a batch of ``B`` cells: one name per cell, when given."""
+    if index is not None and len(index) != B:
+        raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
 
 
 @dataclass
@@ -1363,7 +1380,7 @@ class AmbientSummary(dict):
 
 
 @dataclass
-class Ambient:
+class Ambient(_NamesCalls):
     """What ``ResidentPredictor.ambient`` returns: how a batch's calls fare under ambient-RNA contamination.  B cells (``index``),
     C cell types (``id2label``), L levels (``rho``, ascending: the share of the CONTAMINATED cell's reads that are soup), D draws
     per level.  ``label`` int64 [B] / ``max_prob`` f32 [B]: the call on the cell as given (``classify``'s, -1 = unsure).  Numpy
@@ -1392,9 +1409,6 @@ class Ambient:
     @property
     def n_draws(self) -> int:
         return int(self.draw_label.shape[2])
-
-    def _name(self, ids) -> list:
-        return _call_names(np.asarray(ids, np.int64), self.id2label, self.label_map)[0]
 
     def agreement(self) -> np.ndarray:
         """f64 [B, L]: the share of a cell's draws that keep the call as given; NaN for a cell that is unsure as given."""
@@ -1582,7 +1596,7 @@ class SmoothedSummary(dict):
 
 
 @dataclass
-class Smoothed:
+class Smoothed(_NamesCalls):
     """What ``ResidentPredictor.smooth`` returns: a batch's calls on kNN-POOLED counts next to the calls as given.  B cells
     (``index``), C cell types (``id2label``).  ``label`` int64 [B] / ``max_prob`` f32 [B]: the call on the cell as given
     (``classify``'s, -1 = unsure).  ``smooth_label`` int64 [B] / ``smooth_prob`` f32 [B] / ``logits`` [B, C] (on the device, as
@@ -1608,9 +1622,6 @@ class Smoothed:
     id2label: Sequence[str]
     include_self: bool = True
     label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
-
-    def _name(self, ids) -> list:
-        return _call_names(np.asarray(ids, np.int64), self.id2label, self.label_map)[0]
 
     def _calls(self) -> Tuple[np.ndarray, np.ndarray]:
         return np.asarray(self.label, np.int64), np.asarray(self.smooth_label, np.int64)
@@ -2013,6 +2024,36 @@ class _Aligned:
     csr: Tuple[torch.Tensor, torch.Tensor, torch.Tensor]
 
 
+# The calls that take raw counts, in the words of ``_count_spec``'s two refusals: how the caller asked for the call, what it does
+# to the counts, what the normalize spec is for, and what merged columns would have to be merged under.  The key opens the
+# bad-value error of ``_count_batch``.
+_COUNT_OPS = {
+    "stability": ("thin=\"reads\"", "thins raw counts",
+                  " (the values a draw leaves are log-normalised against the draw's own library size)", "thinning"),
+    "panels": ("renormalize=True", "re-normalises raw counts per panel", "", "panels"),
+    "doublets": ("doublets", "adds raw counts",
+                 " (the summed counts are log-normalised against the sum of the two library sizes)", "pairing"),
+    "ambient": ("ambient", "adds soup reads to raw counts",
+                " (the contaminated counts are log-normalised against the contaminated library size)", "contamination"),
+    "smooth": ("smooth", "adds raw counts", " (the pooled counts are log-normalised against the pooled library size)", "pooling"),
+    "pseudobulk": ("pseudobulk", "adds raw counts",
+                   " (the summed counts are log-normalised against the summed library sizes)", "pooling"),
+}
+
+
+class _CountBatch(NamedTuple):
+    """``ResidentPredictor._count_batch``'s output: a batch of raw counts, resolved and uploaded once, as the count-taking calls
+    use it."""
+    csr: Tuple[torch.Tensor, torch.Tensor, torch.Tensor]      # (rowptr, col, cnt): the counts over the bundle's genes
+    rest: torch.Tensor                               # int64 [B]: a cell's reads outside the bundle
+    lib: torch.Tensor                                # int64 [B]: its library size
+    batch: object                                    # the caller's batch on the device (_caller_batch)
+    gmap: torch.Tensor                               # int32 [n_cols]: a column's bundle gene or -1
+    pred: Optional[np.ndarray] = None                # the call as given (full_call): classify's labels,
+    max_prob: Optional[np.ndarray] = None            # its probabilities (f32)
+    label: Optional[torch.Tensor] = None             # and the labels on the device (int32 [B], either route)
+
+
 class ResidentPredictor:
     """A trained bundle loaded ONCE, its gene side resident on the GPU, classifying any batch of test cells.
 
@@ -2205,7 +2246,10 @@ class ResidentPredictor:
         if spec is None and (isinstance(genes, GeneMap) or (by_name and self.duplicates == "sum")):
             raise ValueError("duplicates=\"sum\" needs normalize=: the batch then holds log-values, and their sum is not the log "
                              "of the summed counts (pass raw counts and normalize=\"lognorm\", or duplicates=\"drop\" / \"first\")")
-        batch, gmap, merged = self._caller_batch(expr, genes)
+        return self._align_batch(*self._caller_batch(expr, genes), threshold, spec)
+
+    def _align_batch(self, batch, gmap, merged, threshold, spec: Optional[LogNormalize]):
+        """``_align`` of a batch that ``_caller_batch`` has resolved already."""
         thr = self.threshold if threshold is None else threshold
         if spec is None:
             return _ops.align_rows(batch, gmap, self.n_genes, float(thr))
@@ -2230,10 +2274,9 @@ class ResidentPredictor:
                                       n_cells=self._n_cells(expr))
             with torch.cuda.device(self.device), torch.no_grad():
                 calls, pred = self._annotate(self._over_genes(expr, genes, normalize), ids, names, None)
-        index = pd.RangeIndex(len(pred)) if index is None else index
-        if len(index) != len(pred):
-            raise ValueError(f"index names {len(index)} cells, the batch holds {len(pred)}")
-        out = _prediction_frame(self.species, self.tissue, "matrix", index, pred, self.id2label, self.bundle, None)
+        _check_index(index, len(pred))
+        out = _prediction_frame(self.species, self.tissue, "matrix", pd.RangeIndex(len(pred)) if index is None else index, pred,
+                                self.id2label, self.bundle, None)
         if clusters is not None:
             per_cluster, _ = calls.consensus(rule, min_fraction)
             per_cell = np.where(ids >= 0, per_cluster[np.maximum(ids, 0)], -3)
@@ -2262,9 +2305,8 @@ class ResidentPredictor:
         detected = self._support_detected
         names = None if isinstance(genes, (torch.Tensor, GeneMap)) else [str(g) for g in genes]
         B = int(n_expressed.shape[0])
+        _check_index(index, B)
         index = pd.RangeIndex(B) if index is None else index
-        if len(index) != B:
-            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
         return Coverage(n_columns=int(ids.shape[0]), n_matched=int(matched.sum()), n_bundle_genes=self.n_genes,
                         n_bundle_absent=int(absent.shape[0]), n_expressed=n_expressed.cpu().numpy(),
                         n_mapped=n_mapped.cpu().numpy(), n_bad=n_bad.cpu().numpy(), total=total.cpu().numpy(),
@@ -2275,8 +2317,8 @@ class ResidentPredictor:
 
     def coverage_file(self, input_file) -> "Coverage":
         """``coverage`` of a test file: its full table and gene names, the cells named by the file's index."""
-        df = _read_expression(input_file, self.file_type)
-        return self.coverage(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], index=df.index)
+        matrix, names, index = self._read_counts_file(input_file)
+        return self.coverage(matrix, names, index=index)
 
     def _device_csr(self, expr):
         """A batch as the kernels take it: (rowptr, col int32, raw f32) on the device, whether its gene ids are in range by
@@ -2318,17 +2360,38 @@ class ResidentPredictor:
             logits = _graph_logits(self.model, self.support, host, self.gene_feat, dev)
             pred, prob = _classify(logits, self.unsure_rate)
             return pred, prob.max(axis=1) if prob.shape[0] else np.zeros(0, np.float32), logits, None
+        def rows(table, alpha, bias, **kw):               # gene ids the caller made are checked in the first layer's launch
+            return _ops.predict_rows(rowptr, col, raw, table, alpha, bias, check_cols=not checked and table is self.tables[0], **kw)
+
+        logits, label, max_prob = self._layers(rows)
+        return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits, label
+
+    def _layers(self, rows, **head_kw):
+        """The fused route's layers over one batch.  ``rows(table, alpha, bias, self_rows=..., **kw)`` launches one layer: a row op
+        of ``ops`` closed over the batch and the operands it takes in every layer.  A hidden layer returns ``h`` [units, Hp], which
+        feeds the next layer's self rows; the last one is launched with the head, the unsure threshold and ``head_kw``, and what
+        it returns is returned."""
         h = None
         for l in range(self.n_layers):
-            self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
-            kw = dict(self_rows=self_rows, check_cols=not checked and l == 0)
-            if l < self.n_layers - 1:
-                h = _ops.predict_rows(rowptr, col, raw, self.tables[l], self.alpha, self.biases[l], **kw)
-            else:
-                logits, label, max_prob = _ops.predict_rows(rowptr, col, raw, self.tables[l], self.alpha, self.biases[l],
-                                                            head=(self.w_head, self.b_head),
-                                                            unsure_threshold=self.unsure_threshold, **kw)
-        return label.cpu().numpy().astype(np.int64), max_prob.cpu().numpy(), logits, label
+            kw = dict(self_rows=None if l == 0 else _ops.linear_fwd(h, self.self_weights[l]))
+            if l == self.n_layers - 1:
+                kw.update(head=(self.w_head, self.b_head), unsure_threshold=self.unsure_threshold, **head_kw)
+            h = rows(self.tables[l], self.alpha, self.biases[l], **kw)
+        return h
+
+    def _cells_per_launch(self, n_units: int) -> int:
+        """Cells per launch of a row op that runs ``n_units`` units (draws, panels) per cell: the [cells x units, Hp] f32
+        intermediates of a deeper model (h, its self rows, the next h) under ``STABILITY_CHUNK_BYTES``, and cells x units below the
+        kernels' 2^31.  Units follow the cell's number in the batch, so chunking changes no bit."""
+        most = (2 ** 31 - 1) // n_units
+        per_cell = n_units * self.hidden_padded * 4 * (3 if self.n_layers > 1 else 0)
+        return most if per_cell == 0 else max(1, min(STABILITY_CHUNK_BYTES // per_cell, most))
+
+    def _require_fused(self, name: str) -> None:
+        """``stability`` and ``panels`` have no graph route: ValueError for a bundle the fused kernels cannot serve."""
+        if self.hidden_padded > 256 or self.n_classes * self.hidden_padded * 4 > _ops.HEAD_LDS_BYTES:
+            raise ValueError(f"{name} runs on the fused kernels only (hidden width <= 256, head <= {_ops.HEAD_LDS_BYTES} bytes); "
+                             f"this bundle has hidden width {self.hidden_padded} and {self.n_classes} cell types")
 
     # ---------------------------------------------------------------------------------------------
     def annotate(self, expr, clusters, cluster_names: Optional[Sequence[str]] = None, n_clusters: Optional[int] = None,
@@ -2357,6 +2420,30 @@ class ResidentPredictor:
         map_file = self.bundle.label_map()
         return None if map_file is None else load_label_map(map_file, self.species)
 
+    def _table_fields(self, B: int, index) -> dict:
+        """The keywords the per-cell result tables share: the cells' names (default ``range(B)``), the cell types, the label map."""
+        return dict(index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label), label_map=self._label_names())
+
+    def _read_counts_file(self, path) -> Tuple[np.ndarray, List[str], pd.Index]:
+        """A test file as ``genes=`` calls take it: its full (cells x genes) float32 table, its gene names, its cell names."""
+        df = _read_expression(path, self.file_type)
+        return df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], df.index
+
+    @staticmethod
+    def _read_clusters_file(path, input_file, index) -> List[str]:
+        """A clusters file laid out as the reference's cell-type files (an index column, the cell's name, its cluster's name) as
+        one stripped ``str`` cluster name per cell of ``input_file``, whose cell names ``index`` holds."""
+        ct = pd.read_csv(path, index_col=0)
+        if ct.shape[1] != 2:
+            raise ValueError(f"{path}: expected an index column, the cell names and the cluster names")
+        ct.columns = ['cell', 'cluster']
+        if [str(c) for c in ct['cell']] != [str(c) for c in index]:
+            raise ValueError(f"cell order of {input_file} and {path} differs")
+        return [str(c).strip() for c in ct['cluster']]
+
+    def _save_frame(self, out: pd.DataFrame, save_path, suffix: str) -> pd.DataFrame:
+        return _write_table(out, save_path, self.species, self.tissue, suffix)
+
     def _annotate(self, expr, ids: np.ndarray, names: Sequence[str], into: Optional[ClusterCalls]):
         """(the table, the per-cell labels) of one classified batch; ``ids`` / ``names`` as ``_cluster_ids`` made them."""
         pred, _, logits, label = self._classify_on_device(expr)
@@ -2379,17 +2466,8 @@ class ResidentPredictor:
         if rule not in ClusterCalls.RULES:
             raise ValueError(f"rule = {rule!r}: pass one of {', '.join(map(repr, ClusterCalls.RULES))}")
         test, index = self._read_test(input_file, normalize)
-        ct = pd.read_csv(clusters_file, index_col=0)
-        if ct.shape[1] != 2:
-            raise ValueError(f"{clusters_file}: expected an index column, the cell names and the cluster names")
-        ct.columns = ['cell', 'cluster']
-        if [str(c) for c in ct['cell']] != [str(c) for c in index]:
-            raise ValueError(f"cell order of {input_file} and {clusters_file} differs")
-        out = self.annotate(test, [str(c).strip() for c in ct['cluster']]).frame(rule, min_fraction)
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_clusters.csv", index=False)
-        return out
+        clusters = self._read_clusters_file(clusters_file, input_file, index)
+        return self._save_frame(self.annotate(test, clusters).frame(rule, min_fraction), save_path, "clusters")
 
     # ---------------------------------------------------------------------------------------------
     def stability(self, expr, keep=(0.75, 0.5, 0.25), n_draws: int = 32, seed: int = 0, genes=None, normalize=None,
@@ -2430,31 +2508,36 @@ class ResidentPredictor:
         B = self._n_cells(expr)
         if into is not None:
             into._require_same(levels, B, self.id2label, seed, thin)
-        if index is not None and len(index) != B:
-            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
-        if self.hidden_padded > 256 or self.n_classes * self.hidden_padded * 4 > _ops.HEAD_LDS_BYTES:
-            raise ValueError(f"stability runs on the fused kernels only (hidden width <= 256, head <= {_ops.HEAD_LDS_BYTES} bytes); "
-                             f"this bundle has hidden width {self.hidden_padded} and {self.n_classes} cell types")
-        if thin == "reads":
-            spec = self.normalize if normalize is None else _normalize_spec(normalize)
-            if genes is None or spec is None:
-                raise ValueError("thin=\"reads\" thins raw counts: pass the batch over its own gene list (genes=) and a normalize "
-                                 "spec (the values a draw leaves are log-normalised against the draw's own library size)")
-            by_name = not isinstance(genes, (torch.Tensor, GeneMap))
-            if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
-                raise ValueError("thin=\"reads\" does not take merged columns (duplicates=\"sum\"): merging under thinning is not built")
-            with torch.cuda.device(self.device), torch.no_grad():
-                return self._stability(None, levels, n_draws, int(seed), index, into, counts=(expr, genes, spec))
+        _check_index(index, B)
+        self._require_fused("stability")
+        counts = (expr, genes, self._count_spec(genes, normalize, "stability")) if thin == "reads" else None
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._stability(self._over_genes(expr, genes, normalize), levels, n_draws, int(seed), index, into)
+            values = None if counts else self._over_genes(expr, genes, normalize)
+            return self._stability(values, levels, n_draws, int(seed), index, into, counts)
 
-    def _thin_operands(self, expr, genes, spec):
-        """``thin="reads"``: the batch's raw counts aligned to the bundle (threshold 0, no normalisation), a cell's reads
-        outside the bundle (int64) and its library size (int64), from one ``coverage_rows`` launch and one fused check."""
-        batch, gmap, _ = self._caller_batch(expr, genes)
+    def _count_spec(self, genes, normalize, op: str) -> LogNormalize:
+        """The normalize spec of a call that takes raw counts (``op``: its key in ``_COUNT_OPS``), which needs ``genes=`` and a
+        spec and takes no merged columns: ValueError otherwise, before anything is launched."""
+        name, what, why, under = _COUNT_OPS[op]
+        spec = self.normalize if normalize is None else _normalize_spec(normalize)
+        if genes is None or spec is None:
+            raise ValueError(f"{name} {what}: pass the batch over its own gene list (genes=) and a normalize spec{why}")
+        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
+        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
+            raise ValueError(f"{name} does not take merged columns (duplicates=\"sum\"): merging under {under} is not built")
+        return spec
+
+    def _count_batch(self, counts, genes, spec: LogNormalize, op: str, *, pair_check: Optional[str] = None,
+                     full_call: bool = True) -> _CountBatch:
+        """What every count-taking call opens with, on a batch resolved and uploaded ONCE (``_caller_batch``): the raw counts
+        aligned to the bundle (threshold 0, no normalisation), a cell's reads outside the bundle and its library size, from one
+        ``coverage_rows`` launch and one fused check (``thin_operand_check``; with ``pair_check``, the sentence
+        ``pair_operand_check`` takes, the 2^23 bound as well) - and, with ``full_call``, the call as given: ``classify``'s on the
+        lognorm-aligned batch.  A bad count raises ``WgnnError`` that opens with ``op``."""
+        batch, gmap, _ = self._caller_batch(counts, genes)
         _, _, n_bad, total, total_mapped, _ = _ops.coverage_rows(batch, gmap, self.n_genes)
         if int(n_bad.sum()):
-            raise WgnnError("stability: a count is negative, NaN or infinite")
+            raise WgnnError(f"{op}: a count is negative, NaN or infinite")
         if spec.library_size is not None:
             lib = spec.library_size if isinstance(spec.library_size, torch.Tensor) else torch.as_tensor(spec.library_size)
             if lib.dim() != 1 or lib.shape[0] != total.shape[0] or lib.is_complex():
@@ -2463,59 +2546,51 @@ class ResidentPredictor:
         rest = total - total_mapped
         csr = _ops.align_rows(batch, gmap, self.n_genes, 0.0)
         _ops.thin_operand_check(csr[0], csr[2], rest, total)
-        return csr, rest.to(torch.int64), total.to(torch.int64)
+        if pair_check is not None:
+            _ops.pair_operand_check(csr[0], csr[2], pair_check)
+        out = _CountBatch(csr, rest.to(torch.int64), total.to(torch.int64), batch, gmap)
+        if not full_call:
+            return out
+        pred, max_prob, _, label = self._classify_on_device(_Aligned(self._align_batch(batch, gmap, None, None, spec)))
+        if label is None:                                 # the graph route classifies on the host
+            label = torch.from_numpy(pred.astype(np.int32)).to(self.device)
+        return out._replace(pred=pred, max_prob=np.asarray(max_prob, np.float32), label=label)
 
     def _stability(self, expr, levels, n_draws, seed, index, into, counts=None):
         dev = self.device
-        thin, rest, n_reads = "genes", None, None
+        thin, n_reads = "genes", None
         if counts is not None:                             # thin="reads": the draws run on the counts, the full call on the values
             thin = "reads"
-            c_expr, c_genes, spec = counts
-            (rowptr, col, raw), rest, n_reads = self._thin_operands(c_expr, c_genes, spec)
-            pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(c_expr, c_genes, None, spec)))
-            thin_kw = dict(scale=float(spec.scale_factor), threshold=float(self.threshold))
+            cb = self._count_batch(*counts, "stability")
+            (rowptr, col, raw), pred, max_prob, n_reads = cb.csr, cb.pred, cb.max_prob, cb.lib
+            draw = functools.partial(_ops.predict_rows_thin, scale=float(counts[2].scale_factor), threshold=float(self.threshold))
         else:
             rowptr, col, raw, checked, _ = self._device_csr(expr)
             if not checked:                                # once for the whole call: every launch below skips the check
                 _ops.check_gene_ids(col, self.n_genes)
             pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
-        B, L, C, Hp = int(rowptr.shape[0]) - 1, len(levels), self.n_classes, self.hidden_padded
+            draw = _ops.predict_rows_dropout
+        B, L, C = int(rowptr.shape[0]) - 1, len(levels), self.n_classes
         if into is None:
             st = Stability(keep=levels, n_draws=0, label=pred, max_prob=np.asarray(max_prob, np.float32),
                            votes=torch.zeros((L, B, C), dtype=torch.int32, device=dev),
                            unsure=torch.zeros((L, B), dtype=torch.int32, device=dev),
                            empty=torch.zeros((L, B), dtype=torch.int32, device=dev),
                            conf_sum=torch.zeros((L, B), dtype=torch.float64, device=dev),
-                           n_entries=np.diff(rowptr.cpu().numpy()).astype(np.int64),
-                           index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label), seed=seed,
-                           label_map=self._label_names(), thin=thin,
-                           n_reads=None if n_reads is None else n_reads.cpu().numpy())
+                           n_entries=np.diff(rowptr.cpu().numpy()).astype(np.int64), seed=seed, thin=thin,
+                           n_reads=None if n_reads is None else n_reads.cpu().numpy(), **self._table_fields(B, index))
         else:
             st = into
         draw0 = st.n_draws
-        # cells per launch: the [cells x draws, Hp] f32 intermediates of a deeper model (h, its self rows, the next h) under the
-        # budget, and cells x draws below the kernel's 2^31
-        per_cell = n_draws * Hp * 4 * (3 if self.n_layers > 1 else 0)
-        step = (2 ** 31 - 1) // n_draws if per_cell == 0 else max(1, min(STABILITY_CHUNK_BYTES // per_cell, (2 ** 31 - 1) // n_draws))
+        step = self._cells_per_launch(n_draws)
         for li, k in enumerate(levels):
             for r0 in range(0, B, step):
                 r1 = min(B, r0 + step)
-                rp = rowptr[r0:r1 + 1]
                 kw = dict(check_cols=False, n_draws=n_draws, keep=k, seed=seed, row0=r0, draw0=draw0)
                 if thin == "reads":
-                    draw = functools.partial(_ops.predict_rows_thin, rest=rest[r0:r1], **thin_kw)
-                else:
-                    draw = _ops.predict_rows_dropout
-                h = None
-                for l in range(self.n_layers):
-                    self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
-                    if l < self.n_layers - 1:
-                        h = draw(rp, col, raw, self.tables[l], self.alpha, self.biases[l], self_rows=self_rows, **kw)
-                    else:
-                        draw(rp, col, raw, self.tables[l], self.alpha, self.biases[l], self_rows=self_rows,
-                             head=(self.w_head, self.b_head), unsure_threshold=self.unsure_threshold,
-                             out=(st.votes[li, r0:r1], st.unsure[li, r0:r1], st.empty[li, r0:r1],
-                                  st.conf_sum[li, r0:r1]), accumulate=draw0 > 0, **kw)
+                    kw["rest"] = cb.rest[r0:r1]
+                self._layers(functools.partial(draw, rowptr[r0:r1 + 1], col, raw, **kw), accumulate=draw0 > 0,
+                             out=(st.votes[li, r0:r1], st.unsure[li, r0:r1], st.empty[li, r0:r1], st.conf_sum[li, r0:r1]))
         st.n_draws = draw0 + n_draws
         return st
 
@@ -2528,16 +2603,12 @@ class ResidentPredictor:
         if thin == "reads":
             if (self.normalize if normalize is None else _normalize_spec(normalize)) is None:
                 raise ValueError("thin=\"reads\" thins raw counts: the file needs a normalize spec")
-            df = _read_expression(input_file, self.file_type)
-            out = self.stability(df.to_numpy(dtype=np.float32), keep=levels, n_draws=n_draws, seed=seed, index=df.index,
-                                 genes=[str(c) for c in df.columns], normalize=normalize, thin=thin).frame()
+            test, genes, index = self._read_counts_file(input_file)
         else:
             test, index = self._read_test(input_file, normalize)
-            out = self.stability(test, keep=levels, n_draws=n_draws, seed=seed, index=index, thin=thin).frame()
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_stability.csv", index=False)
-        return out
+            genes = normalize = None                        # _read_test has applied them
+        out = self.stability(test, keep=levels, n_draws=n_draws, seed=seed, index=index, genes=genes, normalize=normalize, thin=thin)
+        return self._save_frame(out.frame(), save_path, "stability")
 
     # ---------------------------------------------------------------------------------------------
     def panels(self, expr, panels=None, without=None, genes=None, normalize=None, renormalize: bool = False,
@@ -2569,21 +2640,12 @@ class ResidentPredictor:
         by_name = genes is not None and not isinstance(genes, (torch.Tensor, GeneMap))
         spec = None
         if renormalize:
-            spec = self.normalize if normalize is None else _normalize_spec(normalize)
-            if genes is None or spec is None:
-                raise ValueError("renormalize=True re-normalises raw counts per panel: pass the batch over its own gene list (genes=) "
-                                 "and a normalize spec")
+            spec = self._count_spec(genes, normalize, "panels")
             if spec.library_size is not None:
                 raise ValueError("renormalize=True takes a panel's own reads as its library size: LogNormalize(library_size=) does "
                                  "not apply")
-            if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
-                raise ValueError("renormalize=True does not take merged columns (duplicates=\"sum\"): merging under panels is not built")
-        B = self._n_cells(expr)
-        if index is not None and len(index) != B:
-            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
-        if self.hidden_padded > 256 or self.n_classes * self.hidden_padded * 4 > _ops.HEAD_LDS_BYTES:
-            raise ValueError(f"panels runs on the fused kernels only (hidden width <= 256, head <= {_ops.HEAD_LDS_BYTES} bytes); "
-                             f"this bundle has hidden width {self.hidden_padded} and {self.n_classes} cell types")
+        _check_index(index, self._n_cells(expr))
+        self._require_fused("panels")
         column_ids = columns = None
         if genes is not None:
             if by_name:                                    # resolved once: the map goes on to align in place of the names
@@ -2629,10 +2691,9 @@ class ResidentPredictor:
         dev = self.device
         lib = None
         if spec is not None:                               # renormalize: the panels run on the counts, the full call on the values
-            batch, gmap, _ = self._caller_batch(expr, genes)           # on the device once, for the three walks below
-            (rowptr, col, raw), _, _ = self._thin_operands(batch, gmap, spec)
-            lib = self._panel_reads(batch, member_cols)
-            pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(batch, gmap, None, spec)))
+            cb = self._count_batch(expr, genes, spec, "panels")
+            (rowptr, col, raw), pred, max_prob = cb.csr, cb.pred, cb.max_prob
+            lib = self._panel_reads(cb.batch, member_cols)
             mode_kw = dict(scale=float(spec.scale_factor), threshold=float(self.threshold))
         else:
             rowptr, col, raw, checked, _ = self._device_csr(self._over_genes(expr, genes, normalize))
@@ -2640,7 +2701,7 @@ class ResidentPredictor:
                 _ops.check_gene_ids(col, self.n_genes)
             pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
             mode_kw = {}
-        B, P, Hp = int(rowptr.shape[0]) - 1, len(names), self.hidden_padded
+        B, P = int(rowptr.shape[0]) - 1, len(names)
         label = torch.empty((B, P), dtype=torch.int32, device=dev)
         prob = torch.empty((B, P), dtype=torch.float32, device=dev)
         entries = torch.empty((B, P), dtype=torch.int32, device=dev)
@@ -2648,33 +2709,19 @@ class ResidentPredictor:
             p1 = min(P, p0 + _ops.PANELS_PER_LAUNCH)
             n_p = p1 - p0
             member = torch.from_numpy(_member_words(member_genes[p0:p1])).to(dev)
-            # cells per launch: the [cells x panels, Hp] f32 intermediates of a deeper model (h, its self rows, the next h) under
-            # the budget, as _stability chunks its draws
-            per_cell = n_p * Hp * 4 * (3 if self.n_layers > 1 else 0)
-            step = (2 ** 31 - 1) // n_p if per_cell == 0 else max(1, min(STABILITY_CHUNK_BYTES // per_cell, (2 ** 31 - 1) // n_p))
+            step = self._cells_per_launch(n_p)
             for r0 in range(0, B, step):
                 r1 = min(B, r0 + step)
-                rp = rowptr[r0:r1 + 1]
-                kw = dict(check_cols=False, lib=None if lib is None else lib[r0:r1, p0:p1], **mode_kw)
-                h = None
-                for l in range(self.n_layers):
-                    self_rows = None if l == 0 else _ops.linear_fwd(h, self.self_weights[l])
-                    if l < self.n_layers - 1:
-                        h = _ops.predict_rows_panels(rp, col, raw, self.tables[l], self.alpha, self.biases[l], member, n_p,
-                                                     self_rows=self_rows, **kw)
-                    else:
-                        _, lab, mp, ent = _ops.predict_rows_panels(
-                            rp, col, raw, self.tables[l], self.alpha, self.biases[l], member, n_p, self_rows=self_rows,
-                            head=(self.w_head, self.b_head), unsure_threshold=self.unsure_threshold, want_entries=True, **kw)
-                        label[r0:r1, p0:p1], prob[r0:r1, p0:p1], entries[r0:r1, p0:p1] = lab, mp, ent
+                rows = functools.partial(_ops.predict_rows_panels, rowptr[r0:r1 + 1], col, raw, member=member, n_panels=n_p,
+                                         check_cols=False, lib=None if lib is None else lib[r0:r1, p0:p1], **mode_kw)
+                _, label[r0:r1, p0:p1], prob[r0:r1, p0:p1], entries[r0:r1, p0:p1] = self._layers(rows, want_entries=True)
         return PanelCalls(names=names, missing=missing, n_genes=member_genes.sum(axis=1).astype(np.int64),
                           n_columns=None if member_cols is None else member_cols.sum(axis=1).astype(np.int64),
                           label=pred, max_prob=np.asarray(max_prob, np.float32),
                           panel_label=label.cpu().numpy().astype(np.int64), panel_prob=prob.cpu().numpy(),
                           n_entries=entries.cpu().numpy().astype(np.int64),
-                          n_reads=None if lib is None else lib.cpu().numpy(),
-                          index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label),
-                          renormalize=spec is not None, label_map=self._label_names())
+                          n_reads=None if lib is None else lib.cpu().numpy(), renormalize=spec is not None,
+                          **self._table_fields(B, index))
 
     def panels_file(self, input_file, panels=None, without=None, normalize=None, renormalize: bool = False,
                     save_path=None) -> pd.DataFrame:
@@ -2683,13 +2730,10 @@ class ResidentPredictor:
         ``renormalize=True``: the file holds raw counts (a ``normalize`` spec is required)."""
         if renormalize and (self.normalize if normalize is None else _normalize_spec(normalize)) is None:
             raise ValueError("renormalize=True re-normalises raw counts per panel: the file needs a normalize spec")
-        df = _read_expression(input_file, self.file_type)
-        out = self.panels(df.to_numpy(dtype=np.float32), panels=panels, without=without, genes=[str(c) for c in df.columns],
-                          normalize=normalize, renormalize=renormalize, index=df.index).by_type()
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_panels.csv", index=False)
-        return out
+        matrix, genes, index = self._read_counts_file(input_file)
+        out = self.panels(matrix, panels=panels, without=without, genes=genes, normalize=normalize, renormalize=renormalize,
+                          index=index)
+        return self._save_frame(out.by_type(), save_path, "panels")
 
     # ---------------------------------------------------------------------------------------------
     def doublets(self, expr, genes, normalize=None, n_partners: int = 16, across: str = "types", seed: int = 0, index=None,
@@ -2727,32 +2771,21 @@ class ResidentPredictor:
         n_partners = int(n_partners)
         if n_partners < 1:
             raise ValueError(f"n_partners = {n_partners} must be >= 1")
-        spec = self.normalize if normalize is None else _normalize_spec(normalize)
-        if genes is None or spec is None:
-            raise ValueError("doublets adds raw counts: pass the batch over its own gene list (genes=) and a normalize spec (the "
-                             "summed counts are log-normalised against the sum of the two library sizes)")
-        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
-        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
-            raise ValueError("doublets does not take merged columns (duplicates=\"sum\"): merging under pairing is not built")
+        spec = self._count_spec(genes, normalize, "doublets")
         B = self._n_cells(expr)
         if into is not None:
             into._require_same(B, self.id2label, seed, across)
-        if index is not None and len(index) != B:
-            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        _check_index(index, B)
         with torch.cuda.device(self.device), torch.no_grad():
             return self._doublets(expr, genes, spec, n_partners, across, int(seed), index, into)
 
     def _doublets(self, expr, genes, spec, n_partners, across, seed, index, into):
         dev = self.device
-        (rowptr, col, cnt), _, lib = self._thin_operands(expr, genes, spec)
-        _ops.pair_operand_check(rowptr, cnt)
-        rowptr, col, cnt = _ops.csr_rows_ascending(rowptr, col, cnt)
-        pred, max_prob, _, label = self._classify_on_device(_Aligned(self._align(expr, genes, None, spec)))
-        if label is None:                                 # the graph route classifies on the host
-            label = torch.from_numpy(pred.astype(np.int32)).to(dev)
+        cb = self._count_batch(expr, genes, spec, "doublets", pair_check="doublets adds two cells' counts in float32")
+        (rowptr, col, cnt), lib = _ops.csr_rows_ascending(*cb.csr), cb.lib
         B, D = int(rowptr.shape[0]) - 1, n_partners
         draw0 = 0 if into is None else into.n_partners
-        partner = _draw_partners(label, D, seed, across, draw0)
+        partner = _draw_partners(cb.label, D, seed, across, draw0)
         a = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(D)
         b = partner.reshape(-1).contiguous()
         # chunks of consecutive pairs whose merged rows (at most the two rows' lengths, 8 bytes per entry) fit the budget
@@ -2766,9 +2799,8 @@ class ResidentPredictor:
             draw_label[q0:q1], draw_prob[q0:q1] = self._classify_on_device(_Aligned(merged))[:2]
         partner, draw_label, draw_prob = partner.cpu().numpy(), draw_label.reshape(B, D), draw_prob.reshape(B, D)
         if into is None:
-            return Doublets(label=pred, max_prob=np.asarray(max_prob, np.float32), partner=partner, draw_label=draw_label,
-                            draw_prob=draw_prob, index=pd.RangeIndex(B) if index is None else index,
-                            id2label=list(self.id2label), seed=seed, across=across, label_map=self._label_names())
+            return Doublets(label=cb.pred, max_prob=cb.max_prob, partner=partner, draw_label=draw_label, draw_prob=draw_prob,
+                            seed=seed, across=across, **self._table_fields(B, index))
         into.partner = np.concatenate([into.partner, partner], axis=1)
         into.draw_label = np.concatenate([into.draw_label, draw_label], axis=1)
         into.draw_prob = np.concatenate([into.draw_prob, draw_prob], axis=1)
@@ -2778,13 +2810,9 @@ class ResidentPredictor:
                       save_path=None) -> pd.DataFrame:
         """``doublets`` on a test file of raw counts (its full table and gene names): ``Doublets.frame()``, written as
         ``{species}_{tissue}_doublets.csv`` under ``save_path`` when given."""
-        df = _read_expression(input_file, self.file_type)
-        out = self.doublets(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], normalize=normalize,
-                            n_partners=n_partners, across=across, seed=seed, index=df.index).frame()
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_doublets.csv", index=False)
-        return out
+        matrix, genes, index = self._read_counts_file(input_file)
+        out = self.doublets(matrix, genes, normalize=normalize, n_partners=n_partners, across=across, seed=seed, index=index)
+        return self._save_frame(out.frame(), save_path, "doublets")
 
     # ---------------------------------------------------------------------------------------------
     def ambient(self, counts, genes, normalize=None, rho=(0.05, 0.1, 0.2), n_draws: int = 8, profile="batch", seed: int = 0,
@@ -2823,20 +2851,13 @@ class ResidentPredictor:
         n_draws = int(n_draws)
         if n_draws < 1:
             raise ValueError(f"n_draws = {n_draws} must be >= 1")
-        spec = self.normalize if normalize is None else _normalize_spec(normalize)
-        if genes is None or spec is None:
-            raise ValueError("ambient adds soup reads to raw counts: pass the batch over its own gene list (genes=) and a normalize "
-                             "spec (the contaminated counts are log-normalised against the contaminated library size)")
-        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
-        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
-            raise ValueError("ambient does not take merged columns (duplicates=\"sum\"): merging under contamination is not built")
+        spec = self._count_spec(genes, normalize, "ambient")
         if into is not None and not isinstance(into, Ambient):
             raise ValueError("into: pass an earlier Ambient")
         B = self._n_cells(counts)
         if into is not None:
             into._require_same(levels, B, self.id2label, seed)
-        if index is not None and len(index) != B:
-            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        _check_index(index, B)
         if not (isinstance(profile, str) and profile == "batch"):
             if isinstance(profile, str):
                 raise ValueError(f"profile = {profile!r}: pass \"batch\" or one weight per entry of genes")
@@ -2871,11 +2892,10 @@ class ResidentPredictor:
 
     def _ambient(self, counts, genes, spec, levels, n_draws, profile, seed, index, into):
         dev, G, D, L = self.device, self.n_genes, n_draws, len(levels)
-        batch, gmap, _ = self._caller_batch(counts, genes)         # resolved once: every step below takes the device forms
-        (rowptr, col, cnt), _, lib = self._thin_operands(batch, gmap, spec)
-        _ops.pair_operand_check(rowptr, cnt, "ambient adds soup reads to counts held in 32-bit slots")
+        cb = self._count_batch(counts, genes, spec, "ambient", pair_check="ambient adds soup reads to counts held in 32-bit slots")
+        (rowptr, col, cnt), lib = cb.csr, cb.lib
         B = int(rowptr.shape[0]) - 1
-        bundle, rest = self._soup_profile(profile, gmap, rowptr, col, cnt, lib)
+        bundle, rest = self._soup_profile(profile, cb.gmap, rowptr, col, cnt, lib)
         W = int(bundle.sum()) + rest
         if W <= 0:
             raise ValueError("profile: no weight at all (an all-zero soup cannot be drawn from)")
@@ -2886,7 +2906,6 @@ class ResidentPredictor:
             raise ValueError("into: the table was drawn from another soup profile")
         cdf = torch.zeros(G + 2, dtype=torch.int64, device=dev)
         torch.cumsum(torch.cat([bundle, torch.tensor([rest], dtype=torch.int64, device=dev)]), 0, out=cdf[1:])
-        pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(batch, gmap, None, spec)))
         scale, thr = float(spec.scale_factor), float(self.threshold)
         # the soup itself: the profile as one pooled row against its own total
         nz = torch.nonzero(bundle).reshape(-1)
@@ -2919,10 +2938,9 @@ class ResidentPredictor:
                 draw_label[r0:r1, li], draw_prob[r0:r1, li] = lab.reshape(r1 - r0, D), np.asarray(prob).reshape(r1 - r0, D)
                 n_mapped[r0:r1, li] = mapped.cpu().numpy().reshape(r1 - r0, D)
         if into is None:
-            return Ambient(rho=levels, label=pred, max_prob=np.asarray(max_prob, np.float32), draw_label=draw_label, draw_prob=draw_prob,
+            return Ambient(rho=levels, label=cb.pred, max_prob=cb.max_prob, draw_label=draw_label, draw_prob=draw_prob,
                            n_added=n_added, n_mapped=n_mapped, soup_label=int(s_pred[0]), soup_prob=float(np.asarray(s_prob)[0]),
-                           profile=host_profile, index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label),
-                           seed=seed, label_map=self._label_names())
+                           profile=host_profile, seed=seed, **self._table_fields(B, index))
         into.draw_label = np.concatenate([into.draw_label, draw_label], axis=2)
         into.draw_prob = np.concatenate([into.draw_prob, draw_prob], axis=2)
         into.n_mapped = np.concatenate([into.n_mapped, n_mapped], axis=2)
@@ -2932,13 +2950,9 @@ class ResidentPredictor:
                      save_path=None) -> pd.DataFrame:
         """``ambient`` on a test file of raw counts (its full table and gene names): ``Ambient.frame()``, written as
         ``{species}_{tissue}_ambient.csv`` under ``save_path`` when given."""
-        df = _read_expression(data, self.file_type)
-        out = self.ambient(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], normalize=normalize, rho=rho,
-                           n_draws=n_draws, profile=profile, seed=seed, index=df.index).frame()
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_ambient.csv", index=False)
-        return out
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.ambient(matrix, genes, normalize=normalize, rho=rho, n_draws=n_draws, profile=profile, seed=seed, index=index)
+        return self._save_frame(out.frame(), save_path, "ambient")
 
     # ---------------------------------------------------------------------------------------------
     def smooth(self, counts, genes, neighbors, normalize=None, include_self: bool = True, index=None) -> Smoothed:
@@ -2967,27 +2981,18 @@ class ResidentPredictor:
         Out of scope: this does not BUILD the graph - it runs no kNN and no embedding search - and it does not iterate: there
         is one pooling step over the counts as given.  Pooling across a type boundary blurs a rare cell into its neighbours'
         type; ``Smoothed.neighbor_agreement`` shows where a neighbourhood straddles two."""
-        spec = self.normalize if normalize is None else _normalize_spec(normalize)
-        if genes is None or spec is None:
-            raise ValueError("smooth adds raw counts: pass the batch over its own gene list (genes=) and a normalize spec (the "
-                             "pooled counts are log-normalised against the pooled library size)")
-        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
-        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
-            raise ValueError("smooth does not take merged columns (duplicates=\"sum\"): merging under pooling is not built")
+        spec = self._count_spec(genes, normalize, "smooth")
         B = self._n_cells(counts)
-        if index is not None and len(index) != B:
-            raise ValueError(f"index names {len(index)} cells, the batch holds {B}")
+        _check_index(index, B)
         hood_ptr, members = _neighbor_lists(neighbors, B, include_self)
         with torch.cuda.device(self.device), torch.no_grad():
             return self._smooth(counts, genes, spec, hood_ptr, members, bool(include_self), index)
 
     def _smooth(self, counts, genes, spec, hood_ptr, members, include_self, index):
         dev, G, C = self.device, self.n_genes, self.n_classes
-        batch, gmap, _ = self._caller_batch(counts, genes)         # resolved once: every step below takes the device forms
-        (rowptr, col, cnt), _, lib = self._thin_operands(batch, gmap, spec)
-        _ops.pair_operand_check(rowptr, cnt, "smooth adds up to 256 cells' counts in a 32-bit sum")
+        cb = self._count_batch(counts, genes, spec, "smooth", pair_check="smooth adds up to 256 cells' counts in a 32-bit sum")
+        (rowptr, col, cnt), lib = cb.csr, cb.lib
         B = int(rowptr.shape[0]) - 1
-        pred, max_prob, _, _ = self._classify_on_device(_Aligned(self._align(batch, gmap, None, spec)))
         lens = (rowptr[1:] - rowptr[:-1]).long().cpu().numpy()
         per_unit = lambda x: np.diff(np.concatenate([[0], np.cumsum(x[members])])[hood_ptr])      # a unit's sum over its members
         # chunks of consecutive cells whose pooled rows (at most min(G, the members' row lengths together) entries, 8 bytes each)
@@ -3002,12 +3007,11 @@ class ResidentPredictor:
             smooth_label[r0:r1], smooth_prob[r0:r1], part, _ = self._classify_on_device(_Aligned(pooled[:3]))
             logits.append(torch.as_tensor(part))
             kept[r0:r1] = np.diff(pooled[0].cpu().numpy())
-        return Smoothed(label=pred, max_prob=np.asarray(max_prob, np.float32), smooth_label=smooth_label, smooth_prob=smooth_prob,
+        return Smoothed(label=cb.pred, max_prob=cb.max_prob, smooth_label=smooth_label, smooth_prob=smooth_prob,
                         logits=torch.cat(logits) if logits else torch.zeros((0, C), dtype=torch.float32, device=dev),
                         n_neighbors=np.diff(hood_ptr) - (1 if include_self else 0), n_reads=per_unit(lib.cpu().numpy()),
                         n_genes=lens.astype(np.int64), smooth_n_genes=kept, hood_ptr=hood_ptr, members=members,
-                        index=pd.RangeIndex(B) if index is None else index, id2label=list(self.id2label),
-                        include_self=include_self, label_map=self._label_names())
+                        include_self=include_self, **self._table_fields(B, index))
 
     def smooth_file(self, data, neighbors_file, normalize="lognorm", include_self: bool = True, save_path=None) -> pd.DataFrame:
         """``smooth`` on a test file of raw counts (its full table and gene names) and a neighbours file laid out like the
@@ -3015,8 +3019,8 @@ class ResidentPredictor:
         neighbours, empty fields allowed (ragged lists).  The cells may come in any order; a cell without a line has no
         neighbour.  A name that is not in the data file, and a cell with two lines, raise ``ValueError``.  Returns
         ``Smoothed.frame()``, written as ``{species}_{tissue}_smoothed.csv`` under ``save_path`` when given."""
-        df = _read_expression(data, self.file_type)
-        cells = [str(c) for c in df.index]
+        matrix, genes, index = self._read_counts_file(data)
+        cells = [str(c) for c in index]
         at = {name: i for i, name in enumerate(cells)}
         if len(at) != len(cells):
             raise ValueError(f"{data}: a cell name occurs twice")
@@ -3034,12 +3038,8 @@ class ResidentPredictor:
                 raise ValueError(f"{neighbors_file}: the cell {names[0]!r} has two lines")
             seen.add(names[0])
             lists[at[names[0]]] = [at[name] if name else -1 for name in names[1:]]
-        out = self.smooth(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], lists, normalize=normalize,
-                          include_self=include_self, index=df.index).frame()
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_smoothed.csv", index=False)
-        return out
+        out = self.smooth(matrix, genes, lists, normalize=normalize, include_self=include_self, index=index)
+        return self._save_frame(out.frame(), save_path, "smoothed")
 
     # ---------------------------------------------------------------------------------------------
     def pseudobulk(self, expr, genes, clusters, normalize=None, cluster_names: Optional[Sequence[str]] = None,
@@ -3061,13 +3061,7 @@ class ResidentPredictor:
         ``into``: an earlier ``Pseudobulk`` of the same bundle and cluster names; this batch is pooled ON TOP of it, the
         clusters are classified again, and ``into`` is returned: two halves of a cohort equal the whole, bit for bit.  It needs
         the predictor's ``threshold`` to be 0 (a pooled row that dropped entries cannot be added to)."""
-        spec = self.normalize if normalize is None else _normalize_spec(normalize)
-        if genes is None or spec is None:
-            raise ValueError("pseudobulk adds raw counts: pass the batch over its own gene list (genes=) and a normalize spec (the "
-                             "summed counts are log-normalised against the summed library sizes)")
-        by_name = not isinstance(genes, (torch.Tensor, GeneMap))
-        if (isinstance(genes, GeneMap) and genes.n_merged_columns) or (by_name and self.duplicates == "sum"):
-            raise ValueError("pseudobulk does not take merged columns (duplicates=\"sum\"): merging under pooling is not built")
+        spec = self._count_spec(genes, normalize, "pseudobulk")
         if into is not None and not isinstance(into, Pseudobulk):
             raise ValueError("into: pass an earlier Pseudobulk")
         ids, names = _cluster_ids(clusters, cluster_names, n_clusters, into=into,
@@ -3081,8 +3075,9 @@ class ResidentPredictor:
 
     def _pseudobulk(self, expr, genes, spec, ids, names, into):
         dev = self.device
-        (rowptr, col, cnt), _, lib = self._thin_operands(expr, genes, spec)
-        _ops.pair_operand_check(rowptr, cnt, "pseudobulk adds up to 256 cells' counts in a 32-bit partial sum")
+        cb = self._count_batch(expr, genes, spec, "pseudobulk", full_call=False,
+                               pair_check="pseudobulk adds up to 256 cells' counts in a 32-bit partial sum")
+        (rowptr, col, cnt), lib = cb.csr, cb.lib
         group = torch.from_numpy(ids.astype(np.int32)).to(dev)
         seed = None if into is None else (into.rowptr, into.col, into.cnt, torch.from_numpy(np.asarray(into.n_reads, np.int64)).to(dev),
                                           torch.from_numpy(np.asarray(into.n_cells, np.int64)).to(dev))
@@ -3105,19 +3100,9 @@ class ResidentPredictor:
         ``annotate_file`` takes it (an index column, the cell's name, its cluster's name; the cells in the data file's order,
         else ``ValueError``): ``Pseudobulk.frame()``, written as ``{species}_{tissue}_pseudobulk.csv`` under ``save_path`` when
         given.  Cluster names are compared as stripped ``str`` and come in sorted order."""
-        df = _read_expression(input_file, self.file_type)
-        ct = pd.read_csv(clusters_file, index_col=0)
-        if ct.shape[1] != 2:
-            raise ValueError(f"{clusters_file}: expected an index column, the cell names and the cluster names")
-        ct.columns = ['cell', 'cluster']
-        if [str(c) for c in ct['cell']] != [str(c) for c in df.index]:
-            raise ValueError(f"cell order of {input_file} and {clusters_file} differs")
-        out = self.pseudobulk(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns],
-                              [str(c).strip() for c in ct['cluster']], normalize=normalize).frame()
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_pseudobulk.csv", index=False)
-        return out
+        matrix, genes, index = self._read_counts_file(input_file)
+        clusters = self._read_clusters_file(clusters_file, input_file, index)
+        return self._save_frame(self.pseudobulk(matrix, genes, clusters, normalize=normalize).frame(), save_path, "pseudobulk")
 
     # ---------------------------------------------------------------------------------------------
     def explain(self, expr, top_k: int = 10, target="predicted", genes=None, normalize=None) -> "Attribution":
@@ -3256,10 +3241,9 @@ class ResidentPredictor:
         spec = self.normalize if normalize is None else _normalize_spec(normalize)
         if spec is None and self.aliases is None and self.duplicates == "error":
             return _read_test_csr(input_file, self.file_type, self._gene2id, self.threshold)
-        df = _read_expression(input_file, self.file_type)       # aliases / duplicates are align's: the file goes through it
+        matrix, genes, index = self._read_counts_file(input_file)       # aliases / duplicates are align's: the file goes through it
         with torch.cuda.device(self.device), torch.no_grad():
-            csr = self._align(df.to_numpy(dtype=np.float32), [str(c) for c in df.columns], None, spec)
-        return _Aligned(csr), df.index
+            return _Aligned(self._align(matrix, genes, None, spec)), index
 
     def markers_files(self, files, top_k: int = 20, min_fraction: float = 0.0, save_path=None, normalize=None) -> pd.DataFrame:
         """``markers`` over test files streamed into one table (groups = the predicted types), as ``frame(top_k)`` with
@@ -3280,10 +3264,7 @@ class ResidentPredictor:
             out.insert(0, "cell_type", [old2new.get(p, p) for p in names])
         else:
             out.insert(0, "cell_type", names)
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_markers.csv", index=False)
-        return out
+        return self._save_frame(out, save_path, "markers")
 
     def predict(self, input_file, save_path=None, normalize=None) -> pd.DataFrame:
         """``DeepSortPredictor.predict`` on the resident bundle: same columns, label-map handling and output file name.
@@ -3306,10 +3287,7 @@ class ResidentPredictor:
         out["rank"] = k + 1
         out["gene"] = [self.id2gene[g] for g in att.top_genes[r, k]]
         out["score"] = att.top_scores[r, k]
-        if save_path is not None:
-            Path(save_path).mkdir(parents=True, exist_ok=True)
-            out.to_csv(Path(save_path) / f"{self.species}_{self.tissue}_{Path(input_file).stem}_genes.csv", index=False)
-        return out
+        return self._save_frame(out, save_path, f"{Path(input_file).stem}_genes")
 
     def predict_many(self, files, save_path=None, normalize=None) -> List[pd.DataFrame]:
         """One table per test file (``predict.py --test_dataset 1 2 3``), the bundle loaded once.  ``normalize``: as for
