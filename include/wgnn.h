@@ -318,6 +318,25 @@ int wgnn_linear_fwd_ex(const void* x, int x_dtype, int64_t ld_x, const float* w,
 int wgnn_linear_fwd(const float* x, int64_t ld_x, const float* w, int64_t ld_w, const float* bias,
                     float* out, int64_t ld_out, int64_t M, int32_t N, int32_t K, uint32_t flags, void* stream);
 
+/* Two-operand loader (additive exports, WGNN_VERSION stays 206): the same product with its A operand formed on the way into
+ * LDS from two row tables and two per-row coefficient vectors, in exactly this order of operations:
+ *     a[m, k]  = fmaf(c2[m], x2[m, k], c1[m] * x1[m, k])       (c1 * x1 rounded to fp32 first, then ONE fused multiply-add)
+ *     out      = act(a . w^T + bias),   out_scaled[m, :] = row_scale[m] * out[m, :]      (either output may be NULL, as above)
+ * No [M, K] intermediate goes through HBM.  It serves layer 1's genes<-cells rows from a cached feature sum S = A_gc . X_c
+ * (the aggregation is linear and alpha[r] is a per-DESTINATION factor on that side, so sum_c w_rc (X_c W^T)[c] = (S W^T)[r]):
+ *     x1 = S, x2 = X_g, c1[r] = alpha[r] * inv_deg[r], c2[r] = alpha[G] * inv_deg[r]
+ * The coefficients are two [M] vectors (not alpha / inv_deg / self_idx folded into the entry: the product then stays a plain
+ * function of its operands); wgnn_mix_coeffs writes both in one small launch.
+ * x1: fp32, 16-byte aligned; x2: WGNN_F32 (16-byte aligned) or WGNN_F16 (8-byte aligned, widened by the loader that
+ * wgnn_linear_fwd_ex uses); K, ld_x1, ld_x2, ld_w multiples of 4; ld_* >= K (inputs) / N (outputs); M, N arbitrary; flags as
+ * wgnn_linear_fwd_ex. */
+int wgnn_linear_mix_fwd(const float* x1, int64_t ld_x1, const float* c1, const void* x2, int x2_dtype, int64_t ld_x2,
+                        const float* c2, const float* w, int64_t ld_w, const float* bias,
+                        float* out, int64_t ld_out, const float* row_scale, float* out_scaled, int64_t ld_out_scaled,
+                        int64_t M, int32_t N, int32_t K, uint32_t flags, void* stream);
+/* c1[i] = alpha[i] * inv_deg[i], c2[i] = alpha[self_idx] * inv_deg[i] for i in [0, n). */
+int wgnn_mix_coeffs(const float* alpha, int32_t self_idx, const float* inv_deg, float* c1, float* c2, int64_t n, void* stream);
+
 /* Weight gradient of the same Linear (autograd of fc_neigh / linear, train.py:84):
  *     dW[N, K] (+)= sum_m g[m, N] * x[m, K]
  * The node axis M (1e5 at cfg3) is the reduction: it is cut into n_slabs slabs whose partial [N, K] products are folded in

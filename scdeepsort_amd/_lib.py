@@ -60,6 +60,10 @@ SIGNATURES = {
     "wgnn_sample_rows": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, C.c_uint64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wgnn_linear_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _u32, _vp]),
     "wgnn_linear_fwd_ex": (C.c_int, [_vp, _int, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _u32, _vp]),
+    # additive exports (the version stays 206): the two-operand loader of the same GEMM and its row coefficients
+    "wgnn_linear_mix_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _int, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64,
+                                      _i64, _i32, _i32, _u32, _vp]),
+    "wgnn_mix_coeffs": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     "wgnn_linear_wgrad_workspace": (C.c_int, [_i64, _i32, _i32, _vp, _vp]),
     "wgnn_linear_wgrad": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _int, _vp, _i64, _vp]),
     "wgnn_agg_bwd_prepare_workspace": (C.c_int, [_i64, _i32, _vp]),

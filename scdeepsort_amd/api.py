@@ -298,7 +298,8 @@ class DeepSortClassifier:
                 return 1.0, 0
             model.eval()
             with torch.no_grad():
-                pred, _ = _classify(model(graph, feats, seeds=ids), 2.0)
+                # the same (graph, feats) after every weight update: layer 1's gene rows come from the graph's cached feature sum
+                pred, _ = _classify(model(graph, feats, seeds=ids, feature_sum_cache=True), 2.0)
             truth = y[ids - G].cpu().numpy()
             return float((pred == truth).mean()), int((pred < 0).sum())
 

@@ -31,6 +31,8 @@ constexpr int kLinThreads = 256;
 
 struct LinArgs {
     const void* x; long ld_x;            // f32 or f16 rows (TX); f16 is widened in registers on the way into LDS
+    const float* x1; long ld_x1;         // MIX only: the first operand of the two-operand loader (f32 rows), `x` is the second
+    const float* c1; const float* c2;    // MIX only: per-row coefficients [M] of x1 / x
     const float* w; long ld_w;
     const float* bias;
     float* out; long ld_out;             // may be null when only the scaled copy is wanted
@@ -47,7 +49,10 @@ struct LinArgs {
 // MI = 32-row MFMA blocks per wave along M: 2 -> 128 x 128 tiles (wave 64 x 64), 1 -> 64 x 128 tiles (wave 32 x 64).  The
 // smaller tile is for operands whose 128-row tiling leaves the last round of workgroups thin (20k rows = 157 x 2 tiles on
 // 256 CUs): twice the tiles, up to 6 workgroups per CU.
-template <typename TX, bool DUAL, int MI>
+// MIX: the A operand is formed in the loader from two row tables, a[m, k] = fmaf(c2[m], x[m, k], c1[m] * x1[m, k]) (the product
+// rounded first, then one fused multiply-add) - the gene rows of layer 1 served from a cached feature sum S = A_gc X_c:
+// x1 = S, x = X_g, c1 = alpha[r] * inv_deg[r], c2 = alpha[G] * inv_deg[r]; no [G, D_in] intermediate goes through HBM.
+template <typename TX, bool DUAL, int MI, bool MIX>
 __global__ void __launch_bounds__(kLinThreads, 4) linear_mfma_f32(const LinArgs a) {
     constexpr int kBM = 64 * MI;
     __shared__ float As[2][kBM * kLd];
@@ -72,12 +77,28 @@ __global__ void __launch_bounds__(kLinThreads, 4) linear_mfma_f32(const LinArgs 
     constexpr int kNPA = kBM / kRPP, kNPW = kBN / kRPP;        // passes over the X tile / the W tile
     const int lr = t / kTPR, lk = (t % kTPR) * 4;
     float4 xa[kNPA], wa[kNPW];
+    float c1r[kNPA], c2r[kNPA];                                // MIX: this thread's rows keep their coefficients for every slab
+    if constexpr (MIX) {
+#pragma unroll
+        for (int i = 0; i < kNPA; ++i) {
+            const long row = m0 + lr + kRPP * i;
+            c1r[i] = row < a.M ? a.c1[row] : 0.f;
+            c2r[i] = row < a.M ? a.c2[row] : 0.f;
+        }
+    }
     auto gload = [&](int k0) {
         const bool kin = k0 + lk < a.K;                        // K % 4 == 0: a float4 is inside or outside as a whole
 #pragma unroll
         for (int i = 0; i < kNPA; ++i) {
             const long row = m0 + lr + kRPP * i;
             xa[i] = (row < a.M && kin) ? ld4(reinterpret_cast<const TX*>(a.x) + row * a.ld_x + k0 + lk) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (MIX) {
+                const float4 s = (row < a.M && kin) ? ld4(a.x1 + row * a.ld_x1 + k0 + lk) : make_float4(0.f, 0.f, 0.f, 0.f);
+                xa[i].x = __fmaf_rn(c2r[i], xa[i].x, __fmul_rn(c1r[i], s.x));
+                xa[i].y = __fmaf_rn(c2r[i], xa[i].y, __fmul_rn(c1r[i], s.y));
+                xa[i].z = __fmaf_rn(c2r[i], xa[i].z, __fmul_rn(c1r[i], s.z));
+                xa[i].w = __fmaf_rn(c2r[i], xa[i].w, __fmul_rn(c1r[i], s.w));
+            }
         }
 #pragma unroll
         for (int i = 0; i < kNPW; ++i) {
@@ -250,6 +271,43 @@ __global__ void __launch_bounds__(256) wgrad_reduce(const float* __restrict__ pa
     *o = accumulate ? *o + s : s;
 }
 
+// c1[r] = alpha[r] * inv_deg[r], c2[r] = alpha[self_idx] * inv_deg[r]: the row coefficients of the two-operand loader
+__global__ void __launch_bounds__(256) mix_coeffs(const float* __restrict__ alpha, int self_idx, const float* __restrict__ inv_deg,
+                                                  float* __restrict__ c1, float* __restrict__ c2, long n) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float d = inv_deg[i];
+    c1[i] = alpha[i] * d;
+    c2[i] = alpha[self_idx] * d;
+}
+
+// tile height: 128 rows, or 64 when that fills the chip's last round of workgroups better (4 resident workgroups per CU
+// at 128 rows, 6 at 64); a.x1 != nullptr selects the two-operand loader
+int launch_linear(const LinArgs& a, int x_dtype, unsigned flags, void* stream) {
+    const long col_tiles = (a.N + kBN - 1) / kBN;
+    const long t128 = ((a.M + 127) / 128) * col_tiles, t64 = ((a.M + 63) / 64) * col_tiles;
+    auto round_fill = [](long tiles, long slots) { const long r = (tiles + slots - 1) / slots; return (double)tiles / (double)(r * slots); };
+    const bool small = (flags & WGNN_LIN_FORCE_64) || (!(flags & WGNN_LIN_FORCE_128) && round_fill(t64, 256 * 6) > round_fill(t128, 256 * 4) + 0.05);
+    const long tiles = small ? t64 : t128;
+    if (tiles > 0x7FFFFFFFL) return WGNN_ERR_UNSUPPORTED;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)tiles), block(kLinThreads);
+#define WGNN_LIN_LAUNCH(TX, DUAL, MIX)                                                                         \
+    do {                                                                                                       \
+        if (small) hipLaunchKernelGGL((linear_mfma_f32<TX, DUAL, 1, MIX>), grid, block, 0, st, a);             \
+        else hipLaunchKernelGGL((linear_mfma_f32<TX, DUAL, 2, MIX>), grid, block, 0, st, a);                   \
+    } while (0)
+#define WGNN_LIN_PICK(TX)                                                                                      \
+    do {                                                                                                       \
+        if (a.x1) { if (a.out2) WGNN_LIN_LAUNCH(TX, true, true); else WGNN_LIN_LAUNCH(TX, false, true); }      \
+        else { if (a.out2) WGNN_LIN_LAUNCH(TX, true, false); else WGNN_LIN_LAUNCH(TX, false, false); }         \
+    } while (0)
+    if (x_dtype == WGNN_F16) WGNN_LIN_PICK(__half); else WGNN_LIN_PICK(float);
+#undef WGNN_LIN_PICK
+#undef WGNN_LIN_LAUNCH
+    return hipGetLastError() == hipSuccess ? WGNN_OK : WGNN_ERR_LAUNCH;
+}
+
 }  // namespace
 
 extern "C" int wgnn_linear_wgrad_workspace(int64_t M, int32_t N, int32_t K, int64_t* n_slabs, int64_t* bytes) {
@@ -298,29 +356,35 @@ extern "C" int wgnn_linear_fwd_ex(const void* x, int x_dtype, int64_t ld_x, cons
     if (x_dtype == WGNN_F32 ? !aligned16(x) : !aligned8(x)) return WGNN_ERR_ALIGNMENT;
     if (ld_x < K || ld_w < K || (out && ld_out < N) || (out_scaled && ld_out_scaled < N)) return WGNN_ERR_BAD_ARG;
     if (M == 0) return WGNN_OK;
-    // tile height: 128 rows, or 64 when that fills the chip's last round of workgroups better (4 resident workgroups per CU
-    // at 128 rows, 6 at 64)
-    const long col_tiles = (N + kBN - 1) / kBN;
-    const long t128 = ((M + 127) / 128) * col_tiles, t64 = ((M + 63) / 64) * col_tiles;
-    auto round_fill = [](long tiles, long slots) { const long r = (tiles + slots - 1) / slots; return (double)tiles / (double)(r * slots); };
-    const bool small = (flags & WGNN_LIN_FORCE_64) || (!(flags & WGNN_LIN_FORCE_128) && round_fill(t64, 256 * 6) > round_fill(t128, 256 * 4) + 0.05);
-    const long tiles = small ? t64 : t128;
-    if (tiles > 0x7FFFFFFFL) return WGNN_ERR_UNSUPPORTED;
-    LinArgs a{x, (long)ld_x, w, (long)ld_w, bias, out, (long)ld_out, row_scale, out_scaled, (long)ld_out_scaled, (long)M, N, K,
-              flags & WGNN_FLAG_RELU};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)tiles), block(kLinThreads);
-#define WGNN_LIN_LAUNCH(TX, DUAL)                                                                              \
-    do {                                                                                                       \
-        if (small) hipLaunchKernelGGL((linear_mfma_f32<TX, DUAL, 1>), grid, block, 0, st, a);                  \
-        else hipLaunchKernelGGL((linear_mfma_f32<TX, DUAL, 2>), grid, block, 0, st, a);                        \
-    } while (0)
-    if (x_dtype == WGNN_F16) {
-        if (out_scaled) WGNN_LIN_LAUNCH(__half, true); else WGNN_LIN_LAUNCH(__half, false);
-    } else {
-        if (out_scaled) WGNN_LIN_LAUNCH(float, true); else WGNN_LIN_LAUNCH(float, false);
-    }
-#undef WGNN_LIN_LAUNCH
+    LinArgs a{x, (long)ld_x, nullptr, 0, nullptr, nullptr, w, (long)ld_w, bias, out, (long)ld_out, row_scale, out_scaled,
+              (long)ld_out_scaled, (long)M, N, K, flags & WGNN_FLAG_RELU};
+    return launch_linear(a, x_dtype, flags, stream);
+}
+
+extern "C" int wgnn_linear_mix_fwd(const float* x1, int64_t ld_x1, const float* c1, const void* x2, int x2_dtype, int64_t ld_x2,
+                                   const float* c2, const float* w, int64_t ld_w, const float* bias,
+                                   float* out, int64_t ld_out, const float* row_scale, float* out_scaled, int64_t ld_out_scaled,
+                                   int64_t M, int32_t N, int32_t K, uint32_t flags, void* stream) {
+    if (!x1 || !x2 || !c1 || !c2 || !w || (!out && !out_scaled) || M < 0 || N <= 0 || K <= 0) return WGNN_ERR_BAD_ARG;
+    if (flags & ~(WGNN_FLAG_RELU | WGNN_LIN_FORCE_64 | WGNN_LIN_FORCE_128)) return WGNN_ERR_BAD_ARG;
+    if (x2_dtype != WGNN_F32 && x2_dtype != WGNN_F16) return WGNN_ERR_BAD_ARG;
+    if ((out_scaled != nullptr) != (row_scale != nullptr)) return WGNN_ERR_BAD_ARG;
+    if (K % 4 || ld_x1 % 4 || ld_x2 % 4 || ld_w % 4 || !aligned16(w) || !aligned16(x1)) return WGNN_ERR_ALIGNMENT;
+    if (x2_dtype == WGNN_F32 ? !aligned16(x2) : !aligned8(x2)) return WGNN_ERR_ALIGNMENT;
+    if (ld_x1 < K || ld_x2 < K || ld_w < K || (out && ld_out < N) || (out_scaled && ld_out_scaled < N)) return WGNN_ERR_BAD_ARG;
+    if (M == 0) return WGNN_OK;
+    LinArgs a{x2, (long)ld_x2, x1, (long)ld_x1, c1, c2, w, (long)ld_w, bias, out, (long)ld_out, row_scale, out_scaled,
+              (long)ld_out_scaled, (long)M, N, K, flags & WGNN_FLAG_RELU};
+    return launch_linear(a, x2_dtype, flags, stream);
+}
+
+extern "C" int wgnn_mix_coeffs(const float* alpha, int32_t self_idx, const float* inv_deg, float* c1, float* c2, int64_t n,
+                               void* stream) {
+    if (!alpha || !inv_deg || !c1 || !c2 || n < 0 || self_idx < 0) return WGNN_ERR_BAD_ARG;
+    if (n == 0) return WGNN_OK;
+    if ((n + 255) / 256 > 0x7FFFFFFFL) return WGNN_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(mix_coeffs, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), alpha,
+                       self_idx, inv_deg, c1, c2, (long)n);
     return hipGetLastError() == hipSuccess ? WGNN_OK : WGNN_ERR_LAUNCH;
 }
 

@@ -78,6 +78,7 @@ class GNN(nn.Module):
         nn.init.xavier_uniform_(self.linear.weight, gain=nn.init.calculate_gain('relu'))
         self.order = "auto"          # "auto" | "project_first" | "aggregate_first"
         self.fold_alpha = True       # no-grad forward: the layer below the last writes its gene rows alpha-folded (A/B switch)
+        self.feature_sum_cache = False   # default of embed / forward's ``feature_sum_cache``: off (one-shot inference builds nothing)
 
     # -- one NodeFlow block, both node types ------------------------------------------------------
     def _pad_width(self, g: CellGeneGraph, H: int) -> int:
@@ -93,13 +94,15 @@ class GNN(nn.Module):
 
     def _layer(self, g: CellGeneGraph, layer: NodeUpdate, h_g: torch.Tensor, h_c: torch.Tensor,
                want_genes: bool, cell_rows: Optional[torch.Tensor], h_c_compact: bool = False,
-               genes_out_scaled: bool = False, h_g_prescaled: bool = False):
+               genes_out_scaled: bool = False, h_g_prescaled: bool = False, feature_sum: Optional[torch.Tensor] = None):
         """One NodeFlow block for both node types.  ``cell_rows``: compute only these cell rows (a seed batch);
         ``h_c_compact``: ``h_c`` already holds one row per entry of ``cell_rows`` (the previous layer was restricted to
         the seeds) - then cells cannot be sources at this layer (``want_genes`` is False).
         ``genes_out_scaled`` (no-grad path, decided by ``embed``): the gene rows this layer outputs are written as
         ``alpha[g] * h_g'[g]`` by the aggregation epilogue; ``h_g_prescaled``: ``h_g`` IS such a table (this layer reads gene
-        rows only as the source of its cells<-genes pass, which then skips its scale launch)."""
+        rows only as the source of its cells<-genes pass, which then skips its scale launch).
+        ``feature_sum`` (first layer, decided by ``_feature_sum``): ``S = A_gc . h_c``, the graph's cached raw neighbour sum of
+        this layer's input cell rows; the gene rows then come from ``S`` instead of a genes<-cells pass."""
         G = self.gene_num
         if h_c_compact and (want_genes or cell_rows is None):
             raise ValueError("compact cell rows can only feed the seeds' own self-loop")
@@ -165,7 +168,16 @@ class GNN(nn.Module):
             out_c = weighted_mean_aggregate(g.cg, self.alpha, SRC_IS_GENE, G + 1, p_g, p_c_self, bias=b,
                                             relu=fuse_relu, row_ids=cell_rows, self_compact=self_compact, src_scaled=p_g_scaled)
             out_g = None
-            if want_genes:
+            if want_genes and feature_sum is not None:
+                # sum_c w_rc (h_c W^T)[c] = (S W^T)[r]: ONE product whose loader forms (alpha[r] S[r] + alpha[G] h_g[r]) * inv_deg[r]
+                # (ops.linear_mix_fwd), bias / ReLU / the alpha-folded copy in its epilogue as the tile kernel's epilogue has them
+                c1, c2 = _ops.mix_coeffs(self.alpha, G, g.gc.inv_deg)
+                if genes_out_scaled:
+                    out_g = _ops.linear_mix_fwd(feature_sum, c1, h_g, c2, W, b, relu=fuse_relu,
+                                                row_scale=self.alpha.reshape(-1)[:G], want_out=False)[1]
+                else:
+                    out_g = _ops.linear_mix_fwd(feature_sum, c1, h_g, c2, W, b, relu=fuse_relu)
+            elif want_genes:
                 out_g = weighted_mean_aggregate(g.gc, self.alpha, DST_IS_GENE, G, p_c_all, p_g, bias=b, relu=fuse_relu,
                                                 out_scale_alpha=genes_out_scaled)
             return (finish(out_g) if out_g is not None else None), finish(out_c)
@@ -176,7 +188,11 @@ class GNN(nn.Module):
         out_c = _linear_act(z_c, W, b, fuse_relu)
         out_g = None
         if want_genes:
-            z_g = weighted_mean_aggregate(g.gc, self.alpha, DST_IS_GENE, G, h_c, h_g)
+            if feature_sum is not None:                      # the same mix, no product in it: plain elementwise
+                c1, c2 = _ops.mix_coeffs(self.alpha, G, g.gc.inv_deg)
+                z_g = torch.addcmul(c1.unsqueeze(1) * feature_sum, c2.unsqueeze(1), h_g)
+            else:
+                z_g = weighted_mean_aggregate(g.gc, self.alpha, DST_IS_GENE, G, h_c, h_g)
             out_g = finish(_linear_act(z_g, W, b, fuse_relu))
         return out_g, finish(out_c)
 
@@ -207,8 +223,30 @@ class GNN(nn.Module):
                 and Hp == H and nxt.fc_neigh.weight.shape[1] == H
                 and _ops.will_run_tiled(g.cg, H, None if cell_rows is None else int(cell_rows.shape[0])))
 
-    def embed(self, g: CellGeneGraph, features: torch.Tensor, seeds: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Cell embeddings = ``nf.layers[-1].data['activation']`` (gnn.py:66) for ``seeds`` (node ids >= G)."""
+    def _feature_sum(self, g: CellGeneGraph, h_g: torch.Tensor, h_c: torch.Tensor, enabled: Optional[bool]) -> Optional[torch.Tensor]:
+        """The graph's cached ``S = A_gc . h_c`` for the FIRST layer, or None: not asked for (``enabled``, default
+        ``self.feature_sum_cache``; ``WGNN_FEATURE_SUM_CACHE=0`` overrides), nothing to serve (one layer computes no gene
+        rows), or one of the cases in which ``S`` would be wrong or unsafe to reuse - something is differentiated, dropout
+        is active (the sum of DROPPED rows differs per call), a stream capture is in progress (a replay on new feature
+        contents would meet the sum of the old ones), a norm or a non-ReLU activation sits between the mean and the next
+        layer's read, or features / weights are not fp32 rows on the device."""
+        if enabled is None:
+            enabled = getattr(self, "feature_sum_cache", False)
+        layer = self.layers[0]
+        if (not enabled or not _ops.FEATURE_SUM_CACHE or self.n_layers < 2 or torch.is_grad_enabled()
+                or (self.dropout is not None and self.training and self.dropout.p > 0)
+                or layer.norm is not None or not (layer.activation is None or _is_relu(layer.activation))
+                or not h_c.is_cuda or h_g.dtype != torch.float32 or h_c.dtype != torch.float32
+                or layer.fc_neigh.weight.dtype != torch.float32 or self.alpha.dtype != torch.float32
+                or torch.cuda.is_current_stream_capturing()):
+            return None
+        return g.feature_sum(h_c)
+
+    def embed(self, g: CellGeneGraph, features: torch.Tensor, seeds: Optional[torch.Tensor] = None,
+              feature_sum_cache: Optional[bool] = None) -> torch.Tensor:
+        """Cell embeddings = ``nf.layers[-1].data['activation']`` (gnn.py:66) for ``seeds`` (node ids >= G).
+        ``feature_sum_cache``: serve layer 1's genes<-cells pass from the graph's cached feature sum (see ``_feature_sum``;
+        for callers that run repeated no-grad forwards over the same resident features)."""
         G = self.gene_num
         if isinstance(features, (tuple, list)):            # (gene rows, cell rows) kept as separate tensors
             h_g, h_c = features
@@ -229,7 +267,7 @@ class GNN(nn.Module):
             big = (_ops.tiled_kernel_serves(g.cg, -(-min(H0, 256) // 4) * 4)
                    and len(seeds) >= _ops.SEED_FULL_PASS_MIN_FRAC * g.num_cells)
             if big:
-                return self.embed(g, features, None)[seeds.start - G: seeds.stop - G]
+                return self.embed(g, features, None, feature_sum_cache)[seeds.start - G: seeds.stop - G]
             seeds = torch.arange(seeds.start, seeds.stop, device=g.device)
         if seeds is not None:
             cell_rows = (seeds.to(g.device) - G).to(torch.int32)
@@ -240,6 +278,7 @@ class GNN(nn.Module):
         # genes) instead of two; the reference's NodeFlow closure contains exactly these nodes.
         compact = False
         prescaled = False
+        fsum = self._feature_sum(g, h_g, h_c, feature_sum_cache)
         for i, layer in enumerate(self.layers):
             last = i == self.n_layers - 1
             rows = cell_rows if (cell_rows is not None and i >= self.n_layers - 2) else None
@@ -248,7 +287,7 @@ class GNN(nn.Module):
             # that pass on the LDS-streamed kernel, this layer's epilogue writes them folded (no scale launch in between).
             emit = (i == self.n_layers - 2 and not torch.is_grad_enabled() and self._fold_alpha_into_gene_rows(g, layer, cell_rows))
             h_g, h_c = self._layer(g, layer, h_g, h_c, want_genes=not last, cell_rows=rows, h_c_compact=compact,
-                                   genes_out_scaled=emit, h_g_prescaled=prescaled)
+                                   genes_out_scaled=emit, h_g_prescaled=prescaled, feature_sum=fsum if i == 0 else None)
             prescaled = emit
             compact = rows is not None
         H = self.layers[-1].fc_neigh.weight.shape[0]
@@ -301,14 +340,15 @@ class GNN(nn.Module):
 
     def forward(self, g: CellGeneGraph, features: Optional[torch.Tensor] = None,
                 seeds: Optional[torch.Tensor] = None, num_neighbors: int = 0,
-                generator: Optional[torch.Generator] = None, nodeflow=None) -> torch.Tensor:
+                generator: Optional[torch.Generator] = None, nodeflow=None,
+                feature_sum_cache: Optional[bool] = None) -> torch.Tensor:
         """Logits ``[len(seeds), n_classes]`` (all cells in order when ``seeds`` is None); no softmax (gnn.py:66-68).
         ``seeds``: node ids (>= G) as a tensor in any order, or a Python ``range`` for a contiguous block of cells.
 
         ``num_neighbors > 0`` draws a NodeFlow with at most that many in-edges per node (train.py:37-40); ``generator`` is
         a ``sampler.DeviceSampler`` (K5 ``wgnn_sample_rows``: static shapes, sync-free, hipGraph-capturable) or a
         ``torch.Generator`` (torch-op sampler with data-dependent shapes); 0 / None = every in-edge, the reference's
-        default and its eval / predict mode."""
+        default and its eval / predict mode.  ``feature_sum_cache``: see ``embed`` (full-neighbourhood path only)."""
         if features is None:
             features = getattr(g, "features", None)
             if features is None:
@@ -325,4 +365,4 @@ class GNN(nn.Module):
                 nodeflow = sample_nodeflow(g, cells, self.n_layers, int(num_neighbors), generator)
         if nodeflow is not None:
             return self.linear(self.embed_sampled(g, features, nodeflow))
-        return self.linear(self.embed(g, features, seeds))
+        return self.linear(self.embed(g, features, seeds, feature_sum_cache))

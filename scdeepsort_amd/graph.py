@@ -510,6 +510,46 @@ class CellGeneGraph:
         out = agg_fwd(csr, None, NO_ALPHA, 0, gf, None, no_mean=True)
         return out[:, :D] if pad else out
 
+    # -- cached feature sum S = A_gc . X_c (layer 1's genes<-cells pass without the pass) ---------------------------------
+    @staticmethod
+    def _feature_key(h_c: torch.Tensor):
+        return (h_c.data_ptr(), tuple(h_c.shape), tuple(h_c.stride()), h_c.dtype, h_c._version)
+
+    def feature_sum(self, h_c: torch.Tensor) -> Optional[torch.Tensor]:
+        """``S[r] = sum_c w_rc * h_c[c]`` over ``gc`` ([G, D] fp32, D rounded up to a multiple of 4 with zero columns): the raw
+        no-mean neighbour sum of the INPUT cell features.  It depends on the graph and on ``h_c`` only - not on any weight -
+        so it is built once per feature tensor and kept here, on the object whose residency makes it valid.  The entry
+        keeps a strong reference to the tensor it was built from (its address cannot be recycled while the entry lives)
+        and is keyed by ``(data_ptr, shape, strides, dtype, _version)``: an in-place torch write or another tensor rebuilds.
+        Writers that go around torch (raw pointers) call :meth:`invalidate_feature_sums`.  None for feature tensors the sum
+        path does not take (anything but fp32 rows on this graph's device)."""
+        if (h_c.dim() != 2 or h_c.dtype != torch.float32 or h_c.device != self.device or h_c.shape[0] != self.num_cells
+                or h_c.requires_grad):
+            return None
+        key = self._feature_key(h_c)
+        ent = getattr(self, "_feature_sum", None)
+        if ent is not None and ent[0] == key:
+            return ent[2]
+        from . import ops
+        from ._lib import NO_ALPHA
+        x = h_c if h_c.shape[1] % 4 == 0 else torch.nn.functional.pad(h_c, (0, -h_c.shape[1] % 4))
+        self._feature_sum = None                              # the old sum is released before the new one is allocated
+        with ops._Timed(self.device, ("rows", self.num_genes, "cols", self.num_cells, "nnz", self.gc.nnz, "D", x.shape[1],
+                                      "mode", NO_ALPHA, "kernel", "feature_sum_build")):
+            if x.shape[1] > 256 and ops.tiled_kernel_serves(self.gc, 256):
+                # wider than the LDS-streamed kernel carries (cfg3: dense_dim 400): column slabs of <= 256, each a tile pass
+                # (2 x ~1 ms at cfg3 against 17.5 ms for one row-wave pass at D = 400)
+                s = torch.cat([ops.agg_fwd(self.gc, None, NO_ALPHA, 0, x[:, a:a + 256], None, no_mean=True)
+                               for a in range(0, x.shape[1], 256)], dim=1)
+            else:
+                s = ops.agg_fwd(self.gc, None, NO_ALPHA, 0, x, None, no_mean=True)
+        self._feature_sum = (key, h_c, s)
+        return s
+
+    def invalidate_feature_sums(self) -> None:
+        """Drop the cached feature sum (for callers that wrote a features tensor through a raw pointer)."""
+        self._feature_sum = None
+
     def bytes_resident(self) -> int:
         tot = 0
         for d in (self.cg, self.gc):

@@ -691,6 +691,83 @@ def linear_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
     return out if out2 is None else (out, out2)
 
 
+# Layer 1's genes<-cells pass served from the graph's cached feature sum (graph.CellGeneGraph.feature_sum) where a caller
+# asks for it (sharded.ShardedWgnn from its second forward over the same features, api.fit's accuracy());
+# WGNN_FEATURE_SUM_CACHE=0 switches it off everywhere (A/B timing).
+FEATURE_SUM_CACHE = __import__("os").environ.get("WGNN_FEATURE_SUM_CACHE", "1") != "0"
+
+
+def mix_coeffs(alpha: torch.Tensor, self_idx: int, inv_deg: torch.Tensor):
+    """``(alpha[:n] * inv_deg, alpha[self_idx] * inv_deg)`` in one launch (``wgnn_mix_coeffs``): the row coefficients of
+    :func:`linear_mix_fwd` for gene rows."""
+    dev = _require_cuda(alpha, inv_deg)
+    alpha = alpha.detach().reshape(-1).float().contiguous()
+    inv_deg = inv_deg.reshape(-1).float().contiguous()
+    n = inv_deg.shape[0]
+    if alpha.shape[0] < n or not 0 <= self_idx < alpha.shape[0]:
+        raise WgnnError("mix_coeffs: alpha needs one entry per row and one at self_idx")
+    c = torch.empty((2, n), dtype=torch.float32, device=dev)
+    rc = _lib.call(dev, "wgnn_mix_coeffs", _ptr(alpha), self_idx, _ptr(inv_deg), _ptr(c[0]), _ptr(c[1]), n, _stream(dev))
+    _lib.check(rc, "wgnn_mix_coeffs")
+    return c[0], c[1]
+
+
+def linear_mix_fwd(x1: torch.Tensor, c1: torch.Tensor, x2: torch.Tensor, c2: torch.Tensor, weight: torch.Tensor,
+                   bias: Optional[torch.Tensor] = None, relu: bool = False, row_scale: Optional[torch.Tensor] = None,
+                   want_out: bool = True, tile_rows: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                   out_scaled: Optional[torch.Tensor] = None):
+    """``act(a @ weight.T + bias)`` with ``a[m, k] = fmaf(c2[m], x2[m, k], c1[m] * x1[m, k])`` formed in the GEMM's loader
+    (``wgnn_linear_mix_fwd``; no [M, K] intermediate in HBM).  ``x1`` fp32, ``x2`` fp32 or fp16.  Returns ``out``, or with
+    ``row_scale`` ``(out, row_scale[:, None] * out)``; ``want_out=False`` (only with ``row_scale``) skips the unscaled copy
+    and returns ``(None, scaled)``.  ``out`` / ``out_scaled``: caller-owned [M, >= N] fp32 row tables to write into (their
+    row stride is the leading dimension).  Inference helper: no autograd."""
+    dev = _require_cuda(x1, c1, x2, c2, weight, bias, row_scale)
+    x1 = _rowmajor(x1.float())
+    if x2.dtype not in (torch.float32, torch.float16):
+        x2 = x2.float()
+    x2 = _rowmajor(x2) if x2.dtype == torch.float32 else (x2 if x2.stride(1) == 1 and x2.stride(0) % 4 == 0 and x2.data_ptr() % 8 == 0
+                                                          else x2.contiguous())
+    weight = _rowmajor(weight.float())
+    M, K = x1.shape
+    N = weight.shape[0]
+    if tuple(x2.shape) != (M, K) or weight.shape[1] != K:
+        raise WgnnError("linear_mix_fwd: x1 [M, K], x2 [M, K] and weight [N, K] disagree")
+    if K % 4:
+        raise WgnnError(f"K = {K} must be a multiple of 4")
+    c1, c2 = c1.reshape(-1).float().contiguous(), c2.reshape(-1).float().contiguous()
+    if c1.shape[0] < M or c2.shape[0] < M:
+        raise WgnnError("c1 / c2 need one entry per row")
+    if not want_out and row_scale is None:
+        raise WgnnError("want_out=False needs row_scale (the scaled copy is then the only output)")
+
+    def table(t):
+        if t is None:
+            return torch.empty((M, N), dtype=torch.float32, device=dev)
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != M or t.shape[1] < N or t.stride(1) != 1 or t.device != dev:
+            raise WgnnError("out / out_scaled must be fp32 [M, >= N] row tables on the operands' device")
+        return t
+
+    out = table(out) if want_out else None
+    if row_scale is not None:
+        row_scale = row_scale.reshape(-1).float().contiguous()
+        if row_scale.shape[0] < M:
+            raise WgnnError("row_scale needs one entry per row")
+        out_scaled = table(out_scaled)
+    else:
+        out_scaled = None
+    if bias is not None:
+        bias = bias.float().contiguous()
+    # tagged like the wgrad entries (kernel, rows, N, K); cols / nnz / D as well, because bench.py's pass table reads them from
+    # every record of a forward: two row tables of K columns in, no edges
+    with _Timed(dev, ("rows", M, "cols", M, "nnz", 0, "D", K, "N", N, "K", K, "kernel", "linear_mix_mfma_f32")):
+        rc = _lib.call(dev, "wgnn_linear_mix_fwd", _ptr(x1), x1.stride(0), _ptr(c1), _ptr(x2), _dtype_code(x2), x2.stride(0),
+                       _ptr(c2), _ptr(weight), weight.stride(0), _ptr(bias), _ptr(out), out.stride(0) if out is not None else 0,
+                       _ptr(row_scale), _ptr(out_scaled), out_scaled.stride(0) if out_scaled is not None else 0, M, N, K,
+                       (_lib.FLAG_RELU if relu else 0) | {None: 0, 64: 1 << 16, 128: 1 << 17}[tile_rows], _stream(dev))
+    _lib.check(rc, "wgnn_linear_mix_fwd")
+    return out if row_scale is None else (out, out_scaled)
+
+
 WGRAD_MIN_ROWS = 16384       # from this many rows on, the weight gradient of a Linear runs through wgnn_linear_wgrad
 
 
