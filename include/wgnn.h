@@ -1154,6 +1154,45 @@ int wgnn_predict_rows_panels(const void* rowptr, const int32_t* col, const float
                              float* logits, int64_t ld_logits, int32_t* label, float* max_prob, int32_t* entries,
                              uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Rank-based scores of GIVEN gene sets (additive export, WGNN_VERSION stays 206): the kernel behind
+ * api.ResidentPredictor.signatures - UCell's signature score (Andreatta & Carmona 2021), a Mann-Whitney U of the set's ranks
+ * inside the cell's own row.  The batch is a CSR over the bundle's gene ids as wgnn_predict_rows takes it (rowptr int32, or int64
+ * with WGNN_FLAG_ROWPTR_I64; col; val f32), a row of fewer than 2^31 entries; further:
+ *     member   uint64 [n_genes] : bit p of member[g] = gene g belongs to set p - wgnn_predict_rows_panels' word; bits at or
+ *                                 above n_sets are ignored
+ *     n_sets   in [1, 64]
+ *     max_rank in [1, 2^30]     : UCell's maxRank; ranks past it all count as max_rank + 1
+ * The definition, for one cell r (deg stored entries) and one set p - all of it integer arithmetic:
+ *   Order.  Stored entries are ordered by their f32 value, descending, compared on the order-preserving integer key of the
+ *     f32 bits: all bits flipped for a value whose sign bit is set, only the sign bit flipped otherwise.  That is one total
+ *     order over every bit pattern (NaNs and signed zeros included); on finite values it is the numeric order, -0.0 below +0.0.
+ *   Doubled mid-rank of a stored entry j.  gt_j = #{i : key_i > key_j}, eq_j = #{i : key_i == key_j} (j itself included),
+ *     R2_j = 2 * gt_j + eq_j + 1: twice the tie-averaged rank, rank 1 = the highest value.
+ *   Cap.  R2c_j = min(R2_j, 2 * (max_rank + 1)).
+ *   Outputs.  rank2_sum[r, p] int64 = the sum of R2c_j over the stored entries whose gene is in set p; present[r, p] int32 =
+ *     the number of those entries.  Both are [n_rows, ld_*], ld_* >= n_sets; columns >= n_sets are left untouched.
+ *   The genes that are not stored all tie below every stored entry, R2_zero = deg + 1 + n_genes; with n_p = the set's size the
+ *     HOST finishes  two_u = rank2_sum + (n_p - present) * min(deg + 1 + n_genes, 2 * (max_rank + 1)) - n_p * (n_p + 1)  and
+ *     score = 1 - two_u / (2 * n_p * max_rank)  in fp64 (UCell's 1 - U / (n * maxRank)); the kernel does not see n_p.
+ * An entry whose gene id is outside [0, n_genes) belongs to no set and is never used as an index; as a stored value it still
+ * takes part in the other entries' ranks.  A gene listed twice in a row counts twice, as two stored entries.
+ *
+ * One workgroup per cell: the row's keys are staged in LDS (16 384 keys, 64 KiB, at most - a longer row's tail is read from
+ * global memory), the set members are compacted into a stash of 512 entries (a row with more members runs in passes), and a
+ * member's rank is COUNTED against the staged keys - nothing is sorted.  Integers only, no atomics, vector stores only: the
+ * result is independent of the grid, the slab width, the pass structure and the order of the entries within a row, and two
+ * launches are bit-identical.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand; n_rows outside [0, 2^31); n_sets outside [1, 64]; max_rank
+ * outside [1, 2^30]; n_genes <= 0; ld_sum or ld_present < n_sets; an unknown flag), WGNN_ERR_ALIGNMENT (member or rank2_sum not
+ * 8-byte aligned; rowptr not aligned to its entries; col, val or present not 4-byte aligned); wgnn_last_error_string names the
+ * check.  n_rows == 0 is a no-op.
+ * ------------------------------------------------------------------------- */
+int wgnn_rank_sets_rows(const void* rowptr, const int32_t* col, const float* val, int64_t n_rows, int32_t n_genes,
+                        const uint64_t* member, int32_t n_sets, int32_t max_rank,
+                        int64_t* rank2_sum, int64_t ld_sum, int32_t* present, int64_t ld_present,
+                        uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

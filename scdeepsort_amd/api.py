@@ -1980,6 +1980,219 @@ class PanelCalls:
                             n_missing=[len(self.missing.get(n, ())) for n in self.names])
 
 
+def read_gmt(path) -> dict:
+    """A gene-set file in the standard tab-separated GMT layout - one set per line: its name, a description, then its genes -
+    as ``{name: [genes]}`` in file order, which ``ResidentPredictor.signatures`` takes as ``sets``.  Empty lines and empty
+    fields are skipped; a line without a name and a name that occurs twice raise ``ValueError``."""
+    sets = {}
+    with open(path, encoding="utf-8") as f:
+        for n, line in enumerate(f, 1):
+            fields = [x.strip() for x in line.rstrip("\r\n").split("\t")]
+            if not any(fields):
+                continue
+            if not fields[0]:
+                raise ValueError(f"{path}, line {n}: a gene set without a name")
+            if fields[0] in sets:
+                raise ValueError(f"{path}, line {n}: the set {fields[0]!r} occurs twice")
+            sets[fields[0]] = [g for g in fields[2:] if g]
+    return sets
+
+
+def _signature_scores(rank2_sum, present, deg, set_size, n_genes: int, max_rank: int) -> np.ndarray:
+    """The host step of ``wgnn_rank_sets_rows`` (``include/wgnn.h``): f64 [B, P] UCell scores from the kernel's integer sums
+    ``rank2_sum`` / ``present`` [B, P], the cells' stored entries ``deg`` [B] and the sets' sizes ``set_size`` [P].  The genes of
+    a set that the cell does not store all take the doubled rank ``min(deg + 1 + n_genes, 2 * (max_rank + 1))``; a set of no
+    gene scores NaN."""
+    n_p = np.asarray(set_size, np.int64)[None, :]
+    r2_zero = np.minimum(np.asarray(deg, np.int64) + 1 + int(n_genes), 2 * (int(max_rank) + 1))[:, None]
+    # score = 1.0 - float64(two_u) / float64(2 * n_p * max_rank), in place: the tables are [cells, sets], and a fresh temporary
+    # per operator is most of this step's time
+    two_u = n_p - np.asarray(present, np.int64)
+    two_u *= r2_zero
+    two_u += np.asarray(rank2_sum, np.int64)
+    two_u -= n_p * (n_p + 1)
+    score = two_u.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        score /= (2 * n_p * int(max_rank)).astype(np.float64)
+    np.subtract(1.0, score, out=score)
+    score[:, n_p[0] == 0] = np.nan
+    return score
+
+
+class SignatureSummary(dict):
+    """``SignatureScores.summary()``: a dict that prints as one line about the batch and one per set."""
+
+    def __str__(self) -> str:
+        d = self
+        head = f"{d['n_cells']} cells ({d['n_called']} with a call), {len(d['names'])} sets, max_rank {d['max_rank']}"
+        if d["concordant"] is not None:
+            head += f"; {d['n_expected']} cells of a type with an expected set, {d['concordant']:.3f} of them concordant"
+        lines = [head]
+        for name, n, med, top, miss in zip(d["names"], d["set_size"], d["median_score"], d["n_best"], d["n_missing"]):
+            lines.append(f"{name}: {n} bundle genes, median score {med:.3f}, the best set of {top} cells"
+                         + (f", {miss} names not found" if miss else ""))
+        return "\n".join(lines)
+
+
+@dataclass
+class SignatureScores(_NamesCalls):
+    """What ``ResidentPredictor.signatures`` returns: per cell, its call next to UCell's rank-based score of every NAMED gene
+    set.  B cells (``index``), C cell types (``id2label``), P sets (``names``), all small host tables.  ``missing[name]``: the gene
+    names of that set that resolved nowhere; ``set_size`` int64 [P]: a set's genes in the bundle's vocabulary.  ``score`` f64
+    [B, P]: ``1 - U / (n * max_rank)`` in [0, 1], NaN for a set of no gene; ``n_present`` int64 [B, P]: the set's genes the cell
+    stores; ``n_genes`` int64 [B]: the cell's stored entries, the genes its ranks run over.  ``label`` int64 [B] / ``max_prob``
+    f32 [B]: the call on the cell as given (``classify``'s, -1 = unsure).  ``expected``: ``{cell type: set}`` by name, the
+    signature the caller expects for a type (or ``None``).
+
+    The scores have no null distribution: 0.3 for one set and 0.3 for another are not the same evidence when their sizes
+    differ, and nothing here is a p-value."""
+    names: List[str]
+    missing: dict
+    set_size: np.ndarray
+    score: np.ndarray
+    n_present: np.ndarray
+    n_genes: np.ndarray
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    max_rank: int = 1500
+    expected: Optional[dict] = None
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def _set(self, name) -> int:
+        if name not in self.names:
+            raise ValueError(f"no set {name!r}: the sets are {', '.join(map(repr, self.names))}")
+        return list(self.names).index(name)
+
+    def _expected_sets(self) -> np.ndarray:
+        """int64 [C]: the index of the set expected for a cell type, -1 without one."""
+        of_type = np.full(len(self.id2label), -1, np.int64)
+        at = {str(t): i for i, t in enumerate(self.id2label)}
+        for cell_type, name in (self.expected or {}).items():
+            of_type[at[str(cell_type)]] = self._set(str(name))
+        return of_type
+
+    def _own_set(self) -> np.ndarray:
+        """int64 [B]: the index of the set expected for the cell's called type, -1 when unsure or without one."""
+        lab = np.asarray(self.label, np.int64)
+        of_type = self._expected_sets()
+        return np.where(lab >= 0, of_type[np.maximum(lab, 0)], -1) if len(of_type) else np.full(lab.shape, -1, np.int64)
+
+    @staticmethod
+    def _top(score: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(index, value) of each row's largest entry, NaN skipped, the lower index among equals; (-1, NaN) for a row of NaN."""
+        B, P = score.shape
+        if P == 0:
+            return np.full(B, -1, np.int64), np.full(B, np.nan)
+        s = np.where(np.isnan(score), -np.inf, score)
+        ids = s.argmax(axis=1)
+        val = s[np.arange(B), ids]
+        none = np.isneginf(val)
+        return np.where(none, -1, ids).astype(np.int64), np.where(none, np.nan, val)
+
+    def best(self) -> Tuple[np.ndarray, np.ndarray]:
+        """``(ids int64 [B], margin f64 [B])``: per cell the top-scoring set (equal scores: the lower index; sets that score NaN
+        take no part; -1 without one) and its score less the runner-up's (NaN with fewer than two scored sets)."""
+        score = np.asarray(self.score, np.float64)
+        ids, top = self._top(score)
+        rest = score.copy()
+        if rest.shape[1]:
+            rest[np.arange(rest.shape[0]), np.maximum(ids, 0)] = np.nan
+        return ids, top - self._top(rest)[1]
+
+    def own(self) -> np.ndarray:
+        """f64 [B]: the score of the set expected for the cell's called type; NaN when the cell is unsure or its type has no
+        expected set."""
+        own = self._own_set()
+        score = np.asarray(self.score, np.float64)
+        if not score.shape[1]:
+            return np.full(own.shape, np.nan)
+        return np.where(own >= 0, score[np.arange(score.shape[0]), np.maximum(own, 0)], np.nan)
+
+    def _rival(self) -> np.ndarray:
+        """f64 [B]: the best score among the EXPECTED sets other than the cell's own (NaN without one)."""
+        of_type = self._expected_sets()
+        sets = np.unique(of_type[of_type >= 0])                        # the expected sets, ascending
+        rivals = np.asarray(self.score, np.float64)[:, sets].copy()
+        own = self._own_set()
+        rows = np.flatnonzero(own >= 0)
+        if rows.size:
+            rivals[rows, np.searchsorted(sets, own[rows])] = np.nan
+        return self._top(rivals)[1]
+
+    def concordant(self, min_margin: float = 0.0) -> np.ndarray:
+        """Boolean [B]: among the expected sets, the one of the cell's called type scores highest, by at least ``min_margin``
+        (``own() - the best other expected set >= min_margin``; a type whose set is the only expected one is concordant).
+        False for a cell that is unsure, whose type has no expected set, or whose own set scores NaN."""
+        own, rival = self.own(), self._rival()
+        with np.errstate(invalid="ignore"):
+            return ~np.isnan(own) & (np.isnan(rival) | (own - rival >= float(min_margin)))
+
+    def by_type(self, min_margin: float = 0.0) -> pd.DataFrame:
+        """One row per cell type that holds a cell's call: ``cell_type`` (named as ``predict`` names it), ``n_cells``,
+        ``expected`` (its set, ``None`` without one), ``median_own`` (the median of ``own()``), ``concordant`` (the share of
+        ``concordant(min_margin)``; NaN without an expected set), ``other`` (among all sets but the expected one, the set that is
+        the best of most of the type's cells - the lower index among equals, ``None`` without one) and ``other_share``."""
+        lab = np.asarray(self.label, np.int64)
+        of_type, own, ok = self._expected_sets(), self.own(), self.concordant(min_margin)
+        score = np.asarray(self.score, np.float64)
+        P = len(self.names)
+        rows = {k: [] for k in ("cell_type", "n_cells", "expected", "median_own", "concordant", "other", "other_share")}
+        for t in np.unique(lab[lab >= 0]):
+            cells = lab == t
+            n = int(cells.sum())
+            rest = score[cells].copy()
+            if of_type[t] >= 0:
+                rest[:, of_type[t]] = np.nan
+            wins = self._top(rest)[0]
+            votes = np.bincount(wins[wins >= 0], minlength=P)
+            o = int(votes.argmax()) if P else 0
+            rows["cell_type"].append(int(t)); rows["n_cells"].append(n)
+            rows["expected"].append(self.names[of_type[t]] if of_type[t] >= 0 else None)
+            rows["median_own"].append(float(np.median(own[cells])) if of_type[t] >= 0 else np.nan)
+            rows["concordant"].append(float(ok[cells].mean()) if of_type[t] >= 0 else np.nan)
+            rows["other"].append(self.names[o] if P and votes[o] > 0 else None)
+            rows["other_share"].append(votes[o] / n if P else 0.0)
+        rows["cell_type"] = self._name(rows["cell_type"])
+        return pd.DataFrame(rows)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` (named as ``predict`` names it), ``prob``, ``n_genes``, ``best`` (the
+        top-scoring set's name, ``None`` without one), ``margin``, with ``expected`` also ``own`` and ``concordant``, then per
+        set ``score_{name}``."""
+        ids, margin = self.best()
+        out = {"index": list(self.index), "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob),
+               "n_genes": np.asarray(self.n_genes), "best": [self.names[i] if i >= 0 else None for i in ids], "margin": margin}
+        if self.expected:
+            out["own"] = self.own()
+            out["concordant"] = self.concordant()
+        for p, name in enumerate(self.names):
+            out[f"score_{name}"] = np.asarray(self.score)[:, p]
+        return pd.DataFrame(out)
+
+    def discordant(self, min_margin: float = 0.0) -> pd.DataFrame:
+        """The rows of ``frame()`` to look at: cells whose called type has an expected set and that are not
+        ``concordant(min_margin)``."""
+        rows = (self._own_set() >= 0) & ~self.concordant(min_margin)
+        return self.frame()[rows].reset_index(drop=True)
+
+    def summary(self) -> SignatureSummary:
+        """Per set its bundle genes, its median score, the cells it is the best set of and the names that were not found; with
+        ``expected`` the share of concordant cells among those whose type has an expected set; ``print`` it."""
+        ids = self.best()[0]
+        score = np.asarray(self.score, np.float64)
+        with_set = self._own_set() >= 0
+        scored = [score[:, p][~np.isnan(score[:, p])] for p in range(len(self.names))]
+        med = [float(np.median(c)) if c.size else float("nan") for c in scored]
+        return SignatureSummary(n_cells=int(len(self.label)), n_called=int((np.asarray(self.label) >= 0).sum()),
+                                names=list(self.names), max_rank=int(self.max_rank), set_size=[int(n) for n in self.set_size],
+                                median_score=med, n_best=[int((ids == p).sum()) for p in range(len(self.names))],
+                                n_missing=[len(self.missing.get(n, ())) for n in self.names],
+                                n_expected=int(with_set.sum()),
+                                concordant=float(self.concordant()[with_set].mean()) if with_set.any() else None)
+
+
 @dataclass(frozen=True)
 class LogNormalize:
     """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
@@ -2735,6 +2948,106 @@ class ResidentPredictor:
         out = self.panels(matrix, panels=panels, without=without, genes=genes, normalize=normalize, renormalize=renormalize,
                           index=index)
         return self._save_frame(out.by_type(), save_path, "panels")
+
+    # ---------------------------------------------------------------------------------------------
+    def signatures(self, expr, sets, genes=None, normalize=None, max_rank: int = 1500, expected: Optional[dict] = None,
+                   index=None) -> SignatureScores:
+        """Do the cells the model calls T cells express the marker genes you already trust?  The batch is classified once as
+        given (``classify``'s call, bit for bit, either route), and on the same aligned batch - the values as the model sees
+        them - every cell gets UCell's rank-based score (Andreatta & Carmona 2021) of every NAMED gene set: the genes are ranked
+        within the cell's own row and the set's ranks go into a Mann-Whitney U, ``score = 1 - U / (n * max_rank)``.  A cell's
+        ranks depend on its row alone and are invariant under any monotone per-cell normalisation; no control genes are drawn.
+        The ranks are counted on the device in integers (``wgnn_rank_sets_rows``, 64 sets per launch, more sets in several
+        launches) and finished on the host in fp64; ``include/wgnn.h`` has the definition.  Returns a ``SignatureScores``:
+        ``best`` / ``own`` / ``concordant`` / ``by_type`` / ``discordant`` / ``frame`` / ``summary`` on top.  ``expr``, ``genes``
+        and ``normalize`` as for ``classify``; ``index``: the cells' names (default ``range(B)``).
+
+        ``sets`` maps a set's name to its gene names (``read_gmt`` reads a ``.gmt`` file into that).  With ``genes=`` given as
+        names the gene names resolve against the caller's columns, else against the bundle's vocabulary; they are compared as
+        ``str`` and go through the predictor's ``aliases``.  A name that resolves nowhere is no error:
+        ``SignatureScores.missing`` collects it.  ``max_rank`` is UCell's ``maxRank``: ranks past it all count as
+        ``max_rank + 1``.  ``expected`` maps a cell type of the bundle to the name of the set the caller expects for it.
+
+        ``ValueError`` before anything is launched: no set, a set name used twice, a resolved set larger than ``max_rank``
+        (UCell's own precondition), ``max_rank`` outside [1, 2^30], ``expected`` naming an unknown set or cell type.
+
+        What this is not: there are no negative ("GENE-") signatures, no smoothing of the scores over neighbours and no null
+        distribution; genes outside the bundle's vocabulary take no part, neither in the ranks nor in a set, whatever the
+        caller's columns hold."""
+        max_rank = int(max_rank)
+        if not 1 <= max_rank <= _ops.RANK_SETS_MAX_RANK:
+            raise ValueError(f"signatures: max_rank = {max_rank} must be in [1, 2^30]")
+        if not sets:
+            raise ValueError("signatures: pass at least one set (sets={name: gene names})")
+        given = [str(k) for k in sets]
+        twice = sorted({n for n in given if given.count(n) > 1})
+        if twice:
+            raise ValueError(f"signatures: the set name {twice[0]!r} is used twice")
+        for name, gene_names in sets.items():
+            if isinstance(gene_names, (str, bytes)):
+                raise ValueError(f"signatures: {str(name)!r} must list gene names, got one string")
+        _check_index(index, self._n_cells(expr))
+        if genes is None:
+            self._over_genes(expr, None, normalize)        # its refusal of normalize= without genes=, before the device is touched
+        by_name = genes is not None and not isinstance(genes, (torch.Tensor, GeneMap))
+        column_ids = columns = None
+        if genes is not None:
+            if by_name:                                    # resolved once: the map goes on to align in place of the names
+                columns = [str(g) for g in genes]
+                ids, groups = _resolve_genes(columns, self._gene2id, self.aliases, self.duplicates)
+                column_ids = ids
+            else:
+                ids = genes.ids if isinstance(genes, GeneMap) else genes
+                column_ids = ids.detach().cpu().numpy()
+        names, _, member_genes, _, missing = _resolve_panels(sets, None, self._gene2id, self.aliases, columns, column_ids)
+        set_size = member_genes.sum(axis=1).astype(np.int64)
+        if (set_size > max_rank).any():
+            p = int(np.argmax(set_size > max_rank))
+            raise ValueError(f"signatures: the set {names[p]!r} holds {int(set_size[p])} bundle genes, more than max_rank = {max_rank}")
+        expected = None if expected is None else {str(t): str(s) for t, s in expected.items()}
+        for cell_type, name in (expected or {}).items():
+            if cell_type not in set(map(str, self.id2label)):
+                raise ValueError(f"signatures: expected names the cell type {cell_type!r}, which the bundle does not hold")
+            if name not in names:
+                raise ValueError(f"signatures: expected names the set {name!r}, which sets= does not hold")
+        if by_name:
+            if self.duplicates == "sum" and (self.normalize if normalize is None else _normalize_spec(normalize)) is None:
+                raise ValueError("duplicates=\"sum\" needs normalize=: the batch then holds log-values (see align)")
+            genes = torch.from_numpy(ids).to(self.device) if groups is None else self.gene_map(columns, self.aliases, self.duplicates)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._signatures(expr, genes, normalize, names, member_genes, set_size, missing, max_rank, expected, index)
+
+    def _signatures(self, expr, genes, normalize, names, member_genes, set_size, missing, max_rank, expected, index):
+        dev, G = self.device, self.n_genes
+        rowptr, col, raw, checked, _ = self._device_csr(self._over_genes(expr, genes, normalize))
+        if not checked:                                    # once for the whole call: every launch below skips the check
+            _ops.check_gene_ids(col, G)
+        pred, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
+        B, P = int(rowptr.shape[0]) - 1, len(names)
+        rank2 = torch.empty((B, P), dtype=torch.int64, device=dev)
+        present = torch.empty((B, P), dtype=torch.int32, device=dev)
+        for p0 in range(0, P, _ops.SETS_PER_LAUNCH):
+            p1 = min(P, p0 + _ops.SETS_PER_LAUNCH)
+            member = torch.from_numpy(_member_words(member_genes[p0:p1])).to(dev)
+            _ops.rank_sets_rows(rowptr, col, raw, member, p1 - p0, max_rank, G, check_cols=False,
+                                out=(rank2[:, p0:p1], present[:, p0:p1]))
+        deg = (rowptr[1:] - rowptr[:-1]).cpu().numpy().astype(np.int64)
+        present = present.cpu().numpy().astype(np.int64)
+        return SignatureScores(names=names, missing=missing, set_size=set_size,
+                               score=_signature_scores(rank2.cpu().numpy(), present, deg, set_size, G, max_rank),
+                               n_present=present, n_genes=deg, label=pred, max_prob=np.asarray(max_prob, np.float32),
+                               max_rank=max_rank, expected=expected, **self._table_fields(B, index))
+
+    def signatures_file(self, data, sets, normalize=None, max_rank: int = 1500, expected: Optional[dict] = None,
+                        save_path=None) -> pd.DataFrame:
+        """``signatures`` on a test file - its full table, its gene names as ``genes=`` and its cell names:
+        ``SignatureScores.frame()``, written as ``{species}_{tissue}_signatures.csv`` under ``save_path`` when given.  ``sets``:
+        a ``{name: gene names}`` dict or the path of a ``.gmt`` file (``read_gmt``); ``normalize``: as for ``predict``."""
+        if isinstance(sets, (str, os.PathLike)):
+            sets = read_gmt(sets)
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.signatures(matrix, sets, genes=genes, normalize=normalize, max_rank=max_rank, expected=expected, index=index)
+        return self._save_frame(out.frame(), save_path, "signatures")
 
     # ---------------------------------------------------------------------------------------------
     def doublets(self, expr, genes, normalize=None, n_partners: int = 16, across: str = "types", seed: int = 0, index=None,

@@ -1219,6 +1219,56 @@ def predict_rows_panels(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tens
     return (logits, label, max_prob, entries) if want_entries else (logits, label, max_prob)
 
 
+SETS_PER_LAUNCH = 64                # bits of a ``member`` word (include/wgnn.h)
+RANK_SETS_MAX_RANK = 2 ** 30        # wgnn_rank_sets_rows' largest ``max_rank``
+
+
+def rank_sets_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, member: torch.Tensor, n_sets: int, max_rank: int,
+                   n_genes: int, check_cols: bool = True, out=None):
+    """``wgnn_rank_sets_rows``: for every (cell, set) pair of a batch the capped, doubled mid-ranks of the set's genes within
+    the cell's own row, added up - the integer part of UCell's rank-based signature score (``include/wgnn.h`` has the
+    definition).  The batch is a device CSR over ``n_genes`` gene ids (``rowptr`` int32 / int64 [B+1], ``col`` int32, ``val``
+    f32); ``member`` int64 [n_genes] holds the uint64 membership words of ``predict_rows_panels`` (bit ``p`` = the gene belongs
+    to set ``p``; ``n_sets`` in [1, 64], higher bits are ignored); ``max_rank`` in [1, 2^30] is UCell's ``maxRank``.
+    ``check_cols`` as ``predict_rows`` takes it.
+
+    Returns ``(rank2_sum int64 [B, n_sets], present int32 [B, n_sets])``.  ``out``: that pair to write into - either may be a
+    view with unit column stride and a wider row stride; columns beyond ``n_sets`` are left untouched.  CPU tensors are refused;
+    argument errors are ``ValueError``."""
+    name = "rank_sets_rows"
+    dev = _require_cuda(rowptr, col, val, member, *(out or ()))
+    P, R, G = int(n_sets), int(max_rank), int(n_genes)
+    if not 1 <= P <= SETS_PER_LAUNCH:
+        raise ValueError(f"{name}: n_sets = {P} must be in [1, {SETS_PER_LAUNCH}] (split the sets)")
+    if not 1 <= R <= RANK_SETS_MAX_RANK:
+        raise ValueError(f"{name}: max_rank = {R} must be in [1, 2^30]")
+    if G <= 0:
+        raise ValueError(f"{name}: n_genes = {G} must be positive")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
+        raise ValueError(f"{name} takes rowptr int32 / int64, col int32, val float32")
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
+        raise ValueError(f"{name}: rowptr must be [B + 1], col and val one entry each per stored value")
+    if member.dtype != torch.int64 or tuple(member.shape) != (G,):
+        raise ValueError(f"{name}: member must be int64 [{G}] (the uint64 membership words)")
+    B = int(rowptr.shape[0]) - 1
+    if check_cols:
+        check_gene_ids(col, G)
+    rowptr, col, val, member = rowptr.contiguous(), col.contiguous(), val.contiguous(), member.contiguous()
+    if out is None:
+        out = (torch.empty((B, P), dtype=torch.int64, device=dev), torch.empty((B, P), dtype=torch.int32, device=dev))
+    rank2_sum, present = out
+    for t, dt, what in ((rank2_sum, torch.int64, "rank2_sum"), (present, torch.int32, "present")):
+        if t.dtype != dt or t.dim() != 2 or t.shape[0] != B or t.shape[1] < P or (t.shape[1] > 1 and t.stride(1) != 1) or \
+                (B > 1 and t.stride(0) < P):
+            raise ValueError(f"{name}: out's {what} must be {dt} [{B}, >= {P}] with unit column stride and a row stride >= {P}")
+    ld = lambda t: int(t.stride(0)) if B > 1 else max(int(t.stride(0)), P)
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    rc = _lib.call(dev, "wgnn_" + name, _ptr(rowptr), _ptr(col), _ptr(val), B, G, _ptr(member), P, R,
+                   _ptr(rank2_sum), ld(rank2_sum), _ptr(present), ld(present), flags, _stream(dev))
+    _lib.check(rc, "wgnn_" + name)
+    return rank2_sum[:, :P], present[:, :P]
+
+
 def thin_operand_check(rowptr: torch.Tensor, raw: torch.Tensor, rest: torch.Tensor, total: torch.Tensor) -> None:
     """The one fused device check ``stability(thin="reads")`` makes of its operand: every count of ``raw`` an integer in
     [1, 2^24], every ``rest`` (float64 [B], exact) a non-negative integer, every cell's ``total`` below 2^31.  One reduction to
