@@ -1193,6 +1193,48 @@ int wgnn_rank_sets_rows(const void* rowptr, const int32_t* col, const float* val
                         int64_t* rank2_sum, int64_t ld_sum, int32_t* present, int64_t ld_present,
                         uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Wilcoxon rank-sum tables per (group, gene) (additive exports, WGNN_VERSION stays 206): the kernel behind
+ * api.ResidentPredictor.rank_genes - every gene tested for each group of cells against the rest (Mann-Whitney U with the tie
+ * correction; scanpy's rank_genes_groups(method="wilcoxon"), presto).  The operand is the batch GENE-MAJOR exactly as
+ * wgnn_group_gene_reduce takes it (t_rowptr int32 [n_genes + 1], t_cell, t_val f32), group int32 [n_rows] with -1 = the cell
+ * takes no part, and group_size int64 [n_groups] = the histogram of group over [0, n_groups).  All of it is integer arithmetic:
+ *   Taking part.  The cells with group[i] in [0, n_groups); N = their number = the sum of group_size, N_k = group_size[k].
+ *   Values.  For gene g a participating cell that does not list g holds the implicit value +0.0f.  Values are ordered by
+ *     wgnn_rank_sets_rows' order-preserving key of the f32 bits, ASCENDING: one total order over every bit pattern, the numeric
+ *     order on finite values with -0.0 below +0.0.  n_g = the participating stored entries of g, z = N - n_g implicit zeros.
+ *   Doubled mid-rank.  R2_j = 2 * #{less} + #{equal, j included} + 1 over all N values of the gene, rank 1 = the lowest.  For a
+ *     stored entry the z implicit zeros count as "less" when its key is above key(+0.0f) and as "equal" when it equals that key.
+ *     An implicit zero has R2_0 = 2 * #{stored below +0.0f} + t0 + 1 with t0 = z + #{stored equal to +0.0f}.
+ *   Outputs, EVERY element written (the caller does not pre-clear); rank2_sum and count are [n_groups, ld_*], ld_* >= n_genes,
+ *   columns >= n_genes are left untouched:
+ *     rank2_sum int64 [k, g] = the sum of R2 over ALL cells of group k: its stored entries and its (N_k - count[k, g]) zeros
+ *     count     int32 [k, g] = the stored entries of group k
+ *     tie_sum   int64 [g]    = the sum over the gene's tie groups of t^3 - t (= the sum over its N values of eq^2 - 1)
+ *   The HOST finishes in fp64, with n1 = N_k and n2 = N - n1:  U = (rank2_sum - n1 * (n1 + 1)) / 2,  mu = n1 * n2 / 2,
+ *     var = n1 * n2 / 12 * ((N + 1) - tie_sum / (N * (N - 1))),  z = (U - mu) / sqrt(var),  auc = U / (n1 * n2).
+ * An entry whose cell id is outside [0, n_rows) or whose group is outside [0, n_groups) takes no part - in no rank and not in
+ * count; it is never used as an index and never faults.  group_size is trusted: one that is not the histogram of group gives
+ * other numbers, not a fault.
+ *
+ * Nothing is sorted: a work unit is (gene, block of 512 stored entries); the gene's keys stream through an LDS slab of at most
+ * 16 384 keys and every lane counts "less" and "equal" for the entry it owns; a long gene is many units.  Units meet in integer
+ * LDS atomics and 64-bit integer global atomic adds - integer addition commutes, so the result is independent of the grid, the
+ * chunking and the order of cells, and two launches are bit-identical.  A first pass clears the outputs and counts n_g per
+ * gene, a last one adds the implicit zeros' terms.
+ *   workspace: wgnn_rank_genes_groups_workspace bytes (8-byte aligned, caller-owned; about 24 bytes per gene, nothing per entry;
+ *   not read for n_rows == 0).
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand; n_rows outside [0, 2^20], so that N^3 fits int64; n_groups
+ * outside [1, 4096]; n_genes <= 0; ld_sum or ld_count < n_genes; any flag bit - none is defined), WGNN_ERR_WORKSPACE,
+ * WGNN_ERR_ALIGNMENT (rank2_sum, tie_sum, group_size or workspace not 8-byte aligned; another operand not 4-byte aligned);
+ * wgnn_last_error_string names the check.  n_rows == 0 is a valid batch: the tables come back zero.
+ * ------------------------------------------------------------------------- */
+int wgnn_rank_genes_groups_workspace(int64_t n_rows, int64_t nnz, int32_t n_groups, int32_t n_genes, int64_t* bytes);
+int wgnn_rank_genes_groups(const int32_t* t_rowptr, const int32_t* t_cell, const float* t_val, const int32_t* group,
+                           const int64_t* group_size, int64_t n_rows, int32_t n_groups, int32_t n_genes,
+                           int64_t* rank2_sum, int64_t ld_sum, int32_t* count, int64_t ld_count, int64_t* tie_sum,
+                           void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

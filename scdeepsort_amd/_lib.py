@@ -125,6 +125,8 @@ SIGNATURES = {
     "wgnn_hood_rows_fill": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, C.c_double, C.c_float, _i32,
                                       _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_rank_sets_rows": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _u32, _vp]),
+    "wgnn_rank_genes_groups_workspace": (C.c_int, [_i64, _i64, _i32, _i32, _vp]),
+    "wgnn_rank_genes_groups": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _u32, _vp]),
 }
 
 

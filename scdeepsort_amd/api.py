@@ -2193,6 +2193,193 @@ class SignatureScores(_NamesCalls):
                                 concordant=float(self.concordant()[with_set].mean()) if with_set.any() else None)
 
 
+def _rank_genes_stats(rank2_sum, tie_sum, n_cells) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """The host step of ``wgnn_rank_genes_groups`` (``include/wgnn.h``): ``(U, auc, z, p)`` f64 [K, G] from the kernel's integer
+    tables ``rank2_sum`` [K, G] / ``tie_sum`` [G] and the groups' cells ``n_cells`` [K] - a group against the rest of the
+    participating cells, the normal approximation with the tie correction and without a continuity correction.  A group that
+    is empty or holds every cell has NaN throughout; a gene whose values all tie has ``z = 0, p = 1, auc = 0.5``."""
+    from scipy.special import ndtr
+    r2 = np.asarray(rank2_sum, np.int64)
+    n1 = np.asarray(n_cells, np.int64)[:, None]
+    N = int(n1.sum())
+    n2 = N - n1
+    with np.errstate(invalid="ignore", divide="ignore"):
+        U = (r2 - n1 * (n1 + 1)) / 2.0
+        mu = (n1 * n2) / 2.0
+        var = (n1 * n2) / 12.0 * ((N + 1) - np.asarray(tie_sum, np.int64)[None, :] / (N * (N - 1.0)))
+        z = (U - mu) / np.sqrt(var)
+        p = 2 * ndtr(-np.abs(z))
+        auc = U / (n1 * n2)
+    tied = np.broadcast_to(var == 0, U.shape)
+    z, p, auc = np.where(tied, 0.0, z), np.where(tied, 1.0, p), np.where(tied, 0.5, auc)
+    void = np.broadcast_to((n1 == 0) | (n2 == 0), U.shape)
+    return U, np.where(void, np.nan, auc), np.where(void, np.nan, z), np.where(void, np.nan, p)
+
+
+def _benjamini_hochberg(p: np.ndarray) -> np.ndarray:
+    """Benjamini-Hochberg adjusted p-values along the last axis (a row's NaNs stay NaN and take no part)."""
+    p = np.asarray(p, np.float64)
+    out = np.full(p.shape, np.nan)
+    for row, res in zip(p.reshape(-1, p.shape[-1]), out.reshape(-1, p.shape[-1])):
+        ok = np.flatnonzero(~np.isnan(row))
+        if ok.size:
+            order = ok[np.argsort(row[ok], kind="stable")]
+            scaled = row[order] * ok.size / np.arange(1, ok.size + 1)
+            res[order] = np.minimum(np.minimum.accumulate(scaled[::-1])[::-1], 1.0)
+    return out
+
+
+class GeneRanksSummary(dict):
+    """``GeneRanks.summary()``: a dict that prints as one line about the batch and one per group."""
+
+    def __str__(self) -> str:
+        d = self
+        lines = [f"{d['n_cells']} cells in {len(d['group_names'])} groups ({d['n_skipped']} skipped), {d['n_genes']} genes, "
+                 f"p_adj < {d['alpha']}"]
+        for name, n, up, down, top in zip(d["group_names"], d["group_cells"], d["n_up"], d["n_down"], d["top_gene"]):
+            lines.append(f"{name}: {n} cells, {up} genes up, {down} down" + (f", top {top}" if top is not None else ""))
+        return "\n".join(lines)
+
+
+@dataclass
+class GeneRanks:
+    """What ``ResidentPredictor.rank_genes`` returns: a Wilcoxon rank-sum test of every gene, each group's cells against the
+    rest of the participating cells.  K groups (``group_names``), G genes (``id2gene``), all host tables.  ``n_cells`` int64
+    [K]: the cells of each group; ``n_skipped``: the cells with group -1 (unsure, or excluded by the caller), which take no part.
+    The kernel's integers: ``rank2_sum`` int64 [K, G] (the doubled tie-averaged ranks of ALL the group's cells, a cell that does
+    not store the gene holding 0), ``expr_count`` int32 [K, G] (the group's cells that store the gene), ``tie_sum`` int64 [G]
+    (``sum(t^3 - t)`` over the gene's tie groups).  ``mean`` / ``mean_rest`` f64 [K, G]: the mean value in the group and in the
+    rest, over all their cells.  ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call when the groups were the
+    predicted types, else ``None``; ``index``: the cells' names.
+
+    ``p`` is the normal approximation (ties corrected, no continuity correction).  Cells are not samples: with several donors
+    the p-values are far too small (pseudoreplication); ``ResidentPredictor.pseudobulk().counts()`` feeds DESeq2 / edgeR."""
+    group_names: Sequence[str]
+    id2gene: Sequence[str]
+    n_cells: np.ndarray
+    n_skipped: int
+    rank2_sum: np.ndarray
+    expr_count: np.ndarray
+    tie_sum: np.ndarray
+    mean: np.ndarray
+    mean_rest: np.ndarray
+    label: Optional[np.ndarray] = None
+    max_prob: Optional[np.ndarray] = None
+    index: Optional[Sequence] = None
+
+    @functools.cached_property
+    def _stats(self):
+        return _rank_genes_stats(self.rank2_sum, self.tie_sum, self.n_cells)
+
+    def u(self) -> np.ndarray:
+        """f64 [K, G]: Mann-Whitney's U of the group against the rest (``scipy.stats.mannwhitneyu``'s statistic)."""
+        return self._stats[0]
+
+    def auc(self) -> np.ndarray:
+        """f64 [K, G]: ``U / (n1 * n2)``, the chance that a cell of the group holds more of the gene than one of the rest."""
+        return self._stats[1]
+
+    def z(self) -> np.ndarray:
+        """f64 [K, G]: the tie-corrected normal score of U (scanpy's ``scores``); positive = higher in the group."""
+        return self._stats[2]
+
+    def pvals(self) -> np.ndarray:
+        """f64 [K, G]: two-sided, ``2 * ndtr(-|z|)``."""
+        return self._stats[3]
+
+    def pvals_adj(self) -> np.ndarray:
+        """f64 [K, G]: Benjamini-Hochberg over the genes of one group."""
+        return _benjamini_hochberg(self.pvals())
+
+    def logfc(self) -> np.ndarray:
+        """f64 [K, G]: scanpy's ``log2((expm1(mean) + 1e-9) / (expm1(mean_rest) + 1e-9))`` (the values taken as log1p's)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.log2((np.expm1(self.mean) + 1e-9) / (np.expm1(self.mean_rest) + 1e-9))
+
+    def _share(self, count: np.ndarray, n: np.ndarray) -> np.ndarray:
+        n = np.asarray(n, np.float64)[:, None]
+        return np.where(n > 0, count / np.maximum(n, 1.0), 0.0)
+
+    def fraction(self) -> np.ndarray:
+        """f64 [K, G]: the share of the group's cells that store the gene (0 for an empty group)."""
+        return self._share(np.asarray(self.expr_count, np.float64), self.n_cells)
+
+    def fraction_rest(self) -> np.ndarray:
+        """f64 [K, G]: the same among the rest of the participating cells."""
+        count = np.asarray(self.expr_count, np.int64)
+        n = np.asarray(self.n_cells, np.int64)
+        return self._share((count.sum(axis=0)[None, :] - count).astype(np.float64), n.sum() - n)
+
+    def top(self, k: int = 20, min_fraction: float = 0.0, min_logfc: Optional[float] = None,
+            max_padj: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """Per group the ``k`` genes with the highest ``z``, descending, equal scores by the lower gene id, among the genes with
+        ``fraction >= min_fraction``, ``logfc >= min_logfc`` and ``p_adj <= max_padj`` where given: (genes int64 [K, k], -1
+        where a group has fewer; z f64 [K, k], 0 there).  An empty group, or one that holds every cell, has none."""
+        k = int(k)
+        if k < 1:
+            raise ValueError(f"top: k = {k} must be positive")
+        z = self.z()
+        ok = ~np.isnan(z) & (self.fraction() >= float(min_fraction))
+        if min_logfc is not None:
+            ok &= self.logfc() >= float(min_logfc)
+        if max_padj is not None:
+            ok &= self.pvals_adj() <= float(max_padj)
+        K, G = z.shape
+        genes, score = np.full((K, k), -1, np.int64), np.zeros((K, k), np.float64)
+        for i in range(K):
+            cand = np.flatnonzero(ok[i])
+            order = cand[np.argsort(-z[i, cand], kind="stable")][:k]
+            genes[i, :order.size], score[i, :order.size] = order, z[i, order]
+        return genes, score
+
+    def frame(self, k: int = 20, min_fraction: float = 0.0, min_logfc: Optional[float] = None,
+              max_padj: Optional[float] = None) -> pd.DataFrame:
+        """Long form, one row per (group, rank): ``group``, ``rank`` (1 = highest z), ``gene``, ``z``, ``auc``, ``logfc``, ``p``,
+        ``p_adj``, ``fraction``, ``fraction_rest``, ``mean``."""
+        genes, _ = self.top(k, min_fraction, min_logfc, max_padj)
+        r, c = np.nonzero(genes >= 0)
+        at = (r, genes[r, c])
+        return pd.DataFrame({"group": [self.group_names[i] for i in r], "rank": c + 1, "gene": [self.id2gene[j] for j in at[1]],
+                             "z": self.z()[at], "auc": self.auc()[at], "logfc": self.logfc()[at], "p": self.pvals()[at],
+                             "p_adj": self.pvals_adj()[at], "fraction": self.fraction()[at],
+                             "fraction_rest": self.fraction_rest()[at], "mean": np.asarray(self.mean)[at]})
+
+    def compare(self, table: "MarkerTable", k: int = 20) -> pd.DataFrame:
+        """Does the model lean on the genes that separate the type?  Per group the model's top-``k`` attribution genes
+        (``table.top(k)``, ``ResidentPredictor.markers`` of the same bundle and grouping) against the data's top-``k`` by z:
+        ``group``, ``n_model``, ``n_data``, ``n_shared``, ``jaccard`` (NaN when both lists are empty), ``model_only`` and
+        ``data_only`` (gene names, in rank order).  ``ValueError`` when the two tables' group or gene names differ."""
+        if list(table.group_names) != list(self.group_names):
+            raise ValueError("compare: the marker table's group names differ from this table's")
+        if list(table.id2gene) != list(self.id2gene):
+            raise ValueError("compare: the marker table's gene names differ from this table's")
+        model, _ = table.top(k)
+        data, _ = self.top(k)
+        rows = []
+        for i, name in enumerate(self.group_names):
+            m, d = [int(g) for g in model[i] if g >= 0], [int(g) for g in data[i] if g >= 0]
+            shared = set(m) & set(d)
+            union = len(set(m) | set(d))
+            rows.append({"group": name, "n_model": len(m), "n_data": len(d), "n_shared": len(shared),
+                         "jaccard": len(shared) / union if union else float("nan"),
+                         "model_only": [self.id2gene[g] for g in m if g not in shared],
+                         "data_only": [self.id2gene[g] for g in d if g not in shared]})
+        return pd.DataFrame(rows, columns=["group", "n_model", "n_data", "n_shared", "jaccard", "model_only", "data_only"])
+
+    def summary(self, alpha: float = 0.05) -> GeneRanksSummary:
+        """Per group its cells, the genes up and down at ``p_adj < alpha`` and the top gene by z; ``print`` it."""
+        z, adj = self.z(), self.pvals_adj()
+        with np.errstate(invalid="ignore"):
+            sig = adj < float(alpha)
+            up, down = (sig & (z > 0)).sum(axis=1), (sig & (z < 0)).sum(axis=1)
+        first = self.top(1)[0][:, 0]
+        return GeneRanksSummary(n_cells=int(np.asarray(self.n_cells).sum()), n_skipped=int(self.n_skipped),
+                                n_genes=len(self.id2gene), alpha=float(alpha), group_names=list(self.group_names),
+                                group_cells=[int(n) for n in self.n_cells], n_up=[int(n) for n in up],
+                                n_down=[int(n) for n in down],
+                                top_gene=[self.id2gene[g] if g >= 0 else None for g in first])
+
+
 @dataclass(frozen=True)
 class LogNormalize:
     """``normalize=`` of ``ResidentPredictor``: the batch holds raw counts, and Seurat's ``NormalizeData`` defaults
@@ -3505,7 +3692,8 @@ class ResidentPredictor:
         with torch.cuda.device(self.device), torch.no_grad():
             return self._markers(self._over_genes(expr, genes, normalize), groups, target, into, group_names, n_groups)
 
-    def _markers(self, expr, groups, target, into, group_names, n_groups):
+    def _group_names(self, groups, group_names, n_groups) -> Tuple[bool, List[str]]:
+        """``groups=`` of ``markers`` / ``rank_genes``: whether the groups are the predicted types, and the groups' names."""
         predicted = isinstance(groups, str)
         if predicted:
             if groups != "predicted":
@@ -3522,18 +3710,28 @@ class ResidentPredictor:
                 raise ValueError("groups given per cell need group_names or n_groups")
             if not names:
                 raise ValueError("no groups")
+        return predicted, names
+
+    @staticmethod
+    def _group_ids(groups, B: int, K: int) -> np.ndarray:
+        """Groups given per cell as a checked host vector: one integer id in [-1, K) per cell of the batch."""
+        ids = groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)
+        if ids.shape != (B,):
+            raise ValueError(f"groups lists {ids.shape} ids, the batch holds {B} cells")
+        if not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f"groups must be integer ids, got {ids.dtype}")
+        if ids.size and (ids.min() < -1 or ids.max() >= K):
+            raise ValueError(f"group id out of range [-1, {K})")
+        return ids
+
+    def _markers(self, expr, groups, target, into, group_names, n_groups):
+        predicted, names = self._group_names(groups, group_names, n_groups)
         if into is not None:
             into._require_same(names, self.n_genes, self.id2gene)
         rowptr, col, raw, _, _ = csr = self._device_csr(expr)
         B = rowptr.shape[0] - 1
         if not predicted:
-            ids = groups.detach().cpu().numpy() if isinstance(groups, torch.Tensor) else np.asarray(groups)
-            if ids.shape != (B,):
-                raise ValueError(f"groups lists {ids.shape} ids, the batch holds {B} cells")
-            if not np.issubdtype(ids.dtype, np.integer):
-                raise ValueError(f"groups must be integer ids, got {ids.dtype}")
-            if ids.size and (ids.min() < -1 or ids.max() >= len(names)):
-                raise ValueError(f"group id out of range [-1, {len(names)})")
+            ids = self._group_ids(groups, B, len(names))
         att = self._explain(expr if isinstance(expr, _Aligned) else csr[:3] if csr[4] is None else csr[4], 0, target)
         group = att.label if predicted else ids.astype(np.int64)
         dev_group = torch.from_numpy(group.astype(np.int32)).to(self.device)
@@ -3579,6 +3777,79 @@ class ResidentPredictor:
         else:
             out.insert(0, "cell_type", names)
         return self._save_frame(out, save_path, "markers")
+
+    # ---------------------------------------------------------------------------------------------
+    def rank_genes(self, expr, groups="predicted", genes=None, normalize=None, group_names: Optional[Sequence[str]] = None,
+                   n_groups: Optional[int] = None, index=None) -> GeneRanks:
+        """Which genes are differentially expressed in the cells called type k, against the rest?  A Wilcoxon rank-sum
+        (Mann-Whitney) test of every gene of the bundle for every group, on the aligned batch the model sees - what
+        ``scanpy.tl.rank_genes_groups(method="wilcoxon")``, Seurat's ``FindAllMarkers`` and presto compute.  ``markers`` is not
+        this: it sums the model's attribution scores; ``GeneRanks.compare`` sets the two side by side.  ``expr``, ``genes`` and
+        ``normalize`` as for ``markers``.  ``groups="predicted"``: the batch is classified once (``classify``'s call, bit for
+        bit, either route) and grouped by label, unsure cells skipped; else one integer id per cell (-1 = skip) with
+        ``group_names`` or ``n_groups`` - clusters, true labels, conditions.  ``index``: the cells' names.
+
+        One ``wgnn_rank_genes_groups`` launch counts every gene's tie-averaged ranks across the cells in integers and adds
+        them per group, one ``wgnn_group_gene_reduce`` sums the values for the means; the host finishes U, z, p and the AUC
+        in fp64 (``include/wgnn.h`` has the definition).  Returns a ``GeneRanks``: ``z`` / ``pvals`` / ``pvals_adj`` / ``auc``
+        / ``logfc`` / ``top`` / ``frame`` / ``compare`` / ``summary`` on top.  At most 2^20 cells and 4096 groups.
+
+        There is no ``into=``: ranks are not additive over batches - concatenate the batches first.  A PAIRWISE test needs no
+        other call: pass ``groups`` with the cells of every other group at -1.
+
+        What this is not: there are no covariates and no control of pseudoreplication (cells are not samples - with several
+        donors feed ``pseudobulk().counts()`` to DESeq2 / edgeR), ``p`` is the normal approximation, and genes outside the
+        bundle's vocabulary take no part."""
+        _check_index(index, self._n_cells(expr))
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._rank_genes(self._over_genes(expr, genes, normalize), groups, group_names, n_groups, index)
+
+    def _rank_genes(self, expr, groups, group_names, n_groups, index):
+        predicted, names = self._group_names(groups, group_names, n_groups)
+        K, G = len(names), self.n_genes
+        rowptr, col, raw, checked, _ = self._device_csr(expr)
+        B = int(rowptr.shape[0]) - 1
+        if not predicted:
+            ids = self._group_ids(groups, B, K)
+        if not checked:                                    # once for the whole call: every launch below skips the check
+            _ops.check_gene_ids(col, G)
+        label = max_prob = None
+        if predicted:
+            label, max_prob, _, _ = self._classify_on_device(_Aligned((rowptr, col, raw)))
+            max_prob = np.asarray(max_prob, np.float32)
+        group = np.asarray(label if predicted else ids, np.int64)
+        dev_group = torch.from_numpy(group.astype(np.int32)).to(self.device)
+        rank2, count, tie, _ = _ops.rank_genes_groups(rowptr, col, raw, dev_group, K, G, check=False)
+        total, _ = _ops.group_gene_reduce(rowptr, col, raw, dev_group, K, G, check=False)
+        n_cells = np.bincount(group[group >= 0], minlength=K).astype(np.int64)
+        total = total.cpu().numpy()
+        whole = np.zeros(G, np.float64)
+        for k in range(K):                                 # ascending k: one addition order
+            whole += total[k]
+        n1 = n_cells[:, None].astype(np.float64)
+        n2 = float(n_cells.sum()) - n1
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean, mean_rest = total / n1, (whole[None, :] - total) / n2
+        return GeneRanks(group_names=names, id2gene=self.id2gene, n_cells=n_cells, n_skipped=int((group < 0).sum()),
+                         rank2_sum=rank2.cpu().numpy(), expr_count=count.cpu().numpy(), tie_sum=tie.cpu().numpy(), mean=mean,
+                         mean_rest=mean_rest, label=label, max_prob=max_prob, index=pd.RangeIndex(B) if index is None else index)
+
+    def rank_genes_file(self, data, normalize=None, top_k: int = 20, save_path=None) -> pd.DataFrame:
+        """``rank_genes`` on a test file - its full table, its gene names as ``genes=`` and its cell names - with the predicted
+        types as groups: ``GeneRanks.frame(top_k)`` with ``cell_type`` (and ``cell_subtype`` with a label map, as ``predict``
+        names them) in place of ``group``, written as ``{species}_{tissue}_rank_genes.csv`` under ``save_path`` when given.
+        ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.rank_genes(matrix, genes=genes, normalize=normalize, index=index).frame(top_k)
+        names = out.pop("group").tolist()
+        map_file = self.bundle.label_map()
+        if map_file is not None:                                             # as _prediction_frame names them
+            old2new, old2sub = load_label_map(map_file, self.species)
+            out.insert(0, "cell_subtype", [old2sub.get(p, p) for p in names])
+            out.insert(0, "cell_type", [old2new.get(p, p) for p in names])
+        else:
+            out.insert(0, "cell_type", names)
+        return self._save_frame(out, save_path, "rank_genes")
 
     def predict(self, input_file, save_path=None, normalize=None) -> pd.DataFrame:
         """``DeepSortPredictor.predict`` on the resident bundle: same columns, label-map handling and output file name.

@@ -1817,6 +1817,81 @@ def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Ten
     return total, count
 
 
+RANK_GENES_MAX_ROWS = 2 ** 20       # wgnn_rank_genes_groups' largest batch: N^3 must fit int64
+RANK_GENES_MAX_GROUPS = 4096        # and its most groups
+
+
+def rank_genes_groups(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, group: torch.Tensor, n_groups: int,
+                      n_genes: int, check: bool = True, out: Optional[tuple] = None):
+    """``wgnn_rank_genes_groups``: the integer tables of a Wilcoxon rank-sum test of every gene, each group of cells against
+    the rest (``include/wgnn.h`` has the definition).  The batch comes cell-major as ``group_gene_reduce`` takes it (``rowptr``
+    int32 / int64 [B+1], ``col`` int32 gene ids in ``[0, n_genes)``, ``val`` f32; a cell lists a gene at most once); ``group``
+    int32 / int64 [B]: a cell's group in ``[0, n_groups)``, or -1 = the cell takes no part.  ``B <= 2^20``, ``n_groups <= 4096``.
+
+    Returns ``(rank2_sum int64 [K, G], count int32 [K, G], tie_sum int64 [G], group_size int64 [K])``: per (group, gene) the
+    doubled tie-averaged ranks of ALL the group's cells added up (a cell that does not list the gene holds +0.0) and the
+    group's stored entries, per gene the tie term ``sum(t^3 - t)``, per group its cells.  ``out``: the first three to write
+    into - ``rank2_sum`` and ``count`` may be views with unit column stride and a wider row stride; every element of the
+    [K, G] / [G] tables is written, nothing else.  The batch is re-ordered gene-major by the library's stable transpose
+    (``group >= 0`` as its row mask; a stable sort above that kernel's 32 768 columns), then ranks are counted, not sorted, in
+    integers: two calls are bit-identical and the tables do not depend on the order of cells or of a cell's genes.  ``check``:
+    verify the ranges of ``group`` and ``col`` (one ``aminmax`` each and a read-back); without it an out-of-range GROUP takes no
+    part (an out-of-range gene id is the transpose's to fault on).  Argument errors are ``ValueError``."""
+    import ctypes as C
+    from .graph import _transpose_by_sort, _transpose_on_device
+    name = "rank_genes_groups"
+    dev = _require_cuda(rowptr, col, val, group, *(out or ()))
+    K, G = int(n_groups), int(n_genes)
+    if not 1 <= K <= RANK_GENES_MAX_GROUPS:
+        raise ValueError(f"{name}: n_groups = {K} must be in [1, {RANK_GENES_MAX_GROUPS}]")
+    if G <= 0:
+        raise ValueError(f"{name}: n_genes = {G} must be positive")
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
+        raise ValueError(f"{name} takes rowptr int32 / int64, col int32, val float32")
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
+        raise ValueError(f"{name}: rowptr must be [B + 1], col and val one entry each per stored value")
+    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+    if B > RANK_GENES_MAX_ROWS:
+        raise ValueError(f"{name}: {B} cells > 2^20 (the tie term N^3 must fit int64)")
+    if nnz >= 2 ** 31:
+        raise ValueError(f"{name}: nnz >= 2^31")
+    if group.dtype not in (torch.int32, torch.int64) or tuple(group.shape) != (B,):
+        raise ValueError(f"{name}: group must hold one int32 / int64 id per cell ([{B}])")
+    if check and B:
+        lo, hi = torch.aminmax(group)
+        if int(lo) < -1 or int(hi) >= K:
+            raise ValueError(f"{name}: group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
+    if check:
+        check_gene_ids(col, G)
+    if out is None:
+        out = (torch.empty((K, G), dtype=torch.int64, device=dev), torch.empty((K, G), dtype=torch.int32, device=dev),
+               torch.empty(G, dtype=torch.int64, device=dev))
+    rank2_sum, count, tie_sum = out
+    for t, dt, what in ((rank2_sum, torch.int64, "rank2_sum"), (count, torch.int32, "count")):
+        if t.dtype != dt or t.dim() != 2 or tuple(t.shape) != (K, G) or (G > 1 and t.stride(1) != 1) or (K > 1 and t.stride(0) < G):
+            raise ValueError(f"{name}: out's {what} must be {dt} [{K}, {G}] with unit column stride and a row stride >= {G}")
+    if tie_sum.dtype != torch.int64 or tuple(tie_sum.shape) != (G,) or (G > 1 and tie_sum.stride(0) != 1):
+        raise ValueError(f"{name}: out's tie_sum must be a dense int64 [{G}]")
+    ld = lambda t: int(t.stride(0)) if K > 1 else max(int(t.stride(0)), G)
+    group = group.to(torch.int32).contiguous()
+    in_range = (group >= 0) & (group < K)
+    group_size = torch.bincount(group[in_range].long(), minlength=K).to(torch.int64)
+    rowptr32 = rowptr.to(torch.int32).contiguous()           # nnz < 2^31: a safe narrowing
+    transpose = _transpose_on_device if G <= 32768 else _transpose_by_sort
+    if B:
+        t_rowptr, t_cell, t_val = transpose(rowptr32, col.contiguous(), val.contiguous(), B, G, group >= 0)
+    else:                                                    # an empty batch is valid: nothing to transpose
+        t_rowptr, t_cell, t_val = torch.zeros(G + 1, dtype=torch.int32, device=dev), col[:0], val[:0]
+    nb = C.c_int64()
+    _lib.check(_lib.lib().wgnn_rank_genes_groups_workspace(B, nnz, K, G, C.addressof(nb)), "wgnn_rank_genes_groups_workspace")
+    ws = torch.empty((nb.value + 7) // 8, dtype=torch.int64, device=dev)
+    rc = _lib.call(dev, "wgnn_rank_genes_groups", _ptr(t_rowptr), _ptr(t_cell), _ptr(t_val), _ptr(group), _ptr(group_size),
+                   B, K, G, _ptr(rank2_sum), ld(rank2_sum), _ptr(count), ld(count), _ptr(tie_sum), _ptr(ws), nb.value, 0,
+                   _stream(dev))
+    _lib.check(rc, "wgnn_rank_genes_groups")
+    return rank2_sum, count, tie_sum, group_size
+
+
 def group_class_reduce(logits: torch.Tensor, label: torch.Tensor, group: torch.Tensor, n_groups: int,
                        out: Optional[tuple] = None, accumulate: bool = False, check: bool = True):
     """``wgnn_group_class_reduce``: per (group, class) the fp64 sum of the cells' softmax probabilities, taken in fp64 from the
