@@ -1235,6 +1235,44 @@ int wgnn_rank_genes_groups(const int32_t* t_rowptr, const int32_t* t_cell, const
                            int64_t* rank2_sum, int64_t ld_sum, int32_t* count, int64_t ld_count, int64_t* tie_sum,
                            void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Exact k nearest neighbours of dense rows (additive exports, WGNN_VERSION stays 206): the kernel behind
+ * api.ResidentPredictor.knn.  Brute force over every ordered (query, candidate) pair, O(n_q * n_c * D); the [n_q, n_c] distance
+ * matrix is never stored, and symmetry is not exploited.
+ *     Q [n_q, ld_q] f32, X [n_c, ld_x] f32 : queries and candidates, D valid columns each; they may be one buffer
+ *     self_offset                          : query i IS candidate self_offset + i and is left out of its own list; -1 = no
+ *                                            candidate is left out
+ *     n_splits                             : the candidate rows are scanned in this many contiguous ranges (0 = chosen from n_q
+ *                                            and n_c so that a small batch still fills the chip); it changes no bit
+ *     idx int32 [n_q, ld_out], d2 f32 [n_q, ld_out] : the first k columns of a row are written, the others left untouched
+ * Numerics.  The squared Euclidean distance is taken in difference form, one chain per pair:
+ *     d = 0;  for j = 0 .. D-1 ascending:  t = q[j] - x[j] (one f32 rounding);  d = fmaf(t, t, d)
+ *   with no re-association across the kernel's slabs of D.  Hence d >= +0; d2(i, j) and d2(j, i) carry the same bits (t is
+ *   negated, t * t is not changed); every term is non-negative, so against the exact distance of the f32 rows the error is
+ *   bounded RELATIVE TO d: |d - exact| <= gamma * exact, gamma = (D + 3) u / (1 - (D + 3) u), u = 2^-24.  (The norm form
+ *   |q|^2 + |x|^2 - 2 q.x is not used: its error scales with the norms and re-orders exactly the closest neighbours.)
+ * Selection.  Per query the k candidates smallest under the total order (d2, candidate index), ascending: equal distances go
+ *   to the lower index.  A candidate whose distance is NaN is never selected (+inf is a distance like any other).  With fewer
+ *   than k selectable candidates the tail holds idx = -1 and d2 = +inf.  The order is total, so the result does not depend on
+ *   the grid, the tiles, n_splits or the order in which lanes find candidates; two launches are bit-identical.  LDS atomics
+ *   claim staging slots and nothing else; there are no global atomics.
+ * A workgroup holds 64 queries and streams tiles of 64 candidates x 16 columns through LDS; a lane owns 4 x 4 pairs.  Per query
+ * the k best keys (bits(d2) << 32 | index) stay sorted in LDS; a finished distance is compared with the k-th, survivors are
+ * staged and merged by rank, a wavefront per list, when a staging list fills.  LDS per workgroup: 34 KiB + 512 * (k | 1) bytes.
+ *   workspace: wgnn_knn_workspace_bytes(n_q, n_c, k, n_splits) bytes, 8-byte aligned, caller-owned: [splits, n_q, k] 64-bit keys
+ *   that a second kernel merges under the same order; 0 bytes (workspace may be NULL) when the scan is not split.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (n_q or n_c outside [0, 2^31); n_splits outside [0, 64]; ld_out < k; self_offset
+ * below -1 or self_offset + n_q > n_c; any flag bit - none is defined; a missing operand), WGNN_ERR_UNSUPPORTED (k outside
+ * [1, 64], as wgnn_rows_topk; D outside [4, 1024]), WGNN_ERR_ALIGNMENT (D, ld_q or ld_x not a multiple of 4 or ld < D; Q or X
+ * not 16-byte, idx or d2 not 4-byte, workspace not 8-byte aligned), WGNN_ERR_WORKSPACE; wgnn_last_error_string names the check.
+ * n_q == 0 returns WGNN_OK without a launch.
+ * ------------------------------------------------------------------------- */
+int wgnn_knn_workspace_bytes(int64_t n_q, int64_t n_c, int32_t k, int32_t n_splits, int64_t* bytes);
+int wgnn_knn_rows(const float* Q, int64_t ld_q, int64_t n_q, const float* X, int64_t ld_x, int64_t n_c,
+                  int32_t D, int32_t k, int64_t self_offset, int32_t n_splits,
+                  int32_t* idx, float* d2, int64_t ld_out, void* workspace, int64_t workspace_bytes,
+                  uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,8 @@ SOUP_BAD_ROWPTR, SOUP_BAD_COL, SOUP_BAD_ADD = 1, 2, 4     # wgnn_soup_rows_*'s s
 SOUP_MAX_SLAB_GENES = 16384        # wgnn_soup_rows_*'s widest LDS slab (include/wgnn.h)
 HOOD_BAD_INDEX, HOOD_BAD_ROWPTR, HOOD_BAD_COL, HOOD_BAD_SIZE = 1, 2, 4, 8     # wgnn_hood_rows_*'s status bits (include/wgnn.h)
 HOOD_MAX_MEMBERS, HOOD_MAX_SLAB_GENES = 256, 16384     # wgnn_hood_rows_*'s largest unit and widest LDS slab (include/wgnn.h)
-ABI_MAJOR = 2                    # include/wgnn.h WGNN_VERSION / 100
+KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS = 64, 1024, 64    # wgnn_knn_rows' limits (include/wgnn.h)
+ABI_MAJOR = 2                  # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
 _vp, _i32, _i64, _u32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_int
@@ -127,6 +128,8 @@ SIGNATURES = {
     "wgnn_rank_sets_rows": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _vp, _i64, _u32, _vp]),
     "wgnn_rank_genes_groups_workspace": (C.c_int, [_i64, _i64, _i32, _i32, _vp]),
     "wgnn_rank_genes_groups": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _u32, _vp]),
+    "wgnn_knn_workspace_bytes": (C.c_int, [_i64, _i64, _i32, _i32, _vp]),
+    "wgnn_knn_rows": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _u32, _vp]),
 }
 
 

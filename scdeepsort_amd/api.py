@@ -32,9 +32,9 @@ from . import tables as _tables
 from .ops import cross_entropy_sum
 # the result tables and the host helpers they share with the predictor: every name of tables.py is reachable through this module
 from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Coverage, CoverageSummary, Doublets, DoubletsSummary,
-                     GeneRanks, GeneRanksSummary, MarkerTable, PanelCalls, PanelSummary, Pseudobulk, PseudobulkSummary,
-                     SignatureScores, SignatureSummary, Smoothed, SmoothedSummary, Stability, StabilitySummary,
-                     SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
+                     GeneRanks, GeneRanksSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
+                     Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Smoothed, SmoothedSummary, Stability,
+                     StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
                      _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores)
 
 _tables._rows_topk = lambda *a: _ops.rows_topk(*a)      # MarkerTable.top's device route: tables.py itself imports no ops
@@ -1924,6 +1924,93 @@ class ResidentPredictor:
             lists[at[names[0]]] = [at[name] if name else -1 for name in names[1:]]
         out = self.smooth(matrix, genes, lists, normalize=normalize, include_self=include_self, index=index)
         return self._save_frame(out.frame(), save_path, "smoothed")
+
+    # ---------------------------------------------------------------------------------------------
+    def embed(self, expr, genes=None, normalize=None, space: str = "hidden") -> torch.Tensor:
+        """What the model sees of a cell: float32 ``[B, D]`` on the device.  ``expr``, ``genes`` and ``normalize`` as for
+        ``classify``.  ``space="hidden"``: the last layer's post-ReLU row - the vector the head reads, so that
+        ``embed @ w_head.T + b_head`` are ``classify``'s logits up to rounding; ``D`` = the hidden width.  The layers run as in
+        ``classify``'s fused route with the last launch headless, in chunks of consecutive cells under
+        ``STABILITY_CHUNK_BYTES`` (a cell's row depends on its own entries alone: chunking changes no bit).
+        ``space="features"``: the model's INPUT features of the cell, ``rownorm(X) . gene_feat`` (``CellGeneGraph.cell_features``
+        on the device CSR) - no trained weight takes part, this is the unsupervised space; ``D`` = the bundle's dense width.
+
+        Fused kernels only: a hidden width above 256 raises ``ValueError`` (there is no graph route)."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        self._require_fused("embed")
+        with torch.cuda.device(self.device), torch.no_grad():
+            vb = self._values_batch(self._device_csr(self._over_genes(expr, genes, normalize)), full_call=False)
+            return self._embed(vb.csr, space)[:, :self.hidden if space == "hidden" else None]
+
+    def _embed(self, csr, space: str) -> torch.Tensor:
+        """``embed`` of a device CSR whose gene ids are known to be in range; the hidden space comes with its padding columns
+        (zeros), ``[B, hidden_padded]``."""
+        rowptr, col, raw = csr
+        if space == "features":
+            return CellGeneGraph.cell_features(rowptr, col, raw, self.gene_feat)
+        B = int(rowptr.shape[0]) - 1
+        out = torch.empty((B, self.hidden_padded), dtype=torch.float32, device=self.device)
+        step = max(1, self._cells_per_launch(1))
+        for r0 in range(0, B, step):
+            part = rowptr[r0:min(B, r0 + step) + 1]
+
+            def rows(table, alpha, bias, self_rows=None, **_head):        # every launch headless: the last h is the embedding
+                return _ops.predict_rows(part, col, raw, table, alpha, bias, self_rows=self_rows, check_cols=False)
+
+            out[r0:r0 + part.shape[0] - 1] = _ops._pad_cols(self._layers(rows), self.hidden_padded)
+        return out
+
+    def knn(self, expr, k: int = 15, genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
+            index=None) -> NeighborGraph:
+        """The exact k-nearest-neighbour graph of a batch among its OWN cells, in the model's space, built on the device: the
+        batch is classified once (``classify``'s call, bit for bit), embedded (``embed``, ``space`` as there) and searched by
+        ``wgnn_knn_rows`` - brute force over every ordered pair of cells in float32, the ``[B, B]`` distance matrix never
+        stored, neighbours by ascending (squared distance, index) so that duplicate cells are listed in index order, the cell
+        itself left out.  ``k`` in [1, 64].  ``metric="cosine"``: the rows are L2-normalised first
+        (``torch.nn.functional.normalize``) and go through the same kernel - for unit rows ``1 - cos = d2 / 2``, the order
+        is that of the cosine; an all-zero row stays zero, and its distances then mean nothing.  ``index``: the cells' names.
+
+        Returns a ``NeighborGraph``; its ``indices`` are, as they come, the ``neighbors`` argument of ``smooth``, and
+        ``to_scipy()`` is the layout of ``adata.obsp["distances"]``.  Two calls give the same bits.
+
+        What this is not: no approximate index - the cost is ``O(B^2 D)``; no fuzzy-simplicial-set connectivities (UMAP's
+        weights), no clustering; one batch only - no graph across calls.  A graph in ``space="hidden"`` is the classifier's own
+        view: smoothing over it can confirm a wrong call; ``space="features"`` and ``Smoothed.neighbor_agreement()`` are the
+        checks."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
+        if not 1 <= int(k) <= _ops.KNN_MAX_K:
+            raise ValueError(f"k = {k} is outside [1, {_ops.KNN_MAX_K}]")
+        self._require_fused("knn")
+        _check_index(index, self._n_cells(expr))
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._knn(self._over_genes(expr, genes, normalize), int(k), space, metric, index)
+
+    def _knn(self, expr, k, space, metric, index):
+        vb = self._values_batch(self._device_csr(expr))
+        rows = self._embed(vb.csr, space)
+        if metric == "cosine":
+            rows = F.normalize(rows, dim=1)
+        idx, d2 = _ops.knn_rows(rows, k)
+        B = int(rows.shape[0])
+        return NeighborGraph(indices=idx.cpu().numpy().astype(np.int64), sq_distances=d2.cpu().numpy(), k=k, space=space,
+                             metric=metric, label=vb.pred, max_prob=vb.max_prob, **self._table_fields(B, index))
+
+    def knn_file(self, data, k: int = 15, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                 save_path=None) -> pd.DataFrame:
+        """``knn`` on a test file - its full table, its gene names as ``genes=`` and its cell names.  Returns one row per cell,
+        ``cell`` then ``n0`` .. ``n{k-1}``: the cell's name and its neighbours' names, nearest first, empty where a list is
+        short - the layout ``smooth_file`` reads as ``neighbors_file`` - written as ``{species}_{tissue}_neighbors.csv`` under
+        ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        graph = self.knn(matrix, k=k, genes=genes, normalize=normalize, space=space, metric=metric, index=index)
+        cells = [str(c) for c in index]
+        lists = [[cells[j] if j >= 0 else "" for j in row] for row in graph.indices]
+        out = pd.DataFrame([[c] + row for c, row in zip(cells, lists)], columns=["cell"] + [f"n{j}" for j in range(graph.k)])
+        return self._save_frame(out, save_path, "neighbors")
 
     # ---------------------------------------------------------------------------------------------
     def pseudobulk(self, expr, genes, clusters, normalize=None, cluster_names: Optional[Sequence[str]] = None,

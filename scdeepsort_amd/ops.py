@@ -2102,3 +2102,91 @@ def coverage_rows(expr, gene_map: torch.Tensor, n_genes: int):
                          _ptr(status), flags, _stream(dev)), "wgnn_coverage_rows")
     _check_status("coverage_rows", int(status), _ALIGN_STATUS)
     return n_expressed, n_mapped, n_bad, total, total_mapped, col_cells
+
+
+KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS = _lib.KNN_MAX_K, _lib.KNN_MAX_D, _lib.KNN_MAX_SPLITS      # wgnn_knn_rows' limits
+KNN_WORKSPACE_BYTES = 1 << 30       # knn_rows: the [splits, queries of a chunk, k] 64-bit partial lists stay under this
+
+
+def _knn_rows_operand(name: str, what: str, t: torch.Tensor) -> torch.Tensor:
+    """A [n, D] float32 matrix as ``wgnn_knn_rows`` reads it: unit column stride, rows 16-byte aligned, D a multiple of 4
+    (zero columns are appended otherwise: they add ``fmaf(0, 0, d)``, which changes no bit)."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        raise ValueError(f"{name}: {what} must be a 2-D float32 tensor")
+    if t.shape[1] % 4:
+        return _pad_cols(t, -(-t.shape[1] // 4) * 4)
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        return t.contiguous()
+    return t
+
+
+def knn_rows(x: torch.Tensor, k: int, queries: Optional[torch.Tensor] = None, exclude_self: bool = True, n_splits: int = 0,
+             self_offset: int = 0, out: Optional[tuple] = None):
+    """``wgnn_knn_rows``: for every query row the ``k`` (1..64) nearest rows of ``x`` [n_c, D] float32 under squared Euclidean
+    distance - exact brute force on the device, the [n_q, n_c] distance matrix is never stored (``include/wgnn.h`` has the
+    numerics contract: ``t = q[j] - x[j]; d = fmaf(t, t, d)``, j ascending).  ``queries`` [n_q, D] = None: the rows of ``x``
+    themselves.  ``exclude_self``: query ``i`` is row ``self_offset + i`` of ``x`` and is left out of its own list (with
+    ``queries`` a sub-range of ``x``, pass where it starts); False: no row is left out - a query that is a candidate comes
+    first at distance 0.
+
+    Returns ``(idx int32 [n_q, k], d2 f32 [n_q, k])``, ascending under the total order (d2, index): equal distances go to the
+    lower index, a NaN distance is never listed, and with fewer than ``k`` candidates the tail holds -1 / +inf.  ``out``: the
+    two tensors to write into - views with unit column stride and a wider row stride (the same for both) are taken, nothing
+    outside ``[:, :k]`` is written.  ``n_splits`` (0 = chosen from the sizes, else 1..64): how many contiguous candidate ranges
+    are scanned side by side and merged; a large ``n_q`` is chunked over query ranges (halved until the partial lists of
+    a chunk fit ``KNN_WORKSPACE_BYTES``).  Neither changes a bit, and two calls are bit-identical.  ``D`` (after padding to a multiple of
+    4) must be in [4, 1024].  Argument errors are ``ValueError``."""
+    import ctypes as C
+    name = "knn_rows"
+    dev = _require_cuda(x, queries, *(out or ()))
+    k, n_splits = int(k), int(n_splits)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"{name}: k = {k} is outside [1, {KNN_MAX_K}]")
+    if not 0 <= n_splits <= KNN_MAX_SPLITS:
+        raise ValueError(f"{name}: n_splits = {n_splits} is outside [0, {KNN_MAX_SPLITS}] (0 = chosen from the sizes)")
+    x = _knn_rows_operand(name, "x", x)
+    q = x if queries is None else _knn_rows_operand(name, "queries", queries)
+    D, n_q, n_c = int(x.shape[1]), int(q.shape[0]), int(x.shape[0])
+    if q.shape[1] != D:
+        raise ValueError(f"{name}: queries have {q.shape[1]} columns, x {D}")
+    if not 4 <= D <= KNN_MAX_D:
+        raise ValueError(f"{name}: D = {D} is outside [4, {KNN_MAX_D}]")
+    if n_q >= 2 ** 31 or n_c >= 2 ** 31:
+        raise ValueError(f"{name}: n_q and n_c must be below 2^31")
+    first = -1
+    if exclude_self:
+        first = int(self_offset)
+        if first < 0 or first + n_q > n_c:
+            raise ValueError(f"{name}: exclude_self says query i is row self_offset + i of x: self_offset = {first} with "
+                             f"{n_q} queries does not fit {n_c} rows (pass exclude_self=False for queries that are no rows of x)")
+    if out is None:
+        out = (torch.empty((n_q, k), dtype=torch.int32, device=dev), torch.empty((n_q, k), dtype=torch.float32, device=dev))
+    idx, d2 = out
+    for t, dt, what in ((idx, torch.int32, "idx"), (d2, torch.float32, "d2")):
+        if t.dtype != dt or t.dim() != 2 or tuple(t.shape) != (n_q, k) or (k > 1 and t.stride(1) != 1) or (n_q > 1 and t.stride(0) < k):
+            raise ValueError(f"{name}: out's {what} must be {dt} [{n_q}, {k}] with unit column stride and a row stride >= {k}")
+    ld_out = max(int(idx.stride(0)), k) if n_q > 1 else k
+    if n_q > 1 and int(d2.stride(0)) != ld_out:
+        raise ValueError(f"{name}: out's idx and d2 must share one row stride")
+    if n_q == 0:
+        return idx, d2
+    nb = C.c_int64()
+    ask = lambda n: _lib.check(_lib.lib().wgnn_knn_workspace_bytes(n, n_c, k, n_splits, C.addressof(nb)), "wgnn_knn_workspace_bytes")
+    # chunks of consecutive queries, halved until the partial lists of one chunk ([splits, queries, k] 64-bit keys) fit the budget
+    step = n_q
+    ask(step)
+    while nb.value > KNN_WORKSPACE_BYTES and step > 1:
+        step = -(-step // 2)
+        ask(step)
+    ws = None
+    for r0 in range(0, n_q, step):
+        r1 = min(n_q, r0 + step)
+        ask(r1 - r0)
+        if nb.value and (ws is None or ws.numel() * 8 < nb.value):
+            ws = torch.empty((nb.value + 7) // 8, dtype=torch.int64, device=dev)
+        rc = _lib.call(dev, "wgnn_knn_rows", q.data_ptr() + r0 * q.stride(0) * 4, q.stride(0), r1 - r0, _ptr(x), x.stride(0), n_c,
+                       D, k, first + r0 if first >= 0 else -1, n_splits,
+                       idx.data_ptr() + r0 * ld_out * 4, d2.data_ptr() + r0 * ld_out * 4, ld_out,
+                       _ptr(ws) if nb.value else None, nb.value, 0, _stream(dev))
+        _lib.check(rc, "wgnn_knn_rows")
+    return idx, d2

@@ -1645,3 +1645,131 @@ class GeneRanks:
                                 group_cells=[int(n) for n in self.n_cells], n_up=[int(n) for n in up],
                                 n_down=[int(n) for n in down],
                                 top_gene=[self.id2gene[g] if g >= 0 else None for g in first])
+
+
+KNN_SPACES = ("hidden", "features")
+KNN_METRICS = ("euclidean", "cosine")
+
+
+class NeighborGraphSummary(dict):
+    """``NeighborGraph.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_cells']} cells, k = {d['k']} nearest neighbours in the {d['space']} space ({d['metric']}), "
+            f"{d['n_edges']} edges, {d['n_without']} cells without a neighbour",
+            f"median distance to the nearest {d['median_nearest']:.4g}, to the last listed {d['median_kth']:.4g}; "
+            f"{d['mutual_share']:.3f} of the edges are mutual",
+            f"median label agreement {d['median_agreement']:.3f} ({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class NeighborGraph(_NamesCalls):
+    """What ``ResidentPredictor.knn`` returns: the exact k-nearest-neighbour graph of one batch, among the batch's own cells.
+    B cells (``index``), C cell types (``id2label``).  ``indices`` int64 [B, k]: a cell's neighbours by ascending (distance,
+    index), the cell itself left out, -1 = none (a batch of fewer than k + 1 cells, NaN rows) - as it stands the ``neighbors``
+    argument of ``ResidentPredictor.smooth``.  ``sq_distances`` f32 [B, k]: the kernel's squared Euclidean distances, bit for
+    bit (+inf beside a -1); under ``metric="cosine"`` they are those of the L2-normalised rows, ``2 (1 - cos)``.  ``space``
+    ("hidden" | "features") and ``metric`` ("euclidean" | "cosine") say what was measured; ``label`` int64 [B] / ``max_prob``
+    f32 [B]: ``classify``'s call of the batch (-1 = unsure).
+
+    A graph in the hidden space is the classifier's own view of the batch: ``label_agreement`` is high there by construction."""
+    indices: np.ndarray
+    sq_distances: np.ndarray
+    k: int
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def _listed(self) -> np.ndarray:
+        return np.asarray(self.indices, np.int64) >= 0
+
+    def distances(self) -> np.ndarray:
+        """f32 [B, k]: Euclidean distances (the square roots, taken on the host), or for ``metric="cosine"`` the cosine
+        distances ``1 - cos = d2 / 2`` of the unit rows; +inf beside a -1."""
+        d2 = np.asarray(self.sq_distances, np.float32)
+        return d2 / np.float32(2) if self.metric == "cosine" else np.sqrt(d2)
+
+    def to_scipy(self) -> sp.csr_matrix:
+        """CSR ``[B, B]`` of ``distances()``, one stored entry per listed neighbour in the order of the lists - the layout of
+        ``adata.obsp["distances"]`` (a neighbour at distance 0 is a stored zero)."""
+        ok = self._listed()
+        B = ok.shape[0]
+        indptr = np.concatenate([[0], np.cumsum(ok.sum(axis=1))]).astype(np.int64)
+        return sp.csr_matrix((self.distances()[ok], np.asarray(self.indices, np.int64)[ok], indptr), shape=(B, B))
+
+    def mutual(self) -> np.ndarray:
+        """Boolean [B, k]: true where the listed neighbour lists the cell back."""
+        idx, ok = np.asarray(self.indices, np.int64), self._listed()
+        B = idx.shape[0]
+        rows = np.repeat(np.arange(B), ok.sum(axis=1))
+        edges = sp.csr_matrix((np.ones(rows.shape[0], np.int8), (rows, idx[ok])), shape=(B, B))
+        out = np.zeros(idx.shape, bool)
+        out[ok] = np.asarray(edges.T.tocsr()[rows, idx[ok]]).ravel() > 0
+        return out
+
+    def label_agreement(self) -> np.ndarray:
+        """f64 [B]: per cell, the share of its neighbours whose call equals the cell's own; an unsure neighbour, and every
+        neighbour of an unsure cell, counts as disagreeing.  NaN for a cell without a neighbour."""
+        idx, ok = np.asarray(self.indices, np.int64), self._listed()
+        own = np.asarray(self.label, np.int64)
+        theirs = own[np.where(ok, idx, 0)]
+        same = ok & (theirs == own[:, None]) & (theirs >= 0)
+        n = ok.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, same.sum(axis=1) / n, np.nan)
+
+    def by_type(self) -> pd.DataFrame:
+        """One row per call (unsure included, last): ``cell_type``, ``n_cells``, ``median_nearest`` / ``median_kth`` (the
+        distance to the first and to the last listed neighbour), ``mutual`` (the share of the cells' edges that are mutual) and
+        ``agreement`` (the mean ``label_agreement``)."""
+        own, ok = np.asarray(self.label, np.int64), self._listed()
+        dist, mutual, agree = self.distances(), self.mutual(), self.label_agreement()
+        n = ok.sum(axis=1)
+        last = dist[np.arange(len(n)), np.maximum(n - 1, 0)] if dist.shape[1] else np.full(len(n), np.nan, np.float32)
+        rows = []
+        for s in sorted(set(own[own >= 0].tolist())) + ([-1] if (own < 0).any() else []):
+            m = (own == s) if s >= 0 else (own < 0)
+            has = m & (n > 0)
+            med = lambda v: float(np.median(v[has])) if has.any() else float("nan")
+            edges = int(ok[m].sum())
+            rows.append((s, int(m.sum()), med(dist[:, 0]) if dist.shape[1] else float("nan"), med(last),
+                         mutual[m].sum() / edges if edges else float("nan"), float(np.mean(agree[has])) if has.any() else float("nan")))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(6)]
+        return pd.DataFrame({"cell_type": self._name(cols[0]), "n_cells": np.asarray(cols[1], np.int64),
+                             "median_nearest": np.asarray(cols[2], np.float64), "median_kth": np.asarray(cols[3], np.float64),
+                             "mutual": np.asarray(cols[4], np.float64), "agreement": np.asarray(cols[5], np.float64)})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` / ``prob`` (named as ``predict`` names them), ``n_neighbors``,
+        ``nearest`` (the first neighbour's name, ``None`` without one), ``nearest_distance``, ``kth_distance`` (to the last
+        listed neighbour), ``n_mutual`` and ``label_agreement``."""
+        idx, ok = np.asarray(self.indices, np.int64), self._listed()
+        dist, n = self.distances(), ok.sum(axis=1)
+        names = list(self.index)
+        B = len(n)
+        has = n > 0
+        pick = lambda j: np.where(has, dist[np.arange(B), j], np.nan) if dist.shape[1] else np.full(B, np.nan)
+        return pd.DataFrame({"index": names, "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob),
+                             "n_neighbors": n.astype(np.int64),
+                             "nearest": [names[idx[i, 0]] if has[i] else None for i in range(B)],
+                             "nearest_distance": pick(np.zeros(B, np.int64)), "kth_distance": pick(np.maximum(n - 1, 0)),
+                             "n_mutual": self.mutual().sum(axis=1).astype(np.int64), "label_agreement": self.label_agreement()})
+
+    def summary(self) -> NeighborGraphSummary:
+        """Cells, edges, the median nearest and last listed distance, the share of mutual edges and the median label
+        agreement; ``print`` it."""
+        ok, dist, agree = self._listed(), self.distances(), self.label_agreement()
+        n = ok.sum(axis=1)
+        has = n > 0
+        med = lambda v: float(np.median(v)) if len(v) else float("nan")
+        last = dist[np.arange(len(n)), np.maximum(n - 1, 0)][has] if dist.shape[1] else np.zeros(0)
+        return NeighborGraphSummary(n_cells=len(n), k=int(self.k), space=self.space, metric=self.metric, n_edges=int(ok.sum()),
+                                    n_without=int((~has).sum()), median_nearest=med(dist[has, 0]) if dist.shape[1] else float("nan"),
+                                    median_kth=med(last), mutual_share=float(self.mutual().sum() / ok.sum()) if ok.any() else float("nan"),
+                                    n_unsure=int((np.asarray(self.label) < 0).sum()), median_agreement=med(agree[has]))
