@@ -1273,6 +1273,67 @@ int wgnn_knn_rows(const float* Q, int64_t ld_q, int64_t n_q, const float* X, int
                   int32_t* idx, float* d2, int64_t ld_out, void* workspace, int64_t workspace_bytes,
                   uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * k-means++ seeding of dense rows, every round on the device (additive exports, WGNN_VERSION stays 206): the seeding of
+ * ops.kmeans_rows / api.ResidentPredictor.kmeans.  The assignment of a Lloyd step is wgnn_knn_rows with k = 1.
+ *     X [n_rows, ld_x] f32 : the rows, D valid columns
+ *     seed_row int32 [K]   : the chosen rows in the order they were chosen (-1 from the round on in which no valid row was left)
+ *     min_d2 f32 [n_rows]  : a row's squared distance to the nearest of the K seeds (0 for a seed); NaN for an invalid row
+ * A row is VALID iff all its D values are finite; an invalid row has weight 0 in every round and is never chosen.
+ * Round r = 0 .. K-1:
+ *     w_i = 0 for an invalid row; else 1 in round 0, and min_d2[i] against the seeds 0 .. r-1 later: the f32 distance in
+ *           wgnn_knn_rows' chain,  d = 0;  for j = 0 .. D-1 ascending:  t = x[j] - c[j];  d = fmaf(t, t, d),  the minimum over the
+ *           seeds so far (exactly 0 for a seed and for every copy of one), widened to fp64
+ *     u_r = (mix64(mix64(seed) + r) >> 11) * 2^-53 in [0, 1), mix64 the splitmix64 finaliser (x += 0x9E3779B97F4A7C15;
+ *           x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;  x = (x ^ x >> 27) * 0x94D049BB133111EB;  x ^ x >> 31), sums modulo 2^64
+ *     the prefix, ALL in fp64 and in this order - a constant of the kernel, it does not depend on the grid: the rows are cut
+ *           into chunks of 256 consecutive rows;  S_c = the weights of chunk c added in row order from 0.0;  C_0 = 0.0,
+ *           C_{c+1} = C_c + S_c;  T = C_{n_chunks};  the inclusive prefix of row i of chunk c is  P_i = C_c + s_i  with s_i the
+ *           weights of the chunk's rows up to and including i added in row order from 0.0  (P is non-decreasing)
+ *     t = u_r * T (one rounding); the seed is the lowest i with P_i > t - a row of positive weight.  Should rounding give
+ *           t >= T, the last row with w > 0 is taken.
+ *     T == 0 (fewer distinct valid rows than rounds): the lowest-index valid row that is no seed yet; -1 when there is none
+ *           (the caller's to refuse: the kernel cannot see it without a read-back).
+ * Two launches per round and one closing pass, all on `stream`, no read-back in between: a pass over X (a workgroup per chunk,
+ * a lane per row) lowers min_d2 against the newest seed - read through seed_row in device memory - and leaves the chunk sums; a
+ * one-workgroup kernel walks them and the chosen chunk and stores the next seed.  No atomics, vector stores only: two
+ * launches are bit-identical.  Squared distances that overflow f32 are outside the contract (never a fault).
+ *   workspace: wgnn_kmeans_seed_workspace_bytes(n_rows, K) bytes, 8-byte aligned, caller-owned (8 bytes per chunk, 4 per row).
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (n_rows outside [1, 2^31); any flag bit - none is defined; a missing operand),
+ * WGNN_ERR_UNSUPPORTED (K outside [1, 4096]: the cost is O(K n_rows D); D outside [4, 1024]), WGNN_ERR_ALIGNMENT (D or ld_x not a
+ * multiple of 4 or ld_x < D; X not 16-byte, seed_row or min_d2 not 4-byte, workspace not 8-byte aligned), WGNN_ERR_WORKSPACE;
+ * wgnn_last_error_string names the check.
+ * ------------------------------------------------------------------------- */
+int wgnn_kmeans_seed_workspace_bytes(int64_t n_rows, int32_t K, int64_t* bytes);
+int wgnn_kmeans_seed(const float* X, int64_t ld_x, int64_t n_rows, int32_t D, int32_t K, uint64_t seed,
+                     int32_t* seed_row, float* min_d2, void* workspace, int64_t workspace_bytes,
+                     uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Per-group fp64 sums of dense f32 rows (additive exports, WGNN_VERSION stays 206): the update of a Lloyd step.
+ *     X [n_rows, ld_x] f32 : the rows, D valid columns
+ *     order int32 [n_rows], seg_ptr int64 [n_groups + 1] : the batch GROUP-MAJOR, as wgnn_group_class_reduce takes it - the
+ *           rows of group k, ascending, in order[seg_ptr[k] .. seg_ptr[k+1]).  seg_ptr is clamped into [0, n_rows] and an entry
+ *           of `order` outside [0, n_rows) takes no part (it is not counted either): a malformed operand never faults.
+ *     sum f64 [n_groups, ld_sum], count int64 [n_groups] : every element of the first D columns is written
+ *     mean f32 [n_groups, ld_mean], optional : (float)(sum / (double)count), one fp64 divide and one rounding; the row of a
+ *           group with count == 0 is NOT written - what the caller had there stays, bit for bit
+ * Addition order, part of the contract: a group's run is cut into chunks of 64 members; within a chunk the rows are added
+ * sequentially in run order from 0.0, one fp64 accumulator per column; a second kernel adds a group's chunk partials
+ * sequentially in chunk order from 0.0.  No atomics: the result depends on the operand alone, never on the grid.
+ *   workspace: wgnn_group_rows_reduce_workspace(n_rows, n_groups, D) bytes, 8-byte aligned, caller-owned
+ *   ((n_rows / 64 + n_groups) chunk partials of D doubles and one int32).
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (sum, count or seg_ptr missing; n_rows outside [0, 2^31); n_groups <= 0; D <= 0;
+ * ld_x, ld_sum or ld_mean < D; any flag bit - none is defined), WGNN_ERR_UNSUPPORTED (D > 65536; a workspace beyond 2^63
+ * bytes), WGNN_ERR_ALIGNMENT (sum, count, seg_ptr or workspace not 8-byte, X, order or mean not 4-byte aligned),
+ * WGNN_ERR_WORKSPACE; wgnn_last_error_string names the check.  X or order NULL, or n_rows == 0: every group is empty.
+ * ------------------------------------------------------------------------- */
+int wgnn_group_rows_reduce_workspace(int64_t n_rows, int32_t n_groups, int32_t D, int64_t* bytes);
+int wgnn_group_rows_reduce(const float* X, int64_t ld_x, const int32_t* order, const void* seg_ptr, int64_t n_rows,
+                           int32_t n_groups, int32_t D, double* sum, int64_t ld_sum, int64_t* count,
+                           float* mean, int64_t ld_mean, void* workspace, int64_t workspace_bytes,
+                           uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

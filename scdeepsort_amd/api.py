@@ -32,7 +32,7 @@ from . import tables as _tables
 from .ops import cross_entropy_sum
 # the result tables and the host helpers they share with the predictor: every name of tables.py is reachable through this module
 from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Coverage, CoverageSummary, Doublets, DoubletsSummary,
-                     GeneRanks, GeneRanksSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
+                     GeneRanks, GeneRanksSummary, KMeans, KMeansSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
                      Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Smoothed, SmoothedSummary, Stability,
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
                      _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores)
@@ -2011,6 +2011,70 @@ class ResidentPredictor:
         lists = [[cells[j] if j >= 0 else "" for j in row] for row in graph.indices]
         out = pd.DataFrame([[c] + row for c, row in zip(cells, lists)], columns=["cell"] + [f"n{j}" for j in range(graph.k)])
         return self._save_frame(out, save_path, "neighbors")
+
+    # ---------------------------------------------------------------------------------------------
+    def kmeans(self, expr, n_clusters: int, genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
+               init="k-means++", max_iter: int = 100, seed: int = 0, index=None) -> KMeans:
+        """k-means clusters of a batch in the model's space, cut on the device: the batch is classified once (``classify``'s
+        call, bit for bit), embedded (``embed``, ``space`` as there) and clustered by ``ops.kmeans_rows`` - k-means++ seeding
+        without a read-back between its rounds (``wgnn_kmeans_seed``), then Lloyd's iterations with ``wgnn_knn_rows`` (k = 1, the
+        centres as candidates) as the assignment and a deterministic fp64 row sum (``wgnn_group_rows_reduce``) as the update.
+        ``n_clusters`` in [1, 4096] and at most the number of cells; ``init``: ``"k-means++"`` (the draws are a hash of
+        ``seed``) or a float32 ``[n_clusters, D]`` array of starting centres in the space's own width; ``max_iter`` >= 1.
+        ``metric="cosine"``: the rows are L2-normalised first, as ``knn`` does; the centres are then the plain means of unit
+        rows and are NOT re-normalised - this is Euclidean k-means on the unit sphere's points, not spherical k-means.
+        ``index``: the cells' names.
+
+        Returns a ``KMeans``; its ``cluster`` is, as it comes and with ``n_clusters=``, the ``clusters`` argument of
+        ``annotate`` and ``pseudobulk`` and ``rank_genes``' ``groups`` - over-clustering into metacells for those is what this
+        is for.  A cluster the iterations empty stays empty (its centre is left where it was).  Two calls give the same bits.
+
+        What this is not: no Leiden or Louvain on the kNN graph; no ``n_init`` restarts - loop over ``seed`` and keep the
+        lowest ``inertia``; no mini-batch mode and no ``tol`` - it stops on an unchanged assignment or on ``max_iter``; one
+        batch only.  Fused kernels only, as ``embed``."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
+        B = self._n_cells(expr)
+        if not 1 <= int(n_clusters) <= min(_ops.KMEANS_MAX_K, max(B, 1)):
+            raise ValueError(f"n_clusters = {n_clusters} is outside [1, {min(_ops.KMEANS_MAX_K, B)}] (a batch of {B} cells)")
+        if int(max_iter) < 1:
+            raise ValueError(f"max_iter = {max_iter} must be >= 1")
+        if isinstance(init, str) and init not in _ops.KMEANS_INITS:
+            raise ValueError(f"init = {init!r}: pass \"k-means++\" or an array [n_clusters, D]")
+        self._require_fused("kmeans")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._kmeans(self._over_genes(expr, genes, normalize), int(n_clusters), space, metric, init, int(max_iter),
+                                int(seed), index)
+
+    def _kmeans(self, expr, n_clusters, space, metric, init, max_iter, seed, index):
+        vb = self._values_batch(self._device_csr(expr))
+        rows = self._embed(vb.csr, space)[:, :self.hidden if space == "hidden" else None]       # embed's rows
+        if metric == "cosine":
+            rows = F.normalize(rows, dim=1)
+        km =_ops.kmeans_rows(rows, n_clusters, init=init, max_iter=max_iter, seed=seed)
+        trace = [float(v) for v in km.inertia_trace]
+        return KMeans(cluster=km.label.cpu().numpy().astype(np.int64), sq_distance=km.d2.cpu().numpy(),
+                      centers=km.centers.cpu().numpy(), size=km.size.cpu().numpy(),
+                      seed_cells=None if km.seed_row is None else km.seed_row.cpu().numpy().astype(np.int64),
+                      inertia=trace[-1], inertia_trace=trace, n_iter=km.n_iter, converged=km.converged, space=space,
+                      metric=metric, label=vb.pred, max_prob=vb.max_prob, **self._table_fields(int(rows.shape[0]), index))
+
+    def kmeans_file(self, data, n_clusters: int, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                    init="k-means++", max_iter: int = 100, seed: int = 0, save_path=None) -> pd.DataFrame:
+        """``kmeans`` on a test file - its full table, its gene names as ``genes=`` and its cell names.  Returns one row per cell:
+        a running number, ``cell`` (its name) and ``cluster`` (its cluster's name, ``"c0000"``, ...) - with the header line the
+        layout ``annotate_file`` and ``pseudobulk_file`` read as ``clusters_file`` - written as ``{species}_{tissue}_kmeans.csv``
+        under ``save_path`` when given.  A cell whose embedding is not finite has no cluster: ``WgnnError``.  ``normalize``: as
+        for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        km = self.kmeans(matrix, n_clusters, genes=genes, normalize=normalize, space=space, metric=metric, init=init,
+                         max_iter=max_iter, seed=seed, index=index)
+        if (km.cluster < 0).any():
+            raise WgnnError(f"kmeans_file: {int((km.cluster < 0).sum())} cells have no finite embedding and no cluster")
+        return self._save_frame(km.clusters_frame(), save_path, "kmeans")
 
     # ---------------------------------------------------------------------------------------------
     def pseudobulk(self, expr, genes, clusters, normalize=None, cluster_names: Optional[Sequence[str]] = None,

@@ -2190,3 +2190,183 @@ def knn_rows(x: torch.Tensor, k: int, queries: Optional[torch.Tensor] = None, ex
                        _ptr(ws) if nb.value else None, nb.value, 0, _stream(dev))
         _lib.check(rc, "wgnn_knn_rows")
     return idx, d2
+
+
+KMEANS_MAX_K = _lib.KMEANS_MAX_K          # wgnn_kmeans_seed's limit
+KMEANS_INITS = ("k-means++",)
+
+
+def kmeans_seed(x: torch.Tensor, n_clusters: int, seed: int = 0):
+    """``wgnn_kmeans_seed``: k-means++ seeding of the rows of ``x`` [B, D] float32, every round on the device - ``K`` passes over
+    ``x`` and no read-back in between (``include/wgnn.h`` has the contract: the weights are the f32 squared distances to the
+    nearest seed so far in ``wgnn_knn_rows``' chain, the draw ``u_r`` a hash of ``(seed, r)``, the fp64 prefix in a fixed
+    order).  A row that holds a non-finite value is never chosen.  With fewer DISTINCT valid rows than ``n_clusters`` the
+    rounds that find no weight take the lowest-index valid row that is no seed yet.
+
+    Returns ``(seed_row int32 [K], min_d2 f32 [B])``: the chosen rows in the order they were chosen, and every row's squared
+    distance to the nearest of them (NaN for an invalid row).  Two calls are bit-identical.  ``n_clusters`` in [1, 4096] and
+    at most the number of valid rows (one read-back, before the launches), ``D`` (after zero-padding to a multiple of 4) in
+    [4, 1024]; argument errors are ``ValueError``."""
+    import ctypes as C
+    name = "kmeans_seed"
+    dev = _require_cuda(x)
+    K = int(n_clusters)
+    if not 1 <= K <= KMEANS_MAX_K:
+        raise ValueError(f"{name}: n_clusters = {K} is outside [1, {KMEANS_MAX_K}]")
+    x = _knn_rows_operand(name, "x", x)
+    B, D = int(x.shape[0]), int(x.shape[1])
+    if not 4 <= D <= KNN_MAX_D:
+        raise ValueError(f"{name}: D = {D} is outside [4, {KNN_MAX_D}]")
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    n_valid = int(torch.isfinite(x).all(dim=1).sum()) if B else 0
+    if K > n_valid:
+        raise ValueError(f"{name}: n_clusters = {K}, but only {n_valid} of the {B} rows are finite")
+    seed_row = torch.empty(K, dtype=torch.int32, device=dev)
+    min_d2 = torch.empty(B, dtype=torch.float32, device=dev)
+    nb = C.c_int64()
+    _lib.check(_lib.lib().wgnn_kmeans_seed_workspace_bytes(B, K, C.addressof(nb)), "wgnn_kmeans_seed_workspace_bytes")
+    ws = torch.empty(nb.value // 8 + 1, dtype=torch.float64, device=dev)
+    rc = _lib.call(dev, "wgnn_kmeans_seed", _ptr(x), x.stride(0) if B > 1 else D, B, D, K, int(seed) & (2 ** 64 - 1),
+                   _ptr(seed_row), _ptr(min_d2), _ptr(ws), ws.numel() * 8, 0, _stream(dev))
+    _lib.check(rc, "wgnn_kmeans_seed")
+    return seed_row, min_d2
+
+
+def group_rows_reduce(x: torch.Tensor, group: torch.Tensor, n_groups: int, out: Optional[tuple] = None):
+    """``wgnn_group_rows_reduce``: per group the fp64 sum of the rows of ``x`` [B, D] float32 (unit column stride, any row stride
+    ``>= D``), their number, and the mean.  ``group`` int32 / int64 [B]: a row's group in ``[0, n_groups)``; any other id = the row
+    takes no part.  The batch is re-ordered group-major on the device as ``group_class_reduce`` does (a stable sort of the ids,
+    the bounds by a search: no read-back); a group's rows are then added in ascending row order, in chunks of 64 and chunk by
+    chunk - a fixed order, no atomics, two calls are bit-identical.
+
+    Returns ``(sum f64 [K, D], count int64 [K], mean f32 [K, D])`` - ``out`` when given (``mean`` may have a wider row stride).
+    ``mean = float32(sum / count)``; the ``mean`` row of an EMPTY group is not written: with ``out`` it keeps what it held, bit
+    for bit, without ``out`` it is zero."""
+    import ctypes as C
+    dev = _require_cuda(x, group, *(out or ()))
+    K = int(n_groups)
+    if K <= 0:
+        raise ValueError(f"group_rows_reduce: n_groups = {K} must be positive")
+    if x.dim() != 2 or x.dtype != torch.float32 or x.shape[1] < 1:
+        raise ValueError("group_rows_reduce takes x float32 [B, D] with D >= 1")
+    B, D = int(x.shape[0]), int(x.shape[1])
+    if B >= 2 ** 31:
+        raise ValueError("group_rows_reduce: B >= 2^31")
+    if tuple(group.shape) != (B,) or group.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"group must hold one int32 / int64 id per row ([{B}]), got {group.dtype} {tuple(group.shape)}")
+    if out is None:
+        out = (torch.empty((K, D), dtype=torch.float64, device=dev), torch.empty(K, dtype=torch.int64, device=dev),
+               torch.zeros((K, D), dtype=torch.float32, device=dev))
+    if len(out) != 3:
+        raise ValueError("out must be (sum, count, mean)")
+    total, count, mean = out
+    if tuple(total.shape) != (K, D) or total.dtype != torch.float64 or not total.is_contiguous() or \
+            tuple(count.shape) != (K,) or count.dtype != torch.int64 or not count.is_contiguous():
+        raise ValueError(f"out must hold contiguous sum float64 [{K}, {D}] and count int64 [{K}]")
+    if tuple(mean.shape) != (K, D) or mean.dtype != torch.float32 or (D > 1 and mean.stride(1) != 1) or (K > 1 and mean.stride(0) < D):
+        raise ValueError(f"out's mean must be float32 [{K}, {D}] with unit column stride and a row stride >= {D}")
+    if (D > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < D):
+        x = x.contiguous()
+    ld = int(x.stride(0)) if B > 1 else D
+    ids = group.to(torch.int64)
+    ids = torch.where((ids < 0) | (ids >= K), torch.full_like(ids, K), ids)       # the rows that take no part sort last
+    ids, order = torch.sort(ids, stable=True)                                     # rows of a group ascending
+    seg_ptr = torch.searchsorted(ids, torch.arange(K + 1, dtype=torch.int64, device=dev)).contiguous()
+    order = order.to(torch.int32)
+    nb = C.c_int64()
+    _lib.check(_lib.lib().wgnn_group_rows_reduce_workspace(B, K, D, C.addressof(nb)), "wgnn_group_rows_reduce_workspace")
+    ws = torch.empty(nb.value // 8 + 1, dtype=torch.float64, device=dev)
+    rc = _lib.call(dev, "wgnn_group_rows_reduce", _ptr(x), ld, _ptr(order), _ptr(seg_ptr), B, K, D, _ptr(total), D, _ptr(count),
+                   _ptr(mean), int(mean.stride(0)) if K > 1 else D, _ptr(ws), ws.numel() * 8, 0, _stream(dev))
+    _lib.check(rc, "wgnn_group_rows_reduce")
+    return total, count, mean
+
+
+class KMeansRows(NamedTuple):
+    """What ``kmeans_rows`` returns.  On the device: ``label`` int32 [B] (-1 = a row with a non-finite value), ``d2`` f32 [B] (the
+    squared distance to the row's centre as ``wgnn_knn_rows`` leaves it; NaN beside a -1), ``centers`` f32 [K, D], ``size``
+    int64 [K], ``seed_row`` int32 [K] (``None`` with an ``init`` array).  On the host: ``n_iter`` (the assignments made inside
+    the loop), ``converged`` and ``inertia_trace`` (float64, one entry per assignment: the sum of ``d2`` over labelled rows)."""
+    label: torch.Tensor
+    d2: torch.Tensor
+    centers: torch.Tensor
+    size: torch.Tensor
+    seed_row: Optional[torch.Tensor]
+    n_iter: int
+    converged: bool
+    inertia_trace: list
+
+
+def kmeans_rows(x: torch.Tensor, n_clusters: int, init="k-means++", max_iter: int = 100, seed: int = 0) -> KMeansRows:
+    """Lloyd's k-means on the rows of ``x`` [B, D] float32, on the device, deterministic::
+
+        C = x[seed_row]                      (kmeans_seed; or the caller's init array [K, D])
+        for it in 1 .. max_iter:
+            label, d2 = knn_rows(C, 1, queries=x, exclude_self=False);  label = -1 on rows with a non-finite value
+            if it > 1 and label == prev: converged; break
+            C = group_rows_reduce(x, label).mean  (an empty cluster keeps its row);  prev = label
+        if not converged: one more assignment against the final C
+
+    so the labels are always the assignment against the centres that are returned.  The assignment is ``wgnn_knn_rows`` with
+    the centres as candidates: the nearest centre under the total order (distance, index) - of two equal centres the lower
+    index takes every row and the higher stays empty.  An empty cluster is left where it is (no relocation).  One small
+    read-back per iteration (the stop test, and ``d2`` for ``inertia_trace``, summed on the host in fp64).  It stops on an
+    unchanged assignment or on ``max_iter``: there is no ``tol``, no ``n_init`` and no mini-batch mode.  A width that is no
+    multiple of 4 is zero-padded as ``knn_rows`` does.  CPU tensors raise ``WgnnError``; argument errors are ``ValueError``.
+    Returns a ``KMeansRows``."""
+    import numpy as np
+    name = "kmeans_rows"
+    dev = _require_cuda(x)
+    K, max_iter = int(n_clusters), int(max_iter)
+    if not 1 <= K <= KMEANS_MAX_K:
+        raise ValueError(f"{name}: n_clusters = {K} is outside [1, {KMEANS_MAX_K}]")
+    if max_iter < 1:
+        raise ValueError(f"{name}: max_iter = {max_iter} must be >= 1")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"{name}: x must be a 2-D float32 tensor")
+    D = int(x.shape[1])
+    xp = _knn_rows_operand(name, "x", x)
+    B, Dp = int(xp.shape[0]), int(xp.shape[1])
+    if not 4 <= Dp <= KNN_MAX_D:
+        raise ValueError(f"{name}: D = {Dp} is outside [4, {KNN_MAX_D}]")
+    seed_row = None
+    if isinstance(init, str):
+        if init not in KMEANS_INITS:
+            raise ValueError(f"{name}: init = {init!r}: pass \"k-means++\" or an array [n_clusters, D]")
+        seed_row, _ = kmeans_seed(xp, K, seed)
+        centers = xp[seed_row.long()].contiguous()
+    else:
+        c0 = torch.as_tensor(init)
+        if c0.dim() != 2 or tuple(c0.shape) != (K, D) or c0.dtype != torch.float32:
+            raise ValueError(f"{name}: an init array must be float32 [{K}, {D}], got {c0.dtype} {tuple(c0.shape)}")
+        if not bool(torch.isfinite(c0).all()):
+            raise ValueError(f"{name}: the init array holds a non-finite value")
+        centers = _pad_cols(c0.to(dev), Dp).contiguous().clone() if Dp != D else c0.to(dev).contiguous().clone()
+    valid = torch.isfinite(xp).all(dim=1)
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+    minus = torch.full((), -1, dtype=torch.int32, device=dev)
+    total = torch.empty((K, Dp), dtype=torch.float64, device=dev)
+    count = torch.empty(K, dtype=torch.int64, device=dev)
+    trace: list = []
+
+    def assign():
+        idx, d2 = knn_rows(centers, 1, queries=xp, exclude_self=False)
+        label, d2 = torch.where(valid, idx[:, 0], minus), torch.where(valid, d2[:, 0], nan)
+        host = d2.cpu().numpy().astype(np.float64)
+        trace.append(float(host[~np.isnan(host)].sum()))
+        return label, d2
+
+    prev, converged, n_iter = None, False, 0
+    for it in range(1, max_iter + 1):
+        label, d2 = assign()
+        n_iter = it
+        if prev is not None and torch.equal(label, prev):
+            converged = True
+            break
+        group_rows_reduce(xp, label, K, out=(total, count, centers))
+        prev = label
+    if not converged:
+        label, d2 = assign()
+    size = torch.bincount(label[label >= 0].long(), minlength=K)
+    return KMeansRows(label, d2, centers[:, :D], size, seed_row, n_iter, converged, trace)

@@ -1773,3 +1773,103 @@ class NeighborGraph(_NamesCalls):
                                     n_without=int((~has).sum()), median_nearest=med(dist[has, 0]) if dist.shape[1] else float("nan"),
                                     median_kth=med(last), mutual_share=float(self.mutual().sum() / ok.sum()) if ok.any() else float("nan"),
                                     n_unsure=int((np.asarray(self.label) < 0).sum()), median_agreement=med(agree[has]))
+
+
+class KMeansSummary(dict):
+    """``KMeans.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        how = f"converged after {d['n_iter']} assignments" if d["converged"] else f"NOT converged after {d['n_iter']} assignments"
+        return "\n".join([
+            f"{d['n_cells']} cells in {d['n_clusters']} clusters of the {d['space']} space ({d['metric']}), {how}; "
+            f"{d['n_skipped']} cells without a cluster, {d['n_empty']} empty clusters",
+            f"cluster sizes {d['min_size']} .. {d['max_size']} (median {d['median_size']:.4g}), inertia {d['inertia']:.6g}",
+            f"median purity {d['median_purity']:.3f}, {d['n_mixed']} clusters below 0.9 ({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class KMeans(_NamesCalls):
+    """What ``ResidentPredictor.kmeans`` returns: the k-means clusters of one batch in the model's space.  B cells (``index``),
+    K clusters (``cluster_names``: ``"c0000"``, ... - zero-padded, so sorted order is id order), C cell types (``id2label``).
+    ``cluster`` int64 [B]: a cell's cluster, -1 for a cell whose embedding holds a non-finite value - as it stands, with
+    ``n_clusters=K``, the ``clusters`` argument of ``annotate`` / ``pseudobulk`` and ``rank_genes``' ``groups``.
+    ``sq_distance`` f32 [B]: the squared distance to the cell's centre (NaN beside a -1); ``centers`` f32 [K, D];
+    ``size`` int64 [K]; ``seed_cells`` int64 [K]: the cells the seeding chose (``None`` with an init array); ``inertia``: the sum
+    of ``sq_distance``, ``inertia_trace`` the same after every assignment; ``n_iter`` / ``converged``: ``ops.kmeans_rows``'.
+    ``space`` / ``metric`` say what was clustered (under ``"cosine"`` the L2-normalised rows; the centres are their plain means,
+    not re-normalised); ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    cluster: np.ndarray
+    sq_distance: np.ndarray
+    centers: np.ndarray
+    size: np.ndarray
+    seed_cells: Optional[np.ndarray]
+    inertia: float
+    inertia_trace: Sequence[float]
+    n_iter: int
+    converged: bool
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    @property
+    def n_clusters(self) -> int:
+        return int(np.asarray(self.size).shape[0])
+
+    @property
+    def cluster_names(self) -> List[str]:
+        width = max(4, len(str(self.n_clusters - 1)))
+        return [f"c{k:0{width}d}" for k in range(self.n_clusters)]
+
+    def composition(self) -> pd.DataFrame:
+        """Clusters x called types, as counts: one row per cluster (``cluster_names``), one column per cell type in ``id2label``'s
+        order (named as ``predict`` names them) and ``unsure`` last.  A cell without a cluster is counted nowhere."""
+        K, C = self.n_clusters, len(self.id2label)
+        cl, lab = np.asarray(self.cluster, np.int64), np.asarray(self.label, np.int64)
+        on = cl >= 0
+        table = np.zeros((K, C + 1), np.int64)
+        np.add.at(table, (cl[on], np.where(lab[on] >= 0, lab[on], C)), 1)
+        return pd.DataFrame(table, index=self.cluster_names, columns=self._name(np.arange(C)) + ["unsure"])
+
+    def purity(self) -> np.ndarray:
+        """f64 [K]: per cluster, the share of its CALLED cells (unsure ones left out) that carry the cluster's majority call;
+        NaN for a cluster without a called cell."""
+        called = self.composition().to_numpy()[:, :-1]
+        n = called.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, called.max(axis=1, initial=0) / n, np.nan)
+
+    def clusters_frame(self) -> pd.DataFrame:
+        """One row per cell - a running number, the cell's name, its cluster's name (empty for a cell without one): written with
+        its header and without pandas' own index this is the clusters file ``annotate_file`` / ``pseudobulk_file`` read."""
+        names = self.cluster_names
+        return pd.DataFrame({"index": np.arange(len(self.cluster), dtype=np.int64), "cell": [str(c) for c in self.index],
+                             "cluster": [names[k] if k >= 0 else "" for k in np.asarray(self.cluster, np.int64)]})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` / ``prob`` (named as ``predict`` names them), ``cluster`` (its name, ``None``
+        without one), ``sq_distance``, and the cluster's ``cluster_size`` and ``cluster_purity``."""
+        names, cl = self.cluster_names, np.asarray(self.cluster, np.int64)
+        on, at = cl >= 0, np.maximum(cl, 0)
+        return pd.DataFrame({"index": list(self.index), "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob),
+                             "cluster": [names[k] if k >= 0 else None for k in cl],
+                             "sq_distance": np.asarray(self.sq_distance, np.float32),
+                             "cluster_size": np.where(on, np.asarray(self.size, np.int64)[at], 0),
+                             "cluster_purity": np.where(on, self.purity()[at], np.nan)})
+
+    def summary(self) -> KMeansSummary:
+        """Cells, clusters, sizes, the inertia and the clusters' purity against ``classify``'s calls; ``print`` it."""
+        size, purity = np.asarray(self.size, np.int64), self.purity()
+        filled = size[size > 0]
+        known = purity[~np.isnan(purity)]
+        return KMeansSummary(n_cells=len(self.cluster), n_clusters=self.n_clusters, space=self.space, metric=self.metric,
+                             n_iter=int(self.n_iter), converged=bool(self.converged),
+                             n_skipped=int((np.asarray(self.cluster) < 0).sum()), n_empty=int((size == 0).sum()),
+                             min_size=int(filled.min()) if filled.size else 0, max_size=int(filled.max()) if filled.size else 0,
+                             median_size=float(np.median(filled)) if filled.size else float("nan"), inertia=float(self.inertia),
+                             median_purity=float(np.median(known)) if known.size else float("nan"),
+                             n_mixed=int((known < 0.9).sum()), n_unsure=int((np.asarray(self.label) < 0).sum()))
