@@ -171,3 +171,8 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().wgnn_last_error_string(rc).decode()
         raise WgnnError(f"{what} failed: {msg} (code {rc})")
+
+
+def run(device, name: str, *args) -> None:
+    """``call`` then ``check``: the entry is named once."""
+    check(call(device, name, *args), name)

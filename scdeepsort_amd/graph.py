@@ -386,15 +386,15 @@ def _transpose_on_device(rowptr, col, raw, n_rows: int, n_cols: int, row_mask: O
     keep = None if row_mask is None else row_mask.to(device=dev, dtype=torch.uint8).contiguous()
     if keep is not None and keep.shape[0] != n_rows:
         raise ValueError(f"support_mask has {keep.shape[0]} entries for {n_rows} cells")
-    _lib.check(_lib.call(dev, "wgnn_csr_transpose_count", _ptr(rowptr), _ptr(col), _ptr(keep), n_rows, n_cols, nch.value,
-                         _ptr(counts), _ptr(t_count), _stream(dev)), "wgnn_csr_transpose_count")
+    _lib.run(dev, "wgnn_csr_transpose_count", _ptr(rowptr), _ptr(col), _ptr(keep), n_rows, n_cols, nch.value,
+             _ptr(counts), _ptr(t_count), _stream(dev))
     t_rowptr = torch.zeros(n_cols + 1, dtype=torch.int32, device=dev)
     torch.cumsum(t_count, 0, out=t_rowptr[1:])
     nnz_t = col.shape[0] if keep is None else int(t_rowptr[-1])
     t_col = torch.empty(nnz_t, dtype=torch.int32, device=dev)
     t_raw = torch.empty(nnz_t, dtype=torch.float32, device=dev)
-    _lib.check(_lib.call(dev, "wgnn_csr_transpose_fill", _ptr(rowptr), _ptr(col), _ptr(raw), _ptr(keep), n_rows, n_cols, nch.value,
-                         _ptr(counts), _ptr(t_rowptr), _ptr(t_col), _ptr(t_raw), _stream(dev)), "wgnn_csr_transpose_fill")
+    _lib.run(dev, "wgnn_csr_transpose_fill", _ptr(rowptr), _ptr(col), _ptr(raw), _ptr(keep), n_rows, n_cols, nch.value,
+             _ptr(counts), _ptr(t_rowptr), _ptr(t_col), _ptr(t_raw), _stream(dev))
     return t_rowptr, t_col, t_raw
 
 
@@ -405,8 +405,8 @@ def _normalize_on_device(rowptr: torch.Tensor, raw: torch.Tensor) -> Tuple[torch
     n_rows = rowptr.shape[0] - 1
     out = torch.empty_like(raw)
     inv_deg = torch.empty(n_rows, dtype=torch.float32, device=raw.device)
-    _lib.check(_lib.call(raw.device, "wgnn_normalize_rows", _ptr(rowptr), _ptr(raw), _ptr(out), _ptr(inv_deg), n_rows,
-                         _stream(raw.device)), "wgnn_normalize_rows")
+    _lib.run(raw.device, "wgnn_normalize_rows", _ptr(rowptr), _ptr(raw), _ptr(out), _ptr(inv_deg), n_rows,
+             _stream(raw.device))
     return out, inv_deg
 
 
@@ -927,8 +927,8 @@ def build_tile_plan(csr: AggCsr, n_row_tiles: Optional[int] = None, n_col_splits
         rowptr_c, col_c, val_c = csr.rowptr.contiguous(), csr.col.contiguous(), csr.val.contiguous()
         common = (_ptr(slot_vrow), _ptr(vrow32), _ptr(vpart32), _ptr(vk32), _ptr(flat_t), _ptr(hdr_c), n_flat, TILE_WAVES,
                   TILE_ROWS // TILE_WAVES, nblk_max, blk)
-        _lib.check(_lib.call(dev, "wgnn_tile_plan_count", _ptr(rowptr_c), _ptr(col_c), *common, _ptr(seg_total), None,
-                             _stream(dev)), "wgnn_tile_plan_count")
+        _lib.run(dev, "wgnn_tile_plan_count", _ptr(rowptr_c), _ptr(col_c), *common, _ptr(seg_total), None,
+                 _stream(dev))
         seg_ptr = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
         torch.cumsum(seg_total + (seg_total & 1), 0, out=seg_ptr[1:])        # an odd segment is padded to even (ABI 0.2.5)
         n_entries = int(seg_ptr[-1])
@@ -936,8 +936,8 @@ def build_tile_plan(csr: AggCsr, n_row_tiles: Optional[int] = None, n_col_splits
             raise ValueError("tile plan with >= 2^31 entries: shard the operand")
         seg_ptr32 = seg_ptr.to(torch.int32)
         entries = torch.empty((n_entries, 2), dtype=torch.int32, device=dev)
-        _lib.check(_lib.call(dev, "wgnn_tile_plan_fill", _ptr(rowptr_c), _ptr(col_c), _ptr(val_c), *common, _ptr(seg_total),
-                             None, _ptr(seg_ptr32), _ptr(entries), _stream(dev)), "wgnn_tile_plan_fill")
+        _lib.run(dev, "wgnn_tile_plan_fill", _ptr(rowptr_c), _ptr(col_c), _ptr(val_c), *common, _ptr(seg_total),
+                 None, _ptr(seg_ptr32), _ptr(entries), _stream(dev))
         return TilePlan(items.contiguous(), hdr_c, long_rows, n_part,
                         n_row_tiles, n_col_splits, n_loaders, entries, seg_ptr32, nblk_max, block_rows, geom)
     tile_v = torch.empty(V, dtype=torch.int64, device=dev); tile_v[order] = tile

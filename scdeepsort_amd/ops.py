@@ -9,6 +9,7 @@ non-CUDA tensor or a missing ``libwgnn_hip.so`` raises ``WgnnError``.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import NamedTuple, Optional
 
 import torch
@@ -169,14 +170,13 @@ def agg_fwd(csr: AggCsr, alpha: Optional[torch.Tensor], mode: int, self_idx: int
     if PROFILE is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record(torch.cuda.current_stream(dev))
-    rc = _lib.call(dev, "wgnn_agg_fwd",
+    _lib.run(dev, "wgnn_agg_fwd",
         _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.val), _ptr(alpha), mode, self_idx,
         _ptr(h_src), h_src.stride(0), _ptr(h_self), h_self.stride(0) if h_self is not None else 0,
         _ptr(ids), _ptr(csr.inv_deg), _ptr(bias), _ptr(out), out.stride(0), _ptr(neigh_sum), n_out, D,
         _dtype_code(h_src), _dtype_code(out), flags,
         _ptr(plan.items), plan.n_items, _ptr(plan.long_rows) if plan.n_long else None, plan.n_long,
         _ptr(part), plan.n_partials, _stream(dev))
-    _lib.check(rc, "wgnn_agg_fwd")
     if ev is not None:
         ev[1].record(torch.cuda.current_stream(dev))
         PROFILE.append((("rows", csr.n_rows, "cols", csr.n_cols, "nnz", csr.nnz, "D", D, "mode", mode,
@@ -221,24 +221,22 @@ def agg_bwd_src(csr: AggCsr, alpha: Optional[torch.Tensor], mode: int, g: torch.
         n_long = tp.long_rows.shape[0]
         with _Timed(dev, ("rows", t.n_rows, "cols", t.n_cols, "nnz", t.nnz, "D", D, "mode", mode, "kernel",
                           "agg_tiled_tall<EPI_BWD_SRC>" if tp.geom.tall else "agg_tiled_flat4<EPI_BWD_SRC>")):
-            rc = _lib.call(dev, "wgnn_agg_bwd_src_tiled",
+            _lib.run(dev, "wgnn_agg_bwd_src_tiled",
                 _ptr(alpha), mode, _ptr(scale), _ptr(g), g.shape[0], _ptr(scratch),
                 _ptr(h_src), h_src.stride(0) if h_src is not None else 0, _ptr(dh_src), dh_src.stride(0), _ptr(dalpha),
                 int(accumulate), t.n_rows, D, _ptr(tp.entries), _ptr(tp.seg_ptr), tp.nblk_max, tp.block_rows_arg,
                 _ptr(tp.items), _ptr(tp.hdr), tp.n_tiles, _ptr(tp.long_rows) if n_long else None, n_long,
                 _ptr(part), tp.n_partials, _stream(dev))
-        _lib.check(rc, "wgnn_agg_bwd_src_tiled")
         return dh_src
     if prescaled:
         raise WgnnError("prescaled gradient rows are an input of the LDS-streamed K2t only")
     part = _partials(t.plan, D, dev)
-    rc = _lib.call(dev, "wgnn_agg_bwd_src",
+    _lib.run(dev, "wgnn_agg_bwd_src",
         _ptr(t.rowptr), _ptr(t.col), _ptr(t.val), _ptr(alpha), mode, _ptr(inv_deg),
         _ptr(g), g.stride(0), _ptr(h_src), h_src.stride(0) if h_src is not None else 0,
         _ptr(dh_src), dh_src.stride(0), _ptr(dalpha), int(accumulate), t.n_rows, D,
         _ptr(t.plan.items), t.plan.n_items, _ptr(t.plan.long_rows) if t.plan.n_long else None, t.plan.n_long,
         _ptr(part), t.plan.n_partials, _stream(dev))
-    _lib.check(rc, "wgnn_agg_bwd_src")
     return dh_src
 
 
@@ -261,12 +259,11 @@ def agg_bwd_src_block(csr: AggCsr, row_ids: torch.Tensor, alpha: Optional[torch.
         h_src = _rowmajor(h_src.float())
     if alpha is not None:
         alpha = alpha.reshape(-1).float().contiguous()
-    rc = _lib.call(dev, "wgnn_agg_bwd_src",
+    _lib.run(dev, "wgnn_agg_bwd_src",
         _ptr(t_rowptr), _ptr(t_slot), _ptr(t_val), _ptr(alpha), mode, _ptr(inv_rows.float().contiguous()),
         _ptr(g), g.stride(0), _ptr(h_src), h_src.stride(0) if h_src is not None else 0,
         _ptr(dh_src), dh_src.stride(0), _ptr(dalpha), 0, csr.n_cols, D,
         _ptr(items), items.shape[0], None, 0, None, 0, _stream(dev))
-    _lib.check(rc, "wgnn_agg_bwd_src")
     return dh_src
 
 
@@ -294,21 +291,19 @@ def agg_bwd_alpha(csr: AggCsr, g: torch.Tensor, h_src: torch.Tensor, h_self: Opt
         h_src = h_src.contiguous()
         part = torch.empty(tp.n_partials * D, dtype=torch.float32, device=dev) if tp.n_partials else None
         n_long = tp.long_rows.shape[0]
-        rc = _lib.call(dev, "wgnn_agg_bwd_alpha_tiled",
+        _lib.run(dev, "wgnn_agg_bwd_alpha_tiled",
             _ptr(csr.inv_deg), _ptr(g), g.stride(0), _ptr(h_src), _ptr(h_self),
             h_self.stride(0) if h_self is not None else 0, _ptr(d_row), _ptr(d_self), n_out, D,
             _ptr(tp.entries), _ptr(tp.seg_ptr), tp.nblk_max, tp.block_rows_arg, _ptr(tp.items), _ptr(tp.hdr), tp.n_tiles,
             _ptr(tp.long_rows) if n_long else None, n_long, _ptr(part), tp.n_partials, _stream(dev))
-        _lib.check(rc, "wgnn_agg_bwd_alpha_tiled")
         return d_row, d_self
     part = _partials(plan, D, dev)
-    rc = _lib.call(dev, "wgnn_agg_bwd_alpha",
+    _lib.run(dev, "wgnn_agg_bwd_alpha",
         _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.val), _ptr(csr.inv_deg), _ptr(ids),
         _ptr(g), g.stride(0), _ptr(h_src), h_src.stride(0), _ptr(h_self), h_self.stride(0) if h_self is not None else 0,
         _ptr(d_row), _ptr(d_self), n_out, D, _lib.FLAG_SELF_COMPACT if self_compact else 0,
         _ptr(plan.items), plan.n_items, _ptr(plan.long_rows) if plan.n_long else None, plan.n_long,
         _ptr(part), plan.n_partials, _stream(dev))
-    _lib.check(rc, "wgnn_agg_bwd_alpha")
     return d_row, d_self
 
 
@@ -332,7 +327,6 @@ def agg_bwd_prepare(gout: torch.Tensor, out: Optional[torch.Tensor], inv_deg: Op
     """``wgnn_agg_bwd_prepare``: from the upstream gradient ``gout`` [R, D] of one aggregation pass (and the saved forward
     output ``out`` for the ReLU mask) in ONE read: ``g_scaled`` (K2t's pre-scaled source table), ``dh_self``, ``dalpha_row``
     (needs ``neigh_sum``), ``dself_row`` (needs ``h_self``) and ``dbias`` - whichever are asked for."""
-    import ctypes as C
     dev = _require_cuda(gout, out, inv_deg, alpha, h_self, neigh_sum)
     gout = _rowmajor(gout.float())
     R, D = gout.shape
@@ -356,12 +350,11 @@ def agg_bwd_prepare(gout: torch.Tensor, out: Optional[torch.Tensor], inv_deg: Op
         _lib.check(_lib.lib().wgnn_agg_bwd_prepare_workspace(R, D, C.addressof(nf)), "wgnn_agg_bwd_prepare_workspace")
         ws = torch.empty(max(1, nf.value), dtype=torch.float32, device=dev)
     need_self = res["dh_self"] is not None or res["dself_row"] is not None
-    rc = _lib.call(dev, "wgnn_agg_bwd_prepare", _ptr(gout), gout.stride(0), _ptr(out), out.stride(0) if out is not None else 0,
-                   _ptr(inv_deg), _ptr(alpha), mode, self_idx, _ptr(res["g_scaled"]),
-                   _ptr(h_self) if need_self else None, h_self.stride(0) if (need_self and h_self is not None) else 0,
-                   _ptr(res["dh_self"]), D, _ptr(neigh_sum), _ptr(res["dalpha_row"]), _ptr(res["dself_row"]), _ptr(res["dbias"]),
-                   R, D, _ptr(ws), nf.value, _stream(dev))
-    _lib.check(rc, "wgnn_agg_bwd_prepare")
+    _lib.run(dev, "wgnn_agg_bwd_prepare", _ptr(gout), gout.stride(0), _ptr(out), out.stride(0) if out is not None else 0,
+             _ptr(inv_deg), _ptr(alpha), mode, self_idx, _ptr(res["g_scaled"]),
+             _ptr(h_self) if need_self else None, h_self.stride(0) if (need_self and h_self is not None) else 0,
+             _ptr(res["dh_self"]), D, _ptr(neigh_sum), _ptr(res["dalpha_row"]), _ptr(res["dself_row"]), _ptr(res["dbias"]),
+             R, D, _ptr(ws), nf.value, _stream(dev))
     return res
 
 
@@ -371,7 +364,6 @@ class _CrossEntropySum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels):
-        import ctypes as C
         dev = _require_cuda(logits, labels)
         x = logits.float()
         if x.stride(1) != 1:
@@ -383,9 +375,8 @@ class _CrossEntropySum(torch.autograd.Function):
         ws = torch.empty(max(1, nf.value), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
         d = torch.empty((n, c), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
-        rc = _lib.call(dev, "wgnn_ce_sum_fwd_bwd", _ptr(x), x.stride(0), _ptr(y), n, c, _ptr(loss), _ptr(d), c, _ptr(ws), nf.value,
-                       _stream(dev))
-        _lib.check(rc, "wgnn_ce_sum_fwd_bwd")
+        _lib.run(dev, "wgnn_ce_sum_fwd_bwd", _ptr(x), x.stride(0), _ptr(y), n, c, _ptr(loss), _ptr(d), c, _ptr(ws), nf.value,
+                 _stream(dev))
         ctx.save_for_backward(d)
         ctx.in_dtype = logits.dtype
         return loss
@@ -451,13 +442,12 @@ def agg_fwd_tiled(csr: AggCsr, tplan, alpha: Optional[torch.Tensor], mode: int, 
             h_src, flags = src_scaled.contiguous(), flags | _lib.FLAG_SRC_PRESCALED
         else:
             scratch = torch.empty_like(h_src)
-    rc = _lib.call(dev, "wgnn_agg_fwd_tiled",
+    _lib.run(dev, "wgnn_agg_fwd_tiled",
         _ptr(csr.rowptr), _ptr(alpha), mode, self_idx,
         _ptr(h_src), h_src.shape[0], _ptr(scratch), _ptr(h_self), h_self.stride(0) if h_self is not None else 0,
         None, _ptr(csr.inv_deg), _ptr(bias), _ptr(out), out.stride(0), _ptr(neigh_sum), csr.n_rows, D, flags,
         _ptr(tplan.entries), _ptr(tplan.seg_ptr), tplan.nblk_max, tplan.block_rows_arg, _ptr(tplan.items), _ptr(tplan.hdr), tplan.n_tiles,
         _ptr(tplan.long_rows) if n_long else None, n_long, _ptr(part), tplan.n_partials, _stream(dev))
-    _lib.check(rc, "wgnn_agg_fwd_tiled")
     if ev is not None:
         ev[1].record(torch.cuda.current_stream(dev))
         PROFILE.append((("rows", csr.n_rows, "cols", csr.n_cols, "nnz", csr.nnz, "D", D, "mode", mode,
@@ -684,10 +674,9 @@ def linear_fwd(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tenso
         out2 = torch.empty((M, N), dtype=torch.float32, device=dev)
     if bias is not None:
         bias = bias.float().contiguous()
-    rc = _lib.call(dev, "wgnn_linear_fwd_ex", _ptr(x), _dtype_code(x), x.stride(0), _ptr(weight), weight.stride(0), _ptr(bias),
-                   _ptr(out), out.stride(0), _ptr(row_scale), _ptr(out2), N if out2 is not None else 0, M, N, K,
-                   (_lib.FLAG_RELU if relu else 0) | {None: 0, 64: 1 << 16, 128: 1 << 17}[tile_rows], _stream(dev))
-    _lib.check(rc, "wgnn_linear_fwd_ex")
+    _lib.run(dev, "wgnn_linear_fwd_ex", _ptr(x), _dtype_code(x), x.stride(0), _ptr(weight), weight.stride(0), _ptr(bias),
+             _ptr(out), out.stride(0), _ptr(row_scale), _ptr(out2), N if out2 is not None else 0, M, N, K,
+             (_lib.FLAG_RELU if relu else 0) | {None: 0, 64: 1 << 16, 128: 1 << 17}[tile_rows], _stream(dev))
     return out if out2 is None else (out, out2)
 
 
@@ -707,8 +696,7 @@ def mix_coeffs(alpha: torch.Tensor, self_idx: int, inv_deg: torch.Tensor):
     if alpha.shape[0] < n or not 0 <= self_idx < alpha.shape[0]:
         raise WgnnError("mix_coeffs: alpha needs one entry per row and one at self_idx")
     c = torch.empty((2, n), dtype=torch.float32, device=dev)
-    rc = _lib.call(dev, "wgnn_mix_coeffs", _ptr(alpha), self_idx, _ptr(inv_deg), _ptr(c[0]), _ptr(c[1]), n, _stream(dev))
-    _lib.check(rc, "wgnn_mix_coeffs")
+    _lib.run(dev, "wgnn_mix_coeffs", _ptr(alpha), self_idx, _ptr(inv_deg), _ptr(c[0]), _ptr(c[1]), n, _stream(dev))
     return c[0], c[1]
 
 
@@ -760,11 +748,10 @@ def linear_mix_fwd(x1: torch.Tensor, c1: torch.Tensor, x2: torch.Tensor, c2: tor
     # tagged like the wgrad entries (kernel, rows, N, K); cols / nnz / D as well, because bench.py's pass table reads them from
     # every record of a forward: two row tables of K columns in, no edges
     with _Timed(dev, ("rows", M, "cols", M, "nnz", 0, "D", K, "N", N, "K", K, "kernel", "linear_mix_mfma_f32")):
-        rc = _lib.call(dev, "wgnn_linear_mix_fwd", _ptr(x1), x1.stride(0), _ptr(c1), _ptr(x2), _dtype_code(x2), x2.stride(0),
-                       _ptr(c2), _ptr(weight), weight.stride(0), _ptr(bias), _ptr(out), out.stride(0) if out is not None else 0,
-                       _ptr(row_scale), _ptr(out_scaled), out_scaled.stride(0) if out_scaled is not None else 0, M, N, K,
-                       (_lib.FLAG_RELU if relu else 0) | {None: 0, 64: 1 << 16, 128: 1 << 17}[tile_rows], _stream(dev))
-    _lib.check(rc, "wgnn_linear_mix_fwd")
+        _lib.run(dev, "wgnn_linear_mix_fwd", _ptr(x1), x1.stride(0), _ptr(c1), _ptr(x2), _dtype_code(x2), x2.stride(0),
+                 _ptr(c2), _ptr(weight), weight.stride(0), _ptr(bias), _ptr(out), out.stride(0) if out is not None else 0,
+                 _ptr(row_scale), _ptr(out_scaled), out_scaled.stride(0) if out_scaled is not None else 0, M, N, K,
+                 (_lib.FLAG_RELU if relu else 0) | {None: 0, 64: 1 << 16, 128: 1 << 17}[tile_rows], _stream(dev))
     return out if row_scale is None else (out, out_scaled)
 
 
@@ -774,7 +761,6 @@ WGRAD_MIN_ROWS = 16384       # from this many rows on, the weight gradient of a 
 def linear_wgrad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """``dW = g.T @ x`` ([N, K]) with ``wgnn_linear_wgrad``: split along the row (node) axis, fp32 matrix cores, partial
     products folded in fixed order."""
-    import ctypes as C
     dev = _require_cuda(g, x)
     g = _rowmajor(g.float()); x = _rowmajor(x.float())
     M, N = g.shape
@@ -786,9 +772,8 @@ def linear_wgrad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     ws = torch.empty(max(1, nb.value // 4), dtype=torch.float32, device=dev)
     dW = torch.empty((N, K), dtype=torch.float32, device=dev)
     with _Timed(dev, ("rows", M, "N", N, "K", K, "kernel", "wgrad_mfma_f32 + wgrad_reduce")):
-        rc = _lib.call(dev, "wgnn_linear_wgrad", _ptr(g), g.stride(0), _ptr(x), x.stride(0), _ptr(dW), K, M, N, K, 0, _ptr(ws),
-                       ns.value, _stream(dev))
-    _lib.check(rc, "wgnn_linear_wgrad")
+        _lib.run(dev, "wgnn_linear_wgrad", _ptr(g), g.stride(0), _ptr(x), x.stride(0), _ptr(dW), K, M, N, K, 0, _ptr(ws),
+                 ns.value, _stream(dev))
     return dW
 
 
@@ -892,6 +877,95 @@ def check_gene_ids(col: torch.Tensor, n_genes: int) -> None:
             raise WgnnError(f"gene id out of range [0, {n_genes}) in the batch's CSR (min {int(lo)}, max {int(hi)})")
 
 
+# The operand layer of the resident row ops: each host-side chore of the wrappers below has its one place here.  ``name`` is the op
+# that speaks in a message, ``exc`` the class of its argument errors.
+
+def _csr_operand(name, exc, rowptr, col, val, val_name):
+    """A device CSR - ``rowptr`` int32 / int64 [B + 1], ``col`` int32 and the float32 values the op calls ``val_name``, one of each
+    per stored entry - checked: ``(rowptr, col, val, B, nnz, flags)``, the tensors contiguous as the C entries take them,
+    ``flags`` = ``FLAG_ROWPTR_I64`` for an int64 ``rowptr``."""
+    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
+        raise exc(f"{name} takes rowptr int32 / int64, col int32, {val_name} float32")
+    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
+        raise exc(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, {val_name} {tuple(val.shape)}; "
+                  f"col has {col.numel()} entries, {val_name} {val.numel()}")
+    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+    return rowptr.contiguous(), col.contiguous(), val.contiguous(), int(rowptr.shape[0]) - 1, int(col.shape[0]), flags
+
+
+def _group_operand(name, exc, group, B, K, check, dtypes=(torch.int32, torch.int64), says=None):
+    """The per-cell group vector [B] - an id in ``[0, K)``, or -1 = the cell takes no part - checked: shape and dtype (``says``:
+    the op's own words for that refusal), and with ``check`` the range (one ``aminmax`` and a read-back).  Returns ``group`` as
+    it came."""
+    if group.dtype not in dtypes or tuple(group.shape) != (B,):
+        raise exc(f"{says or f'{name}: group must hold one id per cell ([{B}]), int32 / int64'}, got {group.dtype} "
+                  f"{tuple(group.shape)}")
+    if check and B:
+        lo, hi = torch.aminmax(group)
+        if int(lo) < -1 or int(hi) >= K:
+            raise exc(f"{name}: group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
+    return group
+
+
+def _group_major(group, K):
+    """``(order int32 [B], seg_ptr int64 [K + 1])``: the cells group-major, ascending within a group - group ``k`` holds
+    ``order[seg_ptr[k]:seg_ptr[k + 1]]``, the ids outside ``[0, K)`` sort last.  A stable sort of the ids and a search for the
+    groups' bounds in the sorted ids, all on the device: no read-back."""
+    ids = group.to(torch.int64)
+    ids = torch.where((ids < 0) | (ids >= K), torch.full_like(ids, K), ids)
+    ids, order = torch.sort(ids, stable=True)
+    seg_ptr = torch.searchsorted(ids, torch.arange(K + 1, dtype=torch.int64, device=group.device)).contiguous()
+    return order.to(torch.int32), seg_ptr
+
+
+def _gene_major(rowptr, col, val, B, G, group):
+    """``(t_rowptr int32 [G + 1], t_cell int32, t_val f32)``: a checked batch gene-major, cells ascending within a gene and the
+    cells with ``group < 0`` left out - the library's stable transpose, a stable sort above that kernel's 32 768 columns.
+    ``rowptr`` is narrowed to int32 (the callers refuse ``nnz >= 2^31``); an empty batch has nothing to transpose."""
+    from .graph import _transpose_by_sort, _transpose_on_device
+    if B == 0:
+        return torch.zeros(G + 1, dtype=torch.int32, device=col.device), col[:0], val[:0]
+    transpose = _transpose_on_device if G <= 32768 else _transpose_by_sort
+    return transpose(rowptr.to(torch.int32).contiguous(), col, val, B, G, group >= 0)
+
+
+def _workspace_bytes(query, *sizes) -> int:
+    """What the size query ``query`` of a C entry answers for ``sizes``."""
+    nb = C.c_int64()
+    _lib.check(getattr(_lib.lib(), query)(*sizes, C.addressof(nb)), query)
+    return nb.value
+
+
+def _workspace(dev, query, *sizes, have=(None, 0)):
+    """``(workspace | None, n_bytes)`` for the C entry whose size query is ``query``: ``have`` where that already holds the bytes
+    asked for (``(None, 0)`` when none are), else a new 8-byte aligned buffer, rounded up to whole int64 elements."""
+    nb = _workspace_bytes(query, *sizes)
+    if nb <= have[1]:
+        return have
+    ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+    return ws, ws.numel() * 8
+
+
+def _row_strided(t, rows, cols) -> bool:
+    """Whether the 2-D ``t`` has unit column stride and a row stride ``>= cols``, where its shape lets a stride speak."""
+    return (t.shape[1] <= 1 or t.stride(1) == 1) and (rows <= 1 or t.stride(0) >= cols)
+
+
+def _view_2d(name, exc, what, t, dtype, rows, cols, at_least_cols=False):
+    """``t`` checked as a row-strided ``dtype`` [rows, cols] tensor (``at_least_cols``: [rows, >= cols]) - contiguous, or a view
+    into wider rows.  ``what`` names it in the message, after ``name`` where the op gives one."""
+    if (not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 2 or t.shape[0] != rows
+            or (t.shape[1] < cols if at_least_cols else t.shape[1] != cols) or not _row_strided(t, rows, cols)):
+        raise exc(f"{name + ': ' if name else ''}{what} must be {str(dtype)[6:]} [{rows}, {'>= ' if at_least_cols else ''}{cols}] "
+                  f"with unit column stride and a row stride >= {cols}")
+    return t
+
+
+def _ld(t, rows, cols) -> int:
+    """The leading dimension a C entry takes for the row-strided [rows, cols] ``t``: a single row's stride says nothing."""
+    return int(t.stride(0)) if rows > 1 else cols
+
+
 class _RowOperands(NamedTuple):
     """The batch, the table and ``alpha`` of a resident row op, ready for the C call."""
     rowptr: torch.Tensor
@@ -922,11 +996,8 @@ def _row_operands(name, rowptr, col, raw, table, alpha, H, check_cols, nnz_below
         raise WgnnError(f"table must be [G, >= {H}]")
     if alpha.numel() != G + 2:
         raise WgnnError(f"alpha has {alpha.numel()} entries, the table {G} rows (want G + 2)")
-    if col.shape[0] != raw.shape[0]:
-        raise WgnnError(f"col has {col.shape[0]} entries, raw {raw.shape[0]}")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or raw.dtype != torch.float32:
-        raise WgnnError(f"{name} takes rowptr int32 / int64, col int32, raw float32")
-    if nnz_below_2_31 and col.shape[0] >= 2 ** 31:
+    rowptr, col, raw, B, nnz, flags = _csr_operand(name, WgnnError, rowptr, col, raw, "raw")
+    if nnz_below_2_31 and nnz >= 2 ** 31:
         raise WgnnError(f"{name}: nnz >= 2^31 (split the batch)")
     if check_cols:
         check_gene_ids(col, G)
@@ -935,8 +1006,7 @@ def _row_operands(name, rowptr, col, raw, table, alpha, H, check_cols, nnz_below
     alpha = alpha.reshape(-1)
     if alpha.dtype != torch.float32 or not alpha.is_contiguous():
         alpha = alpha.float().contiguous()
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
-    return _RowOperands(rowptr.contiguous(), col.contiguous(), raw.contiguous(), table, alpha, rowptr.shape[0] - 1, G, Hp, flags)
+    return _RowOperands(rowptr, col, raw, table, alpha, B, G, Hp, flags)
 
 
 def _self_rows(self_rows, n_rows, batch, H, Hp, exc):
@@ -966,7 +1036,7 @@ def _headless_out(out, n_rows, Hp, dev, exc):
     if out is None:
         return torch.empty((n_rows, Hp), dtype=torch.float32, device=dev)
     if (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n_rows, Hp)
-            or out.stride(1) != 1 or out.stride(0) % 4 or out.stride(0) < Hp or out.data_ptr() % 16):
+            or not _row_strided(out, n_rows, Hp) or _ld(out, n_rows, Hp) % 4 or out.data_ptr() % 16):
         raise exc(f"out must be float32 [{n_rows}, {Hp}], unit column stride, 16-byte aligned rows")
     return out
 
@@ -987,9 +1057,7 @@ def _draw_outputs(out, B, n_cls, n_draws, accumulate, want_draws, dev, exc):
         draw_label = torch.empty((B, n_draws), dtype=torch.int32, device=dev)
         draw_prob = torch.empty((B, n_draws), dtype=torch.float32, device=dev)
     _require_cuda(votes, unsure, empty, conf_sum, draw_label, draw_prob)
-    if (votes.dtype != torch.int32 or tuple(votes.shape) != (B, n_cls) or (n_cls > 1 and votes.stride(1) != 1)
-            or (B > 1 and votes.stride(0) < n_cls)):
-        raise exc(f"votes must be int32 [{B}, {n_cls}] with unit column stride and a row stride >= {n_cls}")
+    _view_2d(None, exc, "votes", votes, torch.int32, B, n_cls)
     want = ((unsure, torch.int32, (B,)), (empty, torch.int32, (B,)), (conf_sum, torch.float64, (B,)))
     if any(t.dtype != d or tuple(t.shape) != s or not t.is_contiguous() for t, d, s in want):
         raise exc(f"unsure and empty must be contiguous int32 [{B}], conf_sum float64 [{B}]")
@@ -1029,11 +1097,10 @@ def predict_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tab
         logits = torch.empty((B, n_cls), dtype=torch.float32, device=dev) if want_logits else None
         label = torch.empty(B, dtype=torch.int32, device=dev)
         max_prob = torch.empty(B, dtype=torch.float32, device=dev)
-    rc = _lib.call(dev, "wgnn_predict_rows", *o.c_args, _ptr(bias), _ptr(self_rows),
-                   self_rows.stride(0) if self_rows is not None else 0, _ptr(out), Hp if out is not None else 0,
-                   _ptr(w_head), _ptr(b_head), n_cls, float(unsure_threshold), _ptr(logits),
-                   logits.shape[1] if logits is not None else 0, _ptr(label), _ptr(max_prob), o.flags, _stream(dev))
-    _lib.check(rc, "wgnn_predict_rows")
+    _lib.run(dev, "wgnn_predict_rows", *o.c_args, _ptr(bias), _ptr(self_rows),
+             self_rows.stride(0) if self_rows is not None else 0, _ptr(out), Hp if out is not None else 0,
+             _ptr(w_head), _ptr(b_head), n_cls, float(unsure_threshold), _ptr(logits),
+             logits.shape[1] if logits is not None else 0, _ptr(label), _ptr(max_prob), o.flags, _stream(dev))
     if head is None:
         return out if Hp == H else out[:, :H]
     if fused:
@@ -1087,19 +1154,17 @@ def _predict_rows_draws(name, exc, accumulate_flag, thin, rowptr, col, raw, tabl
         if accumulate or want_draws:
             raise exc(f"{name}: accumulate and want_draws need a head")
         out = _headless_out(out, B * n_draws, Hp, dev, exc)
-        rc = _lib.call(dev, "wgnn_" + name, *lead, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
-                       None, None, 0, 0.0, None, 0, None, None, None, None, None, *read_ptrs, o.flags, _stream(dev))
-        _lib.check(rc, "wgnn_" + name)
+        _lib.run(dev, "wgnn_" + name, *lead, _ptr(out), _ld(out, B * n_draws, Hp),
+                 None, None, 0, 0.0, None, 0, None, None, None, None, None, *read_ptrs, o.flags, _stream(dev))
         h = out if Hp == H else out[:, :H]
         return (h, *reads) if want_reads else h
     w_head, b_head, n_cls = _fused_head(
         head, Hp, lambda c: exc(f"{name}: a [{c}, {Hp}] head is beyond the {HEAD_LDS_BYTES} bytes the kernel stages"))
     votes, unsure, empty, conf_sum, draw_label, draw_prob = _draw_outputs(out, B, n_cls, n_draws, accumulate, want_draws, dev, exc)
-    rc = _lib.call(dev, "wgnn_" + name, *lead, None, 0, _ptr(w_head), _ptr(b_head), n_cls,
-                   float(unsure_threshold), _ptr(votes), votes.stride(0) if B > 1 else max(int(votes.stride(0)), n_cls),
-                   _ptr(unsure), _ptr(empty), _ptr(conf_sum), _ptr(draw_label), _ptr(draw_prob), *read_ptrs,
-                   o.flags | (accumulate_flag if accumulate else 0), _stream(dev))
-    _lib.check(rc, "wgnn_" + name)
+    _lib.run(dev, "wgnn_" + name, *lead, None, 0, _ptr(w_head), _ptr(b_head), n_cls,
+             float(unsure_threshold), _ptr(votes), _ld(votes, B, n_cls),
+             _ptr(unsure), _ptr(empty), _ptr(conf_sum), _ptr(draw_label), _ptr(draw_prob), *read_ptrs,
+             o.flags | (accumulate_flag if accumulate else 0), _stream(dev))
     return (votes, unsure, empty, conf_sum, draw_label, draw_prob, *reads)
 
 
@@ -1190,21 +1255,19 @@ def predict_rows_panels(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tens
         raise exc(f"{name}: member must be int64 [{o.G}] (the uint64 membership words)")
     member = member.contiguous()
     if lib is not None:
-        if lib.dtype != torch.int64 or tuple(lib.shape) != (B, P) or (P > 1 and lib.stride(1) != 1) or (B > 1 and lib.stride(0) < P):
-            raise exc(f"{name}: lib must be int64 [{B}, {P}] with unit column stride and a row stride >= {P}")
+        _view_2d(name, exc, "lib", lib, torch.int64, B, P)
     if B * P >= 2 ** 31:
         raise exc(f"{name}: B * n_panels >= 2^31 (split the batch or the panels)")
     bias = _pad_cols(bias, Hp)
     self_rows = _self_rows(self_rows, B * P, f"{B} cells x {P} panels", H, Hp, exc)
-    ld_lib = (int(lib.stride(0)) if B > 1 else max(int(lib.stride(0)), P)) if lib is not None else 0
+    ld_lib = _ld(lib, B, P) if lib is not None else 0
     lead = (*o.c_args, _ptr(bias), _ptr(self_rows), self_rows.stride(0) if self_rows is not None else 0,
             _ptr(member), P, _ptr(lib), ld_lib, float(scale), float(threshold))
     entries = torch.empty((B, P), dtype=torch.int32, device=dev) if want_entries else None
     if head is None:
         out = _headless_out(out, B * P, Hp, dev, exc)
-        rc = _lib.call(dev, "wgnn_" + name, *lead, _ptr(out), out.stride(0) if out.shape[0] > 1 else Hp,
-                       None, None, 0, 0.0, None, 0, None, None, _ptr(entries), o.flags, _stream(dev))
-        _lib.check(rc, "wgnn_" + name)
+        _lib.run(dev, "wgnn_" + name, *lead, _ptr(out), _ld(out, B * P, Hp),
+                 None, None, 0, 0.0, None, 0, None, None, _ptr(entries), o.flags, _stream(dev))
         h = out if Hp == H else out[:, :H]
         return (h, entries) if want_entries else h
     w_head, b_head, n_cls = _fused_head(
@@ -1212,10 +1275,9 @@ def predict_rows_panels(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tens
     logits = torch.empty((B * P, n_cls), dtype=torch.float32, device=dev) if want_logits else None
     label = torch.empty((B, P), dtype=torch.int32, device=dev)
     max_prob = torch.empty((B, P), dtype=torch.float32, device=dev)
-    rc = _lib.call(dev, "wgnn_" + name, *lead, None, 0, _ptr(w_head), _ptr(b_head), n_cls, float(unsure_threshold),
-                   _ptr(logits), n_cls if logits is not None else 0, _ptr(label), _ptr(max_prob), _ptr(entries), o.flags,
-                   _stream(dev))
-    _lib.check(rc, "wgnn_" + name)
+    _lib.run(dev, "wgnn_" + name, *lead, None, 0, _ptr(w_head), _ptr(b_head), n_cls, float(unsure_threshold),
+             _ptr(logits), n_cls if logits is not None else 0, _ptr(label), _ptr(max_prob), _ptr(entries), o.flags,
+             _stream(dev))
     return (logits, label, max_prob, entries) if want_entries else (logits, label, max_prob)
 
 
@@ -1244,28 +1306,19 @@ def rank_sets_rows(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, m
         raise ValueError(f"{name}: max_rank = {R} must be in [1, 2^30]")
     if G <= 0:
         raise ValueError(f"{name}: n_genes = {G} must be positive")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
-        raise ValueError(f"{name} takes rowptr int32 / int64, col int32, val float32")
-    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
-        raise ValueError(f"{name}: rowptr must be [B + 1], col and val one entry each per stored value")
+    rowptr, col, val, B, _, flags = _csr_operand(name, ValueError, rowptr, col, val, "val")
     if member.dtype != torch.int64 or tuple(member.shape) != (G,):
         raise ValueError(f"{name}: member must be int64 [{G}] (the uint64 membership words)")
-    B = int(rowptr.shape[0]) - 1
     if check_cols:
         check_gene_ids(col, G)
-    rowptr, col, val, member = rowptr.contiguous(), col.contiguous(), val.contiguous(), member.contiguous()
+    member = member.contiguous()
     if out is None:
         out = (torch.empty((B, P), dtype=torch.int64, device=dev), torch.empty((B, P), dtype=torch.int32, device=dev))
     rank2_sum, present = out
-    for t, dt, what in ((rank2_sum, torch.int64, "rank2_sum"), (present, torch.int32, "present")):
-        if t.dtype != dt or t.dim() != 2 or t.shape[0] != B or t.shape[1] < P or (t.shape[1] > 1 and t.stride(1) != 1) or \
-                (B > 1 and t.stride(0) < P):
-            raise ValueError(f"{name}: out's {what} must be {dt} [{B}, >= {P}] with unit column stride and a row stride >= {P}")
-    ld = lambda t: int(t.stride(0)) if B > 1 else max(int(t.stride(0)), P)
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
-    rc = _lib.call(dev, "wgnn_" + name, _ptr(rowptr), _ptr(col), _ptr(val), B, G, _ptr(member), P, R,
-                   _ptr(rank2_sum), ld(rank2_sum), _ptr(present), ld(present), flags, _stream(dev))
-    _lib.check(rc, "wgnn_" + name)
+    _view_2d(name, ValueError, "out's rank2_sum", rank2_sum, torch.int64, B, P, at_least_cols=True)
+    _view_2d(name, ValueError, "out's present", present, torch.int32, B, P, at_least_cols=True)
+    _lib.run(dev, "wgnn_" + name, _ptr(rowptr), _ptr(col), _ptr(val), B, G, _ptr(member), P, R,
+             _ptr(rank2_sum), _ld(rank2_sum, B, P), _ptr(present), _ld(present, B, P), flags, _stream(dev))
     return rank2_sum[:, :P], present[:, :P]
 
 
@@ -1338,16 +1391,10 @@ def _count_csr(name, rowptr, col, cnt, lib=None):
     """The operand of those four ops - a device CSR of raw counts over the bundle's gene ids, and ``lib`` int64 [B] where the op
     takes library sizes - checked (``ValueError`` under the op's ``name``): ``(rowptr, col, cnt, lib, B, nnz, flags)``, the
     tensors contiguous, as the C entries take them."""
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or cnt.dtype != torch.float32:
-        raise ValueError(f"{name} takes rowptr int32 / int64, col int32, cnt float32")
-    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != cnt.shape:
-        raise ValueError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, cnt {tuple(cnt.shape)}")
-    B = int(rowptr.shape[0]) - 1
+    rowptr, col, cnt, B, nnz, flags = _csr_operand(name, ValueError, rowptr, col, cnt, "cnt")
     if lib is not None and (lib.dtype != torch.int64 or tuple(lib.shape) != (B,)):
         raise ValueError(f"{name}: lib must be int64 [{B}]")
-    flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
-    return (rowptr.contiguous(), col.contiguous(), cnt.contiguous(), None if lib is None else lib.contiguous(), B,
-            int(col.shape[0]), flags)
+    return rowptr, col, cnt, None if lib is None else lib.contiguous(), B, nnz, flags
 
 
 def _scan(n_out: torch.Tensor):
@@ -1396,12 +1443,12 @@ def pair_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     n_out = torch.empty(n_pairs, dtype=torch.int32, device=dev)
     head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(lib), _ptr(a), _ptr(b), n_pairs, float(scale), float(threshold))
-    _lib.check(_lib.call(dev, "wgnn_pair_rows_count", *head, _ptr(n_out), _ptr(status), flags, _stream(dev)), "wgnn_pair_rows_count")
+    _lib.run(dev, "wgnn_pair_rows_count", *head, _ptr(n_out), _ptr(status), flags, _stream(dev))
     out_rowptr, total = _scan(n_out)
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_val = torch.empty(total, dtype=torch.float32, device=dev)
-    _lib.check(_lib.call(dev, "wgnn_pair_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(status), flags,
-                         _stream(dev)), "wgnn_pair_rows_fill")
+    _lib.run(dev, "wgnn_pair_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(status), flags,
+             _stream(dev))
     _check_status("pair_rows", int(status), _PAIR_STATUS)
     return out_rowptr, out_col, out_val
 
@@ -1462,18 +1509,17 @@ def pool_rows_grouped(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor
             rows = torch.repeat_interleave(torch.arange(n, device=dev), s_rowptr[k0 + 1:k1 + 1] - s_rowptr[k0:k1], output_size=e1 - e0)
             acc[rows, s_col[e0:e1].long()] = s_cnt[e0:e1]                 # a seeded group's genes are unique: plain stores
         gp, tot = group_ptr[k0:k1 + 1], total[k0:k1]
-        _lib.check(_lib.call(dev, "wgnn_pool_rows_accumulate", _ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(gp), _ptr(members),
-                             n, G, _ptr(acc), G, int(cells_per_unit), int(slab_genes), _ptr(status), flags, _stream(dev)),
-                   "wgnn_pool_rows_accumulate")
+        _lib.run(dev, "wgnn_pool_rows_accumulate", _ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(gp), _ptr(members),
+                 n, G, _ptr(acc), G, int(cells_per_unit), int(slab_genes), _ptr(status), flags, _stream(dev))
         head = (_ptr(acc), G, _ptr(tot), n, G, float(scale), float(threshold))
         n_out = torch.empty(n, dtype=torch.int32, device=dev)
-        _lib.check(_lib.call(dev, "wgnn_pool_rows_count", *head, _ptr(n_out), _ptr(status), _stream(dev)), "wgnn_pool_rows_count")
+        _lib.run(dev, "wgnn_pool_rows_count", *head, _ptr(n_out), _ptr(status), _stream(dev))
         ptr, kept = _scan(n_out)
         out_col = torch.empty(kept, dtype=torch.int32, device=dev)
         out_val = torch.empty(kept, dtype=torch.float32, device=dev)
         out_cnt = torch.empty(kept, dtype=torch.int64, device=dev)
-        _lib.check(_lib.call(dev, "wgnn_pool_rows_fill", *head, _ptr(ptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt), _ptr(status),
-                             _stream(dev)), "wgnn_pool_rows_fill")
+        _lib.run(dev, "wgnn_pool_rows_fill", *head, _ptr(ptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt), _ptr(status),
+                 _stream(dev))
         parts.append((n_out, out_col, out_val, out_cnt))
     _check_status("pool_rows", int(status), _POOL_STATUS)
     out_rowptr = torch.zeros(K + 1, dtype=torch.int64, device=dev)
@@ -1516,10 +1562,7 @@ def pool_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
         raise ValueError(f"pool_rows: n_groups = {n_groups} must not be negative")
     if lib.dtype != torch.int64 or tuple(lib.shape) != (B,):
         raise ValueError(f"pool_rows: lib must be int64 [{B}]")
-    if group.dtype != torch.int32 or tuple(group.shape) != (B,):
-        raise ValueError(f"pool_rows: group must be int32 [{B}]")
-    if B and (int(group.min()) < -1 or int(group.max()) >= K):
-        raise ValueError(f"pool_rows: group id out of range [-1, {K})")
+    _group_operand("pool_rows", ValueError, group, B, K, True, dtypes=(torch.int32,), says=f"pool_rows: group must be int32 [{B}]")
     s_total = s_cells = None
     if seed is not None:
         if len(seed) != 5:
@@ -1599,15 +1642,14 @@ def soup_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     soup_mapped = torch.empty(B * D, dtype=torch.int32, device=dev)
     head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(lib), _ptr(n_add), _ptr(cdf), G, D, int(row0), int(draw0),
             int(seed) & (2 ** 64 - 1), float(scale), float(threshold), int(slab_genes))
-    _lib.check(_lib.call(dev, "wgnn_soup_rows_count", *head, _ptr(n_out), _ptr(soup_mapped), _ptr(status), flags, _stream(dev)),
-               "wgnn_soup_rows_count")
+    _lib.run(dev, "wgnn_soup_rows_count", *head, _ptr(n_out), _ptr(soup_mapped), _ptr(status), flags, _stream(dev))
     out_rowptr, total = _scan(n_out)
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_val = torch.empty(total, dtype=torch.float32, device=dev)
     out_cnt = torch.empty(total, dtype=torch.int64, device=dev) if want_cnt else None
     if total:
-        _lib.check(_lib.call(dev, "wgnn_soup_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt),
-                             _ptr(status), flags, _stream(dev)), "wgnn_soup_rows_fill")
+        _lib.run(dev, "wgnn_soup_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt),
+                 _ptr(status), flags, _stream(dev))
     _check_status("soup_rows", int(status), _SOUP_STATUS)
     out = (out_rowptr, out_col, out_val, soup_mapped)
     return out + (out_cnt,) if want_cnt else out
@@ -1658,14 +1700,14 @@ def hood_rows(rowptr: torch.Tensor, col: torch.Tensor, cnt: torch.Tensor, lib: t
     n_out = torch.empty(U, dtype=torch.int32, device=dev)
     head = (_ptr(rowptr), _ptr(col), _ptr(cnt), B, nnz, _ptr(lib), _ptr(hood_ptr), _ptr(members), U, M, G, float(scale),
             float(threshold), int(slab_genes))
-    _lib.check(_lib.call(dev, "wgnn_hood_rows_count", *head, _ptr(n_out), _ptr(status), flags, _stream(dev)), "wgnn_hood_rows_count")
+    _lib.run(dev, "wgnn_hood_rows_count", *head, _ptr(n_out), _ptr(status), flags, _stream(dev))
     out_rowptr, total = _scan(n_out)
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_val = torch.empty(total, dtype=torch.float32, device=dev)
     out_cnt = torch.empty(total, dtype=torch.int64, device=dev)
     if total:
-        _lib.check(_lib.call(dev, "wgnn_hood_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt),
-                             _ptr(status), flags, _stream(dev)), "wgnn_hood_rows_fill")
+        _lib.run(dev, "wgnn_hood_rows_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_val), _ptr(out_cnt),
+                 _ptr(status), flags, _stream(dev))
     _check_status("hood_rows", int(status), _HOOD_STATUS)
     return out_rowptr, out_col, out_val, out_cnt
 
@@ -1708,9 +1750,8 @@ def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tabl
         if explicit_self is None:
             explicit_self = self_rows is not None
         flags |= (_lib.ATTRIB_ACCUMULATE if accumulate else 0) | (_lib.ATTRIB_EXPLICIT_SELF if explicit_self else 0)
-        rc = _lib.call(dev, "wgnn_attrib_rows", *o.c_args, None, None, 0, None, None, 0, None, 0.0, None, _ptr(direction),
-                       direction.stride(0), _ptr(scores), None, None, None, None, 0, flags, _stream(dev))
-        _lib.check(rc, "wgnn_attrib_rows")
+        _lib.run(dev, "wgnn_attrib_rows", *o.c_args, None, None, 0, None, None, 0, None, 0.0, None, _ptr(direction),
+                 direction.stride(0), _ptr(scores), None, None, None, None, 0, flags, _stream(dev))
         return scores
     if accumulate:
         raise WgnnError("head mode overwrites the scores")
@@ -1731,11 +1772,10 @@ def attrib_rows(rowptr: torch.Tensor, col: torch.Tensor, raw: torch.Tensor, tabl
     base = torch.empty(B, dtype=torch.float32, device=dev)
     label = torch.empty(B, dtype=torch.int32, device=dev)
     v = torch.empty((B, Hp), dtype=torch.float32, device=dev) if want_direction else None
-    rc = _lib.call(dev, "wgnn_attrib_rows", *o.c_args, _ptr(bias), _ptr(self_rows),
-                   self_rows.stride(0) if self_rows is not None else 0, _ptr(w_head), _ptr(b_head), n_cls, _ptr(target),
-                   float(unsure_threshold), _ptr(label), None, 0, _ptr(scores), _ptr(target_out), _ptr(logit), _ptr(base), _ptr(v),
-                   Hp if v is not None else 0, flags, _stream(dev))
-    _lib.check(rc, "wgnn_attrib_rows")
+    _lib.run(dev, "wgnn_attrib_rows", *o.c_args, _ptr(bias), _ptr(self_rows),
+             self_rows.stride(0) if self_rows is not None else 0, _ptr(w_head), _ptr(b_head), n_cls, _ptr(target),
+             float(unsure_threshold), _ptr(label), None, 0, _ptr(scores), _ptr(target_out), _ptr(logit), _ptr(base), _ptr(v),
+             Hp if v is not None else 0, flags, _stream(dev))
     return scores, target_out, logit, base, label, (v if v is None or Hp == H else v[:, :H])
 
 
@@ -1745,17 +1785,11 @@ def rows_topk(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Tensor, k: 
     dev = _require_cuda(rowptr, col, scores)
     if not 1 <= int(k) <= 64:
         raise WgnnError(f"rows_topk: k = {k} is outside [1, 64]")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or scores.dtype != torch.float32:
-        raise WgnnError("rows_topk takes rowptr int32 / int64, col int32, scores float32")
-    if col.shape[0] != scores.shape[0]:
-        raise WgnnError(f"col has {col.shape[0]} entries, scores {scores.shape[0]}")
-    B = rowptr.shape[0] - 1
-    rowptr = rowptr.contiguous(); col = col.contiguous(); scores = scores.contiguous()
+    rowptr, col, scores, B, _, flags = _csr_operand("rows_topk", WgnnError, rowptr, col, scores, "scores")
     gene = torch.empty((B, int(k)), dtype=torch.int32, device=dev)
     top = torch.empty((B, int(k)), dtype=torch.float32, device=dev)
-    rc = _lib.call(dev, "wgnn_rows_topk", _ptr(rowptr), _ptr(col), _ptr(scores), B, int(k), _ptr(gene), _ptr(top),
-                   _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0, _stream(dev))
-    _lib.check(rc, "wgnn_rows_topk")
+    _lib.run(dev, "wgnn_rows_topk", _ptr(rowptr), _ptr(col), _ptr(scores), B, int(k), _ptr(gene), _ptr(top),
+             flags, _stream(dev))
     return gene, top
 
 
@@ -1771,28 +1805,15 @@ def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Ten
     library's stable transpose (``group >= 0`` as its row mask; a stable sort above that kernel's 32 768 columns), then one
     wavefront per gene adds in a fixed order: no atomics, two calls are bit-identical.  ``check``: verify the ranges of
     ``group`` and ``col`` (one ``aminmax`` each and a read-back)."""
-    import ctypes as C
-    from .graph import _transpose_by_sort, _transpose_on_device
+    name = "group_gene_reduce"
     dev = _require_cuda(rowptr, col, scores, group, *(out or ()))
     K, G = int(n_groups), int(n_genes)
     if K <= 0 or G <= 0:
-        raise WgnnError(f"group_gene_reduce: n_groups = {K} and n_genes = {G} must be positive")
-    B = rowptr.shape[0] - 1
-    nnz = col.shape[0]
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or scores.dtype != torch.float32:
-        raise WgnnError("group_gene_reduce takes rowptr int32 / int64, col int32, scores float32")
-    if scores.shape != (nnz,):
-        raise WgnnError(f"col has {nnz} entries, scores {tuple(scores.shape)}")
+        raise WgnnError(f"{name}: n_groups = {K} and n_genes = {G} must be positive")
+    rowptr, col, scores, B, nnz, _ = _csr_operand(name, WgnnError, rowptr, col, scores, "scores")
     if nnz >= 2 ** 31:
-        raise WgnnError("group_gene_reduce: nnz >= 2^31 (split the batch and accumulate)")
-    if group.shape != (B,):
-        raise WgnnError(f"group must hold one id per cell ([{B}]), got {tuple(group.shape)}")
-    if group.dtype not in (torch.int32, torch.int64):
-        raise WgnnError("group must be int32 / int64")
-    if check and B:
-        lo, hi = torch.aminmax(group)
-        if int(lo) < -1 or int(hi) >= K:
-            raise WgnnError(f"group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
+        raise WgnnError(f"{name}: nnz >= 2^31 (split the batch and accumulate)")
+    _group_operand(name, WgnnError, group, B, K, check)
     if check:
         check_gene_ids(col, G)
     if out is None:
@@ -1804,16 +1825,10 @@ def group_gene_reduce(rowptr: torch.Tensor, col: torch.Tensor, scores: torch.Ten
             not total.is_contiguous() or not count.is_contiguous():
         raise WgnnError(f"out must be contiguous (float64 [{K}, {G}], int32 [{K}, {G}])")
     group = group.to(torch.int32).contiguous()
-    rowptr32 = rowptr.to(torch.int32).contiguous()           # nnz < 2^31: a safe narrowing
-    col = col.contiguous(); scores = scores.contiguous()
-    transpose = _transpose_on_device if G <= 32768 else _transpose_by_sort
-    t_rowptr, t_cell, t_score = transpose(rowptr32, col, scores, B, G, group >= 0)
-    nb = C.c_int64()
-    _lib.check(_lib.lib().wgnn_group_gene_reduce_workspace(B, nnz, K, G, C.addressof(nb)), "wgnn_group_gene_reduce_workspace")
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev) if nb.value else None
-    rc = _lib.call(dev, "wgnn_group_gene_reduce", _ptr(t_rowptr), _ptr(t_cell), _ptr(t_score), _ptr(group), B, K, G,
-                   _ptr(total), _ptr(count), _ptr(ws), nb.value, _lib.MARKERS_ACCUMULATE if accumulate else 0, _stream(dev))
-    _lib.check(rc, "wgnn_group_gene_reduce")
+    t_rowptr, t_cell, t_score = _gene_major(rowptr, col, scores, B, G, group)
+    ws, ws_bytes = _workspace(dev, "wgnn_group_gene_reduce_workspace", B, nnz, K, G)     # none today: the partial sums live in LDS
+    _lib.run(dev, "wgnn_group_gene_reduce", _ptr(t_rowptr), _ptr(t_cell), _ptr(t_score), _ptr(group), B, K, G,
+             _ptr(total), _ptr(count), _ptr(ws), ws_bytes, _lib.MARKERS_ACCUMULATE if accumulate else 0, _stream(dev))
     return total, count
 
 
@@ -1837,8 +1852,6 @@ def rank_genes_groups(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor
     integers: two calls are bit-identical and the tables do not depend on the order of cells or of a cell's genes.  ``check``:
     verify the ranges of ``group`` and ``col`` (one ``aminmax`` each and a read-back); without it an out-of-range GROUP takes no
     part (an out-of-range gene id is the transpose's to fault on).  Argument errors are ``ValueError``."""
-    import ctypes as C
-    from .graph import _transpose_by_sort, _transpose_on_device
     name = "rank_genes_groups"
     dev = _require_cuda(rowptr, col, val, group, *(out or ()))
     K, G = int(n_groups), int(n_genes)
@@ -1846,49 +1859,30 @@ def rank_genes_groups(rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor
         raise ValueError(f"{name}: n_groups = {K} must be in [1, {RANK_GENES_MAX_GROUPS}]")
     if G <= 0:
         raise ValueError(f"{name}: n_genes = {G} must be positive")
-    if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
-        raise ValueError(f"{name} takes rowptr int32 / int64, col int32, val float32")
-    if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
-        raise ValueError(f"{name}: rowptr must be [B + 1], col and val one entry each per stored value")
-    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+    rowptr, col, val, B, nnz, _ = _csr_operand(name, ValueError, rowptr, col, val, "val")
     if B > RANK_GENES_MAX_ROWS:
         raise ValueError(f"{name}: {B} cells > 2^20 (the tie term N^3 must fit int64)")
     if nnz >= 2 ** 31:
         raise ValueError(f"{name}: nnz >= 2^31")
-    if group.dtype not in (torch.int32, torch.int64) or tuple(group.shape) != (B,):
-        raise ValueError(f"{name}: group must hold one int32 / int64 id per cell ([{B}])")
-    if check and B:
-        lo, hi = torch.aminmax(group)
-        if int(lo) < -1 or int(hi) >= K:
-            raise ValueError(f"{name}: group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
+    _group_operand(name, ValueError, group, B, K, check)
     if check:
         check_gene_ids(col, G)
     if out is None:
         out = (torch.empty((K, G), dtype=torch.int64, device=dev), torch.empty((K, G), dtype=torch.int32, device=dev),
                torch.empty(G, dtype=torch.int64, device=dev))
     rank2_sum, count, tie_sum = out
-    for t, dt, what in ((rank2_sum, torch.int64, "rank2_sum"), (count, torch.int32, "count")):
-        if t.dtype != dt or t.dim() != 2 or tuple(t.shape) != (K, G) or (G > 1 and t.stride(1) != 1) or (K > 1 and t.stride(0) < G):
-            raise ValueError(f"{name}: out's {what} must be {dt} [{K}, {G}] with unit column stride and a row stride >= {G}")
+    _view_2d(name, ValueError, "out's rank2_sum", rank2_sum, torch.int64, K, G)
+    _view_2d(name, ValueError, "out's count", count, torch.int32, K, G)
     if tie_sum.dtype != torch.int64 or tuple(tie_sum.shape) != (G,) or (G > 1 and tie_sum.stride(0) != 1):
         raise ValueError(f"{name}: out's tie_sum must be a dense int64 [{G}]")
-    ld = lambda t: int(t.stride(0)) if K > 1 else max(int(t.stride(0)), G)
     group = group.to(torch.int32).contiguous()
     in_range = (group >= 0) & (group < K)
     group_size = torch.bincount(group[in_range].long(), minlength=K).to(torch.int64)
-    rowptr32 = rowptr.to(torch.int32).contiguous()           # nnz < 2^31: a safe narrowing
-    transpose = _transpose_on_device if G <= 32768 else _transpose_by_sort
-    if B:
-        t_rowptr, t_cell, t_val = transpose(rowptr32, col.contiguous(), val.contiguous(), B, G, group >= 0)
-    else:                                                    # an empty batch is valid: nothing to transpose
-        t_rowptr, t_cell, t_val = torch.zeros(G + 1, dtype=torch.int32, device=dev), col[:0], val[:0]
-    nb = C.c_int64()
-    _lib.check(_lib.lib().wgnn_rank_genes_groups_workspace(B, nnz, K, G, C.addressof(nb)), "wgnn_rank_genes_groups_workspace")
-    ws = torch.empty((nb.value + 7) // 8, dtype=torch.int64, device=dev)
-    rc = _lib.call(dev, "wgnn_rank_genes_groups", _ptr(t_rowptr), _ptr(t_cell), _ptr(t_val), _ptr(group), _ptr(group_size),
-                   B, K, G, _ptr(rank2_sum), ld(rank2_sum), _ptr(count), ld(count), _ptr(tie_sum), _ptr(ws), nb.value, 0,
-                   _stream(dev))
-    _lib.check(rc, "wgnn_rank_genes_groups")
+    t_rowptr, t_cell, t_val = _gene_major(rowptr, col, val, B, G, group)
+    ws, ws_bytes = _workspace(dev, "wgnn_rank_genes_groups_workspace", B, nnz, K, G)
+    _lib.run(dev, "wgnn_rank_genes_groups", _ptr(t_rowptr), _ptr(t_cell), _ptr(t_val), _ptr(group), _ptr(group_size),
+             B, K, G, _ptr(rank2_sum), _ld(rank2_sum, K, G), _ptr(count), _ld(count, K, G), _ptr(tie_sum), _ptr(ws), ws_bytes, 0,
+             _stream(dev))
     return rank2_sum, count, tie_sum, group_size
 
 
@@ -1906,7 +1900,6 @@ def group_class_reduce(logits: torch.Tensor, label: torch.Tensor, group: torch.T
     ids, the groups' bounds by a search in the sorted ids: no read-back), then one wavefront per 256-cell chunk of a group
     adds in a fixed order: no atomics, two calls are bit-identical.  ``check``: verify the range of ``group`` (one ``aminmax``
     and a read-back); without it an id outside ``[0, n_groups)`` takes no part."""
-    import ctypes as C
     dev = _require_cuda(logits, label, group, *(out or ()))
     K = int(n_groups)
     if K <= 0:
@@ -1918,14 +1911,7 @@ def group_class_reduce(logits: torch.Tensor, label: torch.Tensor, group: torch.T
         raise WgnnError("group_class_reduce: B >= 2^31 (split the batch and accumulate)")
     if label.shape != (B,) or label.dtype not in (torch.int32, torch.int64):
         raise WgnnError(f"label must hold one int32 / int64 class id per cell ([{B}]), got {label.dtype} {tuple(label.shape)}")
-    if group.shape != (B,):
-        raise WgnnError(f"group must hold one id per cell ([{B}]), got {tuple(group.shape)}")
-    if group.dtype not in (torch.int32, torch.int64):
-        raise WgnnError("group must be int32 / int64")
-    if check and B:
-        lo, hi = torch.aminmax(group)
-        if int(lo) < -1 or int(hi) >= K:
-            raise WgnnError(f"group id out of range [-1, {K}) (min {int(lo)}, max {int(hi)})")
+    _group_operand("group_class_reduce", WgnnError, group, B, K, check)
     if out is None:
         if accumulate:
             raise WgnnError("accumulate needs the tables to add to (out=)")
@@ -1937,22 +1923,14 @@ def group_class_reduce(logits: torch.Tensor, label: torch.Tensor, group: torch.T
     if any(tuple(o.shape) != s or o.dtype != d or not o.is_contiguous() for o, (s, d) in zip(out, want)):
         raise WgnnError(f"out must be contiguous (float64 [{K}, {n_cls}], float64 [{K}], int32 [{K}, {n_cls}], int32 [{K}, 3])")
     prob_sum, conf_sum, votes, tally = out
-    if logits.stride(1) != 1 or (B > 1 and logits.stride(0) < n_cls):
+    if not _row_strided(logits, B, n_cls):
         logits = logits.contiguous()
-    ld = logits.stride(0) if B > 1 else max(int(logits.stride(0)), n_cls)
     label = label.to(torch.int32).contiguous()
-    ids = group.to(torch.int64)
-    ids = torch.where((ids < 0) | (ids >= K), torch.full_like(ids, K), ids)       # the cells that take no part sort last
-    ids, order = torch.sort(ids, stable=True)                                     # cells of a group ascending
-    seg_ptr = torch.searchsorted(ids, torch.arange(K + 1, dtype=torch.int64, device=dev)).contiguous()
-    order = order.to(torch.int32)
-    nb = C.c_int64()
-    _lib.check(_lib.lib().wgnn_group_class_reduce_workspace(B, K, n_cls, C.addressof(nb)), "wgnn_group_class_reduce_workspace")
-    ws = torch.empty(nb.value // 8 + 1, dtype=torch.float64, device=dev)
-    rc = _lib.call(dev, "wgnn_group_class_reduce", _ptr(logits), ld, _ptr(label), _ptr(order), _ptr(seg_ptr), B, K, n_cls,
-                   _ptr(prob_sum), _ptr(conf_sum), _ptr(votes), _ptr(tally), _ptr(ws), ws.numel() * 8,
-                   _lib.CLUSTERS_ACCUMULATE if accumulate else 0, _stream(dev))
-    _lib.check(rc, "wgnn_group_class_reduce")
+    order, seg_ptr = _group_major(group, K)
+    ws, ws_bytes = _workspace(dev, "wgnn_group_class_reduce_workspace", B, K, n_cls)     # K, C >= 1: never empty
+    _lib.run(dev, "wgnn_group_class_reduce", _ptr(logits), _ld(logits, B, n_cls), _ptr(label), _ptr(order), _ptr(seg_ptr), B, K,
+             n_cls, _ptr(prob_sum), _ptr(conf_sum), _ptr(votes), _ptr(tally), _ptr(ws), ws_bytes,
+             _lib.CLUSTERS_ACCUMULATE if accumulate else 0, _stream(dev))
     return prob_sum, conf_sum, votes, tally
 
 
@@ -1984,19 +1962,13 @@ def _align_operand(name: str, expr, gene_map: torch.Tensor, n_genes: int):
         if x.shape[1] != n_cols:
             raise WgnnError(f"the matrix has {x.shape[1]} columns, gene_map {n_cols} entries")
         B = int(x.shape[0])
-        if (n_cols > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < n_cols):
+        if not _row_strided(x, B, n_cols):
             raise WgnnError(f"{name} takes row-major rows (unit column stride, row stride >= n_cols)")
-        ld = int(x.stride(0)) if B > 1 else n_cols           # a single row's stride says nothing
+        ld = _ld(x, B, n_cols)
     else:
-        rowptr, col, val = expr
-        if rowptr.dtype not in (torch.int32, torch.int64) or col.dtype != torch.int32 or val.dtype != torch.float32:
-            raise WgnnError(f"{name} takes rowptr int32 / int64, col int32, val float32")
-        if rowptr.dim() != 1 or rowptr.shape[0] < 1 or col.dim() != 1 or col.shape != val.shape:
-            raise WgnnError(f"malformed CSR: rowptr {tuple(rowptr.shape)}, col {tuple(col.shape)}, val {tuple(val.shape)}")
-        if not (rowptr.is_contiguous() and col.is_contiguous() and val.is_contiguous()):
+        if not all(t.is_contiguous() for t in expr):          # this batch is refused, not copied
             raise WgnnError(f"{name} takes contiguous rowptr, col and val")
-        B = int(rowptr.shape[0]) - 1
-        flags = _lib.FLAG_ROWPTR_I64 if rowptr.dtype == torch.int64 else 0
+        rowptr, col, val, B, _, flags = _csr_operand(name, WgnnError, *expr, "val")
     return dev, x, ld, rowptr, col, val, B, n_cols, G, flags
 
 
@@ -2062,19 +2034,19 @@ def align_rows(expr, gene_map: torch.Tensor, n_genes: int, threshold: float = 0.
             lib = lib.to(dev).to(torch.float64).contiguous()       # widened on the device
         row_total = torch.empty(B, dtype=torch.float64, device=dev)    # alive until the fill pass has been launched
         ln = (_ptr(row_total), float(scale))                       # the count pass stores the totals, the fill pass reads them
-        _lib.check(_lib.call(dev, "wgnn_align_count_ln" + sfx, *head, *merge, _ptr(lib), *ln, _ptr(counts), _ptr(status), flags,
-                             _stream(dev)), "wgnn_align_count_ln" + sfx)
+        _lib.run(dev, "wgnn_align_count_ln" + sfx, *head, *merge, _ptr(lib), *ln, _ptr(counts), _ptr(status), flags,
+                 _stream(dev))
     else:
-        _lib.check(_lib.call(dev, "wgnn_align_count", *head, _ptr(counts), _ptr(status), flags, _stream(dev)), "wgnn_align_count")
+        _lib.run(dev, "wgnn_align_count", *head, _ptr(counts), _ptr(status), flags, _stream(dev))
     out_rowptr, total = _scan(counts)
     out_col = torch.empty(total, dtype=torch.int32, device=dev)
     out_raw = torch.empty(total, dtype=torch.float32, device=dev)
     if lognorm:
-        _lib.check(_lib.call(dev, "wgnn_align_fill_ln" + sfx, *head, *merge, *ln, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw),
-                             _ptr(status), flags, _stream(dev)), "wgnn_align_fill_ln" + sfx)
+        _lib.run(dev, "wgnn_align_fill_ln" + sfx, *head, *merge, *ln, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw),
+                 _ptr(status), flags, _stream(dev))
     else:
-        _lib.check(_lib.call(dev, "wgnn_align_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status), flags,
-                             _stream(dev)), "wgnn_align_fill")
+        _lib.run(dev, "wgnn_align_fill", *head, _ptr(out_rowptr), _ptr(out_col), _ptr(out_raw), _ptr(status), flags,
+                 _stream(dev))
     bits = int(status)
     merge_text = ("or a group table (col_group, group_ptr, group_cols) points outside its range",)
     _check_status("align_rows", bits, _ALIGN_STATUS, merge_text if merge and bits & _lib.ALIGN_BAD_MAP else ())
@@ -2097,9 +2069,9 @@ def coverage_rows(expr, gene_map: torch.Tensor, n_genes: int):
     n_expressed, n_mapped, n_bad = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
     total, total_mapped = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
     col_cells = torch.empty(n_cols, dtype=torch.int32, device=dev)       # cleared by the entry point, on the stream
-    _lib.check(_lib.call(dev, "wgnn_coverage_rows", _ptr(x), ld, _ptr(rowptr), _ptr(col), _ptr(val), B, n_cols, _ptr(gene_map), G,
-                         _ptr(n_expressed), _ptr(n_mapped), _ptr(n_bad), _ptr(total), _ptr(total_mapped), _ptr(col_cells),
-                         _ptr(status), flags, _stream(dev)), "wgnn_coverage_rows")
+    _lib.run(dev, "wgnn_coverage_rows", _ptr(x), ld, _ptr(rowptr), _ptr(col), _ptr(val), B, n_cols, _ptr(gene_map), G,
+             _ptr(n_expressed), _ptr(n_mapped), _ptr(n_bad), _ptr(total), _ptr(total_mapped), _ptr(col_cells),
+             _ptr(status), flags, _stream(dev))
     _check_status("coverage_rows", int(status), _ALIGN_STATUS)
     return n_expressed, n_mapped, n_bad, total, total_mapped, col_cells
 
@@ -2136,7 +2108,6 @@ def knn_rows(x: torch.Tensor, k: int, queries: Optional[torch.Tensor] = None, ex
     are scanned side by side and merged; a large ``n_q`` is chunked over query ranges (halved until the partial lists of
     a chunk fit ``KNN_WORKSPACE_BYTES``).  Neither changes a bit, and two calls are bit-identical.  ``D`` (after padding to a multiple of
     4) must be in [4, 1024].  Argument errors are ``ValueError``."""
-    import ctypes as C
     name = "knn_rows"
     dev = _require_cuda(x, queries, *(out or ()))
     k, n_splits = int(k), int(n_splits)
@@ -2162,33 +2133,25 @@ def knn_rows(x: torch.Tensor, k: int, queries: Optional[torch.Tensor] = None, ex
     if out is None:
         out = (torch.empty((n_q, k), dtype=torch.int32, device=dev), torch.empty((n_q, k), dtype=torch.float32, device=dev))
     idx, d2 = out
-    for t, dt, what in ((idx, torch.int32, "idx"), (d2, torch.float32, "d2")):
-        if t.dtype != dt or t.dim() != 2 or tuple(t.shape) != (n_q, k) or (k > 1 and t.stride(1) != 1) or (n_q > 1 and t.stride(0) < k):
-            raise ValueError(f"{name}: out's {what} must be {dt} [{n_q}, {k}] with unit column stride and a row stride >= {k}")
-    ld_out = max(int(idx.stride(0)), k) if n_q > 1 else k
-    if n_q > 1 and int(d2.stride(0)) != ld_out:
+    _view_2d(name, ValueError, "out's idx", idx, torch.int32, n_q, k)
+    _view_2d(name, ValueError, "out's d2", d2, torch.float32, n_q, k)
+    ld_out = _ld(idx, n_q, k)
+    if _ld(d2, n_q, k) != ld_out:
         raise ValueError(f"{name}: out's idx and d2 must share one row stride")
     if n_q == 0:
         return idx, d2
-    nb = C.c_int64()
-    ask = lambda n: _lib.check(_lib.lib().wgnn_knn_workspace_bytes(n, n_c, k, n_splits, C.addressof(nb)), "wgnn_knn_workspace_bytes")
+    sizes = lambda n: ("wgnn_knn_workspace_bytes", n, n_c, k, n_splits)
     # chunks of consecutive queries, halved until the partial lists of one chunk ([splits, queries, k] 64-bit keys) fit the budget
     step = n_q
-    ask(step)
-    while nb.value > KNN_WORKSPACE_BYTES and step > 1:
+    while _workspace_bytes(*sizes(step)) > KNN_WORKSPACE_BYTES and step > 1:
         step = -(-step // 2)
-        ask(step)
-    ws = None
+    have = (None, 0)                                          # one allocation serves every chunk that it is large enough for
     for r0 in range(0, n_q, step):
         r1 = min(n_q, r0 + step)
-        ask(r1 - r0)
-        if nb.value and (ws is None or ws.numel() * 8 < nb.value):
-            ws = torch.empty((nb.value + 7) // 8, dtype=torch.int64, device=dev)
-        rc = _lib.call(dev, "wgnn_knn_rows", q.data_ptr() + r0 * q.stride(0) * 4, q.stride(0), r1 - r0, _ptr(x), x.stride(0), n_c,
-                       D, k, first + r0 if first >= 0 else -1, n_splits,
-                       idx.data_ptr() + r0 * ld_out * 4, d2.data_ptr() + r0 * ld_out * 4, ld_out,
-                       _ptr(ws) if nb.value else None, nb.value, 0, _stream(dev))
-        _lib.check(rc, "wgnn_knn_rows")
+        ws, ws_bytes = have = _workspace(dev, *sizes(r1 - r0), have=have)
+        _lib.run(dev, "wgnn_knn_rows", q.data_ptr() + r0 * q.stride(0) * 4, q.stride(0), r1 - r0, _ptr(x), x.stride(0), n_c,
+                 D, k, first + r0 if first >= 0 else -1, n_splits,
+                 idx.data_ptr() + r0 * ld_out * 4, d2.data_ptr() + r0 * ld_out * 4, ld_out, _ptr(ws), ws_bytes, 0, _stream(dev))
     return idx, d2
 
 
@@ -2207,7 +2170,6 @@ def kmeans_seed(x: torch.Tensor, n_clusters: int, seed: int = 0):
     distance to the nearest of them (NaN for an invalid row).  Two calls are bit-identical.  ``n_clusters`` in [1, 4096] and
     at most the number of valid rows (one read-back, before the launches), ``D`` (after zero-padding to a multiple of 4) in
     [4, 1024]; argument errors are ``ValueError``."""
-    import ctypes as C
     name = "kmeans_seed"
     dev = _require_cuda(x)
     K = int(n_clusters)
@@ -2224,12 +2186,9 @@ def kmeans_seed(x: torch.Tensor, n_clusters: int, seed: int = 0):
         raise ValueError(f"{name}: n_clusters = {K}, but only {n_valid} of the {B} rows are finite")
     seed_row = torch.empty(K, dtype=torch.int32, device=dev)
     min_d2 = torch.empty(B, dtype=torch.float32, device=dev)
-    nb = C.c_int64()
-    _lib.check(_lib.lib().wgnn_kmeans_seed_workspace_bytes(B, K, C.addressof(nb)), "wgnn_kmeans_seed_workspace_bytes")
-    ws = torch.empty(nb.value // 8 + 1, dtype=torch.float64, device=dev)
-    rc = _lib.call(dev, "wgnn_kmeans_seed", _ptr(x), x.stride(0) if B > 1 else D, B, D, K, int(seed) & (2 ** 64 - 1),
-                   _ptr(seed_row), _ptr(min_d2), _ptr(ws), ws.numel() * 8, 0, _stream(dev))
-    _lib.check(rc, "wgnn_kmeans_seed")
+    ws, ws_bytes = _workspace(dev, "wgnn_kmeans_seed_workspace_bytes", B, K)             # B >= K >= 1 here: never empty
+    _lib.run(dev, "wgnn_kmeans_seed", _ptr(x), _ld(x, B, D), B, D, K, int(seed) & (2 ** 64 - 1),
+             _ptr(seed_row), _ptr(min_d2), _ptr(ws), ws_bytes, 0, _stream(dev))
     return seed_row, min_d2
 
 
@@ -2243,7 +2202,6 @@ def group_rows_reduce(x: torch.Tensor, group: torch.Tensor, n_groups: int, out: 
     Returns ``(sum f64 [K, D], count int64 [K], mean f32 [K, D])`` - ``out`` when given (``mean`` may have a wider row stride).
     ``mean = float32(sum / count)``; the ``mean`` row of an EMPTY group is not written: with ``out`` it keeps what it held, bit
     for bit, without ``out`` it is zero."""
-    import ctypes as C
     dev = _require_cuda(x, group, *(out or ()))
     K = int(n_groups)
     if K <= 0:
@@ -2253,8 +2211,8 @@ def group_rows_reduce(x: torch.Tensor, group: torch.Tensor, n_groups: int, out: 
     B, D = int(x.shape[0]), int(x.shape[1])
     if B >= 2 ** 31:
         raise ValueError("group_rows_reduce: B >= 2^31")
-    if tuple(group.shape) != (B,) or group.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"group must hold one int32 / int64 id per row ([{B}]), got {group.dtype} {tuple(group.shape)}")
+    _group_operand("group_rows_reduce", ValueError, group, B, K, False,          # any id outside [0, K) is a row that takes no part
+                   says=f"group must hold one int32 / int64 id per row ([{B}])")
     if out is None:
         out = (torch.empty((K, D), dtype=torch.float64, device=dev), torch.empty(K, dtype=torch.int64, device=dev),
                torch.zeros((K, D), dtype=torch.float32, device=dev))
@@ -2264,22 +2222,13 @@ def group_rows_reduce(x: torch.Tensor, group: torch.Tensor, n_groups: int, out: 
     if tuple(total.shape) != (K, D) or total.dtype != torch.float64 or not total.is_contiguous() or \
             tuple(count.shape) != (K,) or count.dtype != torch.int64 or not count.is_contiguous():
         raise ValueError(f"out must hold contiguous sum float64 [{K}, {D}] and count int64 [{K}]")
-    if tuple(mean.shape) != (K, D) or mean.dtype != torch.float32 or (D > 1 and mean.stride(1) != 1) or (K > 1 and mean.stride(0) < D):
-        raise ValueError(f"out's mean must be float32 [{K}, {D}] with unit column stride and a row stride >= {D}")
-    if (D > 1 and x.stride(1) != 1) or (B > 1 and x.stride(0) < D):
+    _view_2d("group_rows_reduce", ValueError, "out's mean", mean, torch.float32, K, D)
+    if not _row_strided(x, B, D):
         x = x.contiguous()
-    ld = int(x.stride(0)) if B > 1 else D
-    ids = group.to(torch.int64)
-    ids = torch.where((ids < 0) | (ids >= K), torch.full_like(ids, K), ids)       # the rows that take no part sort last
-    ids, order = torch.sort(ids, stable=True)                                     # rows of a group ascending
-    seg_ptr = torch.searchsorted(ids, torch.arange(K + 1, dtype=torch.int64, device=dev)).contiguous()
-    order = order.to(torch.int32)
-    nb = C.c_int64()
-    _lib.check(_lib.lib().wgnn_group_rows_reduce_workspace(B, K, D, C.addressof(nb)), "wgnn_group_rows_reduce_workspace")
-    ws = torch.empty(nb.value // 8 + 1, dtype=torch.float64, device=dev)
-    rc = _lib.call(dev, "wgnn_group_rows_reduce", _ptr(x), ld, _ptr(order), _ptr(seg_ptr), B, K, D, _ptr(total), D, _ptr(count),
-                   _ptr(mean), int(mean.stride(0)) if K > 1 else D, _ptr(ws), ws.numel() * 8, 0, _stream(dev))
-    _lib.check(rc, "wgnn_group_rows_reduce")
+    order, seg_ptr = _group_major(group, K)
+    ws, ws_bytes = _workspace(dev, "wgnn_group_rows_reduce_workspace", B, K, D)          # K, D >= 1: never empty
+    _lib.run(dev, "wgnn_group_rows_reduce", _ptr(x), _ld(x, B, D), _ptr(order), _ptr(seg_ptr), B, K, D, _ptr(total), D, _ptr(count),
+             _ptr(mean), _ld(mean, K, D), _ptr(ws), ws_bytes, 0, _stream(dev))
     return total, count, mean
 
 

@@ -105,9 +105,9 @@ def sample_block_static(csr: AggCsr, rows: Optional[torch.Tensor], k: int, sampl
     cnt = torch.zeros(n, dtype=torch.int32, device=dev)
     self_drawn = torch.zeros(n, dtype=torch.float32, device=dev)
     inv = torch.ones(n, dtype=torch.float32, device=dev)
-    _lib.check(_lib.call(dev, "wgnn_sample_rows", _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.val), _ptr(ids32), n, kk,
-                         sampler.seed, _ptr(sampler.step), int(stream_id), _ptr(out_col), _ptr(out_val), _ptr(cnt),
-                         _ptr(self_drawn), _ptr(inv), _stream(dev)), "wgnn_sample_rows")
+    _lib.run(dev, "wgnn_sample_rows", _ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.val), _ptr(ids32), n, kk,
+             sampler.seed, _ptr(sampler.step), int(stream_id), _ptr(out_col), _ptr(out_val), _ptr(cnt),
+             _ptr(self_drawn), _ptr(inv), _stream(dev))
     return ell_block_from_draw(csr, rows_l, kk, out_col, out_val, cnt, self_drawn, inv)
 
 
