@@ -1334,6 +1334,49 @@ int wgnn_group_rows_reduce(const float* X, int64_t ld_x, const int32_t* order, c
                            float* mean, int64_t ld_mean, void* workspace, int64_t workspace_bytes,
                            uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Exact silhouette of dense rows under Euclidean distance (additive exports, WGNN_VERSION stays 206): the kernel behind
+ * ops.silhouette_rows / api.ResidentPredictor.silhouette (Rousseeuw 1987).  Brute force over every ordered pair of rows,
+ * O(n^2 D); the [n, n] distance matrix is never stored, and symmetry is not exploited.
+ *     X [n, ld_x] f32        : the rows GROUP-MAJOR, D valid columns: group k holds the rows seg_ptr[k] .. seg_ptr[k+1] - 1
+ *     seg_ptr int64 [K + 1]  : the groups' bounds; rows at positions >= seg_ptr[K] take no part - neither as queries nor as
+ *                              candidates.  seg_ptr is clamped into [0, n]: a malformed operand never faults.
+ *     n_splits               : the groups are dealt to this many workgroup columns (0 = chosen from n and K so that a small
+ *                              batch still fills the chip); it changes no bit
+ *     a, b, s f64 [n], nearest int32 [n] : per row, at its group-major position; every element is written
+ * Definition, for a participating row i of group g (n_c = the members of group c):
+ *     d2(i, j)  wgnn_knn_rows' chain:  d2 = 0;  for c = 0 .. D-1 ascending:  t = x_i[c] - x_j[c];  d2 = fmaf(t, t, d2)   (f32)
+ *     d(i, j) = sqrtf(d2(i, j)), correctly rounded (f32);  d(i, i) = +0.0 exactly, so the row itself needs no exclusion
+ *     S(i, c) = the fp64 sum of d(i, j) over the members j of group c, in the order below
+ *     a(i)    = S(i, g) / (n_g - 1);  0.0 when n_g == 1
+ *     b(i)    = the minimum over the non-empty groups c != g of S(i, c) / n_c  (one fp64 divide each)
+ *     nearest(i) = the group that attains b(i) under the total order (mean, group id): of equal means the lower id
+ *     s(i)    = (b - a) / max(a, b);  0.0 when n_g == 1 or max(a, b) == 0 (scikit-learn's conventions)
+ *     with no other non-empty group: b = +inf, nearest = -1, s = NaN (also for a singleton)
+ *   A row that takes no part gets a = b = s = NaN and nearest = -1.
+ * Addition order of S(i, c), part of the contract and a constant of the kernel - it depends on neither the grid nor n_splits:
+ *   the member at position p of its group (p = 0 for the row at seg_ptr[c]) goes to partial (p % 64) / 4; each of the 16 partials
+ *   is summed sequentially in ascending p from 0.0; the 16 partials are then added as a balanced tree, partial u with partial
+ *   u ^ 1, the results with those at u ^ 2, then u ^ 4, then u ^ 8.  (A group's members are cut into candidate tiles of 64 from
+ *   the group's own start, a lane owns four consecutive candidates and carries one partial per query across the tiles; the 16
+ *   lanes of a query meet in an xor butterfly.  A position past the group's end adds a selected +0.0.)
+ * A workgroup of 256 threads holds 64 queries and streams the candidate tiles x 16 columns through 17 KiB of LDS; a lane owns
+ * 4 x 4 pairs.  No atomics: two launches are bit-identical.  Distances that overflow f32 are outside the contract (never a
+ * fault), and so are rows with a non-finite value (the caller leaves them out of the groups).
+ *   workspace: wgnn_silhouette_workspace_bytes(n, K, n_splits) bytes, 8-byte aligned, caller-owned: the splits' group ranges
+ *   and per split and row (S_own, best mean, its group), 20 bytes, which a second kernel merges under the same order; 0 bytes
+ *   (workspace may be NULL) when the groups are not split.  Whole groups are dealt, in contiguous ranges balanced by their
+ *   number of candidate tiles: one dominant group bounds the balance.
+ * Errors, before any launch: WGNN_ERR_BAD_ARG (n outside [0, 2^31); n_splits outside [0, 64]; any flag bit - none is defined;
+ * a missing operand), WGNN_ERR_UNSUPPORTED (K outside [1, 4096]; D outside [4, 1024]), WGNN_ERR_ALIGNMENT (D or ld_x not a
+ * multiple of 4 or ld_x < D; X not 16-byte, seg_ptr, a, b, s or workspace not 8-byte, nearest not 4-byte aligned),
+ * WGNN_ERR_WORKSPACE; wgnn_last_error_string names the check.  n == 0 returns WGNN_OK without a launch.
+ * ------------------------------------------------------------------------- */
+int wgnn_silhouette_workspace_bytes(int64_t n, int32_t K, int32_t n_splits, int64_t* bytes);
+int wgnn_silhouette_rows(const float* X, int64_t ld_x, int64_t n, int32_t D, const void* seg_ptr, int32_t K,
+                         int32_t n_splits, double* a, double* b, double* s, int32_t* nearest,
+                         void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

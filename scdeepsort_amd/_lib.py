@@ -31,6 +31,7 @@ HOOD_BAD_INDEX, HOOD_BAD_ROWPTR, HOOD_BAD_COL, HOOD_BAD_SIZE = 1, 2, 4, 8     # 
 HOOD_MAX_MEMBERS, HOOD_MAX_SLAB_GENES = 256, 16384     # wgnn_hood_rows_*'s largest unit and widest LDS slab (include/wgnn.h)
 KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS = 64, 1024, 64    # wgnn_knn_rows' limits (include/wgnn.h)
 KMEANS_MAX_K = 4096                # wgnn_kmeans_seed's limit (include/wgnn.h); its D limits are wgnn_knn_rows'
+SILHOUETTE_MAX_GROUPS, SILHOUETTE_MAX_SPLITS = 4096, 64      # wgnn_silhouette_rows' limits (include/wgnn.h); D as wgnn_knn_rows
 ABI_MAJOR = 2                  # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
@@ -135,6 +136,8 @@ SIGNATURES = {
     "wgnn_kmeans_seed": (C.c_int, [_vp, _i64, _i64, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _i64, _u32, _vp]),
     "wgnn_group_rows_reduce_workspace": (C.c_int, [_i64, _i32, _i32, _vp]),
     "wgnn_group_rows_reduce": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _u32, _vp]),
+    "wgnn_silhouette_workspace_bytes": (C.c_int, [_i64, _i32, _i32, _vp]),
+    "wgnn_silhouette_rows": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _u32, _vp]),
 }
 
 

@@ -33,7 +33,7 @@ from .ops import cross_entropy_sum
 # the result tables and the host helpers they share with the predictor: every name of tables.py is reachable through this module
 from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Coverage, CoverageSummary, Doublets, DoubletsSummary,
                      GeneRanks, GeneRanksSummary, KMeans, KMeansSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
-                     Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Smoothed, SmoothedSummary, Stability,
+                     Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Silhouette, SilhouetteSummary, Smoothed, SmoothedSummary, Stability,
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
                      _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores)
 
@@ -2075,6 +2075,80 @@ class ResidentPredictor:
         if (km.cluster < 0).any():
             raise WgnnError(f"kmeans_file: {int((km.cluster < 0).sum())} cells have no finite embedding and no cluster")
         return self._save_frame(km.clusters_frame(), save_path, "kmeans")
+
+    # ---------------------------------------------------------------------------------------------
+    def silhouette(self, expr, groups="predicted", genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                   group_names: Optional[Sequence[str]] = None, n_groups: Optional[int] = None, index=None) -> Silhouette:
+        """How well are groups of cells separated in the model's space?  The exact silhouette (Rousseeuw 1987) of every cell,
+        on the device: the batch is classified once (``classify``'s call, bit for bit), embedded (``embed``, ``space`` as there)
+        and scored by ``wgnn_silhouette_rows`` - brute force over every ordered pair of cells, the ``[B, B]`` distance matrix
+        never stored, a cell's distances summed per group in fp64 in a fixed order.  Per cell ``a`` is the mean distance to the
+        other cells of its own group, ``b`` the lowest mean distance to another group (``nearest``) and ``score = (b - a) /
+        max(a, b)``: near 1 the cell sits inside its group, below 0 it sits closer to ``nearest``.
+        ``groups="predicted"``: the called types, unsure cells skipped; else one integer id per cell (-1 = skip) with
+        ``group_names`` or ``n_groups``, as for ``rank_genes`` - ``kmeans``' result feeds it as it comes:
+        ``silhouette(expr, groups=km.cluster, n_groups=K, space=km.space, metric=km.metric)``.  ``metric="cosine"``: the rows are
+        L2-normalised first, as ``knn`` and ``kmeans`` do, and the distances are then EUCLIDEAN distances of unit rows,
+        ``sqrt(2 (1 - cos))`` - not ``1 - cos``.  A cell whose embedding holds a non-finite value takes no part.  At most 4096
+        groups; fewer than two non-empty groups raise ``ValueError``.  ``index``: the cells' names.
+
+        Returns a ``Silhouette``: ``mean`` / ``by_group`` / ``misplaced`` / ``frame`` / ``summary`` on top.  Two calls give the
+        same bits.  To choose ``n_clusters``, loop ``kmeans`` and this over K and keep the highest ``mean()`` - inertia falls
+        with every K and cannot choose.
+
+        In ``space="hidden"`` with ``groups="predicted"`` this is the classifier judging itself: the hidden rows are what the
+        head separates, so the called types score high there by construction.  ``space="features"`` is the independent view -
+        no trained weight takes part.
+
+        What this is not: no sampling - the cost is exact ``O(B^2 D)``; no simplified (centroid) silhouette; one batch only;
+        no automatic K sweep.  Fused kernels only, as ``embed``."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
+        self._require_fused("silhouette")
+        _check_index(index, self._n_cells(expr))
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._silhouette(self._over_genes(expr, genes, normalize), groups, group_names, n_groups, space, metric, index)
+
+    def _silhouette(self, expr, groups, group_names, n_groups, space, metric, index):
+        predicted, names = self._group_names(groups, group_names, n_groups)
+        K = len(names)
+        if K > _ops.SILHOUETTE_MAX_GROUPS:
+            raise ValueError(f"{K} groups: silhouette takes at most {_ops.SILHOUETTE_MAX_GROUPS}")
+        device_csr = self._device_csr(expr)
+        B = int(device_csr[0].shape[0]) - 1
+        if not predicted:
+            ids = self._group_ids(groups, B, K)
+        vb = self._values_batch(device_csr)
+        group = np.asarray(vb.pred if predicted else ids, np.int64)
+        if len(set(group[group >= 0].tolist())) < 2:       # the host holds the ids: no read-back
+            raise ValueError("silhouette needs at least two non-empty groups")
+        rows = self._embed(vb.csr, space)[:, :self.hidden if space == "hidden" else None]       # embed's rows
+        if metric == "cosine":
+            rows = F.normalize(rows, dim=1)
+        out = _ops.silhouette_rows(rows, torch.from_numpy(group).to(self.device), K)
+        group = np.where(torch.isfinite(rows).all(dim=1).cpu().numpy(), group, -1)      # a row with a non-finite value took no part
+        return Silhouette(a=out.a.cpu().numpy(), b=out.b.cpu().numpy(), score=out.score.cpu().numpy(),
+                          nearest=out.nearest.cpu().numpy().astype(np.int64), group=group,
+                          group_names=names, size=out.size.cpu().numpy(), n_skipped=int((group < 0).sum()), space=space,
+                          metric=metric, label=vb.pred, max_prob=vb.max_prob, **self._table_fields(B, index))
+
+    def silhouette_file(self, data, clusters_file=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                        save_path=None) -> pd.DataFrame:
+        """``silhouette`` on a test file - its full table, its gene names as ``genes=`` and its cell names.  ``clusters_file``:
+        a clusters file laid out as ``annotate_file`` reads it (an index column, the cell's name, its cluster's name; the
+        cells in the data file's order, else ``ValueError``; the names compared as stripped ``str``, in sorted order) -
+        ``kmeans_file``'s output is one; ``None``: the predicted types.  Returns ``Silhouette.frame()``, written as
+        ``{species}_{tissue}_silhouette.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        kw = dict(genes=genes, normalize=normalize, space=space, metric=metric, index=index)
+        if clusters_file is None:
+            out = self.silhouette(matrix, **kw)
+        else:
+            ids, names = _cluster_ids(self._read_clusters_file(clusters_file, data, index), n_cells=len(index))
+            out = self.silhouette(matrix, groups=ids, group_names=names, **kw)
+        return self._save_frame(out.frame(), save_path, "silhouette")
 
     # ---------------------------------------------------------------------------------------------
     def pseudobulk(self, expr, genes, clusters, normalize=None, cluster_names: Optional[Sequence[str]] = None,

@@ -2319,3 +2319,61 @@ def kmeans_rows(x: torch.Tensor, n_clusters: int, init="k-means++", max_iter: in
         label, d2 = assign()
     size = torch.bincount(label[label >= 0].long(), minlength=K)
     return KMeansRows(label, d2, centers[:, :D], size, seed_row, n_iter, converged, trace)
+
+
+SILHOUETTE_MAX_GROUPS, SILHOUETTE_MAX_SPLITS = _lib.SILHOUETTE_MAX_GROUPS, _lib.SILHOUETTE_MAX_SPLITS     # wgnn_silhouette_rows' limits
+
+
+class SilhouetteRows(NamedTuple):
+    """What ``silhouette_rows`` returns, on the device and in the caller's row order: ``a`` f64 [B] (the mean distance to the other
+    members of the row's own group; 0 for a singleton), ``b`` f64 [B] (the lowest mean distance to another non-empty group; +inf
+    when there is none), ``score`` f64 [B] (``(b - a) / max(a, b)``), ``nearest`` int32 [B] (the group that attains ``b``; -1 when
+    there is none) and ``size`` int64 [K] (the participating rows per group).  A row that takes no part holds NaN / NaN / NaN /
+    -1."""
+    a: torch.Tensor
+    b: torch.Tensor
+    score: torch.Tensor
+    nearest: torch.Tensor
+    size: torch.Tensor
+
+
+def silhouette_rows(x: torch.Tensor, group: torch.Tensor, n_groups: int, n_splits: int = 0) -> SilhouetteRows:
+    """``wgnn_silhouette_rows``: the exact silhouette (Rousseeuw 1987) of every row of ``x`` [B, D] float32 under Euclidean
+    distance, the groups given - brute force over every ordered pair on the device, O(B^2 D), the [B, B] distance matrix is never
+    stored (``include/wgnn.h`` has the numerics contract: ``wgnn_knn_rows``' f32 chain for the squared distance, a correctly rounded
+    ``sqrtf``, fp64 sums per (row, group) in a fixed order, fp64 divides).  ``group`` int32 / int64 [B]: a row's group in
+    ``[0, n_groups)``; any other id = the row takes no part, and neither does a row that holds a non-finite value (it is no
+    member of its group: ``size`` does not count it).
+
+    The rows are gathered group-major once (``B * D * 4`` bytes, a stable sort of the ids and a search for the groups' bounds: no
+    read-back), the kernel streams them, and its four outputs are scattered back to the caller's row order.  Conventions: a
+    singleton scores 0 (its ``a`` is 0), ``max(a, b) == 0`` scores 0, an empty group is ignored, and with fewer than two non-empty
+    groups ``b = +inf``, ``nearest = -1`` and ``score = NaN``.  ``n_splits`` (0 = chosen from the sizes, else 1..64): how many
+    workgroup columns share the groups - it changes no bit, and two calls are bit-identical.  A width that is no multiple of 4 is
+    zero-padded as ``knn_rows`` does; ``D`` must then be in [4, 1024], ``n_groups`` in [1, 4096].  CPU tensors raise ``WgnnError``;
+    argument errors are ``ValueError``.  Returns a ``SilhouetteRows``."""
+    name = "silhouette_rows"
+    dev = _require_cuda(x, group)
+    K, n_splits = int(n_groups), int(n_splits)
+    if not 1 <= K <= SILHOUETTE_MAX_GROUPS:
+        raise ValueError(f"{name}: n_groups = {K} is outside [1, {SILHOUETTE_MAX_GROUPS}]")
+    if not 0 <= n_splits <= SILHOUETTE_MAX_SPLITS:
+        raise ValueError(f"{name}: n_splits = {n_splits} is outside [0, {SILHOUETTE_MAX_SPLITS}] (0 = chosen from the sizes)")
+    x = _knn_rows_operand(name, "x", x)
+    B, D = int(x.shape[0]), int(x.shape[1])
+    if not 4 <= D <= KNN_MAX_D:
+        raise ValueError(f"{name}: D = {D} is outside [4, {KNN_MAX_D}]")
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    _group_operand(name, ValueError, group, B, K, False)                # any id outside [0, K) is a row that takes no part
+    group = torch.where(torch.isfinite(x).all(dim=1), group, torch.full_like(group, -1))
+    order, seg_ptr = _group_major(group, K)
+    rows = x[order.long()]                                              # group-major and contiguous: the kernel streams it
+    a, b, s = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(3))
+    nearest = torch.empty(B, dtype=torch.int32, device=dev)
+    ws, ws_bytes = _workspace(dev, "wgnn_silhouette_workspace_bytes", B, K, n_splits)
+    _lib.run(dev, "wgnn_silhouette_rows", _ptr(rows), D, B, D, _ptr(seg_ptr), K, n_splits, _ptr(a), _ptr(b), _ptr(s), _ptr(nearest),
+             _ptr(ws), ws_bytes, 0, _stream(dev))
+    back = torch.empty_like(order, dtype=torch.int64)
+    back[order.long()] = torch.arange(B, dtype=torch.int64, device=dev)
+    return SilhouetteRows(a[back], b[back], s[back], nearest[back], seg_ptr[1:] - seg_ptr[:-1])

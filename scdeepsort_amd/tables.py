@@ -1873,3 +1873,110 @@ class KMeans(_NamesCalls):
                              median_size=float(np.median(filled)) if filled.size else float("nan"), inertia=float(self.inertia),
                              median_purity=float(np.median(known)) if known.size else float("nan"),
                              n_mixed=int((known < 0.9).sum()), n_unsure=int((np.asarray(self.label) < 0).sum()))
+
+
+class SilhouetteSummary(dict):
+    """``Silhouette.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_cells']} cells in {d['n_groups']} non-empty groups of the {d['space']} space ({d['metric']}); "
+            f"{d['n_skipped']} cells take no part, {d['n_singletons']} groups are singletons",
+            f"mean silhouette {d['mean']:.4f} (median {d['median']:.4f}); {d['n_misplaced']} cells ({d['misplaced_share']:.3f}) "
+            f"sit closer to another group than to their own",
+            f"worst group {d['worst_group']} (mean {d['worst_mean']:.4f}), best group {d['best_group']} (mean {d['best_mean']:.4f}) "
+            f"({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class Silhouette(_NamesCalls):
+    """What ``ResidentPredictor.silhouette`` returns: the exact silhouette (Rousseeuw 1987) of every cell of one batch against
+    given groups, in the model's space.  B cells (``index``), K groups (``group_names``), C cell types (``id2label``).
+    ``group`` int64 [B]: the cell's group as the call resolved it (-1 = the cell takes no part: skipped by the caller, unsure
+    under ``groups="predicted"``, or an embedding with a non-finite value).  ``a`` f64 [B]: the mean distance to the other cells
+    of the cell's own group (0 for a singleton); ``b`` f64 [B]: the lowest mean distance to the cells of another group;
+    ``nearest`` int64 [B]: that group; ``score`` f64 [B]: ``(b - a) / max(a, b)`` in [-1, 1] - 0 for a singleton and where
+    ``max(a, b) == 0``, below 0 where the cell sits closer to ``nearest`` than to its own group.  NaN / NaN / -1 / NaN for a
+    cell that takes no part.  ``size`` int64 [K]: the participating cells per group; ``n_skipped``: the cells that take no part.
+    ``space`` / ``metric`` say what was measured (under ``"cosine"`` the Euclidean distances of the L2-normalised rows);
+    ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    a: np.ndarray
+    b: np.ndarray
+    score: np.ndarray
+    nearest: np.ndarray
+    group: np.ndarray
+    group_names: Sequence[str]
+    size: np.ndarray
+    n_skipped: int
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def _on(self) -> np.ndarray:
+        return np.asarray(self.group, np.int64) >= 0
+
+    def mean(self) -> float:
+        """The mean ``score`` over the participating cells - the figure to compare across ``n_clusters``; NaN without one."""
+        s = np.asarray(self.score, np.float64)[self._on()]
+        return float(s.mean()) if s.size else float("nan")
+
+    def by_group(self) -> pd.DataFrame:
+        """One row per group (``group_names``' order, empty groups included): ``group``, ``n_cells``, ``mean`` and ``median``
+        score, ``negative`` (the share of its cells with ``score < 0``) and ``nearest`` (the group most of THOSE cells are
+        nearest to - of equal counts the lower id; ``None`` without such a cell)."""
+        K = len(self.group_names)
+        g, s, near = np.asarray(self.group, np.int64), np.asarray(self.score, np.float64), np.asarray(self.nearest, np.int64)
+        rows = []
+        for k in range(K):
+            m = g == k
+            n = int(m.sum())
+            neg = m & (s < 0) & (near >= 0)
+            to = np.bincount(near[neg], minlength=K) if neg.any() else None
+            rows.append((self.group_names[k], n, float(s[m].mean()) if n else float("nan"),
+                         float(np.median(s[m])) if n else float("nan"), float((s[m] < 0).mean()) if n else float("nan"),
+                         None if to is None else self.group_names[int(np.argmax(to))]))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(6)]
+        return pd.DataFrame({"group": list(cols[0]), "n_cells": np.asarray(cols[1], np.int64), "mean": np.asarray(cols[2], np.float64),
+                             "median": np.asarray(cols[3], np.float64), "negative": np.asarray(cols[4], np.float64),
+                             "nearest": list(cols[5])})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` / ``prob`` (named as ``predict`` names them), ``group`` and ``nearest``
+        (the groups' names, ``None`` without one), ``a``, ``b`` and ``score``."""
+        names = list(self.group_names)
+        pick = lambda ids: [names[k] if k >= 0 else None for k in np.asarray(ids, np.int64)]
+        return pd.DataFrame({"index": list(self.index), "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob),
+                             "group": pick(self.group), "nearest": pick(self.nearest), "a": np.asarray(self.a, np.float64),
+                             "b": np.asarray(self.b, np.float64), "score": np.asarray(self.score, np.float64)})
+
+    def misplaced(self, max_score: float = 0.0) -> pd.DataFrame:
+        """The rows of ``frame()`` to look at: the participating cells with ``score < max_score``, lowest score first (equal
+        scores in batch order)."""
+        s = np.asarray(self.score, np.float64)
+        rows = np.nonzero(self._on() & (s < float(max_score)))[0]
+        rows = rows[np.argsort(s[rows], kind="stable")]
+        return self.frame().iloc[rows].reset_index(drop=True)
+
+    def summary(self) -> SilhouetteSummary:
+        """Cells, groups, the mean and median score, the cells with a negative score and the worst and best group; ``print`` it."""
+        on, s, size = self._on(), np.asarray(self.score, np.float64), np.asarray(self.size, np.int64)
+        part = s[on]
+        per = self.by_group()
+        known = per[~np.isnan(per["mean"].to_numpy())]
+        worst = known.iloc[int(np.argmin(known["mean"].to_numpy()))] if len(known) else None
+        best = known.iloc[int(np.argmax(known["mean"].to_numpy()))] if len(known) else None
+        return SilhouetteSummary(n_cells=int(on.sum()), n_groups=int((size > 0).sum()), space=self.space, metric=self.metric,
+                                 n_skipped=int(self.n_skipped), n_singletons=int((size == 1).sum()), mean=self.mean(),
+                                 median=float(np.median(part)) if part.size else float("nan"),
+                                 n_misplaced=int((part < 0).sum()),
+                                 misplaced_share=float((part < 0).mean()) if part.size else float("nan"),
+                                 worst_group=None if worst is None else worst["group"],
+                                 worst_mean=float("nan") if worst is None else float(worst["mean"]),
+                                 best_group=None if best is None else best["group"],
+                                 best_mean=float("nan") if best is None else float(best["mean"]),
+                                 n_unsure=int((np.asarray(self.label) < 0).sum()))
