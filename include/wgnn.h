@@ -1377,6 +1377,64 @@ int wgnn_silhouette_rows(const float* X, int64_t ld_x, int64_t n, int32_t D, con
                          int32_t n_splits, double* a, double* b, double* s, int32_t* nearest,
                          void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Graph clusters in integers (additive exports, WGNN_VERSION stays 206): the kernels behind ops.snn_graph / ops.louvain_graph /
+ * api.ResidentPredictor.louvain.  No floating point anywhere: every value is an int32 / int64 and every decision a comparison
+ * of 64-bit integers, so neither the order of the integer atomics below nor the grid changes a bit.
+ *
+ * wgnn_snn_weights - the shared-neighbour weights of a kNN union graph.
+ *     idx [n, ld_idx] int32 (int64 with WGNN_SNN_IDX_I64), k <= 64 valid columns: row i's neighbour list, -1 = none; an entry
+ *         outside [0, n), the row itself and a repeated entry count as none
+ *     rowptr int64 [n + 1], col int32 [nnz] : the symmetric CSR of the union graph ({i, j} is an edge iff one lists the other)
+ *     w int32 [nnz] : w(i, j) = |N+(i) & N+(j)| with N+(i) = {i} + list(i) - at least 1 on a union edge, at most k + 1
+ *   A wavefront takes a row, a lane an entry of its list; for every stored neighbour j the lanes load j's list and count.
+ *
+ * One sweep of a synchronous Louvain on a symmetric CSR with int32 weights (a diagonal entry = the internal weight of the
+ * community a coarse vertex came from; it counts in deg and is skipped for kin).  resolution = num / den, M = the sum of all
+ * stored weights, m_den = M * den; the caller guarantees M * M * max(num, den) < 2^62, below which no product here overflows.
+ *   wgnn_louvain_sweep: every vertex v reads comm / tot / size as they were before the sweep.  kin[C] = the sum of w(v, u)
+ *     over the neighbours u != v with comm[u] = C;
+ *         score(C) = kin[C] * m_den - num * deg[v] * (tot[C] - (C == own ? deg[v] : 0))
+ *     C != own is admissible iff (sweep even: C < own; odd: C > own), not (size[own] == 1 and size[C] == 1 and C > own), and
+ *     score(C) > score(own) (kin[own] = 0 without a neighbour there).  next[v] = the admissible C that is best under (higher
+ *     score, lower id), else comm[v]; gain[v] = score(next) - score(own), 0 for a vertex that stays.
+ *     Rows of at most wave_rows (<= 128) entries are served by a wavefront and an LDS table of 256 slots keyed by the community
+ *     id; the others are listed in heavy int32 [n_heavy]: up to block_rows (<= 2048) entries by a workgroup and an LDS table of
+ *     4096 slots, beyond by a workgroup and its own dense int32 scratch [n] in `workspace`
+ *     (wgnn_louvain_sweep_workspace_bytes(n, scratch_blocks): scratch_blocks <= 256 such workgroups; ZERO on entry, zero again
+ *     on return).  wave_rows, block_rows and scratch_blocks change no bit.
+ *   wgnn_louvain_apply: tot[c] = the sum of deg over label == c, size[c] = their number (both zeroed first; 64-bit integer
+ *     atomics), stats[0] = how many vertices have old_label != label (0 with old_label NULL); stats[1], stats[2] = 0.
+ *   wgnn_louvain_modularity: stats[1] += IN, the stored weight whose two ends share a label, the diagonal included;
+ *     stats[2] += the sum of tot[c]^2.  Qnum = den * M * IN - num * stats[2];  Q = Qnum / (den * M^2).
+ *   stats int64 [4]: [moved, IN, sum tot^2, status].  status is only ever OR-ed into (the caller zeroes it):
+ * ------------------------------------------------------------------------- */
+#define WGNN_SNN_IDX_I64          256   /* wgnn_snn_weights' flag: idx holds int64                                   */
+#define WGNN_LOUVAIN_UNSORTED       1   /* a row is not strictly ascending in col                                    */
+#define WGNN_LOUVAIN_BAD_COL        2   /* a column outside [0, n)                                                   */
+#define WGNN_LOUVAIN_BAD_ROWPTR     4   /* rowptr does not ascend from 0 to nnz                                      */
+#define WGNN_LOUVAIN_NO_SCRATCH     8   /* a row above block_rows entries met no scratch (scratch_blocks == 0)       */
+#define WGNN_LOUVAIN_BAD_LABEL     16   /* a label / community id outside [0, n)                                     */
+#define WGNN_LOUVAIN_BAD_WEIGHT    32   /* a negative weight                                                         */
+/* Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand; n outside [0, 2^31); a negative nnz, sweep, n_heavy or
+ * workspace size; ld_idx < k; m_den or num < 1; scratch_blocks outside [0, 256]; an unknown flag), WGNN_ERR_UNSUPPORTED (k outside
+ * [1, 64]; wave_rows outside [0, 128]; block_rows outside [0, 2048]), WGNN_ERR_ALIGNMENT (64-bit operands not 8-byte, 32-bit
+ * ones not 4-byte aligned), WGNN_ERR_WORKSPACE; wgnn_last_error_string names the check.  What only the entries of the graph can
+ * show - unsorted rows, columns out of range - is reported through the status word by wgnn_louvain_modularity, and no kernel
+ * reads or writes out of bounds on such a graph. */
+int wgnn_snn_weights(const void* idx, int64_t ld_idx, int64_t n, int32_t k, const int64_t* rowptr, const int32_t* col,
+                     int64_t nnz, int32_t* w, uint32_t flags, void* stream);
+int wgnn_louvain_sweep_workspace_bytes(int64_t n, int32_t scratch_blocks, int64_t* bytes);
+int wgnn_louvain_sweep(const int64_t* rowptr, const int32_t* col, const int32_t* w, int64_t n, int64_t nnz,
+                       const int32_t* comm, const int64_t* deg, const int64_t* tot, const int32_t* size,
+                       int64_t m_den, int64_t num, int32_t sweep, const int32_t* heavy, int32_t n_heavy,
+                       int32_t wave_rows, int32_t block_rows, int32_t* next, int64_t* gain, int64_t* stats,
+                       void* workspace, int64_t workspace_bytes, int32_t scratch_blocks, uint32_t flags, void* stream);
+int wgnn_louvain_apply(const int32_t* old_label, const int32_t* label, const int64_t* deg, int64_t n, int64_t* tot,
+                       int32_t* size, int64_t* stats, uint32_t flags, void* stream);
+int wgnn_louvain_modularity(const int64_t* rowptr, const int32_t* col, const int32_t* w, int64_t n, int64_t nnz,
+                            const int32_t* label, const int64_t* tot, int64_t* stats, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,9 @@ HOOD_MAX_MEMBERS, HOOD_MAX_SLAB_GENES = 256, 16384     # wgnn_hood_rows_*'s larg
 KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS = 64, 1024, 64    # wgnn_knn_rows' limits (include/wgnn.h)
 KMEANS_MAX_K = 4096                # wgnn_kmeans_seed's limit (include/wgnn.h); its D limits are wgnn_knn_rows'
 SILHOUETTE_MAX_GROUPS, SILHOUETTE_MAX_SPLITS = 4096, 64      # wgnn_silhouette_rows' limits (include/wgnn.h); D as wgnn_knn_rows
+SNN_MAX_K, SNN_IDX_I64 = 64, 256   # wgnn_snn_weights' limit and flag (include/wgnn.h)
+LOUVAIN_UNSORTED, LOUVAIN_BAD_COL, LOUVAIN_BAD_ROWPTR, LOUVAIN_NO_SCRATCH, LOUVAIN_BAD_LABEL, LOUVAIN_BAD_WEIGHT = 1, 2, 4, 8, 16, 32
+LOUVAIN_WAVE_ROWS, LOUVAIN_BLOCK_ROWS, LOUVAIN_SCRATCH_BLOCKS = 128, 2048, 256      # wgnn_louvain_sweep's largest routes (include/wgnn.h)
 ABI_MAJOR = 2                  # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
@@ -138,6 +141,12 @@ SIGNATURES = {
     "wgnn_group_rows_reduce": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _u32, _vp]),
     "wgnn_silhouette_workspace_bytes": (C.c_int, [_i64, _i32, _i32, _vp]),
     "wgnn_silhouette_rows": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _u32, _vp]),
+    "wgnn_snn_weights": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _u32, _vp]),
+    "wgnn_louvain_sweep_workspace_bytes": (C.c_int, [_i64, _i32, _vp]),
+    "wgnn_louvain_sweep": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _i32, _i32,
+                                     _vp, _vp, _vp, _vp, _i64, _i32, _u32, _vp]),
+    "wgnn_louvain_apply": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_louvain_modularity": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _u32, _vp]),
 }
 
 

@@ -31,7 +31,7 @@ from . import ops as _ops
 from . import tables as _tables
 from .ops import cross_entropy_sum
 # the result tables and the host helpers they share with the predictor: every name of tables.py is reachable through this module
-from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Coverage, CoverageSummary, Doublets, DoubletsSummary,
+from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Communities, CommunitiesSummary, Coverage, CoverageSummary, Doublets, DoubletsSummary,
                      GeneRanks, GeneRanksSummary, KMeans, KMeansSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
                      Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Silhouette, SilhouetteSummary, Smoothed, SmoothedSummary, Stability,
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
@@ -2075,6 +2075,83 @@ class ResidentPredictor:
         if (km.cluster < 0).any():
             raise WgnnError(f"kmeans_file: {int((km.cluster < 0).sum())} cells have no finite embedding and no cluster")
         return self._save_frame(km.clusters_frame(), save_path, "kmeans")
+
+    # ---------------------------------------------------------------------------------------------
+    def louvain(self, expr, k: int = 15, resolution=1.0, weights: str = "snn", genes=None, normalize=None, space: str = "hidden",
+                metric: str = "euclidean", graph=None, max_sweeps: int = 256, index=None) -> Communities:
+        """Louvain communities of a batch's own kNN graph, cut on the device and in integers: the batch is classified once
+        (``classify``'s call, bit for bit), searched as ``knn`` does (``k``, ``space``, ``metric`` as there), the lists made a
+        symmetric graph with shared-neighbour weights (``ops.snn_graph``: ``weights="snn"``, or ``"unit"``) and clustered by
+        ``ops.louvain_graph`` - a synchronous Louvain whose every gain is a 64-bit integer, so that the result depends on no
+        accumulation order.  ``resolution`` (> 0) becomes ``Fraction(resolution).limit_denominator(64)``: higher = more, smaller
+        communities.  ``graph``: an earlier ``NeighborGraph`` of the same batch, or a ``[B, k]`` index array (-1 = none), in
+        place of the search - ``k``, ``space`` and ``metric`` are then the graph's own (an array keeps the arguments').
+        ``index``: the cells' names.
+
+        Returns a ``Communities``; its ``cluster`` is, as it comes and with ``n_clusters=``, the ``clusters`` argument of
+        ``annotate`` / ``pseudobulk`` and the ``groups`` of ``rank_genes`` / ``silhouette``.  A cell without an edge (a NaN row,
+        which ``knn`` lists nowhere) has community -1.  Two calls give the same bits.
+
+        What this is not: it is Louvain, not Leiden - no refinement phase, a community can be internally disconnected; the
+        weights are shared-neighbour counts, not Jaccard indices with pruning and not UMAP connectivities; no random restarts;
+        one batch only; a graph whose total weight ``M`` has ``M^2 max(num, den) >= 2^62`` is refused (about 10^8 edges of
+        weight 16).  Fused kernels only, as ``embed``."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
+        if weights not in _ops.SNN_WEIGHTS:
+            raise ValueError(f"weights = {weights!r}: pass one of {', '.join(map(repr, _ops.SNN_WEIGHTS))}")
+        if not 1 <= int(k) <= _ops.SNN_MAX_K:
+            raise ValueError(f"k = {k} is outside [1, {_ops.SNN_MAX_K}]")
+        if int(max_sweeps) < 1:
+            raise ValueError(f"max_sweeps = {max_sweeps} must be >= 1")
+        _ops.louvain_resolution(resolution)
+        B = self._n_cells(expr)
+        lists = None
+        if graph is not None:
+            lists = np.asarray(graph.indices if isinstance(graph, NeighborGraph) else graph)
+            if lists.ndim != 2 or lists.shape[0] != B or not 1 <= lists.shape[1] <= _ops.SNN_MAX_K or lists.dtype.kind not in "iu":
+                raise ValueError(f"graph must be a NeighborGraph or an integer array [{B}, 1..{_ops.SNN_MAX_K}] of this batch")
+            if isinstance(graph, NeighborGraph):
+                space, metric = graph.space, graph.metric
+            k = int(lists.shape[1])
+        self._require_fused("louvain")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._louvain(self._over_genes(expr, genes, normalize), int(k), resolution, weights, space, metric, lists,
+                                 int(max_sweeps), index)
+
+    def _louvain(self, expr, k, resolution, weights, space, metric, lists, max_sweeps, index):
+        vb = self._values_batch(self._device_csr(expr))
+        B = int(vb.csr[0].shape[0]) - 1
+        if lists is None:
+            rows = self._embed(vb.csr, space)
+            if metric == "cosine":
+                rows = F.normalize(rows, dim=1)
+            idx, _ = _ops.knn_rows(rows, k)
+        else:
+            idx = torch.as_tensor(lists.astype(np.int64), device=self.device)
+        out = _ops.louvain_graph(*_ops.snn_graph(idx, weights), resolution=resolution, max_sweeps=max_sweeps)
+        cluster = out.cluster.cpu().numpy()
+        return Communities(cluster=cluster, size=np.bincount(cluster[cluster >= 0], minlength=0).astype(np.int64),
+                           modularity=out.modularity, resolution=out.resolution, weights=weights, levels=out.levels,
+                           level_labels=[l.cpu().numpy() for l in out.level_labels], converged=out.converged, k=k, space=space,
+                           metric=metric, label=vb.pred, max_prob=vb.max_prob, **self._table_fields(B, index))
+
+    def louvain_file(self, data, k: int = 15, resolution=1.0, weights: str = "snn", normalize=None, space: str = "hidden",
+                     metric: str = "euclidean", max_sweeps: int = 256, save_path=None) -> pd.DataFrame:
+        """``louvain`` on a test file - its full table, its gene names as ``genes=`` and its cell names.  Returns one row per cell:
+        a running number, ``cell`` (its name) and ``cluster`` (its community's name, ``"c0000"``, ...) - ``kmeans_file``'s layout,
+        which ``annotate_file``, ``pseudobulk_file`` and ``silhouette_file`` read as ``clusters_file`` - written as
+        ``{species}_{tissue}_louvain.csv`` under ``save_path`` when given.  A cell without an edge has no community:
+        ``WgnnError``.  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.louvain(matrix, k=k, resolution=resolution, weights=weights, genes=genes, normalize=normalize, space=space,
+                           metric=metric, max_sweeps=max_sweeps, index=index)
+        if (out.cluster < 0).any():
+            raise WgnnError(f"louvain_file: {int((out.cluster < 0).sum())} cells have no edge in the graph and no community")
+        return self._save_frame(out.clusters_frame(), save_path, "louvain")
 
     # ---------------------------------------------------------------------------------------------
     def silhouette(self, expr, groups="predicted", genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",

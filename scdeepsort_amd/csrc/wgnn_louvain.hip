@@ -1,0 +1,434 @@
+// wgnn_louvain.hip - graph clusters in integers (include/wgnn.h has the contracts): the shared-neighbour weights of a kNN union
+// graph and the three kernels of a synchronous Louvain sweep.  Every value is an int32 / int64, every decision a comparison of
+// 64-bit integers: the order of the atomic additions below changes no bit, and neither does the grid.
+//
+// wgnn_snn_weights: a wavefront per row i, a lane per entry of i's neighbour list (k <= 64).  For every stored neighbour j of the
+// union graph the lanes load j's list and count the distinct entries of N+(i) = {i} + list(i) that are in N+(j).
+//
+// wgnn_louvain_sweep: every vertex reads the state before the sweep (comm, tot, size) and leaves the community it moves to and
+// its gain.  kin[C], the weight from v into community C, is collected in a table keyed by the community id:
+//   - rows of at most wave_rows (<= 128) entries: one wavefront (a workgroup of 64 threads), an LDS table of 256 slots;
+//   - rows of at most block_rows (<= 2048) entries: a workgroup of 256 threads, an LDS table of 4096 slots;
+//   - longer rows (a hub cell): a workgroup with a dense int32 scratch per community in global memory, zero before and after.
+// Tables are open addressing, a compare-and-swap on the key and an integer add on the value; at most half full.
+//
+// wgnn_louvain_apply: tot / size of an assignment by 64-bit integer atomics, and how many vertices moved.
+// wgnn_louvain_modularity: IN (the stored weight inside communities, the diagonal included) and sum tot^2, and the checks of the
+// CSR that need the entries (status bits).
+#include <limits.h>
+#include "wgnn_common.h"
+
+namespace {
+using namespace wgnn;
+
+constexpr int kSnnMaxK = 64;
+constexpr int kWaveSlots = 256, kWaveRows = 128;
+constexpr int kBlockSlots = 4096, kBlockRows = 2048;
+constexpr int kMaxBlocks = 8192;
+constexpr int kMaxScratchBlocks = 256;
+
+typedef long long i64;
+typedef unsigned long long u64;
+
+__device__ __forceinline__ i64 clampl(i64 v, i64 hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// ---------------------------------------------------------------------------------------------------------------------------
+struct GArgs {
+    const void* idx; int idx64; long ld; long n; int k;
+    const i64* rowptr; const int* col; long nnz; int* w;
+};
+
+// entry t of row i's list: -1 for none, an id outside [0, n), or the row itself
+__device__ __forceinline__ int list_at(const GArgs& a, long i, int t) {
+    const i64 v = a.idx64 ? reinterpret_cast<const i64*>(a.idx)[i * a.ld + t] : (i64)reinterpret_cast<const int*>(a.idx)[i * a.ld + t];
+    return (v < 0 || v >= a.n || v == i) ? -1 : (int)v;
+}
+
+__global__ void __launch_bounds__(256) snn_weights_kernel(const GArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (long i = (long)blockIdx.x * 4 + wave; i < a.n; i += (long)gridDim.x * 4) {          // wave-uniform
+        int mine = lane < a.k ? list_at(a, i, lane) : -1;
+        bool again = false;                                                                   // an entry listed before: counted once
+        for (int s = 0; s < a.k; ++s) {
+            const int v = __shfl(mine, s, 64);
+            again |= s < lane && v == mine;
+        }
+        if (again) mine = -1;
+        const i64 e0 = clampl(a.rowptr[i], a.nnz), e1 = clampl(a.rowptr[i + 1], a.nnz);
+        for (i64 e = e0; e < e1; ++e) {
+            const int j = a.col[e];
+            int count = 0;
+            if ((unsigned)j < (unsigned long)a.n) {
+                const int theirs = lane < a.k ? list_at(a, j, lane) : -1;
+                bool hit = mine == j;                                                         // j is in N+(j)
+                for (int s = 0; s < a.k; ++s) hit |= __shfl(theirs, s, 64) == mine;
+                hit &= mine >= 0;
+                count = __popcll(__ballot(hit)) + (__ballot(theirs == (int)i) ? 1 : 0);      // ... and i itself when j lists it
+            }
+            if (lane == 0) a.w[e] = count;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+struct LArgs {
+    const i64* rowptr; const int* col; const int* w; long n; long nnz;
+    const int* comm; const i64* deg; const i64* tot; const int* size;
+    i64 mden; i64 num; int odd;
+    const int* heavy; int n_heavy; int wave_rows; int block_rows;
+    int* next; i64* gain; u64* stats;
+    int* scratch; int scratch_blocks;
+};
+
+struct Best { i64 score; int c; };
+
+// the community of neighbour u of v for kin: -1 for the diagonal, for a column or a community id outside [0, n)
+__device__ __forceinline__ int kin_comm(const LArgs& a, long v, int u) {
+    if (u == v || (unsigned long)(unsigned)u >= (unsigned long)a.n) return -1;
+    const int C = a.comm[u];
+    return (unsigned long)(unsigned)C < (unsigned long)a.n ? C : -1;
+}
+// v's own community, or -1 (and the status bit) when comm[v] is no id
+__device__ __forceinline__ int own_comm(const LArgs& a, long v) {
+    const int own = a.comm[v];
+    if ((unsigned long)(unsigned)own < (unsigned long)a.n) return own;
+    if ((threadIdx.x & 63) == 0) atomicOr(&a.stats[3], (u64)WGNN_LOUVAIN_BAD_LABEL);
+    return -1;
+}
+
+// community C with kin[C] = kin against the best so far: the gate, the singleton rule, a score above the own one; then the total
+// order (higher score, lower id).  Seeing a community twice changes nothing.
+__device__ __forceinline__ void consider(Best& b, const LArgs& a, int C, i64 kin, int own, i64 degv, int size_own, i64 score_own) {
+    if (C == own || (a.odd ? C < own : C > own) || (unsigned long)(unsigned)C >= (unsigned long)a.n) return;
+    if (size_own == 1 && C > own && a.size[C] == 1) return;
+    const i64 s = kin * a.mden - a.num * degv * a.tot[C];
+    if (s <= score_own) return;
+    if (b.c < 0 || s > b.score || (s == b.score && C < b.c)) { b.score = s; b.c = C; }
+}
+__device__ __forceinline__ void merge(Best& b, i64 score, int c) {
+    if (c >= 0 && (b.c < 0 || score > b.score || (score == b.score && c < b.c))) { b.score = score; b.c = c; }
+}
+__device__ __forceinline__ void wave_best(Best& b) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const i64 so = __shfl_xor(b.score, off, 64);
+        const int co = __shfl_xor(b.c, off, 64);
+        merge(b, so, co);
+    }
+}
+
+template <int SLOTS>
+__device__ __forceinline__ int slot_of(int C) { return (int)(((unsigned)C * 2654435761u) >> 16) & (SLOTS - 1); }
+
+template <int SLOTS>
+__device__ __forceinline__ void table_add(int* keys, int* vals, int C, int w) {
+    int s = slot_of<SLOTS>(C);
+    for (;;) {
+        const int seen = atomicCAS(&keys[s], -1, C);
+        if (seen == -1 || seen == C) { atomicAdd(&vals[s], w); return; }
+        s = (s + 1) & (SLOTS - 1);
+    }
+}
+template <int SLOTS>
+__device__ __forceinline__ int table_get(const int* keys, const int* vals, int C) {
+    int s = slot_of<SLOTS>(C);
+    for (;;) {
+        const int seen = keys[s];
+        if (seen == C) return vals[s];
+        if (seen == -1) return 0;
+        s = (s + 1) & (SLOTS - 1);
+    }
+}
+
+// one vertex by the THREADS threads of a workgroup through an LDS table of SLOTS slots (the row has at most SLOTS / 2 entries)
+template <int THREADS, int SLOTS>
+__device__ __forceinline__ Best vertex_in_lds(const LArgs& a, long v, i64 e0, i64 e1, int* keys, int* vals, i64* score_own_out) {
+    const int tid = threadIdx.x;
+    for (int s = tid; s < SLOTS; s += THREADS) { keys[s] = -1; vals[s] = 0; }
+    __syncthreads();
+    for (i64 e = e0 + tid; e < e1; e += THREADS) {
+        const int C = kin_comm(a, v, a.col[e]);
+        if (C >= 0) table_add<SLOTS>(keys, vals, C, a.w[e]);
+    }
+    __syncthreads();
+    const int own = own_comm(a, v);
+    const i64 degv = a.deg[v];
+    i64 score_own = 0;
+    Best b{0, -1};
+    if (own >= 0) {
+        const int size_own = a.size[own];
+        score_own = (i64)table_get<SLOTS>(keys, vals, own) * a.mden - a.num * degv * (a.tot[own] - degv);
+        for (int s = tid; s < SLOTS; s += THREADS)
+            if (keys[s] >= 0) consider(b, a, keys[s], (i64)vals[s], own, degv, size_own, score_own);
+    }
+    __syncthreads();                                           // the table is free for the next vertex
+    *score_own_out = score_own;
+    return b;
+}
+
+__device__ __forceinline__ void leave(const LArgs& a, long v, const Best& b, i64 score_own) {
+    a.next[v] = b.c >= 0 ? b.c : a.comm[v];                   // stays where it is
+    a.gain[v] = b.c >= 0 ? b.score - score_own : 0;
+}
+
+// rows of at most wave_rows entries: a workgroup IS a wavefront, so its barriers cost nothing
+__global__ void __launch_bounds__(64) sweep_wave_kernel(const LArgs a) {
+    __shared__ int keys[kWaveSlots];
+    __shared__ int vals[kWaveSlots];
+    for (long v = blockIdx.x; v < a.n; v += gridDim.x) {
+        const i64 e0 = clampl(a.rowptr[v], a.nnz), e1 = clampl(a.rowptr[v + 1], a.nnz);
+        if (e1 - e0 > a.wave_rows) continue;                  // the heavy kernel's
+        if (e1 <= e0) {                                        // no edge: stays
+            if (threadIdx.x == 0) { a.next[v] = a.comm[v]; a.gain[v] = 0; }
+            continue;
+        }
+        i64 score_own;
+        Best b = vertex_in_lds<64, kWaveSlots>(a, v, e0, e1, keys, vals, &score_own);
+        wave_best(b);
+        if (threadIdx.x == 0) leave(a, v, b, score_own);
+    }
+}
+
+// the rows above wave_rows (heavy[]): an LDS table up to block_rows entries, the workgroup's dense scratch beyond
+__global__ void __launch_bounds__(256) sweep_heavy_kernel(const LArgs a) {
+    __shared__ int keys[kBlockSlots];
+    __shared__ int vals[kBlockSlots];
+    __shared__ i64 s_score[4];
+    __shared__ int s_c[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int h = blockIdx.x; h < a.n_heavy; h += gridDim.x) {
+        const long v = a.heavy[h];
+        if (v < 0 || v >= a.n) continue;
+        const i64 e0 = clampl(a.rowptr[v], a.nnz), e1 = clampl(a.rowptr[v + 1], a.nnz);
+        i64 score_own = 0;
+        Best b{0, -1};
+        if (e1 - e0 <= a.block_rows) {
+            b = vertex_in_lds<256, kBlockSlots>(a, v, e0, e1, keys, vals, &score_own);
+        } else if (a.scratch && (int)blockIdx.x < a.scratch_blocks) {
+            int* kin = a.scratch + (size_t)blockIdx.x * a.n;
+            for (i64 e = e0 + tid; e < e1; e += 256) {
+                const int C = kin_comm(a, v, a.col[e]);
+                if (C >= 0) atomicAdd(&kin[C], a.w[e]);
+            }
+            __syncthreads();
+            const int own = own_comm(a, v);
+            const i64 degv = a.deg[v];
+            if (own >= 0) {                                    // the sums were made by atomics: read them where those ran
+                const int size_own = a.size[own];
+                score_own = (i64)__hip_atomic_load(&kin[own], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * a.mden
+                            - a.num * degv * (a.tot[own] - degv);
+                for (i64 e = e0 + tid; e < e1; e += 256) {
+                    const int C = kin_comm(a, v, a.col[e]);
+                    if (C >= 0)
+                        consider(b, a, C, (i64)__hip_atomic_load(&kin[C], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), own, degv,
+                                 size_own, score_own);
+                }
+            }
+            __syncthreads();
+            for (i64 e = e0 + tid; e < e1; e += 256) {         // zero again, for the next long row and the next sweep
+                const int C = kin_comm(a, v, a.col[e]);
+                if (C >= 0) __hip_atomic_store(&kin[C], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+        } else {                                               // a long row and no scratch: the caller sized the workspace wrong
+            if (tid == 0) atomicOr(&a.stats[3], (u64)WGNN_LOUVAIN_NO_SCRATCH);
+        }
+        wave_best(b);
+        if (lane == 0) { s_score[wave] = b.score; s_c[wave] = b.c; }
+        __syncthreads();
+        if (tid == 0) {
+            Best all{0, -1};
+            for (int i = 0; i < 4; ++i) merge(all, s_score[i], s_c[i]);
+            leave(a, v, all, score_own);
+        }
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// the sum of v over the workgroup's 256 threads, in thread 0 (integers: the order is free)
+__device__ __forceinline__ i64 block_sum(i64 v, i64* s_red) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
+}
+
+struct AArgs { const int* old_label; const int* label; const i64* deg; long n; u64* tot; int* size; u64* stats; };
+
+__global__ void __launch_bounds__(256) apply_kernel(const AArgs a) {
+    __shared__ i64 s_red[4];
+    i64 moved = 0;
+    for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < a.n; v += (long)gridDim.x * 256) {
+        const int c = a.label[v];
+        if ((unsigned long)(unsigned)c >= (unsigned long)a.n) { atomicOr(&a.stats[3], (u64)WGNN_LOUVAIN_BAD_LABEL); continue; }
+        atomicAdd(&a.tot[c], (u64)a.deg[v]);
+        atomicAdd(&a.size[c], 1);
+        if (a.old_label) moved += a.old_label[v] != c;
+    }
+    moved = block_sum(moved, s_red);
+    if (threadIdx.x == 0 && moved) atomicAdd(&a.stats[0], (u64)moved);
+}
+
+struct MArgs { const i64* rowptr; const int* col; const int* w; long n; long nnz; const int* label; const i64* tot; u64* stats; };
+
+// a wavefront per row: the weight of the entries whose two ends share a label, and the row's checks
+__global__ void __launch_bounds__(256) inside_kernel(const MArgs a) {
+    __shared__ i64 s_red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    i64 inside = 0;
+    unsigned bad = 0;
+    for (long v = (long)blockIdx.x * 4 + wave; v < a.n; v += (long)gridDim.x * 4) {
+        const i64 r0 = a.rowptr[v], r1 = a.rowptr[v + 1];
+        if (r0 < 0 || r1 < r0 || r1 > a.nnz || (v == 0 && r0 != 0) || (v == a.n - 1 && r1 != a.nnz)) bad |= WGNN_LOUVAIN_BAD_ROWPTR;
+        const i64 e0 = clampl(r0, a.nnz), e1 = clampl(r1, a.nnz);
+        const int mine = a.label[v];
+        for (i64 e = e0 + lane; e < e1; e += 64) {
+            const int u = a.col[e];
+            if ((unsigned long)(unsigned)u >= (unsigned long)a.n) { bad |= WGNN_LOUVAIN_BAD_COL; continue; }
+            if (e > e0 && a.col[e - 1] >= u) bad |= WGNN_LOUVAIN_UNSORTED;
+            if (a.w[e] < 0) bad |= WGNN_LOUVAIN_BAD_WEIGHT;
+            if (a.label[u] == mine) inside += a.w[e];
+        }
+    }
+    if (bad) atomicOr(&a.stats[3], (u64)bad);
+    inside = block_sum(inside, s_red);
+    if (threadIdx.x == 0 && inside) atomicAdd(&a.stats[1], (u64)inside);
+}
+
+__global__ void __launch_bounds__(256) tot2_kernel(const MArgs a) {
+    __shared__ i64 s_red[4];
+    i64 sum = 0;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < a.n; c += (long)gridDim.x * 256) sum += a.tot[c] * a.tot[c];
+    sum = block_sum(sum, s_red);
+    if (threadIdx.x == 0 && sum) atomicAdd(&a.stats[2], (u64)sum);
+}
+
+unsigned grid_for(int64_t items, int per_block) {
+    const int64_t want = (items + per_block - 1) / per_block;
+    return (unsigned)(want < 1 ? 1 : (want < kMaxBlocks ? want : kMaxBlocks));
+}
+
+const char* check_graph_sizes(int64_t n, int64_t nnz) {
+    if (n < 0 || n > INT32_MAX) return "n must be in [0, 2^31)";
+    if (nnz < 0) return "nnz must not be negative";
+    return nullptr;
+}
+
+int64_t scratch_bytes(int64_t n, int32_t scratch_blocks) { return n * 4 * (int64_t)scratch_blocks; }
+
+}  // namespace
+
+extern "C" int wgnn_snn_weights(const void* idx, int64_t ld_idx, int64_t n, int32_t k, const int64_t* rowptr, const int32_t* col,
+                                int64_t nnz, int32_t* w, uint32_t flags, void* stream) {
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_snn_weights", what); };
+    wgnn::error_clear();
+    if (const char* what = check_graph_sizes(n, nnz)) return fail(WGNN_ERR_BAD_ARG, what);
+    if (flags & ~(uint32_t)WGNN_SNN_IDX_I64) return fail(WGNN_ERR_BAD_ARG, "unknown flag (valid: WGNN_SNN_IDX_I64)");
+    if (k < 1 || k > kSnnMaxK) return fail(WGNN_ERR_UNSUPPORTED, "k must be in [1, 64]");
+    if (ld_idx < k) return fail(WGNN_ERR_BAD_ARG, "ld_idx < k");
+    if (!idx || !rowptr || !col || !w) return fail(WGNN_ERR_BAD_ARG, "idx, rowptr, col and w are required");
+    if (!aligned8(rowptr) || ((flags & WGNN_SNN_IDX_I64) && !aligned8(idx)))
+        return fail(WGNN_ERR_ALIGNMENT, "rowptr and an int64 idx must be 8-byte aligned");
+    if (!aligned4(idx) || !aligned4(col) || !aligned4(w)) return fail(WGNN_ERR_ALIGNMENT, "idx, col and w must be 4-byte aligned");
+    if (n == 0 || nnz == 0) return WGNN_OK;
+    GArgs a{};
+    a.idx = idx; a.idx64 = (flags & WGNN_SNN_IDX_I64) ? 1 : 0; a.ld = ld_idx; a.n = n; a.k = k;
+    a.rowptr = reinterpret_cast<const i64*>(rowptr); a.col = col; a.nnz = nnz; a.w = w;
+    hipLaunchKernelGGL(snn_weights_kernel, dim3(grid_for(n, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return hipGetLastError() == hipSuccess ? WGNN_OK : fail(WGNN_ERR_LAUNCH, "HIP launch failed");
+}
+
+extern "C" int wgnn_louvain_sweep_workspace_bytes(int64_t n, int32_t scratch_blocks, int64_t* bytes) {
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_louvain_sweep_workspace_bytes", what); };
+    wgnn::error_clear();
+    if (!bytes) return fail(WGNN_ERR_BAD_ARG, "bytes is required");
+    if (n < 0 || n > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n must be in [0, 2^31)");
+    if (scratch_blocks < 0 || scratch_blocks > kMaxScratchBlocks) return fail(WGNN_ERR_BAD_ARG, "scratch_blocks must be in [0, 256]");
+    *bytes = scratch_bytes(n, scratch_blocks);
+    return WGNN_OK;
+}
+
+extern "C" int wgnn_louvain_sweep(const int64_t* rowptr, const int32_t* col, const int32_t* w, int64_t n, int64_t nnz,
+                                  const int32_t* comm, const int64_t* deg, const int64_t* tot, const int32_t* size,
+                                  int64_t m_den, int64_t num, int32_t sweep, const int32_t* heavy, int32_t n_heavy,
+                                  int32_t wave_rows, int32_t block_rows, int32_t* next, int64_t* gain, int64_t* stats,
+                                  void* workspace, int64_t workspace_bytes, int32_t scratch_blocks, uint32_t flags, void* stream) {
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_louvain_sweep", what); };
+    wgnn::error_clear();
+    if (const char* what = check_graph_sizes(n, nnz)) return fail(WGNN_ERR_BAD_ARG, what);
+    if (flags) return fail(WGNN_ERR_BAD_ARG, "no flag is defined for this entry (flags must be 0)");
+    if (!rowptr || !col || !w || !comm || !deg || !tot || !size || !next || !gain || !stats)
+        return fail(WGNN_ERR_BAD_ARG, "rowptr, col, w, comm, deg, tot, size, next, gain and stats are required");
+    if (m_den < 1 || num < 1) return fail(WGNN_ERR_BAD_ARG, "m_den and num must be positive");
+    if (sweep < 0) return fail(WGNN_ERR_BAD_ARG, "sweep must not be negative");
+    if (n_heavy < 0 || (n_heavy > 0 && !heavy)) return fail(WGNN_ERR_BAD_ARG, "n_heavy is negative, or heavy is missing");
+    if (wave_rows < 0 || wave_rows > kWaveRows) return fail(WGNN_ERR_UNSUPPORTED, "wave_rows must be in [0, 128]");
+    if (block_rows < 0 || block_rows > kBlockRows) return fail(WGNN_ERR_UNSUPPORTED, "block_rows must be in [0, 2048]");
+    if (scratch_blocks < 0 || scratch_blocks > kMaxScratchBlocks) return fail(WGNN_ERR_BAD_ARG, "scratch_blocks must be in [0, 256]");
+    if (!aligned8(rowptr) || !aligned8(deg) || !aligned8(tot) || !aligned8(gain) || !aligned8(stats))
+        return fail(WGNN_ERR_ALIGNMENT, "rowptr, deg, tot, gain and stats must be 8-byte aligned");
+    if (!aligned4(col) || !aligned4(w) || !aligned4(comm) || !aligned4(size) || !aligned4(next) || !aligned4(heavy))
+        return fail(WGNN_ERR_ALIGNMENT, "col, w, comm, size, next and heavy must be 4-byte aligned");
+    if (workspace_bytes < 0) return fail(WGNN_ERR_WORKSPACE, "workspace_bytes is negative");
+    if (scratch_blocks > 0 && (!workspace || workspace_bytes < scratch_bytes(n, scratch_blocks)))
+        return fail(WGNN_ERR_WORKSPACE, "workspace is missing or smaller than wgnn_louvain_sweep_workspace_bytes asks for");
+    if (!aligned4(workspace)) return fail(WGNN_ERR_ALIGNMENT, "workspace must be 4-byte aligned");
+    if (n == 0) return WGNN_OK;
+
+    LArgs a{};
+    a.rowptr = reinterpret_cast<const i64*>(rowptr); a.col = col; a.w = w; a.n = n; a.nnz = nnz;
+    a.comm = comm; a.deg = reinterpret_cast<const i64*>(deg); a.tot = reinterpret_cast<const i64*>(tot); a.size = size;
+    a.mden = m_den; a.num = num; a.odd = sweep & 1;
+    a.heavy = heavy; a.n_heavy = n_heavy; a.wave_rows = wave_rows; a.block_rows = block_rows;
+    a.next = next; a.gain = reinterpret_cast<i64*>(gain); a.stats = reinterpret_cast<u64*>(stats);
+    a.scratch = scratch_blocks > 0 ? static_cast<int*>(workspace) : nullptr; a.scratch_blocks = scratch_blocks;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(sweep_wave_kernel, dim3(grid_for(n, 1)), dim3(64), 0, st, a);
+    if (n_heavy > 0) {
+        const unsigned blocks = scratch_blocks > 0 ? (unsigned)(n_heavy < scratch_blocks ? n_heavy : scratch_blocks) : grid_for(n_heavy, 1);
+        hipLaunchKernelGGL(sweep_heavy_kernel, dim3(blocks), dim3(256), 0, st, a);
+    }
+    return hipGetLastError() == hipSuccess ? WGNN_OK : fail(WGNN_ERR_LAUNCH, "HIP launch failed");
+}
+
+extern "C" int wgnn_louvain_apply(const int32_t* old_label, const int32_t* label, const int64_t* deg, int64_t n, int64_t* tot,
+                                  int32_t* size, int64_t* stats, uint32_t flags, void* stream) {
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_louvain_apply", what); };
+    wgnn::error_clear();
+    if (n < 0 || n > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n must be in [0, 2^31)");
+    if (flags) return fail(WGNN_ERR_BAD_ARG, "no flag is defined for this entry (flags must be 0)");
+    if (!label || !deg || !tot || !size || !stats) return fail(WGNN_ERR_BAD_ARG, "label, deg, tot, size and stats are required");
+    if (!aligned8(deg) || !aligned8(tot) || !aligned8(stats)) return fail(WGNN_ERR_ALIGNMENT, "deg, tot and stats must be 8-byte aligned");
+    if (!aligned4(old_label) || !aligned4(label) || !aligned4(size))
+        return fail(WGNN_ERR_ALIGNMENT, "old_label, label and size must be 4-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (hipMemsetAsync(stats, 0, 3 * sizeof(int64_t), st) != hipSuccess) return fail(WGNN_ERR_LAUNCH, "hipMemsetAsync failed");
+    if (n == 0) return WGNN_OK;
+    if (hipMemsetAsync(tot, 0, (size_t)n * 8, st) != hipSuccess || hipMemsetAsync(size, 0, (size_t)n * 4, st) != hipSuccess)
+        return fail(WGNN_ERR_LAUNCH, "hipMemsetAsync failed");
+    AArgs a{old_label, label, reinterpret_cast<const i64*>(deg), (long)n, reinterpret_cast<u64*>(tot), size,
+            reinterpret_cast<u64*>(stats)};
+    hipLaunchKernelGGL(apply_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, a);
+    return hipGetLastError() == hipSuccess ? WGNN_OK : fail(WGNN_ERR_LAUNCH, "HIP launch failed");
+}
+
+extern "C" int wgnn_louvain_modularity(const int64_t* rowptr, const int32_t* col, const int32_t* w, int64_t n, int64_t nnz,
+                                       const int32_t* label, const int64_t* tot, int64_t* stats, uint32_t flags, void* stream) {
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_louvain_modularity", what); };
+    wgnn::error_clear();
+    if (const char* what = check_graph_sizes(n, nnz)) return fail(WGNN_ERR_BAD_ARG, what);
+    if (flags) return fail(WGNN_ERR_BAD_ARG, "no flag is defined for this entry (flags must be 0)");
+    if (!rowptr || !col || !w || !label || !tot || !stats) return fail(WGNN_ERR_BAD_ARG, "rowptr, col, w, label, tot and stats are required");
+    if (!aligned8(rowptr) || !aligned8(tot) || !aligned8(stats)) return fail(WGNN_ERR_ALIGNMENT, "rowptr, tot and stats must be 8-byte aligned");
+    if (!aligned4(col) || !aligned4(w) || !aligned4(label)) return fail(WGNN_ERR_ALIGNMENT, "col, w and label must be 4-byte aligned");
+    if (n == 0) return WGNN_OK;
+    MArgs a{reinterpret_cast<const i64*>(rowptr), col, w, (long)n, (long)nnz, label, reinterpret_cast<const i64*>(tot),
+            reinterpret_cast<u64*>(stats)};
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(inside_kernel, dim3(grid_for(n, 4)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(tot2_kernel, dim3(grid_for(n, 256)), dim3(256), 0, st, a);
+    return hipGetLastError() == hipSuccess ? WGNN_OK : fail(WGNN_ERR_LAUNCH, "HIP launch failed");
+}

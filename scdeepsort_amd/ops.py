@@ -2377,3 +2377,234 @@ def silhouette_rows(x: torch.Tensor, group: torch.Tensor, n_groups: int, n_split
     back = torch.empty_like(order, dtype=torch.int64)
     back[order.long()] = torch.arange(B, dtype=torch.int64, device=dev)
     return SilhouetteRows(a[back], b[back], s[back], nearest[back], seg_ptr[1:] - seg_ptr[:-1])
+
+
+SNN_MAX_K = _lib.SNN_MAX_K                # wgnn_snn_weights' limit
+SNN_WEIGHTS = ("snn", "unit")
+LOUVAIN_WAVE_ROWS, LOUVAIN_BLOCK_ROWS, LOUVAIN_SCRATCH_BLOCKS = _lib.LOUVAIN_WAVE_ROWS, _lib.LOUVAIN_BLOCK_ROWS, _lib.LOUVAIN_SCRATCH_BLOCKS
+LOUVAIN_MAX_DEN = 64                      # louvain_graph's resolution is a fraction with a denominator up to this
+
+_LOUVAIN_STATUS = ((_lib.LOUVAIN_UNSORTED, "a row is not strictly ascending in col"),
+                   (_lib.LOUVAIN_BAD_COL, "a column is outside [0, n)"),
+                   (_lib.LOUVAIN_BAD_ROWPTR, "rowptr does not ascend from 0 to nnz"),
+                   (_lib.LOUVAIN_NO_SCRATCH, "a row above block_rows entries met no scratch"),
+                   (_lib.LOUVAIN_BAD_LABEL, "a community id is outside [0, n)"),
+                   (_lib.LOUVAIN_BAD_WEIGHT, "a weight is negative"))
+
+
+class SnnGraph(NamedTuple):
+    """What ``snn_graph`` returns, on the device: the symmetric CSR of the union graph - ``rowptr`` int64 [B + 1], ``col`` int32
+    ascending within a row, ``w`` int32."""
+    rowptr: torch.Tensor
+    col: torch.Tensor
+    w: torch.Tensor
+
+
+def snn_graph(idx: torch.Tensor, weights: str = "snn") -> SnnGraph:
+    """The union graph of ``[B, k]`` neighbour lists as ``knn_rows`` leaves them (int32 / int64, -1 = none, ``k`` in [1, 64], no
+    self entries) as a symmetric integer-weighted CSR on the device: ``{i, j}`` is an edge iff ``j`` is in ``i``'s list or ``i``
+    in ``j``'s.  ``weights="snn"``: ``w(i, j) = |N+(i) & N+(j)|`` with ``N+(i) = {i} + list(i)`` - the shared-neighbour count, the
+    numerator of Seurat's Jaccard weight, in [1, k + 1] - counted by ``wgnn_snn_weights``; ``"unit"``: every weight is 1.
+
+    The two directions of every listed pair are concatenated as 64-bit keys, sorted and made unique on the device
+    (``torch.unique``); the edge lists are never read back (one read-back validates the ids, one sizes the edge list).  An id
+    outside [-1, B) is a ``ValueError``; a self entry or a repeated entry is ignored.  Returns an ``SnnGraph``."""
+    name = "snn_graph"
+    dev = _require_cuda(idx)
+    if weights not in SNN_WEIGHTS:
+        raise ValueError(f"{name}: weights = {weights!r}: pass one of {', '.join(map(repr, SNN_WEIGHTS))}")
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: idx must be a 2-D int32 / int64 tensor [B, k]")
+    B, k = int(idx.shape[0]), int(idx.shape[1])
+    if not 1 <= k <= SNN_MAX_K:
+        raise ValueError(f"{name}: k = {k} is outside [1, {SNN_MAX_K}]")
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    idx = idx.contiguous()
+    if B:
+        lo, hi = torch.aminmax(idx)
+        if int(lo) < -1 or int(hi) >= B:
+            raise ValueError(f"{name}: a neighbour id is outside [-1, {B}) (min {int(lo)}, max {int(hi)})")
+    src = torch.arange(B, dtype=torch.int64, device=dev)[:, None].expand(B, k).reshape(-1)
+    dst = idx.reshape(-1).to(torch.int64)
+    listed = (dst >= 0) & (dst != src)
+    src, dst = src[listed], dst[listed]
+    keys = torch.unique(torch.cat([src * B + dst, dst * B + src]))             # sorted: row-major, columns ascending
+    row = torch.div(keys, max(B, 1), rounding_mode="floor")
+    col = (keys - row * B).to(torch.int32)
+    rowptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    if B:
+        torch.cumsum(torch.bincount(row, minlength=B), 0, out=rowptr[1:])
+    nnz = int(col.shape[0])
+    if weights == "unit" or nnz == 0:
+        return SnnGraph(rowptr, col, torch.ones(nnz, dtype=torch.int32, device=dev))
+    w = torch.empty(nnz, dtype=torch.int32, device=dev)
+    _lib.run(dev, "wgnn_snn_weights", _ptr(idx), k, B, k, _ptr(rowptr), _ptr(col), nnz, _ptr(w),
+             _lib.SNN_IDX_I64 if idx.dtype == torch.int64 else 0, _stream(dev))
+    return SnnGraph(rowptr, col, w)
+
+
+class LouvainRows(NamedTuple):
+    """What ``louvain_graph`` returns.  On the device: ``cluster`` int64 [B] (final ids by descending size, ties by the lowest
+    member; -1 for a vertex without an edge) and ``level_labels`` (one int64 [B] per level run: the dendrogram; a
+    level's ids are dense, in ascending order of the communities' own ids; the last level merged nothing and repeats the cut).  On the host: ``levels`` (per
+    level a dict ``vertices`` / ``communities`` / ``sweeps`` / ``fallback_moves``), ``qnum_trace`` (Python ints, strictly
+    increasing: the start, then one entry per kept sweep or fallback move), ``modularity`` (``Qnum / (den M^2)``),
+    ``resolution`` (the ``Fraction`` used), ``M`` and ``converged`` (False when a level stopped at ``max_sweeps``)."""
+    cluster: torch.Tensor
+    level_labels: list
+    levels: list
+    qnum_trace: list
+    modularity: float
+    resolution: object
+    M: int
+    converged: bool
+
+
+def louvain_resolution(resolution):
+    """``Fraction(resolution).limit_denominator(64)``, positive - the value ``louvain_graph`` uses; ``ValueError`` otherwise."""
+    from fractions import Fraction
+    try:
+        frac = Fraction(resolution).limit_denominator(LOUVAIN_MAX_DEN)
+    except (TypeError, ValueError, OverflowError, ZeroDivisionError):
+        raise ValueError(f"louvain_graph: resolution = {resolution!r} is no finite number") from None
+    if frac <= 0:
+        raise ValueError(f"louvain_graph: resolution = {resolution!r} must be positive (at least 1/128)")
+    return frac
+
+
+def louvain_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, resolution=1.0, max_sweeps: int = 256,
+                  wave_rows: int = LOUVAIN_WAVE_ROWS, block_rows: int = LOUVAIN_BLOCK_ROWS, scratch_blocks: int = 32) -> LouvainRows:
+    """Louvain communities of a symmetric CSR graph with int32 weights and no self loops (``rowptr`` int64 [B + 1], ``col`` int32
+    ascending within a row, ``w`` int32 >= 0 - what ``snn_graph`` returns), on the device and in integers (``include/wgnn.h``
+    has the contract).  ``resolution`` becomes ``num / den = Fraction(resolution).limit_denominator(64)``; with ``M`` the sum of
+    all weights, ``M * M * max(num, den) >= 2^62`` is a ``ValueError`` before any launch - below it every product fits int64.
+
+    A level's local moving is synchronous: sweep ``t`` (``wgnn_louvain_sweep``) lets every vertex pick, from the state before the
+    sweep, the best community of its neighbours that lies below its own id (``t`` even) or above (odd) and scores higher than
+    staying; ``wgnn_louvain_apply`` / ``wgnn_louvain_modularity`` then give ``Qnum`` of the new assignment, and one read-back of
+    four integers decides: kept when ``Qnum`` rose, else discarded for the single best move of the sweep (largest gain, lowest
+    vertex).  A level ends after two consecutive sweeps without a move or at ``max_sweeps``; its communities, renumbered densely
+    in ascending order of their ids, are the next level's vertices (the aggregation is ``torch.unique`` and an integer
+    ``index_add_`` on the device), until a level merges nothing.  No refinement phase (this is Louvain, not Leiden), no random
+    restarts.  ``wave_rows`` (<= 128), ``block_rows`` (<= 2048) and ``scratch_blocks`` (1..256) bound the three routes of the sweep
+    kernel by row length and change no bit; two calls are bit-identical.  CPU tensors raise ``WgnnError``; argument errors are
+    ``ValueError``; a malformed graph (unsorted rows, columns out of range) raises ``WgnnError``.  Returns a ``LouvainRows``."""
+    name = "louvain_graph"
+    dev = _require_cuda(rowptr, col, w)
+    max_sweeps, wave_rows, block_rows, scratch_blocks = int(max_sweeps), int(wave_rows), int(block_rows), int(scratch_blocks)
+    if max_sweeps < 1:
+        raise ValueError(f"{name}: max_sweeps = {max_sweeps} must be >= 1")
+    if not 0 <= wave_rows <= LOUVAIN_WAVE_ROWS or not 0 <= block_rows <= LOUVAIN_BLOCK_ROWS or \
+            not 1 <= scratch_blocks <= LOUVAIN_SCRATCH_BLOCKS:
+        raise ValueError(f"{name}: wave_rows in [0, {LOUVAIN_WAVE_ROWS}], block_rows in [0, {LOUVAIN_BLOCK_ROWS}] and scratch_blocks in "
+                         f"[1, {LOUVAIN_SCRATCH_BLOCKS}], got {wave_rows}, {block_rows}, {scratch_blocks}")
+    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
+            w.dtype != torch.int32 or w.shape != col.shape:
+        raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and w int32 [nnz] are expected")
+    frac = louvain_resolution(resolution)
+    num, den = frac.numerator, frac.denominator
+    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    rowptr, col, w = rowptr.contiguous(), col.contiguous(), w.contiguous()
+    M = int(w.sum(dtype=torch.int64)) if nnz else 0
+    if M * M * max(num, den) >= 2 ** 62:
+        raise ValueError(f"{name}: M * M * max(num, den) = {M * M * max(num, den)} >= 2^62 (M = {M}, resolution {frac}): the "
+                         "integer gains would not fit 64 bits")
+    if B and (int(rowptr[0]) != 0 or int(rowptr[-1]) != nnz):
+        raise WgnnError(f"{name}: rowptr does not run from 0 to nnz = {nnz}")
+    ids = torch.arange(B, dtype=torch.int64, device=dev)
+    if M == 0:
+        return LouvainRows(torch.full((B,), -1, dtype=torch.int64, device=dev), [ids],
+                           [dict(vertices=B, communities=B, sweeps=0, fallback_moves=0)], [0], 0.0, frac, 0, True)
+    isolated = rowptr[1:] == rowptr[:-1]
+    stream = _stream(dev)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+
+    def measure(n, graph, old, label, deg):
+        """tot / size of ``label`` and ``(moved, Qnum)``: apply, modularity and the one read-back."""
+        tot, size = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.run(dev, "wgnn_louvain_apply", _ptr(old), _ptr(label), _ptr(deg), n, _ptr(tot), _ptr(size), _ptr(stats), 0, stream)
+        _lib.run(dev, "wgnn_louvain_modularity", _ptr(graph[0]), _ptr(graph[1]), _ptr(graph[2]), n, int(graph[1].shape[0]),
+                 _ptr(label), _ptr(tot), _ptr(stats), 0, stream)
+        moved, inside, tot2, status = (int(v) for v in stats.tolist())
+        _check_status(name, status, _LOUVAIN_STATUS)
+        return tot, size, moved, den * M * inside - num * tot2
+
+    member, trace, levels, level_labels, converged = ids, None, [], [], True
+    while True:
+        n, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+        graph = (rowptr, col, w)
+        lens = rowptr[1:] - rowptr[:-1]
+        row = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), lens, output_size=nnz)
+        if trace is None and bool((row == col).any()):
+            raise ValueError(f"{name}: the graph holds a self loop")
+        deg = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, row, w.to(torch.int64))
+        comm = torch.arange(n, dtype=torch.int32, device=dev)
+        heavy = torch.nonzero(lens > wave_rows).reshape(-1).to(torch.int32)
+        n_heavy = int(heavy.shape[0])
+        n_scratch = min(scratch_blocks, int((lens > block_rows).sum())) if n_heavy else 0
+        ws, ws_bytes = (None, 0)
+        if n_scratch:                                               # zero on entry; the kernel leaves it zero
+            ws_bytes = _workspace_bytes("wgnn_louvain_sweep_workspace_bytes", n, n_scratch)
+            ws = torch.zeros(ws_bytes // 4, dtype=torch.int32, device=dev)
+        tot, size, _, q = measure(n, graph, None, comm, deg)       # the singletons' state, and the graph's checks
+        if trace is None:
+            trace = [q]
+        elif q != trace[-1]:                                        # aggregation keeps the partition, so Qnum too
+            raise WgnnError(f"{name}: Qnum changed across the aggregation ({trace[-1]} -> {q})")
+        t = idle = fallback = 0
+        while True:
+            if t >= max_sweeps:
+                converged = False
+                break
+            nxt = torch.empty(n, dtype=torch.int32, device=dev)
+            gain = torch.empty(n, dtype=torch.int64, device=dev)
+            _lib.run(dev, "wgnn_louvain_sweep", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(comm), _ptr(deg), _ptr(tot),
+                     _ptr(size), M * den, num, t, _ptr(heavy) if n_heavy else None, n_heavy, wave_rows, block_rows, _ptr(nxt),
+                     _ptr(gain), _ptr(stats), _ptr(ws) if n_scratch else None, ws_bytes, n_scratch, 0, stream)
+            tot2, size2, moved, q = measure(n, graph, comm, nxt, deg)
+            t += 1
+            if moved == 0:
+                idle += 1
+                if idle == 2:
+                    break
+                continue
+            idle = 0
+            if q > trace[-1]:
+                comm, tot, size = nxt, tot2, size2
+            else:                                                   # discarded: the single best move, ties to the lowest vertex
+                v = int(torch.nonzero(gain == gain.max()).reshape(-1)[0])
+                one = comm.clone()
+                one[v] = nxt[v]
+                tot, size, _, q = measure(n, graph, comm, one, deg)
+                if q <= trace[-1]:
+                    raise WgnnError(f"{name}: a single positive-gain move did not raise Qnum ({trace[-1]} -> {q}): the graph is "
+                                    "not symmetric")
+                comm = one
+                fallback += 1
+            trace.append(q)
+        uniq, inv = torch.unique(comm, return_inverse=True)         # dense ids in ascending order of the old ones
+        nc = int(uniq.shape[0])
+        member = inv[member]
+        levels.append(dict(vertices=n, communities=nc, sweeps=t, fallback_moves=fallback))
+        level_labels.append(member)
+        if nc == n:
+            break
+        key, kinv = torch.unique(inv[row] * nc + inv[col.long()], return_inverse=True)
+        w = torch.zeros(key.shape[0], dtype=torch.int64, device=dev).index_add_(0, kinv, w.to(torch.int64)).to(torch.int32)
+        crow = torch.div(key, nc, rounding_mode="floor")
+        col = (key - crow * nc).to(torch.int32)
+        rowptr = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(crow, minlength=nc), 0, out=rowptr[1:])
+    # final ids: by descending size, ties by the lowest member; a vertex without an edge has none
+    on = ~isolated
+    cluster = torch.full((B,), -1, dtype=torch.int64, device=dev)
+    uniq, inv, count = torch.unique(member[on], return_inverse=True, return_counts=True)
+    first = torch.full((int(uniq.shape[0]),), B, dtype=torch.int64, device=dev).scatter_reduce_(0, inv, ids[on], "amin")
+    order = torch.argsort((B - count) * B + first)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(order.shape[0], dtype=torch.int64, device=dev)
+    cluster[on] = rank[inv]
+    return LouvainRows(cluster, level_labels, levels, trace, trace[-1] / (den * M * M), frac, M, converged)

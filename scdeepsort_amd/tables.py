@@ -1788,33 +1788,9 @@ class KMeansSummary(dict):
             f"median purity {d['median_purity']:.3f}, {d['n_mixed']} clusters below 0.9 ({d['n_unsure']} cells unsure)"])
 
 
-@dataclass
-class KMeans(_NamesCalls):
-    """What ``ResidentPredictor.kmeans`` returns: the k-means clusters of one batch in the model's space.  B cells (``index``),
-    K clusters (``cluster_names``: ``"c0000"``, ... - zero-padded, so sorted order is id order), C cell types (``id2label``).
-    ``cluster`` int64 [B]: a cell's cluster, -1 for a cell whose embedding holds a non-finite value - as it stands, with
-    ``n_clusters=K``, the ``clusters`` argument of ``annotate`` / ``pseudobulk`` and ``rank_genes``' ``groups``.
-    ``sq_distance`` f32 [B]: the squared distance to the cell's centre (NaN beside a -1); ``centers`` f32 [K, D];
-    ``size`` int64 [K]; ``seed_cells`` int64 [K]: the cells the seeding chose (``None`` with an init array); ``inertia``: the sum
-    of ``sq_distance``, ``inertia_trace`` the same after every assignment; ``n_iter`` / ``converged``: ``ops.kmeans_rows``'.
-    ``space`` / ``metric`` say what was clustered (under ``"cosine"`` the L2-normalised rows; the centres are their plain means,
-    not re-normalised); ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
-    cluster: np.ndarray
-    sq_distance: np.ndarray
-    centers: np.ndarray
-    size: np.ndarray
-    seed_cells: Optional[np.ndarray]
-    inertia: float
-    inertia_trace: Sequence[float]
-    n_iter: int
-    converged: bool
-    space: str
-    metric: str
-    label: np.ndarray
-    max_prob: np.ndarray
-    index: Sequence
-    id2label: Sequence[str]
-    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+class _CellClusters(_NamesCalls):
+    """What the tables of per-cell clusters (``KMeans``, ``Communities``) share: ``cluster`` int64 [B] with -1 = none, ``size``
+    int64 [K], ``label`` / ``index`` / ``id2label``."""
 
     @property
     def n_clusters(self) -> int:
@@ -1849,6 +1825,35 @@ class KMeans(_NamesCalls):
         names = self.cluster_names
         return pd.DataFrame({"index": np.arange(len(self.cluster), dtype=np.int64), "cell": [str(c) for c in self.index],
                              "cluster": [names[k] if k >= 0 else "" for k in np.asarray(self.cluster, np.int64)]})
+
+
+@dataclass
+class KMeans(_CellClusters):
+    """What ``ResidentPredictor.kmeans`` returns: the k-means clusters of one batch in the model's space.  B cells (``index``),
+    K clusters (``cluster_names``: ``"c0000"``, ... - zero-padded, so sorted order is id order), C cell types (``id2label``).
+    ``cluster`` int64 [B]: a cell's cluster, -1 for a cell whose embedding holds a non-finite value - as it stands, with
+    ``n_clusters=K``, the ``clusters`` argument of ``annotate`` / ``pseudobulk`` and ``rank_genes``' ``groups``.
+    ``sq_distance`` f32 [B]: the squared distance to the cell's centre (NaN beside a -1); ``centers`` f32 [K, D];
+    ``size`` int64 [K]; ``seed_cells`` int64 [K]: the cells the seeding chose (``None`` with an init array); ``inertia``: the sum
+    of ``sq_distance``, ``inertia_trace`` the same after every assignment; ``n_iter`` / ``converged``: ``ops.kmeans_rows``'.
+    ``space`` / ``metric`` say what was clustered (under ``"cosine"`` the L2-normalised rows; the centres are their plain means,
+    not re-normalised); ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    cluster: np.ndarray
+    sq_distance: np.ndarray
+    centers: np.ndarray
+    size: np.ndarray
+    seed_cells: Optional[np.ndarray]
+    inertia: float
+    inertia_trace: Sequence[float]
+    n_iter: int
+    converged: bool
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
 
     def frame(self) -> pd.DataFrame:
         """One row per cell: ``index``, ``cell_type`` / ``prob`` (named as ``predict`` names them), ``cluster`` (its name, ``None``
@@ -1980,3 +1985,83 @@ class Silhouette(_NamesCalls):
                                  best_group=None if best is None else best["group"],
                                  best_mean=float("nan") if best is None else float(best["mean"]),
                                  n_unsure=int((np.asarray(self.label) < 0).sum()))
+
+
+class CommunitiesSummary(dict):
+    """``Communities.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        how = "converged" if d["converged"] else "NOT converged (a level stopped at max_sweeps)"
+        return "\n".join([
+            f"{d['n_cells']} cells in {d['n_clusters']} Louvain communities of the k = {d['k']} graph in the {d['space']} space "
+            f"({d['metric']}, {d['weights']} weights), resolution {d['resolution']}, {how}; {d['n_skipped']} cells without an edge",
+            f"{d['n_levels']} levels, {d['n_sweeps']} sweeps, {d['n_fallback']} fallback moves, modularity {d['modularity']:.4f}",
+            f"community sizes {d['min_size']} .. {d['max_size']} (median {d['median_size']:.4g})",
+            f"median purity {d['median_purity']:.3f}, {d['n_mixed']} communities below 0.9 ({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class Communities(_CellClusters):
+    """What ``ResidentPredictor.louvain`` returns: the Louvain communities of one batch's kNN graph.  B cells (``index``), K
+    communities (``cluster_names``: ``"c0000"``, ... as ``KMeans``), C cell types (``id2label``).  ``cluster`` int64 [B]: a cell's
+    community, ids by descending size (ties by the lowest member), -1 for a cell without an edge (a NaN row) - as it stands, with
+    ``n_clusters=K``, the ``clusters`` argument of ``annotate`` / ``pseudobulk`` and the ``groups`` of ``rank_genes`` /
+    ``silhouette``.  ``size`` int64 [K]; ``modularity``: ``Qnum / (den M^2)`` of the final cut at ``resolution`` (the ``Fraction``
+    used); ``weights`` ("snn" | "unit"); ``level_labels``: one int64 [B] per level of the dendrogram (``at_level``), ``levels`` the
+    per-level dicts of ``ops.louvain_graph``; ``converged``.  ``space`` / ``metric`` / ``k`` say which graph was cut; ``label``
+    int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    cluster: np.ndarray
+    size: np.ndarray
+    modularity: float
+    resolution: object
+    weights: str
+    levels: Sequence[dict]
+    level_labels: Sequence[np.ndarray]
+    converged: bool
+    k: int
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def at_level(self, level: int) -> np.ndarray:
+        """int64 [B]: the cut after level ``level`` (0 = the finest, -1 = the final one), ids renumbered as ``cluster``'s are - by
+        descending size, ties by the lowest member - and -1 where ``cluster`` is."""
+        lab = np.asarray(self.level_labels[level], np.int64)
+        on = np.asarray(self.cluster, np.int64) >= 0
+        out = np.full(lab.shape[0], -1, np.int64)
+        if on.any():
+            uniq, first, inv, count = np.unique(lab[on], return_index=True, return_inverse=True, return_counts=True)
+            rank = np.empty(len(uniq), np.int64)
+            rank[np.lexsort((first, -count))] = np.arange(len(uniq))
+            out[on] = rank[inv.reshape(-1)]
+        return out
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` / ``prob`` (named as ``predict`` names them), ``cluster`` (its name, ``None``
+        without one), and the community's ``cluster_size`` and ``cluster_purity``."""
+        names, cl = self.cluster_names, np.asarray(self.cluster, np.int64)
+        on, at = cl >= 0, np.maximum(cl, 0)
+        size = np.asarray(self.size, np.int64)
+        return pd.DataFrame({"index": list(self.index), "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob),
+                             "cluster": [names[k] if k >= 0 else None for k in cl],
+                             "cluster_size": np.where(on, size[at], 0) if size.size else np.zeros(len(cl), np.int64),
+                             "cluster_purity": np.where(on, self.purity()[at], np.nan) if size.size else np.full(len(cl), np.nan)})
+
+    def summary(self) -> CommunitiesSummary:
+        """Cells, communities, levels and sweeps, the modularity, sizes and the purity against ``classify``'s calls; ``print`` it."""
+        size, purity = np.asarray(self.size, np.int64), self.purity()
+        known = purity[~np.isnan(purity)]
+        return CommunitiesSummary(n_cells=len(self.cluster), n_clusters=self.n_clusters, k=int(self.k), space=self.space,
+                                  metric=self.metric, weights=self.weights, resolution=str(self.resolution),
+                                  converged=bool(self.converged), n_skipped=int((np.asarray(self.cluster) < 0).sum()),
+                                  n_levels=len(self.levels), n_sweeps=int(sum(l["sweeps"] for l in self.levels)),
+                                  n_fallback=int(sum(l["fallback_moves"] for l in self.levels)), modularity=float(self.modularity),
+                                  min_size=int(size.min()) if size.size else 0, max_size=int(size.max()) if size.size else 0,
+                                  median_size=float(np.median(size)) if size.size else float("nan"),
+                                  median_purity=float(np.median(known)) if known.size else float("nan"),
+                                  n_mixed=int((known < 0.9).sum()), n_unsure=int((np.asarray(self.label) < 0).sum()))
