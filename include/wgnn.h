@@ -1435,6 +1435,63 @@ int wgnn_louvain_apply(const int32_t* old_label, const int32_t* label, const int
 int wgnn_louvain_modularity(const int64_t* rowptr, const int32_t* col, const int32_t* w, int64_t n, int64_t nnz,
                             const int32_t* label, const int64_t* tot, int64_t* stats, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The fuzzy kNN graph and a synchronous 2-D layout (additive exports, WGNN_VERSION stays 206): the kernels behind
+ * ops.fuzzy_graph / ops.layout_graph / api.ResidentPredictor.umap.  Every floating-point operation named here is rounded on its
+ * own (no fused multiply-add), every sum runs in the stated order and nothing depends on the grid: two calls give the same bits.
+ *
+ * wgnn_fuzzy_rows - the memberships of each row's own neighbour list (UMAP's smooth kNN distances, local_connectivity = 1).
+ *     idx [n, ld_idx] int32 (int64 with WGNN_FUZZY_IDX_I64) and d2 [n, ld_d2] float32, k <= 64 valid columns, as wgnn_knn_rows
+ *         leaves them; an entry is LISTED iff idx >= 0 and d2 is finite
+ *     target = log2(k + 1), passed by the host
+ *   Per row: d_j = sqrtf(d2_j) in float32, all that follows in float64.  rho = the smallest d_j > 0 (0 without one);
+ *   x_j = d_j - rho;  p(s) = the sum over the listed j, in list order, of (x_j > 0 ? exp(-x_j / s) : 1).  From lo = 0, hi = inf,
+ *   s = 1, exactly 64 times: p(s) > target ? (hi = s, s = (lo + hi) / 2) : (lo = s, s = hi == inf ? 2 s : (lo + hi) / 2).  Then
+ *   sigma = max(s, 1e-3 * mean_j d_j) (the mean over the listed entries, summed in list order) and
+ *   member_j = (float)(x_j > 0 ? exp(-x_j / sigma) : 1) for a listed entry, 0 for another.
+ *     rho, sigma float64 [n]; member float32 [n, k] (dense).  A row with nothing listed: rho = sigma = 0, members 0.
+ *
+ * wgnn_fuzzy_union - the weights of the symmetric union graph (set_op_mix_ratio = 1).
+ *     rowptr int64 [n + 1], col int32 [nnz]: the union CSR (ops.snn_graph's); idx / member as above
+ *   For the stored edge (i, c): p = member[i, t] at the first t with idx[i, t] == c (0 without one), q the same with i and c
+ *   swapped;  w = (p + q) - p * q, three float32 operations - so w(i, c) and w(c, i) are the same bits.  A column outside [0, n)
+ *   gives 0.
+ *
+ * wgnn_layout_init - the "hash" start: y[t] = ((float)(h >> 40) * 2^-24) * 20 - 10 in float32, in [-10, 10), with
+ *     h = mix64(mix64(((u64)seed << 32) | 0xFFFFFFFF) + t) for t = 2 * vertex + component (mix64: the splitmix64 finaliser).
+ *
+ * wgnn_layout_epoch - epoch `epoch` of n_epochs: reads y_in, writes y_out (another buffer), float32 [n, 2].
+ *   The directed edge at CSR position e of vertex i, other end j:  r = w[e] / wmax;  it FIRES iff
+ *   floorf((float)(epoch + 1) * r) != floorf((float)epoch * r) - both directions of an undirected edge in the same epochs.
+ *   A firing edge adds, in this order, with dx = y_i - y_j, q = dx0 * dx0 + dx1 * dx1 and qb = q^b:
+ *     the attraction, if q > 0:  c = (((-2 * a) * b) * qb / q) / (1 + a * qb);  g = clamp(c * dx, -4, 4) per component
+ *     for s = 0 .. n_neg - 1 a repulsion from vertex t = ((h >> 32) * n) >> 32,
+ *       h = mix64(mix64(((u64)seed << 32) | epoch) + e * n_neg + s), if t != i and (dx = y_i - y_t) q > 0:
+ *       c = ((2 * gamma) * b) / ((0.001f + q) * (1 + a * qb));  g = clamp(c * dx, -4, 4)
+ *   An edge that does not fire adds nothing (no negatives either).  qb = q itself when b == 1.0f, else
+ *   (float)pow((double)q, (double)b).  WGNN_LAYOUT_LANES lanes serve a vertex: lane (e - rowptr[i]) % 16 adds its edges' terms in
+ *   e order to its partial G (from +0), and the partials fold by halves (lane l += lane l + 8, then 4, 2, 1).
+ *   y_out_i = y_i + alpha * G_i (one multiply, one add per component); a vertex without a stored edge copies its position.
+ *   fired int64 [n] (optional): fired[i] += the number of i's edges that fired.  No atomics, no workspace.
+ * ------------------------------------------------------------------------- */
+#define WGNN_FUZZY_IDX_I64        256   /* wgnn_fuzzy_rows' / wgnn_fuzzy_union's flag: idx holds int64               */
+#define WGNN_LAYOUT_LANES          16   /* lanes per vertex: part of wgnn_layout_epoch's sum order                   */
+#define WGNN_LAYOUT_MAX_EPOCHS  10000   /* (float)epoch is exact far beyond; the schedule is the caller's            */
+#define WGNN_LAYOUT_MAX_NEG        64
+/* Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand; n outside [0, 2^31); a negative nnz; ld < k; a target, wmax, a,
+ * b, gamma or alpha that is not finite, target or wmax not positive; epoch outside [0, n_epochs), n_epochs outside [1, 10000];
+ * n_neg outside [0, 64]; y_out == y_in; an unknown flag), WGNN_ERR_UNSUPPORTED (k outside [1, 64]), WGNN_ERR_ALIGNMENT (64-bit
+ * operands and the positions not 8-byte, 32-bit ones not 4-byte aligned); wgnn_last_error_string names the check.  No kernel reads
+ * or writes out of bounds on a malformed graph: rowptr is clamped to [0, nnz] and a column outside [0, n) is skipped. */
+int wgnn_fuzzy_rows(const void* idx, int64_t ld_idx, const float* d2, int64_t ld_d2, int64_t n, int32_t k, double target,
+                    double* rho, double* sigma, float* member, uint32_t flags, void* stream);
+int wgnn_fuzzy_union(const void* idx, int64_t ld_idx, const float* member, int64_t n, int32_t k, const int64_t* rowptr,
+                     const int32_t* col, int64_t nnz, float* w, uint32_t flags, void* stream);
+int wgnn_layout_init(float* y, int64_t n, uint32_t seed, uint32_t flags, void* stream);
+int wgnn_layout_epoch(const int64_t* rowptr, const int32_t* col, const float* w, int64_t n, int64_t nnz, float wmax,
+                      const float* y_in, float* y_out, int32_t epoch, int32_t n_epochs, float a, float b, float gamma,
+                      float alpha, int32_t n_neg, uint32_t seed, int64_t* fired, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,7 @@ from . import tables as _tables
 from .ops import cross_entropy_sum
 # the result tables and the host helpers they share with the predictor: every name of tables.py is reachable through this module
 from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Communities, CommunitiesSummary, Coverage, CoverageSummary, Doublets, DoubletsSummary,
-                     GeneRanks, GeneRanksSummary, KMeans, KMeansSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
+                     GeneRanks, GeneRanksSummary, KMeans, KMeansSummary, Layout, LayoutSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
                      Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Silhouette, SilhouetteSummary, Smoothed, SmoothedSummary, Stability,
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
                      _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores)
@@ -1975,7 +1975,8 @@ class ResidentPredictor:
         ``to_scipy()`` is the layout of ``adata.obsp["distances"]``.  Two calls give the same bits.
 
         What this is not: no approximate index - the cost is ``O(B^2 D)``; no fuzzy-simplicial-set connectivities (UMAP's
-        weights), no clustering; one batch only - no graph across calls.  A graph in ``space="hidden"`` is the classifier's own
+        weights: ``umap`` builds them from these lists, ``graph=`` there takes this table) and no clustering (``kmeans``,
+        ``louvain``); one batch only - no graph across calls.  A graph in ``space="hidden"`` is the classifier's own
         view: smoothing over it can confirm a wrong call; ``space="features"`` and ``Smoothed.neighbor_agreement()`` are the
         checks."""
         if space not in KNN_SPACES:
@@ -2093,7 +2094,8 @@ class ResidentPredictor:
         which ``knn`` lists nowhere) has community -1.  Two calls give the same bits.
 
         What this is not: it is Louvain, not Leiden - no refinement phase, a community can be internally disconnected; the
-        weights are shared-neighbour counts, not Jaccard indices with pruning and not UMAP connectivities; no random restarts;
+        weights are shared-neighbour counts, not Jaccard indices with pruning and not UMAP connectivities (``umap`` computes those, for its layout
+        only: ``Layout.connectivities()``); no random restarts;
         one batch only; a graph whose total weight ``M`` has ``M^2 max(num, den) >= 2^62`` is refused (about 10^8 edges of
         weight 16).  Fused kernels only, as ``embed``."""
         if space not in KNN_SPACES:
@@ -2152,6 +2154,130 @@ class ResidentPredictor:
         if (out.cluster < 0).any():
             raise WgnnError(f"louvain_file: {int((out.cluster < 0).sum())} cells have no edge in the graph and no community")
         return self._save_frame(out.clusters_frame(), save_path, "louvain")
+
+    # ---------------------------------------------------------------------------------------------
+    def umap(self, expr, k: int = 15, min_dist: float = 0.1, spread: float = 1.0, a=None, b=None, n_epochs: Optional[int] = None,
+             n_neg: int = 5, seed: int = 0, init="pca", genes=None, normalize=None, space: str = "hidden",
+             metric: str = "euclidean", graph=None, index=None) -> Layout:
+        """A 2-D layout of a batch from the fuzzy graph of its own kNN lists - the picture the calls and clusters are drawn on -
+        without a host round trip: the batch is classified once (``classify``'s call, bit for bit), searched as ``knn`` does
+        (``k``, ``space``, ``metric`` as there), the lists and their distances made UMAP's connectivities (``ops.fuzzy_graph``)
+        and laid out by ``ops.layout_graph``: UMAP's attraction along the edges and repulsion from ``n_neg`` hashed draws per
+        firing edge, applied synchronously - every epoch reads the positions of the one before, every sum has a fixed order.
+        ``a`` / ``b``: the curve, by default ``ops.layout_curve(min_dist, spread)`` (a scipy fit on the host); ``n_epochs`` =
+        None: 500 below 10 000 cells, 200 from there on.  ``graph``: an earlier ``NeighborGraph`` of the same batch in place of
+        the search - ``k``, ``space`` and ``metric`` are then the graph's own; a bare index array is refused, distances are
+        needed.  ``index``: the cells' names.
+
+        ``init``: ``"pca"`` - the first two principal components of the searched rows, scaled to max-abs 10 - is the ONE step not
+        run by this project's kernels: mean, ``[D, D]`` covariance and projection are framework operations in float64 on the
+        device with ``numpy.linalg.eigh`` on the host in between (each axis' sign fixed by its largest component), so its bits
+        follow the installed libraries; ``"hash"`` (uniform in [-10, 10) from ``seed``) and a ``[B, 2]`` array start from
+        stated bits, and for them two calls give the same bits.
+
+        Returns a ``Layout``.  A cell without an edge (a NaN row, which ``knn`` lists nowhere) keeps its start position - the
+        origin under ``"pca"`` - and has ``placed`` False.
+
+        What this is not: not umap-learn's order of updates - there (Hogwild SGD) an edge moves both ends at once and later
+        edges see the move, here a firing edge moves each end once, from that end's own row, off the previous epoch's
+        positions; no spectral init, no ``transform`` of new cells, no 3-D, no supervised mode; one batch only.  Fused kernels
+        only, as ``embed``."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
+        if not 1 <= int(k) <= _ops.FUZZY_MAX_K:
+            raise ValueError(f"k = {k} is outside [1, {_ops.FUZZY_MAX_K}]")
+        if n_epochs is not None and not 1 <= int(n_epochs) <= _ops.LAYOUT_MAX_EPOCHS:
+            raise ValueError(f"n_epochs = {n_epochs} is outside [1, {_ops.LAYOUT_MAX_EPOCHS}]")
+        if not 0 <= int(n_neg) <= _ops.LAYOUT_MAX_NEG:
+            raise ValueError(f"n_neg = {n_neg} is outside [0, {_ops.LAYOUT_MAX_NEG}]")
+        if not 0 <= int(seed) < 2 ** 32:
+            raise ValueError(f"seed = {seed} is outside [0, 2^32)")
+        if a is None or b is None:
+            fit = _ops.layout_curve(min_dist, spread)
+            a, b = fit[0] if a is None else a, fit[1] if b is None else b
+        a, b = float(a), float(b)
+        if not (0.0 < a < float("inf") and 0.0 < b < float("inf")):
+            raise ValueError(f"a = {a} and b = {b} must be positive and finite")
+        B = self._n_cells(expr)
+        start = init
+        if not isinstance(init, str):
+            start = np.asarray(init)
+            if start.shape != (B, 2) or start.dtype.kind not in "fiu" or not np.isfinite(start).all():
+                raise ValueError(f"init must be 'pca', 'hash' or a finite array [{B}, 2]")
+            start = start.astype(np.float32)
+        elif init not in ("pca", "hash"):
+            raise ValueError(f"init = {init!r}: pass 'pca', 'hash' or an array [{B}, 2]")
+        lists = None
+        if graph is not None:
+            if not isinstance(graph, NeighborGraph):
+                raise ValueError("graph must be a NeighborGraph: the layout needs the neighbours' distances, which a bare index "
+                                 "array does not carry")
+            lists = (np.asarray(graph.indices), np.asarray(graph.sq_distances))
+            if lists[0].ndim != 2 or lists[0].shape[0] != B or not 1 <= lists[0].shape[1] <= _ops.FUZZY_MAX_K or \
+                    lists[1].shape != lists[0].shape:
+                raise ValueError(f"graph must be a NeighborGraph of this batch: [{B}, 1..{_ops.FUZZY_MAX_K}] lists and distances")
+            space, metric, k = graph.space, graph.metric, int(lists[0].shape[1])
+        self._require_fused("umap")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._umap(self._over_genes(expr, genes, normalize), int(k), a, b, n_epochs, int(n_neg), int(seed), start,
+                              space, metric, lists, index)
+
+    def _umap(self, expr, k, a, b, n_epochs, n_neg, seed, start, space, metric, lists, index):
+        vb = self._values_batch(self._device_csr(expr))
+        B = int(vb.csr[0].shape[0]) - 1
+        rows = None
+        if lists is None or (isinstance(start, str) and start == "pca"):
+            rows = self._embed(vb.csr, space)
+            if metric == "cosine":
+                rows = F.normalize(rows, dim=1)
+        if lists is None:
+            idx, d2 = _ops.knn_rows(rows, k)
+        else:
+            idx = torch.as_tensor(lists[0].astype(np.int64), device=self.device)
+            d2 = torch.as_tensor(lists[1].astype(np.float32), device=self.device)
+        fuzzy = _ops.fuzzy_graph(idx, d2)
+        if isinstance(start, str):
+            how, y0 = start, (self._pca_start(rows) if start == "pca" else "hash")
+        else:
+            how, y0 = "array", torch.as_tensor(start, device=self.device)
+        out = _ops.layout_graph(fuzzy.rowptr, fuzzy.col, fuzzy.w, y0, n_epochs=n_epochs, a=a, b=b, n_neg=n_neg, seed=seed)
+        rowptr = fuzzy.rowptr.cpu().numpy()
+        return Layout(coords=out.y.cpu().numpy(), placed=rowptr[1:] > rowptr[:-1], rho=fuzzy.rho.cpu().numpy(),
+                      sigma=fuzzy.sigma.cpu().numpy(), rowptr=rowptr, col=fuzzy.col.cpu().numpy(), weight=fuzzy.w.cpu().numpy(),
+                      a=a, b=b, n_epochs=out.n_epochs, n_fired=out.n_fired, seed=seed, init=how, k=k, space=space, metric=metric,
+                      label=vb.pred, max_prob=vb.max_prob, **self._table_fields(B, index))
+
+    @staticmethod
+    def _pca_start(rows: torch.Tensor) -> torch.Tensor:
+        """``umap``'s ``init="pca"``: the finite rows' first two principal components in float64 (framework operations and a host
+        ``eigh``), each axis' sign fixed by its largest component, scaled to max-abs 10; a non-finite row sits at the origin."""
+        x = rows.double()
+        ok = torch.isfinite(x).all(dim=1)
+        y = torch.zeros((x.shape[0], 2), dtype=torch.float64, device=x.device)
+        if int(ok.sum()) > 0:
+            centred = x[ok] - x[ok].mean(dim=0)
+            cov = (centred.T @ centred / centred.shape[0]).cpu().numpy()
+            axes = np.linalg.eigh(cov)[1][:, ::-1][:, :2]
+            axes = axes * np.where(axes[np.abs(axes).argmax(axis=0), np.arange(2)] < 0, -1.0, 1.0)
+            y[ok] = centred @ torch.from_numpy(np.ascontiguousarray(axes)).to(x.device)
+            top = float(y.abs().max())
+            if top > 0:
+                y = y * (10.0 / top)
+        return y.float()
+
+    def umap_file(self, data, k: int = 15, min_dist: float = 0.1, spread: float = 1.0, a=None, b=None,
+                  n_epochs: Optional[int] = None, n_neg: int = 5, seed: int = 0, init="pca", normalize=None,
+                  space: str = "hidden", metric: str = "euclidean", save_path=None) -> pd.DataFrame:
+        """``umap`` on a test file - its full table, its gene names as ``genes=`` and its cell names.  Returns one row per cell:
+        ``cell`` (its name), ``x`` and ``y`` - written as ``{species}_{tissue}_umap.csv`` under ``save_path`` when
+        given.  A cell without an edge is written at its start position.  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.umap(matrix, k=k, min_dist=min_dist, spread=spread, a=a, b=b, n_epochs=n_epochs, n_neg=n_neg, seed=seed,
+                        init=init, genes=genes, normalize=normalize, space=space, metric=metric, index=index)
+        return self._save_frame(out.coords_frame(), save_path, "umap")
 
     # ---------------------------------------------------------------------------------------------
     def silhouette(self, expr, groups="predicted", genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",

@@ -10,6 +10,7 @@ non-CUDA tensor or a missing ``libwgnn_hip.so`` raises ``WgnnError``.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import NamedTuple, Optional
 
 import torch
@@ -2608,3 +2609,157 @@ def louvain_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, reso
     rank[order] = torch.arange(order.shape[0], dtype=torch.int64, device=dev)
     cluster[on] = rank[inv]
     return LouvainRows(cluster, level_labels, levels, trace, trace[-1] / (den * M * M), frac, M, converged)
+
+
+FUZZY_MAX_K = _lib.FUZZY_MAX_K            # wgnn_fuzzy_rows' limit
+LAYOUT_LANES, LAYOUT_MAX_EPOCHS, LAYOUT_MAX_NEG = _lib.LAYOUT_LANES, _lib.LAYOUT_MAX_EPOCHS, _lib.LAYOUT_MAX_NEG
+LAYOUT_A, LAYOUT_B = 1.577, 0.895         # layout_curve(0.1, 1.0), rounded: layout_graph's defaults
+LAYOUT_INITS = ("hash",)
+
+
+class FuzzyGraph(NamedTuple):
+    """What ``fuzzy_graph`` returns, on the device: the symmetric CSR of the union graph (``rowptr`` int64 [B + 1], ``col`` int32
+    ascending within a row) with UMAP's connectivities ``w`` float32 [nnz] - ``w(i, j)`` and ``w(j, i)`` are the same bits - and the
+    per-row ``rho`` / ``sigma`` float64 [B] and ``member`` float32 [B, k] of ``wgnn_fuzzy_rows``."""
+    rowptr: torch.Tensor
+    col: torch.Tensor
+    w: torch.Tensor
+    rho: torch.Tensor
+    sigma: torch.Tensor
+    member: torch.Tensor
+
+
+def fuzzy_graph(idx: torch.Tensor, d2: torch.Tensor) -> FuzzyGraph:
+    """UMAP's fuzzy simplicial set of ``[B, k]`` neighbour lists as ``knn_rows`` leaves them (``idx`` int32 / int64 with -1 = none,
+    ``d2`` float32 squared distances with +inf = none; ``k`` in [1, 64]; views into wider rows are taken), on the device
+    (``include/wgnn.h`` has the contract).  ``wgnn_fuzzy_rows`` gives every row its ``rho`` (the nearest positive distance), its
+    ``sigma`` (64 bisection steps towards ``sum_j exp(-(d_j - rho) / sigma) = log2(k + 1)``, floored at 1e-3 of the row's mean
+    distance) and the memberships of its own list; ``wgnn_fuzzy_union`` joins the two directions on ``snn_graph(idx, "unit")``'s
+    structure as ``w = a + b - a b``.  Given ``member``, numpy reproduces ``w`` bit for bit; ``member`` itself is within one
+    float32 ulp (2^-24 absolute) of a numpy restatement, the two ``exp`` differing in the last bit of a float64.
+
+    Against umap-learn: the bisection never exits early (no 1e-5 tolerance); the floor uses the row's own mean even when
+    ``rho = 0`` (umap-learn then takes the mean of all distances); ``local_connectivity`` is fixed at 1 and ``set_op_mix_ratio`` at
+    1.  An entry with ``idx >= 0`` and a finite ``d2`` is listed, a self entry among them; an id outside [-1, B) or a negative
+    ``d2`` is a ``ValueError``.  Returns a ``FuzzyGraph``."""
+    name = "fuzzy_graph"
+    dev = _require_cuda(idx, d2)
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: idx must be a 2-D int32 / int64 tensor [B, k]")
+    B, k = int(idx.shape[0]), int(idx.shape[1])
+    if not 1 <= k <= FUZZY_MAX_K:
+        raise ValueError(f"{name}: k = {k} is outside [1, {FUZZY_MAX_K}]")
+    if not _row_strided(idx, B, k):
+        raise ValueError(f"{name}: idx must have unit column stride and a row stride >= {k}")
+    _view_2d(name, ValueError, "d2", d2, torch.float32, B, k)
+    if B and bool((d2 < 0).any()):
+        raise ValueError(f"{name}: d2 holds a negative squared distance")
+    rowptr, col, _ = snn_graph(idx, "unit")                                     # checks the ids
+    rho = torch.empty(B, dtype=torch.float64, device=dev)
+    sigma = torch.empty(B, dtype=torch.float64, device=dev)
+    member = torch.empty((B, k), dtype=torch.float32, device=dev)
+    nnz = int(col.shape[0])
+    w = torch.empty(nnz, dtype=torch.float32, device=dev)
+    flags = _lib.FUZZY_IDX_I64 if idx.dtype == torch.int64 else 0
+    _lib.run(dev, "wgnn_fuzzy_rows", _ptr(idx), _ld(idx, B, k), _ptr(d2), _ld(d2, B, k), B, k, math.log2(k + 1), _ptr(rho),
+             _ptr(sigma), _ptr(member), flags, _stream(dev))
+    _lib.run(dev, "wgnn_fuzzy_union", _ptr(idx), _ld(idx, B, k), _ptr(member), B, k, _ptr(rowptr), _ptr(col), nnz, _ptr(w), flags,
+             _stream(dev))
+    return FuzzyGraph(rowptr, col, w, rho, sigma, member)
+
+
+class LayoutRows(NamedTuple):
+    """What ``layout_graph`` returns: ``y`` float32 [B, 2] on the device, ``n_epochs`` (the number run) and ``n_fired`` (how many
+    times a stored, directed edge fired over all epochs; a Python int)."""
+    y: torch.Tensor
+    n_epochs: int
+    n_fired: int
+
+
+def layout_curve(min_dist: float = 0.1, spread: float = 1.0):
+    """``(a, b)`` of the layout's similarity ``1 / (1 + a d^(2 b))``: the least-squares fit to ``d < min_dist ? 1 :
+    exp(-(d - min_dist) / spread)`` on 300 points of [0, 3 spread] that umap-learn's ``find_ab_params`` makes, by
+    ``scipy.optimize.curve_fit`` on the host.  ``min_dist`` in [0, spread], ``spread`` > 0, else ``ValueError``."""
+    import numpy as np
+    from scipy.optimize import curve_fit
+    min_dist, spread = float(min_dist), float(spread)
+    if not (0.0 < spread < float("inf")) or not 0.0 <= min_dist <= spread:
+        raise ValueError(f"layout_curve: spread must be positive and min_dist in [0, spread], got {min_dist}, {spread}")
+    xv = np.linspace(0.0, 3.0 * spread, 300)
+    yv = np.where(xv < min_dist, 1.0, np.exp(-(xv - min_dist) / spread))
+    (a, b), _ = curve_fit(lambda x, a, b: 1.0 / (1.0 + a * x ** (2.0 * b)), xv, yv)
+    return float(a), float(b)
+
+
+def layout_epochs(n_cells: int) -> int:
+    """umap-learn's default number of epochs: 500 below 10 000 cells, 200 from there on."""
+    return 500 if n_cells < 10000 else 200
+
+
+def layout_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, init="hash", n_epochs: Optional[int] = None,
+                 a: float = LAYOUT_A, b: float = LAYOUT_B, gamma: float = 1.0, n_neg: int = 5, lr: float = 1.0,
+                 seed: int = 0) -> LayoutRows:
+    """A 2-D layout of a symmetric weighted CSR graph (``rowptr`` int64 [B + 1], ``col`` int32, ``w`` float32 >= 0 - what
+    ``fuzzy_graph`` returns) by UMAP's forces applied SYNCHRONOUSLY: every epoch (``wgnn_layout_epoch``, one launch each on the
+    current stream, no read-back and no graph capture in between) reads the positions of the epoch before and writes new ones
+    into a second buffer, and every vertex's sum runs in a fixed order (``include/wgnn.h`` has the contract) - so two calls give
+    the same bits, whatever the grid.  A stored edge fires in ``floor(n_epochs w / max w)`` of the epochs, both its directions in
+    the same ones; a firing edge pulls its row's vertex towards the other end and pushes it away from ``n_neg`` vertices drawn
+    by a counter hash of ``(seed, epoch, edge, draw)``; the step is ``lr (1 - epoch / n_epochs)``, computed here in float64.
+
+    ``init``: a float32 [B, 2] tensor (copied) or ``"hash"`` - uniform in [-10, 10) from the same hash of ``seed``
+    (``wgnn_layout_init``).  ``n_epochs`` = None: 500 below 10 000 vertices, 200 from there on; at most 10 000.  ``a`` / ``b``:
+    ``layout_curve``'s (the defaults are its values for ``min_dist`` 0.1, ``spread`` 1); with ``b == 1`` the whole epoch is +, -,
+    x, / in float32 and numpy restates it bit for bit, otherwise ``q^b`` is a float64 ``pow`` rounded to float32.  A vertex
+    without an edge keeps its position.  One read-back before the loop (``max w`` and the finiteness of ``w`` and ``init``) and one
+    after it (``n_fired``).  Not umap-learn's order: there an edge moves both ends at once and later edges see the move.
+    A non-finite or negative ``w``, a non-finite ``init`` and every other argument error are ``ValueError``; CPU tensors raise
+    ``WgnnError``.  Returns a ``LayoutRows``."""
+    name = "layout_graph"
+    dev = _require_cuda(rowptr, col, w, init if isinstance(init, torch.Tensor) else None)
+    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
+            w.dtype != torch.float32 or w.shape != col.shape:
+        raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and w float32 [nnz] are expected")
+    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    n_epochs = layout_epochs(B) if n_epochs is None else int(n_epochs)
+    n_neg, seed = int(n_neg), int(seed)
+    if not 1 <= n_epochs <= LAYOUT_MAX_EPOCHS:
+        raise ValueError(f"{name}: n_epochs = {n_epochs} is outside [1, {LAYOUT_MAX_EPOCHS}]")
+    if not 0 <= n_neg <= LAYOUT_MAX_NEG:
+        raise ValueError(f"{name}: n_neg = {n_neg} is outside [0, {LAYOUT_MAX_NEG}]")
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{name}: seed = {seed} is outside [0, 2^32)")
+    a, b, gamma, lr = float(a), float(b), float(gamma), float(lr)
+    if not (0.0 < a < float("inf") and 0.0 < b < float("inf") and 0.0 <= gamma < float("inf") and 0.0 < lr < float("inf")):
+        raise ValueError(f"{name}: a, b and lr must be positive, gamma not negative, all finite (got {a}, {b}, {gamma}, {lr})")
+    stream = _stream(dev)
+    if isinstance(init, torch.Tensor):
+        if init.dtype != torch.float32 or tuple(init.shape) != (B, 2):
+            raise ValueError(f"{name}: init must be a float32 [{B}, 2] tensor or one of {', '.join(map(repr, LAYOUT_INITS))}")
+        y = init.contiguous().clone()
+    elif isinstance(init, str) and init in LAYOUT_INITS:
+        y = torch.empty((B, 2), dtype=torch.float32, device=dev)
+        _lib.run(dev, "wgnn_layout_init", _ptr(y), B, seed, 0, stream)
+    else:
+        raise ValueError(f"{name}: init = {init!r}: pass a float32 [{B}, 2] tensor or one of {', '.join(map(repr, LAYOUT_INITS))}")
+    rowptr, col, w = rowptr.contiguous(), col.contiguous(), w.contiguous()
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    wmax, wmin, bad_w, bad_y = torch.stack([w.max() if nnz else zero, w.min() if nnz else zero,
+                                            (~torch.isfinite(w)).sum().float(), (~torch.isfinite(y)).sum().float()]).tolist()
+    if bad_w or wmin < 0:
+        raise ValueError(f"{name}: w holds a non-finite or a negative weight")
+    if bad_y:
+        raise ValueError(f"{name}: init holds a non-finite position")
+    if B and (int(rowptr[0]) != 0 or int(rowptr[-1]) != nnz):
+        raise ValueError(f"{name}: rowptr does not run from 0 to nnz = {nnz}")
+    if B == 0 or nnz == 0 or wmax <= 0:                                         # nothing can fire
+        return LayoutRows(y, n_epochs, 0)
+    fired = torch.zeros(B, dtype=torch.int64, device=dev)
+    other = torch.empty_like(y)
+    for n in range(n_epochs):
+        _lib.run(dev, "wgnn_layout_epoch", _ptr(rowptr), _ptr(col), _ptr(w), B, nnz, wmax, _ptr(y), _ptr(other), n, n_epochs, a, b,
+                 gamma, lr * (1.0 - n / n_epochs), n_neg, seed, _ptr(fired), 0, stream)
+        y, other = other, y
+    return LayoutRows(y, n_epochs, int(fired.sum()))

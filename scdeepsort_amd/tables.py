@@ -2065,3 +2065,98 @@ class Communities(_CellClusters):
                                   median_size=float(np.median(size)) if size.size else float("nan"),
                                   median_purity=float(np.median(known)) if known.size else float("nan"),
                                   n_mixed=int((known < 0.9).sum()), n_unsure=int((np.asarray(self.label) < 0).sum()))
+
+
+class LayoutSummary(dict):
+    """``Layout.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_cells']} cells laid out in 2-D from the k = {d['k']} graph in the {d['space']} space ({d['metric']}): "
+            f"{d['n_edges']} undirected edges, {d['n_unplaced']} cells without an edge keep their start",
+            f"{d['n_epochs']} synchronous epochs from the {d['init']} start, a = {d['a']:.4g}, b = {d['b']:.4g}, seed {d['seed']}; "
+            f"{d['n_fired']} edge firings",
+            f"x in [{d['x_min']:.4g}, {d['x_max']:.4g}], y in [{d['y_min']:.4g}, {d['y_max']:.4g}]; median sigma {d['median_sigma']:.4g}",
+            f"{d['n_types']} called types, median spread around a type's centroid {d['median_spread']:.4g} ({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class Layout(_NamesCalls):
+    """What ``ResidentPredictor.umap`` returns: a 2-D layout of one batch from the fuzzy graph of its own kNN lists.  B cells
+    (``index``), C cell types (``id2label``).  ``coords`` f32 [B, 2]; ``placed`` bool [B]: False for a cell without an edge (a NaN
+    row), which keeps its start position; ``rho`` / ``sigma`` f64 [B]: the cell's nearest positive distance and the bandwidth of
+    its memberships (``ops.fuzzy_graph``); ``rowptr`` int64 [B + 1] / ``col`` int32 / ``weight`` f32: the symmetric union graph with
+    UMAP's connectivities, on the host (``connectivities()``).  ``a`` / ``b``: the curve used; ``n_epochs``, ``n_fired`` (edge
+    firings over all epochs), ``seed``, ``init`` ("pca" | "hash" | "array"); ``k`` / ``space`` / ``metric`` say which graph was laid
+    out; ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    coords: np.ndarray
+    placed: np.ndarray
+    rho: np.ndarray
+    sigma: np.ndarray
+    rowptr: np.ndarray
+    col: np.ndarray
+    weight: np.ndarray
+    a: float
+    b: float
+    n_epochs: int
+    n_fired: int
+    seed: int
+    init: str
+    k: int
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def connectivities(self) -> sp.csr_matrix:
+        """CSR ``[B, B]`` float32 of the union graph's weights, symmetric, columns ascending - the layout of
+        ``adata.obsp["connectivities"]``."""
+        B = len(self.rowptr) - 1
+        return sp.csr_matrix((np.asarray(self.weight, np.float32), np.asarray(self.col, np.int32), np.asarray(self.rowptr, np.int64)),
+                             shape=(B, B))
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``x``, ``y``, ``label`` (the call's name, as ``predict`` names it) and ``max_prob``."""
+        xy = np.asarray(self.coords, np.float32)
+        return pd.DataFrame({"index": list(self.index), "x": xy[:, 0], "y": xy[:, 1], "label": self._name(self.label),
+                             "max_prob": np.asarray(self.max_prob)})
+
+    def coords_frame(self) -> pd.DataFrame:
+        """One row per cell - ``cell`` (its name), ``x`` and ``y``: what ``umap_file`` writes."""
+        xy = np.asarray(self.coords, np.float32)
+        return pd.DataFrame({"cell": [str(c) for c in self.index], "x": xy[:, 0], "y": xy[:, 1]})
+
+    def by_type(self) -> pd.DataFrame:
+        """One row per call (unsure included, last) over the placed cells: ``cell_type``, ``n_cells``, the centroid ``x`` / ``y`` and
+        ``spread`` (the root mean squared distance of the type's cells to it)."""
+        own, xy = np.asarray(self.label, np.int64), np.asarray(self.coords, np.float64)
+        on = np.asarray(self.placed, bool)
+        rows = []
+        for s in sorted(set(own[on & (own >= 0)].tolist())) + ([-1] if (on & (own < 0)).any() else []):
+            m = on & ((own == s) if s >= 0 else (own < 0))
+            centre = xy[m].mean(axis=0)
+            rows.append((s, int(m.sum()), centre[0], centre[1], float(np.sqrt(((xy[m] - centre) ** 2).sum(axis=1).mean()))))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(5)]
+        return pd.DataFrame({"cell_type": self._name(cols[0]), "n_cells": np.asarray(cols[1], np.int64),
+                             "x": np.asarray(cols[2], np.float64), "y": np.asarray(cols[3], np.float64),
+                             "spread": np.asarray(cols[4], np.float64)})
+
+    def summary(self) -> LayoutSummary:
+        """Cells, edges, epochs and firings, the extent of the layout and the spread of the called types; ``print`` it."""
+        xy, on = np.asarray(self.coords, np.float64), np.asarray(self.placed, bool)
+        types = self.by_type()
+        if (on & (np.asarray(self.label, np.int64) < 0)).any():                 # the unsure cells' row comes last
+            types = types.iloc[:-1]
+        ext = lambda v, f: float(f(v)) if len(v) else float("nan")
+        sigma = np.asarray(self.sigma, np.float64)[on]
+        return LayoutSummary(n_cells=len(xy), k=int(self.k), space=self.space, metric=self.metric, n_edges=int(len(self.col) // 2),
+                             n_unplaced=int((~on).sum()), n_epochs=int(self.n_epochs), n_fired=int(self.n_fired), init=self.init,
+                             a=float(self.a), b=float(self.b), seed=int(self.seed),
+                             x_min=ext(xy[on, 0], np.min), x_max=ext(xy[on, 0], np.max), y_min=ext(xy[on, 1], np.min),
+                             y_max=ext(xy[on, 1], np.max), median_sigma=ext(sigma, np.median), n_types=int(len(types)),
+                             median_spread=ext(np.asarray(types["spread"]), np.median),
+                             n_unsure=int((np.asarray(self.label) < 0).sum()))
