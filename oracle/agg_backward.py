@@ -102,27 +102,50 @@ def bwd_alpha(A, inv_deg, g, h_src, h_self=None, row_ids=None, self_compact: boo
     return res
 
 
-def fwd(A, inv_deg, alpha, mode: int, self_idx: int, h_src, h_self=None) -> dict:
-    """K1 (``wgnn_agg_fwd``, all rows, no bias / ReLU):
+def fwd(A, inv_deg, alpha, mode: int, self_idx: int, h_src, h_self=None, *, row_ids=None, self_compact: bool = False, bias=None,
+        relu: bool = False, no_mean: bool = False, no_self: bool = False, out_scale_alpha: bool = False) -> dict:
+    """K1 (``wgnn_agg_fwd`` / ``wgnn_agg_fwd_tiled``): for each output slot i (row r = row_ids[i] or i), in the header's order
 
-        SRC_IS_GENE: neigh[r] = sum_j A[r,j]*alpha[j]*h_src[j];  out[r] = (neigh[r] + alpha[self_idx]*h_self[r]) * inv_deg[r]
-        DST_IS_GENE: neigh[r] = sum_j A[r,j]*h_src[j];           out[r] = (alpha[r]*neigh[r] + alpha[self_idx]*h_self[r]) * inv_deg[r]
-        NO_ALPHA   : neigh[r] = sum_j A[r,j]*h_src[j];           out[r] = (neigh[r] + h_self[r]) * inv_deg[r]
+        neigh[i] = sum_j A[r,j] * (alpha[j] if SRC_IS_GENE) * h_src[j]                  the kernels' ``neigh_sum`` (raw sum)
+        pre[i]   = (alpha[r] if DST_IS_GENE) * neigh[i] + a_self * h_self[i if self_compact else r]
+                   a_self = alpha[self_idx] (1 for NO_ALPHA); no self term with ``no_self`` (WGNN_FLAG_NO_SELF) or h_self None
+        out[i]   = pre[i] * f[r]                f[r] = inv_deg[r]; 1 / (row length + 1) for ``inv_deg=None``; 1 with ``no_mean``
+        out[i]  += bias ;  out[i] = max(out[i], 0) with ``relu`` ;  out[i] *= alpha[r] with ``out_scale_alpha`` (DST_IS_GENE only)
 
-    ``neigh`` is the kernels' ``neigh_sum`` output (the raw sum before the row factor)."""
+    ``abs_out`` follows every step (the bias adds ``|bias|``, the post-scale multiplies), ``n_terms`` is the row length of every
+    slot, ``row_factor`` the f[r] used, ``pre_relu`` the rows before the ReLU and the post-scale."""
     A = _csr64(A)
     R, S = A.shape
-    inv_deg, alpha, h_src, h_self = _f64(inv_deg), _f64(alpha), _f64(h_src), _f64(h_self)
+    inv_deg, alpha, h_src, h_self, bias = _f64(inv_deg), _f64(alpha), _f64(h_src), _f64(h_self), _f64(bias)
+    if out_scale_alpha and mode != DST_IS_GENE:
+        raise ValueError("out_scale_alpha is defined for DST_IS_GENE only")
+    rows = np.arange(R) if row_ids is None else np.asarray(row_ids, dtype=np.int64)
+    Ar = A[rows] if len(rows) else sp.csr_matrix((0, S), dtype=np.float64)
     X = alpha[:S, None] * h_src if mode == SRC_IS_GENE else h_src
-    neigh = A @ X
-    abs_neigh = _abs(A) @ np.abs(X)
-    rs = alpha[:R, None] if mode == DST_IS_GENE else 1.0
+    neigh = Ar @ X
+    abs_neigh = _abs(Ar) @ np.abs(X)
+    a_row = alpha[rows, None] if mode == DST_IS_GENE else 1.0
     a_self = 1.0 if mode == NO_ALPHA else alpha[self_idx]
-    pre, abs_pre = rs * neigh, np.abs(rs) * abs_neigh
-    if h_self is not None:
-        pre, abs_pre = pre + a_self * h_self, abs_pre + abs(a_self) * np.abs(h_self)
-    return dict(neigh=neigh, abs_neigh=abs_neigh, out=pre * inv_deg[:, None], abs_out=abs_pre * np.abs(inv_deg)[:, None],
-                n_terms=np.diff(A.indptr).astype(np.int64))
+    pre, abs_pre = a_row * neigh, np.abs(a_row) * abs_neigh
+    if h_self is not None and not no_self:
+        hs = h_self if (self_compact or row_ids is None) else h_self[rows]
+        pre, abs_pre = pre + a_self * hs, abs_pre + abs(a_self) * np.abs(hs)
+    n_terms = np.diff(Ar.indptr).astype(np.int64)
+    if no_mean:
+        f = np.ones(len(rows))
+    elif inv_deg is None:
+        f = 1.0 / (n_terms + 1.0)
+    else:
+        f = inv_deg[rows]
+    out, abs_out = pre * f[:, None], abs_pre * np.abs(f)[:, None]
+    if bias is not None:
+        out, abs_out = out + bias, abs_out + np.abs(bias)
+    pre_relu = out
+    if relu:
+        out = np.maximum(out, 0.0)
+    if out_scale_alpha:
+        out, abs_out = out * a_row, abs_out * np.abs(a_row)
+    return dict(neigh=neigh, abs_neigh=abs_neigh, out=out, abs_out=abs_out, n_terms=n_terms, row_factor=f, pre_relu=pre_relu)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -171,10 +194,15 @@ def bwd_src_units(mode: int) -> dict:
 BWD_ALPHA_UNITS = dict(S=U_VAL, dalpha_row=U_VAL * U_SCALE, dself_row=U_SCALE)
 
 
-def fwd_units(mode: int) -> dict:
+def fwd_units(mode: int, out_scale_alpha: bool = False, max_deg: Optional[int] = None) -> dict:
+    """Lattice units of K1's sums.  ``out``: edge sum x row scale and the self term, times the row factor - U_SCALE, or
+    1 / (max_deg + 1) when the kernel derives the factor from the row length (``inv_deg=None`` on rows whose length + 1 is a
+    power of two: every factor is a multiple of the smallest); the integer bias is a multiple of either; the post-scale by
+    alpha[row] halves the unit."""
     u_n = U_VAL * (U_ALPHA if mode == SRC_IS_GENE else 1.0)
     u_pre = min(u_n * (U_ALPHA if mode == DST_IS_GENE else 1.0), U_ALPHA)
-    return dict(neigh=u_n, out=u_pre * U_SCALE)
+    u_out = u_pre * (U_SCALE if max_deg is None else 1.0 / (max_deg + 1))
+    return dict(neigh=u_n, out=u_out * (U_ALPHA if out_scale_alpha else 1.0))
 
 
 def check_bwd_src_budget(ref: dict, mode: int, prior_dh=None, prior_dalpha=None) -> dict:
@@ -195,8 +223,8 @@ def check_bwd_alpha_budget(ref: dict) -> dict:
     return out
 
 
-def check_fwd_budget(ref: dict, mode: int) -> dict:
-    u = fwd_units(mode)
+def check_fwd_budget(ref: dict, mode: int, out_scale_alpha: bool = False, max_deg: Optional[int] = None) -> dict:
+    u = fwd_units(mode, out_scale_alpha, max_deg)
     return dict(neigh=lattice_budget(ref["abs_neigh"], u["neigh"]), out=lattice_budget(ref["abs_out"], u["out"]))
 
 
