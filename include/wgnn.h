@@ -1436,6 +1436,46 @@ int wgnn_louvain_modularity(const int64_t* rowptr, const int32_t* col, const int
                             const int32_t* label, const int64_t* tot, int64_t* stats, uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * The refinement of a deterministic, synchronous, integer Leiden (additive exports, WGNN_VERSION stays 206): the kernels that
+ * ops.leiden_graph / api.ResidentPredictor.leiden add to the Louvain ones above.  Graph, resolution, M, m_den, deg, the guard
+ * M * M * max(num, den) < 2^62 and the total orders are wgnn_louvain_sweep's; no floating point, no random number.
+ *     P   int32 [n] : the partition the moving phase left (ids in [0, n)); totP int64 [n] = the sum of deg over P == c
+ *     ref int32 [n] : the refined partition inside P.  A refined community's id is the id of the vertex that founded it, so
+ *         P[ref[v]] == P[v]; the refinement starts from ref = identity.  tot / size int64 / int32 [n]: wgnn_louvain_apply's of ref
+ *   wgnn_leiden_boundary: kinP[v] = the sum of w(v, u) over the stored u != v with P[u] == P[v] (kinP may be NULL: not wanted);
+ *     ext[S] = the sum of w(u, x) over the stored off-diagonal entries with ref[u] == S, P[x] == P[u] and ref[x] != S (zeroed
+ *     first; one 64-bit integer atomic per row).
+ *   wgnn_leiden_refine_sweep: every vertex reads the state before the sweep.  v MAY MOVE iff size[ref[v]] == 1 and
+ *         kinP[v] * m_den >= num * deg[v] * (totP[P[v]] - deg[v])
+ *     kin[S] = the sum of w(v, u) over u != v with P[u] == P[v] and ref[u] == S;  score(S) = kin[S] * m_den - num * deg[v] * tot[S].
+ *     S != ref[v] is admissible iff (sweep even: S < ref[v]; odd: S > ref[v]),
+ *         ext[S] * m_den >= num * tot[S] * (totP[P[v]] - tot[S])
+ *     and score(S) > 0.  prop[v] = the admissible S that is best under (higher score, lower id), gain[v] = its score; a vertex
+ *     that may not move or has no admissible S leaves prop[v] = ref[v], gain[v] = 0.  ext, tot and kinP are at most M, so every
+ *     product stays below 2^62.  heavy, wave_rows, block_rows, the workspace (wgnn_louvain_sweep_workspace_bytes; ZERO on entry,
+ *     zero again on return) and scratch_blocks are wgnn_louvain_sweep's: the same tables, the same three routes, no bit changed.
+ *   wgnn_leiden_accept: next[v] = prop[v] iff prop[prop[v]] == prop[v] - the vertex whose id is the target's label stays at
+ *     home - else next[v] = ref[v] and gain[v] = 0.  stats[0] = how many vertices have next != ref (set, not added to).  An
+ *     accepted target keeps every member it had and every vertex that joins it is adjacent to one of them, so a refined
+ *     community is connected.  Runs behind the sweep on the same stream with no read-back between them.
+ *   stats int64 [4] as above; the status word takes the WGNN_LOUVAIN_* bits and
+ * ------------------------------------------------------------------------- */
+#define WGNN_LEIDEN_BAD_PARTITION  64   /* a ref / P id outside [0, n), or a ref label whose founder lies in another P-community */
+/* Errors, before any launch: as for the Louvain entries.  No kernel reads or writes out of bounds on a malformed graph or
+ * partition: an id outside [0, n) is skipped and reported. */
+int wgnn_leiden_boundary(const int64_t* rowptr, const int32_t* col, const int32_t* w, int64_t n, int64_t nnz,
+                         const int32_t* P, const int32_t* ref, int64_t* ext, int64_t* kinP, int64_t* stats,
+                         uint32_t flags, void* stream);
+int wgnn_leiden_refine_sweep(const int64_t* rowptr, const int32_t* col, const int32_t* w, int64_t n, int64_t nnz,
+                             const int32_t* P, const int32_t* ref, const int64_t* deg, const int64_t* totP,
+                             const int64_t* tot, const int32_t* size, const int64_t* ext, const int64_t* kinP,
+                             int64_t m_den, int64_t num, int32_t sweep, const int32_t* heavy, int32_t n_heavy,
+                             int32_t wave_rows, int32_t block_rows, int32_t* prop, int64_t* gain, int64_t* stats,
+                             void* workspace, int64_t workspace_bytes, int32_t scratch_blocks, uint32_t flags, void* stream);
+int wgnn_leiden_accept(const int32_t* ref, const int32_t* prop, int64_t n, int32_t* next, int64_t* gain, int64_t* stats,
+                       uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * The fuzzy kNN graph and a synchronous 2-D layout (additive exports, WGNN_VERSION stays 206): the kernels behind
  * ops.fuzzy_graph / ops.layout_graph / api.ResidentPredictor.umap.  Every floating-point operation named here is rounded on its
  * own (no fused multiply-add), every sum runs in the stated order and nothing depends on the grid: two calls give the same bits.

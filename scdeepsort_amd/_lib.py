@@ -34,6 +34,7 @@ KMEANS_MAX_K = 4096                # wgnn_kmeans_seed's limit (include/wgnn.h); 
 SILHOUETTE_MAX_GROUPS, SILHOUETTE_MAX_SPLITS = 4096, 64      # wgnn_silhouette_rows' limits (include/wgnn.h); D as wgnn_knn_rows
 SNN_MAX_K, SNN_IDX_I64 = 64, 256   # wgnn_snn_weights' limit and flag (include/wgnn.h)
 LOUVAIN_UNSORTED, LOUVAIN_BAD_COL, LOUVAIN_BAD_ROWPTR, LOUVAIN_NO_SCRATCH, LOUVAIN_BAD_LABEL, LOUVAIN_BAD_WEIGHT = 1, 2, 4, 8, 16, 32
+LEIDEN_BAD_PARTITION = 64          # the bit the wgnn_leiden_* entries add to the WGNN_LOUVAIN_* status bits (include/wgnn.h)
 LOUVAIN_WAVE_ROWS, LOUVAIN_BLOCK_ROWS, LOUVAIN_SCRATCH_BLOCKS = 128, 2048, 256      # wgnn_louvain_sweep's largest routes (include/wgnn.h)
 FUZZY_MAX_K, FUZZY_IDX_I64 = 64, 256       # wgnn_fuzzy_rows' / wgnn_fuzzy_union's limit and flag (include/wgnn.h)
 LAYOUT_LANES, LAYOUT_MAX_EPOCHS, LAYOUT_MAX_NEG = 16, 10000, 64      # wgnn_layout_epoch's sum order and limits (include/wgnn.h)
@@ -149,6 +150,10 @@ SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _i64, _i32, _u32, _vp]),
     "wgnn_louvain_apply": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_louvain_modularity": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_leiden_boundary": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_leiden_refine_sweep": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32,
+                                           _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _u32, _vp]),
+    "wgnn_leiden_accept": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_fuzzy_rows": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, C.c_double, _vp, _vp, _vp, _u32, _vp]),
     "wgnn_fuzzy_union": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _u32, _vp]),
     "wgnn_layout_init": (C.c_int, [_vp, _i64, _u32, _u32, _vp]),

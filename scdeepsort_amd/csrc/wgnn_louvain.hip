@@ -10,27 +10,19 @@
 //   - rows of at most wave_rows (<= 128) entries: one wavefront (a workgroup of 64 threads), an LDS table of 256 slots;
 //   - rows of at most block_rows (<= 2048) entries: a workgroup of 256 threads, an LDS table of 4096 slots;
 //   - longer rows (a hub cell): a workgroup with a dense int32 scratch per community in global memory, zero before and after.
-// Tables are open addressing, a compare-and-swap on the key and an integer add on the value; at most half full.
+// Tables are open addressing, a compare-and-swap on the key and an integer add on the value; at most half full
+// (wgnn_graph_tables.h, shared with wgnn_leiden.hip).
 //
 // wgnn_louvain_apply: tot / size of an assignment by 64-bit integer atomics, and how many vertices moved.
 // wgnn_louvain_modularity: IN (the stored weight inside communities, the diagonal included) and sum tot^2, and the checks of the
 // CSR that need the entries (status bits).
-#include <limits.h>
-#include "wgnn_common.h"
+#include "wgnn_graph_tables.h"
 
 namespace {
 using namespace wgnn;
+using namespace wgnn::graph;
 
 constexpr int kSnnMaxK = 64;
-constexpr int kWaveSlots = 256, kWaveRows = 128;
-constexpr int kBlockSlots = 4096, kBlockRows = 2048;
-constexpr int kMaxBlocks = 8192;
-constexpr int kMaxScratchBlocks = 256;
-
-typedef long long i64;
-typedef unsigned long long u64;
-
-__device__ __forceinline__ i64 clampl(i64 v, i64 hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 struct GArgs {
@@ -80,8 +72,6 @@ struct LArgs {
     int* scratch; int scratch_blocks;
 };
 
-struct Best { i64 score; int c; };
-
 // the community of neighbour u of v for kin: -1 for the diagonal, for a column or a community id outside [0, n)
 __device__ __forceinline__ int kin_comm(const LArgs& a, long v, int u) {
     if (u == v || (unsigned long)(unsigned)u >= (unsigned long)a.n) return -1;
@@ -105,41 +95,6 @@ __device__ __forceinline__ void consider(Best& b, const LArgs& a, int C, i64 kin
     if (s <= score_own) return;
     if (b.c < 0 || s > b.score || (s == b.score && C < b.c)) { b.score = s; b.c = C; }
 }
-__device__ __forceinline__ void merge(Best& b, i64 score, int c) {
-    if (c >= 0 && (b.c < 0 || score > b.score || (score == b.score && c < b.c))) { b.score = score; b.c = c; }
-}
-__device__ __forceinline__ void wave_best(Best& b) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const i64 so = __shfl_xor(b.score, off, 64);
-        const int co = __shfl_xor(b.c, off, 64);
-        merge(b, so, co);
-    }
-}
-
-template <int SLOTS>
-__device__ __forceinline__ int slot_of(int C) { return (int)(((unsigned)C * 2654435761u) >> 16) & (SLOTS - 1); }
-
-template <int SLOTS>
-__device__ __forceinline__ void table_add(int* keys, int* vals, int C, int w) {
-    int s = slot_of<SLOTS>(C);
-    for (;;) {
-        const int seen = atomicCAS(&keys[s], -1, C);
-        if (seen == -1 || seen == C) { atomicAdd(&vals[s], w); return; }
-        s = (s + 1) & (SLOTS - 1);
-    }
-}
-template <int SLOTS>
-__device__ __forceinline__ int table_get(const int* keys, const int* vals, int C) {
-    int s = slot_of<SLOTS>(C);
-    for (;;) {
-        const int seen = keys[s];
-        if (seen == C) return vals[s];
-        if (seen == -1) return 0;
-        s = (s + 1) & (SLOTS - 1);
-    }
-}
-
 // one vertex by the THREADS threads of a workgroup through an LDS table of SLOTS slots (the row has at most SLOTS / 2 entries)
 template <int THREADS, int SLOTS>
 __device__ __forceinline__ Best vertex_in_lds(const LArgs& a, long v, i64 e0, i64 e1, int* keys, int* vals, i64* score_own_out) {
@@ -246,16 +201,6 @@ __global__ void __launch_bounds__(256) sweep_heavy_kernel(const LArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// the sum of v over the workgroup's 256 threads, in thread 0 (integers: the order is free)
-__device__ __forceinline__ i64 block_sum(i64 v, i64* s_red) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
-
 struct AArgs { const int* old_label; const int* label; const i64* deg; long n; u64* tot; int* size; u64* stats; };
 
 __global__ void __launch_bounds__(256) apply_kernel(const AArgs a) {
@@ -305,19 +250,6 @@ __global__ void __launch_bounds__(256) tot2_kernel(const MArgs a) {
     sum = block_sum(sum, s_red);
     if (threadIdx.x == 0 && sum) atomicAdd(&a.stats[2], (u64)sum);
 }
-
-unsigned grid_for(int64_t items, int per_block) {
-    const int64_t want = (items + per_block - 1) / per_block;
-    return (unsigned)(want < 1 ? 1 : (want < kMaxBlocks ? want : kMaxBlocks));
-}
-
-const char* check_graph_sizes(int64_t n, int64_t nnz) {
-    if (n < 0 || n > INT32_MAX) return "n must be in [0, 2^31)";
-    if (nnz < 0) return "nnz must not be negative";
-    return nullptr;
-}
-
-int64_t scratch_bytes(int64_t n, int32_t scratch_blocks) { return n * 4 * (int64_t)scratch_blocks; }
 
 }  // namespace
 

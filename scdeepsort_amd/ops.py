@@ -2474,6 +2474,149 @@ def louvain_resolution(resolution):
     return frac
 
 
+class _GraphRun:
+    """What ``louvain_graph`` and ``leiden_graph`` share: the argument checks, a level's state on the device, the apply / modularity
+    pair with its one read-back, the moving phase, the aggregation and the final ids."""
+
+    def __init__(self, name, rowptr, col, w, resolution, max_sweeps, wave_rows, block_rows, scratch_blocks):
+        self.name = name
+        self.dev = dev = _require_cuda(rowptr, col, w)
+        max_sweeps, wave_rows, block_rows, scratch_blocks = int(max_sweeps), int(wave_rows), int(block_rows), int(scratch_blocks)
+        if max_sweeps < 1:
+            raise ValueError(f"{name}: max_sweeps = {max_sweeps} must be >= 1")
+        if not 0 <= wave_rows <= LOUVAIN_WAVE_ROWS or not 0 <= block_rows <= LOUVAIN_BLOCK_ROWS or \
+                not 1 <= scratch_blocks <= LOUVAIN_SCRATCH_BLOCKS:
+            raise ValueError(f"{name}: wave_rows in [0, {LOUVAIN_WAVE_ROWS}], block_rows in [0, {LOUVAIN_BLOCK_ROWS}] and scratch_blocks in "
+                             f"[1, {LOUVAIN_SCRATCH_BLOCKS}], got {wave_rows}, {block_rows}, {scratch_blocks}")
+        if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
+                w.dtype != torch.int32 or w.shape != col.shape:
+            raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and w int32 [nnz] are expected")
+        self.max_sweeps, self.wave_rows, self.block_rows, self.scratch_blocks = max_sweeps, wave_rows, block_rows, scratch_blocks
+        self.frac = frac = louvain_resolution(resolution)
+        self.num, self.den = num, den = frac.numerator, frac.denominator
+        self.B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+        if self.B >= 2 ** 31:
+            raise ValueError(f"{name}: B must be below 2^31")
+        self.rowptr, self.col, self.w = rowptr.contiguous(), col.contiguous(), w.contiguous()
+        self.M = M = int(w.sum(dtype=torch.int64)) if nnz else 0
+        if M * M * max(num, den) >= 2 ** 62:
+            raise ValueError(f"{name}: M * M * max(num, den) = {M * M * max(num, den)} >= 2^62 (M = {M}, resolution {frac}): the "
+                             "integer gains would not fit 64 bits")
+        if self.B and (int(rowptr[0]) != 0 or int(rowptr[-1]) != nnz):
+            raise WgnnError(f"{name}: rowptr does not run from 0 to nnz = {nnz}")
+        self.ids = torch.arange(self.B, dtype=torch.int64, device=dev)
+        self.isolated = rowptr[1:] == rowptr[:-1]
+        self.stream = _stream(dev)
+        self.stats = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.status = _LOUVAIN_STATUS
+        self.trace, self.converged, self.first = None, True, True
+
+    def level(self):
+        """The state of the level whose graph is ``rowptr`` / ``col`` / ``w``: its rows, degrees, long rows and scratch."""
+        dev, name = self.dev, self.name
+        self.n, self.nnz = int(self.rowptr.shape[0]) - 1, int(self.col.shape[0])
+        n, nnz = self.n, self.nnz
+        self.graph = (self.rowptr, self.col, self.w)
+        lens = self.rowptr[1:] - self.rowptr[:-1]
+        self.row = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), lens, output_size=nnz)
+        if self.first and bool((self.row == self.col).any()):
+            raise ValueError(f"{name}: the graph holds a self loop")
+        self.first = False
+        self.deg = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, self.row, self.w.to(torch.int64))
+        self.heavy = torch.nonzero(lens > self.wave_rows).reshape(-1).to(torch.int32)
+        self.n_heavy = int(self.heavy.shape[0])
+        self.n_scratch = min(self.scratch_blocks, int((lens > self.block_rows).sum())) if self.n_heavy else 0
+        self.ws, self.ws_bytes = (None, 0)
+        if self.n_scratch:                                          # zero on entry; the kernels leave it zero
+            self.ws_bytes = _workspace_bytes("wgnn_louvain_sweep_workspace_bytes", n, self.n_scratch)
+            self.ws = torch.zeros(self.ws_bytes // 4, dtype=torch.int32, device=dev)
+
+    def routes(self):
+        """The operands of the sweep kernels that say which route serves which row."""
+        return (_ptr(self.heavy) if self.n_heavy else None, self.n_heavy, self.wave_rows, self.block_rows)
+
+    def scratch(self):
+        return (_ptr(self.ws) if self.n_scratch else None, self.ws_bytes, self.n_scratch)
+
+    def measure(self, old, label):
+        """tot / size of ``label`` and ``(moved, Qnum)``: apply, modularity and the one read-back."""
+        dev, n, graph, stats = self.dev, self.n, self.graph, self.stats
+        tot, size = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        _lib.run(dev, "wgnn_louvain_apply", _ptr(old), _ptr(label), _ptr(self.deg), n, _ptr(tot), _ptr(size), _ptr(stats), 0,
+                 self.stream)
+        _lib.run(dev, "wgnn_louvain_modularity", _ptr(graph[0]), _ptr(graph[1]), _ptr(graph[2]), n, int(graph[1].shape[0]),
+                 _ptr(label), _ptr(tot), _ptr(stats), 0, self.stream)
+        moved, inside, tot2, status = (int(v) for v in stats.tolist())
+        _check_status(self.name, status, self.status)
+        return tot, size, moved, self.den * self.M * inside - self.num * tot2
+
+    def move(self, comm):
+        """The moving phase of a level from the partition ``comm``: ``(comm, tot, sweeps, fallback moves)``; the trace grows."""
+        dev, name, n, nnz, trace = self.dev, self.name, self.n, self.nnz, self.trace
+        rowptr, col, w = self.graph
+        tot, size, _, q = self.measure(None, comm)                  # the start's state, and the graph's checks
+        if trace is None:
+            self.trace = trace = [q]
+        elif q != trace[-1]:                                        # aggregation keeps the partition, so Qnum too
+            raise WgnnError(f"{name}: Qnum changed across the aggregation ({trace[-1]} -> {q})")
+        t = idle = fallback = 0
+        while True:
+            if t >= self.max_sweeps:
+                self.converged = False
+                break
+            nxt = torch.empty(n, dtype=torch.int32, device=dev)
+            gain = torch.empty(n, dtype=torch.int64, device=dev)
+            _lib.run(dev, "wgnn_louvain_sweep", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(comm), _ptr(self.deg), _ptr(tot),
+                     _ptr(size), self.M * self.den, self.num, t, *self.routes(), _ptr(nxt), _ptr(gain), _ptr(self.stats),
+                     *self.scratch(), 0, self.stream)
+            tot2, size2, moved, q = self.measure(comm, nxt)
+            t += 1
+            if moved == 0:
+                idle += 1
+                if idle == 2:
+                    break
+                continue
+            idle = 0
+            if q > trace[-1]:
+                comm, tot, size = nxt, tot2, size2
+            else:                                                   # discarded: the single best move, ties to the lowest vertex
+                v = int(torch.nonzero(gain == gain.max()).reshape(-1)[0])
+                one = comm.clone()
+                one[v] = nxt[v]
+                tot, size, _, q = self.measure(comm, one)
+                if q <= trace[-1]:
+                    raise WgnnError(f"{name}: a single positive-gain move did not raise Qnum ({trace[-1]} -> {q}): the graph is "
+                                    "not symmetric")
+                comm = one
+                fallback += 1
+            trace.append(q)
+        return comm, tot, t, fallback
+
+    def coarsen(self, inv, nc):
+        """The next level's graph: the ``nc`` communities ``inv`` (dense ids per vertex) as vertices, their internal weight on
+        the diagonal."""
+        dev = self.dev
+        key, kinv = torch.unique(inv[self.row] * nc + inv[self.col.long()], return_inverse=True)
+        self.w = torch.zeros(key.shape[0], dtype=torch.int64, device=dev).index_add_(0, kinv, self.w.to(torch.int64)).to(torch.int32)
+        crow = torch.div(key, nc, rounding_mode="floor")
+        self.col = (key - crow * nc).to(torch.int32)
+        self.rowptr = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(crow, minlength=nc), 0, out=self.rowptr[1:])
+
+    def clusters(self, member):
+        """Final ids: by descending size, ties by the lowest member; a vertex without an edge has none."""
+        B, dev, ids = self.B, self.dev, self.ids
+        on = ~self.isolated
+        cluster = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        uniq, inv, count = torch.unique(member[on], return_inverse=True, return_counts=True)
+        first = torch.full((int(uniq.shape[0]),), B, dtype=torch.int64, device=dev).scatter_reduce_(0, inv, ids[on], "amin")
+        order = torch.argsort((B - count) * B + first)
+        rank = torch.empty_like(order)
+        rank[order] = torch.arange(order.shape[0], dtype=torch.int64, device=dev)
+        cluster[on] = rank[inv]
+        return cluster
+
+
 def louvain_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, resolution=1.0, max_sweeps: int = 256,
                   wave_rows: int = LOUVAIN_WAVE_ROWS, block_rows: int = LOUVAIN_BLOCK_ROWS, scratch_blocks: int = 32) -> LouvainRows:
     """Louvain communities of a symmetric CSR graph with int32 weights and no self loops (``rowptr`` int64 [B + 1], ``col`` int32
@@ -2491,101 +2634,16 @@ def louvain_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, reso
     restarts.  ``wave_rows`` (<= 128), ``block_rows`` (<= 2048) and ``scratch_blocks`` (1..256) bound the three routes of the sweep
     kernel by row length and change no bit; two calls are bit-identical.  CPU tensors raise ``WgnnError``; argument errors are
     ``ValueError``; a malformed graph (unsorted rows, columns out of range) raises ``WgnnError``.  Returns a ``LouvainRows``."""
-    name = "louvain_graph"
-    dev = _require_cuda(rowptr, col, w)
-    max_sweeps, wave_rows, block_rows, scratch_blocks = int(max_sweeps), int(wave_rows), int(block_rows), int(scratch_blocks)
-    if max_sweeps < 1:
-        raise ValueError(f"{name}: max_sweeps = {max_sweeps} must be >= 1")
-    if not 0 <= wave_rows <= LOUVAIN_WAVE_ROWS or not 0 <= block_rows <= LOUVAIN_BLOCK_ROWS or \
-            not 1 <= scratch_blocks <= LOUVAIN_SCRATCH_BLOCKS:
-        raise ValueError(f"{name}: wave_rows in [0, {LOUVAIN_WAVE_ROWS}], block_rows in [0, {LOUVAIN_BLOCK_ROWS}] and scratch_blocks in "
-                         f"[1, {LOUVAIN_SCRATCH_BLOCKS}], got {wave_rows}, {block_rows}, {scratch_blocks}")
-    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
-            w.dtype != torch.int32 or w.shape != col.shape:
-        raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and w int32 [nnz] are expected")
-    frac = louvain_resolution(resolution)
-    num, den = frac.numerator, frac.denominator
-    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
-    if B >= 2 ** 31:
-        raise ValueError(f"{name}: B must be below 2^31")
-    rowptr, col, w = rowptr.contiguous(), col.contiguous(), w.contiguous()
-    M = int(w.sum(dtype=torch.int64)) if nnz else 0
-    if M * M * max(num, den) >= 2 ** 62:
-        raise ValueError(f"{name}: M * M * max(num, den) = {M * M * max(num, den)} >= 2^62 (M = {M}, resolution {frac}): the "
-                         "integer gains would not fit 64 bits")
-    if B and (int(rowptr[0]) != 0 or int(rowptr[-1]) != nnz):
-        raise WgnnError(f"{name}: rowptr does not run from 0 to nnz = {nnz}")
-    ids = torch.arange(B, dtype=torch.int64, device=dev)
-    if M == 0:
-        return LouvainRows(torch.full((B,), -1, dtype=torch.int64, device=dev), [ids],
-                           [dict(vertices=B, communities=B, sweeps=0, fallback_moves=0)], [0], 0.0, frac, 0, True)
-    isolated = rowptr[1:] == rowptr[:-1]
-    stream = _stream(dev)
-    stats = torch.zeros(4, dtype=torch.int64, device=dev)
-
-    def measure(n, graph, old, label, deg):
-        """tot / size of ``label`` and ``(moved, Qnum)``: apply, modularity and the one read-back."""
-        tot, size = torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
-        _lib.run(dev, "wgnn_louvain_apply", _ptr(old), _ptr(label), _ptr(deg), n, _ptr(tot), _ptr(size), _ptr(stats), 0, stream)
-        _lib.run(dev, "wgnn_louvain_modularity", _ptr(graph[0]), _ptr(graph[1]), _ptr(graph[2]), n, int(graph[1].shape[0]),
-                 _ptr(label), _ptr(tot), _ptr(stats), 0, stream)
-        moved, inside, tot2, status = (int(v) for v in stats.tolist())
-        _check_status(name, status, _LOUVAIN_STATUS)
-        return tot, size, moved, den * M * inside - num * tot2
-
-    member, trace, levels, level_labels, converged = ids, None, [], [], True
+    run = _GraphRun("louvain_graph", rowptr, col, w, resolution, max_sweeps, wave_rows, block_rows, scratch_blocks)
+    B, dev = run.B, run.dev
+    if run.M == 0:
+        return LouvainRows(torch.full((B,), -1, dtype=torch.int64, device=dev), [run.ids],
+                           [dict(vertices=B, communities=B, sweeps=0, fallback_moves=0)], [0], 0.0, run.frac, 0, True)
+    member, levels, level_labels = run.ids, [], []
     while True:
-        n, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
-        graph = (rowptr, col, w)
-        lens = rowptr[1:] - rowptr[:-1]
-        row = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), lens, output_size=nnz)
-        if trace is None and bool((row == col).any()):
-            raise ValueError(f"{name}: the graph holds a self loop")
-        deg = torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, row, w.to(torch.int64))
-        comm = torch.arange(n, dtype=torch.int32, device=dev)
-        heavy = torch.nonzero(lens > wave_rows).reshape(-1).to(torch.int32)
-        n_heavy = int(heavy.shape[0])
-        n_scratch = min(scratch_blocks, int((lens > block_rows).sum())) if n_heavy else 0
-        ws, ws_bytes = (None, 0)
-        if n_scratch:                                               # zero on entry; the kernel leaves it zero
-            ws_bytes = _workspace_bytes("wgnn_louvain_sweep_workspace_bytes", n, n_scratch)
-            ws = torch.zeros(ws_bytes // 4, dtype=torch.int32, device=dev)
-        tot, size, _, q = measure(n, graph, None, comm, deg)       # the singletons' state, and the graph's checks
-        if trace is None:
-            trace = [q]
-        elif q != trace[-1]:                                        # aggregation keeps the partition, so Qnum too
-            raise WgnnError(f"{name}: Qnum changed across the aggregation ({trace[-1]} -> {q})")
-        t = idle = fallback = 0
-        while True:
-            if t >= max_sweeps:
-                converged = False
-                break
-            nxt = torch.empty(n, dtype=torch.int32, device=dev)
-            gain = torch.empty(n, dtype=torch.int64, device=dev)
-            _lib.run(dev, "wgnn_louvain_sweep", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(comm), _ptr(deg), _ptr(tot),
-                     _ptr(size), M * den, num, t, _ptr(heavy) if n_heavy else None, n_heavy, wave_rows, block_rows, _ptr(nxt),
-                     _ptr(gain), _ptr(stats), _ptr(ws) if n_scratch else None, ws_bytes, n_scratch, 0, stream)
-            tot2, size2, moved, q = measure(n, graph, comm, nxt, deg)
-            t += 1
-            if moved == 0:
-                idle += 1
-                if idle == 2:
-                    break
-                continue
-            idle = 0
-            if q > trace[-1]:
-                comm, tot, size = nxt, tot2, size2
-            else:                                                   # discarded: the single best move, ties to the lowest vertex
-                v = int(torch.nonzero(gain == gain.max()).reshape(-1)[0])
-                one = comm.clone()
-                one[v] = nxt[v]
-                tot, size, _, q = measure(n, graph, comm, one, deg)
-                if q <= trace[-1]:
-                    raise WgnnError(f"{name}: a single positive-gain move did not raise Qnum ({trace[-1]} -> {q}): the graph is "
-                                    "not symmetric")
-                comm = one
-                fallback += 1
-            trace.append(q)
+        run.level()
+        n = run.n
+        comm, _, t, fallback = run.move(torch.arange(n, dtype=torch.int32, device=dev))
         uniq, inv = torch.unique(comm, return_inverse=True)         # dense ids in ascending order of the old ones
         nc = int(uniq.shape[0])
         member = inv[member]
@@ -2593,22 +2651,149 @@ def louvain_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, reso
         level_labels.append(member)
         if nc == n:
             break
-        key, kinv = torch.unique(inv[row] * nc + inv[col.long()], return_inverse=True)
-        w = torch.zeros(key.shape[0], dtype=torch.int64, device=dev).index_add_(0, kinv, w.to(torch.int64)).to(torch.int32)
-        crow = torch.div(key, nc, rounding_mode="floor")
-        col = (key - crow * nc).to(torch.int32)
-        rowptr = torch.zeros(nc + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(torch.bincount(crow, minlength=nc), 0, out=rowptr[1:])
-    # final ids: by descending size, ties by the lowest member; a vertex without an edge has none
-    on = ~isolated
-    cluster = torch.full((B,), -1, dtype=torch.int64, device=dev)
-    uniq, inv, count = torch.unique(member[on], return_inverse=True, return_counts=True)
-    first = torch.full((int(uniq.shape[0]),), B, dtype=torch.int64, device=dev).scatter_reduce_(0, inv, ids[on], "amin")
-    order = torch.argsort((B - count) * B + first)
-    rank = torch.empty_like(order)
-    rank[order] = torch.arange(order.shape[0], dtype=torch.int64, device=dev)
-    cluster[on] = rank[inv]
-    return LouvainRows(cluster, level_labels, levels, trace, trace[-1] / (den * M * M), frac, M, converged)
+        run.coarsen(inv, nc)
+    trace = run.trace
+    return LouvainRows(run.clusters(member), level_labels, levels, trace, trace[-1] / (run.den * run.M * run.M), run.frac, run.M,
+                       run.converged)
+
+
+class LeidenRows(NamedTuple):
+    """What ``leiden_graph`` returns: ``LouvainRows``' fields and ``refined_labels``.  ``level_labels[l]`` is the partition ``P``
+    the moving phase of level ``l`` left, per original vertex and dense; one more entry follows when the final cut split a
+    community into its connected components (``levels[-1]["split"]`` > 0), and ``cluster`` is the last entry's ids by descending
+    size.  ``refined_labels[l]`` is level ``l``'s refined partition (dense, in ascending order of the founders' ids): the next
+    level's vertices.  Each ``levels[l]`` adds ``refined`` (how many refined communities), ``refine_sweeps`` and
+    ``refine_fallback_moves``; the last adds ``split`` (how many communities the final cut added).  ``qnum_trace`` holds the moving
+    phases' entries and the final cut's; the refinement keeps a running value of its own."""
+    cluster: torch.Tensor
+    level_labels: list
+    refined_labels: list
+    levels: list
+    qnum_trace: list
+    modularity: float
+    resolution: object
+    M: int
+    converged: bool
+
+
+_LEIDEN_STATUS = _LOUVAIN_STATUS + ((_lib.LEIDEN_BAD_PARTITION, "a refined or moved id is outside [0, n), or a refined community's "
+                                                                "founder lies in another community"),)
+
+
+def _leiden_refine(run: _GraphRun, P: torch.Tensor, totP: torch.Tensor):
+    """The refinement of one level inside the partition ``P``: ``(ref, sweeps, fallback moves)``.  Per sweep five launches
+    (boundary, refine sweep, accept, apply, modularity) and one read-back."""
+    dev, name, n, nnz, stats, stream = run.dev, run.name, run.n, run.nnz, run.stats, run.stream
+    rowptr, col, w = run.graph
+    ref = torch.arange(n, dtype=torch.int32, device=dev)
+    tot, size, _, running = run.measure(None, ref)
+    ext = torch.empty(n, dtype=torch.int64, device=dev)
+    kinP = torch.empty(n, dtype=torch.int64, device=dev)
+    r = idle = fallback = 0
+    while True:
+        if r >= run.max_sweeps:
+            run.converged = False
+            break
+        prop, nxt = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        gain = torch.empty(n, dtype=torch.int64, device=dev)
+        _lib.run(dev, "wgnn_leiden_boundary", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(P), _ptr(ref), _ptr(ext),
+                 _ptr(kinP) if r == 0 else None, _ptr(stats), 0, stream)                     # kinP depends on P alone
+        _lib.run(dev, "wgnn_leiden_refine_sweep", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(P), _ptr(ref), _ptr(run.deg),
+                 _ptr(totP), _ptr(tot), _ptr(size), _ptr(ext), _ptr(kinP), run.M * run.den, run.num, r, *run.routes(), _ptr(prop),
+                 _ptr(gain), _ptr(stats), *run.scratch(), 0, stream)
+        _lib.run(dev, "wgnn_leiden_accept", _ptr(ref), _ptr(prop), n, _ptr(nxt), _ptr(gain), _ptr(stats), 0, stream)
+        tot2, size2, moved, q = run.measure(ref, nxt)               # counts the accepted moves again: the one read-back
+        r += 1
+        if moved == 0:
+            idle += 1
+            if idle == 2:
+                break
+            continue
+        idle = 0
+        if q > running:
+            ref, tot, size = nxt, tot2, size2
+        else:                                                       # discarded: the single best accepted move, the lowest vertex
+            v = int(torch.nonzero(gain == gain.max()).reshape(-1)[0])
+            one = ref.clone()
+            one[v] = nxt[v]
+            tot, size, _, q = run.measure(ref, one)
+            if q <= running:
+                raise WgnnError(f"{name}: a single accepted move did not raise Qnum ({running} -> {q}): the graph is not symmetric")
+            ref = one
+            fallback += 1
+        running = q
+    return ref, r, fallback
+
+
+def _leiden_components(run: _GraphRun, P: torch.Tensor) -> torch.Tensor:
+    """The lowest vertex of every vertex's connected component inside its community of ``P``: min-label propagation over the
+    entries whose two ends share a community, on the device, until a round changes nothing (one read-back per round)."""
+    same = P[run.row] == P[run.col.long()]
+    r, c = run.row[same], run.col[same].long()
+    label = torch.arange(run.n, dtype=torch.int64, device=run.dev)
+    while True:
+        nxt = label.clone().scatter_reduce_(0, r, label[c], "amin")
+        if bool((nxt == label).all()):
+            return label.to(torch.int32)
+        label = nxt
+
+
+def leiden_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, resolution=1.0, max_sweeps: int = 256,
+                 wave_rows: int = LOUVAIN_WAVE_ROWS, block_rows: int = LOUVAIN_BLOCK_ROWS, scratch_blocks: int = 32) -> LeidenRows:
+    """Leiden communities of the graph ``louvain_graph`` takes, on the device and in integers: deterministic and synchronous, no
+    floating point and no random number, so two calls and every launch geometry give the same bits (``include/wgnn.h`` and
+    DESIGN.md section 3 have the contract).  What it buys over ``louvain_graph`` is that every community is connected; it does
+    not claim a higher modularity.
+
+    A level (1) runs ``louvain_graph``'s moving phase from the partition it inherited (singletons at level 0), which leaves
+    ``P``; (2) refines: from singletons, a vertex that is alone and well connected to its community of ``P`` proposes the best
+    well-connected refined community of its neighbours inside that community (``wgnn_leiden_boundary``,
+    ``wgnn_leiden_refine_sweep``), a proposal holds iff the founder of its target stays (``wgnn_leiden_accept``), and a sweep that
+    does not raise ``Qnum`` is discarded for its single best accepted move; (3) aggregates by the refined partition, the next
+    level starting from the refined communities grouped by ``P``.  A level whose refinement merges nothing ends the run, and the
+    last ``P`` is cut into its connected components.  ``max_sweeps`` bounds the moving phase and the refinement of a level each.
+    Arguments, refusals and errors are ``louvain_graph``'s.  Returns a ``LeidenRows``."""
+    run = _GraphRun("leiden_graph", rowptr, col, w, resolution, max_sweeps, wave_rows, block_rows, scratch_blocks)
+    run.status = _LEIDEN_STATUS
+    B, dev = run.B, run.dev
+    if run.M == 0:
+        return LeidenRows(torch.full((B,), -1, dtype=torch.int64, device=dev), [run.ids], [run.ids],
+                          [dict(vertices=B, communities=B, sweeps=0, fallback_moves=0, refined=B, refine_sweeps=0,
+                                refine_fallback_moves=0, split=0)], [0], 0.0, run.frac, 0, True)
+    member, levels, level_labels, refined_labels = run.ids, [], [], []
+    comm0 = torch.arange(B, dtype=torch.int32, device=dev)
+    while True:
+        run.level()
+        n = run.n
+        P, totP, t, fallback = run.move(comm0)
+        ref, r, r_fallback = _leiden_refine(run, P, totP)
+        dense_P = torch.unique(P, return_inverse=True)[1]
+        uniq, inv = torch.unique(ref, return_inverse=True)          # dense ids in ascending order of the founders' ids
+        nc = int(uniq.shape[0])
+        levels.append(dict(vertices=n, communities=int(dense_P.max()) + 1, sweeps=t, fallback_moves=fallback, refined=nc,
+                           refine_sweeps=r, refine_fallback_moves=r_fallback))
+        level_labels.append(dense_P[member])
+        refined_labels.append(inv[member])
+        if nc == n:
+            break
+        lowest = torch.full((n,), nc, dtype=torch.int64, device=dev).scatter_reduce_(0, P.long(), inv, "amin")
+        comm0 = torch.empty(nc, dtype=torch.int32, device=dev)
+        comm0[inv] = lowest[P.long()].to(torch.int32)               # the refined communities of one community of P start together
+        member = inv[member]
+        run.coarsen(inv, nc)
+    trace = run.trace
+    parts = _leiden_components(run, P)                              # the final cut: a coarse move can leave a community in pieces
+    uniq, dense_parts = torch.unique(parts, return_inverse=True)
+    split = int(uniq.shape[0]) - levels[-1]["communities"]
+    levels[-1]["split"] = split
+    if split:
+        _, _, _, q = run.measure(None, parts)
+        if q <= trace[-1]:
+            raise WgnnError(f"leiden_graph: the cut into connected components did not raise Qnum ({trace[-1]} -> {q})")
+        trace.append(q)
+        level_labels.append(dense_parts[member])
+    return LeidenRows(run.clusters(level_labels[-1]), level_labels, refined_labels, levels, trace,
+                      trace[-1] / (run.den * run.M * run.M), run.frac, run.M, run.converged)
 
 
 FUZZY_MAX_K = _lib.FUZZY_MAX_K            # wgnn_fuzzy_rows' limit

@@ -1994,7 +1994,7 @@ class CommunitiesSummary(dict):
         d = self
         how = "converged" if d["converged"] else "NOT converged (a level stopped at max_sweeps)"
         return "\n".join([
-            f"{d['n_cells']} cells in {d['n_clusters']} Louvain communities of the k = {d['k']} graph in the {d['space']} space "
+            f"{d['n_cells']} cells in {d['n_clusters']} {d.get('method', 'louvain').capitalize()} communities of the k = {d['k']} graph in the {d['space']} space "
             f"({d['metric']}, {d['weights']} weights), resolution {d['resolution']}, {how}; {d['n_skipped']} cells without an edge",
             f"{d['n_levels']} levels, {d['n_sweeps']} sweeps, {d['n_fallback']} fallback moves, modularity {d['modularity']:.4f}",
             f"community sizes {d['min_size']} .. {d['max_size']} (median {d['median_size']:.4g})",
@@ -2010,7 +2010,10 @@ class Communities(_CellClusters):
     ``silhouette``.  ``size`` int64 [K]; ``modularity``: ``Qnum / (den M^2)`` of the final cut at ``resolution`` (the ``Fraction``
     used); ``weights`` ("snn" | "unit"); ``level_labels``: one int64 [B] per level of the dendrogram (``at_level``), ``levels`` the
     per-level dicts of ``ops.louvain_graph``; ``converged``.  ``space`` / ``metric`` / ``k`` say which graph was cut; ``label``
-    int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure).  ``method``: "louvain", or "leiden" for what
+    ``ResidentPredictor.leiden`` returns - then every community is connected, ``levels`` are ``ops.leiden_graph``'s dicts,
+    ``level_labels`` its moving-phase partitions (and the final cut when it split something) and ``refined_labels`` its refined
+    partitions, one int64 [B] per level."""
     cluster: np.ndarray
     size: np.ndarray
     modularity: float
@@ -2027,6 +2030,8 @@ class Communities(_CellClusters):
     index: Sequence
     id2label: Sequence[str]
     label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+    method: str = "louvain"
+    refined_labels: Optional[Sequence[np.ndarray]] = field(default=None, repr=False)
 
     def at_level(self, level: int) -> np.ndarray:
         """int64 [B]: the cut after level ``level`` (0 = the finest, -1 = the final one), ids renumbered as ``cluster``'s are - by
@@ -2057,7 +2062,7 @@ class Communities(_CellClusters):
         size, purity = np.asarray(self.size, np.int64), self.purity()
         known = purity[~np.isnan(purity)]
         return CommunitiesSummary(n_cells=len(self.cluster), n_clusters=self.n_clusters, k=int(self.k), space=self.space,
-                                  metric=self.metric, weights=self.weights, resolution=str(self.resolution),
+                                  metric=self.metric, weights=self.weights, resolution=str(self.resolution), method=self.method,
                                   converged=bool(self.converged), n_skipped=int((np.asarray(self.cluster) < 0).sum()),
                                   n_levels=len(self.levels), n_sweeps=int(sum(l["sweeps"] for l in self.levels)),
                                   n_fallback=int(sum(l["fallback_moves"] for l in self.levels)), modularity=float(self.modularity),
