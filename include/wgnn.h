@@ -1532,6 +1532,40 @@ int wgnn_layout_epoch(const int64_t* rowptr, const int32_t* col, const float* w,
                       const float* y_in, float* y_out, int32_t epoch, int32_t n_epochs, float a, float b, float gamma,
                       float alpha, int32_t n_neg, uint32_t seed, int64_t* fired, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Geodesic distances on a graph (additive export, WGNN_VERSION stays 206): the kernel behind ops.geodesic_rows /
+ * api.ResidentPredictor.pseudotime - one round of a SYNCHRONOUS Bellman-Ford over float32 edge lengths.  The only floating-point
+ * operation is one float32 add per stored entry, rounded on its own; everything else is a comparison.  Nothing depends on the
+ * grid or on the order of the threads: two calls give the same bits, and numpy restates a round exactly.
+ *     rowptr int64 [n + 1], col int32 [nnz] strictly ascending within a row, length float32 [nnz] >= 0 and finite: a CSR that
+ *         stores both directions of every edge (ops.distance_graph's); row v lists the u that can hand v a distance
+ *     dist_in float32 [n] (+inf = not reached), pred_in int32 [n] (-1 = a root or not reached): the state before the round
+ *     dist_out, pred_out : the state after it - other buffers than dist_in / pred_in (the caller swaps them: ping-pong)
+ *   For every vertex v:  cand(u) = dist_in[u] + length(u, v) in float32 for every stored neighbour u whose dist_in[u] is finite;
+ *   best = the least under the total order (cand, u).  If best.cand < dist_in[v] (strictly) then dist_out[v] = best.cand and
+ *   pred_out[v] = best.u, else both are copied.  A vertex that is reached never loses its predecessor to an equal candidate, and
+ *   a round at the fixed point is the identity.
+ *   *changed (int64) += the number of vertices the round improved (one 64-bit integer atomic per wavefront that has any: the
+ *   caller hands every round of a batch its own zeroed slot and reads them back together); *status (int64) is only ever OR-ed
+ *   into (the caller zeroes it) with the bits below.  No atomic touches dist or pred.
+ *   WGNN_GEODESIC_LANES lanes serve a row - lane l its entries l, l + 16, ... - and fold their partial minima by halves; rows are
+ *   taken in a grid-stride loop by min(grid_blocks, ceil(n / 16)) workgroups of 256 (grid_blocks == 0: at most
+ *   WGNN_GEODESIC_MAX_BLOCKS).  The minimum of a total order is associative and commutative: neither changes a bit.
+ * ------------------------------------------------------------------------- */
+#define WGNN_GEODESIC_LANES        16   /* lanes per row                                                             */
+#define WGNN_GEODESIC_MAX_BLOCKS 8192   /* the largest grid                                                          */
+#define WGNN_GEODESIC_UNSORTED      1   /* a row is not strictly ascending in col                                    */
+#define WGNN_GEODESIC_BAD_COL       2   /* a column outside [0, n): the entry is skipped                             */
+#define WGNN_GEODESIC_BAD_ROWPTR    4   /* rowptr does not ascend from 0 to nnz: the row is clamped to [0, nnz]      */
+#define WGNN_GEODESIC_BAD_LENGTH    8   /* a negative, infinite or NaN length: the entry is skipped                  */
+/* Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand; n outside [0, 2^31); a negative nnz; grid_blocks outside
+ * [0, 8192]; dist_out == dist_in or pred_out == pred_in; any flag bit - none is defined), WGNN_ERR_ALIGNMENT (rowptr, changed or
+ * status not 8-byte, the others not 4-byte aligned); wgnn_last_error_string names the check.  n == 0 returns WGNN_OK without a
+ * launch.  No kernel reads or writes out of bounds on a malformed graph. */
+int wgnn_geodesic_round(const int64_t* rowptr, const int32_t* col, const float* length, int64_t n, int64_t nnz,
+                        const float* dist_in, const int32_t* pred_in, float* dist_out, int32_t* pred_out,
+                        int64_t* changed, int64_t* status, int32_t grid_blocks, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

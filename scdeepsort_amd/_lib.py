@@ -38,7 +38,9 @@ LEIDEN_BAD_PARTITION = 64          # the bit the wgnn_leiden_* entries add to th
 LOUVAIN_WAVE_ROWS, LOUVAIN_BLOCK_ROWS, LOUVAIN_SCRATCH_BLOCKS = 128, 2048, 256      # wgnn_louvain_sweep's largest routes (include/wgnn.h)
 FUZZY_MAX_K, FUZZY_IDX_I64 = 64, 256       # wgnn_fuzzy_rows' / wgnn_fuzzy_union's limit and flag (include/wgnn.h)
 LAYOUT_LANES, LAYOUT_MAX_EPOCHS, LAYOUT_MAX_NEG = 16, 10000, 64      # wgnn_layout_epoch's sum order and limits (include/wgnn.h)
-ABI_MAJOR = 2                # include/wgnn.h WGNN_VERSION / 100
+GEODESIC_UNSORTED, GEODESIC_BAD_COL, GEODESIC_BAD_ROWPTR, GEODESIC_BAD_LENGTH = 1, 2, 4, 8      # wgnn_geodesic_round's status bits
+GEODESIC_LANES, GEODESIC_MAX_BLOCKS = 16, 8192     # wgnn_geodesic_round's lanes per row and largest grid (include/wgnn.h)
+ABI_MAJOR = 2               # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
 _vp, _i32, _i64, _u32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_int
@@ -159,6 +161,7 @@ SIGNATURES = {
     "wgnn_layout_init": (C.c_int, [_vp, _i64, _u32, _u32, _vp]),
     "wgnn_layout_epoch": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_float, _vp, _vp, _i32, _i32, C.c_float, C.c_float, C.c_float,
                                     C.c_float, _i32, _u32, _vp, _u32, _vp]),
+    "wgnn_geodesic_round": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _u32, _vp]),
 }
 
 

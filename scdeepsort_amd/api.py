@@ -35,7 +35,8 @@ from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Communi
                      GeneRanks, GeneRanksSummary, KMeans, KMeansSummary, Layout, LayoutSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
                      Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Silhouette, SilhouetteSummary, Smoothed, SmoothedSummary, Stability,
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
-                     _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores)
+                     _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores,
+                     Abstraction, AbstractionSummary, Pseudotime, PseudotimeSummary, _paga_connectivities, _scaled_pseudotime)
 
 _tables._rows_topk = lambda *a: _ops.rows_topk(*a)      # MarkerTable.top's device route: tables.py itself imports no ops
 
@@ -2313,6 +2314,191 @@ class ResidentPredictor:
         out = self.umap(matrix, k=k, min_dist=min_dist, spread=spread, a=a, b=b, n_epochs=n_epochs, n_neg=n_neg, seed=seed,
                         init=init, genes=genes, normalize=normalize, space=space, metric=metric, index=index)
         return self._save_frame(out.coords_frame(), save_path, "umap")
+
+    # ---------------------------------------------------------------------------------------------
+    def _graph_lists(self, what, graph, B, k, space, metric, need_distances):
+        """``graph=`` of ``pseudotime`` / ``paga``: ``(lists | None, k, space, metric)`` - ``lists`` the host ``(indices,
+        sq_distances | None)`` of an earlier ``NeighborGraph`` of this batch (or, where no distances are needed, of a bare
+        ``[B, k]`` index array), whose own ``k`` / ``space`` / ``metric`` then replace the call's."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
+        if not 1 <= int(k) <= _ops.SNN_MAX_K:
+            raise ValueError(f"k = {k} is outside [1, {_ops.SNN_MAX_K}]")
+        if graph is None:
+            return None, int(k), space, metric
+        if need_distances and not isinstance(graph, NeighborGraph):
+            raise ValueError(f"graph must be a NeighborGraph: {what} needs the neighbours' distances, which a bare index array "
+                             "does not carry")
+        idx = np.asarray(graph.indices if isinstance(graph, NeighborGraph) else graph)
+        if idx.ndim != 2 or idx.shape[0] != B or not 1 <= idx.shape[1] <= _ops.SNN_MAX_K or idx.dtype.kind not in "iu":
+            raise ValueError(f"graph must be a NeighborGraph or an integer array [{B}, 1..{_ops.SNN_MAX_K}] of this batch")
+        d2 = None
+        if isinstance(graph, NeighborGraph):
+            space, metric = graph.space, graph.metric
+            d2 = np.asarray(graph.sq_distances)
+            if need_distances and d2.shape != idx.shape:
+                raise ValueError(f"graph must be a NeighborGraph of this batch: its distances are {d2.shape}, its lists {idx.shape}")
+        return (idx, d2), int(idx.shape[1]), space, metric
+
+    def _lists_on_device(self, vb, lists, k, space, metric):
+        """``(idx, d2)`` on the device: ``knn``'s search of the classified batch ``vb``, or the host ``lists`` of ``_graph_lists``."""
+        if lists is None:
+            rows = self._embed(vb.csr, space)
+            if metric == "cosine":
+                rows = F.normalize(rows, dim=1)
+            return _ops.knn_rows(rows, k)
+        idx = torch.as_tensor(lists[0].astype(np.int64), device=self.device)
+        return idx, None if lists[1] is None else torch.as_tensor(lists[1].astype(np.float32), device=self.device)
+
+    def pseudotime(self, expr, root, k: int = 15, genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                   graph=None, max_rounds: Optional[int] = None, index=None) -> Pseudotime:
+        """Order the cells of a batch along its own kNN graph: every cell's geodesic distance from ``root`` - the shortest path
+        over the graph's edges, each as long as the two cells are apart in the searched space - without a host round trip.  The
+        batch is classified once (``classify``'s call, bit for bit), searched as ``knn`` does (``k``, ``space``, ``metric`` as
+        there), the lists and their distances made a symmetric graph of edge lengths (``ops.distance_graph``) and walked by
+        ``ops.geodesic_rows``: a synchronous Bellman-Ford in float32, one individually rounded add per edge and round, so that two
+        calls give the same bits.  This is Monocle 3's ``order_cells`` on a kNN graph, and what ``scipy.sparse.csgraph.dijkstra``
+        would give on ``knn().to_scipy()`` made symmetric, up to one float32 rounding per hop.
+
+        ``root``: a cell's position, a sequence of positions (the distance is then to the nearest of them), a cell's name when
+        ``index`` is given, or ``{"type": "<a called type's name>"}`` - that type's most confident cell (the highest
+        ``max_prob``, ties to the lowest position; ``ValueError`` if no cell has that call).  ``graph``: an earlier
+        ``NeighborGraph`` of the same batch in place of the search - ``k``, ``space`` and ``metric`` are then the graph's own; a
+        bare index array is refused, distances are needed.  ``max_rounds`` (None = the number of cells): a cap on the rounds;
+        ``converged`` says whether it was hit.  ``index``: the cells' names.
+
+        Returns a ``Pseudotime``.  A cell in another component than every root (a NaN row, which ``knn`` lists nowhere, among
+        them) is not reached: ``distance`` +inf, ``pseudotime`` NaN.
+
+        What this is not: geodesic distance, not diffusion pseudotime (scanpy's ``tl.dpt`` averages over all paths, this takes
+        the shortest); no branch detection - ``paga`` and ``Abstraction.directed`` are the coarse view of the branches; the
+        lengths are distances in the searched space, so ``space="hidden"`` orders the cells as the classifier sees them
+        (``space="features"`` is the view no trained weight takes part in); one batch only; the cost is ``O(rounds x edges)``
+        where ``rounds`` is the hop diameter from the root, which reaches the number of cells on a chain.  Fused kernels only, as
+        ``embed``."""
+        B = self._n_cells(expr)
+        lists, k, space, metric = self._graph_lists("pseudotime", graph, B, k, space, metric, True)
+        if max_rounds is not None and int(max_rounds) < 0:
+            raise ValueError(f"max_rounds = {max_rounds} must not be negative")
+        self._require_fused("pseudotime")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._pseudotime(self._over_genes(expr, genes, normalize), root, k, space, metric, lists, max_rounds, index)
+
+    def _root_cells(self, root, B, index, pred, max_prob) -> np.ndarray:
+        """``pseudotime``'s ``root`` as checked positions, ascending."""
+        if isinstance(root, dict):
+            if set(root) != {"type"}:
+                raise ValueError(f"root = {root!r}: a dict root is {{'type': <a called type's name>}}")
+            names = [str(n) for n in self.id2label]
+            if str(root["type"]) not in names:
+                raise ValueError(f"root type {root['type']!r} is no cell type of this bundle")
+            own = np.nonzero(np.asarray(pred, np.int64) == names.index(str(root["type"])))[0]
+            if own.size == 0:
+                raise ValueError(f"root type {root['type']!r}: no cell of the batch has that call")
+            return own[[int(np.argmax(np.asarray(max_prob)[own]))]].astype(np.int64)        # the first of equal maxima
+        if isinstance(root, str) or (index is not None and not isinstance(root, (int, np.integer))
+                                     and np.ndim(root) == 0 and not isinstance(root, torch.Tensor)):
+            if index is None:
+                raise ValueError(f"root = {root!r} names a cell: pass index= with the cells' names")
+            at = [i for i, c in enumerate(index) if c == root or str(c) == str(root)]
+            if len(at) != 1:
+                raise ValueError(f"root = {root!r} names {len(at)} cells of index")
+            return np.asarray(at, np.int64)
+        cells = root.detach().cpu().numpy() if isinstance(root, torch.Tensor) else np.asarray(root)
+        if cells.dtype.kind not in "iu" or cells.ndim > 1 or cells.size == 0:
+            raise ValueError(f"root = {root!r}: pass a cell's position, a non-empty sequence of positions, a cell's name with "
+                             "index=, or {'type': name}")
+        cells = np.unique(cells.reshape(-1).astype(np.int64))
+        if cells[0] < 0 or cells[-1] >= B:
+            raise ValueError(f"root position out of range [0, {B})")
+        return cells
+
+    def _pseudotime(self, expr, root, k, space, metric, lists, max_rounds, index):
+        vb = self._values_batch(self._device_csr(expr))
+        B = int(vb.csr[0].shape[0]) - 1
+        cells = self._root_cells(root, B, index, vb.pred, vb.max_prob)
+        idx, d2 = self._lists_on_device(vb, lists, k, space, metric)
+        out = _ops.geodesic_rows(*_ops.distance_graph(idx, d2), torch.as_tensor(cells, device=self.device), max_rounds=max_rounds)
+        distance = out.dist.cpu().numpy()
+        return Pseudotime(distance=distance, pseudotime=_scaled_pseudotime(distance), pred=out.pred.cpu().numpy().astype(np.int64),
+                          root=cells, reached=out.reached, rounds=out.rounds, converged=out.converged, k=k, space=space,
+                          metric=metric, label=vb.pred, max_prob=vb.max_prob, **self._table_fields(B, index))
+
+    def pseudotime_file(self, data, root, k: int = 15, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                        max_rounds: Optional[int] = None, save_path=None) -> pd.DataFrame:
+        """``pseudotime`` on a test file - its full table, its gene names as ``genes=`` and its cell names (so ``root`` may name a
+        cell).  Returns one row per cell: ``cell`` (its name) and ``pseudotime`` - empty where the cell was not reached, which is
+        no error - written as ``{species}_{tissue}_pseudotime.csv`` under ``save_path`` when given.  ``normalize``: as for
+        ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.pseudotime(matrix, root, k=k, genes=genes, normalize=normalize, space=space, metric=metric,
+                              max_rounds=max_rounds, index=index)
+        return self._save_frame(out.pseudotime_frame(), save_path, "pseudotime")
+
+    def paga(self, expr, groups="predicted", k: int = 15, genes=None, normalize=None, space: str = "hidden",
+             metric: str = "euclidean", graph=None, group_names: Optional[Sequence[str]] = None, n_groups: Optional[int] = None,
+             index=None) -> Abstraction:
+        """How do groups of cells hang together on the batch's own kNN graph?  The PAGA connectivity (Wolf et al. 2019) of every
+        pair of groups: the batch is classified once (``classify``'s call, bit for bit), searched as ``knn`` does, and the
+        directed list entries are counted per pair of groups on the device (``ops.group_edges``: integer counts); a pair's
+        connectivity is the entries between the two groups over what a random wiring of the same out-degrees would put there,
+        ``(e[a, b] + e[b, a]) (n - 1) / (es[a] ns[b] + es[b] ns[a])`` capped at 1 - one fp64 division of integers
+        (``Abstraction`` has the tables).  This is scanpy's ``tl.paga`` connectivity, ``model="v1.2"``, as stated on the
+        unit-weight directed kNN graph; the comparison with scanpy itself was not run.
+
+        ``groups="predicted"``: the called types, unsure cells skipped; else one integer id per cell (-1 = skip) with
+        ``group_names`` or ``n_groups``, as for ``silhouette`` - ``leiden``'s result feeds it as it comes:
+        ``paga(expr, groups=lc.cluster, n_groups=lc.n_clusters, graph=g)``.  ``graph``: an earlier ``NeighborGraph`` of the same
+        batch, or a ``[B, k]`` index array (counts need no distances), in place of the search.  At most 4096 groups.
+
+        Returns an ``Abstraction``: ``tree`` / ``frame`` / ``centroids`` / ``directed`` / ``summary`` on top.
+
+        What this is not: no connectivities of a weighted (UMAP) graph - every list entry counts 1; no ``model="v1.0"``; no
+        thresholding or layout of the abstracted graph (``centroids`` puts the groups on a ``umap``); no transitions from RNA
+        velocity - ``directed`` orients the pairs by ``pseudotime`` alone; one batch only.  Fused kernels only, as ``embed``."""
+        B = self._n_cells(expr)
+        lists, k, space, metric = self._graph_lists("paga", graph, B, k, space, metric, False)
+        self._require_fused("paga")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._paga(self._over_genes(expr, genes, normalize), groups, group_names, n_groups, k, space, metric, lists)
+
+    def _paga(self, expr, groups, group_names, n_groups, k, space, metric, lists):
+        predicted, names = self._group_names(groups, group_names, n_groups)
+        K = len(names)
+        if K > _ops.GROUP_EDGES_MAX_GROUPS:
+            raise ValueError(f"{K} groups: paga takes at most {_ops.GROUP_EDGES_MAX_GROUPS}")
+        device_csr = self._device_csr(expr)
+        B = int(device_csr[0].shape[0]) - 1
+        if not predicted:
+            ids = self._group_ids(groups, B, K)
+        vb = self._values_batch(device_csr)
+        group = np.asarray(vb.pred if predicted else ids, np.int64)
+        group = np.where(group >= 0, group, -1)
+        idx, _ = self._lists_on_device(vb, lists, k, space, metric)
+        out = _ops.group_edges(idx, torch.from_numpy(group).to(self.device), K)
+        edges, size = out.edges.cpu().numpy(), out.size.cpu().numpy()
+        out_edges, expected, conn = _paga_connectivities(edges, size)
+        return Abstraction(edges=edges, size=size, out_edges=out_edges, connectivities=conn, expected=expected, group_names=names,
+                           n_skipped=int((group < 0).sum()), group=group, k=k, space=space, metric=metric)
+
+    def paga_file(self, data, clusters_file=None, k: int = 15, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                  save_path=None) -> pd.DataFrame:
+        """``paga`` on a test file - its full table, its gene names as ``genes=`` and its cell names.  ``clusters_file``: a
+        clusters file laid out as ``annotate_file`` reads it - what ``kmeans_file`` / ``louvain_file`` / ``leiden_file`` write;
+        ``None``: the predicted types.  Returns ``Abstraction.frame()``, written as ``{species}_{tissue}_paga.csv`` under
+        ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        kw = dict(k=k, genes=genes, normalize=normalize, space=space, metric=metric, index=index)
+        if clusters_file is None:
+            out = self.paga(matrix, **kw)
+        else:
+            ids, names = _cluster_ids(self._read_clusters_file(clusters_file, data, index), n_cells=len(index))
+            out = self.paga(matrix, groups=ids, group_names=names, **kw)
+        return self._save_frame(out.frame(), save_path, "paga")
 
     # ---------------------------------------------------------------------------------------------
     def silhouette(self, expr, groups="predicted", genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",

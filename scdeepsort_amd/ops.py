@@ -2401,6 +2401,38 @@ class SnnGraph(NamedTuple):
     w: torch.Tensor
 
 
+def _list_entries(name, idx):
+    """``[B, k]`` neighbour lists (int32 / int64, -1 = none, ``k`` in [1, 64]) checked - one read-back validates the ids - and
+    flattened: ``(B, k, src, dst)``, the int64 row and entry of every list position."""
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{name}: idx must be a 2-D int32 / int64 tensor [B, k]")
+    B, k = int(idx.shape[0]), int(idx.shape[1])
+    if not 1 <= k <= SNN_MAX_K:
+        raise ValueError(f"{name}: k = {k} is outside [1, {SNN_MAX_K}]")
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    if B:
+        lo, hi = torch.aminmax(idx)
+        if int(lo) < -1 or int(hi) >= B:
+            raise ValueError(f"{name}: a neighbour id is outside [-1, {B}) (min {int(lo)}, max {int(hi)})")
+    src = torch.arange(B, dtype=torch.int64, device=idx.device)[:, None].expand(B, k).reshape(-1)
+    return B, k, src, idx.reshape(-1).to(torch.int64)
+
+
+def _union_csr(B, src, dst, return_inverse=False):
+    """``(rowptr int64 [B + 1], col int32, inverse | None)``: the symmetric CSR that stores both directions of every pair
+    ``(src, dst)`` once - 64-bit keys, sorted and made unique on the device (one read-back sizes the edge list).  ``inverse``: the
+    CSR position of ``cat([src -> dst, dst -> src])``'s entries."""
+    keys = torch.unique(torch.cat([src * B + dst, dst * B + src]), return_inverse=return_inverse)      # sorted: row-major, columns ascending
+    keys, inverse = keys if return_inverse else (keys, None)
+    row = torch.div(keys, max(B, 1), rounding_mode="floor")
+    col = (keys - row * B).to(torch.int32)
+    rowptr = torch.zeros(B + 1, dtype=torch.int64, device=src.device)
+    if B:
+        torch.cumsum(torch.bincount(row, minlength=B), 0, out=rowptr[1:])
+    return rowptr, col, inverse
+
+
 def snn_graph(idx: torch.Tensor, weights: str = "snn") -> SnnGraph:
     """The union graph of ``[B, k]`` neighbour lists as ``knn_rows`` leaves them (int32 / int64, -1 = none, ``k`` in [1, 64], no
     self entries) as a symmetric integer-weighted CSR on the device: ``{i, j}`` is an edge iff ``j`` is in ``i``'s list or ``i``
@@ -2414,28 +2446,10 @@ def snn_graph(idx: torch.Tensor, weights: str = "snn") -> SnnGraph:
     dev = _require_cuda(idx)
     if weights not in SNN_WEIGHTS:
         raise ValueError(f"{name}: weights = {weights!r}: pass one of {', '.join(map(repr, SNN_WEIGHTS))}")
-    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{name}: idx must be a 2-D int32 / int64 tensor [B, k]")
-    B, k = int(idx.shape[0]), int(idx.shape[1])
-    if not 1 <= k <= SNN_MAX_K:
-        raise ValueError(f"{name}: k = {k} is outside [1, {SNN_MAX_K}]")
-    if B >= 2 ** 31:
-        raise ValueError(f"{name}: B must be below 2^31")
+    B, k, src, dst = _list_entries(name, idx)
     idx = idx.contiguous()
-    if B:
-        lo, hi = torch.aminmax(idx)
-        if int(lo) < -1 or int(hi) >= B:
-            raise ValueError(f"{name}: a neighbour id is outside [-1, {B}) (min {int(lo)}, max {int(hi)})")
-    src = torch.arange(B, dtype=torch.int64, device=dev)[:, None].expand(B, k).reshape(-1)
-    dst = idx.reshape(-1).to(torch.int64)
     listed = (dst >= 0) & (dst != src)
-    src, dst = src[listed], dst[listed]
-    keys = torch.unique(torch.cat([src * B + dst, dst * B + src]))             # sorted: row-major, columns ascending
-    row = torch.div(keys, max(B, 1), rounding_mode="floor")
-    col = (keys - row * B).to(torch.int32)
-    rowptr = torch.zeros(B + 1, dtype=torch.int64, device=dev)
-    if B:
-        torch.cumsum(torch.bincount(row, minlength=B), 0, out=rowptr[1:])
+    rowptr, col, _ = _union_csr(B, src[listed], dst[listed])
     nnz = int(col.shape[0])
     if weights == "unit" or nnz == 0:
         return SnnGraph(rowptr, col, torch.ones(nnz, dtype=torch.int32, device=dev))
@@ -2948,3 +2962,175 @@ def layout_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, init=
                  gamma, lr * (1.0 - n / n_epochs), n_neg, seed, _ptr(fired), 0, stream)
         y, other = other, y
     return LayoutRows(y, n_epochs, int(fired.sum()))
+
+
+GEODESIC_LANES, GEODESIC_MAX_BLOCKS = _lib.GEODESIC_LANES, _lib.GEODESIC_MAX_BLOCKS
+GROUP_EDGES_MAX_GROUPS = 4096             # group_edges' most groups: a [K, K] int64 table
+
+_GEODESIC_STATUS = ((_lib.GEODESIC_UNSORTED, "a row is not strictly ascending in col"),
+                    (_lib.GEODESIC_BAD_COL, "a column is outside [0, n)"),
+                    (_lib.GEODESIC_BAD_ROWPTR, "rowptr does not ascend from 0 to nnz"),
+                    (_lib.GEODESIC_BAD_LENGTH, "a length is negative, infinite or NaN"))
+
+
+class DistanceGraph(NamedTuple):
+    """What ``distance_graph`` returns, on the device: the symmetric CSR of the union graph - ``rowptr`` int64 [B + 1], ``col`` int32
+    ascending within a row (``snn_graph``'s structure) - and ``length`` float32 [nnz], the Euclidean length of every stored edge;
+    ``length(i, j)`` and ``length(j, i)`` are the same bits."""
+    rowptr: torch.Tensor
+    col: torch.Tensor
+    length: torch.Tensor
+
+
+def distance_graph(idx: torch.Tensor, d2: torch.Tensor) -> DistanceGraph:
+    """The union graph of ``[B, k]`` neighbour lists with their distances as edge lengths: ``idx`` int32 / int64 (-1 = none) and
+    ``d2`` float32 squared distances as ``knn_rows`` leaves them, ``k`` in [1, 64]; ``{i, j}`` is an edge iff one lists the other -
+    ``snn_graph``'s keys and ``torch.unique``, so the structure is ``snn_graph``'s exactly - and ``length = sqrt(d2)`` of the listed
+    direction.  ``knn_rows`` gives ``d(i, j)`` and ``d(j, i)`` the same bits; where a caller's two directions differ, the smaller
+    one is kept, so the result never depends on an order.
+
+    The root is float32 and correctly rounded - the bits of ``np.sqrt(np.float32(d2))``: it is taken in float64 and rounded once
+    more, which cannot differ (the root of a 24-bit number lies at least 2^-51, relatively, from every midpoint of two float32
+    values, beyond the last bit of a float64), however the framework's float32 ``sqrt`` was built (measured on an MI355X: the
+    same bits on 4 000 000 values).  Framework ops only; one read-back
+    validates the ids and the distances, one sizes the edge list.  An id outside [-1, B) and a negative, NaN or infinite ``d2`` on a
+    listed entry are ``ValueError`` (a self entry is not listed); CPU tensors raise ``WgnnError``.  Returns a ``DistanceGraph``."""
+    name = "distance_graph"
+    dev = _require_cuda(idx, d2)
+    B, k, src, dst = _list_entries(name, idx)
+    if not isinstance(d2, torch.Tensor) or d2.dtype != torch.float32 or tuple(d2.shape) != (B, k):
+        raise ValueError(f"{name}: d2 must be a float32 [{B}, {k}] tensor")
+    listed = (dst >= 0) & (dst != src)
+    sq = d2.reshape(-1)[listed]
+    if bool((~((sq >= 0) & (sq < float("inf")))).any()):
+        raise ValueError(f"{name}: d2 holds a negative, NaN or infinite squared distance on a listed entry")
+    rowptr, col, inverse = _union_csr(B, src[listed], dst[listed], return_inverse=True)
+    root = torch.sqrt(sq.to(torch.float64)).to(torch.float32)
+    length = torch.full((int(col.shape[0]),), float("inf"), dtype=torch.float32, device=dev)
+    length.scatter_reduce_(0, inverse, torch.cat([root, root]), "amin")
+    return DistanceGraph(rowptr, col, length)
+
+
+class GeodesicRows(NamedTuple):
+    """What ``geodesic_rows`` returns.  On the device: ``dist`` float32 [B] (+inf = not reached) and ``pred`` int32 [B] (the
+    neighbour the distance came through; -1 = a root or not reached).  On the host: ``rounds`` (how many rounds changed
+    something), ``converged`` (False when ``max_rounds`` cut the run before a round changed nothing) and ``reached`` (the number of
+    vertices with a finite distance, the roots included)."""
+    dist: torch.Tensor
+    pred: torch.Tensor
+    rounds: int
+    converged: bool
+    reached: int
+
+
+def _geodesic_roots(name, roots, B, dev):
+    """``roots`` - an int, or a 1-D sequence / tensor of ints - as a sorted, unique int64 tensor on ``dev``, checked."""
+    if isinstance(roots, torch.Tensor):
+        if roots.dtype not in (torch.int32, torch.int64) or roots.dim() > 1:
+            raise ValueError(f"{name}: roots must be an int or a 1-D int32 / int64 tensor / sequence")
+        r = roots.reshape(-1).to(device=dev, dtype=torch.int64)
+    else:
+        import numpy as np
+        arr = np.asarray(roots)
+        if arr.dtype.kind not in "iu" or arr.ndim > 1:
+            raise ValueError(f"{name}: roots must be an int or a 1-D sequence of ints, got {roots!r}")
+        r = torch.as_tensor(arr.reshape(-1).astype(np.int64), device=dev)
+    if r.numel() == 0:
+        raise ValueError(f"{name}: the root set is empty")
+    lo, hi = torch.aminmax(r)
+    if int(lo) < 0 or int(hi) >= B:
+        raise ValueError(f"{name}: a root is outside [0, {B}) (min {int(lo)}, max {int(hi)})")
+    return torch.unique(r)
+
+
+def geodesic_rows(rowptr: torch.Tensor, col: torch.Tensor, length: torch.Tensor, roots, max_rounds: Optional[int] = None,
+                  check_every: int = 8, grid_blocks: int = 0) -> GeodesicRows:
+    """The geodesic (shortest-path) distance of every vertex of a graph to the nearest of ``roots``, by a SYNCHRONOUS Bellman-Ford
+    in float32 on the device.  ``rowptr`` int64 [B + 1], ``col`` int32 ascending within a row and ``length`` float32 >= 0 - what
+    ``distance_graph`` returns: both directions of every edge are stored.  ``roots``: an int, or a 1-D int sequence / tensor.
+
+    From ``dist = 0`` at the roots and ``+inf`` elsewhere, every round (``wgnn_geodesic_round``, ``include/wgnn.h`` has the
+    contract) reads the state before it and gives every vertex ``min_u float32(dist[u] + length(u, v))`` under the total order
+    (candidate, u) when that is STRICTLY below what it has - one individually rounded add per stored entry, two buffers, no
+    atomics on the state - so numpy restates the run round by round and two calls give the same bits.  The fixed point is the
+    float32 distance a heap Dijkstra with the same add finds; against float64 it differs by one rounding per hop.
+
+    ``check_every`` rounds are enqueued at a time, each with its own counter, and read back together; a round past the fixed
+    point is the identity, so the extra rounds change no bit.  ``max_rounds`` (None = ``B``) caps the rounds RUN - the last batch
+    is cut to it - and a run that was still changing when it hit the cap returns the state after exactly ``max_rounds`` rounds with
+    ``converged=False``.  ``grid_blocks`` (0 = from ``B``) caps the grid and changes no bit.  O(rounds x nnz): ``rounds`` is the hop
+    diameter from the roots, up to ``B - 1`` on a chain.
+
+    A malformed graph (unsorted row, column out of range, bad ``rowptr``, a negative / infinite / NaN length) raises ``WgnnError``
+    from the kernel's status word; an out-of-range or empty root set and every other argument error are ``ValueError``; CPU
+    tensors raise ``WgnnError``.  Returns a ``GeodesicRows``."""
+    name = "geodesic_rows"
+    dev = _require_cuda(rowptr, col, length, roots if isinstance(roots, torch.Tensor) else None)
+    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
+            length.dtype != torch.float32 or length.shape != col.shape:
+        raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and length float32 [nnz] are expected")
+    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    max_rounds = B if max_rounds is None else int(max_rounds)
+    check_every, grid_blocks = int(check_every), int(grid_blocks)
+    if max_rounds < 0:
+        raise ValueError(f"{name}: max_rounds = {max_rounds} must not be negative")
+    if check_every < 1:
+        raise ValueError(f"{name}: check_every = {check_every} must be >= 1")
+    if not 0 <= grid_blocks <= GEODESIC_MAX_BLOCKS:
+        raise ValueError(f"{name}: grid_blocks = {grid_blocks} is outside [0, {GEODESIC_MAX_BLOCKS}] (0 = from B)")
+    dist = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
+    dist[_geodesic_roots(name, roots, B, dev)] = 0.0
+    pred = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    rowptr, col, length = rowptr.contiguous(), col.contiguous(), length.contiguous()
+    stream = _stream(dev)
+    dist2, pred2 = torch.empty_like(dist), torch.empty_like(pred)
+    slots = torch.empty(check_every + 1, dtype=torch.int64, device=dev)        # one counter per round of a batch, then the status
+    status = slots.data_ptr() + 8 * check_every
+    done, rounds, converged = 0, 0, B == 0
+    while not converged and done < max_rounds:
+        batch = min(check_every, max_rounds - done)
+        slots.zero_()
+        for t in range(batch):
+            _lib.run(dev, "wgnn_geodesic_round", _ptr(rowptr), _ptr(col), _ptr(length), B, nnz, _ptr(dist), _ptr(pred), _ptr(dist2),
+                     _ptr(pred2), slots.data_ptr() + 8 * t, status, grid_blocks, 0, stream)
+            dist, dist2, pred, pred2 = dist2, dist, pred2, pred
+        counts = slots.tolist()
+        _check_status(name, counts[check_every], _GEODESIC_STATUS)
+        done += batch
+        changed = sum(1 for c in counts[:batch] if c)
+        rounds += changed
+        converged = changed < batch                # a round that changed nothing: the fixed point, and every later round is the identity
+    reached = int(torch.isfinite(dist).sum()) if B else 0
+    return GeodesicRows(dist, pred, rounds, converged, reached)
+
+
+class GroupEdges(NamedTuple):
+    """What ``group_edges`` returns, on the device: ``edges`` int64 [K, K] - ``edges[a, b]`` = the number of list entries that lead
+    from a cell of group ``a`` to a cell of group ``b`` - and ``size`` int64 [K], the cells per group."""
+    edges: torch.Tensor
+    size: torch.Tensor
+
+
+def group_edges(idx: torch.Tensor, group: torch.Tensor, n_groups: int) -> GroupEdges:
+    """The directed kNN graph counted by group: ``idx`` [B, k] int32 / int64 neighbour lists (-1 = none, ``k`` in [1, 64]) and
+    ``group`` int32 / int64 [B], a cell's group in ``[0, n_groups)`` or -1 = it takes no part.
+    ``edges[a, b] = #{(i, j) : j in list(i), group[i] = a, group[j] = b}`` - an entry with either end at -1 does not count (``knn_rows``
+    lists no cell in its own list; a self entry given all the same counts on the diagonal) - and ``size[a]`` = the number of cells of group ``a``; both int64, one integer ``bincount`` of
+    ``group[i] * K + group[j]`` each (the coarsening idiom of ``louvain_graph``): exact, whatever the order.  ``n_groups`` in
+    [1, 4096].  An id outside [-1, B) and a group outside [-1, n_groups) are ``ValueError``; CPU tensors raise ``WgnnError``."""
+    name = "group_edges"
+    _require_cuda(idx, group)
+    K = int(n_groups)
+    if not 1 <= K <= GROUP_EDGES_MAX_GROUPS:
+        raise ValueError(f"{name}: n_groups = {K} is outside [1, {GROUP_EDGES_MAX_GROUPS}]")
+    B, _, src, dst = _list_entries(name, idx)
+    _group_operand(name, ValueError, group, B, K, True)
+    g = group.to(torch.int64)
+    listed = dst >= 0
+    ga, gb = g[src[listed]], g[dst[listed]]
+    both = (ga >= 0) & (gb >= 0)
+    edges = torch.bincount(ga[both] * K + gb[both], minlength=K * K).reshape(K, K)
+    size = torch.bincount(g[g >= 0], minlength=K)
+    return GroupEdges(edges, size)

@@ -2165,3 +2165,279 @@ class Layout(_NamesCalls):
                              y_max=ext(xy[on, 1], np.max), median_sigma=ext(sigma, np.median), n_types=int(len(types)),
                              median_spread=ext(np.asarray(types["spread"]), np.median),
                              n_unsure=int((np.asarray(self.label) < 0).sum()))
+
+
+class PseudotimeSummary(dict):
+    """``Pseudotime.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        how = "converged" if d["converged"] else "NOT converged (stopped at max_rounds)"
+        return "\n".join([
+            f"{d['n_cells']} cells ordered by geodesic distance on the k = {d['k']} graph in the {d['space']} space ({d['metric']}) "
+            f"from {d['n_roots']} root cell(s); {d['n_reached']} reached, {d['n_unreached']} not",
+            f"{d['rounds']} rounds, {how}; the farthest cell lies {d['max_distance']:.4g} away over {d['max_hops']} hops "
+            f"(median {d['median_distance']:.4g})",
+            f"{d['n_types']} called types, earliest {d['first_type']}, latest {d['last_type']} by median pseudotime "
+            f"({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class Pseudotime(_NamesCalls):
+    """What ``ResidentPredictor.pseudotime`` returns: every cell's geodesic distance from the root cells along one batch's own kNN
+    graph.  B cells (``index``), C cell types (``id2label``).  ``distance`` f32 [B]: ``ops.geodesic_rows``' bits, the shortest path
+    over the union graph's edges in the searched space (+inf = not reached); ``pseudotime`` f64 [B]: ``distance`` over the largest
+    finite distance, in [0, 1], NaN where not reached and all 0 when that largest distance is 0; ``pred`` int64 [B]: the
+    neighbour the distance came through (-1 = a root or not reached); ``root`` int64: the root cells' positions, ascending;
+    ``reached`` (cells with a finite distance), ``rounds`` (Bellman-Ford rounds that changed something) and ``converged`` (False
+    when ``max_rounds`` stopped the run early).  ``k`` / ``space`` / ``metric`` say which graph was walked; ``label`` int64 [B] /
+    ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    distance: np.ndarray
+    pseudotime: np.ndarray
+    pred: np.ndarray
+    root: np.ndarray
+    reached: int
+    rounds: int
+    converged: bool
+    k: int
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def hops(self) -> np.ndarray:
+        """int64 [B]: the number of edges on the cell's path from its root (0 at a root, -1 where not reached), by pointer
+        jumping on ``pred`` - ``ceil(log2(longest path))`` passes."""
+        pred = np.asarray(self.pred, np.int64)
+        B = len(pred)
+        hops = (pred >= 0).astype(np.int64)
+        up = np.where(pred >= 0, pred, np.arange(B))
+        for _ in range(max(1, B).bit_length() + 1):
+            if not (hops[up] > 0).any():
+                break
+            hops, up = hops + hops[up], up[up]
+        hops[~np.isfinite(np.asarray(self.distance, np.float64))] = -1
+        return hops
+
+    def path(self, cell: int) -> np.ndarray:
+        """int64: the positions from a root to ``cell`` along ``pred``, both included; empty where the cell was not reached."""
+        pred, cell = np.asarray(self.pred, np.int64), int(cell)
+        if not 0 <= cell < len(pred):
+            raise ValueError(f"cell = {cell} is outside [0, {len(pred)})")
+        if not np.isfinite(float(np.asarray(self.distance)[cell])):
+            return np.zeros(0, np.int64)
+        out = [cell]
+        while pred[out[-1]] >= 0 and len(out) <= len(pred):
+            out.append(int(pred[out[-1]]))
+        return np.asarray(out[::-1], np.int64)
+
+    def by_group(self, groups, group_names: Optional[Sequence[str]] = None) -> pd.DataFrame:
+        """One row per group of ``groups`` (one integer id per cell, -1 = skip) that has a reached cell, sorted by median
+        pseudotime (ties by id): ``group`` (its name from ``group_names``, else the id), ``n_cells`` (reached ones), ``median``,
+        ``min`` and ``max`` pseudotime."""
+        g, t = np.asarray(groups), np.asarray(self.pseudotime, np.float64)
+        if g.shape != t.shape or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"groups must hold one integer id per cell ([{len(t)}]), got {g.dtype} {g.shape}")
+        on = (g >= 0) & ~np.isnan(t)
+        rows = [(int(s), int((on & (g == s)).sum()), float(np.median(t[on & (g == s)])), float(t[on & (g == s)].min()),
+                 float(t[on & (g == s)].max())) for s in sorted(set(g[on].tolist()))]
+        rows.sort(key=lambda r: (r[2], r[0]))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(5)]
+        names = list(cols[0]) if group_names is None else [group_names[s] for s in cols[0]]
+        return pd.DataFrame({"group": names, "n_cells": np.asarray(cols[1], np.int64), "median": np.asarray(cols[2], np.float64),
+                             "min": np.asarray(cols[3], np.float64), "max": np.asarray(cols[4], np.float64)})
+
+    def by_type(self) -> pd.DataFrame:
+        """``by_group`` over the called types (unsure cells skipped): ``cell_type``, ``n_cells``, ``median``, ``min``, ``max``,
+        sorted by median pseudotime."""
+        label = np.asarray(self.label, np.int64)
+        out = self.by_group(np.where(label >= 0, label, -1))
+        out["group"] = self._name(out["group"].tolist())
+        return out.rename(columns={"group": "cell_type"})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``pseudotime``, ``distance``, ``pred``, ``label`` (the call's name, as ``predict`` names
+        it) and ``max_prob``."""
+        return pd.DataFrame({"index": list(self.index), "pseudotime": np.asarray(self.pseudotime, np.float64),
+                             "distance": np.asarray(self.distance, np.float32), "pred": np.asarray(self.pred, np.int64),
+                             "label": self._name(self.label), "max_prob": np.asarray(self.max_prob)})
+
+    def pseudotime_frame(self) -> pd.DataFrame:
+        """One row per cell - ``cell`` (its name) and ``pseudotime`` (empty where not reached): what ``pseudotime_file`` writes."""
+        return pd.DataFrame({"cell": [str(c) for c in self.index], "pseudotime": np.asarray(self.pseudotime, np.float64)})
+
+    def summary(self) -> PseudotimeSummary:
+        """Cells, roots, rounds, the farthest cell and the earliest and latest called type; ``print`` it."""
+        d = np.asarray(self.distance, np.float64)
+        fin = d[np.isfinite(d)]
+        types, hops = self.by_type(), self.hops()
+        return PseudotimeSummary(n_cells=len(d), k=int(self.k), space=self.space, metric=self.metric, n_roots=len(self.root),
+                                 n_reached=int(self.reached), n_unreached=len(d) - int(self.reached), rounds=int(self.rounds),
+                                 converged=bool(self.converged), max_distance=float(fin.max()) if fin.size else float("nan"),
+                                 median_distance=float(np.median(fin)) if fin.size else float("nan"),
+                                 max_hops=int(hops.max()) if hops.size else 0, n_types=len(types),
+                                 first_type=types["cell_type"].iloc[0] if len(types) else None,
+                                 last_type=types["cell_type"].iloc[-1] if len(types) else None,
+                                 n_unsure=int((np.asarray(self.label) < 0).sum()))
+
+
+def _scaled_pseudotime(distance) -> np.ndarray:
+    """``Pseudotime.pseudotime`` of ``distance``: float64, over the largest finite distance; NaN where not reached, all 0 when that
+    largest distance is 0."""
+    d = np.asarray(distance, np.float32).astype(np.float64)
+    fin = np.isfinite(d)
+    top = d[fin].max() if fin.any() else 0.0
+    out = np.where(fin, d / top if top > 0 else 0.0, np.nan)
+    return out
+
+
+def _paga_connectivities(edges, size) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(out_edges int64 [K], expected f64 [K, K], connectivities f64 [K, K])`` of ``ops.group_edges``' tables, the PAGA
+    connectivity (Wolf et al. 2019) on the unit-weight directed kNN graph: with ``es[a] = sum_b edges[a, b]``, ``n = sum size``
+    and ``inter[a, b] = edges[a, b] + edges[b, a]`` for ``a != b``, ``den = es[a] size[b] + es[b] size[a]``, ``expected = den /
+    (n - 1)`` (one fp64 division of integers) and the connectivity 0 where ``inter == 0``, 1 where ``inter (n - 1) >= den`` (an
+    integer comparison), else ``float64(inter (n - 1)) / float64(den)``.  Symmetric, zero diagonal."""
+    e, ns = np.asarray(edges, np.int64), np.asarray(size, np.int64)
+    K = len(ns)
+    if e.shape != (K, K) or (e < 0).any() or (ns < 0).any():
+        raise ValueError(f"edges must be a non-negative [{K}, {K}] table beside size [{K}]")
+    es, n = e.sum(axis=1), int(ns.sum())
+    if int(e.sum()) * max(n, 1) >= 2 ** 62:
+        raise ValueError("the PAGA tables would not fit 64-bit integers")
+    inter = e + e.T
+    np.fill_diagonal(inter, 0)
+    den = es[:, None] * ns[None, :] + es[None, :] * ns[:, None]
+    np.fill_diagonal(den, 0)
+    num = inter * (n - 1)
+    expected = np.zeros((K, K), np.float64)
+    conn = np.zeros((K, K), np.float64)
+    if n > 1:
+        expected = den.astype(np.float64) / np.float64(n - 1)
+        part = (inter > 0) & (num < den)
+        conn[(inter > 0) & (num >= den)] = 1.0
+        conn[part] = num[part].astype(np.float64) / den[part].astype(np.float64)
+    return es, expected, conn
+
+
+class AbstractionSummary(dict):
+    """``Abstraction.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_cells']} cells in {d['n_groups']} non-empty groups on the k = {d['k']} graph in the {d['space']} space "
+            f"({d['metric']}); {d['n_skipped']} cells take no part",
+            f"{d['n_edges']} list entries between participating cells, {d['n_within']} inside a group; {d['n_pairs']} pairs of groups "
+            f"share an edge, {d['n_tree_edges']} of them on the spanning forest ({d['n_components']} components)",
+            f"strongest pair {d['top_pair']} (connectivity {d['top_connectivity']:.4f}); median connectivity of the connected pairs "
+            f"{d['median_connectivity']:.4f}"])
+
+
+@dataclass
+class Abstraction:
+    """What ``ResidentPredictor.paga`` returns: how the groups of one batch hang together on its own kNN graph - the PAGA
+    connectivity (Wolf et al. 2019) on the unit-weight directed graph.  K groups (``group_names``).  ``edges`` int64 [K, K]: the
+    list entries from a cell of group a to a cell of group b; ``size`` int64 [K]: the participating cells; ``out_edges`` int64
+    [K]: ``edges``' row sums; ``expected`` f64 [K, K]: the entries a random wiring of the same out-degrees would put between the
+    pair; ``connectivities`` f64 [K, K]: the observed over the expected, capped at 1 - symmetric, zero diagonal
+    (``tables._paga_connectivities`` has the formula).  ``n_skipped``: the cells that take no part; ``group`` int64 [B]: every cell's
+    group as the call resolved it (-1 = it takes no part); ``k`` / ``space`` / ``metric`` say which graph was counted."""
+    edges: np.ndarray
+    size: np.ndarray
+    out_edges: np.ndarray
+    connectivities: np.ndarray
+    expected: np.ndarray
+    group_names: Sequence[str]
+    n_skipped: int
+    group: Optional[np.ndarray] = field(default=None, repr=False)
+    k: int = 0
+    space: str = ""
+    metric: str = ""
+
+    def _inter(self) -> np.ndarray:
+        e = np.asarray(self.edges, np.int64)
+        inter = e + e.T
+        np.fill_diagonal(inter, 0)
+        return inter
+
+    def tree(self) -> np.ndarray:
+        """int64 [K, K], symmetric 0 / 1: the maximum spanning forest of ``connectivities`` - scipy's
+        ``minimum_spanning_tree`` on ``1 / connectivities`` of the non-zero entries - the backbone PAGA draws."""
+        from scipy.sparse.csgraph import minimum_spanning_tree
+        c = np.asarray(self.connectivities, np.float64)
+        a, b = np.nonzero(np.triu(c, 1))
+        K = c.shape[0]
+        forest = minimum_spanning_tree(sp.csr_matrix((1.0 / c[a, b], (a, b)), shape=(K, K))).tocoo()
+        out = np.zeros((K, K), np.int64)
+        out[forest.row, forest.col] = 1
+        out[forest.col, forest.row] = 1
+        return out
+
+    def frame(self, min_connectivity: float = 0.0) -> pd.DataFrame:
+        """One row per unordered pair of groups that share a list entry (``a`` before ``b`` in ``group_names``' order) with
+        ``connectivity >= min_connectivity``: ``a``, ``b``, ``edges`` (both directions), ``expected``, ``connectivity``,
+        ``in_tree``."""
+        inter, c = self._inter(), np.asarray(self.connectivities, np.float64)
+        a, b = np.nonzero(np.triu(inter, 1))
+        keep = c[a, b] >= float(min_connectivity)
+        a, b = a[keep], b[keep]
+        names = list(self.group_names)
+        return pd.DataFrame({"a": [names[i] for i in a], "b": [names[i] for i in b], "edges": inter[a, b],
+                             "expected": np.asarray(self.expected, np.float64)[a, b], "connectivity": c[a, b],
+                             "in_tree": self.tree()[a, b].astype(bool)})
+
+    def _cells(self, what, shape) -> np.ndarray:
+        if self.group is None:
+            raise ValueError(f"{what} needs the cells' groups: this table was built without ``group``")
+        g = np.asarray(self.group, np.int64)
+        if g.shape != tuple(shape):
+            raise ValueError(f"{what}: the table holds {len(g)} cells, got {tuple(shape)}")
+        return g
+
+    def centroids(self, coords) -> np.ndarray:
+        """f64 [K, 2]: the mean of ``coords`` ([B, 2], a ``Layout.coords`` of the same batch) over the cells of every group - where
+        to draw the groups on the UMAP; NaN for an empty group."""
+        xy = np.asarray(coords, np.float64)
+        K = len(self.group_names)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError(f"coords must be [B, 2], got {xy.shape}")
+        g = self._cells("centroids", xy.shape[:1])
+        on = g >= 0
+        count = np.bincount(g[on], minlength=K).astype(np.float64)
+        out = np.stack([np.bincount(g[on], weights=xy[on, j], minlength=K) for j in range(2)], axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return out / count[:, None]
+
+    def directed(self, pseudotime) -> pd.DataFrame:
+        """``frame()`` with every pair oriented in time: ``a`` is the group of lower median pseudotime (``pseudotime``: a
+        ``Pseudotime`` of the same batch, or one value per cell; ties and groups without a reached cell keep ``group_names``'
+        order), with ``median_a`` / ``median_b`` added."""
+        t = np.asarray(getattr(pseudotime, "pseudotime", pseudotime), np.float64)
+        g = self._cells("directed", t.shape)
+        names = list(self.group_names)
+        med = {names[s]: float(np.median(t[(g == s) & ~np.isnan(t)])) for s in range(len(names)) if ((g == s) & ~np.isnan(t)).any()}
+        out = self.frame()
+        ma = np.asarray([med.get(x, np.nan) for x in out["a"]], np.float64)
+        mb = np.asarray([med.get(x, np.nan) for x in out["b"]], np.float64)
+        flip = mb < ma
+        a, b = out["a"].to_numpy(object), out["b"].to_numpy(object)
+        out["a"], out["b"] = np.where(flip, b, a), np.where(flip, a, b)
+        out["median_a"], out["median_b"] = np.where(flip, mb, ma), np.where(flip, ma, mb)
+        return out
+
+    def summary(self) -> AbstractionSummary:
+        """Cells, groups, edges, the connected pairs, the spanning forest and the strongest pair; ``print`` it."""
+        from scipy.sparse.csgraph import connected_components
+        e, ns, per = np.asarray(self.edges, np.int64), np.asarray(self.size, np.int64), self.frame()
+        live = ns > 0
+        n_comp = int(connected_components(sp.csr_matrix(self._inter()[live][:, live] > 0), directed=False)[0]) if live.any() else 0
+        top = per.iloc[int(np.argmax(per["connectivity"].to_numpy()))] if len(per) else None
+        return AbstractionSummary(n_cells=int(ns.sum()), n_groups=int(live.sum()), k=int(self.k), space=self.space, metric=self.metric,
+                                  n_skipped=int(self.n_skipped), n_edges=int(e.sum()), n_within=int(np.trace(e)), n_pairs=len(per),
+                                  n_tree_edges=int(per["in_tree"].sum()) if len(per) else 0, n_components=n_comp,
+                                  top_pair=None if top is None else (top["a"], top["b"]),
+                                  top_connectivity=float("nan") if top is None else float(top["connectivity"]),
+                                  median_connectivity=float(np.median(per["connectivity"])) if len(per) else float("nan"))
