@@ -2103,42 +2103,23 @@ class ResidentPredictor:
 
     def _graph_clusters(self, method, expr, k, resolution, weights, genes, normalize, space, metric, graph, max_sweeps, index):
         """``louvain`` / ``leiden``: the checks, the graph and the cut named ``method``."""
-        if space not in KNN_SPACES:
-            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
-        if metric not in KNN_METRICS:
-            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
         if weights not in _ops.SNN_WEIGHTS:
             raise ValueError(f"weights = {weights!r}: pass one of {', '.join(map(repr, _ops.SNN_WEIGHTS))}")
-        if not 1 <= int(k) <= _ops.SNN_MAX_K:
-            raise ValueError(f"k = {k} is outside [1, {_ops.SNN_MAX_K}]")
         if int(max_sweeps) < 1:
             raise ValueError(f"max_sweeps = {max_sweeps} must be >= 1")
         _ops.louvain_resolution(resolution)
         B = self._n_cells(expr)
-        lists = None
-        if graph is not None:
-            lists = np.asarray(graph.indices if isinstance(graph, NeighborGraph) else graph)
-            if lists.ndim != 2 or lists.shape[0] != B or not 1 <= lists.shape[1] <= _ops.SNN_MAX_K or lists.dtype.kind not in "iu":
-                raise ValueError(f"graph must be a NeighborGraph or an integer array [{B}, 1..{_ops.SNN_MAX_K}] of this batch")
-            if isinstance(graph, NeighborGraph):
-                space, metric = graph.space, graph.metric
-            k = int(lists.shape[1])
+        lists, k, space, metric = self._graph_lists(method, graph, B, k, space, metric, False)
         self._require_fused(method)
         _check_index(index, B)
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._louvain(self._over_genes(expr, genes, normalize), int(k), resolution, weights, space, metric, lists,
+            return self._louvain(self._over_genes(expr, genes, normalize), k, resolution, weights, space, metric, lists,
                                  int(max_sweeps), index, method)
 
     def _louvain(self, expr, k, resolution, weights, space, metric, lists, max_sweeps, index, method="louvain"):
         vb = self._values_batch(self._device_csr(expr))
         B = int(vb.csr[0].shape[0]) - 1
-        if lists is None:
-            rows = self._embed(vb.csr, space)
-            if metric == "cosine":
-                rows = F.normalize(rows, dim=1)
-            idx, _ = _ops.knn_rows(rows, k)
-        else:
-            idx = torch.as_tensor(lists.astype(np.int64), device=self.device)
+        idx, _, _ = self._lists_on_device(vb, lists, k, space, metric)
         cut = _ops.leiden_graph if method == "leiden" else _ops.louvain_graph
         out = cut(*_ops.snn_graph(idx, weights), resolution=resolution, max_sweeps=max_sweeps)
         more = dict(method=method, refined_labels=[l.cpu().numpy() for l in out.refined_labels]) if method == "leiden" else {}
@@ -2155,12 +2136,16 @@ class ResidentPredictor:
         which ``annotate_file``, ``pseudobulk_file`` and ``silhouette_file`` read as ``clusters_file`` - written as
         ``{species}_{tissue}_louvain.csv`` under ``save_path`` when given.  A cell without an edge has no community:
         ``WgnnError``.  ``normalize``: as for ``predict``."""
+        return self._graph_clusters_file("louvain", data, save_path, k=k, resolution=resolution, weights=weights, normalize=normalize,
+                                         space=space, metric=metric, max_sweeps=max_sweeps)
+
+    def _graph_clusters_file(self, method, data, save_path, **kw):
+        """``louvain_file`` / ``leiden_file``: the cut named ``method`` on a test file, every cell in a community."""
         matrix, genes, index = self._read_counts_file(data)
-        out = self.louvain(matrix, k=k, resolution=resolution, weights=weights, genes=genes, normalize=normalize, space=space,
-                           metric=metric, max_sweeps=max_sweeps, index=index)
+        out = getattr(self, method)(matrix, genes=genes, index=index, **kw)
         if (out.cluster < 0).any():
-            raise WgnnError(f"louvain_file: {int((out.cluster < 0).sum())} cells have no edge in the graph and no community")
-        return self._save_frame(out.clusters_frame(), save_path, "louvain")
+            raise WgnnError(f"{method}_file: {int((out.cluster < 0).sum())} cells have no edge in the graph and no community")
+        return self._save_frame(out.clusters_frame(), save_path, method)
 
     def leiden(self, expr, k: int = 15, resolution=1.0, weights: str = "snn", genes=None, normalize=None, space: str = "hidden",
                metric: str = "euclidean", graph=None, max_sweeps: int = 256, index=None) -> Communities:
@@ -2184,12 +2169,8 @@ class ResidentPredictor:
         """``leiden`` on a test file, as ``louvain_file``: one row per cell - a running number, ``cell`` and ``cluster`` - the layout
         ``annotate_file``, ``pseudobulk_file`` and ``silhouette_file`` read as ``clusters_file``, written as
         ``{species}_{tissue}_leiden.csv`` under ``save_path`` when given.  A cell without an edge has no community: ``WgnnError``."""
-        matrix, genes, index = self._read_counts_file(data)
-        out = self.leiden(matrix, k=k, resolution=resolution, weights=weights, genes=genes, normalize=normalize, space=space,
-                          metric=metric, max_sweeps=max_sweeps, index=index)
-        if (out.cluster < 0).any():
-            raise WgnnError(f"leiden_file: {int((out.cluster < 0).sum())} cells have no edge in the graph and no community")
-        return self._save_frame(out.clusters_frame(), save_path, "leiden")
+        return self._graph_clusters_file("leiden", data, save_path, k=k, resolution=resolution, weights=weights, normalize=normalize,
+                                         space=space, metric=metric, max_sweeps=max_sweeps)
 
     # ---------------------------------------------------------------------------------------------
     def umap(self, expr, k: int = 15, min_dist: float = 0.1, spread: float = 1.0, a=None, b=None, n_epochs: Optional[int] = None,
@@ -2218,12 +2199,10 @@ class ResidentPredictor:
         edges see the move, here a firing edge moves each end once, from that end's own row, off the previous epoch's
         positions; no spectral init, no ``transform`` of new cells, no 3-D, no supervised mode; one batch only.  Fused kernels
         only, as ``embed``."""
-        if space not in KNN_SPACES:
-            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
-        if metric not in KNN_METRICS:
-            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
-        if not 1 <= int(k) <= _ops.FUZZY_MAX_K:
-            raise ValueError(f"k = {k} is outside [1, {_ops.FUZZY_MAX_K}]")
+        B = self._n_cells(expr)
+        lists, k, space, metric = self._graph_lists(
+            "the layout", graph, B, k, space, metric, True, max_k=_ops.FUZZY_MAX_K,
+            misfit=f"graph must be a NeighborGraph of this batch: [{B}, 1..{_ops.FUZZY_MAX_K}] lists and distances")
         if n_epochs is not None and not 1 <= int(n_epochs) <= _ops.LAYOUT_MAX_EPOCHS:
             raise ValueError(f"n_epochs = {n_epochs} is outside [1, {_ops.LAYOUT_MAX_EPOCHS}]")
         if not 0 <= int(n_neg) <= _ops.LAYOUT_MAX_NEG:
@@ -2236,7 +2215,6 @@ class ResidentPredictor:
         a, b = float(a), float(b)
         if not (0.0 < a < float("inf") and 0.0 < b < float("inf")):
             raise ValueError(f"a = {a} and b = {b} must be positive and finite")
-        B = self._n_cells(expr)
         start = init
         if not isinstance(init, str):
             start = np.asarray(init)
@@ -2245,35 +2223,17 @@ class ResidentPredictor:
             start = start.astype(np.float32)
         elif init not in ("pca", "hash"):
             raise ValueError(f"init = {init!r}: pass 'pca', 'hash' or an array [{B}, 2]")
-        lists = None
-        if graph is not None:
-            if not isinstance(graph, NeighborGraph):
-                raise ValueError("graph must be a NeighborGraph: the layout needs the neighbours' distances, which a bare index "
-                                 "array does not carry")
-            lists = (np.asarray(graph.indices), np.asarray(graph.sq_distances))
-            if lists[0].ndim != 2 or lists[0].shape[0] != B or not 1 <= lists[0].shape[1] <= _ops.FUZZY_MAX_K or \
-                    lists[1].shape != lists[0].shape:
-                raise ValueError(f"graph must be a NeighborGraph of this batch: [{B}, 1..{_ops.FUZZY_MAX_K}] lists and distances")
-            space, metric, k = graph.space, graph.metric, int(lists[0].shape[1])
         self._require_fused("umap")
         _check_index(index, B)
         with torch.cuda.device(self.device), torch.no_grad():
-            return self._umap(self._over_genes(expr, genes, normalize), int(k), a, b, n_epochs, int(n_neg), int(seed), start,
+            return self._umap(self._over_genes(expr, genes, normalize), k, a, b, n_epochs, int(n_neg), int(seed), start,
                               space, metric, lists, index)
 
     def _umap(self, expr, k, a, b, n_epochs, n_neg, seed, start, space, metric, lists, index):
         vb = self._values_batch(self._device_csr(expr))
         B = int(vb.csr[0].shape[0]) - 1
-        rows = None
-        if lists is None or (isinstance(start, str) and start == "pca"):
-            rows = self._embed(vb.csr, space)
-            if metric == "cosine":
-                rows = F.normalize(rows, dim=1)
-        if lists is None:
-            idx, d2 = _ops.knn_rows(rows, k)
-        else:
-            idx = torch.as_tensor(lists[0].astype(np.int64), device=self.device)
-            d2 = torch.as_tensor(lists[1].astype(np.float32), device=self.device)
+        pca = isinstance(start, str) and start == "pca"
+        idx, d2, rows = self._lists_on_device(vb, lists, k, space, metric, want_rows=pca)      # "pca" embeds the batch once
         fuzzy = _ops.fuzzy_graph(idx, d2)
         if isinstance(start, str):
             how, y0 = start, (self._pca_start(rows) if start == "pca" else "hash")
@@ -2316,41 +2276,48 @@ class ResidentPredictor:
         return self._save_frame(out.coords_frame(), save_path, "umap")
 
     # ---------------------------------------------------------------------------------------------
-    def _graph_lists(self, what, graph, B, k, space, metric, need_distances):
-        """``graph=`` of ``pseudotime`` / ``paga``: ``(lists | None, k, space, metric)`` - ``lists`` the host ``(indices,
-        sq_distances | None)`` of an earlier ``NeighborGraph`` of this batch (or, where no distances are needed, of a bare
-        ``[B, k]`` index array), whose own ``k`` / ``space`` / ``metric`` then replace the call's."""
+    def _graph_lists(self, what, graph, B, k, space, metric, need_distances, max_k=_ops.SNN_MAX_K, misfit=None):
+        """``graph=`` of the calls on a kNN graph, and their ``space`` / ``metric`` / ``k`` checks: ``(lists | None, k, space,
+        metric)`` - ``lists`` the host ``(indices, sq_distances | None)`` of an earlier ``NeighborGraph`` of this batch (or, where
+        no distances are needed, of a bare ``[B, k]`` index array), whose own ``k`` / ``space`` / ``metric`` then replace the
+        call's.  ``what``: who needs the distances, in that refusal; ``max_k``: the caller's limit of ``k``; ``misfit``: the
+        caller's own words for lists or distances that are not this batch's."""
         if space not in KNN_SPACES:
             raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
         if metric not in KNN_METRICS:
             raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
-        if not 1 <= int(k) <= _ops.SNN_MAX_K:
-            raise ValueError(f"k = {k} is outside [1, {_ops.SNN_MAX_K}]")
+        if not 1 <= int(k) <= max_k:
+            raise ValueError(f"k = {k} is outside [1, {max_k}]")
         if graph is None:
             return None, int(k), space, metric
         if need_distances and not isinstance(graph, NeighborGraph):
             raise ValueError(f"graph must be a NeighborGraph: {what} needs the neighbours' distances, which a bare index array "
                              "does not carry")
         idx = np.asarray(graph.indices if isinstance(graph, NeighborGraph) else graph)
-        if idx.ndim != 2 or idx.shape[0] != B or not 1 <= idx.shape[1] <= _ops.SNN_MAX_K or idx.dtype.kind not in "iu":
-            raise ValueError(f"graph must be a NeighborGraph or an integer array [{B}, 1..{_ops.SNN_MAX_K}] of this batch")
+        if idx.ndim != 2 or idx.shape[0] != B or not 1 <= idx.shape[1] <= max_k or idx.dtype.kind not in "iu":
+            raise ValueError(misfit or f"graph must be a NeighborGraph or an integer array [{B}, 1..{max_k}] of this batch")
         d2 = None
         if isinstance(graph, NeighborGraph):
             space, metric = graph.space, graph.metric
             d2 = np.asarray(graph.sq_distances)
             if need_distances and d2.shape != idx.shape:
-                raise ValueError(f"graph must be a NeighborGraph of this batch: its distances are {d2.shape}, its lists {idx.shape}")
+                raise ValueError(misfit or f"graph must be a NeighborGraph of this batch: its distances are {d2.shape}, its lists "
+                                 f"{idx.shape}")
         return (idx, d2), int(idx.shape[1]), space, metric
 
-    def _lists_on_device(self, vb, lists, k, space, metric):
-        """``(idx, d2)`` on the device: ``knn``'s search of the classified batch ``vb``, or the host ``lists`` of ``_graph_lists``."""
-        if lists is None:
+    def _lists_on_device(self, vb, lists, k, space, metric, want_rows=False):
+        """``(idx, d2, rows)`` on the device: ``knn``'s search of the classified batch ``vb``, or the host ``lists`` of
+        ``_graph_lists``.  ``rows``: the embedded rows that were, or would have been, searched - embedded once - when the search
+        ran or ``want_rows``, else None."""
+        rows = None
+        if lists is None or want_rows:
             rows = self._embed(vb.csr, space)
             if metric == "cosine":
                 rows = F.normalize(rows, dim=1)
-            return _ops.knn_rows(rows, k)
+        if lists is None:
+            return (*_ops.knn_rows(rows, k), rows)
         idx = torch.as_tensor(lists[0].astype(np.int64), device=self.device)
-        return idx, None if lists[1] is None else torch.as_tensor(lists[1].astype(np.float32), device=self.device)
+        return idx, None if lists[1] is None else torch.as_tensor(lists[1].astype(np.float32), device=self.device), rows
 
     def pseudotime(self, expr, root, k: int = 15, genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
                    graph=None, max_rounds: Optional[int] = None, index=None) -> Pseudotime:
@@ -2420,7 +2387,7 @@ class ResidentPredictor:
         vb = self._values_batch(self._device_csr(expr))
         B = int(vb.csr[0].shape[0]) - 1
         cells = self._root_cells(root, B, index, vb.pred, vb.max_prob)
-        idx, d2 = self._lists_on_device(vb, lists, k, space, metric)
+        idx, d2, _ = self._lists_on_device(vb, lists, k, space, metric)
         out = _ops.geodesic_rows(*_ops.distance_graph(idx, d2), torch.as_tensor(cells, device=self.device), max_rounds=max_rounds)
         distance = out.dist.cpu().numpy()
         return Pseudotime(distance=distance, pseudotime=_scaled_pseudotime(distance), pred=out.pred.cpu().numpy().astype(np.int64),
@@ -2478,7 +2445,7 @@ class ResidentPredictor:
         vb = self._values_batch(device_csr)
         group = np.asarray(vb.pred if predicted else ids, np.int64)
         group = np.where(group >= 0, group, -1)
-        idx, _ = self._lists_on_device(vb, lists, k, space, metric)
+        idx, _, _ = self._lists_on_device(vb, lists, k, space, metric)
         out = _ops.group_edges(idx, torch.from_numpy(group).to(self.device), K)
         edges, size = out.edges.cpu().numpy(), out.size.cpu().numpy()
         out_edges, expected, conn = _paga_connectivities(edges, size)

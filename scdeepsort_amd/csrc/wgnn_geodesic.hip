@@ -7,23 +7,23 @@
 // holds about 26 entries).  Lane l takes the row's entries l, l + 16, ... and keeps the least (cand, u) it met; the sixteen partial
 // minima fold by halves.  (cand, u) is a total order and its minimum associative and commutative, so neither the lane count nor
 // the fold changes a bit.  A hub row is a longer loop for its sixteen lanes.  Plain C++: no LDS, no scratch, no inline assembly.
+// The integer types, the rowptr clamp, the grid and the n / nnz check are wgnn_graph.h's, shared with the other graph files; that
+// header holds integer code only, so the contraction switched off below covers every floating-point operation of this file.
 #include <float.h>
 #include <limits.h>
 #include <math.h>
-#include "wgnn_common.h"
+#include "wgnn_graph.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 using namespace wgnn;
+using namespace wgnn::graph;
 
 constexpr int kLanes = WGNN_GEODESIC_LANES;        // lanes per row
 constexpr int kRowsPerBlock = 256 / kLanes;
-constexpr int kMaxBlocks = WGNN_GEODESIC_MAX_BLOCKS;
 static_assert(kLanes == 16, "the fold below and include/wgnn.h state sixteen lanes");
-
-typedef long long i64;
-typedef unsigned long long u64;
+static_assert(kMaxBlocks == WGNN_GEODESIC_MAX_BLOCKS, "grid_for's cap is the largest grid include/wgnn.h states");
 
 struct GArgs {
     const i64* rowptr; const int* col; const float* length; long n; long nnz;
@@ -39,8 +39,8 @@ __global__ void __launch_bounds__(256) geodesic_round_kernel(const GArgs a) {
         i64 e0 = a.rowptr[v], e1 = a.rowptr[v + 1];
         if (e0 < 0 || e1 < e0 || e1 > a.nnz || (v == 0 && e0 != 0) || (v == a.n - 1 && e1 != a.nnz)) {
             bits |= WGNN_GEODESIC_BAD_ROWPTR;                      // nothing outside [0, nnz) is read
-            e0 = e0 < 0 ? 0 : (e0 > a.nnz ? a.nnz : e0);
-            e1 = e1 < e0 ? e0 : (e1 > a.nnz ? a.nnz : e1);
+            e0 = clampl(e0, a.nnz);
+            e1 = e1 < e0 ? e0 : (e1 > a.nnz ? a.nnz : e1);     // not clampl: a row that runs backwards is empty
         }
         float best = HUGE_VALF;
         int from = INT_MAX;
@@ -91,8 +91,7 @@ extern "C" int wgnn_geodesic_round(const int64_t* rowptr, const int32_t* col, co
                                    int64_t* changed, int64_t* status, int32_t grid_blocks, uint32_t flags, void* stream) {
     auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_geodesic_round", what); };
     wgnn::error_clear();
-    if (n < 0 || n > INT32_MAX) return fail(WGNN_ERR_BAD_ARG, "n must be in [0, 2^31)");
-    if (nnz < 0) return fail(WGNN_ERR_BAD_ARG, "nnz must not be negative");
+    if (const char* what = check_graph_sizes(n, nnz)) return fail(WGNN_ERR_BAD_ARG, what);
     if (flags) return fail(WGNN_ERR_BAD_ARG, "no flag is defined for this entry (flags must be 0)");
     if (grid_blocks < 0 || grid_blocks > kMaxBlocks) return fail(WGNN_ERR_BAD_ARG, "grid_blocks must be in [0, 8192] (0 = from n)");
     if (!rowptr || !col || !length || !dist_in || !pred_in || !dist_out || !pred_out || !changed || !status)
@@ -108,9 +107,8 @@ extern "C" int wgnn_geodesic_round(const int64_t* rowptr, const int32_t* col, co
     a.rowptr = reinterpret_cast<const i64*>(rowptr); a.col = col; a.length = length; a.n = n; a.nnz = nnz;
     a.dist_in = dist_in; a.pred_in = pred_in; a.dist_out = dist_out; a.pred_out = pred_out;
     a.changed = reinterpret_cast<u64*>(changed); a.status = reinterpret_cast<u64*>(status);
-    const int64_t want = (n + kRowsPerBlock - 1) / kRowsPerBlock;
-    const int64_t cap = grid_blocks ? grid_blocks : kMaxBlocks;
-    hipLaunchKernelGGL(geodesic_round_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), a);
+    unsigned blocks = grid_for(n, kRowsPerBlock);
+    if (grid_blocks && (unsigned)grid_blocks < blocks) blocks = (unsigned)grid_blocks;
+    hipLaunchKernelGGL(geodesic_round_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), a);
     return hipGetLastError() == hipSuccess ? WGNN_OK : fail(WGNN_ERR_LAUNCH, "HIP launch failed");
 }

@@ -4,26 +4,23 @@
 // connected.
 //
 // wgnn_leiden_boundary: a wavefront per row; kinP[v] by a wavefront sum, ext[ref[v]] by one 64-bit atomic per row.
-// wgnn_leiden_refine_sweep: wgnn_louvain_sweep's tables and its three routes by row length, keyed by the refined id of the
-//   neighbours in v's own P-community.  A vertex that may not move leaves before its row is read.
+// wgnn_leiden_refine_sweep: the kin sweep of wgnn_graph.h - wgnn_louvain_sweep's tables and its three routes by row length - with
+//   a policy of its own: keyed by the refined id of the neighbours in v's own P-community.  A vertex that may not move leaves
+//   before its row is read.
 // wgnn_leiden_accept: a thread per vertex.
-#include "wgnn_graph_tables.h"
+#include "wgnn_graph.h"
 
 namespace {
 using namespace wgnn;
 using namespace wgnn::graph;
 
 struct RArgs {
-    const i64* rowptr; const int* col; const int* w; long n; long nnz;
+    KinGraph g;
     const int* P; const int* ref; const i64* deg; const i64* totP; const i64* tot; const int* size;
     const i64* ext; const i64* kinP;
     i64 mden; i64 num; int odd;
-    const int* heavy; int n_heavy; int wave_rows; int block_rows;
-    int* prop; i64* gain; u64* stats;
-    int* scratch; int scratch_blocks;
+    int* prop; i64* gain;
 };
-
-__device__ __forceinline__ bool is_id(int x, long n) { return (unsigned long)(unsigned)x < (unsigned long)n; }
 
 // ref[v] and P[v] are ids and the founder of ref[v] lies in P[v]
 __device__ __forceinline__ bool part_ok(const int* P, const int* ref, long n, long v) {
@@ -31,121 +28,46 @@ __device__ __forceinline__ bool part_ok(const int* P, const int* ref, long n, lo
     return is_id(own, n) && is_id(Pv, n) && P[own] == Pv;
 }
 
-struct Mover { int own; int Pv; i64 degv; i64 totPv; };
+// the refinement's policy for the kin sweep (wgnn_graph.h): the key of a neighbour in v's own P-community is its refined id
+struct Refine {
+    typedef RArgs Args;
+    struct Vertex { int own; int Pv; i64 degv; i64 totPv; };
 
-// may v move?  Alone in its refined community and well connected to its P-community.  The same for every thread of a workgroup.
-__device__ __forceinline__ bool mover(const RArgs& a, long v, Mover& m) {
-    if (!part_ok(a.P, a.ref, a.n, v)) {
-        if ((threadIdx.x & 63) == 0) atomicOr(&a.stats[3], (u64)WGNN_LEIDEN_BAD_PARTITION);
-        return false;
-    }
-    m.own = a.ref[v]; m.Pv = a.P[v]; m.degv = a.deg[v]; m.totPv = a.totP[m.Pv];
-    return a.size[m.own] == 1 && a.kinP[v] * a.mden >= a.num * m.degv * (m.totPv - m.degv);
-}
-
-// the refined community of neighbour u of v for kin: -1 for the diagonal, another P-community, or an id outside [0, n)
-__device__ __forceinline__ int kin_ref(const RArgs& a, long v, int Pv, int u) {
-    if (u == v || !is_id(u, a.n) || a.P[u] != Pv) return -1;
-    const int S = a.ref[u];
-    return is_id(S, a.n) ? S : -1;
-}
-
-// refined community S with kin[S] = kin against the best so far: the gate, S's own well-connectedness, a score above 0; then the
-// total order (higher score, lower id)
-__device__ __forceinline__ void consider_ref(Best& b, const RArgs& a, int S, i64 kin, const Mover& m) {
-    if (S == m.own || (a.odd ? S < m.own : S > m.own) || !is_id(S, a.n)) return;
-    const i64 ts = a.tot[S];
-    if (a.ext[S] * a.mden < a.num * ts * (m.totPv - ts)) return;
-    const i64 s = kin * a.mden - a.num * m.degv * ts;
-    if (s <= 0) return;
-    if (b.c < 0 || s > b.score || (s == b.score && S < b.c)) { b.score = s; b.c = S; }
-}
-
-template <int THREADS, int SLOTS>
-__device__ __forceinline__ Best refine_in_lds(const RArgs& a, long v, i64 e0, i64 e1, const Mover& m, int* keys, int* vals) {
-    const int tid = threadIdx.x;
-    for (int s = tid; s < SLOTS; s += THREADS) { keys[s] = -1; vals[s] = 0; }
-    __syncthreads();
-    for (i64 e = e0 + tid; e < e1; e += THREADS) {
-        const int S = kin_ref(a, v, m.Pv, a.col[e]);
-        if (S >= 0) table_add<SLOTS>(keys, vals, S, a.w[e]);
-    }
-    __syncthreads();
-    Best b{0, -1};
-    for (int s = tid; s < SLOTS; s += THREADS)
-        if (keys[s] >= 0) consider_ref(b, a, keys[s], (i64)vals[s], m);
-    __syncthreads();                                           // the table is free for the next vertex
-    return b;
-}
-
-__device__ __forceinline__ void propose(const RArgs& a, long v, const Best& b) {
-    a.prop[v] = b.c >= 0 ? b.c : a.ref[v];
-    a.gain[v] = b.c >= 0 ? b.score : 0;
-}
-
-__global__ void __launch_bounds__(64) refine_wave_kernel(const RArgs a) {
-    __shared__ int keys[kWaveSlots];
-    __shared__ int vals[kWaveSlots];
-    for (long v = blockIdx.x; v < a.n; v += gridDim.x) {
-        const i64 e0 = clampl(a.rowptr[v], a.nnz), e1 = clampl(a.rowptr[v + 1], a.nnz);
-        if (e1 - e0 > a.wave_rows) continue;                  // the heavy kernel's
-        Mover m;
-        Best b{0, -1};
-        if (e1 > e0 && mover(a, v, m)) {
-            b = refine_in_lds<64, kWaveSlots>(a, v, e0, e1, m, keys, vals);
-            wave_best(b);
+    // may v move?  Alone in its refined community and well connected to its P-community; a malformed partition stays and is
+    // reported.  The same in every thread of the workgroup.
+    static __device__ __forceinline__ bool enter(const RArgs& a, long v, Vertex& x) {
+        if (!part_ok(a.P, a.ref, a.g.n, v)) {
+            if ((threadIdx.x & 63) == 0) atomicOr(&a.g.stats[3], (u64)WGNN_LEIDEN_BAD_PARTITION);
+            return false;
         }
-        if (threadIdx.x == 0) propose(a, v, b);
+        x.own = a.ref[v]; x.Pv = a.P[v]; x.degv = a.deg[v]; x.totPv = a.totP[x.Pv];
+        return a.size[x.own] == 1 && a.kinP[v] * a.mden >= a.num * x.degv * (x.totPv - x.degv);
     }
-}
+    // the refined community of neighbour u of v for kin: -1 for the diagonal, another P-community, or an id outside [0, n)
+    static __device__ __forceinline__ int key(const RArgs& a, const Vertex& x, long v, int u) {
+        if (u == v || !is_id(u, a.g.n) || a.P[u] != x.Pv) return -1;
+        const int S = a.ref[u];
+        return is_id(S, a.g.n) ? S : -1;
+    }
+    static constexpr bool kOwnKin = false;                     // a vertex that may move is alone: staying scores 0
+    // refined community S with kin[S] = kin against the best so far: the gate, S's own well-connectedness, a score above 0; then
+    // the total order (higher score, lower id)
+    static __device__ __forceinline__ void consider(Best& b, const RArgs& a, const Vertex& x, int S, i64 kin) {
+        if (S == x.own || (a.odd ? S < x.own : S > x.own) || !is_id(S, a.g.n)) return;
+        const i64 ts = a.tot[S];
+        if (a.ext[S] * a.mden < a.num * ts * (x.totPv - ts)) return;
+        const i64 s = kin * a.mden - a.num * x.degv * ts;
+        if (s <= 0) return;
+        if (b.c < 0 || s > b.score || (s == b.score && S < b.c)) { b.score = s; b.c = S; }
+    }
+    static __device__ __forceinline__ void write(const RArgs& a, long v, const Vertex&, const Best& b) {
+        a.prop[v] = b.c >= 0 ? b.c : a.ref[v];
+        a.gain[v] = b.c >= 0 ? b.score : 0;
+    }
+};
 
-__global__ void __launch_bounds__(256) refine_heavy_kernel(const RArgs a) {
-    __shared__ int keys[kBlockSlots];
-    __shared__ int vals[kBlockSlots];
-    __shared__ i64 s_score[4];
-    __shared__ int s_c[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int h = blockIdx.x; h < a.n_heavy; h += gridDim.x) {
-        const long v = a.heavy[h];
-        if (v < 0 || v >= a.n) continue;
-        const i64 e0 = clampl(a.rowptr[v], a.nnz), e1 = clampl(a.rowptr[v + 1], a.nnz);
-        Mover m;
-        Best b{0, -1};
-        if (!mover(a, v, m)) {
-            // stays
-        } else if (e1 - e0 <= a.block_rows) {
-            b = refine_in_lds<256, kBlockSlots>(a, v, e0, e1, m, keys, vals);
-        } else if (a.scratch && (int)blockIdx.x < a.scratch_blocks) {
-            int* kin = a.scratch + (size_t)blockIdx.x * a.n;
-            for (i64 e = e0 + tid; e < e1; e += 256) {
-                const int S = kin_ref(a, v, m.Pv, a.col[e]);
-                if (S >= 0) atomicAdd(&kin[S], a.w[e]);
-            }
-            __syncthreads();
-            for (i64 e = e0 + tid; e < e1; e += 256) {         // the sums were made by atomics: read them where those ran
-                const int S = kin_ref(a, v, m.Pv, a.col[e]);
-                if (S >= 0) consider_ref(b, a, S, (i64)__hip_atomic_load(&kin[S], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), m);
-            }
-            __syncthreads();
-            for (i64 e = e0 + tid; e < e1; e += 256) {         // zero again, for the next long row and the next sweep
-                const int S = kin_ref(a, v, m.Pv, a.col[e]);
-                if (S >= 0) __hip_atomic_store(&kin[S], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            __syncthreads();
-        } else {                                               // a long row and no scratch: the caller sized the workspace wrong
-            if (tid == 0) atomicOr(&a.stats[3], (u64)WGNN_LOUVAIN_NO_SCRATCH);
-        }
-        wave_best(b);
-        if (lane == 0) { s_score[wave] = b.score; s_c[wave] = b.c; }
-        __syncthreads();
-        if (tid == 0) {
-            Best all{0, -1};
-            for (int i = 0; i < 4; ++i) merge(all, s_score[i], s_c[i]);
-            propose(a, v, all);
-        }
-        __syncthreads();
-    }
-}
+__global__ void __launch_bounds__(64) refine_wave_kernel(const RArgs a) { kin_sweep_wave<Refine>(a); }
+__global__ void __launch_bounds__(256) refine_heavy_kernel(const RArgs a) { kin_sweep_heavy<Refine>(a); }
 
 struct BArgs { const i64* rowptr; const int* col; const int* w; long n; long nnz; const int* P; const int* ref; u64* ext; i64* kinP; u64* stats; };
 
@@ -228,36 +150,25 @@ extern "C" int wgnn_leiden_refine_sweep(const int64_t* rowptr, const int32_t* co
         return fail(WGNN_ERR_BAD_ARG, "rowptr, col, w, P, ref, deg, totP, tot, size, ext, kinP, prop, gain and stats are required");
     if (m_den < 1 || num < 1) return fail(WGNN_ERR_BAD_ARG, "m_den and num must be positive");
     if (sweep < 0) return fail(WGNN_ERR_BAD_ARG, "sweep must not be negative");
-    if (n_heavy < 0 || (n_heavy > 0 && !heavy)) return fail(WGNN_ERR_BAD_ARG, "n_heavy is negative, or heavy is missing");
-    if (wave_rows < 0 || wave_rows > kWaveRows) return fail(WGNN_ERR_UNSUPPORTED, "wave_rows must be in [0, 128]");
-    if (block_rows < 0 || block_rows > kBlockRows) return fail(WGNN_ERR_UNSUPPORTED, "block_rows must be in [0, 2048]");
-    if (scratch_blocks < 0 || scratch_blocks > kMaxScratchBlocks) return fail(WGNN_ERR_BAD_ARG, "scratch_blocks must be in [0, 256]");
+    if (const Refusal r = check_routes(heavy, n_heavy, wave_rows, block_rows, scratch_blocks); r.code) return fail(r.code, r.what);
     if (!aligned8(rowptr) || !aligned8(deg) || !aligned8(totP) || !aligned8(tot) || !aligned8(ext) || !aligned8(kinP) || !aligned8(gain) ||
         !aligned8(stats))
         return fail(WGNN_ERR_ALIGNMENT, "rowptr, deg, totP, tot, ext, kinP, gain and stats must be 8-byte aligned");
     if (!aligned4(col) || !aligned4(w) || !aligned4(P) || !aligned4(ref) || !aligned4(size) || !aligned4(prop) || !aligned4(heavy))
         return fail(WGNN_ERR_ALIGNMENT, "col, w, P, ref, size, prop and heavy must be 4-byte aligned");
-    if (workspace_bytes < 0) return fail(WGNN_ERR_WORKSPACE, "workspace_bytes is negative");
-    if (scratch_blocks > 0 && (!workspace || workspace_bytes < scratch_bytes(n, scratch_blocks)))
-        return fail(WGNN_ERR_WORKSPACE, "workspace is missing or smaller than wgnn_louvain_sweep_workspace_bytes asks for");
-    if (!aligned4(workspace)) return fail(WGNN_ERR_ALIGNMENT, "workspace must be 4-byte aligned");
+    if (const Refusal r = check_scratch(n, workspace, workspace_bytes, scratch_blocks); r.code) return fail(r.code, r.what);
     if (n == 0) return WGNN_OK;
 
     RArgs a{};
-    a.rowptr = reinterpret_cast<const i64*>(rowptr); a.col = col; a.w = w; a.n = n; a.nnz = nnz;
+    a.g = kin_graph(rowptr, col, w, n, nnz, heavy, n_heavy, wave_rows, block_rows, workspace, scratch_blocks, stats);
     a.P = P; a.ref = ref; a.deg = reinterpret_cast<const i64*>(deg); a.totP = reinterpret_cast<const i64*>(totP);
     a.tot = reinterpret_cast<const i64*>(tot); a.size = size;
     a.ext = reinterpret_cast<const i64*>(ext); a.kinP = reinterpret_cast<const i64*>(kinP);
     a.mden = m_den; a.num = num; a.odd = sweep & 1;
-    a.heavy = heavy; a.n_heavy = n_heavy; a.wave_rows = wave_rows; a.block_rows = block_rows;
-    a.prop = prop; a.gain = reinterpret_cast<i64*>(gain); a.stats = reinterpret_cast<u64*>(stats);
-    a.scratch = scratch_blocks > 0 ? static_cast<int*>(workspace) : nullptr; a.scratch_blocks = scratch_blocks;
+    a.prop = prop; a.gain = reinterpret_cast<i64*>(gain);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(refine_wave_kernel, dim3(grid_for(n, 1)), dim3(64), 0, st, a);
-    if (n_heavy > 0) {
-        const unsigned blocks = scratch_blocks > 0 ? (unsigned)(n_heavy < scratch_blocks ? n_heavy : scratch_blocks) : grid_for(n_heavy, 1);
-        hipLaunchKernelGGL(refine_heavy_kernel, dim3(blocks), dim3(256), 0, st, a);
-    }
+    if (n_heavy > 0) hipLaunchKernelGGL(refine_heavy_kernel, dim3(heavy_grid(n_heavy, scratch_blocks)), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? WGNN_OK : fail(WGNN_ERR_LAUNCH, "HIP launch failed");
 }
 

@@ -6,17 +6,14 @@
 // union graph the lanes load j's list and count the distinct entries of N+(i) = {i} + list(i) that are in N+(j).
 //
 // wgnn_louvain_sweep: every vertex reads the state before the sweep (comm, tot, size) and leaves the community it moves to and
-// its gain.  kin[C], the weight from v into community C, is collected in a table keyed by the community id:
-//   - rows of at most wave_rows (<= 128) entries: one wavefront (a workgroup of 64 threads), an LDS table of 256 slots;
-//   - rows of at most block_rows (<= 2048) entries: a workgroup of 256 threads, an LDS table of 4096 slots;
-//   - longer rows (a hub cell): a workgroup with a dense int32 scratch per community in global memory, zero before and after.
-// Tables are open addressing, a compare-and-swap on the key and an integer add on the value; at most half full
-// (wgnn_graph_tables.h, shared with wgnn_leiden.hip).
+// its gain.  kin[C], the weight from v into community C, is collected in a table keyed by the community id by the kin sweep of
+// wgnn_graph.h - its three routes by row length, its tables and its scratch are there, shared with wgnn_leiden.hip; here is only
+// the policy: the key, the score and what is written.
 //
 // wgnn_louvain_apply: tot / size of an assignment by 64-bit integer atomics, and how many vertices moved.
 // wgnn_louvain_modularity: IN (the stored weight inside communities, the diagonal included) and sum tot^2, and the checks of the
 // CSR that need the entries (status bits).
-#include "wgnn_graph_tables.h"
+#include "wgnn_graph.h"
 
 namespace {
 using namespace wgnn;
@@ -64,141 +61,55 @@ __global__ void __launch_bounds__(256) snn_weights_kernel(const GArgs a) {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 struct LArgs {
-    const i64* rowptr; const int* col; const int* w; long n; long nnz;
+    KinGraph g;
     const int* comm; const i64* deg; const i64* tot; const int* size;
     i64 mden; i64 num; int odd;
-    const int* heavy; int n_heavy; int wave_rows; int block_rows;
-    int* next; i64* gain; u64* stats;
-    int* scratch; int scratch_blocks;
+    int* next; i64* gain;
 };
 
-// the community of neighbour u of v for kin: -1 for the diagonal, for a column or a community id outside [0, n)
-__device__ __forceinline__ int kin_comm(const LArgs& a, long v, int u) {
-    if (u == v || (unsigned long)(unsigned)u >= (unsigned long)a.n) return -1;
-    const int C = a.comm[u];
-    return (unsigned long)(unsigned)C < (unsigned long)a.n ? C : -1;
-}
-// v's own community, or -1 (and the status bit) when comm[v] is no id
-__device__ __forceinline__ int own_comm(const LArgs& a, long v) {
-    const int own = a.comm[v];
-    if ((unsigned long)(unsigned)own < (unsigned long)a.n) return own;
-    if ((threadIdx.x & 63) == 0) atomicOr(&a.stats[3], (u64)WGNN_LOUVAIN_BAD_LABEL);
-    return -1;
-}
+// the sweep's policy for the kin sweep (wgnn_graph.h): the key of a neighbour is its community
+struct Move {
+    typedef LArgs Args;
+    struct Vertex { int own; int size_own; i64 degv; i64 score_own; };
 
-// community C with kin[C] = kin against the best so far: the gate, the singleton rule, a score above the own one; then the total
-// order (higher score, lower id).  Seeing a community twice changes nothing.
-__device__ __forceinline__ void consider(Best& b, const LArgs& a, int C, i64 kin, int own, i64 degv, int size_own, i64 score_own) {
-    if (C == own || (a.odd ? C < own : C > own) || (unsigned long)(unsigned)C >= (unsigned long)a.n) return;
-    if (size_own == 1 && C > own && a.size[C] == 1) return;
-    const i64 s = kin * a.mden - a.num * degv * a.tot[C];
-    if (s <= score_own) return;
-    if (b.c < 0 || s > b.score || (s == b.score && C < b.c)) { b.score = s; b.c = C; }
-}
-// one vertex by the THREADS threads of a workgroup through an LDS table of SLOTS slots (the row has at most SLOTS / 2 entries)
-template <int THREADS, int SLOTS>
-__device__ __forceinline__ Best vertex_in_lds(const LArgs& a, long v, i64 e0, i64 e1, int* keys, int* vals, i64* score_own_out) {
-    const int tid = threadIdx.x;
-    for (int s = tid; s < SLOTS; s += THREADS) { keys[s] = -1; vals[s] = 0; }
-    __syncthreads();
-    for (i64 e = e0 + tid; e < e1; e += THREADS) {
-        const int C = kin_comm(a, v, a.col[e]);
-        if (C >= 0) table_add<SLOTS>(keys, vals, C, a.w[e]);
-    }
-    __syncthreads();
-    const int own = own_comm(a, v);
-    const i64 degv = a.deg[v];
-    i64 score_own = 0;
-    Best b{0, -1};
-    if (own >= 0) {
-        const int size_own = a.size[own];
-        score_own = (i64)table_get<SLOTS>(keys, vals, own) * a.mden - a.num * degv * (a.tot[own] - degv);
-        for (int s = tid; s < SLOTS; s += THREADS)
-            if (keys[s] >= 0) consider(b, a, keys[s], (i64)vals[s], own, degv, size_own, score_own);
-    }
-    __syncthreads();                                           // the table is free for the next vertex
-    *score_own_out = score_own;
-    return b;
-}
-
-__device__ __forceinline__ void leave(const LArgs& a, long v, const Best& b, i64 score_own) {
-    a.next[v] = b.c >= 0 ? b.c : a.comm[v];                   // stays where it is
-    a.gain[v] = b.c >= 0 ? b.score - score_own : 0;
-}
-
-// rows of at most wave_rows entries: a workgroup IS a wavefront, so its barriers cost nothing
-__global__ void __launch_bounds__(64) sweep_wave_kernel(const LArgs a) {
-    __shared__ int keys[kWaveSlots];
-    __shared__ int vals[kWaveSlots];
-    for (long v = blockIdx.x; v < a.n; v += gridDim.x) {
-        const i64 e0 = clampl(a.rowptr[v], a.nnz), e1 = clampl(a.rowptr[v + 1], a.nnz);
-        if (e1 - e0 > a.wave_rows) continue;                  // the heavy kernel's
-        if (e1 <= e0) {                                        // no edge: stays
-            if (threadIdx.x == 0) { a.next[v] = a.comm[v]; a.gain[v] = 0; }
-            continue;
+    // v's own community; a comm[v] that is no id stays and is reported.  The same in every thread of the workgroup.
+    static __device__ __forceinline__ bool enter(const LArgs& a, long v, Vertex& x) {
+        x.own = a.comm[v];
+        if (!is_id(x.own, a.g.n)) {
+            if ((threadIdx.x & 63) == 0) atomicOr(&a.g.stats[3], (u64)WGNN_LOUVAIN_BAD_LABEL);
+            return false;
         }
-        i64 score_own;
-        Best b = vertex_in_lds<64, kWaveSlots>(a, v, e0, e1, keys, vals, &score_own);
-        wave_best(b);
-        if (threadIdx.x == 0) leave(a, v, b, score_own);
+        x.size_own = a.size[x.own]; x.degv = a.deg[v];
+        return true;
     }
-}
+    // the community of neighbour u of v for kin: -1 for the diagonal, for a column or a community id outside [0, n)
+    static __device__ __forceinline__ int key(const LArgs& a, const Vertex&, long v, int u) {
+        if (u == v || !is_id(u, a.g.n)) return -1;
+        const int C = a.comm[u];
+        return is_id(C, a.g.n) ? C : -1;
+    }
+    static constexpr bool kOwnKin = true;                      // staying has a score of its own
+    static __device__ __forceinline__ int own(const Vertex& x) { return x.own; }
+    static __device__ __forceinline__ void own_kin(const LArgs& a, Vertex& x, i64 kin) {
+        x.score_own = kin * a.mden - a.num * x.degv * (a.tot[x.own] - x.degv);
+    }
+    // community C with kin[C] = kin against the best so far: the gate, the singleton rule, a score above the own one; then the
+    // total order (higher score, lower id).  Seeing a community twice changes nothing.
+    static __device__ __forceinline__ void consider(Best& b, const LArgs& a, const Vertex& x, int C, i64 kin) {
+        if (C == x.own || (a.odd ? C < x.own : C > x.own) || !is_id(C, a.g.n)) return;
+        if (x.size_own == 1 && C > x.own && a.size[C] == 1) return;
+        const i64 s = kin * a.mden - a.num * x.degv * a.tot[C];
+        if (s <= x.score_own) return;
+        if (b.c < 0 || s > b.score || (s == b.score && C < b.c)) { b.score = s; b.c = C; }
+    }
+    static __device__ __forceinline__ void write(const LArgs& a, long v, const Vertex& x, const Best& b) {
+        a.next[v] = b.c >= 0 ? b.c : a.comm[v];               // stays where it is
+        a.gain[v] = b.c >= 0 ? b.score - x.score_own : 0;
+    }
+};
 
-// the rows above wave_rows (heavy[]): an LDS table up to block_rows entries, the workgroup's dense scratch beyond
-__global__ void __launch_bounds__(256) sweep_heavy_kernel(const LArgs a) {
-    __shared__ int keys[kBlockSlots];
-    __shared__ int vals[kBlockSlots];
-    __shared__ i64 s_score[4];
-    __shared__ int s_c[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int h = blockIdx.x; h < a.n_heavy; h += gridDim.x) {
-        const long v = a.heavy[h];
-        if (v < 0 || v >= a.n) continue;
-        const i64 e0 = clampl(a.rowptr[v], a.nnz), e1 = clampl(a.rowptr[v + 1], a.nnz);
-        i64 score_own = 0;
-        Best b{0, -1};
-        if (e1 - e0 <= a.block_rows) {
-            b = vertex_in_lds<256, kBlockSlots>(a, v, e0, e1, keys, vals, &score_own);
-        } else if (a.scratch && (int)blockIdx.x < a.scratch_blocks) {
-            int* kin = a.scratch + (size_t)blockIdx.x * a.n;
-            for (i64 e = e0 + tid; e < e1; e += 256) {
-                const int C = kin_comm(a, v, a.col[e]);
-                if (C >= 0) atomicAdd(&kin[C], a.w[e]);
-            }
-            __syncthreads();
-            const int own = own_comm(a, v);
-            const i64 degv = a.deg[v];
-            if (own >= 0) {                                    // the sums were made by atomics: read them where those ran
-                const int size_own = a.size[own];
-                score_own = (i64)__hip_atomic_load(&kin[own], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) * a.mden
-                            - a.num * degv * (a.tot[own] - degv);
-                for (i64 e = e0 + tid; e < e1; e += 256) {
-                    const int C = kin_comm(a, v, a.col[e]);
-                    if (C >= 0)
-                        consider(b, a, C, (i64)__hip_atomic_load(&kin[C], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), own, degv,
-                                 size_own, score_own);
-                }
-            }
-            __syncthreads();
-            for (i64 e = e0 + tid; e < e1; e += 256) {         // zero again, for the next long row and the next sweep
-                const int C = kin_comm(a, v, a.col[e]);
-                if (C >= 0) __hip_atomic_store(&kin[C], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            __syncthreads();
-        } else {                                               // a long row and no scratch: the caller sized the workspace wrong
-            if (tid == 0) atomicOr(&a.stats[3], (u64)WGNN_LOUVAIN_NO_SCRATCH);
-        }
-        wave_best(b);
-        if (lane == 0) { s_score[wave] = b.score; s_c[wave] = b.c; }
-        __syncthreads();
-        if (tid == 0) {
-            Best all{0, -1};
-            for (int i = 0; i < 4; ++i) merge(all, s_score[i], s_c[i]);
-            leave(a, v, all, score_own);
-        }
-        __syncthreads();
-    }
-}
+__global__ void __launch_bounds__(64) sweep_wave_kernel(const LArgs a) { kin_sweep_wave<Move>(a); }
+__global__ void __launch_bounds__(256) sweep_heavy_kernel(const LArgs a) { kin_sweep_heavy<Move>(a); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 struct AArgs { const int* old_label; const int* label; const i64* deg; long n; u64* tot; int* size; u64* stats; };
@@ -296,33 +207,22 @@ extern "C" int wgnn_louvain_sweep(const int64_t* rowptr, const int32_t* col, con
         return fail(WGNN_ERR_BAD_ARG, "rowptr, col, w, comm, deg, tot, size, next, gain and stats are required");
     if (m_den < 1 || num < 1) return fail(WGNN_ERR_BAD_ARG, "m_den and num must be positive");
     if (sweep < 0) return fail(WGNN_ERR_BAD_ARG, "sweep must not be negative");
-    if (n_heavy < 0 || (n_heavy > 0 && !heavy)) return fail(WGNN_ERR_BAD_ARG, "n_heavy is negative, or heavy is missing");
-    if (wave_rows < 0 || wave_rows > kWaveRows) return fail(WGNN_ERR_UNSUPPORTED, "wave_rows must be in [0, 128]");
-    if (block_rows < 0 || block_rows > kBlockRows) return fail(WGNN_ERR_UNSUPPORTED, "block_rows must be in [0, 2048]");
-    if (scratch_blocks < 0 || scratch_blocks > kMaxScratchBlocks) return fail(WGNN_ERR_BAD_ARG, "scratch_blocks must be in [0, 256]");
+    if (const Refusal r = check_routes(heavy, n_heavy, wave_rows, block_rows, scratch_blocks); r.code) return fail(r.code, r.what);
     if (!aligned8(rowptr) || !aligned8(deg) || !aligned8(tot) || !aligned8(gain) || !aligned8(stats))
         return fail(WGNN_ERR_ALIGNMENT, "rowptr, deg, tot, gain and stats must be 8-byte aligned");
     if (!aligned4(col) || !aligned4(w) || !aligned4(comm) || !aligned4(size) || !aligned4(next) || !aligned4(heavy))
         return fail(WGNN_ERR_ALIGNMENT, "col, w, comm, size, next and heavy must be 4-byte aligned");
-    if (workspace_bytes < 0) return fail(WGNN_ERR_WORKSPACE, "workspace_bytes is negative");
-    if (scratch_blocks > 0 && (!workspace || workspace_bytes < scratch_bytes(n, scratch_blocks)))
-        return fail(WGNN_ERR_WORKSPACE, "workspace is missing or smaller than wgnn_louvain_sweep_workspace_bytes asks for");
-    if (!aligned4(workspace)) return fail(WGNN_ERR_ALIGNMENT, "workspace must be 4-byte aligned");
+    if (const Refusal r = check_scratch(n, workspace, workspace_bytes, scratch_blocks); r.code) return fail(r.code, r.what);
     if (n == 0) return WGNN_OK;
 
     LArgs a{};
-    a.rowptr = reinterpret_cast<const i64*>(rowptr); a.col = col; a.w = w; a.n = n; a.nnz = nnz;
+    a.g = kin_graph(rowptr, col, w, n, nnz, heavy, n_heavy, wave_rows, block_rows, workspace, scratch_blocks, stats);
     a.comm = comm; a.deg = reinterpret_cast<const i64*>(deg); a.tot = reinterpret_cast<const i64*>(tot); a.size = size;
     a.mden = m_den; a.num = num; a.odd = sweep & 1;
-    a.heavy = heavy; a.n_heavy = n_heavy; a.wave_rows = wave_rows; a.block_rows = block_rows;
-    a.next = next; a.gain = reinterpret_cast<i64*>(gain); a.stats = reinterpret_cast<u64*>(stats);
-    a.scratch = scratch_blocks > 0 ? static_cast<int*>(workspace) : nullptr; a.scratch_blocks = scratch_blocks;
+    a.next = next; a.gain = reinterpret_cast<i64*>(gain);
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(sweep_wave_kernel, dim3(grid_for(n, 1)), dim3(64), 0, st, a);
-    if (n_heavy > 0) {
-        const unsigned blocks = scratch_blocks > 0 ? (unsigned)(n_heavy < scratch_blocks ? n_heavy : scratch_blocks) : grid_for(n_heavy, 1);
-        hipLaunchKernelGGL(sweep_heavy_kernel, dim3(blocks), dim3(256), 0, st, a);
-    }
+    if (n_heavy > 0) hipLaunchKernelGGL(sweep_heavy_kernel, dim3(heavy_grid(n_heavy, scratch_blocks)), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? WGNN_OK : fail(WGNN_ERR_LAUNCH, "HIP launch failed");
 }
 

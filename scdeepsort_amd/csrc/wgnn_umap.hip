@@ -10,26 +10,24 @@
 // wgnn_layout_epoch: WGNN_LAYOUT_LANES = 16 lanes per vertex.  Lane l takes the row's edges l, l + 16, ... in order and adds each
 //   edge's terms (the attraction, then the negatives) to its own partial; the partials fold 8, 4, 2, 1.  Reads y_in only, writes
 //   y_out only: no atomics, no scratch, and a hub row is a longer loop for its sixteen lanes.
+// The integer types, the rowptr clamp, the grid and the n / nnz check are wgnn_graph.h's, shared with the other graph files; that
+// header holds integer code only.
 #include <float.h>
 #include <limits.h>
 #include <math.h>
 #include "wgnn_resident_rows.h"
+#include "wgnn_graph.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 using namespace wgnn;
+using namespace wgnn::graph;
 
 constexpr int kMaxK = 64;
 constexpr int kLanes = WGNN_LAYOUT_LANES;          // lanes per vertex (and per row of the union)
 constexpr int kRowsPerBlock = 256 / kLanes;
-constexpr int kMaxBlocks = 8192;
 static_assert(kLanes == 16, "the fold below and include/wgnn.h state sixteen lanes");
-
-typedef long long i64;
-typedef unsigned long long u64;
-
-__device__ __forceinline__ i64 clampl(i64 v, i64 hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
 struct FArgs {
@@ -189,17 +187,6 @@ __global__ void __launch_bounds__(256) layout_epoch_kernel(const LArgs a) {
             if (a.fired) a.fired[i] += fired;
         }
     }
-}
-
-unsigned grid_for(int64_t items, int per_block) {
-    const int64_t want = (items + per_block - 1) / per_block;
-    return (unsigned)(want < 1 ? 1 : (want < kMaxBlocks ? want : kMaxBlocks));
-}
-
-const char* check_graph_sizes(int64_t n, int64_t nnz) {
-    if (n < 0 || n > INT32_MAX) return "n must be in [0, 2^31)";
-    if (nnz < 0) return "nnz must not be negative";
-    return nullptr;
 }
 
 }  // namespace

@@ -894,6 +894,19 @@ def _csr_operand(name, exc, rowptr, col, val, val_name):
     return rowptr.contiguous(), col.contiguous(), val.contiguous(), int(rowptr.shape[0]) - 1, int(col.shape[0]), flags
 
 
+def _graph_operand(name, rowptr, col, val, val_name, dtype):
+    """A device CSR graph - ``rowptr`` int64 [B + 1], ``col`` int32 [nnz] and one ``dtype`` value the op calls ``val_name`` per
+    stored entry - checked: ``(rowptr, col, val, B, nnz)``, the tensors contiguous as the C entries take them.  Whether ``rowptr``
+    runs from 0 to ``nnz`` is the caller's to check: each reports it in its own way."""
+    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
+            val.dtype != dtype or val.shape != col.shape:
+        raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and {val_name} {str(dtype)[6:]} [nnz] are expected")
+    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+    if B >= 2 ** 31:
+        raise ValueError(f"{name}: B must be below 2^31")
+    return rowptr.contiguous(), col.contiguous(), val.contiguous(), B, nnz
+
+
 def _group_operand(name, exc, group, B, K, check, dtypes=(torch.int32, torch.int64), says=None):
     """The per-cell group vector [B] - an id in ``[0, K)``, or -1 = the cell takes no part - checked: shape and dtype (``says``:
     the op's own words for that refusal), and with ``check`` the range (one ``aminmax`` and a read-back).  Returns ``group`` as
@@ -2502,16 +2515,10 @@ class _GraphRun:
                 not 1 <= scratch_blocks <= LOUVAIN_SCRATCH_BLOCKS:
             raise ValueError(f"{name}: wave_rows in [0, {LOUVAIN_WAVE_ROWS}], block_rows in [0, {LOUVAIN_BLOCK_ROWS}] and scratch_blocks in "
                              f"[1, {LOUVAIN_SCRATCH_BLOCKS}], got {wave_rows}, {block_rows}, {scratch_blocks}")
-        if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
-                w.dtype != torch.int32 or w.shape != col.shape:
-            raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and w int32 [nnz] are expected")
+        self.rowptr, self.col, self.w, self.B, nnz = _graph_operand(name, rowptr, col, w, "w", torch.int32)
         self.max_sweeps, self.wave_rows, self.block_rows, self.scratch_blocks = max_sweeps, wave_rows, block_rows, scratch_blocks
         self.frac = frac = louvain_resolution(resolution)
         self.num, self.den = num, den = frac.numerator, frac.denominator
-        self.B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
-        if self.B >= 2 ** 31:
-            raise ValueError(f"{name}: B must be below 2^31")
-        self.rowptr, self.col, self.w = rowptr.contiguous(), col.contiguous(), w.contiguous()
         self.M = M = int(w.sum(dtype=torch.int64)) if nnz else 0
         if M * M * max(num, den) >= 2 ** 62:
             raise ValueError(f"{name}: M * M * max(num, den) = {M * M * max(num, den)} >= 2^62 (M = {M}, resolution {frac}): the "
@@ -2564,26 +2571,20 @@ class _GraphRun:
         _check_status(self.name, status, self.status)
         return tot, size, moved, self.den * self.M * inside - self.num * tot2
 
-    def move(self, comm):
-        """The moving phase of a level from the partition ``comm``: ``(comm, tot, sweeps, fallback moves)``; the trace grows."""
-        dev, name, n, nnz, trace = self.dev, self.name, self.n, self.nnz, self.trace
-        rowptr, col, w = self.graph
-        tot, size, _, q = self.measure(None, comm)                  # the start's state, and the graph's checks
-        if trace is None:
-            self.trace = trace = [q]
-        elif q != trace[-1]:                                        # aggregation keeps the partition, so Qnum too
-            raise WgnnError(f"{name}: Qnum changed across the aggregation ({trace[-1]} -> {q})")
+    def sweeps(self, label, tot, size, q0, propose, what):
+        """The sweeps of a phase from the labelling ``label`` with its ``tot`` / ``size`` and ``Qnum`` ``q0``, until two in a row
+        move nothing or ``max_sweeps``: ``(label, tot, sweeps, fallback moves, the Qnum after every kept step)``.
+        ``propose(t, label, tot, size)`` enqueues sweep ``t``'s launches and returns ``(next, gain)``; ``measure`` is the one
+        read-back per sweep.  A sweep is kept when ``Qnum`` rose, else discarded for its single best move (largest gain, lowest
+        vertex) - ``what`` names that move when it does not raise ``Qnum`` either."""
         t = idle = fallback = 0
+        kept = []
         while True:
             if t >= self.max_sweeps:
                 self.converged = False
                 break
-            nxt = torch.empty(n, dtype=torch.int32, device=dev)
-            gain = torch.empty(n, dtype=torch.int64, device=dev)
-            _lib.run(dev, "wgnn_louvain_sweep", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(comm), _ptr(self.deg), _ptr(tot),
-                     _ptr(size), self.M * self.den, self.num, t, *self.routes(), _ptr(nxt), _ptr(gain), _ptr(self.stats),
-                     *self.scratch(), 0, self.stream)
-            tot2, size2, moved, q = self.measure(comm, nxt)
+            nxt, gain = propose(t, label, tot, size)
+            tot2, size2, moved, q = self.measure(label, nxt)
             t += 1
             if moved == 0:
                 idle += 1
@@ -2591,19 +2592,41 @@ class _GraphRun:
                     break
                 continue
             idle = 0
-            if q > trace[-1]:
-                comm, tot, size = nxt, tot2, size2
+            if q > q0:
+                label, tot, size = nxt, tot2, size2
             else:                                                   # discarded: the single best move, ties to the lowest vertex
                 v = int(torch.nonzero(gain == gain.max()).reshape(-1)[0])
-                one = comm.clone()
+                one = label.clone()
                 one[v] = nxt[v]
-                tot, size, _, q = self.measure(comm, one)
-                if q <= trace[-1]:
-                    raise WgnnError(f"{name}: a single positive-gain move did not raise Qnum ({trace[-1]} -> {q}): the graph is "
-                                    "not symmetric")
-                comm = one
+                tot, size, _, q = self.measure(label, one)
+                if q <= q0:
+                    raise WgnnError(f"{self.name}: a single {what} move did not raise Qnum ({q0} -> {q}): the graph is not symmetric")
+                label = one
                 fallback += 1
-            trace.append(q)
+            q0 = q
+            kept.append(q)
+        return label, tot, t, fallback, kept
+
+    def move(self, comm):
+        """The moving phase of a level from the partition ``comm``: ``(comm, tot, sweeps, fallback moves)``; the trace grows."""
+        dev, name, n, nnz = self.dev, self.name, self.n, self.nnz
+        rowptr, col, w = self.graph
+        tot, size, _, q = self.measure(None, comm)                  # the start's state, and the graph's checks
+        if self.trace is None:
+            self.trace = [q]
+        elif q != self.trace[-1]:                                   # aggregation keeps the partition, so Qnum too
+            raise WgnnError(f"{name}: Qnum changed across the aggregation ({self.trace[-1]} -> {q})")
+
+        def propose(t, comm, tot, size):
+            nxt = torch.empty(n, dtype=torch.int32, device=dev)
+            gain = torch.empty(n, dtype=torch.int64, device=dev)
+            _lib.run(dev, "wgnn_louvain_sweep", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(comm), _ptr(self.deg), _ptr(tot),
+                     _ptr(size), self.M * self.den, self.num, t, *self.routes(), _ptr(nxt), _ptr(gain), _ptr(self.stats),
+                     *self.scratch(), 0, self.stream)
+            return nxt, gain
+
+        comm, tot, t, fallback, kept = self.sweeps(comm, tot, size, q, propose, "positive-gain")
+        self.trace += kept
         return comm, tot, t, fallback
 
     def coarsen(self, inv, nc):
@@ -2696,18 +2719,15 @@ _LEIDEN_STATUS = _LOUVAIN_STATUS + ((_lib.LEIDEN_BAD_PARTITION, "a refined or mo
 
 def _leiden_refine(run: _GraphRun, P: torch.Tensor, totP: torch.Tensor):
     """The refinement of one level inside the partition ``P``: ``(ref, sweeps, fallback moves)``.  Per sweep five launches
-    (boundary, refine sweep, accept, apply, modularity) and one read-back."""
-    dev, name, n, nnz, stats, stream = run.dev, run.name, run.n, run.nnz, run.stats, run.stream
+    (boundary, refine sweep, accept, apply, modularity) and one read-back; the running ``Qnum`` is the loop's own, not the trace's."""
+    dev, n, nnz, stats, stream = run.dev, run.n, run.nnz, run.stats, run.stream
     rowptr, col, w = run.graph
     ref = torch.arange(n, dtype=torch.int32, device=dev)
-    tot, size, _, running = run.measure(None, ref)
+    tot, size, _, q = run.measure(None, ref)
     ext = torch.empty(n, dtype=torch.int64, device=dev)
     kinP = torch.empty(n, dtype=torch.int64, device=dev)
-    r = idle = fallback = 0
-    while True:
-        if r >= run.max_sweeps:
-            run.converged = False
-            break
+
+    def propose(r, ref, tot, size):
         prop, nxt = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
         gain = torch.empty(n, dtype=torch.int64, device=dev)
         _lib.run(dev, "wgnn_leiden_boundary", _ptr(rowptr), _ptr(col), _ptr(w), n, nnz, _ptr(P), _ptr(ref), _ptr(ext),
@@ -2716,26 +2736,9 @@ def _leiden_refine(run: _GraphRun, P: torch.Tensor, totP: torch.Tensor):
                  _ptr(totP), _ptr(tot), _ptr(size), _ptr(ext), _ptr(kinP), run.M * run.den, run.num, r, *run.routes(), _ptr(prop),
                  _ptr(gain), _ptr(stats), *run.scratch(), 0, stream)
         _lib.run(dev, "wgnn_leiden_accept", _ptr(ref), _ptr(prop), n, _ptr(nxt), _ptr(gain), _ptr(stats), 0, stream)
-        tot2, size2, moved, q = run.measure(ref, nxt)               # counts the accepted moves again: the one read-back
-        r += 1
-        if moved == 0:
-            idle += 1
-            if idle == 2:
-                break
-            continue
-        idle = 0
-        if q > running:
-            ref, tot, size = nxt, tot2, size2
-        else:                                                       # discarded: the single best accepted move, the lowest vertex
-            v = int(torch.nonzero(gain == gain.max()).reshape(-1)[0])
-            one = ref.clone()
-            one[v] = nxt[v]
-            tot, size, _, q = run.measure(ref, one)
-            if q <= running:
-                raise WgnnError(f"{name}: a single accepted move did not raise Qnum ({running} -> {q}): the graph is not symmetric")
-            ref = one
-            fallback += 1
-        running = q
+        return nxt, gain                                            # measure counts the accepted moves again: the one read-back
+
+    ref, _, r, fallback, _ = run.sweeps(ref, tot, size, q, propose, "accepted")
     return ref, r, fallback
 
 
@@ -2843,17 +2846,14 @@ def fuzzy_graph(idx: torch.Tensor, d2: torch.Tensor) -> FuzzyGraph:
     ``d2`` is a ``ValueError``.  Returns a ``FuzzyGraph``."""
     name = "fuzzy_graph"
     dev = _require_cuda(idx, d2)
-    if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
-        raise ValueError(f"{name}: idx must be a 2-D int32 / int64 tensor [B, k]")
-    B, k = int(idx.shape[0]), int(idx.shape[1])
-    if not 1 <= k <= FUZZY_MAX_K:
-        raise ValueError(f"{name}: k = {k} is outside [1, {FUZZY_MAX_K}]")
+    B, k, src, dst = _list_entries(name, idx)                                   # rank, dtype, k and the ids
     if not _row_strided(idx, B, k):
         raise ValueError(f"{name}: idx must have unit column stride and a row stride >= {k}")
     _view_2d(name, ValueError, "d2", d2, torch.float32, B, k)
     if B and bool((d2 < 0).any()):
         raise ValueError(f"{name}: d2 holds a negative squared distance")
-    rowptr, col, _ = snn_graph(idx, "unit")                                     # checks the ids
+    listed = (dst >= 0) & (dst != src)
+    rowptr, col, _ = _union_csr(B, src[listed], dst[listed])                    # snn_graph(idx, "unit")'s structure
     rho = torch.empty(B, dtype=torch.float64, device=dev)
     sigma = torch.empty(B, dtype=torch.float64, device=dev)
     member = torch.empty((B, k), dtype=torch.float32, device=dev)
@@ -2916,12 +2916,7 @@ def layout_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, init=
     ``WgnnError``.  Returns a ``LayoutRows``."""
     name = "layout_graph"
     dev = _require_cuda(rowptr, col, w, init if isinstance(init, torch.Tensor) else None)
-    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
-            w.dtype != torch.float32 or w.shape != col.shape:
-        raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and w float32 [nnz] are expected")
-    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
-    if B >= 2 ** 31:
-        raise ValueError(f"{name}: B must be below 2^31")
+    rowptr, col, w, B, nnz = _graph_operand(name, rowptr, col, w, "w", torch.float32)
     n_epochs = layout_epochs(B) if n_epochs is None else int(n_epochs)
     n_neg, seed = int(n_neg), int(seed)
     if not 1 <= n_epochs <= LAYOUT_MAX_EPOCHS:
@@ -2943,7 +2938,6 @@ def layout_graph(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, init=
         _lib.run(dev, "wgnn_layout_init", _ptr(y), B, seed, 0, stream)
     else:
         raise ValueError(f"{name}: init = {init!r}: pass a float32 [{B}, 2] tensor or one of {', '.join(map(repr, LAYOUT_INITS))}")
-    rowptr, col, w = rowptr.contiguous(), col.contiguous(), w.contiguous()
     zero = torch.zeros((), dtype=torch.float32, device=dev)
     wmax, wmin, bad_w, bad_y = torch.stack([w.max() if nnz else zero, w.min() if nnz else zero,
                                             (~torch.isfinite(w)).sum().float(), (~torch.isfinite(y)).sum().float()]).tolist()
@@ -3066,12 +3060,7 @@ def geodesic_rows(rowptr: torch.Tensor, col: torch.Tensor, length: torch.Tensor,
     tensors raise ``WgnnError``.  Returns a ``GeodesicRows``."""
     name = "geodesic_rows"
     dev = _require_cuda(rowptr, col, length, roots if isinstance(roots, torch.Tensor) else None)
-    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32 or \
-            length.dtype != torch.float32 or length.shape != col.shape:
-        raise ValueError(f"{name}: rowptr int64 [B + 1], col int32 [nnz] and length float32 [nnz] are expected")
-    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
-    if B >= 2 ** 31:
-        raise ValueError(f"{name}: B must be below 2^31")
+    rowptr, col, length, B, nnz = _graph_operand(name, rowptr, col, length, "length", torch.float32)
     max_rounds = B if max_rounds is None else int(max_rounds)
     check_every, grid_blocks = int(check_every), int(grid_blocks)
     if max_rounds < 0:
@@ -3083,7 +3072,6 @@ def geodesic_rows(rowptr: torch.Tensor, col: torch.Tensor, length: torch.Tensor,
     dist = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
     dist[_geodesic_roots(name, roots, B, dev)] = 0.0
     pred = torch.full((B,), -1, dtype=torch.int32, device=dev)
-    rowptr, col, length = rowptr.contiguous(), col.contiguous(), length.contiguous()
     stream = _stream(dev)
     dist2, pred2 = torch.empty_like(dist), torch.empty_like(pred)
     slots = torch.empty(check_every + 1, dtype=torch.int64, device=dev)        # one counter per round of a batch, then the status
