@@ -1566,6 +1566,80 @@ int wgnn_geodesic_round(const int64_t* rowptr, const int32_t* col, const float* 
                         const float* dist_in, const int32_t* pred_in, float* dist_out, int32_t* pred_out,
                         int64_t* changed, int64_t* status, int32_t grid_blocks, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * The diffusion operator of a graph and a Lanczos iteration on it (additive exports, WGNN_VERSION stays 206): the kernels behind
+ * ops.diffusion_operator / ops.lanczos_graph / ops.basis_combine / ops.diffusion_distance and api.ResidentPredictor.diffmap / dpt.
+ * All arithmetic is float64; every operation named here is rounded on its own (no fused multiply-add), every sum runs in the
+ * stated order and nothing depends on the grid: two calls give the same bits, and numpy restates every entry exactly.
+ *     rowptr int64 [n + 1], col int32 [nnz] strictly ascending within a row: a CSR that stores both directions of every edge
+ *         (ops.fuzzy_graph's), with w float32 [nnz] >= 0 and finite, or t float64 [nnz] >= 0 and finite
+ *   A ROW SUM is wgnn_layout_epoch's: WGNN_DIFFUSION_LANES lanes serve a row, lane l adds the row's entries l, l + 16, ... in
+ *   order from +0.0, and the partials fold by halves (lane l += lane l + 8, then 4, 2, 1).
+ *   A DOT of two vectors of n elements: chunks of WGNN_LANCZOS_CHUNK consecutive elements; within a chunk element s gives one
+ *   rounded product (+0.0 past n) and the 256 values fold by halves (p[s] += p[s + 128], then 64, ..., 1); the chunks' values are
+ *   added in ascending chunk order from +0.0.
+ *
+ * wgnn_diffusion_degree  - q == null: out_i = the row sum of (double)w_ij.  With q float64 [n]: out_i = sqrt(row sum of K_ij),
+ *     K_ij = (double)w_ij / (q_i * q_j); an entry with w == 0 adds +0.0 without a division.  An empty row gives 0.
+ * wgnn_diffusion_weights - t_ij = K_ij / (z_i * z_j) with z float64 [n], +0.0 where w == 0: scanpy's density-normalised symmetric
+ *     transition matrix.  Both products are commutative, so t_ij and t_ji are the same bits.
+ * wgnn_lanczos_init      - w0_i = mask_i ? z_i : 0 and w1_i = mask_i ? ((double)(h >> 11) * 2^-53) * 2 - 1 : 0, in [-1, 1), with
+ *     h = mix64(mix64(((u64)seed << 32) | 0xFFFFFFFE) + i) (wgnn_layout_init's hash, its own key word); mask uint8 [n].
+ * wgnn_lanczos_apply     - y_i = the row sum of t_ij * x_j (each product rounded); y another buffer than x.
+ * wgnn_lanczos_dots      - c[r] = the dot of V[r, :] and w for r = 0 .. n_rows - 1; V float64 [n_rows, ld], a basis vector per
+ *     row.  A workgroup takes a chunk for all rows; workspace holds one float64 per (chunk, row)
+ *     (wgnn_lanczos_dots_workspace_bytes).  *keep (optional) = c[n_rows - 1].  With WGNN_LANCZOS_NORM: V is null, n_rows 1, and
+ *     c[0] = sqrt(the dot of w with itself); if that is not above WGNN_LANCZOS_BREAKDOWN (a NaN is not) *halt = tag.
+ * wgnn_lanczos_update    - w_i = w_i - V[r, i] * c[r] for r = 0 .. n_rows - 1 ascending (a product and a subtraction each).
+ * wgnn_lanczos_scale     - v_i = w_i / *beta (a division; beta float64 on the device).
+ *   halt (int64 on the device, optional; 0 = running): apply, dots, update and scale return at once, writing nothing, when they
+ *   find it set - a step enqueued behind a breakdown is inert - and only a norm sets it.  No read-back is needed inside a step.
+ * wgnn_basis_combine     - Y[i, 0] = V[0, i];  Y[i, c] = sum_{j = 1 .. m} V[j, i] * S[j - 1, c - 1] for c = 1 .. n_cols, j ascending
+ *     from +0.0 (a product and an add each); S float64 [m, lds] and Y float64 [n, ldy] on the device.
+ * wgnn_diffusion_distance - d_i = min over the roots r of sqrt(sum_{l = 1 .. n_dcs - 1} (g_l * (Y[r, l] - Y[i, l]))^2), l
+ *     ascending from +0.0; roots int64 [n_roots], one outside [0, n) is skipped; a NaN distance stays.  g float64 [n_dcs].
+ *
+ *   *status (int64) is only ever OR-ed into (the caller zeroes it) with the bits below, by degree, weights and apply; no other
+ *   atomic is used.  No kernel reads or writes out of bounds on a malformed graph: a row is clamped to [0, nnz], a column
+ *   outside [0, n) and a bad weight are skipped (weights writes +0.0 there).
+ * ------------------------------------------------------------------------- */
+#define WGNN_DIFFUSION_LANES        16   /* lanes per row: part of the row sum's order                                */
+#define WGNN_DIFFUSION_MAX_BLOCKS 8192   /* the largest grid                                                          */
+#define WGNN_DIFFUSION_MAX_COMPS    64   /* the most components (the stationary one included)                         */
+#define WGNN_DIFFUSION_UNSORTED      1   /* a row is not strictly ascending in col                                    */
+#define WGNN_DIFFUSION_BAD_COL       2   /* a column outside [0, n): the entry is skipped                             */
+#define WGNN_DIFFUSION_BAD_ROWPTR    4   /* rowptr does not ascend from 0 to nnz: the row is clamped to [0, nnz]      */
+#define WGNN_DIFFUSION_BAD_WEIGHT    8   /* a negative, infinite or NaN w or t: the entry is skipped                  */
+#define WGNN_LANCZOS_CHUNK         256   /* elements per chunk: part of the dot's order                               */
+#define WGNN_LANCZOS_MAX_STEPS    1024   /* V holds at most 1025 rows                                                 */
+#define WGNN_LANCZOS_NORM          256   /* wgnn_lanczos_dots' flag: the norm of w                                    */
+#define WGNN_LANCZOS_BREAKDOWN 0x1p-26   /* a norm at or below this halts the run                                     */
+/* Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand; n outside [0, 2^31); a negative nnz; grid_blocks outside
+ * [0, 8192]; ld < n; n_rows outside [1, 1025]; m outside [0, 1024]; n_cols outside [0, 63]; n_dcs outside [2, 64]; n_roots < 1;
+ * tag == 0; an output that is, or lies inside, an input; an unknown flag), WGNN_ERR_WORKSPACE (a workspace smaller than asked
+ * for), WGNN_ERR_ALIGNMENT (64-bit operands not 8-byte, 32-bit ones not 4-byte aligned); wgnn_last_error_string names the check.
+ * n == 0 returns WGNN_OK without a launch. */
+int wgnn_diffusion_degree(const int64_t* rowptr, const int32_t* col, const float* w, int64_t n, int64_t nnz, const double* q,
+                          double* out, int64_t* status, int32_t grid_blocks, uint32_t flags, void* stream);
+int wgnn_diffusion_weights(const int64_t* rowptr, const int32_t* col, const float* w, int64_t n, int64_t nnz, const double* q,
+                           const double* z, double* t, int64_t* status, int32_t grid_blocks, uint32_t flags, void* stream);
+int wgnn_lanczos_init(const double* z, const uint8_t* mask, int64_t n, uint32_t seed, double* w0, double* w1, uint32_t flags,
+                      void* stream);
+int wgnn_lanczos_apply(const int64_t* rowptr, const int32_t* col, const double* t, int64_t n, int64_t nnz, const double* x,
+                       double* y, const int64_t* halt, int64_t* status, int32_t grid_blocks, uint32_t flags, void* stream);
+int64_t wgnn_lanczos_dots_workspace_bytes(int64_t n, int32_t n_rows);
+int wgnn_lanczos_dots(const double* V, int64_t ld, int32_t n_rows, const double* w, int64_t n, double* c, double* keep,
+                      int64_t* halt, int64_t tag, void* workspace, int64_t workspace_bytes, int32_t grid_blocks,
+                      uint32_t flags, void* stream);
+int wgnn_lanczos_update(const double* V, int64_t ld, int32_t n_rows, const double* c, double* w, int64_t n,
+                        const int64_t* halt, int32_t grid_blocks, uint32_t flags, void* stream);
+int wgnn_lanczos_scale(const double* w, const double* beta, double* v, int64_t n, const int64_t* halt, int32_t grid_blocks,
+                       uint32_t flags, void* stream);
+int wgnn_basis_combine(const double* V, int64_t ld, int32_t m, const double* S, int64_t lds, int32_t n_cols, double* Y,
+                       int64_t ldy, int64_t n, uint32_t flags, void* stream);
+int wgnn_diffusion_distance(const double* Y, int64_t ldy, int64_t n, const double* g, int32_t n_dcs, const int64_t* roots,
+                            int32_t n_roots, double* d, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

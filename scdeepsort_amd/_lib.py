@@ -40,6 +40,9 @@ FUZZY_MAX_K, FUZZY_IDX_I64 = 64, 256       # wgnn_fuzzy_rows' / wgnn_fuzzy_union
 LAYOUT_LANES, LAYOUT_MAX_EPOCHS, LAYOUT_MAX_NEG = 16, 10000, 64      # wgnn_layout_epoch's sum order and limits (include/wgnn.h)
 GEODESIC_UNSORTED, GEODESIC_BAD_COL, GEODESIC_BAD_ROWPTR, GEODESIC_BAD_LENGTH = 1, 2, 4, 8      # wgnn_geodesic_round's status bits
 GEODESIC_LANES, GEODESIC_MAX_BLOCKS = 16, 8192     # wgnn_geodesic_round's lanes per row and largest grid (include/wgnn.h)
+DIFFUSION_UNSORTED, DIFFUSION_BAD_COL, DIFFUSION_BAD_ROWPTR, DIFFUSION_BAD_WEIGHT = 1, 2, 4, 8    # the wgnn_diffusion_* / wgnn_lanczos_apply status bits
+DIFFUSION_LANES, DIFFUSION_MAX_BLOCKS, DIFFUSION_MAX_COMPS = 16, 8192, 64      # the row sum's lanes, the largest grid, the most components
+LANCZOS_CHUNK, LANCZOS_MAX_STEPS, LANCZOS_NORM, LANCZOS_BREAKDOWN = 256, 1024, 256, 2.0 ** -26    # wgnn_lanczos_*'s dot order, limit, flag and halt bound
 ABI_MAJOR = 2               # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
@@ -162,6 +165,16 @@ SIGNATURES = {
     "wgnn_layout_epoch": (C.c_int, [_vp, _vp, _vp, _i64, _i64, C.c_float, _vp, _vp, _i32, _i32, C.c_float, C.c_float, C.c_float,
                                     C.c_float, _i32, _u32, _vp, _u32, _vp]),
     "wgnn_geodesic_round": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _u32, _vp]),
+    "wgnn_diffusion_degree": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i32, _u32, _vp]),
+    "wgnn_diffusion_weights": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _u32, _vp]),
+    "wgnn_lanczos_init": (C.c_int, [_vp, _vp, _i64, _u32, _vp, _vp, _u32, _vp]),
+    "wgnn_lanczos_apply": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _u32, _vp]),
+    "wgnn_lanczos_dots_workspace_bytes": (_i64, [_i64, _i32]),
+    "wgnn_lanczos_dots": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _u32, _vp]),
+    "wgnn_lanczos_update": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _u32, _vp]),
+    "wgnn_lanczos_scale": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _u32, _vp]),
+    "wgnn_basis_combine": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _u32, _vp]),
+    "wgnn_diffusion_distance": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _u32, _vp]),
 }
 
 

@@ -36,7 +36,8 @@ from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Communi
                      Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Silhouette, SilhouetteSummary, Smoothed, SmoothedSummary, Stability,
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
                      _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores,
-                     Abstraction, AbstractionSummary, Pseudotime, PseudotimeSummary, _paga_connectivities, _scaled_pseudotime)
+                     Abstraction, AbstractionSummary, Pseudotime, PseudotimeSummary, _paga_connectivities, _scaled_pseudotime,
+                     DiffusionMap, DiffusionMapSummary, DiffusionPseudotime, DiffusionPseudotimeSummary)
 
 _tables._rows_topk = lambda *a: _ops.rows_topk(*a)      # MarkerTable.top's device route: tables.py itself imports no ops
 
@@ -2466,6 +2467,143 @@ class ResidentPredictor:
             ids, names = _cluster_ids(self._read_clusters_file(clusters_file, data, index), n_cells=len(index))
             out = self.paga(matrix, groups=ids, group_names=names, **kw)
         return self._save_frame(out.frame(), save_path, "paga")
+
+    # ---------------------------------------------------------------------------------------------
+    def diffmap(self, expr, n_comps: int = 15, k: int = 15, genes=None, normalize=None, space: str = "hidden",
+                metric: str = "euclidean", graph=None, n_steps: Optional[int] = None, seed: int = 0, tol: float = 1e-8,
+                index=None) -> DiffusionMap:
+        """The diffusion map of a batch's own kNN graph - the leading eigenvectors of its density-normalised transition matrix,
+        scanpy's ``tl.diffmap`` - without a host round trip of the graph: the batch is classified once (``classify``'s call, bit
+        for bit), searched as ``knn`` does (``k``, ``space``, ``metric`` as there), the lists and their distances made UMAP's
+        connectivities (``ops.fuzzy_graph``, the graph ``umap`` lays out), these made the symmetric transition matrix
+        (``ops.diffusion_operator``) and its largest connected component (``ops.graph_components``; ties in size go to the
+        component that holds the lowest cell) handed to ``ops.lanczos_graph``: a Lanczos iteration with full
+        re-orthogonalisation and a fixed number of steps, every sum in a stated order, so that two calls give the same bits.
+        The small tridiagonal problem is solved on the host (``ops.lanczos_ritz``: ``numpy.linalg.eigh``) and the eigenvectors
+        are put together on the device (``ops.basis_combine``), each with the sign that makes its largest entry positive.
+
+        ``n_comps`` in [2, 64] counts the stationary component 0, as scanpy does.  ``n_steps`` = None: 128 below 10 000 cells,
+        256 from there on; at most 1024.  ``seed``: of the start vector.  ``tol``: what ``converged`` holds the residuals to.
+        ``graph``: an earlier ``NeighborGraph`` of the same batch in place of the search - ``k``, ``space`` and ``metric`` are
+        then the graph's own; a bare index array is refused, distances are needed.  ``index``: the cells' names.
+
+        Returns a ``DiffusionMap``.  Fewer components than asked for (a small component, a breakdown) are reported, not raised;
+        a cell outside the component (a NaN row, which ``knn`` lists nowhere, among them) has NaN coordinates.
+
+        What this is not: no Gaussian-kernel connectivities (scanpy's ``method="gauss"``) - the weights are UMAP's; no restarts,
+        so a residual above ``tol`` is reported (``converged`` False) and the caller raises ``n_steps``; one component, one batch;
+        an eigenvalue within about ``tol`` of another gives a basis of that eigenspace, not scanpy's particular vectors; the
+        comparison with scanpy itself was not run, the formulas of ``include/wgnn.h`` are the contract.  Fused kernels only, as
+        ``embed``."""
+        B = self._n_cells(expr)
+        lists, k, space, metric = self._graph_lists(
+            "the diffusion map", graph, B, k, space, metric, True, max_k=_ops.FUZZY_MAX_K,
+            misfit=f"graph must be a NeighborGraph of this batch: [{B}, 1..{_ops.FUZZY_MAX_K}] lists and distances")
+        n_comps, seed, tol = int(n_comps), int(seed), float(tol)
+        if not 2 <= n_comps <= _ops.DIFFUSION_MAX_COMPS:
+            raise ValueError(f"n_comps = {n_comps} is outside [2, {_ops.DIFFUSION_MAX_COMPS}]")
+        if n_steps is not None and not 1 <= int(n_steps) <= _ops.LANCZOS_MAX_STEPS:
+            raise ValueError(f"n_steps = {n_steps} is outside [1, {_ops.LANCZOS_MAX_STEPS}]")
+        if not 0 <= seed < 2 ** 32:
+            raise ValueError(f"seed = {seed} is outside [0, 2^32)")
+        if not 0.0 <= tol < float("inf"):
+            raise ValueError(f"tol = {tol} must be finite and not negative")
+        self._require_fused("diffmap")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._diffmap(self._over_genes(expr, genes, normalize), n_comps, k, space, metric, lists, n_steps, seed, tol,
+                                 index)
+
+    def _diffmap(self, expr, n_comps, k, space, metric, lists, n_steps, seed, tol, index):
+        vb = self._values_batch(self._device_csr(expr))
+        B = int(vb.csr[0].shape[0]) - 1
+        idx, d2, _ = self._lists_on_device(vb, lists, k, space, metric)
+        fuzzy = _ops.fuzzy_graph(idx, d2)
+        lowest = _ops.graph_components(fuzzy.rowptr, fuzzy.col)
+        size = torch.bincount(lowest, minlength=B)
+        mask = lowest == torch.nonzero(size == size.max())[0, 0] if B else lowest == 0      # the first of the largest
+        op = _ops.diffusion_operator(fuzzy.rowptr, fuzzy.col, fuzzy.w)
+        run = _ops.lanczos_graph(fuzzy.rowptr, fuzzy.col, op.t, op.z, mask, n_steps=n_steps, seed=seed)
+        theta, S, res = _ops.lanczos_ritz(run.alpha, run.beta, run.n_run)
+        n_found = min(n_comps, run.n_run + 1)
+        on = mask.cpu().numpy()
+        coords = _ops.basis_combine(run.V, S[:, :n_found - 1]).cpu().numpy()
+        coords[~on] = np.nan
+        residual = np.concatenate([[0.0], res[:n_found - 1]])
+        return DiffusionMap(coords=coords, eigenvalues=np.concatenate([[1.0], theta[:n_found - 1]]), residual=residual,
+                            converged=bool((residual <= tol).all()), tol=tol, n_steps=run.n_run, breakdown=run.breakdown,
+                            in_component=on, n_components=int((size > 0).sum()), seed=seed, k=k, space=space, metric=metric,
+                            label=vb.pred, max_prob=vb.max_prob, **self._table_fields(B, index))
+
+    def diffmap_file(self, data, n_comps: int = 15, k: int = 15, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                     n_steps: Optional[int] = None, seed: int = 0, tol: float = 1e-8, save_path=None) -> pd.DataFrame:
+        """``diffmap`` on a test file - its full table, its gene names as ``genes=`` and its cell names.  Returns one row per cell:
+        ``cell`` (its name), ``dc1``, ``dc2``, ... - empty where the cell lies outside the component, which is no error - written
+        as ``{species}_{tissue}_diffmap.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.diffmap(matrix, n_comps=n_comps, k=k, genes=genes, normalize=normalize, space=space, metric=metric,
+                           n_steps=n_steps, seed=seed, tol=tol, index=index)
+        return self._save_frame(out.coords_frame(), save_path, "diffmap")
+
+    def dpt(self, expr, root, n_dcs: int = 10, diffmap: Optional[DiffusionMap] = None, n_comps: int = 15, k: int = 15, genes=None,
+            normalize=None, space: str = "hidden", metric: str = "euclidean", graph=None, n_steps: Optional[int] = None,
+            seed: int = 0, tol: float = 1e-8, index=None) -> DiffusionPseudotime:
+        """Order the cells of a batch by diffusion pseudotime (Haghverdi et al. 2016, scanpy's ``tl.dpt`` without branchings):
+        every cell's distance from ``root`` in the diffusion map, ``sqrt(sum_l (lambda_l / (1 - lambda_l))^2 (y_l[root] -
+        y_l[cell])^2)`` over the components ``l = 1 .. n_dcs - 1`` - the sum of the transition matrix's powers, which averages
+        over every path of the graph where ``pseudotime`` takes the shortest, so that one spurious edge across a gap does not
+        short-cut the order.  ``ops.diffusion_distance`` on the device, the sum sequential and every operation rounded on its
+        own; ``lambda / (1 - lambda)`` is taken on the host in float64.
+
+        ``root``: as ``pseudotime`` takes it - a cell's position, a sequence of positions (the distance is then to the nearest
+        of them), a cell's name when ``index`` is given, or ``{"type": "<a called type's name>"}``; a root outside the
+        component is a ``ValueError``.  ``n_dcs`` in [2, the components found] counts the stationary component, as ``n_comps``.
+        ``diffmap``: an earlier ``DiffusionMap`` of this batch - nothing is classified or searched then, and the other
+        arguments of ``diffmap`` are not read; else ``diffmap`` runs with them.
+
+        Returns a ``DiffusionPseudotime``: ``distance`` and ``pseudotime`` are NaN for a cell outside the component.
+
+        What this is not: no branch detection (scanpy's ``n_branchings``) - ``paga`` and ``Abstraction.directed``, which takes
+        this table as it takes ``pseudotime``'s, are the coarse view of the branches; and what ``diffmap`` is not.  Fused kernels
+        only, as ``embed``."""
+        B = self._n_cells(expr)
+        _check_index(index, B)
+        if diffmap is None:
+            diffmap = self.diffmap(expr, n_comps=n_comps, k=k, genes=genes, normalize=normalize, space=space, metric=metric,
+                                   graph=graph, n_steps=n_steps, seed=seed, tol=tol, index=index)
+        elif not isinstance(diffmap, DiffusionMap) or len(diffmap.in_component) != B:
+            raise ValueError(f"diffmap must be a DiffusionMap of this batch of {B} cells")
+        n_dcs = int(n_dcs)
+        if not 2 <= n_dcs <= diffmap.n_found:
+            raise ValueError(f"n_dcs = {n_dcs} is outside [2, {diffmap.n_found}] (the components found)")
+        cells = self._root_cells(root, B, index, diffmap.label, diffmap.max_prob)
+        outside = cells[~np.asarray(diffmap.in_component, bool)[cells]]
+        if outside.size:
+            raise ValueError(f"root cell(s) {outside.tolist()} lie outside the component the diffusion map was taken on")
+        self._require_fused("dpt")
+        lam = np.asarray(diffmap.eigenvalues, np.float64)[:n_dcs]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            g = lam / (1.0 - lam)
+        g[0] = 0.0                                                              # the stationary component is not read
+        with torch.cuda.device(self.device), torch.no_grad():
+            Y = torch.as_tensor(np.ascontiguousarray(np.asarray(diffmap.coords, np.float64)[:, :n_dcs]), device=self.device)
+            distance = _ops.diffusion_distance(Y, g, torch.as_tensor(cells, device=self.device)).cpu().numpy()
+        return DiffusionPseudotime(distance=distance, pseudotime=_scaled_pseudotime(distance), roots=cells, n_dcs=n_dcs,
+                                   label=diffmap.label, max_prob=diffmap.max_prob,
+                                   index=diffmap.index if index is None else index, id2label=list(diffmap.id2label),
+                                   label_map=diffmap.label_map)
+
+    def dpt_file(self, data, root, n_dcs: int = 10, n_comps: int = 15, k: int = 15, normalize=None, space: str = "hidden",
+                 metric: str = "euclidean", n_steps: Optional[int] = None, seed: int = 0, tol: float = 1e-8,
+                 save_path=None) -> pd.DataFrame:
+        """``dpt`` on a test file - its full table, its gene names as ``genes=`` and its cell names (so ``root`` may name a cell).
+        Returns one row per cell: ``cell`` (its name) and ``pseudotime`` - empty where the cell lies outside the component, which
+        is no error - written as ``{species}_{tissue}_dpt.csv`` under ``save_path`` when given.  ``normalize``: as for
+        ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        out = self.dpt(matrix, root, n_dcs=n_dcs, n_comps=n_comps, k=k, genes=genes, normalize=normalize, space=space,
+                       metric=metric, n_steps=n_steps, seed=seed, tol=tol, index=index)
+        return self._save_frame(out.pseudotime_frame(), save_path, "dpt")
 
     # ---------------------------------------------------------------------------------------------
     def silhouette(self, expr, groups="predicted", genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",

@@ -2746,12 +2746,17 @@ def _leiden_components(run: _GraphRun, P: torch.Tensor) -> torch.Tensor:
     """The lowest vertex of every vertex's connected component inside its community of ``P``: min-label propagation over the
     entries whose two ends share a community, on the device, until a round changes nothing (one read-back per round)."""
     same = P[run.row] == P[run.col.long()]
-    r, c = run.row[same], run.col[same].long()
-    label = torch.arange(run.n, dtype=torch.int64, device=run.dev)
+    return _min_labels(run.n, run.row[same], run.col[same].long(), run.dev).to(torch.int32)
+
+
+def _min_labels(n: int, r: torch.Tensor, c: torch.Tensor, dev) -> torch.Tensor:
+    """int64 [n]: the lowest vertex every vertex reaches over the directed entries ``(r, c)`` (both directions stored), by
+    min-label propagation in integers until a round changes nothing (one read-back per round)."""
+    label = torch.arange(n, dtype=torch.int64, device=dev)
     while True:
         nxt = label.clone().scatter_reduce_(0, r, label[c], "amin")
         if bool((nxt == label).all()):
-            return label.to(torch.int32)
+            return label
         label = nxt
 
 
@@ -3122,3 +3127,253 @@ def group_edges(idx: torch.Tensor, group: torch.Tensor, n_groups: int) -> GroupE
     edges = torch.bincount(ga[both] * K + gb[both], minlength=K * K).reshape(K, K)
     size = torch.bincount(g[g >= 0], minlength=K)
     return GroupEdges(edges, size)
+
+
+DIFFUSION_LANES, DIFFUSION_MAX_BLOCKS, DIFFUSION_MAX_COMPS = _lib.DIFFUSION_LANES, _lib.DIFFUSION_MAX_BLOCKS, _lib.DIFFUSION_MAX_COMPS
+LANCZOS_CHUNK, LANCZOS_MAX_STEPS, LANCZOS_BREAKDOWN = _lib.LANCZOS_CHUNK, _lib.LANCZOS_MAX_STEPS, _lib.LANCZOS_BREAKDOWN
+LANCZOS_BASIS_BYTES = 4 << 30             # lanczos_graph: the basis [steps + 1, B] float64 stays under this
+
+_DIFFUSION_STATUS = ((_lib.DIFFUSION_UNSORTED, "a row is not strictly ascending in col"),
+                     (_lib.DIFFUSION_BAD_COL, "a column is outside [0, n)"),
+                     (_lib.DIFFUSION_BAD_ROWPTR, "rowptr does not ascend from 0 to nnz"),
+                     (_lib.DIFFUSION_BAD_WEIGHT, "a weight is negative, infinite or NaN"))
+
+
+def _check_grid(name, grid_blocks) -> int:
+    grid_blocks = int(grid_blocks)
+    if not 0 <= grid_blocks <= DIFFUSION_MAX_BLOCKS:
+        raise ValueError(f"{name}: grid_blocks = {grid_blocks} is outside [0, {DIFFUSION_MAX_BLOCKS}] (0 = from B)")
+    return grid_blocks
+
+
+def graph_components(rowptr: torch.Tensor, col: torch.Tensor) -> torch.Tensor:
+    """The connected components of a symmetric CSR graph (``rowptr`` int64 [B + 1], ``col`` int32; both directions of every edge
+    stored), on the device: int64 [B], the lowest vertex of every vertex's component - min-label propagation with framework ops,
+    in integers, one read-back per round and as many rounds as the longest shortest path to a component's lowest vertex.  A
+    ``rowptr`` that does not ascend from 0 to ``nnz`` or a column outside [0, B) is a ``ValueError`` (one read-back); CPU tensors
+    raise ``WgnnError``."""
+    name = "graph_components"
+    dev = _require_cuda(rowptr, col)
+    if rowptr.dim() != 1 or rowptr.dtype != torch.int64 or rowptr.shape[0] < 1 or col.dim() != 1 or col.dtype != torch.int32:
+        raise ValueError(f"{name}: rowptr int64 [B + 1] and col int32 [nnz] are expected")
+    B, nnz = int(rowptr.shape[0]) - 1, int(col.shape[0])
+    deg = rowptr[1:] - rowptr[:-1]
+    bad = torch.stack([rowptr[0] != 0, rowptr[-1] != nnz, (deg < 0).any(), ((col < 0) | (col >= B)).any()]).tolist()
+    if any(bad):
+        raise ValueError(f"{name}: rowptr does not ascend from 0 to nnz = {nnz}, or a column is outside [0, {B})")
+    row = torch.repeat_interleave(torch.arange(B, dtype=torch.int64, device=dev), deg)
+    return _min_labels(B, row, col.long(), dev)
+
+
+class DiffusionOperator(NamedTuple):
+    """What ``diffusion_operator`` returns, on the device, float64: ``t`` [nnz] - the density-normalised symmetric transition
+    matrix on the graph's own structure, ``t(i, j)`` and ``t(j, i)`` the same bits - and the per-row ``q`` (the sum of the row's
+    weights) and ``z`` (the root of the sum of the row's ``w / (q_i q_j)``) [B]; an empty row has ``q = z = 0``."""
+    t: torch.Tensor
+    q: torch.Tensor
+    z: torch.Tensor
+
+
+def diffusion_operator(rowptr: torch.Tensor, col: torch.Tensor, w: torch.Tensor, grid_blocks: int = 0) -> DiffusionOperator:
+    """scanpy's density-normalised symmetric transition matrix of a symmetric weighted CSR graph (``rowptr`` int64 [B + 1], ``col``
+    int32 ascending within a row, ``w`` float32 >= 0 - what ``fuzzy_graph`` returns), in float64 on the device: ``q_i = sum_j w_ij``,
+    ``K_ij = w_ij / (q_i q_j)``, ``z_i = sqrt(sum_j K_ij)``, ``t_ij = K_ij / (z_i z_j)`` (``include/wgnn.h`` has the contract) -
+    ``neighbors.Neighbors.compute_transitions(density_normalize=True)``'s ``transitions_sym``.  Every row sum runs in
+    ``wgnn_layout_epoch``'s order and every operation is rounded on its own, so numpy restates it bit for bit and the grid
+    (``grid_blocks``, 0 = from ``B``) changes nothing; an entry with ``w == 0`` gives ``t = +0.0``.  The matrix has the eigenvalue 1
+    with the eigenvector ``z`` on every connected component.  Three launches and one read-back (the status word): a malformed
+    graph (unsorted row, column out of range, bad ``rowptr``, a negative / infinite / NaN weight) raises ``WgnnError``; every
+    argument error is a ``ValueError``; CPU tensors raise ``WgnnError``.  Returns a ``DiffusionOperator``."""
+    name = "diffusion_operator"
+    dev = _require_cuda(rowptr, col, w)
+    rowptr, col, w, B, nnz = _graph_operand(name, rowptr, col, w, "w", torch.float32)
+    grid_blocks = _check_grid(name, grid_blocks)
+    stream = _stream(dev)
+    q, z = torch.zeros(B, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.float64, device=dev)
+    t = torch.zeros(nnz, dtype=torch.float64, device=dev)
+    status = torch.zeros(1, dtype=torch.int64, device=dev)
+    graph = (_ptr(rowptr), _ptr(col), _ptr(w), B, nnz)
+    _lib.run(dev, "wgnn_diffusion_degree", *graph, None, _ptr(q), _ptr(status), grid_blocks, 0, stream)
+    _lib.run(dev, "wgnn_diffusion_degree", *graph, _ptr(q), _ptr(z), _ptr(status), grid_blocks, 0, stream)
+    _lib.run(dev, "wgnn_diffusion_weights", *graph, _ptr(q), _ptr(z), _ptr(t), _ptr(status), grid_blocks, 0, stream)
+    _check_status(name, int(status), _DIFFUSION_STATUS)
+    return DiffusionOperator(t, q, z)
+
+
+class LanczosRows(NamedTuple):
+    """What ``lanczos_graph`` returns.  On the device, float64: ``V`` [m + 1, B] - the basis, a vector per contiguous row, ``V[0]``
+    the deflated ``z mask / ||z mask||`` and the rows past ``n_run`` zero - and ``alpha`` / ``beta`` [m] (``alpha[j - 1]`` is step
+    ``j``'s diagonal entry, ``beta[j - 1]`` the norm it left; zero past ``n_run``).  On the host: ``n_run`` (the steps run: ``m =
+    min(n_steps, cells of the mask - 1)`` unless the run broke down), ``breakdown`` (a norm fell to 2^-26 or below: the Krylov
+    space is exhausted) and ``n_cells`` (the cells of the mask)."""
+    V: torch.Tensor
+    alpha: torch.Tensor
+    beta: torch.Tensor
+    n_run: int
+    breakdown: bool
+    n_cells: int
+
+
+def lanczos_steps(n_cells: int) -> int:
+    """``lanczos_graph``'s default number of steps: 128 below 10 000 cells, 256 from there on (the float64 prototype's figures in
+    profiles/resident_diffmap.md: 128 steps leave the 15 leading eigenvalues of a 20 000-cell graph at 4e-11, 256 at 5e-15)."""
+    return 128 if n_cells < 10000 else 256
+
+
+def lanczos_graph(rowptr: torch.Tensor, col: torch.Tensor, t: torch.Tensor, z: torch.Tensor, mask: torch.Tensor,
+                  n_steps: Optional[int] = None, seed: int = 0, check_every: int = 16, grid_blocks: int = 0) -> LanczosRows:
+    """A Lanczos iteration with full re-orthogonalisation and a fixed number of steps on the symmetric matrix ``t`` float64 [nnz]
+    over the CSR ``rowptr`` int64 [B + 1] / ``col`` int32 (``diffusion_operator``'s), restricted to the cells of ``mask`` bool [B] -
+    a union of connected components - with the known eigenvector ``z`` float64 [B] of eigenvalue 1 deflated, on the device
+    (``include/wgnn.h`` has the contracts).  ``V[0] = z mask / ||z mask||``; ``V[1]`` starts from a counter hash of ``(seed, i)`` in
+    [-1, 1), zero outside the mask, orthogonalised against ``V[0]`` twice and normalised.  Step ``j = 1 .. m``: ``w = T V[j]``
+    (``wgnn_lanczos_apply``); ``c = V[0 .. j] w`` with ``alpha_j = c[j]`` (``wgnn_lanczos_dots``); ``w -= V[r] c[r]``, ``r`` ascending
+    (``wgnn_lanczos_update``); dots and update once more (classical Gram-Schmidt twice); ``beta_j = ||w||``; ``V[j + 1] = w /
+    beta_j`` (``wgnn_lanczos_scale``; not formed after the last step).  ``m = min(n_steps, cells of the mask - 1)``; ``n_steps`` =
+    None: 128 below 10 000 cells, 256 from there on; at most 1024.  Every sum runs in a stated order and every operation is
+    rounded on its own, so numpy restates the run bit for bit, two calls give the same bits and ``grid_blocks`` (0 = from ``B``)
+    changes none; a row outside the mask stays exactly zero.
+
+    The run ends after the first step that leaves ``beta_j <= 2^-26`` (``breakdown``).  ``beta`` stays on the device: the norm that
+    finds it sets a halt word there, every launch enqueued behind it finds the word and does nothing, and the host reads the
+    word once per ``check_every`` steps - no read-back inside a step.  Ten launches a step.  The basis takes ``(m + 1) B`` float64;
+    more than ``LANCZOS_BASIS_BYTES`` is a ``ValueError``, as every argument error; a malformed graph raises ``WgnnError`` from
+    the status word; CPU tensors raise ``WgnnError``.  Returns a ``LanczosRows``."""
+    name = "lanczos_graph"
+    dev = _require_cuda(rowptr, col, t, z, mask)
+    rowptr, col, t, B, nnz = _graph_operand(name, rowptr, col, t, "t", torch.float64)
+    if z.dtype != torch.float64 or tuple(z.shape) != (B,) or mask.dtype != torch.bool or tuple(mask.shape) != (B,):
+        raise ValueError(f"{name}: z float64 [{B}] and mask bool [{B}] are expected")
+    n_steps = lanczos_steps(B) if n_steps is None else int(n_steps)
+    seed, check_every, grid_blocks = int(seed), int(check_every), _check_grid(name, grid_blocks)
+    if not 1 <= n_steps <= LANCZOS_MAX_STEPS:
+        raise ValueError(f"{name}: n_steps = {n_steps} is outside [1, {LANCZOS_MAX_STEPS}]")
+    if not 0 <= seed < 2 ** 32:
+        raise ValueError(f"{name}: seed = {seed} is outside [0, 2^32)")
+    if check_every < 1:
+        raise ValueError(f"{name}: check_every = {check_every} must be >= 1")
+    n_c = int(mask.sum()) if B else 0
+    m = max(0, min(n_steps, n_c - 1))
+    if (m + 1) * B * 8 > LANCZOS_BASIS_BYTES:
+        raise ValueError(f"{name}: the basis [{m + 1}, {B}] float64 takes {(m + 1) * B * 8} bytes, above LANCZOS_BASIS_BYTES = "
+                         f"{LANCZOS_BASIS_BYTES}: lower n_steps")
+    V = torch.zeros((m + 1, B), dtype=torch.float64, device=dev)
+    alpha, beta = torch.zeros(m, dtype=torch.float64, device=dev), torch.zeros(m, dtype=torch.float64, device=dev)
+    if n_c == 0:
+        return LanczosRows(V, alpha, beta, 0, False, 0)
+    stream = _stream(dev)
+    z, mask8 = z.contiguous(), mask.to(torch.uint8).contiguous()
+    w, w1 = torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.float64, device=dev)
+    c, nrm = torch.empty(m + 1, dtype=torch.float64, device=dev), torch.empty(1, dtype=torch.float64, device=dev)
+    words = torch.zeros(2, dtype=torch.int64, device=dev)                      # the halt word, then the status
+    halt, status = words.data_ptr(), words.data_ptr() + 8
+    ws_bytes = int(_lib.lib().wgnn_lanczos_dots_workspace_bytes(B, m + 1))
+    ws = torch.empty(max(1, ws_bytes // 8), dtype=torch.float64, device=dev)
+    row = lambda j: V.data_ptr() + 8 * B * j
+
+    def ortho(n_rows, vec, keep=None):                                          # classical Gram-Schmidt, twice
+        for k in (keep, None):
+            _lib.run(dev, "wgnn_lanczos_dots", _ptr(V), B, n_rows, _ptr(vec), B, _ptr(c), k, halt, 1, _ptr(ws), ws_bytes, grid_blocks,
+                     0, stream)
+            _lib.run(dev, "wgnn_lanczos_update", _ptr(V), B, n_rows, _ptr(c), _ptr(vec), B, halt, grid_blocks, 0, stream)
+
+    def norm(vec, keep, tag):
+        _lib.run(dev, "wgnn_lanczos_dots", None, 0, 1, _ptr(vec), B, _ptr(nrm), keep, halt, tag, _ptr(ws), ws_bytes, grid_blocks,
+                 _lib.LANCZOS_NORM, stream)
+
+    def scale(vec, by, j):
+        _lib.run(dev, "wgnn_lanczos_scale", _ptr(vec), by, row(j), B, halt, grid_blocks, 0, stream)
+
+    _lib.run(dev, "wgnn_lanczos_init", _ptr(z), _ptr(mask8), B, seed, _ptr(w), _ptr(w1), 0, stream)
+    norm(w, None, -1)
+    scale(w, _ptr(nrm), 0)
+    if m >= 1:
+        ortho(1, w1)
+        norm(w1, None, -1)
+        scale(w1, _ptr(nrm), 1)
+    done, halted, bits = 0, 0, 0
+    while True:
+        batch = min(check_every, m - done)
+        for j in range(done + 1, done + batch + 1):
+            _lib.run(dev, "wgnn_lanczos_apply", _ptr(rowptr), _ptr(col), _ptr(t), B, nnz, row(j), _ptr(w), halt, status, grid_blocks, 0,
+                     stream)
+            ortho(j + 1, w, alpha.data_ptr() + 8 * (j - 1))
+            norm(w, beta.data_ptr() + 8 * (j - 1), j)
+            if j < m:
+                scale(w, beta.data_ptr() + 8 * (j - 1), j + 1)
+        done += batch
+        halted, bits = words.tolist()
+        _check_status(name, bits, _DIFFUSION_STATUS)
+        if halted or done >= m:
+            break
+    n_run = m if not halted else max(0, halted)                                 # -1: a start vector had no norm
+    return LanczosRows(V, alpha, beta, n_run, bool(halted), n_c)
+
+
+def lanczos_ritz(alpha, beta, n: int):
+    """The host step between ``lanczos_graph`` and ``basis_combine``, in numpy: ``(theta [n], S [n, n], residual [n])`` of the
+    ``n x n`` tridiagonal with diagonal ``alpha[:n]`` and off-diagonal ``beta[:n - 1]`` by ``numpy.linalg.eigh`` on the dense
+    matrix - the Ritz values descending (ties by ``eigh``'s position), ``S``'s columns in that order, and the residual estimate
+    ``|beta[n - 1] S[n - 1, c]|`` of every Ritz pair.  ``alpha`` / ``beta``: arrays or tensors with at least ``n`` entries."""
+    import numpy as np
+    to_host = lambda v: v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    a, b, n = to_host(alpha).astype(np.float64), to_host(beta).astype(np.float64), int(n)
+    if n < 0 or a.ndim != 1 or b.ndim != 1 or len(a) < n or len(b) < n:
+        raise ValueError(f"lanczos_ritz: alpha and beta must hold at least n = {n} entries")
+    if n == 0:
+        return np.zeros(0), np.zeros((0, 0)), np.zeros(0)
+    theta, S = np.linalg.eigh(np.diag(a[:n]) + np.diag(b[:n - 1], 1) + np.diag(b[:n - 1], -1))
+    order = np.argsort(-theta, kind="stable")
+    return theta[order], np.ascontiguousarray(S[:, order]), np.abs(b[n - 1] * S[n - 1, order])
+
+
+def basis_combine(V: torch.Tensor, S) -> torch.Tensor:
+    """The Ritz vectors of a Lanczos run on the device: ``Y`` float64 [B, 1 + n_cols] with ``Y[:, 0] = V[0]`` and ``Y[i, c] =
+    sum_{j = 1 .. m} V[j, i] S[j - 1, c - 1]``, ``j`` ascending, every product and add rounded on its own (``wgnn_basis_combine``;
+    row-local, so numpy restates it bit for bit).  ``V`` float64 [>= m + 1, B] (``lanczos_graph``'s), ``S`` float64 [m, n_cols] -
+    columns of ``lanczos_ritz``'s, a numpy array or a tensor - with ``n_cols`` <= 63.  Then every column but the first is given
+    the sign that makes its entry of largest magnitude (the lowest cell among equal ones) positive, with framework ops: a
+    multiplication by +-1."""
+    import numpy as np
+    name = "basis_combine"
+    dev = _require_cuda(V)
+    S = torch.as_tensor(np.ascontiguousarray(S, dtype=np.float64) if not isinstance(S, torch.Tensor) else S, device=dev)
+    if V.dim() != 2 or V.dtype != torch.float64 or S.dim() != 2 or S.dtype != torch.float64:
+        raise ValueError(f"{name}: V float64 [m + 1, B] and S float64 [m, n_cols] are expected")
+    (m, n_cols), B = S.shape, int(V.shape[1])
+    if V.shape[0] < m + 1 or m > LANCZOS_MAX_STEPS or n_cols >= DIFFUSION_MAX_COMPS:
+        raise ValueError(f"{name}: S [{m}, {n_cols}] does not fit V {tuple(V.shape)} (at most {LANCZOS_MAX_STEPS} steps, "
+                         f"{DIFFUSION_MAX_COMPS - 1} columns)")
+    V, S = V.contiguous(), S.contiguous()
+    Y = torch.zeros((B, n_cols + 1), dtype=torch.float64, device=dev)
+    _lib.run(dev, "wgnn_basis_combine", _ptr(V), B, m, _ptr(S) if n_cols else None, n_cols, n_cols, _ptr(Y), n_cols + 1, B, 0,
+             _stream(dev))
+    if B and n_cols:
+        mag = Y[:, 1:].abs()
+        cells = torch.arange(B, device=dev)[:, None].expand(B, n_cols)
+        first = torch.where(mag == mag.max(dim=0).values, cells, B).min(dim=0).values.clamp(max=B - 1)   # a NaN column: any cell
+        Y[:, 1:] *= torch.where(Y[first, torch.arange(1, n_cols + 1, device=dev)] < 0, -1.0, 1.0)
+    return Y
+
+
+def diffusion_distance(Y: torch.Tensor, g, roots) -> torch.Tensor:
+    """Diffusion pseudotime's distance on the device: ``d_i = min over roots r of sqrt(sum_{l = 1 .. n_dcs - 1} (g_l (Y[r, l] -
+    Y[i, l]))^2)``, float64 [B], the sum sequential in ``l`` and every operation rounded on its own (``wgnn_diffusion_distance``;
+    numpy restates it bit for bit).  ``Y`` float64 [B, >= n_dcs] (``basis_combine``'s; column 0 is not read), ``g`` float64
+    [n_dcs] - ``lambda_l / (1 - lambda_l)``, computed by the caller; ``n_dcs`` in [2, 64] - and ``roots`` as ``geodesic_rows``
+    takes them.  A NaN coordinate gives a NaN distance."""
+    import numpy as np
+    name = "diffusion_distance"
+    dev = _require_cuda(Y, roots if isinstance(roots, torch.Tensor) else None)
+    g = torch.as_tensor(np.ascontiguousarray(g, dtype=np.float64) if not isinstance(g, torch.Tensor) else g, device=dev)
+    if Y.dim() != 2 or Y.dtype != torch.float64 or g.dim() != 1 or g.dtype != torch.float64:
+        raise ValueError(f"{name}: Y float64 [B, n] and g float64 [n_dcs] are expected")
+    B, n_dcs = int(Y.shape[0]), int(g.shape[0])
+    if not 2 <= n_dcs <= min(DIFFUSION_MAX_COMPS, int(Y.shape[1])):
+        raise ValueError(f"{name}: n_dcs = {n_dcs} is outside [2, {min(DIFFUSION_MAX_COMPS, int(Y.shape[1]))}]")
+    r = _geodesic_roots(name, roots, B, dev)
+    Y, g = Y.contiguous(), g.contiguous()
+    d = torch.empty(B, dtype=torch.float64, device=dev)
+    _lib.run(dev, "wgnn_diffusion_distance", _ptr(Y), int(Y.shape[1]), B, _ptr(g), n_dcs, _ptr(r), int(r.shape[0]), _ptr(d), 0,
+             _stream(dev))
+    return d

@@ -2182,8 +2182,41 @@ class PseudotimeSummary(dict):
             f"({d['n_unsure']} cells unsure)"])
 
 
+class _OrderedCells(_NamesCalls):
+    """For a result table with ``pseudotime`` f64 [B] (NaN = the cell has none), ``label`` and ``index``: the views by group, by
+    called type and per cell that ``Pseudotime`` and ``DiffusionPseudotime`` share."""
+
+    def by_group(self, groups, group_names: Optional[Sequence[str]] = None) -> pd.DataFrame:
+        """One row per group of ``groups`` (one integer id per cell, -1 = skip) that has a reached cell, sorted by median
+        pseudotime (ties by id): ``group`` (its name from ``group_names``, else the id), ``n_cells`` (reached ones), ``median``,
+        ``min`` and ``max`` pseudotime."""
+        g, t = np.asarray(groups), np.asarray(self.pseudotime, np.float64)
+        if g.shape != t.shape or not np.issubdtype(g.dtype, np.integer):
+            raise ValueError(f"groups must hold one integer id per cell ([{len(t)}]), got {g.dtype} {g.shape}")
+        on = (g >= 0) & ~np.isnan(t)
+        rows = [(int(s), int((on & (g == s)).sum()), float(np.median(t[on & (g == s)])), float(t[on & (g == s)].min()),
+                 float(t[on & (g == s)].max())) for s in sorted(set(g[on].tolist()))]
+        rows.sort(key=lambda r: (r[2], r[0]))
+        cols = list(zip(*rows)) if rows else [[] for _ in range(5)]
+        names = list(cols[0]) if group_names is None else [group_names[s] for s in cols[0]]
+        return pd.DataFrame({"group": names, "n_cells": np.asarray(cols[1], np.int64), "median": np.asarray(cols[2], np.float64),
+                             "min": np.asarray(cols[3], np.float64), "max": np.asarray(cols[4], np.float64)})
+
+    def by_type(self) -> pd.DataFrame:
+        """``by_group`` over the called types (unsure cells skipped): ``cell_type``, ``n_cells``, ``median``, ``min``, ``max``,
+        sorted by median pseudotime."""
+        label = np.asarray(self.label, np.int64)
+        out = self.by_group(np.where(label >= 0, label, -1))
+        out["group"] = self._name(out["group"].tolist())
+        return out.rename(columns={"group": "cell_type"})
+
+    def pseudotime_frame(self) -> pd.DataFrame:
+        """One row per cell - ``cell`` (its name) and ``pseudotime`` (empty where not reached): what ``pseudotime_file`` writes."""
+        return pd.DataFrame({"cell": [str(c) for c in self.index], "pseudotime": np.asarray(self.pseudotime, np.float64)})
+
+
 @dataclass
-class Pseudotime(_NamesCalls):
+class Pseudotime(_OrderedCells):
     """What ``ResidentPredictor.pseudotime`` returns: every cell's geodesic distance from the root cells along one batch's own kNN
     graph.  B cells (``index``), C cell types (``id2label``).  ``distance`` f32 [B]: ``ops.geodesic_rows``' bits, the shortest path
     over the union graph's edges in the searched space (+inf = not reached); ``pseudotime`` f64 [B]: ``distance`` over the largest
@@ -2234,40 +2267,12 @@ class Pseudotime(_NamesCalls):
             out.append(int(pred[out[-1]]))
         return np.asarray(out[::-1], np.int64)
 
-    def by_group(self, groups, group_names: Optional[Sequence[str]] = None) -> pd.DataFrame:
-        """One row per group of ``groups`` (one integer id per cell, -1 = skip) that has a reached cell, sorted by median
-        pseudotime (ties by id): ``group`` (its name from ``group_names``, else the id), ``n_cells`` (reached ones), ``median``,
-        ``min`` and ``max`` pseudotime."""
-        g, t = np.asarray(groups), np.asarray(self.pseudotime, np.float64)
-        if g.shape != t.shape or not np.issubdtype(g.dtype, np.integer):
-            raise ValueError(f"groups must hold one integer id per cell ([{len(t)}]), got {g.dtype} {g.shape}")
-        on = (g >= 0) & ~np.isnan(t)
-        rows = [(int(s), int((on & (g == s)).sum()), float(np.median(t[on & (g == s)])), float(t[on & (g == s)].min()),
-                 float(t[on & (g == s)].max())) for s in sorted(set(g[on].tolist()))]
-        rows.sort(key=lambda r: (r[2], r[0]))
-        cols = list(zip(*rows)) if rows else [[] for _ in range(5)]
-        names = list(cols[0]) if group_names is None else [group_names[s] for s in cols[0]]
-        return pd.DataFrame({"group": names, "n_cells": np.asarray(cols[1], np.int64), "median": np.asarray(cols[2], np.float64),
-                             "min": np.asarray(cols[3], np.float64), "max": np.asarray(cols[4], np.float64)})
-
-    def by_type(self) -> pd.DataFrame:
-        """``by_group`` over the called types (unsure cells skipped): ``cell_type``, ``n_cells``, ``median``, ``min``, ``max``,
-        sorted by median pseudotime."""
-        label = np.asarray(self.label, np.int64)
-        out = self.by_group(np.where(label >= 0, label, -1))
-        out["group"] = self._name(out["group"].tolist())
-        return out.rename(columns={"group": "cell_type"})
-
     def frame(self) -> pd.DataFrame:
         """One row per cell: ``index``, ``pseudotime``, ``distance``, ``pred``, ``label`` (the call's name, as ``predict`` names
         it) and ``max_prob``."""
         return pd.DataFrame({"index": list(self.index), "pseudotime": np.asarray(self.pseudotime, np.float64),
                              "distance": np.asarray(self.distance, np.float32), "pred": np.asarray(self.pred, np.int64),
                              "label": self._name(self.label), "max_prob": np.asarray(self.max_prob)})
-
-    def pseudotime_frame(self) -> pd.DataFrame:
-        """One row per cell - ``cell`` (its name) and ``pseudotime`` (empty where not reached): what ``pseudotime_file`` writes."""
-        return pd.DataFrame({"cell": [str(c) for c in self.index], "pseudotime": np.asarray(self.pseudotime, np.float64)})
 
     def summary(self) -> PseudotimeSummary:
         """Cells, roots, rounds, the farthest cell and the earliest and latest called type; ``print`` it."""
@@ -2441,3 +2446,153 @@ class Abstraction:
                                   top_pair=None if top is None else (top["a"], top["b"]),
                                   top_connectivity=float("nan") if top is None else float(top["connectivity"]),
                                   median_connectivity=float(np.median(per["connectivity"])) if len(per) else float("nan"))
+
+
+class DiffusionMapSummary(dict):
+    """``DiffusionMap.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        how = "converged" if d["converged"] else f"NOT converged (largest residual {d['max_residual']:.3g} > tol {d['tol']:.3g}: raise n_steps)"
+        return "\n".join([
+            f"{d['n_cells']} cells, k = {d['k']} graph in the {d['space']} space ({d['metric']}): {d['n_components']} connected "
+            f"components, the largest holds {d['n_in_component']} cells ({d['n_outside']} outside have no coordinates)",
+            f"{d['n_found']} diffusion components from {d['n_steps']} Lanczos steps (seed {d['seed']}"
+            f"{', breakdown: the Krylov space is exhausted' if d['breakdown'] else ''}), {how}",
+            f"eigenvalues 1, {d['second']:.6g} ... {d['last']:.6g}; gap after the stationary one {d['gap']:.4g}",
+            f"{d['n_types']} called types in the component ({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class DiffusionMap(_NamesCalls):
+    """What ``ResidentPredictor.diffmap`` returns: the diffusion map of the largest connected component of one batch's own kNN
+    graph.  B cells (``index``), C cell types (``id2label``).  ``coords`` f64 [B, n_found]: the leading eigenvectors of the
+    density-normalised symmetric transition matrix, unit length, column 0 the stationary one - scanpy's ``X_diffmap`` - NaN in
+    the rows of cells outside the component; ``eigenvalues`` f64 [n_found], descending, ``eigenvalues[0] == 1``; ``residual`` f64
+    [n_found]: the Lanczos estimate ``|beta_m s_mc|`` of ``||T y - lambda y||`` per component (0 for the stationary one, which is
+    known and not searched for); ``converged``: every residual is at most ``tol``; ``n_steps``: the Lanczos steps actually run;
+    ``breakdown``: the run ended because a step left no new direction (always on a component of fewer than ``n_steps + 2``
+    cells); ``in_component`` bool [B]; ``n_components``: the graph's connected components, single cells included; ``seed``.
+    ``n_found`` can be below the ``n_comps`` asked for: a small component, or a breakdown.  ``k`` / ``space`` / ``metric`` say
+    which graph it was; ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure)."""
+    coords: np.ndarray
+    eigenvalues: np.ndarray
+    residual: np.ndarray
+    converged: bool
+    tol: float
+    n_steps: int
+    breakdown: bool
+    in_component: np.ndarray
+    n_components: int
+    seed: int
+    k: int
+    space: str
+    metric: str
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    @property
+    def n_found(self) -> int:
+        return int(np.asarray(self.coords).shape[1])
+
+    def spectral_init(self) -> np.ndarray:
+        """f32 [B, 2]: components 1 and 2 scaled to max-abs 10, zero rows outside the component (and a zero column where the
+        component was not found) - a start for ``umap(init=...)`` as it stands."""
+        xy = np.zeros((len(self.in_component), 2), np.float64)
+        have = min(2, self.n_found - 1)
+        xy[:, :have] = np.nan_to_num(np.asarray(self.coords, np.float64)[:, 1:1 + have], nan=0.0)
+        top = np.abs(xy).max() if xy.size else 0.0
+        return (xy * (10.0 / top) if top > 0 else xy).astype(np.float32)
+
+    def coords_frame(self) -> pd.DataFrame:
+        """One row per cell - ``cell`` (its name), ``dc1``, ``dc2``, ... (column 0, the stationary component, is left out; empty
+        outside the component): what ``diffmap_file`` writes."""
+        y = np.asarray(self.coords, np.float64)
+        return pd.DataFrame({"cell": [str(c) for c in self.index], **{f"dc{c}": y[:, c] for c in range(1, y.shape[1])}})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``in_component``, ``dc1``, ``dc2``, ..., ``label`` (the call's name, as ``predict`` names
+        it) and ``max_prob``."""
+        y = np.asarray(self.coords, np.float64)
+        return pd.DataFrame({"index": list(self.index), "in_component": np.asarray(self.in_component, bool),
+                             **{f"dc{c}": y[:, c] for c in range(1, y.shape[1])}, "label": self._name(self.label),
+                             "max_prob": np.asarray(self.max_prob)})
+
+    def by_type(self) -> pd.DataFrame:
+        """One row per call (unsure included, last) over the cells of the component: ``cell_type``, ``n_cells`` and the type's
+        mean ``dc1``, ``dc2``, ..."""
+        own, y, on = np.asarray(self.label, np.int64), np.asarray(self.coords, np.float64), np.asarray(self.in_component, bool)
+        ids = sorted(set(own[on & (own >= 0)].tolist())) + ([-1] if (on & (own < 0)).any() else [])
+        members = [on & ((own == s) if s >= 0 else (own < 0)) for s in ids]
+        out = pd.DataFrame({"cell_type": self._name(ids), "n_cells": np.asarray([int(m.sum()) for m in members], np.int64)})
+        for c in range(1, y.shape[1]):
+            out[f"dc{c}"] = np.asarray([y[m, c].mean() for m in members], np.float64)
+        return out
+
+    def summary(self) -> DiffusionMapSummary:
+        """Cells, components, steps, convergence and the leading eigenvalues; ``print`` it."""
+        lam, res, on = np.asarray(self.eigenvalues, np.float64), np.asarray(self.residual, np.float64), np.asarray(self.in_component, bool)
+        own = np.asarray(self.label, np.int64)
+        at = lambda i: float(lam[i]) if -len(lam) <= i < len(lam) and len(lam) > 1 else float("nan")
+        return DiffusionMapSummary(n_cells=len(on), k=int(self.k), space=self.space, metric=self.metric,
+                                   n_components=int(self.n_components), n_in_component=int(on.sum()), n_outside=int((~on).sum()),
+                                   n_found=self.n_found, n_steps=int(self.n_steps), seed=int(self.seed), breakdown=bool(self.breakdown),
+                                   converged=bool(self.converged), tol=float(self.tol),
+                                   max_residual=float(res.max()) if res.size else 0.0, second=at(1), last=at(-1),
+                                   gap=1.0 - at(1), n_types=len(set(own[on & (own >= 0)].tolist())),
+                                   n_unsure=int((own < 0).sum()))
+
+
+class DiffusionPseudotimeSummary(dict):
+    """``DiffusionPseudotime.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        return "\n".join([
+            f"{d['n_cells']} cells ordered by diffusion distance over {d['n_dcs']} diffusion components from {d['n_roots']} root "
+            f"cell(s); {d['n_ordered']} in the component, {d['n_outside']} outside it have none",
+            f"the farthest cell lies {d['max_distance']:.4g} away (median {d['median_distance']:.4g})",
+            f"{d['n_types']} called types, earliest {d['first_type']}, latest {d['last_type']} by median pseudotime "
+            f"({d['n_unsure']} cells unsure)"])
+
+
+@dataclass
+class DiffusionPseudotime(_OrderedCells):
+    """What ``ResidentPredictor.dpt`` returns: every cell's diffusion distance from the root cells.  B cells (``index``), C cell
+    types (``id2label``).  ``distance`` f64 [B]: ``ops.diffusion_distance``' bits - ``sqrt(sum_l (lambda_l / (1 - lambda_l))^2
+    (y_l[root] - y_l[cell])^2)`` over the components ``l = 1 .. n_dcs - 1``, to the nearest root - NaN for a cell outside the
+    component; ``pseudotime`` f64 [B]: ``distance`` over the largest one, in [0, 1], NaN outside the component (``Pseudotime``'s
+    scaling); ``roots`` int64: the root cells' positions, ascending; ``n_dcs``: the diffusion components used, the stationary one
+    counted; ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch (-1 = unsure).  ``by_group``,
+    ``by_type`` and ``pseudotime_frame`` are ``Pseudotime``'s, and ``Abstraction.directed`` takes the table as it stands."""
+    distance: np.ndarray
+    pseudotime: np.ndarray
+    roots: np.ndarray
+    n_dcs: int
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``pseudotime``, ``distance``, ``label`` (the call's name, as ``predict`` names it) and
+        ``max_prob``."""
+        return pd.DataFrame({"index": list(self.index), "pseudotime": np.asarray(self.pseudotime, np.float64),
+                             "distance": np.asarray(self.distance, np.float64), "label": self._name(self.label),
+                             "max_prob": np.asarray(self.max_prob)})
+
+    def summary(self) -> DiffusionPseudotimeSummary:
+        """Cells, roots, the farthest cell and the earliest and latest called type; ``print`` it."""
+        d = np.asarray(self.distance, np.float64)
+        fin = d[np.isfinite(d)]
+        types = self.by_type()
+        return DiffusionPseudotimeSummary(n_cells=len(d), n_dcs=int(self.n_dcs), n_roots=len(self.roots), n_ordered=int(fin.size),
+                                          n_outside=len(d) - int(fin.size), max_distance=float(fin.max()) if fin.size else float("nan"),
+                                          median_distance=float(np.median(fin)) if fin.size else float("nan"), n_types=len(types),
+                                          first_type=types["cell_type"].iloc[0] if len(types) else None,
+                                          last_type=types["cell_type"].iloc[-1] if len(types) else None,
+                                          n_unsure=int((np.asarray(self.label) < 0).sum()))
