@@ -1274,6 +1274,56 @@ int wgnn_knn_rows(const float* Q, int64_t ld_q, int64_t n_q, const float* X, int
                   uint32_t flags, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Exact k nearest neighbours per SEGMENT of the rows (additive exports, WGNN_VERSION stays 206): the search behind
+ * ops.knn_segments / api.ResidentPredictor.bbknn, a batch-balanced kNN graph.  Every query row lists its k nearest rows in
+ * each of n_segs segments of the same matrix; brute force, O(n_q * n_rows * D), nothing of the distance matrix is stored.
+ *     X [n_rows, ld_x] f32          : the rows, D valid columns, under wgnn_knn_rows' alignment rules; they stay in the
+ *                                     caller's order
+ *     order int32 [n_rows]          : the row ids segment-major
+ *     seg_ptr int64 [n_segs + 1]    : segment s holds the candidates order[seg_ptr[s] .. seg_ptr[s+1]); a segment may be empty
+ *     q_first, n_q                  : the queries are the rows q_first .. q_first + n_q - 1 of X
+ *     n_segs in [1, 64], k in [1, 64], n_segs * k <= 64
+ *     n_splits                      : every segment's candidate tiles are scanned in this many contiguous sub-ranges; 0 = chosen
+ *                                     from n_q, n_rows and n_segs so that a small batch still fills the chip; a value above
+ *                                     64 / n_segs is lowered to that (a query tile has at most 64 work units); it changes no bit
+ *     idx int32, d2 f32 [n_q, ld_out]  : the BLOCKED lists, ld_out >= n_segs * k: columns s*k .. s*k+k-1 hold segment s's list,
+ *                                     ascending, with a tail of -1 / +inf; the other columns of a row are left untouched
+ *     merged_idx, merged_d2 [n_q, ld_merged] : optional (both or neither; ld_merged >= n_segs * k): the same n_segs * k entries
+ *                                     as ONE ascending list, the -1 / +inf entries last
+ *     status int32 [1] on the device: bits are OR-ed in, the caller clears it
+ * Numerics are wgnn_knn_rows': d = 0; for j = 0 .. D-1 ascending: t = q[j] - x[j]; d = fmaf(t, t, d), one chain per pair, so
+ *   a distance carries the bits wgnn_knn_rows gives that pair.  Selection is on the key (bits(d2) << 32 | ORIGINAL row id): the
+ *   low word is order[c], not the position c, so equal distances go to the lower row id within a block and, in the merged list,
+ *   across blocks.  A query is left out of the list of the segment that holds it (order[c] == q); a NaN distance is never
+ *   listed.  The order is total: the result is a function of the operands alone, not of the grid, n_splits or lane timing.
+ *   Atomics claim LDS staging slots and OR into the status word, nothing else.
+ * A work unit is (64-query tile, segment, sub-range): it streams its candidates in tiles of 64 through LDS, rows loaded by id
+ * through `order`, a lane owning 4 x 4 pairs as in wgnn_knn_rows, the last tile of a segment ending at seg_ptr[s+1]; it leaves k
+ * sorted keys per query in the workspace.  A second kernel, a wavefront per query and a lane per unit, pops the smallest head
+ * n_segs * k times under a quota of k per segment and writes each pop at its rank in both layouts.
+ * Malformed operands are safe: seg_ptr is clamped into [0, n_rows] (and to ascend); an order id outside [0, n_rows) is skipped
+ * and sets WGNN_KNN_SEGMENTS_BAD_ORDER.  (An id listed twice is searched twice; a list may then name it twice.)
+ *   workspace: wgnn_knn_segments_workspace_bytes(n_q, n_rows, n_segs, k, n_splits) = n_segs * splits * n_q * k * 8 bytes,
+ *   8-byte aligned, caller-owned.
+ * Errors, before any launch, with wgnn_knn_rows' codes: WGNN_ERR_BAD_ARG (n_q or n_rows outside [0, 2^31); n_splits outside
+ * [0, 64]; ld_out or ld_merged < n_segs * k; one of merged_idx / merged_d2 without the other; q_first < 0 or q_first + n_q >
+ * n_rows; any flag bit - none is defined; a missing operand), WGNN_ERR_UNSUPPORTED (k or n_segs outside [1, 64]; n_segs * k >
+ * 64; D outside [4, 1024]), WGNN_ERR_ALIGNMENT (D or ld_x not a multiple of 4 or ld_x < D; X not 16-byte, seg_ptr or workspace
+ * not 8-byte, another operand not 4-byte aligned), WGNN_ERR_WORKSPACE; wgnn_last_error_string names the check.  n_q == 0 returns
+ * WGNN_OK without a launch.
+ * ------------------------------------------------------------------------- */
+#define WGNN_KNN_SEGMENTS_MAX_SEGS  64   /* the most segments                                                          */
+#define WGNN_KNN_SEGMENTS_MAX_LIST  64   /* the largest n_segs * k: a query's whole list                                */
+#define WGNN_KNN_SEGMENTS_BAD_ORDER  1   /* status bit: an order id outside [0, n_rows): the candidate is skipped        */
+int wgnn_knn_segments_workspace_bytes(int64_t n_q, int64_t n_rows, int32_t n_segs, int32_t k, int32_t n_splits, int64_t* bytes);
+int wgnn_knn_segments(const float* X, int64_t ld_x, int64_t n_rows, int32_t D,
+                      const int32_t* order, const int64_t* seg_ptr, int32_t n_segs, int32_t k,
+                      int64_t q_first, int64_t n_q, int32_t n_splits,
+                      int32_t* idx, float* d2, int64_t ld_out,
+                      int32_t* merged_idx, float* merged_d2, int64_t ld_merged,
+                      int32_t* status, void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
+
+/* ---------------------------------------------------------------------------
  * k-means++ seeding of dense rows, every round on the device (additive exports, WGNN_VERSION stays 206): the seeding of
  * ops.kmeans_rows / api.ResidentPredictor.kmeans.  The assignment of a Lloyd step is wgnn_knn_rows with k = 1.
  *     X [n_rows, ld_x] f32 : the rows, D valid columns

@@ -30,6 +30,7 @@ SOUP_MAX_SLAB_GENES = 16384        # wgnn_soup_rows_*'s widest LDS slab (include
 HOOD_BAD_INDEX, HOOD_BAD_ROWPTR, HOOD_BAD_COL, HOOD_BAD_SIZE = 1, 2, 4, 8     # wgnn_hood_rows_*'s status bits (include/wgnn.h)
 HOOD_MAX_MEMBERS, HOOD_MAX_SLAB_GENES = 256, 16384     # wgnn_hood_rows_*'s largest unit and widest LDS slab (include/wgnn.h)
 KNN_MAX_K, KNN_MAX_D, KNN_MAX_SPLITS = 64, 1024, 64    # wgnn_knn_rows' limits (include/wgnn.h)
+KNN_SEGMENTS_MAX_SEGS, KNN_SEGMENTS_MAX_LIST, KNN_SEGMENTS_BAD_ORDER = 64, 64, 1     # wgnn_knn_segments' limits and status bit (include/wgnn.h)
 KMEANS_MAX_K = 4096                # wgnn_kmeans_seed's limit (include/wgnn.h); its D limits are wgnn_knn_rows'
 SILHOUETTE_MAX_GROUPS, SILHOUETTE_MAX_SPLITS = 4096, 64      # wgnn_silhouette_rows' limits (include/wgnn.h); D as wgnn_knn_rows
 SNN_MAX_K, SNN_IDX_I64 = 64, 256   # wgnn_snn_weights' limit and flag (include/wgnn.h)
@@ -143,6 +144,9 @@ SIGNATURES = {
     "wgnn_rank_genes_groups": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _u32, _vp]),
     "wgnn_knn_workspace_bytes": (C.c_int, [_i64, _i64, _i32, _i32, _vp]),
     "wgnn_knn_rows": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _u32, _vp]),
+    "wgnn_knn_segments_workspace_bytes": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _vp]),
+    "wgnn_knn_segments": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64,
+                                    _vp, _vp, _i64, _u32, _vp]),
     "wgnn_kmeans_seed_workspace_bytes": (C.c_int, [_i64, _i32, _vp]),
     "wgnn_kmeans_seed": (C.c_int, [_vp, _i64, _i64, _i32, _i32, C.c_uint64, _vp, _vp, _vp, _i64, _u32, _vp]),
     "wgnn_group_rows_reduce_workspace": (C.c_int, [_i64, _i32, _i32, _vp]),

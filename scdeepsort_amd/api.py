@@ -31,7 +31,7 @@ from . import ops as _ops
 from . import tables as _tables
 from .ops import cross_entropy_sum
 # the result tables and the host helpers they share with the predictor: every name of tables.py is reachable through this module
-from .tables import (Ambient, AmbientSummary, Attribution, ClusterCalls, Communities, CommunitiesSummary, Coverage, CoverageSummary, Doublets, DoubletsSummary,
+from .tables import (Ambient, AmbientSummary, Attribution, BatchGraph, BatchGraphSummary, ClusterCalls, Communities, CommunitiesSummary, Coverage, CoverageSummary, Doublets, DoubletsSummary,
                      GeneRanks, GeneRanksSummary, KMeans, KMeansSummary, Layout, LayoutSummary, MarkerTable, NeighborGraph, NeighborGraphSummary, PanelCalls, PanelSummary,
                      Pseudobulk, PseudobulkSummary, SignatureScores, SignatureSummary, Silhouette, SilhouetteSummary, Smoothed, SmoothedSummary, Stability,
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
@@ -1978,7 +1978,8 @@ class ResidentPredictor:
 
         What this is not: no approximate index - the cost is ``O(B^2 D)``; no fuzzy-simplicial-set connectivities (UMAP's
         weights: ``umap`` builds them from these lists, ``graph=`` there takes this table) and no clustering (``kmeans``,
-        ``louvain``); one batch only - no graph across calls.  A graph in ``space="hidden"`` is the classifier's own
+        ``louvain``); one batch only - no graph across calls (cells of several samples: ``bbknn`` lists neighbours per sample).
+        A graph in ``space="hidden"`` is the classifier's own
         view: smoothing over it can confirm a wrong call; ``space="features"`` and ``Smoothed.neighbor_agreement()`` are the
         checks."""
         if space not in KNN_SPACES:
@@ -2014,6 +2015,72 @@ class ResidentPredictor:
         lists = [[cells[j] if j >= 0 else "" for j in row] for row in graph.indices]
         out = pd.DataFrame([[c] + row for c, row in zip(cells, lists)], columns=["cell"] + [f"n{j}" for j in range(graph.k)])
         return self._save_frame(out, save_path, "neighbors")
+
+    def bbknn(self, expr, batch, k_within: int = 3, genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
+              batch_names: Optional[Sequence[str]] = None, n_batches: Optional[int] = None, index=None) -> BatchGraph:
+        """The batch-balanced kNN graph of a cohort of several samples (BBKNN, Polanski et al. 2020), built on the device: on a
+        plain ``knn`` graph the cells of one sample list each other, and clusters, layouts and pseudotime split by sample before
+        they split by biology; here every cell takes its ``k_within`` nearest cells in EACH batch separately and the union of
+        those lists is the graph.  The batch is classified once and embedded exactly as ``knn`` does (``space`` and ``metric``
+        as there), and searched by ``wgnn_knn_segments`` in one launch pair - exact brute force per batch, the rows left where
+        they are, ``knn``'s distances bit for bit, ties by (squared distance, index) within a batch and across batches.
+        ``batch``: one id or name per cell, resolved as ``annotate``'s ``clusters`` are (integer ids need ``batch_names`` or
+        ``n_batches``; ``str`` names are factorised in sorted order) - every cell has a batch, -1 is refused.  At most 64
+        batches, and ``n_batches * k_within <= 64``.  With a single batch the graph is ``knn(k=k_within)``'s.
+
+        Returns a ``BatchGraph``.  It is a ``NeighborGraph`` with ``k = n_batches * k_within``: every ``graph=`` argument
+        (``louvain``, ``leiden``, ``umap``, ``pseudotime``, ``paga``, ``diffmap``) takes it as it is, and ``smooth`` its
+        ``indices``.  Two calls give the same bits.  Whether the repair is needed at all is what ``NeighborGraph.lisi`` over the
+        batch ids says of a PLAIN ``knn`` graph; this graph is balanced by construction and its own batch LISI says nothing.
+
+        What this is not: no ``trim`` of the lists; no approximate index - the cost is ``O(B^2 D)``; no correction of the
+        embedding itself (no Harmony or MNN vectors: ``embed`` is unchanged); and no connectivities of its own - they are
+        whatever the consumer builds from the lists, ``snn`` weights (``louvain``, ``leiden``) or the fuzzy graph (``umap``,
+        ``diffmap``)."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if metric not in KNN_METRICS:
+            raise ValueError(f"metric = {metric!r}: pass one of {', '.join(map(repr, KNN_METRICS))}")
+        B, k_within = self._n_cells(expr), int(k_within)
+        ids, names = _cluster_ids(batch, batch_names, n_batches, n_cells=B)
+        if (ids < 0).any():
+            raise ValueError("batch: every cell needs a batch, -1 is not taken")
+        limit = min(_ops.SNN_MAX_K, _ops.FUZZY_MAX_K)
+        if len(names) > _ops.KNN_SEGMENTS_MAX_SEGS or k_within < 1 or len(names) * k_within > limit:
+            raise ValueError(f"{len(names)} batches with k_within = {k_within}: at most {_ops.KNN_SEGMENTS_MAX_SEGS} batches, "
+                             f"k_within >= 1 and n_batches * k_within <= {limit}")
+        self._require_fused("bbknn")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            return self._bbknn(self._over_genes(expr, genes, normalize), ids, names, k_within, space, metric, index)
+
+    def _bbknn(self, expr, ids, names, k_within, space, metric, index):
+        vb = self._values_batch(self._device_csr(expr))
+        rows = self._embed(vb.csr, space)
+        if metric == "cosine":
+            rows = F.normalize(rows, dim=1)
+        lists = _ops.knn_segments(rows, torch.from_numpy(ids).to(self.device), len(names), k_within)
+        B = int(rows.shape[0])
+        return BatchGraph(indices=lists.merged_idx.cpu().numpy().astype(np.int64), sq_distances=lists.merged_d2.cpu().numpy(),
+                          k=len(names) * k_within, space=space, metric=metric, label=vb.pred, max_prob=vb.max_prob,
+                          batch=ids, batch_names=list(names), k_within=k_within,
+                          by_batch_indices=lists.idx.cpu().numpy().astype(np.int64), by_batch_sq_distances=lists.d2.cpu().numpy(),
+                          **self._table_fields(B, index))
+
+    def bbknn_file(self, data, batch_file, k_within: int = 3, normalize=None, space: str = "hidden", metric: str = "euclidean",
+                   save_path=None) -> pd.DataFrame:
+        """``bbknn`` on a test file - its full table, its gene names as ``genes=`` and its cell names - and a batch file laid
+        out like a clusters file (an index column, the cell's name, its batch's name; the cells in the data file's order, else
+        ``ValueError``).  Returns ``knn_file``'s layout - ``cell`` then ``n0`` .. ``n{k-1}``, ``k = n_batches * k_within``,
+        nearest first, empty where a list is short - which ``smooth_file`` reads as ``neighbors_file``; written as
+        ``{species}_{tissue}_bbknn.csv`` under ``save_path`` when given.  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        batch = self._read_clusters_file(batch_file, data, index)
+        graph = self.bbknn(matrix, batch, k_within=k_within, genes=genes, normalize=normalize, space=space, metric=metric, index=index)
+        cells = [str(c) for c in index]
+        lists = [[cells[j] if j >= 0 else "" for j in row] for row in graph.indices]
+        out = pd.DataFrame([[c] + row for c, row in zip(cells, lists)], columns=["cell"] + [f"n{j}" for j in range(graph.k)])
+        return self._save_frame(out, save_path, "bbknn")
 
     # ---------------------------------------------------------------------------------------------
     def kmeans(self, expr, n_clusters: int, genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",
@@ -2098,7 +2165,8 @@ class ResidentPredictor:
         What this is not: it is Louvain, not Leiden - no refinement phase, a community can be internally disconnected; the
         weights are shared-neighbour counts, not Jaccard indices with pruning and not UMAP connectivities (``umap`` computes those, for its layout
         only: ``Layout.connectivities()``); no random restarts;
-        one batch only; a graph whose total weight ``M`` has ``M^2 max(num, den) >= 2^62`` is refused (about 10^8 edges of
+        one batch only (cells of several samples: ``bbknn`` lists neighbours per sample, and ``graph=`` takes its table);
+        a graph whose total weight ``M`` has ``M^2 max(num, den) >= 2^62`` is refused (about 10^8 edges of
         weight 16).  Fused kernels only, as ``embed``."""
         return self._graph_clusters("louvain", expr, k, resolution, weights, genes, normalize, space, metric, graph, max_sweeps, index)
 
@@ -2162,7 +2230,7 @@ class ResidentPredictor:
         What this is not: the published Leiden's randomised refinement (no theta, no random number); no CPM or other quality
         function than modularity; one pass, no repeated outer iterations - feeding a result back as the start partition is the
         obvious follow-up; it does not claim a higher modularity than ``louvain`` (measured: 0.99 to 1.005 of it).  The rest as
-        ``louvain``."""
+        ``louvain``: one batch only (cells of several samples: ``bbknn`` lists neighbours per sample, and ``graph=`` takes its table)."""
         return self._graph_clusters("leiden", expr, k, resolution, weights, genes, normalize, space, metric, graph, max_sweeps, index)
 
     def leiden_file(self, data, k: int = 15, resolution=1.0, weights: str = "snn", normalize=None, space: str = "hidden",
@@ -2198,7 +2266,8 @@ class ResidentPredictor:
 
         What this is not: not umap-learn's order of updates - there (Hogwild SGD) an edge moves both ends at once and later
         edges see the move, here a firing edge moves each end once, from that end's own row, off the previous epoch's
-        positions; no spectral init, no ``transform`` of new cells, no 3-D, no supervised mode; one batch only.  Fused kernels
+        positions; no spectral init, no ``transform`` of new cells, no 3-D, no supervised mode; one batch only
+        (cells of several samples: ``bbknn`` lists neighbours per sample, and ``graph=`` takes its table).  Fused kernels
         only, as ``embed``."""
         B = self._n_cells(expr)
         lists, k, space, metric = self._graph_lists(
@@ -2343,7 +2412,8 @@ class ResidentPredictor:
         What this is not: geodesic distance, not diffusion pseudotime (scanpy's ``tl.dpt`` averages over all paths, this takes
         the shortest); no branch detection - ``paga`` and ``Abstraction.directed`` are the coarse view of the branches; the
         lengths are distances in the searched space, so ``space="hidden"`` orders the cells as the classifier sees them
-        (``space="features"`` is the view no trained weight takes part in); one batch only; the cost is ``O(rounds x edges)``
+        (``space="features"`` is the view no trained weight takes part in); one batch only
+        (cells of several samples: ``bbknn`` lists neighbours per sample, and ``graph=`` takes its table); the cost is ``O(rounds x edges)``
         where ``rounds`` is the hop diameter from the root, which reaches the number of cells on a chain.  Fused kernels only, as
         ``embed``."""
         B = self._n_cells(expr)
@@ -2426,7 +2496,8 @@ class ResidentPredictor:
 
         What this is not: no connectivities of a weighted (UMAP) graph - every list entry counts 1; no ``model="v1.0"``; no
         thresholding or layout of the abstracted graph (``centroids`` puts the groups on a ``umap``); no transitions from RNA
-        velocity - ``directed`` orients the pairs by ``pseudotime`` alone; one batch only.  Fused kernels only, as ``embed``."""
+        velocity - ``directed`` orients the pairs by ``pseudotime`` alone; one batch only
+        (cells of several samples: ``bbknn`` lists neighbours per sample, and ``graph=`` takes its table).  Fused kernels only, as ``embed``."""
         B = self._n_cells(expr)
         lists, k, space, metric = self._graph_lists("paga", graph, B, k, space, metric, False)
         self._require_fused("paga")
@@ -2491,7 +2562,8 @@ class ResidentPredictor:
         a cell outside the component (a NaN row, which ``knn`` lists nowhere, among them) has NaN coordinates.
 
         What this is not: no Gaussian-kernel connectivities (scanpy's ``method="gauss"``) - the weights are UMAP's; no restarts,
-        so a residual above ``tol`` is reported (``converged`` False) and the caller raises ``n_steps``; one component, one batch;
+        so a residual above ``tol`` is reported (``converged`` False) and the caller raises ``n_steps``; one component, one batch
+        (cells of several samples: ``bbknn`` lists neighbours per sample, and ``graph=`` takes its table);
         an eigenvalue within about ``tol`` of another gives a basis of that eigenspace, not scanpy's particular vectors; the
         comparison with scanpy itself was not run, the formulas of ``include/wgnn.h`` are the contract.  Fused kernels only, as
         ``embed``."""

@@ -2169,6 +2169,80 @@ def knn_rows(x: torch.Tensor, k: int, queries: Optional[torch.Tensor] = None, ex
     return idx, d2
 
 
+KNN_SEGMENTS_MAX_SEGS, KNN_SEGMENTS_MAX_LIST = _lib.KNN_SEGMENTS_MAX_SEGS, _lib.KNN_SEGMENTS_MAX_LIST      # wgnn_knn_segments' limits
+
+_KNN_SEGMENTS_STATUS = ((_lib.KNN_SEGMENTS_BAD_ORDER, "order names a row outside [0, n_rows)"),)
+
+
+class SegmentLists(NamedTuple):
+    """What ``knn_segments`` returns, on the device.  ``idx`` int32 / ``d2`` f32 [n, n_groups, k]: per row and group the ``k``
+    nearest rows of that group, ascending under (d2, row id), the row itself left out, -1 / +inf where the group holds fewer.
+    ``merged_idx`` / ``merged_d2`` [n, n_groups * k]: the same entries as one ascending list, the -1 / +inf entries last."""
+    idx: torch.Tensor
+    d2: torch.Tensor
+    merged_idx: torch.Tensor
+    merged_d2: torch.Tensor
+
+
+def knn_segments(x: torch.Tensor, group: torch.Tensor, n_groups: int, k: int, n_splits: int = 0) -> SegmentLists:
+    """``wgnn_knn_segments``: for every row of ``x`` [n, D] float32 its ``k`` nearest rows in EACH of ``n_groups`` groups of the
+    rows - the lists of a batch-balanced kNN graph - exact brute force on the device in one launch pair, the rows left where
+    they are (``include/wgnn.h`` has the contract; the distance is ``knn_rows``' chain, so a pair's distance carries the bits
+    ``knn_rows`` gives it).  ``group``: an integer id in ``[0, n_groups)`` per row; an empty group is allowed, anything else is
+    a ``ValueError``.  ``n_groups`` in [1, 64], ``k`` in [1, 64], ``n_groups * k <= 64``.
+
+    Returns ``SegmentLists``.  The order within a list and in the merged list is (d2, row id): equal distances go to the lower
+    row id, within a group and across groups; a NaN distance is never listed.  The groups reach the kernel as a stable sort of
+    the ids (rows ascending within a group) and the groups' bounds, both built on the device.  ``n_splits`` (0 = chosen from
+    the sizes, else the sub-ranges of every group's scan, lowered to ``64 // n_groups``) and the chunking of a large ``n`` over
+    query ranges (halved until the partial lists of a chunk fit ``KNN_WORKSPACE_BYTES``) change no bit; two calls are
+    bit-identical.  ``D`` is zero-padded to a multiple of 4 as ``knn_rows`` does and must then be in [4, 1024].  CPU tensors
+    raise ``WgnnError``; argument errors are ``ValueError``."""
+    name = "knn_segments"
+    dev = _require_cuda(x, group)
+    n_groups, k, n_splits = int(n_groups), int(k), int(n_splits)
+    if not 1 <= n_groups <= KNN_SEGMENTS_MAX_SEGS or not 1 <= k <= KNN_MAX_K or n_groups * k > KNN_SEGMENTS_MAX_LIST:
+        raise ValueError(f"{name}: n_groups = {n_groups} and k = {k} must be in [1, {KNN_SEGMENTS_MAX_SEGS}] and [1, {KNN_MAX_K}] "
+                         f"with n_groups * k <= {KNN_SEGMENTS_MAX_LIST}")
+    if not 0 <= n_splits <= KNN_MAX_SPLITS:
+        raise ValueError(f"{name}: n_splits = {n_splits} is outside [0, {KNN_MAX_SPLITS}] (0 = chosen from the sizes)")
+    x = _knn_rows_operand(name, "x", x)
+    n, D = int(x.shape[0]), int(x.shape[1])
+    if not 4 <= D <= KNN_MAX_D:
+        raise ValueError(f"{name}: D = {D} is outside [4, {KNN_MAX_D}]")
+    if n >= 2 ** 31:
+        raise ValueError(f"{name}: n must be below 2^31")
+    if not isinstance(group, torch.Tensor) or group.dtype not in (torch.int32, torch.int64) or tuple(group.shape) != (n,):
+        raise ValueError(f"{name}: group must hold one id per row ([{n}]), int32 / int64")
+    width = n_groups * k
+    idx = torch.empty((n, width), dtype=torch.int32, device=dev)
+    d2 = torch.empty((n, width), dtype=torch.float32, device=dev)
+    m_idx, m_d2 = torch.empty_like(idx), torch.empty_like(d2)
+    out = lambda: SegmentLists(idx.view(n, n_groups, k), d2.view(n, n_groups, k), m_idx, m_d2)
+    if n == 0:
+        return out()
+    lo, hi = torch.aminmax(group)
+    if int(lo) < 0 or int(hi) >= n_groups:
+        raise ValueError(f"{name}: group id out of range [0, {n_groups}) (min {int(lo)}, max {int(hi)})")
+    order, seg_ptr = _group_major(group, n_groups)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    sizes = lambda rows: ("wgnn_knn_segments_workspace_bytes", rows, n, n_groups, k, n_splits)
+    # chunks of consecutive queries, halved until the partial lists of one chunk ([units, queries, k] 64-bit keys) fit the budget
+    step = n
+    while _workspace_bytes(*sizes(step)) > KNN_WORKSPACE_BYTES and step > 1:
+        step = -(-step // 2)
+    have = (None, 0)                                          # one allocation serves every chunk that it is large enough for
+    for r0 in range(0, n, step):
+        r1 = min(n, r0 + step)
+        ws, ws_bytes = have = _workspace(dev, *sizes(r1 - r0), have=have)
+        _lib.run(dev, "wgnn_knn_segments", _ptr(x), x.stride(0), n, D, _ptr(order), _ptr(seg_ptr), n_groups, k, r0, r1 - r0,
+                 n_splits, idx.data_ptr() + r0 * width * 4, d2.data_ptr() + r0 * width * 4, width,
+                 m_idx.data_ptr() + r0 * width * 4, m_d2.data_ptr() + r0 * width * 4, width, _ptr(status), _ptr(ws), ws_bytes, 0,
+                 _stream(dev))
+    _check_status(name, int(status), _KNN_SEGMENTS_STATUS)
+    return out()
+
+
 KMEANS_MAX_K = _lib.KMEANS_MAX_K          # wgnn_kmeans_seed's limit
 KMEANS_INITS = ("k-means++",)
 

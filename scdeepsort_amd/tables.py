@@ -1774,6 +1774,147 @@ class NeighborGraph(_NamesCalls):
                                     median_kth=med(last), mutual_share=float(self.mutual().sum() / ok.sum()) if ok.any() else float("nan"),
                                     n_unsure=int((np.asarray(self.label) < 0).sum()), median_agreement=med(agree[has]))
 
+    def _named_labels(self, name: str) -> np.ndarray:
+        """``lisi``'s ``labels`` given as a word."""
+        if name == "predicted":
+            return np.asarray(self.label, np.int64)
+        raise ValueError(f"labels = {name!r}: pass one id per cell or 'predicted'")
+
+    def lisi(self, labels="predicted", perplexity: Optional[float] = None, n_labels: Optional[int] = None) -> np.ndarray:
+        """f64 [B]: the Local Inverse Simpson's Index of ``labels`` on this graph (Korsunsky et al. 2019) - per cell the
+        effective number of labels among its neighbours, between 1 (one label) and the number of labels (all equally
+        present).  On the host in float64; ``O(B k)``.  ``labels``: one integer id per cell in ``[-1, n_labels)``
+        (``n_labels`` = None: the largest id + 1), or ``"predicted"`` for the graph's own ``label``.
+
+        Per cell, over its listed neighbours ``j`` with a finite distance: ``D_j = distances()[j]`` minus the nearest of them,
+        ``P_j = exp(-beta D_j)``, with ``beta`` from the t-SNE search of the published ``compute_simpson_index`` - start at 1,
+        double or halve until bracketed, then bisect - towards the entropy ``log(perplexity)``, a fixed 64 tries with no
+        tolerance exit (so that the result is a function of the lists alone); then ``1 / sum_l (sum_{j in l} P_j / sum_j P_j)^2``.
+        ``perplexity`` defaults to ``k / 3``; outside ``[1, k)`` it raises ``ValueError``.  A cell with fewer than two such
+        neighbours gives NaN.  A neighbour with label -1 (unsure) counts as a label of its own kind: its ``P_j`` stays in
+        ``sum_j P_j`` and is left out of every label's numerator, so it raises the index like a stranger would; a cell whose
+        neighbours are all -1 gives NaN.
+
+        LISI over BATCHES measures the mixing of a PLAIN ``knn`` graph - whether ``bbknn`` is needed at all.  A ``BatchGraph``
+        is balanced by construction and its batch LISI says nothing."""
+        idx = np.asarray(self.indices, np.int64)
+        B, k = idx.shape
+        lab = self._named_labels(labels) if isinstance(labels, str) else np.asarray(labels)
+        if lab.ndim != 1 or lab.shape[0] != B or lab.dtype.kind not in "iu":
+            raise ValueError(f"labels must hold one integer id per cell ([{B}]), got {lab.dtype} {lab.shape}")
+        lab = lab.astype(np.int64)
+        L = int(n_labels) if n_labels is not None else (int(lab.max()) + 1 if B else 0)
+        if B and (lab.min() < -1 or lab.max() >= L):
+            raise ValueError(f"label id out of range [-1, {L})")
+        perplexity = k / 3 if perplexity is None else float(perplexity)
+        if not 1 <= perplexity < k:
+            raise ValueError(f"perplexity = {perplexity:g} is outside [1, k = {k})")
+        dist = self.distances().astype(np.float64)
+        ok = (idx >= 0) & np.isfinite(dist)
+        with np.errstate(invalid="ignore"):
+            D = np.where(ok, dist - np.min(np.where(ok, dist, np.inf), axis=1, keepdims=True), 0.0)
+        theirs = np.where(ok, lab[np.where(ok, idx, 0)], -1)
+        target = np.log(perplexity)
+
+        def entropy(beta):                                   # column by column: a row's sums run in list order
+            P = np.where(ok, np.exp(-D * beta[:, None]), 0.0)
+            total, weighted = np.zeros(B), np.zeros(B)
+            for j in range(k):
+                total, weighted = total + P[:, j], weighted + D[:, j] * P[:, j]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return np.log(total) + beta * weighted / total, P, total
+
+        beta, low, high = np.ones(B), np.full(B, -np.inf), np.full(B, np.inf)
+        H, P, total = entropy(beta)
+        for _ in range(64):
+            up = H > target                                  # too flat: sharpen
+            with np.errstate(invalid="ignore"):
+                low, high = np.where(up, beta, low), np.where(up, high, beta)
+                beta = np.where(up, np.where(np.isinf(high), beta * 2.0, (beta + high) / 2.0),
+                                np.where(np.isinf(low), beta / 2.0, (beta + low) / 2.0))
+            H, P, total = entropy(beta)
+        share = np.zeros((B, max(L, 1)))
+        for j in range(k):
+            rows = np.flatnonzero(theirs[:, j] >= 0)
+            share[rows, theirs[rows, j]] += P[rows, j]
+        simpson = np.zeros(B)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            for l in range(L):
+                s = share[:, l] / total
+                simpson = simpson + s * s
+            return np.where((ok.sum(axis=1) >= 2) & (simpson > 0), 1.0 / simpson, np.nan)
+
+
+class BatchGraphSummary(NeighborGraphSummary):
+    """``BatchGraph.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        sizes = ", ".join(f"{name}: {n}" for name, n in d["batch_sizes"].items())
+        return "\n".join([NeighborGraphSummary.__str__(self),
+                          f"{d['n_batches']} batches, {d['k_within']} neighbours from each ({sizes}); {d['n_short']} cells with a "
+                          f"short list, median share of neighbours from another batch {d['median_batch_share']:.3f}"])
+
+
+@dataclass(kw_only=True)
+class BatchGraph(NeighborGraph):
+    """What ``ResidentPredictor.bbknn`` returns: a batch-balanced kNN graph (BBKNN, Polanski et al. 2020) - every cell lists its
+    ``k_within`` nearest cells in EACH of S batches.  It IS a ``NeighborGraph``: ``indices`` / ``sq_distances`` [B, k] with ``k =
+    S * k_within`` are the union of a cell's S lists as one list, ascending by (distance, index), -1 / +inf last - what every
+    ``graph=`` argument reads.  ``batch`` int64 [B]: a cell's batch id; ``batch_names``: the S names; ``by_batch_indices`` int64 /
+    ``by_batch_sq_distances`` f32 [B, S, k_within]: the lists one batch at a time, each ascending, a cell left out of the list
+    into its own batch, -1 / +inf where a batch holds fewer cells."""
+    batch: np.ndarray
+    batch_names: Sequence[str]
+    k_within: int
+    by_batch_indices: np.ndarray
+    by_batch_sq_distances: np.ndarray
+
+    def _named_labels(self, name: str) -> np.ndarray:
+        if name == "batch":
+            return np.asarray(self.batch, np.int64)
+        return super()._named_labels(name)
+
+    def batch_share(self) -> np.ndarray:
+        """f64 [B]: per cell, the share of its listed neighbours that come from another batch - ``(S - 1) / S`` by construction
+        wherever all S lists are full.  NaN for a cell without a neighbour."""
+        idx, ok = np.asarray(self.indices, np.int64), self._listed()
+        own = np.asarray(self.batch, np.int64)
+        other = ok & (own[np.where(ok, idx, 0)] != own[:, None])
+        n = ok.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n > 0, other.sum(axis=1) / n, np.nan)
+
+    def _nearest_by_batch(self) -> np.ndarray:
+        """f32 [B, S]: a cell's distance (as ``distances()`` measures) to its nearest cell of every batch, +inf without one."""
+        d2 = np.asarray(self.by_batch_sq_distances, np.float32)[:, :, 0]
+        return d2 / np.float32(2) if self.metric == "cosine" else np.sqrt(d2)
+
+    def by_batch(self) -> pd.DataFrame:
+        """One row per batch, over the cells OF that batch: ``batch``, ``n_cells``, ``n_short`` (its cells with fewer than ``k``
+        listed neighbours - some batch holds fewer than ``k_within`` other cells) and one column ``nearest_{name}`` per batch:
+        the median distance from the row's cells to their nearest cell of that batch (NaN without one).  The row's own column is
+        the scale within the batch that the others are read against."""
+        own, n = np.asarray(self.batch, np.int64), self._listed().sum(axis=1)
+        near = self._nearest_by_batch().astype(np.float64)
+        near[~np.isfinite(near)] = np.nan
+        names = list(self.batch_names)
+        out = {"batch": names, "n_cells": np.asarray([(own == s).sum() for s in range(len(names))], np.int64),
+               "n_short": np.asarray([((own == s) & (n < self.k)).sum() for s in range(len(names))], np.int64)}
+        for c, name in enumerate(names):
+            col = [near[own == s, c] for s in range(len(names))]
+            out[f"nearest_{name}"] = np.asarray([np.nanmedian(v) if np.isfinite(v).any() else np.nan for v in col], np.float64)
+        return pd.DataFrame(out)
+
+    def summary(self) -> BatchGraphSummary:
+        """``NeighborGraph.summary()`` with the batch sizes, the cells with a short list and the median ``batch_share``."""
+        own, share = np.asarray(self.batch, np.int64), self.batch_share()
+        share = share[~np.isnan(share)]
+        return BatchGraphSummary(**NeighborGraph.summary(self), n_batches=len(self.batch_names), k_within=int(self.k_within),
+                                 batch_sizes={str(name): int((own == s).sum()) for s, name in enumerate(self.batch_names)},
+                                 n_short=int((self._listed().sum(axis=1) < self.k).sum()),
+                                 median_batch_share=float(np.median(share)) if len(share) else float("nan"))
+
 
 class KMeansSummary(dict):
     """``KMeans.summary()``: a dict that prints as a few lines."""
