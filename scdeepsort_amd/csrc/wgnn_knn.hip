@@ -4,9 +4,9 @@
 // A workgroup of 256 threads holds a tile of 64 queries and streams tiles of 64 candidates past it, 16 columns of D at a time,
 // through two LDS buffers (k-major, so a lane reads four queries or four candidates with one 16-byte read).  Each lane owns a
 // 4 x 4 micro-tile of (query, candidate) pairs and carries its 16 distances in registers across the slabs of D:
-//     t = q[j] - x[j];  d = fmaf(t, t, d);   j = 0 .. D-1 ascending, d = 0 to start
+//     t = q[j] - x[j];  d = fma(t, t, d) in f32;   j = 0 .. D-1 ascending, d = 0 to start
 // - the difference form, one chain per pair, never re-associated.  Columns past D and rows past the end are loaded as zeros:
-// fmaf(0, 0, d) == d, so padding changes no bit.
+// fma(0, 0, d) == d, so padding changes no bit.
 //
 // Selection runs on the 64-bit key (bits(d) << 32 | candidate): d >= +0, so the f32 bits order as unsigned integers, every NaN
 // sorts above +inf, and keys of one query are distinct - a total order.  Per query the k smallest keys live in LDS, sorted; a
@@ -18,26 +18,23 @@
 // With n_splits > 1 the candidate tiles are dealt to grid.y in contiguous ranges, every split writes its k keys per query
 // into the workspace, and knn_merge - a wavefront per query, a lane per split - merges them under the same order.
 // Symmetry (d(i, j) == d(j, i)) is not exploited: every ordered pair is computed.
+//
+// The tile - its geometry, the loader, the chain - is wgnn_pair_tile.h's, which wgnn_knn_segments.hip and wgnn_silhouette.hip
+// run as well; the selection - the keys, the staging lists, the rank merge, the append rounds - is wgnn_topk_select.h's, shared
+// with wgnn_knn_segments.hip.  This file keeps which rows a tile holds, the test that makes a pair a survivor, and the splits.
 #include <limits.h>
 #include "wgnn_build_rows.h"
+#include "wgnn_pair_tile.h"
+#include "wgnn_topk_select.h"
 
 namespace wgnn {
 namespace {
 
-constexpr int kTQ = 64;                 // queries of a workgroup
-constexpr int kTC = 64;                 // candidates of a tile
-constexpr int kKS = 16;                 // columns of D per slab
-constexpr int kPitch = kTQ + 4;         // floats between two k-rows of a slab: 16-byte aligned, transposing writes 2-way at worst
 constexpr int kStage = 32;              // staging slots per query
 constexpr int kStagePitch = kStage + 1; // 64-bit words between two queries' staging lists (odd: the merging lanes spread over banks)
 constexpr int kMergeMark = 16;          // a staging list that has taken more keys than this is merged after the round
-constexpr int kKnnBlock = 256;
 constexpr int kMaxK = 64;
-constexpr int kMaxD = 1024;
 constexpr int kMaxSplits = 64;          // knn_merge gives every split a lane
-constexpr int kSlabFloats = 2 * kKS * kPitch;             // one buffer: the query slab, then the candidate slab
-typedef unsigned long long u64;
-constexpr u64 kNone = ((u64)0x7f800000u << 32) | 0x7fffffffu;        // (+inf, no candidate): above every selectable key
 
 struct NArgs {
     const float* Q; long ld_q; const float* X; long ld_x;
@@ -47,46 +44,11 @@ struct NArgs {
     u64* ws;
 };
 
-__host__ __device__ inline int sorted_pitch(int k) { return k | 1; }          // odd, as kStagePitch
-
 inline int knn_lds_bytes(int k) {
     return kTQ * sorted_pitch(k) * 8 + kTQ * kStagePitch * 8 + 2 * kSlabFloats * 4 + kTQ * 4 + 16;
 }
 
-// Merge the n <= kStage staged keys of one query into its sorted list of k, one WAVEFRONT's work, by rank: a lane takes up to
-// two keys of the union (k + n <= 96), counts the keys below each - every lane reads the whole union, one broadcast read per
-// key - and stores a real key whose rank is below k at that rank.  Real keys are distinct, so the ranks below k are taken once
-// each; kNone is above every real key, keeps its place at the tail (the real keys only grow in number) and is never stored.
-// All of a lane's reads are issued before its first store, and a wavefront's LDS operations complete in order.
-__device__ __forceinline__ void merge_staged(u64* list, const u64* stage, int n, int k, int lane) {
-    const int total = k + n;
-    const u64 mine0 = lane < k ? list[lane] : (lane < total ? stage[lane - k] : kNone);
-    const u64 mine1 = lane + 64 < total ? stage[lane + 64 - k] : kNone;          // k <= 64: the second key is a staged one
-    int r0 = 0, r1 = 0;
-    for (int e = 0; e < k; ++e) { const u64 v = list[e]; r0 += v < mine0; r1 += v < mine1; }
-    for (int e = 0; e < n; ++e) { const u64 v = stage[e]; r0 += v < mine0; r1 += v < mine1; }
-    __builtin_amdgcn_wave_barrier();                      // the compiler keeps the stores below the reads
-    if (mine0 != kNone && r0 < k) list[r0] = mine0;
-    if (mine1 != kNone && r1 < k) list[r1] = mine1;
-}
-
-// Every query of the workgroup whose staging count is above `mark` is merged and its count cleared: wavefront w looks after
-// the queries w, w + 4, ...; its first 16 lanes read their counts, a ballot names the lists to merge.  A count above kStage
-// says that appends found no slot (their lanes still hold the keys): the list holds kStage keys.
-__device__ __forceinline__ void merge_marked(u64* s_sorted, const u64* s_stage, int* s_cnt, int mark, int sp, int k, int wave, int lane) {
-    const int mine = wave + (kKnnBlock / 64) * (lane & 15);
-    const int n = s_cnt[mine];
-    unsigned long long todo = __ballot(lane < 16 && n > mark);
-    while (todo) {                                        // wave-uniform
-        const int b = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int ql = wave + (kKnnBlock / 64) * b;
-        merge_staged(s_sorted + ql * sp, s_stage + ql * kStagePitch, min(__shfl(n, b, 64), kStage), k, lane);
-        if (lane == 0) s_cnt[ql] = 0;
-    }
-}
-
-__global__ void __launch_bounds__(kKnnBlock) knn_kernel(const NArgs a) {
+__global__ void __launch_bounds__(kPairBlock) knn_kernel(const NArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int k = a.k, sp = sorted_pitch(k);
     u64* s_sorted = reinterpret_cast<u64*>(smem);                               // [kTQ][sp]
@@ -104,61 +66,24 @@ __global__ void __launch_bounds__(kKnnBlock) knn_kernel(const NArgs a) {
     const long t0 = n_tiles * blockIdx.y / a.n_splits, t1 = n_tiles * (blockIdx.y + 1) / a.n_splits;
     const int n_slabs = (a.D + kKS - 1) / kKS;
 
-    for (int i = tid; i < kTQ * sp; i += kKnnBlock) s_sorted[i] = kNone;
+    for (int i = tid; i < kTQ * sp; i += kPairBlock) s_sorted[i] = kNone;
     if (tid < kTQ) s_cnt[tid] = 0;
     if (tid < 3) s_flag[tid] = 0;                         // "a lane has a survivor", and the two `over` words of the rounds
 
     const bool q_ok = q0 + lrow < a.n_q;
     const float* q_src = a.Q + (size_t)(q_ok ? q0 + lrow : 0) * a.ld_q + lk4 * 4;
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto put = [&](float* dst, const float4& v) {         // transposed: column lk4*4 + i of the slab, row lrow
-        float* p = dst + (lk4 * 4) * kPitch + lrow;
-        p[0] = v.x; p[kPitch] = v.y; p[2 * kPitch] = v.z; p[3 * kPitch] = v.w;
-    };
 
     for (long t = t0; t < t1; ++t) {
         const long c0 = t * kTC;
         const bool x_ok = c0 + lrow < a.n_c;
         const float* x_src = a.X + (size_t)(x_ok ? c0 + lrow : 0) * a.ld_x + lk4 * 4;
         float acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-        float4 gq = (q_ok && lk4 * 4 < a.D) ? ld4(q_src) : zero4;
-        float4 gx = (x_ok && lk4 * 4 < a.D) ? ld4(x_src) : zero4;
-        put(s_slab, gq); put(s_slab + kKS * kPitch, gx);
-        __syncthreads();              // also orders the last tile's selection (and the set-up above) before this tile's
-        for (int s = 0; s < n_slabs; ++s) {
-            const bool more = s + 1 < n_slabs;
-            if (more) {
-                const int col = (s + 1) * kKS + lk4 * 4;
-                gq = (q_ok && col < a.D) ? ld4(q_src + (s + 1) * kKS) : zero4;
-                gx = (x_ok && col < a.D) ? ld4(x_src + (s + 1) * kKS) : zero4;
-            }
-            const float* qs = s_slab + (s & 1) * kSlabFloats + ty * 4;
-            const float* xs = s_slab + (s & 1) * kSlabFloats + kKS * kPitch + tx * 4;
-#pragma unroll 8
-            for (int kk = 0; kk < kKS; ++kk) {
-                const float4 qa = ld4(qs + kk * kPitch), xb = ld4(xs + kk * kPitch);
-                const float qv[4] = {qa.x, qa.y, qa.z, qa.w}, xv[4] = {xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float d = qv[i] - xv[j];
-                        acc[i][j] = fmaf(d, d, acc[i][j]);
-                    }
-            }
-            if (more) {
-                float* nb = s_slab + ((s + 1) & 1) * kSlabFloats;
-                put(nb, gq); put(nb + kKS * kPitch, gx);
-            }
-            __syncthreads();
-        }
+        pair_tile_d2(acc, s_slab, q_src, q_ok, x_src, x_ok, a.D, n_slabs, tid);
 
         // selection: which of the 16 pairs beat their query's k-th key (read once; it only tightens)
+        int cid[4];                                       // the lane's four candidates: one that counts is below n_c < 2^31
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cid[j] = (int)(c0 + tx * 4 + j);
         unsigned mask = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -167,48 +92,18 @@ __global__ void __launch_bounds__(kKnnBlock) knn_kernel(const NArgs a) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const long c = c0 + tx * 4 + j;
-                const u64 key = ((u64)__float_as_uint(acc[i][j]) << 32) | (unsigned)c;
+                const u64 key = pair_key(acc[i][j], cid[j]);
                 const bool self = a.self_offset >= 0 && c == a.self_offset + q;
                 if (q < a.n_q && c < a.n_c && !self && key < kth) mask |= 1u << (i * 4 + j);
             }
         }
-        if (mask) *s_flag = 1;
-        __syncthreads();
-        if (*s_flag) {                                    // uniform over the workgroup
-            // Rounds of: every lane appends what it still holds; then, if a list passed the merge mark or overflowed, the lists
-            // above the mark are merged and emptied and the lanes whose keys found no slot try again.  A round without such a
-            // list - the usual one - costs one barrier.  `over` alternates between two words: the one a round clears is set
-            // again two rounds (at least one barrier) later.
-            unsigned pending = mask;
-            for (int round = 0;; ++round) {
-                int* over = s_flag + 1 + (round & 1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (pending & (1u << (i * 4 + j))) {
-                            const int ql = ty * 4 + i;
-                            const int slot = atomicAdd(&s_cnt[ql], 1);
-                            if (slot < kStage) {
-                                s_stage[ql * kStagePitch + slot] = ((u64)__float_as_uint(acc[i][j]) << 32) | (unsigned)(c0 + tx * 4 + j);
-                                pending &= ~(1u << (i * 4 + j));
-                            }
-                            if (slot >= kMergeMark) *over = 1;
-                        }
-                __syncthreads();
-                if (!*over) break;                        // uniform; no list overflowed, so no lane holds a key any more
-                merge_marked(s_sorted, s_stage, s_cnt, kMergeMark, sp, k, wave, lane);
-                __syncthreads();
-                if (tid == 0) *over = 0;
-            }
-            if (tid == 0) *s_flag = 0;                    // read again only after the next tile's barriers
-        }
+        stage_survivors(acc, cid, mask, s_sorted, s_stage, s_cnt, s_flag, kMergeMark, kStage, kStagePitch, sp, k, tid);
     }
 
     __syncthreads();
-    merge_marked(s_sorted, s_stage, s_cnt, 0, sp, k, wave, lane);
+    merge_marked(s_sorted, s_stage, s_cnt, 0, kStage, kStagePitch, sp, k, wave, lane);
     __syncthreads();
-    for (int e = tid; e < kTQ * k; e += kKnnBlock) {
+    for (int e = tid; e < kTQ * k; e += kPairBlock) {
         const int ql = e / k, j = e - ql * k;
         const long q = q0 + ql;
         if (q >= a.n_q) continue;
@@ -298,8 +193,7 @@ extern "C" int wgnn_knn_rows(const float* Q, int64_t ld_q, int64_t n_q, const fl
     int code = 0;
     if (const char* what = check_sizes(n_q, n_c, k, n_splits, &code)) return fail(code, what);
     if (flags) return fail(WGNN_ERR_BAD_ARG, "no flag is defined for this entry (flags must be 0)");
-    if (D < 4 || D > kMaxD) return fail(WGNN_ERR_UNSUPPORTED, "D must be in [4, 1024]");
-    if (D % 4) return fail(WGNN_ERR_ALIGNMENT, "D must be a multiple of 4 (zero-pad the rows)");
+    if (int rc = check_row_width("wgnn_knn_rows", D)) return rc;
     if (ld_q < D || ld_q % 4 || ld_x < D || ld_x % 4) return fail(WGNN_ERR_ALIGNMENT, "ld_q and ld_x must be >= D and multiples of 4");
     if (ld_out < k) return fail(WGNN_ERR_BAD_ARG, "ld_out must be >= k");
     if (self_offset < -1 || (self_offset >= 0 && self_offset + n_q > n_c))
@@ -326,7 +220,7 @@ extern "C" int wgnn_knn_rows(const float* Q, int64_t ld_q, int64_t n_q, const fl
     const int lds = knn_lds_bytes(k);
     if (raise_lds(g_knn_lds, reinterpret_cast<const void*>(knn_kernel), lds) != WGNN_OK) return failed();
     const unsigned q_tiles = (unsigned)((n_q + kTQ - 1) / kTQ);
-    hipLaunchKernelGGL(knn_kernel, dim3(q_tiles, (unsigned)splits), dim3(kKnnBlock), lds, st, a);
+    hipLaunchKernelGGL(knn_kernel, dim3(q_tiles, (unsigned)splits), dim3(kPairBlock), lds, st, a);
     if (hipGetLastError() != hipSuccess) return failed();
     if (need == 0) return WGNN_OK;
     hipLaunchKernelGGL(knn_merge, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, st, a);

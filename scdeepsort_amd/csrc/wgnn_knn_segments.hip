@@ -5,7 +5,7 @@
 // The search is wgnn_knn.hip's, with a segment where that file has the whole candidate matrix: a workgroup of 256 threads holds
 // a tile of 64 queries and streams tiles of 64 candidates of ONE segment past it, 16 columns of D at a time, through two LDS
 // buffers; a lane owns a 4 x 4 micro-tile of pairs and carries its 16 distances in registers across the slabs of D,
-//     t = q[j] - x[j];  d = fmaf(t, t, d);   j = 0 .. D-1 ascending, d = 0 to start
+//     t = q[j] - x[j];  d = fma(t, t, d) in f32;   j = 0 .. D-1 ascending, d = 0 to start
 // so that a distance carries the bits wgnn_knn_rows gives the pair.  A loader thread owns one candidate row of the tile and
 // fetches it by its id, order[c]: the gather is the loader's address and nothing else.  The tile's 64 ids go to LDS beside the
 // slabs; the selection key is (bits(d) << 32 | id) - the ORIGINAL row id, so equal distances go to the lower row id within a
@@ -17,29 +17,22 @@
 // smallest head n_segs * k times under a quota of k per segment, and writes every pop at its rank in the merged list and at its
 // rank within its segment in the blocked one.  Keys are totally ordered, so the result is a function of the operands alone.
 //
-// The staging and merging of survivors (merge_staged, merge_marked) restate wgnn_knn.hip's: that file's machine code is pinned
-// by its tests and shares nothing.
+// The tile is the shared one (wgnn_pair_tile.h), and so is the staging and merging of survivors (wgnn_topk_select.h has the
+// comments): this file passes its run-time staging size where wgnn_knn.hip passes a constant.
 #include <limits.h>
 #include "wgnn_build_rows.h"
+#include "wgnn_pair_tile.h"
+#include "wgnn_topk_select.h"
 
 namespace wgnn {
 namespace {
 
-constexpr int kTQ = 64;                 // queries of a workgroup
-constexpr int kTC = 64;                 // candidates of a tile
-constexpr int kKS = 16;                 // columns of D per slab
-constexpr int kPitch = kTQ + 4;         // floats between two k-rows of a slab: 16-byte aligned, transposing writes 2-way at worst
 constexpr int kMaxStage = 32;           // staging slots per query, at most (stage_slots); a list's pitch is slots + 1 64-bit words (odd:
                                         // the merging lanes spread over banks), and a list that has taken more than half is merged
-constexpr int kSegBlock = 256;
 constexpr int kMaxK = 64;
-constexpr int kMaxD = 1024;
 constexpr int kMaxSegs = WGNN_KNN_SEGMENTS_MAX_SEGS;
 constexpr int kMaxList = WGNN_KNN_SEGMENTS_MAX_LIST;      // n_segs * k: the merge gives every entry of a query's lists a lane
 constexpr int kMaxUnits = 64;                             // n_segs * splits: the merge gives every unit a lane
-constexpr int kSlabFloats = 2 * kKS * kPitch;             // one buffer: the query slab, then the candidate slab
-typedef unsigned long long u64;
-constexpr u64 kNone = ((u64)0x7f800000u << 32) | 0x7fffffffu;        // (+inf, no candidate): above every selectable key
 
 struct SArgs {
     const float* X; long ld_x;
@@ -53,8 +46,6 @@ struct SArgs {
     int stage;
 };
 
-__host__ __device__ inline int sorted_pitch(int k) { return k | 1; }          // odd, as a staging list's pitch
-
 // Staging slots per query.  The kernel takes 96 registers: five workgroups fit a CU's register files, and 160 KiB of LDS hold
 // five only below 32 KiB each.  The slabs take 17 KiB, 32 staging slots 16.5 KiB: with 16 slots the short lists of a balanced
 // graph (k <= 8, 0.5 KiB * (k | 1) of sorted keys) leave room for the fifth workgroup; a longer list does not, and keeps 32.
@@ -65,34 +56,7 @@ inline int seg_lds_bytes(int k) {
     return kTQ * sorted_pitch(k) * 8 + kTQ * (stage_slots(k) + 1) * 8 + 2 * kSlabFloats * 4 + kTQ * 4 + kTC * 4 + 16;
 }
 
-// wgnn_knn.hip's merge of the n <= 32 staged keys of one query into its sorted list of k, one wavefront's work, by rank
-__device__ __forceinline__ void merge_staged(u64* list, const u64* stage, int n, int k, int lane) {
-    const int total = k + n;
-    const u64 mine0 = lane < k ? list[lane] : (lane < total ? stage[lane - k] : kNone);
-    const u64 mine1 = lane + 64 < total ? stage[lane + 64 - k] : kNone;          // k <= 64: the second key is a staged one
-    int r0 = 0, r1 = 0;
-    for (int e = 0; e < k; ++e) { const u64 v = list[e]; r0 += v < mine0; r1 += v < mine1; }
-    for (int e = 0; e < n; ++e) { const u64 v = stage[e]; r0 += v < mine0; r1 += v < mine1; }
-    __builtin_amdgcn_wave_barrier();                      // the compiler keeps the stores below the reads
-    if (mine0 != kNone && r0 < k) list[r0] = mine0;
-    if (mine1 != kNone && r1 < k) list[r1] = mine1;
-}
-
-// ... and of every query of the workgroup whose staging count is above `mark`: wavefront w looks after the queries w, w + 4, ...
-__device__ __forceinline__ void merge_marked(u64* s_sorted, const u64* s_stage, int* s_cnt, int mark, int stage, int sp, int k, int wave, int lane) {
-    const int mine = wave + (kSegBlock / 64) * (lane & 15);
-    const int n = s_cnt[mine];
-    unsigned long long todo = __ballot(lane < 16 && n > mark);
-    while (todo) {                                        // wave-uniform
-        const int b = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        const int ql = wave + (kSegBlock / 64) * b;
-        merge_staged(s_sorted + ql * sp, s_stage + ql * (stage + 1), min(__shfl(n, b, 64), stage), k, lane);
-        if (lane == 0) s_cnt[ql] = 0;
-    }
-}
-
-__global__ void __launch_bounds__(kSegBlock) knn_segments_kernel(const SArgs a) {
+__global__ void __launch_bounds__(kPairBlock) knn_segments_kernel(const SArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     const int k = a.k, sp = sorted_pitch(k), stage = a.stage, mark = stage >> 1;
     u64* s_sorted = reinterpret_cast<u64*>(smem);                               // [kTQ][sp]
@@ -116,17 +80,12 @@ __global__ void __launch_bounds__(kSegBlock) knn_segments_kernel(const SArgs a) 
     const long t0 = n_tiles * part / a.splits, t1 = n_tiles * (part + 1) / a.splits;
     const int n_slabs = (a.D + kKS - 1) / kKS;
 
-    for (int i = tid; i < kTQ * sp; i += kSegBlock) s_sorted[i] = kNone;
+    for (int i = tid; i < kTQ * sp; i += kPairBlock) s_sorted[i] = kNone;
     if (tid < kTQ) s_cnt[tid] = 0;
     if (tid < 3) s_flag[tid] = 0;                         // "a lane has a survivor", and the two `over` words of the rounds
 
     const bool q_ok = q0 + lrow < a.n_q;
     const float* q_src = a.X + (size_t)(q_ok ? a.q_first + q0 + lrow : 0) * a.ld_x + lk4 * 4;
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto put = [&](float* dst, const float4& v) {         // transposed: column lk4*4 + i of the slab, row lrow
-        float* p = dst + (lk4 * 4) * kPitch + lrow;
-        p[0] = v.x; p[kPitch] = v.y; p[2 * kPitch] = v.z; p[3 * kPitch] = v.w;
-    };
 
     for (long t = t0; t < t1; ++t) {
         const long c = c_lo + t * kTC + lrow;             // the loader's place in `order`: the tile ends where the segment does
@@ -142,45 +101,10 @@ __global__ void __launch_bounds__(kSegBlock) knn_segments_kernel(const SArgs a) 
         const float* x_src = a.X + (size_t)(x_ok ? row : 0) * a.ld_x + lk4 * 4;
         if (lk4 == 0) s_id[lrow] = row;                   // read after this tile's barriers, written again after its selection's
         float acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-        float4 gq = (q_ok && lk4 * 4 < a.D) ? ld4(q_src) : zero4;
-        float4 gx = (x_ok && lk4 * 4 < a.D) ? ld4(x_src) : zero4;
-        put(s_slab, gq); put(s_slab + kKS * kPitch, gx);
-        __syncthreads();              // also orders the last tile's selection (and the set-up above) before this tile's
-        for (int s = 0; s < n_slabs; ++s) {
-            const bool more = s + 1 < n_slabs;
-            if (more) {
-                const int col = (s + 1) * kKS + lk4 * 4;
-                gq = (q_ok && col < a.D) ? ld4(q_src + (s + 1) * kKS) : zero4;
-                gx = (x_ok && col < a.D) ? ld4(x_src + (s + 1) * kKS) : zero4;
-            }
-            const float* qs = s_slab + (s & 1) * kSlabFloats + ty * 4;
-            const float* xs = s_slab + (s & 1) * kSlabFloats + kKS * kPitch + tx * 4;
-#pragma unroll 8
-            for (int kk = 0; kk < kKS; ++kk) {
-                const float4 qa = ld4(qs + kk * kPitch), xb = ld4(xs + kk * kPitch);
-                const float qv[4] = {qa.x, qa.y, qa.z, qa.w}, xv[4] = {xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float d = qv[i] - xv[j];
-                        acc[i][j] = fmaf(d, d, acc[i][j]);
-                    }
-            }
-            if (more) {
-                float* nb = s_slab + ((s + 1) & 1) * kSlabFloats;
-                put(nb, gq); put(nb + kKS * kPitch, gx);
-            }
-            __syncthreads();
-        }
+        pair_tile_d2(acc, s_slab, q_src, q_ok, x_src, x_ok, a.D, n_slabs, tid);
 
         // selection: which of the 16 pairs beat their query's k-th key (read once; it only tightens).  The ids of the lane's
-        // four candidates leave LDS here, before the barrier below: the next tile's loaders write s_id after it.
+        // four candidates leave LDS here, before the first barrier of stage_survivors: the next tile's loaders write s_id after it.
         const int4 ids = *reinterpret_cast<const int4*>(s_id + tx * 4);
         const int cid[4] = {ids.x, ids.y, ids.z, ids.w};
         unsigned mask = 0;
@@ -190,46 +114,17 @@ __global__ void __launch_bounds__(kSegBlock) knn_segments_kernel(const SArgs a) 
             const u64 kth = s_sorted[(ty * 4 + i) * sp + k - 1];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const u64 key = ((u64)__float_as_uint(acc[i][j]) << 32) | (unsigned)cid[j];
+                const u64 key = pair_key(acc[i][j], cid[j]);
                 if (q < a.n_q && cid[j] >= 0 && cid[j] != a.q_first + q && key < kth) mask |= 1u << (i * 4 + j);
             }
         }
-        if (mask) *s_flag = 1;
-        __syncthreads();
-        if (*s_flag) {                                    // uniform over the workgroup
-            // Rounds of: every lane appends what it still holds; then, if a list passed the merge mark or overflowed, the lists
-            // above the mark are merged and emptied and the lanes whose keys found no slot try again.  `over` alternates between
-            // two words: the one a round clears is set again two rounds (at least one barrier) later.
-            unsigned pending = mask;
-            for (int round = 0;; ++round) {
-                int* over = s_flag + 1 + (round & 1);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (pending & (1u << (i * 4 + j))) {
-                            const int ql = ty * 4 + i;
-                            const int slot = atomicAdd(&s_cnt[ql], 1);
-                            if (slot < stage) {
-                                s_stage[ql * (stage + 1) + slot] = ((u64)__float_as_uint(acc[i][j]) << 32) | (unsigned)cid[j];
-                                pending &= ~(1u << (i * 4 + j));
-                            }
-                            if (slot >= mark) *over = 1;
-                        }
-                __syncthreads();
-                if (!*over) break;                        // uniform; no list overflowed, so no lane holds a key any more
-                merge_marked(s_sorted, s_stage, s_cnt, mark, stage, sp, k, wave, lane);
-                __syncthreads();
-                if (tid == 0) *over = 0;
-            }
-            if (tid == 0) *s_flag = 0;                    // read again only after the next tile's barriers
-        }
+        stage_survivors(acc, cid, mask, s_sorted, s_stage, s_cnt, s_flag, mark, stage, stage + 1, sp, k, tid);
     }
 
     __syncthreads();
-    merge_marked(s_sorted, s_stage, s_cnt, 0, stage, sp, k, wave, lane);
+    merge_marked(s_sorted, s_stage, s_cnt, 0, stage, stage + 1, sp, k, wave, lane);
     __syncthreads();
-    for (int e = tid; e < kTQ * k; e += kSegBlock) {
+    for (int e = tid; e < kTQ * k; e += kPairBlock) {
         const int ql = e / k, j = e - ql * k;
         if (q0 + ql >= a.n_q) continue;
         a.ws[((size_t)blockIdx.y * a.n_q + q0 + ql) * k + j] = s_sorted[ql * sp + j];
@@ -334,8 +229,7 @@ extern "C" int wgnn_knn_segments(const float* X, int64_t ld_x, int64_t n_rows, i
     int code = 0;
     if (const char* what = check_seg_sizes(n_q, n_rows, n_segs, k, n_splits, &code)) return fail(code, what);
     if (flags) return fail(WGNN_ERR_BAD_ARG, "no flag is defined for this entry (flags must be 0)");
-    if (D < 4 || D > kMaxD) return fail(WGNN_ERR_UNSUPPORTED, "D must be in [4, 1024]");
-    if (D % 4) return fail(WGNN_ERR_ALIGNMENT, "D must be a multiple of 4 (zero-pad the rows)");
+    if (int rc = check_row_width("wgnn_knn_segments", D)) return rc;
     if (ld_x < D || ld_x % 4) return fail(WGNN_ERR_ALIGNMENT, "ld_x must be >= D and a multiple of 4");
     if (ld_out < n_segs * k) return fail(WGNN_ERR_BAD_ARG, "ld_out must be >= n_segs * k");
     if ((merged_idx == nullptr) != (merged_d2 == nullptr)) return fail(WGNN_ERR_BAD_ARG, "merged_idx and merged_d2 come together or not at all");
@@ -368,7 +262,7 @@ extern "C" int wgnn_knn_segments(const float* X, int64_t ld_x, int64_t n_rows, i
     const int lds = seg_lds_bytes(k);
     if (raise_lds(g_seg_lds, reinterpret_cast<const void*>(knn_segments_kernel), lds) != WGNN_OK) return failed();
     const unsigned q_tiles = (unsigned)((n_q + kTQ - 1) / kTQ);
-    hipLaunchKernelGGL(knn_segments_kernel, dim3(q_tiles, (unsigned)(n_segs * splits)), dim3(kSegBlock), lds, st, a);
+    hipLaunchKernelGGL(knn_segments_kernel, dim3(q_tiles, (unsigned)(n_segs * splits)), dim3(kPairBlock), lds, st, a);
     if (hipGetLastError() != hipSuccess) return failed();
     hipLaunchKernelGGL(knn_segments_merge, dim3((unsigned)((n_q + 3) / 4)), dim3(256), 0, st, a);
     return hipGetLastError() == hipSuccess ? WGNN_OK : failed();

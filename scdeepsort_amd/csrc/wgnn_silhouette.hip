@@ -2,11 +2,11 @@
 // Euclidean distance (include/wgnn.h has the contract).  Brute force over every ordered pair, O(n^2 D); the [n, n] distance matrix
 // is never stored.
 //
-// The skeleton is wgnn_knn_rows': a workgroup of 256 threads holds a tile of 64 queries and streams tiles of 64 candidates past
-// it, 16 columns of D at a time, through two LDS buffers (k-major); each lane owns a 4 x 4 micro-tile of (query, candidate) pairs
-// and carries the 16 squared distances in registers across the slabs of D
-//     t = q[j] - x[j];  d2 = fmaf(t, t, d2);   j = 0 .. D-1 ascending, d2 = 0 to start
-// - that kernel's chain, bit for bit.  In place of its selection stands a reduction per group.  A candidate tile never straddles
+// The tile is the one wgnn_knn_rows runs (wgnn_pair_tile.h): a workgroup of 256 threads holds a tile of 64 queries and streams
+// tiles of 64 candidates past it, 16 columns of D at a time, through two LDS buffers (k-major); each lane owns a 4 x 4 micro-tile
+// of (query, candidate) pairs and carries the 16 squared distances in registers across the slabs of D
+//     t = q[j] - x[j];  d2 = fma(t, t, d2) in f32;   j = 0 .. D-1 ascending, d2 = 0 to start
+// - that kernel's chain bit for bit, being the same code.  In place of its selection stands a reduction per group.  A candidate tile never straddles
 // two groups: a group's members are cut into tiles of 64 from the group's own start, and a position past the group's end adds a
 // SELECTED +0.0 (its distance is computed against a row of zeros and thrown away).  The order of additions is fixed:
 //     a lane adds sqrtf(d2) of its own four candidates, ascending, into one fp64 partial per owned query, carried over the
@@ -22,20 +22,13 @@
 // computed inside one workgroup, so neither n_splits nor the grid changes a bit.  A group is never cut, so one dominant group
 // bounds the balance.
 #include <limits.h>
-#include "wgnn_build_rows.h"
+#include "wgnn_pair_tile.h"
 
 namespace wgnn {
 namespace {
 
-constexpr int kTQ = 64;                 // queries of a workgroup
-constexpr int kTC = 64;                 // candidates of a tile: part of the sums' addition order, never tuned per device
-constexpr int kKS = 16;                 // columns of D per slab
-constexpr int kPitch = kTQ + 4;         // floats between two k-rows of a slab, as in wgnn_knn.hip
-constexpr int kSilBlock = 256;
-constexpr int kMaxD = 1024;
 constexpr int kMaxGroups = 4096;
 constexpr int kMaxSplits = 64;
-constexpr int kSlabFloats = 2 * kKS * kPitch;             // one buffer: the query slab, then the candidate slab
 
 struct SilArgs {
     const float* X; long ld; const long long* seg;
@@ -76,7 +69,7 @@ __device__ __forceinline__ void finish(const SilArgs& a, long q, double s_own, l
     a.a[q] = av; a.b[q] = b; a.s[q] = sv; a.nearest[q] = nearest;
 }
 
-__global__ void __launch_bounds__(kSilBlock) sil_kernel(const SilArgs a) {
+__global__ void __launch_bounds__(kPairBlock) sil_kernel(const SilArgs a) {
     __shared__ __align__(16) float s_slab[2 * kSlabFloats];                     // [2][2][kKS][kPitch]
     __shared__ int s_g[kTQ];
 
@@ -108,11 +101,6 @@ __global__ void __launch_bounds__(kSilBlock) sil_kernel(const SilArgs a) {
 
     const bool q_ok = q0 + lrow < n_on;
     const float* q_src = a.X + (size_t)(q_ok ? q0 + lrow : 0) * a.ld + lk4 * 4;
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto put = [&](float* dst, const float4& v) {         // transposed: column lk4*4 + i of the slab, row lrow
-        float* p = dst + (lk4 * 4) * kPitch + lrow;
-        p[0] = v.x; p[kPitch] = v.y; p[2 * kPitch] = v.z; p[3 * kPitch] = v.w;
-    };
 
     for (int c = c_lo; c < c_hi; ++c) {                   // uniform over the workgroup, as everything below but the selects
         const long begin = seg_at(a, c), end = seg_at(a, c + 1);
@@ -123,42 +111,7 @@ __global__ void __launch_bounds__(kSilBlock) sil_kernel(const SilArgs a) {
             const bool x_ok = c0 + lrow < end;
             const float* x_src = a.X + (size_t)(x_ok ? c0 + lrow : 0) * a.ld + lk4 * 4;
             float acc[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-
-            float4 gq = (q_ok && lk4 * 4 < a.D) ? ld4(q_src) : zero4;
-            float4 gx = (x_ok && lk4 * 4 < a.D) ? ld4(x_src) : zero4;
-            put(s_slab, gq); put(s_slab + kKS * kPitch, gx);
-            __syncthreads();
-            for (int s = 0; s < n_slabs; ++s) {
-                const bool more = s + 1 < n_slabs;
-                if (more) {
-                    const int col = (s + 1) * kKS + lk4 * 4;
-                    gq = (q_ok && col < a.D) ? ld4(q_src + (s + 1) * kKS) : zero4;
-                    gx = (x_ok && col < a.D) ? ld4(x_src + (s + 1) * kKS) : zero4;
-                }
-                const float* qs = s_slab + (s & 1) * kSlabFloats + ty * 4;
-                const float* xs = s_slab + (s & 1) * kSlabFloats + kKS * kPitch + tx * 4;
-#pragma unroll 8
-                for (int kk = 0; kk < kKS; ++kk) {
-                    const float4 qa = ld4(qs + kk * kPitch), xb = ld4(xs + kk * kPitch);
-                    const float qv[4] = {qa.x, qa.y, qa.z, qa.w}, xv[4] = {xb.x, xb.y, xb.z, xb.w};
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float d = qv[i] - xv[j];
-                            acc[i][j] = fmaf(d, d, acc[i][j]);
-                        }
-                }
-                if (more) {
-                    float* nb = s_slab + ((s + 1) & 1) * kSlabFloats;
-                    put(nb, gq); put(nb + kKS * kPitch, gx);
-                }
-                __syncthreads();
-            }
+            pair_tile_d2(acc, s_slab, q_src, q_ok, x_src, x_ok, a.D, n_slabs, tid);
             // the lane's four candidates in ascending position; one past the group's end adds a selected +0.0
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -296,8 +249,7 @@ extern "C" int wgnn_silhouette_rows(const float* X, int64_t ld_x, int64_t n, int
     int code = 0;
     if (const char* what = check_sizes(n, K, n_splits, &code)) return fail(code, what);
     if (flags) return fail(WGNN_ERR_BAD_ARG, "no flag is defined for this entry (flags must be 0)");
-    if (D < 4 || D > kMaxD) return fail(WGNN_ERR_UNSUPPORTED, "D must be in [4, 1024]");
-    if (D % 4) return fail(WGNN_ERR_ALIGNMENT, "D must be a multiple of 4 (zero-pad the rows)");
+    if (int rc = check_row_width("wgnn_silhouette_rows", D)) return rc;
     if (ld_x < D || ld_x % 4) return fail(WGNN_ERR_ALIGNMENT, "ld_x must be >= D and a multiple of 4");
     if (workspace_bytes < 0) return fail(WGNN_ERR_WORKSPACE, "workspace_bytes is negative");
     if (n == 0) return WGNN_OK;
@@ -329,7 +281,7 @@ extern "C" int wgnn_silhouette_rows(const float* X, int64_t ld_x, int64_t n, int
         hipLaunchKernelGGL(sil_plan, dim3(1), dim3(256), 0, st, g);
         if (hipGetLastError() != hipSuccess) return failed();
     }
-    hipLaunchKernelGGL(sil_kernel, dim3(q_tiles, (unsigned)splits), dim3(kSilBlock), 0, st, g);
+    hipLaunchKernelGGL(sil_kernel, dim3(q_tiles, (unsigned)splits), dim3(kPairBlock), 0, st, g);
     if (hipGetLastError() != hipSuccess) return failed();
     if (need == 0) return WGNN_OK;
     hipLaunchKernelGGL(sil_merge, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, g);

@@ -13,6 +13,9 @@ from scdeepsort_amd import _lib, ops
 
 ROOT = Path(__file__).resolve().parent.parent
 NAME = "wgnn_knn_rows"
+CSRC = ROOT / "scdeepsort_amd" / "csrc"
+SHARED = ("wgnn_pair_tile.h", "wgnn_topk_select.h")                    # the pair tile (it holds the chain) and the top-k selection
+code = lambda name: re.sub(r"//.*", "", (CSRC / name).read_text())     # a file of csrc without its comments
 
 
 def test_symbols_are_declared_bound_and_exported():
@@ -29,9 +32,29 @@ def test_symbols_are_declared_bound_and_exported():
     assert (ops.KNN_MAX_K, ops.KNN_MAX_D, ops.KNN_MAX_SPLITS) == (64, 1024, 64)
     from scdeepsort_amd import build
     assert "wgnn_knn.hip" in [p.name for p in build.SRC]
-    src = re.sub(r"//.*", "", (ROOT / "scdeepsort_amd" / "csrc" / "wgnn_knn.hip").read_text())
-    assert "asm" not in src and "fmaf(" in src and "double" not in src                # plain C++, the chain in explicit fmaf
+    raw = (CSRC / "wgnn_knn.hip").read_text()
+    assert all('#include "%s"' % h in raw for h in SHARED) and "fmaf(" not in raw      # the shared tile and selection, no copy of them
+    src = "".join(code(name) for name in ("wgnn_knn.hip",) + SHARED)
+    assert "asm" not in src and "double" not in src and "fmaf(" in code(SHARED[0])    # plain C++, the chain in explicit fmaf
     assert not re.search(r"atomic\w*\s*\(\s*(&\s*)?a\.", src)                         # no atomic on a global operand
+
+
+def test_the_shared_tile_keeps_the_resources_the_timings_stand_on(tmp_path):
+    """The compiler's resource remarks for the three kernels built on csrc/wgnn_pair_tile.h: the occupancy each was measured
+    at, nothing in scratch, and the silhouette kernel's static LDS (the two slab buffers and its 64 group ids)."""
+    import subprocess
+    from scdeepsort_amd import build
+    for name, kernel, occupancy, lds in (("wgnn_knn", "knn_kernel", 4, None), ("wgnn_knn_segments", "knn_segments_kernel", 5, None),
+                                         ("wgnn_silhouette", "sil_kernel", 4, 17664)):
+        r = subprocess.run([build.hipcc(), *build.FLAGS, "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
+                            str(CSRC / (name + ".hip")), "-o", str(tmp_path / (name + ".s"))], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-2000:]
+        blocks = [b for b in r.stderr.split("Function Name: ")[1:] if kernel in b.split()[0]]
+        assert len(blocks) == 1, (name, kernel)
+        figure = lambda what: int(re.search(r"%s: (\d+)" % re.escape(what), blocks[0]).group(1))
+        assert figure("Occupancy [waves/SIMD]") == occupancy, (kernel, figure("Occupancy [waves/SIMD]"))
+        assert (figure("ScratchSize [bytes/lane]"), figure("VGPRs Spill"), figure("SGPRs Spill")) == (0, 0, 0), kernel
+        assert lds is None or figure("LDS Size [bytes/block]") == lds, kernel
 
 
 def test_the_kernels_compile_without_scratch(tmp_path):

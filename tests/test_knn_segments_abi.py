@@ -14,6 +14,7 @@ from scdeepsort_amd import _lib, ops
 ROOT = Path(__file__).resolve().parent.parent
 NAME = "wgnn_knn_segments"
 SOURCE = ROOT / "scdeepsort_amd" / "csrc" / "wgnn_knn_segments.hip"
+SHARED = (SOURCE.with_name("wgnn_pair_tile.h"), SOURCE.with_name("wgnn_topk_select.h"))      # the pair tile (it holds the chain), the selection
 
 
 def test_symbols_are_declared_bound_and_exported():
@@ -35,8 +36,11 @@ def test_symbols_are_declared_bound_and_exported():
     assert hasattr(sda.NeighborGraph, "lisi")
     from scdeepsort_amd import build
     assert SOURCE.name in [p.name for p in build.SRC]
-    src = re.sub(r"//.*", "", SOURCE.read_text())
-    assert "asm" not in src and "fmaf(" in src and "double" not in src                # plain C++, the chain in explicit fmaf
+    raw = SOURCE.read_text()
+    assert all('#include "%s"' % h.name in raw for h in SHARED) and "fmaf(" not in raw          # the shared tile and selection, no copy
+    code = lambda path: re.sub(r"//.*", "", path.read_text())
+    src = "".join(code(path) for path in (SOURCE,) + SHARED)
+    assert "asm" not in src and "double" not in src and "fmaf(" in code(SHARED[0])    # plain C++, the chain in explicit fmaf
     atomics = re.findall(r"atomic\w*\s*\(\s*(&\s*)?a\.(\w+)", src)                    # atomics on a global operand:
     assert atomics and all(field == "status" for _, field in atomics)                # the status word, nothing else
 

@@ -13,6 +13,7 @@ from scdeepsort_amd import _lib, ops
 
 ROOT = Path(__file__).resolve().parent.parent
 SOURCE = ROOT / "scdeepsort_amd" / "csrc" / "wgnn_silhouette.hip"
+TILE = SOURCE.with_name("wgnn_pair_tile.h")                            # the pair tile it shares with the kNN kernels: it holds the chain
 ENTRIES = (("wgnn_silhouette_rows", 15), ("wgnn_silhouette_workspace_bytes", 4))
 
 
@@ -31,8 +32,12 @@ def test_symbols_are_declared_bound_and_exported():
     assert ops.SILHOUETTE_MAX_GROUPS == 4096 and ops.SILHOUETTE_MAX_SPLITS == 64
     from scdeepsort_amd import build
     assert "wgnn_silhouette.hip" in [p.name for p in build.SRC]
-    src = re.sub(r"//.*", "", SOURCE.read_text())
-    assert "asm" not in src and "fmaf(" in src and "sqrtf(" in src and not re.search(r"\batomic\w*\s*\(", src)
+    raw = SOURCE.read_text()
+    assert '#include "%s"' % TILE.name in raw and "fmaf(" not in raw   # the shared pair tile, no copy of its chain
+    tile = re.sub(r"//.*", "", TILE.read_text())
+    src = re.sub(r"//.*", "", raw) + tile
+    assert "asm" not in src and "fmaf(" in tile and "sqrtf(" in src and not re.search(r"\batomic\w*\s*\(", src)
+    assert "double" not in tile                                        # fp64 is this file's partial sums, never the chain
     assert "__fsqrt_rn" not in src                                     # the bare hardware square root is not correctly rounded
     tables_src = (ROOT / "scdeepsort_amd" / "tables.py").read_text()
     assert not re.search(r"^\s*from\s+\.?(api|ops)\b|^\s*from\s+\.\s+import\s+.*\b(api|ops)\b|^\s*import\s+.*\b(api|ops)\b",
