@@ -293,6 +293,27 @@ int wgnn_normalize_rows_i64(const int64_t* rowptr, const float* val_in, float* v
  *       out_inv  [n_rows]              : 1 / (number of drawn edges)   - fn.mean's divisor
  *     Random numbers = hash(seed, *step, stream_id, row, draw): `step` is a DEVICE counter the caller advances on the
  *     stream (a captured hipGraph therefore draws a new sample at every replay); no state is read back.  k <= 256.
+ *
+ * The draw law (pinned bit for bit by tests/sample_reference.py).  All integer arithmetic in uint64 with wrap-around; mix32 is
+ * the upper half of the splitmix64 finaliser, as the dropout block below defines it.
+ *     K_STEP = 0xD6E8FEB86659FD93,  K_STREAM = 0xA24BAED4963EE407,  K_ROW = 0x9FB21C651E98DF25,  K_DRAW = 0xC2B2AE3D27D4EB4F
+ *   For slot s:  r = row_ids ? row_ids[s] : s,  b = rowptr[r],  deg = rowptr[r + 1] - b,  m = deg + 1 candidates: candidate
+ *   x < deg is the CSR entry b + x, candidate deg is the self-loop.
+ *     m <= k : the chosen list is 0, 1, .., deg.
+ *     m >  k : Robert Floyd's algorithm on hashed draws,
+ *         base = seed ^ (step[0] * K_STEP) ^ ((uint32)stream_id * K_STREAM) ^ ((uint64)(int64)r * K_ROW)
+ *         for i = 0 .. k-1:   j = m - k + i,   h = mix32(base + i * K_DRAW),   t = (h * (j + 1)) >> 32        (t in [0, j])
+ *                             x_i = j if t is among x_0 .. x_{i-1}, otherwise t
+ *       The key holds the ROW r, not the slot: a row repeated in row_ids gets the same list in every slot.
+ *   Output, the x_i != deg in order of i (DRAW order, the self-loop taken out, nothing sorted):
+ *     out_col / out_val [s*k + 0 ..) = col[b + x_i] / val[b + x_i], val copied bit for bit;  out_cnt[s] = their number;
+ *     out_self[s] = 1.0f iff some x_i == deg, else 0.0f;  out_inv[s] = 1.0f / max(1, out_cnt + out_self) in float32
+ *     (a correctly rounded division).  The slots [s*k + out_cnt[s], (s+1)*k) are NOT written.
+ *   Pure consequences: out_cnt + out_self == min(k, m); every k-subset of the m candidates is equally likely over the keys;
+ *   for an operand whose longest row has L entries, k' = min(k, L + 1) gives the lists of k in every row.
+ *   Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand other than row_ids, n_rows < 0, k <= 0),
+ *   WGNN_ERR_UNSUPPORTED (k > 256); n_rows == 0 is WGNN_OK and writes nothing; wgnn_last_error_string names the check.
+ *   row_ids is not checked against the operand's row count (the entry is not given it).
  * ------------------------------------------------------------------------- */
 int wgnn_sample_rows(const int32_t* rowptr, const int32_t* col, const float* val, const int32_t* row_ids,
                      int64_t n_rows, int32_t k, uint64_t seed, const int64_t* step, int32_t stream_id,

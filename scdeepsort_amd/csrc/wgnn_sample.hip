@@ -93,10 +93,13 @@ extern "C" int wgnn_sample_rows(const int32_t* rowptr, const int32_t* col, const
                                 int64_t n_rows, int32_t k, uint64_t seed, const int64_t* step, int32_t stream_id,
                                 int32_t* out_col, float* out_val, int32_t* out_cnt, float* out_self, float* out_inv,
                                 void* stream) {
-    if (!rowptr || !col || !val || !step || !out_col || !out_val || !out_cnt || !out_self || !out_inv || n_rows < 0)
-        return WGNN_ERR_BAD_ARG;
-    if (k <= 0) return WGNN_ERR_BAD_ARG;
-    if (k > 64 * kMaxQ) return WGNN_ERR_UNSUPPORTED;
+    auto fail = [](int code, const char* what) { return wgnn::fail(code, "wgnn_sample_rows", what); };
+    wgnn::error_clear();
+    if (!rowptr || !col || !val || !step || !out_col || !out_val || !out_cnt || !out_self || !out_inv)
+        return fail(WGNN_ERR_BAD_ARG, "rowptr, col, val, step and the five outputs are required");
+    if (n_rows < 0) return fail(WGNN_ERR_BAD_ARG, "n_rows is negative");
+    if (k <= 0) return fail(WGNN_ERR_BAD_ARG, "k must be positive");
+    if (k > 64 * kMaxQ) return fail(WGNN_ERR_UNSUPPORTED, "k must be <= 256");
     if (n_rows == 0) return WGNN_OK;
     SArgs a{rowptr, col, val, row_ids, (long)n_rows, k, (unsigned long long)seed, reinterpret_cast<const long long*>(step),
             stream_id, out_col, out_val, out_cnt, out_self, out_inv};
