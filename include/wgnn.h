@@ -1711,6 +1711,68 @@ int wgnn_basis_combine(const double* V, int64_t ld, int32_t m, const double* S, 
 int wgnn_diffusion_distance(const double* Y, int64_t ldy, int64_t n, const double* g, int32_t n_dcs, const int64_t* roots,
                             int32_t n_roots, double* d, uint32_t flags, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Harmony (Korsunsky et al. 2019) on dense rows (additive exports, WGNN_VERSION stays 206): the kernels behind ops.harmony_rows
+ * and api.ResidentPredictor.harmony.  All arithmetic is float64; every operation named here is rounded on its own (no fused
+ * multiply-add), every sum runs in the stated order, which the data alone fix: nothing depends on the grid, there is no atomic,
+ * two calls give the same bits, and numpy restates every entry (bit for bit where no exp / pow / log takes part).
+ *     B cells, D columns, K clusters, S batches;  b_i int32 in [0, S): a cell's batch;  unit(z) = z / sqrt(sum_j z_j^2), j ascending
+ *     U = unit(Z0) [B, D];  Y [K, D] unit centres;  R, dist, e [B, K] contiguous;  T [n_blocks, K, S];  O, E, pen [K, S];
+ *     M [K, S, D], n [K, S];  Pr_s = N_s / B;  theta [S];  block q = { i : i mod n_blocks == q }, member m of it is cell q + m n_blocks
+ *
+ * wgnn_harmony_scores        - dot_ik = sum_j U_ij Y_kj (a product and an add each, j ascending from +0.0), dist_ik = 2 (1 - dot_ik),
+ *     a_ik = -dist_ik / sigma, e_ik = exp(a_ik - max_k a_ik).  dot is optional.
+ * wgnn_harmony_assign_block  - for the members of block q: t_ik = e_ik * pen[k, b_i] (pen == null: t = e), R_ik = t_ik / sum_k t_ik
+ *     with k ascending from +0.0.  It also leaves, in the workspace, one [K, S] table per chunk of WGNN_HARMONY_T_CHUNK members:
+ *     P[c, k, s] = the sum of R_ik over the chunk's members with b_i = s, members ascending from +0.0.
+ * wgnn_harmony_fold          - one workgroup.  q_store >= 0: T[q_store] = sum_c P[c], c ascending from +0.0 (an empty block: +0.0).
+ *     Then O = sum of T[q'] over q' != q_skip, q' ascending from +0.0 (q_skip = -1: over all), E_ks = (sum_s O_ks) * Pr_s with s
+ *     ascending, and, where pen is given, pen_ks = pow((E_ks + 1) / (O_ks + 1), theta_s).  The sum without a block replaces
+ *     Harmony's remove-and-add-back of a block, which drifts.
+ * wgnn_weighted_group_reduce - M[k, s, :] = sum of R_ik * X_i over the rows of group s and n[k, s] = the sum of R_ik (a product and
+ *     an add each).  order int32 [B] / seg_ptr int64 [S + 1]: the rows group-major, ascending within a group.  A group's rows are
+ *     cut into chunks of WGNN_HARMONY_W_CHUNK, a chunk is added in order from +0.0, then the chunks in order from +0.0.  With S = 1
+ *     and X = U these are the centres before unit().
+ * wgnn_harmony_objective     - out[1] = sum R_ik dist_ik, out[2] = sum R_ik log R_ik (0 where R_ik = 0), out[3] = sum R_ik (theta_b
+ *     log((O_kb + 1) / (E_kb + 1))) with b = b_i; out[0] = (out[1] + sigma out[2]) + sigma out[3].  A row adds its terms k ascending,
+ *     WGNN_HARMONY_OBJ_CHUNK consecutive rows are added in row order, then the chunks in order, each from +0.0.
+ * wgnn_harmony_apply         - Zc_i = Z0_i - sum_k R_ik W[k, b_i, :] (k ascending from +0.0) and U_i = unit(Zc_i).  R == null:
+ *     U_i = unit(Z0_i) alone (Zc, W and batch are not read).  A zero row gives NaN: the caller checks.
+ *   A batch id outside [0, S) reads nothing out of bounds: the cell gets pen = 1, no correction, and takes no part in T or the
+ *   objective (ops refuses such ids before any launch).
+ * ------------------------------------------------------------------------- */
+#define WGNN_HARMONY_MAX_K        256   /* clusters                                                                   */
+#define WGNN_HARMONY_MAX_BATCHES   64   /* batches                                                                    */
+#define WGNN_HARMONY_MAX_D       1024   /* columns                                                                    */
+#define WGNN_HARMONY_MAX_BLOCKS    64   /* blocks of a sweep                                                          */
+#define WGNN_HARMONY_T_CHUNK       64   /* members per partial table: part of T's order                               */
+#define WGNN_HARMONY_W_CHUNK      256   /* rows per partial moment: part of M's and n's order                         */
+#define WGNN_HARMONY_OBJ_CHUNK    256   /* rows per partial objective: part of its order                              */
+/* Errors, before any launch: WGNN_ERR_BAD_ARG (a missing operand; n_rows outside [1, 2^31); sigma not positive and finite; q,
+ * q_store or q_skip outside its range; ld < D; grid_blocks outside [0, 65536]; an unknown flag), WGNN_ERR_UNSUPPORTED (K outside
+ * [1, 256], S outside [1, 64], D outside [1, 1024], n_blocks outside [1, 64]), WGNN_ERR_WORKSPACE (a workspace smaller than asked
+ * for), WGNN_ERR_ALIGNMENT (64-bit operands not 8-byte, 32-bit ones not 4-byte aligned); wgnn_last_error_string names the check. */
+int wgnn_harmony_scores(const double* U, int64_t ld_u, const double* Y, int64_t ld_y, int64_t n_rows, int32_t D, int32_t K,
+                        double sigma, double* dot, double* dist, double* e, uint32_t flags, void* stream);
+int wgnn_harmony_assign_workspace_bytes(int64_t n_rows, int32_t K, int32_t S, int32_t n_blocks, int64_t* bytes);
+int wgnn_harmony_assign_block(const double* e, const int32_t* batch, const double* pen, int64_t n_rows, int32_t K, int32_t S,
+                              int32_t n_blocks, int32_t q, double* R, void* workspace, int64_t workspace_bytes,
+                              int32_t grid_blocks, uint32_t flags, void* stream);
+int wgnn_harmony_fold(const void* workspace, int64_t workspace_bytes, int64_t n_rows, double* T, const double* Pr,
+                      const double* theta, int32_t K, int32_t S, int32_t n_blocks, int32_t q_store, int32_t q_skip, double* O,
+                      double* E, double* pen, uint32_t flags, void* stream);
+int wgnn_weighted_group_reduce_workspace_bytes(int64_t n_rows, int32_t K, int32_t S, int32_t D, int64_t* bytes);
+int wgnn_weighted_group_reduce(const double* X, int64_t ld_x, const double* R, const int32_t* order, const void* seg_ptr,
+                               int64_t n_rows, int32_t D, int32_t K, int32_t S, double* M, double* n, void* workspace,
+                               int64_t workspace_bytes, int32_t grid_blocks, uint32_t flags, void* stream);
+int wgnn_harmony_objective_workspace_bytes(int64_t n_rows, int64_t* bytes);
+int wgnn_harmony_objective(const double* R, const double* dist, const int32_t* batch, const double* O, const double* E,
+                           const double* theta, int64_t n_rows, int32_t K, int32_t S, double sigma, double* out,
+                           void* workspace, int64_t workspace_bytes, uint32_t flags, void* stream);
+int wgnn_harmony_apply(const double* Z0, int64_t ld_z, const double* R, const double* W, const int32_t* batch, int64_t n_rows,
+                       int32_t D, int32_t K, int32_t S, double* Zc, double* U, int32_t grid_blocks, uint32_t flags,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,9 @@ GEODESIC_LANES, GEODESIC_MAX_BLOCKS = 16, 8192     # wgnn_geodesic_round's lanes
 DIFFUSION_UNSORTED, DIFFUSION_BAD_COL, DIFFUSION_BAD_ROWPTR, DIFFUSION_BAD_WEIGHT = 1, 2, 4, 8    # the wgnn_diffusion_* / wgnn_lanczos_apply status bits
 DIFFUSION_LANES, DIFFUSION_MAX_BLOCKS, DIFFUSION_MAX_COMPS = 16, 8192, 64      # the row sum's lanes, the largest grid, the most components
 LANCZOS_CHUNK, LANCZOS_MAX_STEPS, LANCZOS_NORM, LANCZOS_BREAKDOWN = 256, 1024, 256, 2.0 ** -26    # wgnn_lanczos_*'s dot order, limit, flag and halt bound
-ABI_MAJOR = 2               # include/wgnn.h WGNN_VERSION / 100
+HARMONY_MAX_K, HARMONY_MAX_BATCHES, HARMONY_MAX_D, HARMONY_MAX_BLOCKS = 256, 64, 1024, 64      # the wgnn_harmony_* limits (include/wgnn.h)
+HARMONY_T_CHUNK, HARMONY_W_CHUNK, HARMONY_OBJ_CHUNK = 64, 256, 256     # ... and the chunks that are part of their sums' orders
+ABI_MAJOR = 2              # include/wgnn.h WGNN_VERSION / 100
 ABI_MIN = 206                      # 0.2.1: shared-pair marks in tile-plan entries; 0.2.2: WGNN_FLAG_OUT_SCALE_ALPHA (gnn.GNN sets it); 0.2.3: fused training glue; 0.2.5: even-padded plan segments
 
 _vp, _i32, _i64, _u32, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_int
@@ -179,6 +181,15 @@ SIGNATURES = {
     "wgnn_lanczos_scale": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _u32, _vp]),
     "wgnn_basis_combine": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i64, _u32, _vp]),
     "wgnn_diffusion_distance": (C.c_int, [_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _u32, _vp]),
+    "wgnn_harmony_scores": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, C.c_double, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_harmony_assign_workspace_bytes": (C.c_int, [_i64, _i32, _i32, _i32, _vp]),
+    "wgnn_harmony_assign_block": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _u32, _vp]),
+    "wgnn_harmony_fold": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _u32, _vp]),
+    "wgnn_weighted_group_reduce_workspace_bytes": (C.c_int, [_i64, _i32, _i32, _i32, _vp]),
+    "wgnn_weighted_group_reduce": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _u32, _vp]),
+    "wgnn_harmony_objective_workspace_bytes": (C.c_int, [_i64, _vp]),
+    "wgnn_harmony_objective": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.c_double, _vp, _vp, _i64, _u32, _vp]),
+    "wgnn_harmony_apply": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i32, _u32, _vp]),
 }
 
 

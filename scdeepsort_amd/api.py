@@ -37,7 +37,8 @@ from .tables import (Ambient, AmbientSummary, Attribution, BatchGraph, BatchGrap
                      StabilitySummary, KNN_METRICS, KNN_SPACES, SMOOTH_MAX_NEIGHBORS, _NamesCalls, _benjamini_hochberg, _call_names, _check_index, _cluster_ids, _keep_levels,
                      _neighbor_lists, _rank_genes_stats, _rho_levels, _signature_scores,
                      Abstraction, AbstractionSummary, Pseudotime, PseudotimeSummary, _paga_connectivities, _scaled_pseudotime,
-                     DiffusionMap, DiffusionMapSummary, DiffusionPseudotime, DiffusionPseudotimeSummary)
+                     DiffusionMap, DiffusionMapSummary, DiffusionPseudotime, DiffusionPseudotimeSummary,
+                     Harmonized, HarmonizedGraph, HarmonizedSummary)
 
 _tables._rows_topk = lambda *a: _ops.rows_topk(*a)      # MarkerTable.top's device route: tables.py itself imports no ops
 
@@ -2081,6 +2082,83 @@ class ResidentPredictor:
         lists = [[cells[j] if j >= 0 else "" for j in row] for row in graph.indices]
         out = pd.DataFrame([[c] + row for c, row in zip(cells, lists)], columns=["cell"] + [f"n{j}" for j in range(graph.k)])
         return self._save_frame(out, save_path, "bbknn")
+
+    def harmony(self, expr, batch, n_clusters: Optional[int] = None, theta=2.0, sigma: float = 0.1, lamb: float = 1.0, k: Optional[int] = 15,
+                compare: bool = True, n_blocks: int = 20, max_iter: int = 10, max_iter_cluster: int = 20, epsilon_cluster: float = 1e-5,
+                epsilon: float = 1e-4, seed: int = 0, genes=None, normalize=None, space: str = "hidden",
+                batch_names: Optional[Sequence[str]] = None, n_batches: Optional[int] = None, index=None) -> Harmonized:
+        """The batch-corrected embedding of a cohort of several samples (Harmony, Korsunsky et al. 2019), computed on the device.
+        ``bbknn`` repairs the graph; everything that reads ROWS - ``ops.kmeans_rows``, a plain ``knn`` graph, distances - still
+        sees the sample before the biology.  Here the rows themselves are moved: the batch is classified once and embedded
+        exactly as ``knn`` does (``space`` as there), and ``ops.harmony_rows`` takes soft clusters of the unit rows under a
+        batch-diversity penalty (``theta``, a scalar or one value per batch; ``sigma`` the softness) and removes a per-cluster,
+        per-batch ridge offset (``lamb``) from every cell, round by round until the objective settles - all in float64, in
+        fixed summation orders: two calls give the same bits.  ``batch``: as ``bbknn`` takes it (-1 is refused); at most 64
+        batches.  ``n_clusters`` defaults to ``min(round(B / 30), 100)``; the other keywords are ``ops.harmony_rows``'.
+
+        ``k`` (1..64, default 15): the corrected unit rows are searched by ``wgnn_knn_rows`` and returned as ``graph`` - a
+        ``NeighborGraph`` with ``metric="cosine"`` that knows the batches, so that ``graph.lisi("batch")`` says whether the
+        samples now mix, and that ``louvain``, ``leiden``, ``umap``, ``pseudotime``, ``paga`` and ``diffmap`` take as ``graph=``
+        (``smooth`` its ``indices``).  ``k=None`` skips it.  ``compare=True`` also searches the UNCORRECTED unit rows
+        (``graph_before`` - ``knn(metric="cosine")``'s lists), which ``Harmonized.mixing()`` / ``summary()`` read against.
+
+        Returns a ``Harmonized``.  A cell whose embedding is all zero or holds a non-finite value raises ``ValueError``.
+
+        What this is not: one categorical covariate only; no ``tau`` (no discounting of small clusters); no per-batch automatic
+        ``lamb``; the blocks are a fixed stride over the cells (``i mod n_blocks``), not a random order; ``kmeans`` /
+        ``silhouette`` still embed from ``expr`` - ``ops.kmeans_rows(torch.from_numpy(h.coords).to(device), K)`` is the way for now;
+        one batch of cells per call.  The comparison with harmonypy was not run: the formulas in ``include/wgnn.h`` and their
+        numpy restatement are the contract."""
+        if space not in KNN_SPACES:
+            raise ValueError(f"space = {space!r}: pass one of {', '.join(map(repr, KNN_SPACES))}")
+        if k is not None and not 1 <= int(k) <= _ops.KNN_MAX_K:
+            raise ValueError(f"k = {k} is outside [1, {_ops.KNN_MAX_K}] (None: no graph)")
+        B = self._n_cells(expr)
+        ids, names = _cluster_ids(batch, batch_names, n_batches, n_cells=B)
+        if (ids < 0).any():
+            raise ValueError("batch: every cell needs a batch, -1 is not taken")
+        if len(names) > _ops.HARMONY_MAX_BATCHES:
+            raise ValueError(f"{len(names)} batches: at most {_ops.HARMONY_MAX_BATCHES}")
+        self._require_fused("harmony")
+        _check_index(index, B)
+        with torch.cuda.device(self.device), torch.no_grad():
+            vb = self._values_batch(self._device_csr(self._over_genes(expr, genes, normalize)))
+            full = self._embed(vb.csr, space)                          # the hidden space comes with its zero padding columns
+            rows = full[:, :self.hidden].contiguous() if space == "hidden" else full
+            run = _ops.harmony_rows(rows, torch.from_numpy(ids).to(self.device), len(names), n_clusters=n_clusters, theta=theta,
+                                    sigma=sigma, lamb=lamb, n_blocks=n_blocks, max_iter=max_iter, max_iter_cluster=max_iter_cluster,
+                                    epsilon_cluster=epsilon_cluster, epsilon=epsilon, seed=seed)
+            coords = run.coords.to(torch.float32)
+            fields = self._table_fields(B, index)
+
+            def graph_of(x):
+                idx, d2 = _ops.knn_rows(F.normalize(x, dim=1), int(k))
+                return HarmonizedGraph(indices=idx.cpu().numpy().astype(np.int64), sq_distances=d2.cpu().numpy(), k=int(k),
+                                       space=space, metric="cosine", label=vb.pred, max_prob=vb.max_prob, batch=ids,
+                                       batch_names=list(names), **fields)
+
+            R = run.R.cpu().numpy() if run.R is not None else np.zeros((B, 0), np.float64)
+            return Harmonized(coords=coords.cpu().numpy(), embedding=rows.cpu().numpy(), cluster_prob=R,
+                              cluster=R.argmax(axis=1).astype(np.int64) if R.shape[1] else np.zeros(B, np.int64),
+                              centers=run.centers.cpu().numpy() if run.centers is not None else np.zeros((0, rows.shape[1])),
+                              batch=ids, batch_names=list(names), objective=list(run.objective), n_iter=run.n_iter,
+                              converged=run.converged, space=space, graph=None if k is None else graph_of(coords),
+                              graph_before=graph_of(full) if k is not None and compare else None, label=vb.pred,
+                              max_prob=vb.max_prob, **fields)
+
+    def harmony_file(self, data, batch_file, normalize=None, space: str = "hidden", save_path=None, **harmony) -> pd.DataFrame:
+        """``harmony`` on a test file - its full table, its gene names as ``genes=`` and its cell names - and a batch file laid
+        out as ``bbknn_file`` reads it (an index column, the cell's name, its batch's name; the cells in the data file's order,
+        else ``ValueError``).  Returns one row per cell, ``cell`` then ``h1`` .. ``hD``: the corrected coordinates, written as
+        ``{species}_{tissue}_harmony.csv`` under ``save_path`` when given.  ``harmony``: the call's other keywords (``theta``,
+        ``n_clusters``, ...; no graph is built).  ``normalize``: as for ``predict``."""
+        matrix, genes, index = self._read_counts_file(data)
+        batch = self._read_clusters_file(batch_file, data, index)
+        harmony.update(k=None, compare=False)
+        h = self.harmony(matrix, batch, genes=genes, normalize=normalize, space=space, index=index, **harmony)
+        out = pd.DataFrame({"cell": [str(c) for c in index],
+                            **{f"h{j + 1}": h.coords[:, j] for j in range(h.coords.shape[1])}})
+        return self._save_frame(out, save_path, "harmony")
 
     # ---------------------------------------------------------------------------------------------
     def kmeans(self, expr, n_clusters: int, genes=None, normalize=None, space: str = "hidden", metric: str = "euclidean",

@@ -21,7 +21,7 @@ SRC = [PKG / "csrc" / "wgnn_kernels.hip", PKG / "csrc" / "wgnn_tiled.hip", PKG /
        PKG / "csrc" / "wgnn_rank_genes.hip", PKG / "csrc" / "wgnn_knn.hip", PKG / "csrc" / "wgnn_kmeans.hip",
        PKG / "csrc" / "wgnn_silhouette.hip", PKG / "csrc" / "wgnn_louvain.hip", PKG / "csrc" / "wgnn_leiden.hip",
        PKG / "csrc" / "wgnn_umap.hip", PKG / "csrc" / "wgnn_geodesic.hip", PKG / "csrc" / "wgnn_diffusion.hip",
-       PKG / "csrc" / "wgnn_knn_segments.hip"]
+       PKG / "csrc" / "wgnn_knn_segments.hip", PKG / "csrc" / "wgnn_harmony.hip"]
 LIB = PKG / "libwgnn_hip.so"
 GEN = PKG / "csrc" / "gen_flat_asm.py"          # writes csrc/wgnn_flat_asm.inc (the hand-scheduled entry pipeline)
 

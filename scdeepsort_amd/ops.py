@@ -3451,3 +3451,355 @@ def diffusion_distance(Y: torch.Tensor, g, roots) -> torch.Tensor:
     _lib.run(dev, "wgnn_diffusion_distance", _ptr(Y), int(Y.shape[1]), B, _ptr(g), n_dcs, _ptr(r), int(r.shape[0]), _ptr(d), 0,
              _stream(dev))
     return d
+
+
+HARMONY_MAX_K, HARMONY_MAX_BATCHES, HARMONY_MAX_D, HARMONY_MAX_BLOCKS = (_lib.HARMONY_MAX_K, _lib.HARMONY_MAX_BATCHES, _lib.HARMONY_MAX_D,
+                                                                         _lib.HARMONY_MAX_BLOCKS)      # the wgnn_harmony_* limits
+HARMONY_MAX_GRID = 1 << 16
+
+
+def _f64(name, what, t, shape):
+    """``t`` checked as a contiguous float64 tensor of ``shape`` (``None`` entries are free); returns it."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.dim() != len(shape) or not t.is_contiguous() or \
+            any(s is not None and int(n) != s for n, s in zip(t.shape, shape)):
+        want = ", ".join("*" if s is None else str(s) for s in shape)
+        raise ValueError(f"{name}: {what} must be a contiguous float64 tensor [{want}]")
+    return t
+
+
+def _harmony_sizes(name, B=None, K=None, S=None, D=None, n_blocks=None, grid_blocks=0):
+    for what, v, lo, hi in (("B", B, 1, 2 ** 31 - 1), ("K", K, 1, HARMONY_MAX_K), ("S", S, 1, HARMONY_MAX_BATCHES),
+                            ("D", D, 1, HARMONY_MAX_D), ("n_blocks", n_blocks, 1, HARMONY_MAX_BLOCKS),
+                            ("grid_blocks", grid_blocks, 0, HARMONY_MAX_GRID)):
+        if v is not None and not lo <= int(v) <= hi:
+            raise ValueError(f"{name}: {what} = {int(v)} is outside [{lo}, {hi}]")
+
+
+def _harmony_batch(name, batch, B):
+    if not isinstance(batch, torch.Tensor) or batch.dtype != torch.int32 or tuple(batch.shape) != (B,) or not batch.is_contiguous():
+        raise ValueError(f"{name}: batch must be a contiguous int32 tensor [{B}]")
+    return batch
+
+
+def harmony_scores(U: torch.Tensor, Y: torch.Tensor, sigma: float, want_dot: bool = False):
+    """``wgnn_harmony_scores``: ``(dot | None, dist, e)`` float64 [B, K] of the unit rows ``U`` [B, D] against the unit centres
+    ``Y`` [K, D] (both float64): ``dot_ik = sum_j U_ij Y_kj`` (``j`` ascending, a product and an add each), ``dist = 2 (1 - dot)``,
+    ``e_ik = exp(-dist_ik / sigma - max_k(-dist_ik / sigma))``.  ``dot`` and ``dist`` are numpy's bits."""
+    name = "harmony_scores"
+    U, Y = _f64(name, "U", U, (None, None)), _f64(name, "Y", Y, (None, None))
+    (B, D), K = U.shape, int(Y.shape[0])
+    if Y.shape[1] != D:
+        raise ValueError(f"{name}: Y has {Y.shape[1]} columns, U {D}")
+    _harmony_sizes(name, B=B, K=K, D=D)
+    if not (float(sigma) > 0 and math.isfinite(float(sigma))):
+        raise ValueError(f"{name}: sigma = {sigma} must be positive and finite")
+    dev = _require_cuda(U, Y)
+    dot = torch.empty((B, K), dtype=torch.float64, device=dev) if want_dot else None
+    dist, e = torch.empty((B, K), dtype=torch.float64, device=dev), torch.empty((B, K), dtype=torch.float64, device=dev)
+    _lib.run(dev, "wgnn_harmony_scores", _ptr(U), D, _ptr(Y), D, B, D, K, float(sigma), _ptr(dot), _ptr(dist), _ptr(e), 0,
+             _stream(dev))
+    return dot, dist, e
+
+
+def harmony_assign_block(e: torch.Tensor, batch: torch.Tensor, n_batches: int, n_blocks: int, q: int, R: torch.Tensor,
+                         pen: Optional[torch.Tensor] = None, workspace: Optional[tuple] = None, grid_blocks: int = 0) -> tuple:
+    """``wgnn_harmony_assign_block``: the rows ``q, q + n_blocks, ...`` of ``R`` float64 [B, K] become ``e * pen[:, b_i]``
+    divided by its sum over ``k`` (ascending); ``pen`` float64 [K, S] = None: ones.  No other row of ``R`` is written.  Returns
+    the workspace ``(tensor, n_bytes)`` that now holds the block's chunk tables - ``harmony_fold``'s first argument, and what to
+    pass back as ``workspace`` for the next block.  ``grid_blocks`` (0 = chosen) changes no bit."""
+    name = "harmony_assign_block"
+    e = _f64(name, "e", e, (None, None))
+    B, K = e.shape
+    S, n_blocks, q = int(n_batches), int(n_blocks), int(q)
+    _harmony_sizes(name, B=B, K=K, S=S, n_blocks=n_blocks, grid_blocks=grid_blocks)
+    if not 0 <= q < n_blocks:
+        raise ValueError(f"{name}: q = {q} is outside [0, {n_blocks})")
+    _f64(name, "R", R, (B, K))
+    _harmony_batch(name, batch, B)
+    if pen is not None:
+        _f64(name, "pen", pen, (K, S))
+    dev = _require_cuda(e, batch, R, pen)
+    ws, ws_bytes = _workspace(dev, "wgnn_harmony_assign_workspace_bytes", B, K, S, n_blocks, have=workspace or (None, 0))
+    _lib.run(dev, "wgnn_harmony_assign_block", _ptr(e), _ptr(batch), _ptr(pen), B, K, S, n_blocks, q, _ptr(R), _ptr(ws), ws_bytes,
+             int(grid_blocks), 0, _stream(dev))
+    return ws, ws_bytes
+
+
+def harmony_fold(T: torch.Tensor, Pr: torch.Tensor, theta: Optional[torch.Tensor], n_rows: int, q_store: int = -1, q_skip: int = -1,
+                 workspace: Optional[tuple] = None, want_pen: bool = True, out: Optional[tuple] = None):
+    """``wgnn_harmony_fold``, one workgroup: with ``q_store >= 0`` the table ``T[q_store]`` of ``T`` float64 [n_blocks, K, S] is
+    retaken from the chunk tables that ``harmony_assign_block`` left in ``workspace``; then ``O`` = the sum of ``T`` without block
+    ``q_skip`` (-1: of all), ``E = rowsum(O) * Pr`` and ``pen = pow((E + 1) / (O + 1), theta)``.  Returns ``(O, E, pen | None)``
+    float64 [K, S] - ``out`` when given."""
+    name = "harmony_fold"
+    T = _f64(name, "T", T, (None, None, None))
+    n_blocks, K, S = T.shape
+    _harmony_sizes(name, B=n_rows, K=K, S=S, n_blocks=n_blocks)
+    _f64(name, "Pr", Pr, (S,))
+    if want_pen:
+        _f64(name, "theta", theta, (S,))
+    q_store, q_skip = int(q_store), int(q_skip)
+    if not -1 <= q_store < n_blocks or not -1 <= q_skip < n_blocks:
+        raise ValueError(f"{name}: q_store = {q_store} and q_skip = {q_skip} must be in [-1, {n_blocks})")
+    if q_store >= 0 and workspace is None:
+        raise ValueError(f"{name}: q_store needs the workspace that harmony_assign_block returned")
+    dev = _require_cuda(T, Pr, theta)
+    if out is None:
+        out = tuple(torch.empty((K, S), dtype=torch.float64, device=dev) for _ in range(3 if want_pen else 2))
+    O, E = _f64(name, "out's O", out[0], (K, S)), _f64(name, "out's E", out[1], (K, S))
+    pen = _f64(name, "out's pen", out[2], (K, S)) if want_pen else None
+    ws, ws_bytes = workspace if q_store >= 0 else (None, 0)
+    _lib.run(dev, "wgnn_harmony_fold", _ptr(ws), ws_bytes, int(n_rows), _ptr(T), _ptr(Pr), _ptr(theta) if want_pen else None, K, S,
+             n_blocks, q_store, q_skip, _ptr(O), _ptr(E), _ptr(pen), 0, _stream(dev))
+    return O, E, pen
+
+
+def weighted_group_reduce(X: torch.Tensor, R: torch.Tensor, group: Optional[torch.Tensor], n_groups: int,
+                          out: Optional[tuple] = None, major: Optional[tuple] = None, grid_blocks: int = 0):
+    """``wgnn_weighted_group_reduce``: ``(M float64 [K, S, D], n float64 [K, S])`` with ``M[k, s] = sum of R[i, k] * X[i]`` and
+    ``n[k, s] = sum of R[i, k]`` over the rows ``i`` of group ``s`` - ``X`` float64 [B, D], ``R`` float64 [B, K], ``group`` int32 /
+    int64 [B] in ``[0, S)`` (any other id = the row takes no part; ``None`` with ``S = 1``: every row).  The rows of a group are
+    added in ascending order, in chunks of 256 and chunk by chunk, every product and add rounded on its own: numpy's bits, and
+    two calls are bit-identical.  ``major``: ``_group_major(group, S)`` where the caller already has it; ``grid_blocks`` (0 =
+    chosen) changes no bit."""
+    name = "weighted_group_reduce"
+    X, R = _f64(name, "X", X, (None, None)), _f64(name, "R", R, (None, None))
+    (B, D), K, S = X.shape, int(R.shape[1]), int(n_groups)
+    if R.shape[0] != B:
+        raise ValueError(f"{name}: R has {R.shape[0]} rows, X {B}")
+    _harmony_sizes(name, B=B, K=K, S=S, D=D, grid_blocks=grid_blocks)
+    if group is None and major is None and S != 1:
+        raise ValueError(f"{name}: without group, n_groups must be 1")
+    dev = _require_cuda(X, R, group)
+    if major is None:
+        if group is None:
+            group = torch.zeros(B, dtype=torch.int32, device=dev)
+        _group_operand(name, ValueError, group, B, S, False, says=f"{name}: group must hold one int32 / int64 id per row ([{B}])")
+        major = _group_major(group, S)
+    order, seg_ptr = major
+    if out is None:
+        out = (torch.empty((K, S, D), dtype=torch.float64, device=dev), torch.empty((K, S), dtype=torch.float64, device=dev))
+    M, n = _f64(name, "out's M", out[0], (K, S, D)), _f64(name, "out's n", out[1], (K, S))
+    ws, ws_bytes = _workspace(dev, "wgnn_weighted_group_reduce_workspace_bytes", B, K, S, D)
+    _lib.run(dev, "wgnn_weighted_group_reduce", _ptr(X), D, _ptr(R), _ptr(order), _ptr(seg_ptr), B, D, K, S, _ptr(M), _ptr(n),
+             _ptr(ws), ws_bytes, int(grid_blocks), 0, _stream(dev))
+    return M, n
+
+
+def harmony_objective(R: torch.Tensor, dist: torch.Tensor, batch: torch.Tensor, O: torch.Tensor, E: torch.Tensor,
+                      theta: torch.Tensor, sigma: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``wgnn_harmony_objective``: float64 [4] on the device - harmonypy's objective ``sum R dist + sigma sum R log R + sigma sum
+    R theta log((O + 1) / (E + 1))`` and its three sums (the last two before ``sigma``), rows in chunks of 256."""
+    name = "harmony_objective"
+    R = _f64(name, "R", R, (None, None))
+    B, K = R.shape
+    _f64(name, "dist", dist, (B, K))
+    O = _f64(name, "O", O, (K, None))
+    S = int(O.shape[1])
+    _harmony_sizes(name, B=B, K=K, S=S)
+    _f64(name, "E", E, (K, S)), _f64(name, "theta", theta, (S,))
+    _harmony_batch(name, batch, B)
+    if not (float(sigma) > 0 and math.isfinite(float(sigma))):
+        raise ValueError(f"{name}: sigma = {sigma} must be positive and finite")
+    dev = _require_cuda(R, dist, batch, O, E, theta)
+    out = torch.empty(4, dtype=torch.float64, device=dev) if out is None else _f64(name, "out", out, (4,))
+    ws, ws_bytes = _workspace(dev, "wgnn_harmony_objective_workspace_bytes", B)
+    _lib.run(dev, "wgnn_harmony_objective", _ptr(R), _ptr(dist), _ptr(batch), _ptr(O), _ptr(E), _ptr(theta), B, K, S, float(sigma),
+             _ptr(out), _ptr(ws), ws_bytes, 0, _stream(dev))
+    return out
+
+
+def harmony_apply(Z0: torch.Tensor, R: Optional[torch.Tensor] = None, W: Optional[torch.Tensor] = None,
+                  batch: Optional[torch.Tensor] = None, out: Optional[tuple] = None, grid_blocks: int = 0):
+    """``wgnn_harmony_apply``: ``(Zc, U)`` float64 [B, D] with ``Zc_i = Z0_i - sum_k R[i, k] W[k, b_i]`` (``k`` ascending) and
+    ``U_i = Zc_i / sqrt(sum_j Zc_ij^2)`` (``j`` ascending) - ``W`` float64 [K, S, D].  Without ``R``: ``(Z0, unit(Z0))``.  numpy's
+    bits; a zero row gives NaN."""
+    name = "harmony_apply"
+    Z0 = _f64(name, "Z0", Z0, (None, None))
+    B, D = Z0.shape
+    K = S = 1
+    if R is not None:
+        R = _f64(name, "R", R, (B, None))
+        K = int(R.shape[1])
+        W = _f64(name, "W", W, (K, None, D))
+        S = int(W.shape[1])
+        _harmony_batch(name, batch, B)
+    _harmony_sizes(name, B=B, K=K, S=S, D=D, grid_blocks=grid_blocks)
+    dev = _require_cuda(Z0, R, W, batch)
+    if out is None:
+        out = (torch.empty((B, D), dtype=torch.float64, device=dev) if R is not None else Z0,
+               torch.empty((B, D), dtype=torch.float64, device=dev))
+    Zc, U = _f64(name, "out's Zc", out[0], (B, D)), _f64(name, "out's U", out[1], (B, D))
+    _lib.run(dev, "wgnn_harmony_apply", _ptr(Z0), D, _ptr(R), _ptr(W) if R is not None else None,
+             _ptr(batch) if R is not None else None, B, D, K, S, _ptr(Zc) if R is not None else None, _ptr(U), int(grid_blocks), 0,
+             _stream(dev))
+    return Zc, U
+
+
+def harmony_ridge(M: torch.Tensor, n: torch.Tensor, lamb: float) -> torch.Tensor:
+    """``W`` float64 [K, S, D]: the ridge offsets of harmonypy's ``moe_correct_ridge`` from the moments ``M`` [K, S, D] and ``n``
+    [K, S] in closed form (the system has an arrow shape; the intercept is dropped)::
+
+        w0_k = (sum_s lamb M_ks / (n_ks + lamb)) / (sum_s lamb n_ks / (n_ks + lamb));    W_ks = (M_ks - n_ks w0_k) / (n_ks + lamb)
+
+    with float64 framework operations, one rounding each, the sums sequential with ``s`` ascending from 0: numpy's bits."""
+    K, S, D = M.shape
+    lamb = float(lamb)
+    num, den = torch.zeros((K, D), dtype=torch.float64, device=M.device), torch.zeros(K, dtype=torch.float64, device=M.device)
+    for s in range(S):
+        nl = n[:, s] + lamb
+        num = num + (M[:, s] * lamb) / nl[:, None]
+        den = den + (n[:, s] * lamb) / nl
+    w0 = num / den[:, None]
+    W = torch.empty_like(M)
+    for s in range(S):
+        W[:, s] = (M[:, s] - n[:, s, None] * w0) / (n[:, s] + lamb)[:, None]
+    return W
+
+
+class HarmonyRows(NamedTuple):
+    """What ``harmony_rows`` returns.  On the device, float64: ``coords`` [B, D] (the corrected rows), ``R`` [B, K] (the soft
+    cluster memberships), ``centers`` [K, D] (unit rows), ``O`` / ``E`` [K, S] (observed and expected cluster-by-batch mass).  On
+    the host: ``objective`` (one value per round, the seeding's first), ``objective_cluster`` (every clustering iteration's),
+    ``inner_iters`` (clustering iterations per round), ``n_iter`` (rounds) and ``converged``."""
+    coords: torch.Tensor
+    R: Optional[torch.Tensor]
+    centers: Optional[torch.Tensor]
+    O: Optional[torch.Tensor]
+    E: Optional[torch.Tensor]
+    objective: list
+    objective_cluster: list
+    inner_iters: list
+    n_iter: int
+    converged: bool
+
+
+def harmony_default_clusters(n_cells: int) -> int:
+    """Harmony's default number of clusters: ``min(round(B / 30), 100)``, at least 1."""
+    return max(1, min(int(round(n_cells / 30.0)), 100))
+
+
+def harmony_rows(x: torch.Tensor, batch: torch.Tensor, n_batches: int, n_clusters: Optional[int] = None, theta=2.0,
+                 sigma: float = 0.1, lamb: float = 1.0, n_blocks: int = 20, max_iter: int = 10, max_iter_cluster: int = 20,
+                 epsilon_cluster: float = 1e-5, epsilon: float = 1e-4, seed: int = 0) -> HarmonyRows:
+    """Harmony (Korsunsky et al. 2019) on the rows of ``x`` [B, D] float32 with one batch id per row (``batch`` int32 / int64 in
+    ``[0, n_batches)``; an empty batch is allowed), on the device, in float64, deterministic::
+
+        Z0 = f64(x);  U = unit(Z0);  Y = unit(f64(kmeans_rows(f32(U), K, seed=seed, max_iter=25).centers))
+        scores;  R = softmax(-dist / sigma) block by block;  objective
+        for round in 1 .. max_iter:
+            for it in 1 .. max_iter_cluster:
+                Y = unit(sum_i R_ik U_i);  scores;  for q in 0 .. n_blocks - 1: re-assign block q under pen_q;  objective
+                stop from it = 4 on when (old - new) / |old| < epsilon_cluster, old / new the sums of the previous / latest 3 values
+            M, n = moments of Z0 under R per (cluster, batch);  W = harmony_ridge(M, n, lamb);  Zc = Z0 - sum_k R_ik W[k, b_i];  U = unit(Zc)
+            stop when (obj[-2] - obj[-1]) / |obj[-2]| < epsilon on the rounds' last objectives
+
+    Block ``q`` is the cells ``i`` with ``i mod n_blocks == q`` - a fixed stride where the published algorithm draws a random
+    order - and ``pen_q = pow((E + 1) / (O + 1), theta)`` is taken from the tables WITHOUT block ``q``, recomputed as a sum of the
+    other blocks' tables (``include/wgnn.h``; ``tests/harmony_reference.py`` restates every step).  One 8-byte read-back per
+    clustering iteration.  ``theta`` is a scalar or one value per batch.  ``n_clusters`` defaults to ``min(round(B / 30), 100)``.
+    With ``n_batches == 1`` the correction is zero by algebra: ``f64(x)`` is returned unchanged, without iterating.
+
+    A row that holds a non-finite value or has a zero norm raises ``ValueError`` naming how many; so does a batch id outside
+    ``[0, n_batches)``.  A centre of zero norm, or an objective that is no finite number, raises ``WgnnError``.  Argument errors
+    are ``ValueError``; CPU tensors raise ``WgnnError``.  Returns a ``HarmonyRows``."""
+    import numpy as np
+    name = "harmony_rows"
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError(f"{name}: x must be a 2-D float32 tensor")
+    B, D = int(x.shape[0]), int(x.shape[1])
+    S = int(n_batches)
+    K = harmony_default_clusters(B) if n_clusters is None else int(n_clusters)
+    if B < 1:
+        raise ValueError(f"{name}: x holds no row")
+    if not 1 <= -(-D // 4) * 4 <= KNN_MAX_D:
+        raise ValueError(f"{name}: D = {D} is outside [1, {KNN_MAX_D}]")
+    if not 1 <= K <= HARMONY_MAX_K:
+        raise ValueError(f"{name}: n_clusters = {K} is outside [1, {HARMONY_MAX_K}]")
+    if K > B:
+        raise ValueError(f"{name}: n_clusters = {K}, but there are only {B} rows")
+    if not 1 <= S <= HARMONY_MAX_BATCHES:
+        raise ValueError(f"{name}: n_batches = {S} is outside [1, {HARMONY_MAX_BATCHES}]")
+    if not 1 <= int(n_blocks) <= HARMONY_MAX_BLOCKS:
+        raise ValueError(f"{name}: n_blocks = {n_blocks} is outside [1, {HARMONY_MAX_BLOCKS}]")
+    n_blocks = int(n_blocks)
+    th = np.asarray(theta, np.float64)
+    if th.ndim > 1 or (th.ndim == 1 and th.shape[0] != S) or not np.all(np.isfinite(th)) or np.any(th < 0):
+        raise ValueError(f"{name}: theta must be a finite scalar >= 0 or one such value per batch ([{S}])")
+    th = np.ascontiguousarray(np.broadcast_to(th, (S,)))
+    for what, v in (("sigma", sigma), ("lamb", lamb)):
+        if not (float(v) > 0 and math.isfinite(float(v))):
+            raise ValueError(f"{name}: {what} = {v} must be positive and finite")
+    for what, v in (("epsilon_cluster", epsilon_cluster), ("epsilon", epsilon)):
+        if not float(v) >= 0:
+            raise ValueError(f"{name}: {what} = {v} must be >= 0")
+    if int(max_iter) < 1 or int(max_iter_cluster) < 1:
+        raise ValueError(f"{name}: max_iter and max_iter_cluster must be >= 1")
+    if not isinstance(batch, torch.Tensor) or batch.dtype not in (torch.int32, torch.int64) or tuple(batch.shape) != (B,):
+        raise ValueError(f"{name}: batch must hold one int32 / int64 id per row ([{B}])")
+    dev = _require_cuda(x, batch)
+    lo, hi = torch.aminmax(batch)
+    if int(lo) < 0 or int(hi) >= S:
+        raise ValueError(f"{name}: batch id out of range [0, {S}) (min {int(lo)}, max {int(hi)})")
+    n_bad = int((~torch.isfinite(x).all(dim=1)).sum())
+    if n_bad:
+        raise ValueError(f"{name}: {n_bad} of the {B} rows hold a non-finite value")
+    Z0 = x.to(torch.float64).contiguous()
+    if S == 1:
+        return HarmonyRows(Z0, None, None, None, None, [], [], [], 0, True)
+    _, U = harmony_apply(Z0)
+    n_zero = int((~torch.isfinite(U).all(dim=1)).sum())
+    if n_zero:
+        raise ValueError(f"{name}: {n_zero} of the {B} rows have a zero norm")
+    batch = batch.to(torch.int32).contiguous()
+    theta_d, sigma, lamb = torch.as_tensor(th, device=dev), float(sigma), float(lamb)
+    Pr = (torch.bincount(batch.long(), minlength=S).to(torch.float64) / float(B)).contiguous()
+    _, Y = harmony_apply(kmeans_rows(U.to(torch.float32), K, seed=seed, max_iter=25).centers.to(torch.float64).contiguous())
+    if not bool(torch.isfinite(Y).all()):
+        raise WgnnError(f"{name}: a seeded centre has a zero norm")
+    R = torch.empty((B, K), dtype=torch.float64, device=dev)
+    T = torch.zeros((n_blocks, K, S), dtype=torch.float64, device=dev)
+    tables = tuple(torch.empty((K, S), dtype=torch.float64, device=dev) for _ in range(3))       # O, E, pen
+    M1, n1 = torch.empty((K, 1, D), dtype=torch.float64, device=dev), torch.empty((K, 1), dtype=torch.float64, device=dev)
+    MS, nS = torch.empty((K, S, D), dtype=torch.float64, device=dev), torch.empty((K, S), dtype=torch.float64, device=dev)
+    Zc, obj = torch.empty_like(Z0), torch.empty(4, dtype=torch.float64, device=dev)
+    all_rows = (torch.arange(B, dtype=torch.int32, device=dev), torch.tensor([0, B], dtype=torch.int64, device=dev))
+    by_batch = _group_major(batch, S)
+    trace: list = []
+
+    def sweep(e, first):
+        ws = None
+        if not first:
+            harmony_fold(T, Pr, theta_d, B, q_skip=0, out=tables)
+        for q in range(n_blocks):
+            ws = harmony_assign_block(e, batch, S, n_blocks, q, R, pen=None if first else tables[2], workspace=ws)
+            last = q + 1 == n_blocks
+            harmony_fold(T, Pr, theta_d, B, q_store=q, q_skip=-1 if last or first else q + 1, workspace=ws, out=tables)
+
+    def cluster_step(first=False):
+        _, dist, e = harmony_scores(U, Y, sigma)
+        sweep(e, first)
+        value = float(harmony_objective(R, dist, batch, tables[0], tables[1], theta_d, sigma, out=obj)[0])
+        if not math.isfinite(value):
+            raise WgnnError(f"{name}: the objective is {value}: a centre of zero norm or a cluster without weight")
+        trace.append(value)
+
+    cluster_step(first=True)
+    outer, inner, converged = [trace[-1]], [], False
+    for _ in range(int(max_iter)):
+        for it in range(1, int(max_iter_cluster) + 1):
+            weighted_group_reduce(U, R, None, 1, out=(M1, n1), major=all_rows)
+            harmony_apply(M1.view(K, D), out=(M1.view(K, D), Y))
+            cluster_step()
+            if it >= 4:
+                old, new = sum(trace[-4:-1]), sum(trace[-3:])
+                if (old - new) / abs(old) < float(epsilon_cluster):
+                    break
+        inner.append(it)
+        outer.append(trace[-1])
+        weighted_group_reduce(Z0, R, None, S, out=(MS, nS), major=by_batch)
+        harmony_apply(Z0, R, harmony_ridge(MS, nS, lamb).contiguous(), batch, out=(Zc, U))
+        if (outer[-2] - outer[-1]) / abs(outer[-2]) < float(epsilon):
+            converged = True
+            break
+    return HarmonyRows(Zc, R, Y, tables[0], tables[1], outer, trace, inner, len(inner), converged)

@@ -2737,3 +2737,125 @@ class DiffusionPseudotime(_OrderedCells):
                                           first_type=types["cell_type"].iloc[0] if len(types) else None,
                                           last_type=types["cell_type"].iloc[-1] if len(types) else None,
                                           n_unsure=int((np.asarray(self.label) < 0).sum()))
+
+
+@dataclass(kw_only=True)
+class HarmonizedGraph(NeighborGraph):
+    """The kNN graph of a cohort's unit rows, before or after ``ResidentPredictor.harmony`` corrected them.  It IS a
+    ``NeighborGraph`` (``metric="cosine"``) - what every ``graph=`` argument reads - that also knows the cells' batches:
+    ``batch`` int64 [B], ``batch_names`` the S names, and ``lisi("batch")`` is the mixing of the samples on it."""
+    batch: np.ndarray
+    batch_names: Sequence[str]
+
+    def _named_labels(self, name: str) -> np.ndarray:
+        if name == "batch":
+            return np.asarray(self.batch, np.int64)
+        return super()._named_labels(name)
+
+
+class HarmonizedSummary(dict):
+    """``Harmonized.summary()``: a dict that prints as a few lines."""
+
+    def __str__(self) -> str:
+        d = self
+        how = f"converged after {d['n_iter']} rounds" if d["converged"] else f"NOT converged after {d['n_iter']} rounds"
+        sizes = ", ".join(f"{name}: {n}" for name, n in d["batch_sizes"].items())
+        lines = [f"{d['n_cells']} cells of {d['n_batches']} batches ({sizes}) in the {d['space']} space, {d['n_clusters']} soft "
+                 f"clusters, {how}; objective {d['objective_first']:.6g} -> {d['objective_last']:.6g}",
+                 f"median shift {d['median_shift']:.4g} (median row length {d['median_norm']:.4g})"]
+        if d["batch_lisi_after"] is not None:
+            before = lambda v: "not compared" if v is None else f"{v:.3f}"
+            lines.append(f"median batch LISI {before(d['batch_lisi_before'])} -> {d['batch_lisi_after']:.3f}, median type LISI "
+                         f"{before(d['type_lisi_before'])} -> {d['type_lisi_after']:.3f} (k = {d['k']})")
+            if d["type_lisi_before"] is not None and d["type_lisi_after"] > d["type_lisi_before"]:
+                lines.append("WARNING: the predicted-type LISI rose - the correction mixed cell types as well as batches")
+        return "\n".join(lines)
+
+
+@dataclass
+class Harmonized(_NamesCalls):
+    """What ``ResidentPredictor.harmony`` returns: the batch-corrected embedding of one cohort (Harmony, Korsunsky et al. 2019).
+    B cells (``index``), D columns, K soft clusters, S batches (``batch_names``), C cell types (``id2label``).  ``coords`` f32
+    [B, D]: the corrected rows - ``ops.kmeans_rows`` / ``ops.knn_rows`` take them as they are; ``embedding`` f32 [B, D]: the rows
+    before; ``cluster_prob`` f64 [B, K]: Harmony's soft memberships ``R`` and ``cluster`` int64 [B] their argmax; ``centers`` f64
+    [K, D]: the unit centres; ``batch`` int64 [B]; ``objective``: one value per round (the seeding's first); ``n_iter`` /
+    ``converged``: ``ops.harmony_rows``'; ``label`` int64 [B] / ``max_prob`` f32 [B]: ``classify``'s call of the batch, made on
+    the uncorrected input (-1 = unsure).  ``graph`` / ``graph_before``: the kNN graphs (``HarmonizedGraph``, cosine, ``k``
+    neighbours) of the corrected and of the uncorrected unit rows, ``None`` where the call skipped them.  With a single batch
+    nothing is corrected: ``coords`` equals ``embedding``, ``cluster_prob`` / ``centers`` are empty and ``cluster`` is 0."""
+    coords: np.ndarray
+    embedding: np.ndarray
+    cluster_prob: np.ndarray
+    cluster: np.ndarray
+    centers: np.ndarray
+    batch: np.ndarray
+    batch_names: Sequence[str]
+    objective: Sequence[float]
+    n_iter: int
+    converged: bool
+    space: str
+    graph: Optional[HarmonizedGraph]
+    graph_before: Optional[HarmonizedGraph]
+    label: np.ndarray
+    max_prob: np.ndarray
+    index: Sequence
+    id2label: Sequence[str]
+    label_map: Optional[Tuple[dict, dict]] = field(default=None, repr=False)
+
+    def shift(self) -> np.ndarray:
+        """f64 [B]: the length of each cell's correction, ``|coords - embedding|``."""
+        return np.sqrt(((np.asarray(self.coords, np.float64) - np.asarray(self.embedding, np.float64)) ** 2).sum(axis=1))
+
+    def mixing(self) -> pd.DataFrame:
+        """One row per cell: ``batch_lisi_before`` / ``batch_lisi_after`` - ``NeighborGraph.lisi`` of the batch ids on
+        ``graph_before`` / ``graph`` - and ``type_lisi_before`` / ``type_lisi_after``, the same of ``classify``'s calls.  A
+        correction that works raises the first pair and leaves the second where it was.  NaN columns where a graph was skipped;
+        without ``graph`` it raises ``ValueError``."""
+        if self.graph is None:
+            raise ValueError("mixing needs the graph of the corrected rows: call harmony with k, not k=None")
+        B = len(self.batch)
+        nan = np.full(B, np.nan)
+        lisi = lambda g, what: nan if g is None else g.lisi(what, n_labels=len(self.batch_names) if what == "batch" else len(self.id2label))
+        return pd.DataFrame({"index": list(self.index),
+                             "batch_lisi_before": lisi(self.graph_before, "batch"), "batch_lisi_after": lisi(self.graph, "batch"),
+                             "type_lisi_before": lisi(self.graph_before, "predicted"),
+                             "type_lisi_after": lisi(self.graph, "predicted")})
+
+    def by_batch(self) -> pd.DataFrame:
+        """One row per batch: ``batch``, ``n_cells`` and ``median_shift``, the median length of its cells' corrections (NaN for
+        an empty batch)."""
+        own, shift = np.asarray(self.batch, np.int64), self.shift()
+        names = list(self.batch_names)
+        return pd.DataFrame({"batch": names, "n_cells": np.asarray([(own == s).sum() for s in range(len(names))], np.int64),
+                             "median_shift": np.asarray([np.median(shift[own == s]) if (own == s).any() else np.nan
+                                                         for s in range(len(names))], np.float64)})
+
+    def frame(self) -> pd.DataFrame:
+        """One row per cell: ``index``, ``cell_type`` / ``prob`` (named as ``predict`` names them), ``batch`` (its name),
+        ``cluster`` and ``cluster_prob`` (the largest membership), ``shift``, then the corrected coordinates ``h1`` .. ``hD``."""
+        coords, prob = np.asarray(self.coords, np.float32), np.asarray(self.cluster_prob, np.float64)
+        out = {"index": list(self.index), "cell_type": self._name(self.label), "prob": np.asarray(self.max_prob),
+               "batch": [self.batch_names[s] for s in np.asarray(self.batch, np.int64)],
+               "cluster": np.asarray(self.cluster, np.int64),
+               "cluster_prob": prob.max(axis=1) if prob.shape[1] else np.ones(len(self.batch)), "shift": self.shift()}
+        out.update({f"h{j + 1}": coords[:, j] for j in range(coords.shape[1])})
+        return pd.DataFrame(out)
+
+    def summary(self) -> HarmonizedSummary:
+        """Cells, batches, rounds, the objective, the median shift and - where the graphs were built - the median batch and
+        predicted-type LISI before -> after, with a warning line when the type LISI rises; ``print`` it."""
+        own = np.asarray(self.batch, np.int64)
+        med = lambda v: None if np.isnan(v).all() else float(np.nanmedian(v))
+        mix = self.mixing() if self.graph is not None else None
+        get = lambda col: None if mix is None else med(mix[col].to_numpy())
+        objective = list(self.objective) or [float("nan")]
+        return HarmonizedSummary(
+            n_cells=len(own), n_batches=len(self.batch_names), space=self.space,
+            batch_sizes={str(name): int((own == s).sum()) for s, name in enumerate(self.batch_names)},
+            n_clusters=int(np.asarray(self.cluster_prob).shape[1]), n_iter=int(self.n_iter), converged=bool(self.converged),
+            objective_first=float(objective[0]), objective_last=float(objective[-1]),
+            median_shift=float(np.median(self.shift())) if len(own) else float("nan"),
+            median_norm=float(np.median(np.sqrt((np.asarray(self.embedding, np.float64) ** 2).sum(axis=1)))) if len(own) else float("nan"),
+            k=None if self.graph is None else int(self.graph.k),
+            batch_lisi_before=get("batch_lisi_before"), batch_lisi_after=get("batch_lisi_after"),
+            type_lisi_before=get("type_lisi_before"), type_lisi_after=get("type_lisi_after"))
